@@ -9,6 +9,10 @@ then noptepochs x nminibatches clipped-surrogate train steps (fwd + loss + backw
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus N ...        (starts its N ranks itself, as a child torch.distributed.run; one rank per GPU over RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds what the headline does not need:
+the per-kernel pass, the phase split and the roofline block, the CPU baselines and (cfg3) the configs[1] and host-Env legs.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) for output-for-output comparison of two builds.
 """
 import argparse
 import json
@@ -49,6 +53,7 @@ LR, CR, GAMMA, LAM = 3.93141e-4, 0.161023, 0.99, 0.95      # README.md:70-81, pp
 PEAK_F32_MFMA_TFLOPS = 157.3                                # MI355X_MICROARCH.md: v_mfma_f32_*_f32 dense peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0                              # MI355X_MICROARCH.md: bf16 MFMA dense peak (not the 2:1-sparsity figure)
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 60_000_000                                     # --dump-outputs: under 64 MB in all, .npy headers included
 
 
 def flops_per_row(O, A, hidden):
@@ -268,10 +273,32 @@ def cpu_baseline(cfg, name="cfg3", budget_s=20.0):
     return out
 
 
+def dump_outputs(g, losses, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the rollout that step collected (every field of
+    ppo_rollout_download, one row per time step x environment), the weights its update left (ppo_get_flat) and its mean losses --
+    as <out_dir>/<name>.npy in float32.  When everything would exceed DUMP_BYTES, the rollout keeps a fixed seeded sample of its
+    rows: the same rows in every run of the same configuration."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": g.get_flat(0), "losses": np.asarray(losses, np.float32)}
+    rows = g.T * g.E
+    rollout = {}
+    for f in g.FIELDS:
+        a = g.rollout_get(f)
+        rollout[f] = a.reshape((rows,) + a.shape[2:])
+    row_bytes = sum(a[0].nbytes for a in rollout.values())
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // row_bytes
+    if room < rows:
+        keep = np.sort(np.random.RandomState(0).choice(rows, room, replace=False))
+        rollout = {f: a[keep] for f, a in rollout.items()}
+    arrays.update(rollout)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def count_gpus_from_sysfs():
     """GPU nodes of /sys/class/kfd/kfd/topology (a node with simd_count > 0 is a GPU; CPUs have 0), cut by ROCR_VISIBLE_DEVICES /
     HIP_VISIBLE_DEVICES when they are plain index lists.  No topology directory = no amdgpu compute driver on this machine = 0 devices; None only when the
-    files exist and cannot be read"""
+    files exist, cannot be read and no such list bounds the count (a container may hide the nodes of devices it does not expose)"""
     import glob
     n = 0
     files = glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties")
@@ -284,11 +311,12 @@ def count_gpus_from_sysfs():
                 if k == "simd_count" and int(v) > 0:
                     n += 1
     except OSError:
-        return None
+        n = None
     for var in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES"):
         v = os.environ.get(var)
         if v is not None and all(x.strip().isdigit() for x in v.split(",") if x.strip()):
-            n = min(n, len([x for x in v.split(",") if x.strip()]))
+            listed = len([x for x in v.split(",") if x.strip()])
+            n = listed if n is None else min(n, listed)
     return n
 
 
@@ -338,8 +366,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel pass, phase split, roofline, CPU baselines, (cfg3) configs[1] and host-Env legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rollout, weights, mean losses) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the configs[1] side measurement")
     ap.add_argument("--host-env", action="store_true", help="also time the Env-on-host path (PCIe inclusive)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank runs the config's n_envs; strong: the config's n_envs are divided over the ranks "
@@ -349,6 +381,8 @@ def main():
                          "one-shot peer all-reduce over IPC-mapped buffers, or auto = when the peer probe passes on every rank, TIME both over "
                          "a few steps and keep the faster one for the timed region (both timings go into `collectives`)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))                     # BEFORE the package is imported or any GPU call is made
@@ -455,24 +489,28 @@ def main():
             g.close()
             sys.exit(3)
 
-    # per-kernel device time of the same workload, HIP events on the handle's stream, right after the timed region
-    g.prof_enable(True)
-    t_c0 = time.perf_counter()
-    g.collect_synthetic(1234, GAMMA, LAM, None, env0=env0, step0=(args.warmup + args.steps) * T, first=False)
-    t_collect = time.perf_counter() - t_c0
-    g.update(LR, CR, ep, nmb, None, seed=999, want_rows=False)
-    prof = g.prof_read()
-    g.prof_enable(False)
-    # the reference's own shape with minibatches of <= 64 rows: ONE launch per epoch runs all its train steps (narrow_epoch_kernel: forward, backward, weight
-    # gradients, assembly, clip + Adam of every minibatch) -- the "train_fwd_bwd" class is then that launch
-    epoch_fused = g.kernel_counts().get("narrow_epoch_kernel", 0) > 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(g, losses, args.dump_outputs)
 
-    # phase split of one un-profiled step
-    t_a = time.perf_counter()
-    g.collect_synthetic(1234, GAMMA, LAM, None, env0=env0, step0=(args.warmup + args.steps + 1) * T, first=False)
-    t_b = time.perf_counter()
-    g.update(LR, CR, ep, nmb, None, seed=998, want_rows=False)
-    t_c = time.perf_counter()
+    if args.full:
+        # per-kernel device time of the same workload, HIP events on the handle's stream, right after the timed region
+        g.prof_enable(True)
+        t_c0 = time.perf_counter()
+        g.collect_synthetic(1234, GAMMA, LAM, None, env0=env0, step0=(args.warmup + args.steps) * T, first=False)
+        t_collect = time.perf_counter() - t_c0
+        g.update(LR, CR, ep, nmb, None, seed=999, want_rows=False)
+        prof = g.prof_read()
+        g.prof_enable(False)
+        # the reference's own shape with minibatches of <= 64 rows: ONE launch per epoch runs all its train steps (narrow_epoch_kernel: forward, backward, weight
+        # gradients, assembly, clip + Adam of every minibatch) -- the "train_fwd_bwd" class is then that launch
+        epoch_fused = g.kernel_counts().get("narrow_epoch_kernel", 0) > 0
+
+        # phase split of one un-profiled step
+        t_a = time.perf_counter()
+        g.collect_synthetic(1234, GAMMA, LAM, None, env0=env0, step0=(args.warmup + args.steps + 1) * T, first=False)
+        t_b = time.perf_counter()
+        g.update(LR, CR, ep, nmb, None, seed=998, want_rows=False)
+        t_c = time.perf_counter()
 
     if world > 1:
         # orderly shutdown: every rank is past its last collective before any communicator is torn down
@@ -484,78 +522,6 @@ def main():
             return
     if rank != 0:
         return
-    f_fwd, f_dx, f_dw = flops_per_row(cfg["obs"], cfg["act"], cfg["hidden"])
-    kflops = {"train_fwd_bwd": (f_fwd + f_dx) * M, "weight_grad": f_dw * M, "policy_step": f_fwd * E}
-    if epoch_fused:
-        kflops["train_fwd_bwd"] = (f_fwd + f_dx + f_dw) * M * nmb
-    kern = {k: {"avg_us": 1e3 * ms / n, "launches": n} for k, (ms, n) in prof.items() if n}
-    dom = max((k for k in kern if k in kflops), key=lambda k: kern[k]["avg_us"] * kern[k]["launches"])
-    ach = kflops[dom] / (kern[dom]["avg_us"] * 1e-6) / 1e12
-    # PMC passes and the profiler's kernel trace cannot run inside the timed process: both come from the committed files that
-    # profiles/current.json names (written with the round's profiles), and the JSON line says so
-    traffic = traffic_source = rocprof_avg_us = rocprof_source = None
-    # kernel names of the dominant class, most specific first (the class "train_fwd_bwd" is train8_kernel on the 18-obs / [256,256] shape,
-    # train_fwd_bwd_kernel on other wide fp32 shapes, narrow_train_kernel for nets <= 64 wide, the tanh GEMM on the bf16 path)
-    # The timed class may be ONE kernel (fp32 paths) or a SEQUENCE of launches per train step (bf16 path: L tanh GEMMs, the head kernel, the loss
-    # kernel, L TanhGrad GEMMs).  `members` = (kernel-name pattern, launches of it per launch of the class); the profile numbers of a
-    # class are the sums over its members x their launches per step, so that traffic / rocprof_avg_us describe the same thing as
-    # flop_per_launch and avg_us.  (For a single-kernel class that is just that kernel's row.)
-    L = len(cfg["hidden"])
-    if bf16:
-        # (round 5: the hidden layers of a pass are ONE chained launch at this minibatch size; a profile taken with PPO_HIP_NO_BF16_CHAIN=1 holds the
-        # launch-per-layer names instead -- `alt_members` below)
-        alt_members = [("gemm_nt_bf16_kernel<4, 0>", L), ("bf16_heads_kernel", 1), ("bf16_loss_kernel", 1), ("gemm_nt_bf16_kernel<4, 1>", L)]
-        members = {"train_fwd_bwd": [("gemm_chain_bf16_kernel<0>", 1), ("bf16_heads_kernel", 1), ("bf16_loss_kernel", 1), ("gemm_chain_bf16_kernel<1>", 1)],
-                   "weight_grad": [("gemm_dw_bf16_kernel", 1)],
-                   "policy_step": [("bf16_stage_kernel", 1), ("gemm_nt_bf16_kernel<4, 0>", L), ("bf16_heads_kernel", 1), ("bf16_sample_kernel", 1)]}[dom]
-    else:
-        first = {"train_fwd_bwd": ["train8_kernel", "train_fwd_bwd_kernel", "narrow_epoch_kernel", "narrow_train_kernel"],
-                 "weight_grad": ["weight_grad_assemble_kernel", "weight_grad_kernel"],
-                 "policy_step": ["policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_step_kernel"]}[dom]
-        members = None                                       # resolved below: the first of these names the profile holds
-        alt_members = None
-    try:
-        idx = json.load(open(os.path.join(ROOT, "profiles", "current.json"))).get(args.config, {})
-        note = (" [profiled with %s]" % idx["env"]) if idx.get("env") else ""      # e.g. eager launches where the profiler cannot follow the update's graph
-        if idx.get("hbm_traffic"):
-            kk = json.load(open(os.path.join(ROOT, "profiles", idx["hbm_traffic"])))["kernels"]
-            if members and dom == "train_fwd_bwd" and alt_members and not any(members[0][0] in k for k in kk):
-                members = alt_members
-            mem = members or [(n, 1) for n in first if any(n in k for k in kk)][:1]
-            tot, ok = 0.0, bool(mem)
-            for pat, per in mem:
-                hit = [v for k, v in kk.items() if pat in k][:1]
-                if not hit or "FETCH_SIZE" not in hit[0] or "WRITE_SIZE" not in hit[0]:
-                    ok = False
-                    break
-                tot += per * (2.0 * hit[0]["FETCH_SIZE"] + hit[0]["WRITE_SIZE"]) * 1024.0
-            if ok:
-                traffic = tot
-                traffic_source = "profiles/%s (offline rocprofv3 --pmc passes of this command; FETCH_SIZE doubled per MI355X_MICROARCH.md; %s)%s" % (
-                    idx["hbm_traffic"], " + ".join("%d x %s" % (per, pat) for pat, per in mem), note)
-        if idx.get("kernel_stats"):
-            import csv
-            rows = list(csv.DictReader(open(os.path.join(ROOT, "profiles", idx["kernel_stats"]))))
-            if members and dom == "train_fwd_bwd" and alt_members and not any(members[0][0] in r["Name"] for r in rows):
-                members = alt_members
-            mem = members or [(n, 1) for n in first if any(n in r["Name"] for r in rows)][:1]
-            tot, ok = 0.0, bool(mem)
-            for pat, per in mem:
-                hit = [r for r in rows if pat in r["Name"]][:1]
-                if not hit:
-                    ok = False
-                    break
-                tot += per * float(hit[0]["AverageNs"]) / 1e3
-            if ok:
-                rocprof_avg_us = tot
-                rocprof_source = "profiles/%s (rocprofv3 --kernel-trace --stats of this command; %s)%s" % (
-                    idx["kernel_stats"], " + ".join("%d x %s" % (per, pat) for pat, per in mem), note)
-    except Exception as e:
-        traffic_source = "unavailable: %r" % (e,)
-    step_flops = (f_fwd + f_dx + f_dw) * M
-    step_us = sum(kern[k]["avg_us"] for k in ("train_fwd_bwd", "weight_grad", "grad_reduce", "adam") if k in kern)
-    if epoch_fused:
-        step_us = kern["train_fwd_bwd"]["avg_us"] / nmb
     out = {
         "metric": "PPO env-steps/s", "value": world * B * args.steps / dt, "unit": "env-steps/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
@@ -563,29 +529,104 @@ def main():
         "config": {"workload": "BASELINE configs[%d] (%s): %s" % (BASELINE_INDEX[args.config], args.config, cfg["desc"]), "n_envs_per_gpu": E, "n_steps": T,
                    "n_batch_per_gpu": B, "minibatch_rows_per_gpu": M, "parallelism": "dp%d" % world,
                    "env": "on-device seeded synthetic env (env_mock shape), rollout buffers resident in HBM"},
-        "update_samples_per_s": world * ep * B / (t_c - t_b),
-        "phase_ms": {"collect": 1e3 * (t_b - t_a), "update": 1e3 * (t_c - t_b)},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": ach, "peak": peak, "unit": "TFLOP/s",
-                     "frac": ach / peak, "traffic": traffic, "traffic_source": traffic_source,
-                     "rocprof_avg_us": rocprof_avg_us, "rocprof_source": rocprof_source,
-                     "flop_per_launch": kflops[dom], "avg_us": kern[dom]["avg_us"],
-                     "timing": "HIP events on the handle's stream around every launch of an eager pass right after the timed region: "
-                               "an UPPER bound on kernel time (launch gaps included); the rocprofv3 kernel-trace of the same command is in profiles/",
-                     # whole train step against the same peak, from the graph-replayed update phase (no launch gaps, device paced)
-                     "step_frac": step_flops / ((t_c - t_b) / (ep * nmb)) / 1e12 / peak,
-                     "train_step": {"flop": step_flops, "us_from_update_phase": 1e6 * (t_c - t_b) / (ep * nmb), "event_us_sum_upper_bound": step_us,
-                                    "achieved": step_flops / ((t_c - t_b) / (ep * nmb)) / 1e12,
-                                    **({"launches": "one narrow_epoch_kernel launch per epoch = %d train steps (the dominant class is that launch)" % nmb} if epoch_fused else {})}},
-        "kernels": kern,
         "losses": [float(x) for x in losses],
     }
     if collectives is not None:
         out["collectives"] = collectives
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        f_fwd, f_dx, f_dw = flops_per_row(cfg["obs"], cfg["act"], cfg["hidden"])
+        kflops = {"train_fwd_bwd": (f_fwd + f_dx) * M, "weight_grad": f_dw * M, "policy_step": f_fwd * E}
+        if epoch_fused:
+            kflops["train_fwd_bwd"] = (f_fwd + f_dx + f_dw) * M * nmb
+        kern = {k: {"avg_us": 1e3 * ms / n, "launches": n} for k, (ms, n) in prof.items() if n}
+        dom = max((k for k in kern if k in kflops), key=lambda k: kern[k]["avg_us"] * kern[k]["launches"])
+        ach = kflops[dom] / (kern[dom]["avg_us"] * 1e-6) / 1e12
+        # PMC passes and the profiler's kernel trace cannot run inside the timed process: both come from the committed files that
+        # profiles/current.json names (written with the round's profiles), and the JSON line says so
+        traffic = traffic_source = rocprof_avg_us = rocprof_source = None
+        # kernel names of the dominant class, most specific first (the class "train_fwd_bwd" is train8_kernel on the 18-obs / [256,256] shape,
+        # train_fwd_bwd_kernel on other wide fp32 shapes, narrow_train_kernel for nets <= 64 wide, the tanh GEMM on the bf16 path)
+        # The timed class may be ONE kernel (fp32 paths) or a SEQUENCE of launches per train step (bf16 path: L tanh GEMMs, the head kernel, the loss
+        # kernel, L TanhGrad GEMMs).  `members` = (kernel-name pattern, launches of it per launch of the class); the profile numbers of a
+        # class are the sums over its members x their launches per step, so that traffic / rocprof_avg_us describe the same thing as
+        # flop_per_launch and avg_us.  (For a single-kernel class that is just that kernel's row.)
+        L = len(cfg["hidden"])
+        if bf16:
+            # (round 5: the hidden layers of a pass are ONE chained launch at this minibatch size; a profile taken with PPO_HIP_NO_BF16_CHAIN=1 holds the
+            # launch-per-layer names instead -- `alt_members` below)
+            alt_members = [("gemm_nt_bf16_kernel<4, 0>", L), ("bf16_heads_kernel", 1), ("bf16_loss_kernel", 1), ("gemm_nt_bf16_kernel<4, 1>", L)]
+            members = {"train_fwd_bwd": [("gemm_chain_bf16_kernel<0>", 1), ("bf16_heads_kernel", 1), ("bf16_loss_kernel", 1), ("gemm_chain_bf16_kernel<1>", 1)],
+                       "weight_grad": [("gemm_dw_bf16_kernel", 1)],
+                       "policy_step": [("bf16_stage_kernel", 1), ("gemm_nt_bf16_kernel<4, 0>", L), ("bf16_heads_kernel", 1), ("bf16_sample_kernel", 1)]}[dom]
+        else:
+            first = {"train_fwd_bwd": ["train8_kernel", "train_fwd_bwd_kernel", "narrow_epoch_kernel", "narrow_train_kernel"],
+                     "weight_grad": ["weight_grad_assemble_kernel", "weight_grad_kernel"],
+                     "policy_step": ["policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_step_kernel"]}[dom]
+            members = None                                       # resolved below: the first of these names the profile holds
+            alt_members = None
+        try:
+            idx = json.load(open(os.path.join(ROOT, "profiles", "current.json"))).get(args.config, {})
+            note = (" [profiled with %s]" % idx["env"]) if idx.get("env") else ""      # e.g. eager launches where the profiler cannot follow the update's graph
+            if idx.get("hbm_traffic"):
+                kk = json.load(open(os.path.join(ROOT, "profiles", idx["hbm_traffic"])))["kernels"]
+                if members and dom == "train_fwd_bwd" and alt_members and not any(members[0][0] in k for k in kk):
+                    members = alt_members
+                mem = members or [(n, 1) for n in first if any(n in k for k in kk)][:1]
+                tot, ok = 0.0, bool(mem)
+                for pat, per in mem:
+                    hit = [v for k, v in kk.items() if pat in k][:1]
+                    if not hit or "FETCH_SIZE" not in hit[0] or "WRITE_SIZE" not in hit[0]:
+                        ok = False
+                        break
+                    tot += per * (2.0 * hit[0]["FETCH_SIZE"] + hit[0]["WRITE_SIZE"]) * 1024.0
+                if ok:
+                    traffic = tot
+                    traffic_source = "profiles/%s (offline rocprofv3 --pmc passes of this command; FETCH_SIZE doubled per MI355X_MICROARCH.md; %s)%s" % (
+                        idx["hbm_traffic"], " + ".join("%d x %s" % (per, pat) for pat, per in mem), note)
+            if idx.get("kernel_stats"):
+                import csv
+                rows = list(csv.DictReader(open(os.path.join(ROOT, "profiles", idx["kernel_stats"]))))
+                if members and dom == "train_fwd_bwd" and alt_members and not any(members[0][0] in r["Name"] for r in rows):
+                    members = alt_members
+                mem = members or [(n, 1) for n in first if any(n in r["Name"] for r in rows)][:1]
+                tot, ok = 0.0, bool(mem)
+                for pat, per in mem:
+                    hit = [r for r in rows if pat in r["Name"]][:1]
+                    if not hit:
+                        ok = False
+                        break
+                    tot += per * float(hit[0]["AverageNs"]) / 1e3
+                if ok:
+                    rocprof_avg_us = tot
+                    rocprof_source = "profiles/%s (rocprofv3 --kernel-trace --stats of this command; %s)%s" % (
+                        idx["kernel_stats"], " + ".join("%d x %s" % (per, pat) for pat, per in mem), note)
+        except Exception as e:
+            traffic_source = "unavailable: %r" % (e,)
+        step_flops = (f_fwd + f_dx + f_dw) * M
+        step_us = sum(kern[k]["avg_us"] for k in ("train_fwd_bwd", "weight_grad", "grad_reduce", "adam") if k in kern)
+        if epoch_fused:
+            step_us = kern["train_fwd_bwd"]["avg_us"] / nmb
+        out.update({
+            "update_samples_per_s": world * ep * B / (t_c - t_b),
+            "phase_ms": {"collect": 1e3 * (t_b - t_a), "update": 1e3 * (t_c - t_b)},
+            "roofline": {"bound": "mfma", "kernel": dom, "achieved": ach, "peak": peak, "unit": "TFLOP/s",
+                         "frac": ach / peak, "traffic": traffic, "traffic_source": traffic_source,
+                         "rocprof_avg_us": rocprof_avg_us, "rocprof_source": rocprof_source,
+                         "flop_per_launch": kflops[dom], "avg_us": kern[dom]["avg_us"],
+                         "timing": "HIP events on the handle's stream around every launch of an eager pass right after the timed region: "
+                                   "an UPPER bound on kernel time (launch gaps included); the rocprofv3 kernel-trace of the same command is in profiles/",
+                         # whole train step against the same peak, from the graph-replayed update phase (no launch gaps, device paced)
+                         "step_frac": step_flops / ((t_c - t_b) / (ep * nmb)) / 1e12 / peak,
+                         "train_step": {"flop": step_flops, "us_from_update_phase": 1e6 * (t_c - t_b) / (ep * nmb), "event_us_sum_upper_bound": step_us,
+                                        "achieved": step_flops / ((t_c - t_b) / (ep * nmb)) / 1e12,
+                                        **({"launches": "one narrow_epoch_kernel launch per epoch = %d train steps (the dominant class is that launch)" % nmb} if epoch_fused else {})}},
+            "kernels": kern,
+        })
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(cfg, args.config)
     # (skipped under rocprofv3: instantiating a second handle's hipGraph in one traced process crashes the profiler)
     profiled = any("ROCPROF" in k for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
-    if world == 1 and args.config == "cfg3" and not args.no_extra and not profiled:
+    if args.full and world == 1 and args.config == "cfg3" and not args.no_extra and not profiled:
         # BASELINE configs[1] (one environment, MLP [64,64], 2048 steps per update: launch-latency bound) measured in the
         # same run, so that both single-GPU configurations of the baseline are on record; `value` stays configs[2]
         g.close()
@@ -642,8 +683,8 @@ def main():
                 "note": "SeededEnvMock on the host; resident rollout kernel, actions / transitions through pinned memory"}
         except Exception as e:
             out["also"]["BASELINE configs[1] (cfg2), Env on the host"] = {"error": repr(e)}
-    # PCIe-inclusive leg: on by default in the plain single-GPU run (same guard as above), or forced with --host-env
-    if world == 1 and (args.host_env or (args.config == "cfg3" and not args.no_extra and not profiled)):
+    # PCIe-inclusive leg: on in the single-GPU --full run (same guard as above), or forced with --host-env
+    if world == 1 and (args.host_env or (args.full and args.config == "cfg3" and not args.no_extra and not profiled)):
         # PCIe-inclusive: the reference's own stack (N x mock Env -> VecEnv -> EnvNormalize -> PPO2::learn) on the host,
         # actions D2H / observations H2D every env step.  Reported beside `value`, never as `value`.
         try:

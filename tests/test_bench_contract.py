@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -41,6 +41,40 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert c["scalar_port"]["cores"] == 1 and 0 < c["scalar_port"]["value"] < c["value"]
 
 
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_what_its_last_step_computed(tmp_path):
+    """Without --full the run times --steps steps and prints the headline keys only; --dump-outputs writes the last timed step's rollout,
+    weights and mean losses as float32 .npy files, 64 MB at most in all.  The same arguments give the same outputs bit for bit (every step
+    is seeded), and one step fewer gives other outputs."""
+    def run(dump, steps):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--dump-outputs", dump],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+    dump = str(tmp_path / "out")
+    d = run(dump, 3)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["value"] > 1e5 and abs(d["value"] - 65536.0 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("roofline", "kernels", "phase_ms", "cpu_baseline", "also", "host_env"):
+        assert k not in d, k
+    import numpy as np
+    names = {"params", "losses", "obs", "actions", "values", "neglogp", "dones", "rewards", "returns"}
+    assert {f[:-4] for f in os.listdir(dump)} == names
+    arrays = {n: np.load(os.path.join(dump, n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in os.listdir(dump)) <= 64 * 2 ** 20
+    assert arrays["obs"].shape == (65536, 18) and arrays["actions"].shape == (65536, 18) and arrays["values"].shape == (65536,)
+    np.testing.assert_allclose(arrays["losses"], d["losses"], rtol=1e-6)
+    run(str(tmp_path / "again"), 3)
+    for n in names:
+        assert np.array_equal(np.load(os.path.join(str(tmp_path / "again"), n + ".npy")), arrays[n]), n
+    run(str(tmp_path / "fewer"), 2)
+    for n in ("params", "obs"):
+        assert not np.array_equal(np.load(os.path.join(str(tmp_path / "fewer"), n + ".npy")), arrays[n]), n
+
+
 def test_cpu_baseline_leg_runs_without_a_gpu_and_covers_a_whole_update():
     """CPU-runnable: the vectorised leg in its child process (BLAS threads fixed before NumPy loads) on a small configuration"""
     sys.path.insert(0, ROOT)
@@ -54,7 +88,7 @@ def test_cpu_baseline_leg_runs_without_a_gpu_and_covers_a_whole_update():
 def test_bench_roofline_of_a_multi_kernel_class_is_consistent_at_cfg5():
     """bf16 path: the timed class `train_fwd_bwd` is a SEQUENCE of launches per train step; the profile-derived numbers in the roofline
     block (rocprof_avg_us, traffic) must describe the same sequence as flop_per_launch / avg_us, not one of its kernels."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg5", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])

@@ -1,19 +1,11 @@
-"""Build-container check that reference environments drop in UNCHANGED (north star; SURVEY 8b 'env-side boundary'):
-the reference's own env/env_mock.hpp -- which pulls the reference's env/env.hpp, common/serializable.hpp and json.hpp --
-is compiled together with THIS repository's pooled VecEnv (host/env/vec_env.hpp) and Mat (host/mat.hpp through the
-Eigen/Dense shim; the image has no Eigen), and the reference's VecEnv test (test/vecenv_test.cpp: simulate_steps + its
-TEST_CASE for 1, 2 and 16 environments, under the reference's own Catch header) runs against it.  Nothing of the reference
-is copied into the repository: the test lines are spliced from the mounted tree at test time; skipped elsewhere."""
+"""Reference environments drop in UNCHANGED (north star; SURVEY 8b 'env-side boundary'): THIS repository's Mat (host/mat.hpp
+through the Eigen/Dense shim; the image has no Eigen) must evaluate the Eigen expressions the reference's headers use, written
+exactly as they write them."""
 import os
 import subprocess
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 HOST = os.path.join(ROOT, "ppo_cpp_amd", "host")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only mounted in the build container")
 
 
 def _compile_and_run(tmp_path, src, name, extra=()):
@@ -25,27 +17,6 @@ def _compile_and_run(tmp_path, src, name, extra=()):
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     return subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-
-
-def test_reference_env_mock_and_vecenv_test_run_against_the_kept_headers(tmp_path):
-    lines = open(os.path.join(REF, "test", "vecenv_test.cpp")).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith("typedef Eigen::Matrix"))
-    body = "\n".join(lines[start:])                          # typedef Mat, simulate_steps, TEST_CASE
-    src = """
-#define CATCH_CONFIG_MAIN
-#include <chrono>
-#include <iostream>
-#include <memory>
-#include <thread>
-#include "%s/test/catch.hpp"
-#include "%s/env/env_mock.hpp"        // the reference's file, unchanged (brings the reference's env.hpp / serializable.hpp / json.hpp)
-#include "env/vec_env.hpp"            // this repository's pooled VecEnv behind the same class interface
-%s
-""" % (REF, REF, body)
-    # (the reference's 2019 Catch header predates glibc's non-constant MINSIGSTKSZ: its signal handler is switched off)
-    r = _compile_and_run(tmp_path, src, "vecenv_ref_test", extra=("-DCATCH_CONFIG_NO_POSIX_SIGNALS",))
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "All tests passed" in r.stdout
 
 
 def test_mat_shim_covers_the_eigen_surface_the_reference_headers_use(tmp_path):

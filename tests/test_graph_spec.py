@@ -1,9 +1,8 @@
 """Graph-spec importer: the C++ reader of the reference's MetaGraphDef text file recovers the network
-shape, the graph-baked constants and the initial weights.  The 565 KB graph file itself is not copied into the repo; the
-test runs where the reference tree is mounted (this container) and is skipped elsewhere; its expected values are the
-committed fixtures (tests/golden/g45_init.npz) extracted independently by oracle/extract_fixtures.py."""
+shape, the graph-baked constants and the initial weights.  The 565 KB graph file itself is not copied into the repo: the
+importer reads a graph file in the same layout written from the committed fixtures (tests/golden/g45_init.npz, extracted
+independently by oracle/extract_fixtures.py)."""
 import ctypes as C
-import glob
 
 import numpy as np
 import pytest
@@ -12,17 +11,15 @@ from ppo_cpp_amd import hostapi
 from ppo_cpp_amd.capi import PPOConfig
 from tests import helpers as H
 
-GRAPHS = glob.glob("/root/reference/resources/ppo_cl/graphs/*.meta.txt")
 
-
-@pytest.mark.skipif(not GRAPHS, reason="reference graph file not present on this machine")
-def test_graph_spec_importer_matches_fixtures():
+def test_graph_spec_importer_matches_fixtures(tmp_path):
     lib = hostapi.load_host_library()
     cfg = PPOConfig(); pw = (C.c_float * 2)(); buf = np.zeros(4096, np.float32)
     consts, _ = H.g45_consts()
     init = H.g45_init()
+    path = str(tmp_path / "g45.meta.txt"); write_meta_graph(path, init, consts)
     for name, ref in init.items():
-        n = lib.ppo_host_graph_spec(GRAPHS[0].encode(), C.byref(cfg), pw, name.encode(), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size)
+        n = lib.ppo_host_graph_spec(path.encode(), C.byref(cfg), pw, name.encode(), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size)
         assert n == ref.size, name
         np.testing.assert_array_equal(buf[:n], ref.reshape(-1))
     assert (cfg.obs_dim, cfg.act_dim, cfg.n_hidden, cfg.hidden[0], cfg.hidden[1]) == (18, 18, 2, 4, 5)

@@ -1,13 +1,13 @@
 #!/bin/bash
 # A/B of prebuilt library variants at configs[4] (cfg5): tools/ab_variants_cfg5.sh <tag> <lib or "default"> ...   three alternating rounds
 tag=$1; shift
-mkdir -p gpurun_out/abv
+out=${OUT_DIR:-$(mktemp -d)}/abv; mkdir -p $out          # bench lines + logs of every run
 for r in 1 2 3; do
   for v in "$@"; do
     name=$(basename $v .so)
     if [ "$v" = "default" ]; then unset PPO_HIP_LIBRARY; else export PPO_HIP_LIBRARY=$PWD/$v; fi
-    python bench.py --config cfg5 --steps ${STEPS:-4} --warmup 2 --no-cpu-baseline --no-extra > gpurun_out/abv/${tag}_${name}_$r.json 2> gpurun_out/abv/${tag}_${name}_$r.err
-    python - "$name" $r gpurun_out/abv/${tag}_${name}_$r.json <<'PY'
+    python bench.py --config cfg5 --steps ${STEPS:-4} --warmup 2 --full --no-cpu-baseline --no-extra > $out/${tag}_${name}_$r.json 2> $out/${tag}_${name}_$r.err
+    python - "$name" $r $out/${tag}_${name}_$r.json <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[3]).read().strip().splitlines()[-1]); k=d["kernels"]

@@ -64,7 +64,7 @@ def main():
     steps, warm = ("2", "1") if a.quick else ("20", "5")
 
     def bench(n, config, collective, extra=()):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", steps, "--warmup", warm, "--config", config, "--no-cpu-baseline", "--no-extra"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", steps, "--warmup", warm, "--config", config]
         if n > 1:
             cmd += ["--collective", collective]
         st, out = child(cmd + list(extra), env)

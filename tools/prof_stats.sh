@@ -1,10 +1,12 @@
 #!/bin/bash
-# rocprofv3 kernel-trace stats of bench.py at one config: tools/prof_stats.sh <tag> <config> [ENV=1 ...]  -> gpurun_out/prof_<tag>_stats.csv
+# rocprofv3 kernel-trace stats of bench.py --full at one config: tools/prof_stats.sh <tag> <config> [ENV=1 ...]  -> $OUT_DIR/prof_<tag>_stats.csv
+# (OUT_DIR: a fresh temporary directory by default)
 tag=$1; cfg=$2; shift; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-out=$GRAFT_REPO_ROOT/gpurun_out
+out=${OUT_DIR:-$(mktemp -d)}; mkdir -p $out
 for kv in "$@"; do export "$kv"; done
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $GRAFT_REPO_ROOT/bench.py --config $cfg --steps 3 --warmup 2 --no-cpu-baseline --no-extra > $out/prof_${tag}_bench.json 2> $out/prof_${tag}.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $root/bench.py --config $cfg --steps 3 --warmup 2 --full --no-cpu-baseline --no-extra > $out/prof_${tag}_bench.json 2> $out/prof_${tag}.err
 f=$(find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1)
 cp "$f" $out/prof_${tag}_stats.csv
 # kernels launched at several sizes (the staging kernel per env step and per epoch): median duration per (kernel, grid size)
