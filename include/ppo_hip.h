@@ -65,7 +65,19 @@ typedef struct ppo_config {
 void ppo_config_default(ppo_config* cfg, int32_t obs_dim, int32_t act_dim, int32_t n_hidden, const int32_t* hidden);
 
 /* ---- lifecycle: SessionCreator::load_graph + Session::Run("init") (ppo2/session_creator.hpp:23-66) ---- */
+/* ppo_create = ppo_create_ex(cfg, PPO_ACT_GAUSSIAN, out): the diagonal-Gaussian head (pi/logstd, a = mu + sigma * eps). */
 int ppo_create(const ppo_config* cfg, ppo_handle** out);
+/* Action distribution of the policy head (the reference's Env::get_action_space, env/env.hpp:51-56):
+ *   PPO_ACT_GAUSSIAN     SPACE_CONTINOUS: cfg->act_dim = action dimensions
+ *   PPO_ACT_CATEGORICAL  SPACE_DISCRETE: cfg->act_dim = number of categories A >= 2 (stable-baselines' CategoricalProbabilityDistribution:
+ *                        logits l = h_L W_pi + b_pi, a = argmax_j (l_j - log(-log u_j)), neglogp = softmax cross-entropy against one_hot(a)).
+ *                        An action is ONE float per row holding the category index ("categorical handle" below).  PPO_F32 only: PPO_BF16
+ *                        is refused.  It runs the generic fp32 kernel families.  Errors: act_dim < 2, an unknown
+ *                        action_dist, PPO_BF16. */
+#define PPO_ACT_GAUSSIAN    0
+#define PPO_ACT_CATEGORICAL 1
+int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out);
+int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL */
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);
@@ -73,6 +85,7 @@ int ppo_abi_version(void);
 /* ---- variables: initializer consts G:2249-5297 / saver G:32312-33437 (ppo2/ppo2.hpp:107-223) ----------
  * Tensors are addressed by index in TF trainable-variable order
  *   pi_fc0/w, pi_fc0/b, vf_fc0/w, vf_fc0/b, pi_fc1/w, ... , vf/w, vf/b, pi/w, pi/b, pi/logstd   (4L+5 tensors)
+ * A categorical handle has no pi/logstd (4L+4 tensors; pi/w is [h_last, A], pi/b [A]); the flat vector and ppo_get_last_grad follow. 
  * `which`: 0 = weights, 1 = Adam m slot, 2 = Adam v slot. */
 int ppo_num_tensors(const ppo_handle* h);
 int ppo_tensor_info(const ppo_handle* h, int index, char name[32], int32_t* rows, int32_t* cols); /* cols 0 = 1-D */
@@ -95,7 +108,9 @@ int ppo_seed(ppo_handle* h, uint64_t seed);
 
 /* ---- act model ------------------------------------------------------------------------------------------
  * MlpPolicy::step (ppo2/policies.hpp:33-46): feeds input/Ob:0, fetches output/_action, _value_flat, _neglogp.
- * noise [n,A] = the N(0,1) draw of G:5894 made explicit (parity mode); NULL = on-device counter RNG. */
+ * noise [n,A] = the N(0,1) draw of G:5894 made explicit (parity mode); NULL = on-device counter RNG.
+ * Categorical handle: action [n] (category indices); noise [n,A] = the uniforms u in [0,1) of the Gumbel-argmax draw, NULL = an on-device
+ * counter draw in (0,1) keyed like the Gaussian's (seed, global row, call counter, category).  ppo_act_deterministic writes argmax_j l_j [n]. */
 int ppo_step(ppo_handle* h, const float* obs, int32_t n, const float* noise, float* action, float* value,
              float* neglogp);
 /* MlpPolicy::value (ppo2/policies.hpp:64-77) */
@@ -110,6 +125,8 @@ int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* act
 int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, const float* actions,
                    const float* advs, const float* returns, const float* old_neglogp, const float* old_values,
                    int32_t n, float losses[5]);
+/* Categorical handle: actions [n], every value an integer in [0, A) (checked on the host before the upload: an error otherwise); the loss
+ * is the same surrogate with the softmax cross-entropy as neglogp and the categorical entropy. */
 /* gradient of the last train step (of ppo_train_step, or the last one of ppo_update) BEFORE clipping (debug/parity), dense flat order.
  * PPO_BF16 handles on one GPU do not keep it: it is rebuilt here from the step's partial sums (same bits), which stay valid until the next train step. */
 int ppo_get_last_grad(ppo_handle* h, float* dst, int64_t count, float* global_norm);
@@ -158,10 +175,11 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam);
 /* device-env path: the whole T-step collect against the on-device seeded synthetic env (obs ~ U(-1,1)^O,
  * reward ~ U(-1,1), done ~ Bernoulli(1/300), keyed by (seed, global env id, step counter)); env ids start at
  * env0 (rank sharding).  first != 0 performs the reset (step counter step0), otherwise continues from the carried
- * obs/dones.  noise [T,E,A] or NULL.  Ends with bootstrap + GAE. */
+ * obs/dones.  noise [T,E,A] or NULL.  Ends with bootstrap + GAE.
+ * Categorical handle: noise [T,E,A] (ppo_collect_synthetic) / [E,A] (ppo_rollout_act) are uniforms, actions_out of ppo_rollout_act is [E]. */
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first,
                           const float* noise, float gamma, float lam);
-/* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]) */
+/* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]); a categorical handle's field 1 is [T,E] */
 int ppo_rollout_download(ppo_handle* h, int field, float* dst, int64_t count);
 int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count);
 

@@ -54,13 +54,20 @@ def _f32(a, shape=None):
     return a
 
 
+ACTION_DISTS = {"gaussian": 0, "categorical": 1}        # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL
+
+
 class PPOHip:
     """One handle = one GPU + stream; mirrors the TF session state of the reference (weights, Adam slots, beta
-    powers) plus the device-resident rollout and normaliser."""
+    powers) plus the device-resident rollout and normaliser.
+
+    action_dist="categorical": act_dim is the number of categories; actions are (n,) float category indices
+    (step / act_deterministic / rollout_act return them, train_step takes them, rollout_get("actions") is [T, E]);
+    explicit noise keeps the Gaussian's shape and holds the uniforms of the Gumbel-argmax draw."""
 
     FIELDS = {"obs": 0, "actions": 1, "values": 2, "neglogp": 3, "dones": 4, "rewards": 5, "returns": 6}
 
-    def __init__(self, obs_dim, act_dim, hidden, device=-1, **overrides):
+    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", **overrides):
         self.lib = load_library()
         cfg = PPOConfig()
         hid = (C.c_int32 * len(hidden))(*hidden)
@@ -70,8 +77,12 @@ class PPOHip:
             setattr(cfg, k, v)
         self.cfg = cfg
         self.O, self.A, self.hidden = obs_dim, act_dim, list(hidden)
+        if action_dist not in ACTION_DISTS:
+            raise ValueError("action_dist must be one of %s, not %r" % (sorted(ACTION_DISTS), action_dist))
+        self.action_dist = action_dist
+        self._act_shape = (act_dim,) if action_dist == "gaussian" else ()      # per row
         h = C.c_void_p()
-        if self.lib.ppo_create(C.byref(cfg), C.byref(h)) != 0:
+        if self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist], C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)
@@ -140,7 +151,7 @@ class PPOHip:
     # ---- act model --------------------------------------------------------------------------------
     def step(self, obs, noise=None):
         obs = _f32(obs); n = obs.shape[0]
-        a = np.empty((n, self.A), np.float32); v = np.empty(n, np.float32); nlp = np.empty(n, np.float32)
+        a = np.empty((n,) + self._act_shape, np.float32); v = np.empty(n, np.float32); nlp = np.empty(n, np.float32)
         nz = _f32(noise, (n, self.A)) if noise is not None else None
         self._ck(self.lib.ppo_step(self.h, _fp(obs), n, _fp(nz) if nz is not None else None, _fp(a), _fp(v), _fp(nlp)))
         return a, v, nlp
@@ -153,7 +164,7 @@ class PPOHip:
 
     def act_deterministic(self, obs):
         obs = _f32(obs); n = obs.shape[0]
-        a = np.empty((n, self.A), np.float32)
+        a = np.empty((n,) + self._act_shape, np.float32)
         self._ck(self.lib.ppo_act_deterministic(self.h, _fp(obs), n, _fp(a)))
         return a
 
@@ -161,6 +172,8 @@ class PPOHip:
     def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v):
         arrs = [_f32(x) for x in (obs, actions, advs, returns, old_nlp, old_v)]
         n = arrs[0].shape[0]
+        if self.action_dist == "categorical":
+            arrs[1] = _f32(arrs[1], (n,))
         losses = np.empty(5, np.float32)
         self._ck(self.lib.ppo_train_step(self.h, C.c_float(lr), C.c_float(cliprange), *[_fp(x) for x in arrs], n, _fp(losses)))
         return losses
@@ -223,7 +236,7 @@ class PPOHip:
         self._ck(self.lib.ppo_rollout_reset(self.h, _fp(x)))
 
     def rollout_act(self, t, noise=None):
-        out = np.empty((self.E, self.A), np.float32)
+        out = np.empty((self.E,) + self._act_shape, np.float32)
         nz = _f32(noise, (self.E, self.A)) if noise is not None else None
         self._ck(self.lib.ppo_rollout_act(self.h, t, _fp(nz) if nz is not None else None, _fp(out)))
         return out
@@ -241,7 +254,7 @@ class PPOHip:
                                                 _fp(nz) if nz is not None else None, C.c_float(gamma), C.c_float(lam)))
 
     def rollout_get(self, field):
-        shape = {"obs": (self.T, self.E, self.O), "actions": (self.T, self.E, self.A)}.get(field, (self.T, self.E))
+        shape = {"obs": (self.T, self.E, self.O), "actions": (self.T, self.E) + self._act_shape}.get(field, (self.T, self.E))
         out = np.empty(shape, np.float32)
         self._ck(self.lib.ppo_rollout_download(self.h, self.FIELDS[field], _fp(out), C.c_int64(out.size)))
         return out

@@ -50,11 +50,13 @@ const char* kProfNames[PK_COUNT] = {"policy_step", "train_fwd_bwd", "weight_grad
 
 // which kernel VARIANT a call took (ppo_kernel_counts): the fast paths are chosen by shape, and a test must be able to say which one ran
 enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN, KV_NARROW_STEP_STATIC, KV_NARROW_STEP,
-                     KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH, KV_COUNT };
+                     KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH,
+                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
-                                       "bf16_train_sequence", "bf16_step_sequence", "bf16_reduce_adam_kernel", "narrow_epoch_kernel"};
+                                       "bf16_train_sequence", "bf16_step_sequence", "bf16_reduce_adam_kernel", "narrow_epoch_kernel",
+                                       "policy_step_kernel<cat>", "train_fwd_bwd_kernel<cat>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -78,6 +80,8 @@ struct ppo_handle {
     int CT = 1;                       // column tiles per wave in the dense layers (4 for wide nets)
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
+    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
+    int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian) or 1 (categorical: the category index)
     NetDev net{};
     std::vector<Tensor> tensors;
     int P_dense = 0, P_pad = 0, n_blocks = 0, PT = 0;
@@ -392,7 +396,11 @@ int build_layout(ppo_handle* h) {
     n.bv_off = op;  add_tensor(h, "vf/b", 1, 0, 1, bf ? n.Ap : 1, od, op);
     add_tensor(h, "pi/w", HL, n.A, HpL, n.Ap, od, op, !bf); n.wmu_off = h->tensors.back().off_pad;
     n.bmu_off = op; add_tensor(h, "pi/b", n.A, 0, 1, n.Ap, od, op);
-    n.ls_off = op;  add_tensor(h, "pi/logstd", 1, n.A, 1, n.Ap, od, op);
+    // categorical: the logstd slot stays in the padded vector (the weight-gradient, reduce and Adam kernels keep their layout) but is no tensor:
+    // no gradient source, so its gradient is 0 and Adam never moves it; it is not in the tensor list, the flat vector or a checkpoint
+    n.ls_off = op;
+    if (h->dist == PPO_ACT_CATEGORICAL) op += ru(n.Ap, 256);
+    else add_tensor(h, "pi/logstd", 1, n.A, 1, n.Ap, od, op);
     h->P_dense = od; h->P_pad = op; h->n_blocks = op / 256;
     // transposed copies streamed by the backward pass
     int ot = 0;
@@ -493,7 +501,7 @@ int build_layout(ppo_handle* h) {
 void build_narrow_layout(ppo_handle* h) {
     const NetDev& n = h->net;
     h->narrow = false;
-    if (h->bf.on || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
+    if (h->bf.on || h->dist != PPO_ACT_GAUSSIAN || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
     for (int l = 0; l < n.L; ++l) if (n.Hp[l] > 64) return;
     const char* off = getenv("PPO_HIP_NO_NARROW");
     if (off && off[0] == '1') return;
@@ -661,7 +669,7 @@ int ensure_staging(ppo_handle* h, int rows) {
     HIP_OK(h, hipStreamSynchronize(h->stream));
     const NetDev& n = h->net;
     if (dev_alloc(h, &h->st_obs, (size_t)rows * n.O)) return -1;
-    if (dev_alloc(h, &h->st_act, (size_t)rows * n.A)) return -1;
+    if (dev_alloc(h, &h->st_act, (size_t)rows * h->Aw)) return -1;
     if (dev_alloc(h, &h->st_noise, (size_t)rows * n.A)) return -1;
     for (int i = 0; i < 6; ++i) if (dev_alloc(h, &h->st_vec[i], (size_t)rows)) return -1;
     h->st_rows = rows;
@@ -1017,7 +1025,7 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 // X(KP0, HP, AP, L) is the launch statement
 #define NW_DISPATCH(h, X) do { if (!(h)->nw_static) { X(0, 0, 0, 0); } else if ((h)->net.Kp0 == 32) { X(32, 64, 32, 2); } else { X(64, 64, 32, 2); } } while (0)
 
-template <int CT, int KS, int CTH, bool WIDE>
+template <int CT, int KS, int CTH, bool WIDE, bool CAT = false>
 void launch_step_t(ppo_handle* h, const StepArgs& a0) {
     StepArgs a = a0;
     dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
@@ -1025,11 +1033,20 @@ void launch_step_t(ppo_handle* h, const StepArgs& a0) {
     if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
     a.stamps = grid.x <= 256 ? g_stamps + 4096 * 44 : nullptr;
 #endif
-    hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE>), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
+    hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT>), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
 }
 int launch_step(ppo_handle* h, const StepArgs& a) {
     if (h->bf.on) { ++h->kv[KV_BF16_STEP]; return launch_step_bf16(h, a); }
     ProfScope ps(h, PK_STEP);
+    if (h->dist == PPO_ACT_CATEGORICAL) {
+        ++h->kv[KV_POLICY_STEP_CAT];
+        if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true, true>(h, a); else launch_step_t<1, 1, 0, true, true>(h, a); }
+        else if (h->CT == 4 && h->CTH == 2) launch_step_t<4, 2, 2, false, true>(h, a);
+        else if (h->CT == 4) launch_step_t<4, 2, 0, false, true>(h, a);
+        else launch_step_t<1, 1, 0, false, true>(h, a);
+        HIP_OK(h, hipGetLastError());
+        return 0;
+    }
     ++h->kv[h->narrow ? (h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP) : KV_POLICY_STEP];
     if (h->narrow) {
         dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
@@ -1382,8 +1399,18 @@ int enqueue_train(ppo_handle* h, TrainArgs ta, float* loss_row, bool defer = fal
         dim3 grid(n_rb, 2);
         const size_t lds_bytes = (size_t)n.lds_total * sizeof(float);
         const dim3 blk(BLOCK_THREADS);
-        ++h->kv[(h->t8 && !n.wide) ? KV_TRAIN8 : KV_TRAIN_FB];
-        if (n.wide) {
+        ++h->kv[h->dist == PPO_ACT_CATEGORICAL ? KV_TRAIN_FB_CAT : (h->t8 && !n.wide) ? KV_TRAIN8 : KV_TRAIN_FB];
+        if (h->dist == PPO_ACT_CATEGORICAL) {                    // (no train8 / dw2 for this head: ppo_create_ex)
+            if (n.wide) {
+                if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
+                else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            }
+            else if (h->CT == 4 && h->CTH == 2 && h->early) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            else if (h->CT == 4 && h->CTH == 2) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            else if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, false, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, false, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
+        }
+        else if (n.wide) {
             if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true>), grid, blk, lds_bytes, h->stream, n, ta);
             else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true>), grid, blk, lds_bytes, h->stream, n, ta);
         }
@@ -1536,6 +1563,7 @@ static int host_quiesce(ppo_handle* h);
 extern "C" {
 
 int ppo_abi_version(void) { return PPO_ABI_VERSION; }
+int ppo_action_dist(const ppo_handle* h) { return h ? h->dist : -1; }
 
 void ppo_config_default(ppo_config* cfg, int32_t obs_dim, int32_t act_dim, int32_t n_hidden, const int32_t* hidden) {
     memset(cfg, 0, sizeof *cfg);
@@ -1550,11 +1578,19 @@ void ppo_config_default(ppo_config* cfg, int32_t obs_dim, int32_t act_dim, int32
 
 const char* ppo_last_error(const ppo_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int ppo_create(const ppo_config* cfg, ppo_handle** out) {
+int ppo_create(const ppo_config* cfg, ppo_handle** out) { return ppo_create_ex(cfg, PPO_ACT_GAUSSIAN, out); }
+
+int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) {
     if (!cfg || !out) return fail(nullptr, "ppo_create: null argument");
     *out = nullptr;
     if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
     if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
+    if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL)
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL)", (int)action_dist);
+    if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
+        return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
+    if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported (the categorical head runs on the PPO_F32 path only)");
     for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -1562,6 +1598,8 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out) {
         return fail(nullptr, "ppo_create: no HIP device available (%s); libppo_hip has no CPU fallback", hipGetErrorString(e));
     ppo_handle* h = new ppo_handle();
     h->cfg = *cfg;
+    h->dist = action_dist;
+    h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : cfg->act_dim;
     int dev = cfg->device;
     if (dev < 0) { const char* lr = getenv("LOCAL_RANK"); dev = lr ? atoi(lr) % ndev : 0; }
     h->device = dev;
@@ -1589,6 +1627,14 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out) {
     set_lds((const void*)policy_step_kernel<1, 1, 0, false>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false>);
     set_lds((const void*)policy_step_kernel<4, 2, 0, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true>);
     set_lds((const void*)policy_step_kernel<1, 1, 0, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true>);
+    if (h->dist == PPO_ACT_CATEGORICAL) {
+        set_lds((const void*)policy_step_kernel<4, 2, 2, false, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, false, true>);
+        set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, true, true>);
+        set_lds((const void*)policy_step_kernel<4, 2, 0, false, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, false, false, true>);
+        set_lds((const void*)policy_step_kernel<1, 1, 0, false, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false, false, true>);
+        set_lds((const void*)policy_step_kernel<4, 2, 0, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true, false, true>);
+        set_lds((const void*)policy_step_kernel<1, 1, 0, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true, false, true>);
+    }
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
     if (!attr_ok) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); return bail(0); }
@@ -1600,10 +1646,10 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out) {
     build_narrow_layout(h);
     if (upload_grad_src(h)) return bail(0);
     { const char* e = getenv("PPO_HIP_NO_DW2"); const NetDev& nn = h->net;
-      h->dw2 = !(e && e[0] == '1') && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
+      h->dw2 = !(e && e[0] == '1') && h->dist == PPO_ACT_GAUSSIAN && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
     { const char* e = getenv("PPO_HIP_NO_T8"); const NetDev& nn = h->net;
       // any observation / action width up to 64 (tiles of 32 or 64 columns) in front of hidden [256,256]
-      h->t8 = !(e && e[0] == '1') && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64;
+      h->t8 = !(e && e[0] == '1') && h->dist == PPO_ACT_GAUSSIAN && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64;
       if ((h->t8 || h->dw2) && !(set_lds_pair<32, 32>() && set_lds_pair<64, 32>() && set_lds_pair<32, 64>() && set_lds_pair<64, 64>())) {
           fail(h, "hipFuncSetAttribute failed for train8_kernel / weight_grad_assemble_kernel"); return bail(0); } }
     if (h->dw2) {
@@ -1865,7 +1911,7 @@ static int step_common(ppo_handle* h, const float* obs, int n, const float* nois
     // rollout must not shift the rollout's noise)
     a.seed = h->rng_seed; a.rng_step = (sample && action && !noise) ? h->rng_calls++ : h->rng_calls; a.row_base = (uint32_t)h->rank * (uint32_t)(h->nz_envs > 0 ? h->nz_envs : n);
     if (launch_step(h, a)) return -1;
-    if (action || det_action) HIP_OK(h, hipMemcpyAsync(action ? action : det_action, h->st_act, (size_t)n * net.A * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (action || det_action) HIP_OK(h, hipMemcpyAsync(action ? action : det_action, h->st_act, (size_t)n * h->Aw * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (value) HIP_OK(h, hipMemcpyAsync(value, h->st_vec[0], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (neglogp) HIP_OK(h, hipMemcpyAsync(neglogp, h->st_vec[1], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (bf16_chain_err_async(h)) return -1;
@@ -1893,12 +1939,18 @@ int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, c
                    const float* returns, const float* old_neglogp, const float* old_values, int32_t n, float losses[5]) {
     ENTER_Q(h);
     if (n < 2) return fail(h, "ppo_train_step: n=%d (the reference asserts more than one row, ppo2.hpp:402)", n);
+    if (h->dist == PPO_ACT_CATEGORICAL)
+        for (int32_t i = 0; i < n; ++i) {
+            const float x = actions[i];
+            if (!(x >= 0.f && x < (float)h->net.A && x == floorf(x)))
+                return fail(h, "ppo_train_step: actions[%d] = %g is not a category index in [0, %d)", (int)i, (double)x, h->net.A);
+        }
     h->bf.epoch_staged = false;
     if (ensure_staging(h, n) || ensure_train_ws(h, n)) return -1;
     const NetDev& net = h->net;
     const size_t fb = sizeof(float);
     HIP_OK(h, hipMemcpyAsync(h->st_obs, obs, (size_t)n * net.O * fb, hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipMemcpyAsync(h->st_act, actions, (size_t)n * net.A * fb, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipMemcpyAsync(h->st_act, actions, (size_t)n * h->Aw * fb, hipMemcpyHostToDevice, h->stream));
     const float* vecs[4] = {advs, returns, old_neglogp, old_values};
     for (int i = 0; i < 4; ++i) HIP_OK(h, hipMemcpyAsync(h->st_vec[2 + i], vecs[i], (size_t)n * fb, hipMemcpyHostToDevice, h->stream));
     if (set_hyper(h, lr, cliprange)) return -1;
@@ -1985,7 +2037,7 @@ int ppo_norm_init(ppo_handle* h, int32_t n_envs, float gamma, float clip_obs, fl
     if (h->pin_in) { (void)hipHostFree(h->pin_in); h->pin_in = nullptr; }
     if (h->pin_out) { (void)hipHostFree(h->pin_out); h->pin_out = nullptr; }
     HIP_OK(h, hipHostMalloc((void**)&h->pin_in, in_n * sizeof(float), hipHostMallocDefault));
-    HIP_OK(h, hipHostMalloc((void**)&h->pin_out, (size_t)n_envs * h->net.A * sizeof(float), hipHostMallocDefault));
+    HIP_OK(h, hipHostMalloc((void**)&h->pin_out, (size_t)n_envs * h->Aw * sizeof(float), hipHostMallocDefault));
     if (!h->pin_flag) { HIP_OK(h, hipHostMalloc((void**)&h->pin_flag, 1024, hipHostMallocDefault)); memset(h->pin_flag, 0, 1024); h->act_seq = 0; }
     if (h->pin_wgflag) { (void)hipHostFree(h->pin_wgflag); h->pin_wgflag = nullptr; }
     h->pin_wgflag_n = (n_envs + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
@@ -2000,7 +2052,7 @@ int ppo_norm_init(ppo_handle* h, int32_t n_envs, float gamma, float clip_obs, fl
         HIP_OK(h, hipHostGetDevicePointer(&d, h->pin_flag, 0)); h->pin_flag_dev = (unsigned*)d;
     }
     h->host_pending = false;
-    h->pin_in_n = in_n; h->pin_out_n = (size_t)n_envs * h->net.A;
+    h->pin_in_n = in_n; h->pin_out_n = (size_t)n_envs * h->Aw;
     {
         if (h->vram_in) { (void)hipFree(h->vram_in); h->vram_in = nullptr; h->vram_h2d = nullptr; }
         int large_bar = 0;
@@ -2179,7 +2231,7 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
     drop_graph(h);
     const NetDev& n = h->net;
     const size_t B = (size_t)E * T;
-    if (dev_alloc(h, &h->ro_obs, B * n.O) || dev_alloc(h, &h->ro_act, B * n.A) || dev_alloc(h, &h->ro_val, B) || dev_alloc(h, &h->ro_nlp, B) ||
+    if (dev_alloc(h, &h->ro_obs, B * n.O) || dev_alloc(h, &h->ro_act, B * h->Aw) || dev_alloc(h, &h->ro_val, B) || dev_alloc(h, &h->ro_nlp, B) ||
         dev_alloc(h, &h->ro_done, B) || dev_alloc(h, &h->ro_rew, B) || dev_alloc(h, &h->ro_ret, B) ||
         dev_alloc(h, &h->last_val, E) || dev_alloc(h, &h->ro_noise, B * n.A))
         return -1;
@@ -2200,7 +2252,7 @@ static int enqueue_rollout_act(ppo_handle* h, int t, const float* noise_dev, uin
     const size_t E = h->E;
     if (h->done_staged != t) HIP_OK(h, hipMemcpyAsync(h->ro_done + t * E, h->cur_done, E * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     StepArgs a{};
-    a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.noise = noise_dev; a.action = h->ro_act + t * E * n.A; a.det_action = nullptr;
+    a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.noise = noise_dev; a.action = h->ro_act + t * E * h->Aw; a.det_action = nullptr;
     a.value = h->ro_val + t * E; a.neglogp = h->ro_nlp + t * E; a.obs_out = h->ro_obs + t * E * n.O; a.nz = obs_norm(h); a.n = (int)E;
     a.seed = seed; a.rng_step = rng_step; a.row_base = row_base;
     if (direct) { a.host_action = h->pin_out_dev; a.host_flags = h->pin_wgflag_dev; a.host_seq = ++h->wg_seq; }
@@ -2378,9 +2430,9 @@ int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions
     if (!h->E || t < 0 || t >= h->T) return fail(h, "ppo_rollout_act: bad step %d", t);
     ENTER(h);
     const NetDev& n = h->net;
-    const size_t cnt = (size_t)h->E * n.A;
+    const size_t cnt = (size_t)h->E * h->Aw;                 // actions out; the noise is [E, A]
     float* nd = nullptr;
-    if (noise) { nd = h->ro_noise; HIP_OK(h, hipMemcpyAsync(nd, noise, cnt * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
+    if (noise) { nd = h->ro_noise; HIP_OK(h, hipMemcpyAsync(nd, noise, (size_t)h->E * n.A * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
     if (host_resident(h) && !noise) {
         // the kernel stays resident over the rollout: actions and transitions travel through the pinned blocks, sequence words
         // order them; (re)launched here when it is not running (first step, or it parked itself after a long host pause)
@@ -2452,7 +2504,7 @@ int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions
         // kernel, so once its last block has published, the pinned input block is free again -- without a stream synchronisation.
         const unsigned want = h->wg_seq;
         const int G = (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-        const size_t blk = (size_t)ROWS_PER_BLOCK * n.A;
+        const size_t blk = (size_t)ROWS_PER_BLOCK * h->Aw;
         unsigned long spins = 0;
         for (int b = 0; b < G; ) {
             if (__atomic_load_n(h->pin_wgflag + b, __ATOMIC_ACQUIRE) == want) {
@@ -2680,7 +2732,7 @@ static float* rollout_field(ppo_handle* h, int field, size_t* count) {
     const size_t B = (size_t)h->E * h->T;
     switch (field) {
         case 0: *count = B * h->net.O; return h->ro_obs;
-        case 1: *count = B * h->net.A; return h->ro_act;
+        case 1: *count = B * h->Aw; return h->ro_act;
         case 2: *count = B; return h->ro_val;
         case 3: *count = B; return h->ro_nlp;
         case 4: *count = B; return h->ro_done;
@@ -2728,7 +2780,7 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
         {"dy_vf_1", ws && n.L > 1 ? h->dyg[1][1] : nullptr, R * n.Hp[n.L > 1 ? 1 : 0]},
         {"slots_pi", ws ? h->slots[0] : nullptr, (R / 16) * n.slot_w}, {"slots_vf", ws ? h->slots[1] : nullptr, (R / 16) * n.slot_w},
         {"slabs", h->narrow ? nullptr : h->slabs, (size_t)h->max_split * P},
-        {"mb_obs", h->mb_obs, U * n.O}, {"mb_act", h->mb_act, U * n.A}, {"mb_adv", h->mb_adv, U}, {"mb_ret", h->mb_ret, U}, {"mb_val", h->mb_val, U}, {"mb_nlp", h->mb_nlp, U},
+        {"mb_obs", h->mb_obs, U * n.O}, {"mb_act", h->mb_act, U * h->Aw}, {"mb_adv", h->mb_adv, U}, {"mb_ret", h->mb_ret, U}, {"mb_val", h->mb_val, U}, {"mb_nlp", h->mb_nlp, U},
         {"gidx", h->d_gidx, U}, {"advstats", h->d_advstats, (size_t)2 * h->upd_cap_steps}, {"keys", h->d_keys, (size_t)2 * h->upd_cap_steps}, {"loss_rows", h->d_loss_rows, (size_t)5 * h->upd_cap_steps},
         {"nw_img", h->nw_img, h->narrow ? (size_t)2 * h->nw.w_total : 0}, {"nw_partials", h->nw_partials, (size_t)4 * h->nw_groups_cap * h->nw_stride},
         {"nw_theta1", h->nw_theta1, P}, {"nw_m1", h->nw_m1, P}, {"nw_v1", h->nw_v1, P}, {"nw_epoch_words", h->nw_epoch_words, NW_EPOCH_WORDS},
@@ -2770,7 +2822,7 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
                 ea.phase = 0;
                 if (!h->bf.on && M <= EPG_MAX_M) {
                     // index map, advantage statistics AND the gather of the epoch in one launch (fp32 paths; the bf16 path stages its epoch separately)
-                    GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->net.A, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
+                    GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->Aw, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
                                   h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp};
 #ifdef PPO_STAMPS
                     if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
@@ -2796,10 +2848,10 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
         }
         if (!merged) {
             ProfScope ps(h, PK_EPOCH);
-            GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->net.A, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
+            GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->Aw, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
                           h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp};
             if (h->global_shuffle && h->comm && h->world > 1) { ga.obs = h->gs_obs; ga.act = h->gs_act; ga.ret = h->gs_ret; ga.val = h->gs_val; ga.nlp = h->gs_nlp; }
-            const bool wide4 = h->net.O % 4 == 0 && h->net.A % 4 == 0;
+            const bool wide4 = h->net.O % 4 == 0 && h->Aw % 4 == 0;
             // bf16 path: the epoch's observations become bf16 once; a minibatch is then a row slice.  With 16-byte rows the gather writes them itself
             const bool fuse_stage = wide4 && h->bf.on && M % GB_PAD == 0 && h->bf.xe_rows >= B && h->net.Kp0 % 4 == 0 && !(h->global_shuffle && h->comm && h->world > 1);
             if (wide4) {
@@ -2853,7 +2905,7 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
         for (int k = 0; k < nmb; ++k) {
             TrainArgs ta{};
             const size_t r0 = (size_t)k * M;
-            ta.obs = h->mb_obs + r0 * h->net.O; ta.actions = h->mb_act + r0 * h->net.A; ta.returns = h->mb_ret + r0; ta.old_values = h->mb_val + r0;
+            ta.obs = h->mb_obs + r0 * h->net.O; ta.actions = h->mb_act + r0 * h->Aw; ta.returns = h->mb_ret + r0; ta.old_values = h->mb_val + r0;
             ta.old_neglogp = h->mb_nlp + r0; ta.advs = h->mb_adv + r0; ta.adv_stats = nullptr; ta.n = M;
             ta.inv_n = 1.0f / (float)((int64_t)M * h->world);
             if (enqueue_train(h, ta, h->d_loss_rows + (size_t)(ep * nmb + k) * 5, /*defer*/ true)) return -1;
@@ -2879,7 +2931,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
     if (gs && Bp > h->gs_rows) {
         HIP_OK(h, hipStreamSynchronize(h->stream));
         drop_graph(h);
-        if (dev_alloc(h, &h->gs_obs, (size_t)Bp * h->net.O) || dev_alloc(h, &h->gs_act, (size_t)Bp * h->net.A) || dev_alloc(h, &h->gs_ret, Bp) ||
+        if (dev_alloc(h, &h->gs_obs, (size_t)Bp * h->net.O) || dev_alloc(h, &h->gs_act, (size_t)Bp * h->Aw) || dev_alloc(h, &h->gs_ret, Bp) ||
             dev_alloc(h, &h->gs_val, Bp) || dev_alloc(h, &h->gs_nlp, Bp)) return -1;
         h->gs_rows = Bp;
     }
@@ -2887,7 +2939,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
         HIP_OK(h, hipStreamSynchronize(h->stream));
         drop_graph(h);
         const int cr = std::max(Bp, h->upd_cap_rows), cs = std::max(steps, h->upd_cap_steps);
-        if (dev_alloc(h, &h->mb_obs, (size_t)cr * h->net.O) || dev_alloc(h, &h->mb_act, (size_t)cr * h->net.A) || dev_alloc(h, &h->mb_adv, cr) ||
+        if (dev_alloc(h, &h->mb_obs, (size_t)cr * h->net.O) || dev_alloc(h, &h->mb_act, (size_t)cr * h->Aw) || dev_alloc(h, &h->mb_adv, cr) ||
             dev_alloc(h, &h->mb_ret, cr) || dev_alloc(h, &h->mb_val, cr) || dev_alloc(h, &h->mb_nlp, cr)) return -1;
         if (h->d_perms) { (void)hipFree(h->d_perms); h->d_perms = nullptr; h->upd_cap_epochs = 0; }      // sized on demand below
         if (dev_alloc(h, &h->d_inv, cr) || dev_alloc(h, &h->d_gidx, cr) ||
@@ -2937,7 +2989,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
         // the rollout rows of all ranks, rank-major [world][T][E][.], once per update (10 MB per rank at config 3), outside the graph
         if (!h->rccl.AllGather) return fail(h, "ppo_update: the collective library has no ncclAllGather (needed by ppo_dist_global_shuffle)");
         const size_t rows = (size_t)B;
-        struct { const float* src; float* dst; size_t w; } gl[5] = {{h->ro_obs, h->gs_obs, (size_t)h->net.O}, {h->ro_act, h->gs_act, (size_t)h->net.A},
+        struct { const float* src; float* dst; size_t w; } gl[5] = {{h->ro_obs, h->gs_obs, (size_t)h->net.O}, {h->ro_act, h->gs_act, (size_t)h->Aw},
                                                                     {h->ro_ret, h->gs_ret, 1}, {h->ro_val, h->gs_val, 1}, {h->ro_nlp, h->gs_nlp, 1}};
         for (auto& x : gl) {
             const int rc = h->rccl.AllGather(x.src, x.dst, rows * x.w, /*ncclFloat32*/ 7, h->comm, h->stream);

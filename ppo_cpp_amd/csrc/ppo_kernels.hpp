@@ -100,6 +100,12 @@ __device__ __forceinline__ float ctr_normal(uint32_t seed, uint32_t row, uint32_
     const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);              // [0,1)
     return sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530717958647692f * u2);
 }
+// U(0,1) (open interval) from one counter hash: the categorical head's Gumbel draw when the caller passes no explicit uniforms.
+// Its own key, so that it never shares a lane with ctr_normal.
+__device__ __forceinline__ float ctr_uniform(uint32_t seed, uint32_t row, uint32_t step, uint32_t j) {
+    const uint32_t h = ctr_hash(seed ^ 0x3C5A96C3u, row, step, j);
+    return ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
+}
 
 // tanh on the hardware exp2 / rcp units: 1 - 2/(e^{2|x|}+1) with the sign restored, and the odd Taylor polynomial for
 // |x| < 1/16 where that form would cancel.  Absolute error <= 2 ulp of 1.0 (~1.2e-7) everywhere, ~10 instructions
@@ -181,6 +187,18 @@ __device__ __forceinline__ float group16_sum(float v) {
     v += dpp_move<0x141>(v);     // row_half_mirror: lane i <-> 7 - i within each 8
     v += dpp_move<0x140>(v);     // row_mirror:      lane i <-> 15 - i within each 16
     return v;
+}
+// (value, index) argmax over the same 16 lanes and the same butterfly: the larger value wins, a tie goes to the lower index (tf.argmax)
+__device__ __forceinline__ void argmax_step(float& v, int& i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+template <int CTRL>
+__device__ __forceinline__ int dpp_move_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+__device__ __forceinline__ void group16_argmax(float& v, int& i) {
+    argmax_step(v, i, dpp_move<0xB1>(v), dpp_move_i<0xB1>(i));
+    argmax_step(v, i, dpp_move<0x4E>(v), dpp_move_i<0x4E>(i));
+    argmax_step(v, i, dpp_move<0x141>(v), dpp_move_i<0x141>(i));
+    argmax_step(v, i, dpp_move<0x140>(v), dpp_move_i<0x140>(i));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -630,13 +648,14 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // `after_issue` runs right after this block's loads have been issued and before the first of them is consumed: loads the
 // caller issues there queue BEHIND the inputs (the inputs are needed first) but ahead of the wait, so they are in flight
 // during the staging round trip.
-template <class Hook = NoHook>
+// CAT: the categorical head's actions, ONE column per row (the category index), land in column 0 of the action tile
+template <bool CAT = false, class Hook = NoHook>
 __device__ __forceinline__ void stage_block_inputs(const NetDev& net, const float* __restrict__ par_src, float* par, float* Xs, int ldx,
                                                    const float* __restrict__ obs, int row0, int nrows,
                                                    ObsNorm nz, float* __restrict__ obs_out, float* __restrict__ x0g, RowScalars rs,
                                                    float* acts, float* rowv, Hook&& after_issue = Hook()) {
     const int tid = threadIdx.x;
-    const int Kp0 = net.Kp0, O = net.O, A = net.A, Ap = net.Ap;
+    const int Kp0 = net.Kp0, O = net.O, A = CAT ? 1 : net.A, Ap = net.Ap;
     constexpr int PK = 4, OK = 2, AK = 2;
     float pv[PK], ov[OK], av[AK], r0 = 0.f, r1 = 0.f, r2 = 0.f, s0 = 0.f, s1 = 1.f;
     // element i = tid + 256 k of a [16][W] tile is (row, col) = (i / W, i % W): one division per tile width instead of
@@ -778,7 +797,9 @@ struct StepArgs {
 #define PSTAMP(i) do { } while (0)
 #endif
 
-template <int CT, int KS, int CTH, bool WIDE>
+// CAT: categorical head (stable-baselines CategoricalProbabilityDistribution over the logits in place of mu): the action is ONE float per row
+// (the category index), `noise` holds the uniforms u [n,A] of the Gumbel-argmax draw, det_action = argmax of the logits
+template <int CT, int KS, int CTH, bool WIDE, bool CAT = false>
 __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev net, StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     PSTAMP(0);
@@ -824,6 +845,32 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
     // sampling + neglogp (G:5894-6672): 16 lanes per row, each lane owns actions j = part, part+16, ...
     const int r = threadIdx.x >> 4, part = threadIdx.x & 15;
     const int row = row0 + r;
+    if constexpr (CAT) {
+        // a = argmax_j (l_j - log(-log u_j)), neglogp = log sum_j exp(l_j - m) - (l_a - m), m = max_j l_j (softmax cross-entropy against one_hot(a))
+        float bp = -INFINITY, bl = -INFINITY;
+        int ip = 0, il = 0;
+        for (int j = part; j < net.A; j += 16) {
+            const float l = mus[r * ldm + j];
+            float u = 0.5f;
+            if (row < a.n) u = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+            const float pl = l - logf(-logf(u));
+            if (pl > bp) { bp = pl; ip = j; }
+            if (l > bl) { bl = l; il = j; }
+        }
+        group16_argmax(bp, ip);
+        group16_argmax(bl, il);
+        const float m = bl;
+        float z = 0.f;
+        for (int j = part; j < net.A; j += 16) z += expf(mus[r * ldm + j] - m);
+        z = group16_sum(z);
+        const float la = mus[r * ldm + ip] - m;
+        if (part == 0 && row < a.n) {
+            if (a.action) a.action[row] = (float)ip;
+            if (a.det_action) a.det_action[row] = (float)il;
+            if (a.neglogp) a.neglogp[row] = logf(z) - la;
+        }
+        if (a.host_action && part == 0) lds[net.lds_mu + r * ldm] = (float)ip;   // (after every lane of the row has read the tile: one wave, program order)
+    } else {
     float ssq = 0.f, slog = 0.f;
     for (int j = part; j < net.A; j += 16) {
         const float mu = mus[r * ldm + j];
@@ -844,18 +891,20 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
     ssq = group16_sum(ssq);
     slog = group16_sum(slog);
     if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+    }
     if (a.host_action) {
         // The block's rows are contiguous in the landing buffer ([16][A] floats from byte 64 A blockIdx.x): whole 16-byte pieces, the last rows' odd
         // elements one by one.  Pinned host memory is uncached on the device: a store leaves for the host at once.  Every storing thread waits for
         // its stores to be acknowledged, the barrier collects the waves, then ONE word: the host reads the block only after that word shows host_seq.
         lds_barrier();
-        const int live = min(ROWS_PER_BLOCK, a.n - row0) * net.A;       // elements of this block
-        float* dst = a.host_action + (size_t)row0 * net.A;
+        const int Aw = CAT ? 1 : net.A;                                  // action columns per row
+        const int live = min(ROWS_PER_BLOCK, a.n - row0) * Aw;          // elements of this block
+        float* dst = a.host_action + (size_t)row0 * Aw;
         const float* tile = lds + net.lds_mu;
         for (int k = threadIdx.x; 4 * k < live; k += BLOCK_THREADS) {
             float v[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { const int e = min(4 * k + i, live - 1); v[i] = tile[(e / net.A) * ldm + e % net.A]; }
+            for (int i = 0; i < 4; ++i) { const int e = min(4 * k + i, live - 1); v[i] = tile[(e / Aw) * ldm + e % Aw]; }
             if (4 * k + 3 < live) {
                 typedef float f32x4_t __attribute__((ext_vector_type(4)));
                 const f32x4_t q = {v[0], v[1], v[2], v[3]};
@@ -902,7 +951,8 @@ struct TrainArgs {
 // behind the input loads and stay in registers (the kernel runs one workgroup per CU: the whole 512-entry register file of
 // a SIMD belongs to one wave), and the second layer's first ring stages follow them.  The small phases then pay neither
 // their own weight round trip nor the burst that requests the next product's weights.
-template <int CT, int KS, int CTH, bool WIDE, bool EARLY = false>
+// CAT: categorical head -- `actions` holds ONE float per row (the category index); d logits go where d mu goes, the aux (d logstd) slot gets zeros
+template <int CT, int KS, int CTH, bool WIDE, bool EARLY = false, bool CAT = false>
 __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net, TrainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs)>();
@@ -936,7 +986,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
     RowScalars rs;
     if (tower == 0) rs = RowScalars{a.actions, a.advs ? a.advs : a.returns, a.advs ? nullptr : a.old_values, a.old_neglogp, a.adv_stats, 1};
     else rs = RowScalars{nullptr, a.returns, nullptr, a.old_values, nullptr, 2};
-    stage_block_inputs(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, nz, nullptr,
+    stage_block_inputs<CAT>(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, nz, nullptr,
                        tower == 0 ? a.x0g : nullptr, rs, acts, rowv, [&]() __attribute__((always_inline)) {
                            if constexpr (EARLY) {
                                load_frag<CT, KS>(wl0, a.theta + net.w_off[tower][0], net.Hp[0]);
@@ -1003,7 +1053,32 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
         STAMP(6);
         const float* mus = lds + net.lds_mu;
         const int ldm = net.Ap + LDS_PAD;
+        // categorical: m = max_j l_j, a0 = l - m, z = sum exp(a0); neglogp = log z - a0[act], entropy = sum_j p_j (log z - a0_j)
+        float cm = 0.f, cz = 1.f, clz = 0.f, cnlp = 0.f, cent = 0.f;
+        int cact = -1;
+        if constexpr (CAT) {
+            cact = live ? (int)acts[r * net.Ap] : -1;
+            float bl = -INFINITY;
+            int il = 0;
+            for (int j = part; j < net.A; j += 16) { const float l = mus[r * ldm + j]; if (l > bl) { bl = l; il = j; } }
+            group16_argmax(bl, il);
+            cm = bl;
+            float la = 0.f;
+            cz = 0.f;
+            for (int j = part; j < net.A; j += 16) {
+                const float a0 = mus[r * ldm + j] - cm;
+                cz += expf(a0);
+                if (j == cact) la = a0;
+            }
+            cz = group16_sum(cz); la = group16_sum(la);
+            clz = logf(cz);
+            for (int j = part; j < net.A; j += 16) { const float a0 = mus[r * ldm + j] - cm; cent += (expf(a0) / cz) * (clz - a0); }
+            cent = group16_sum(cent);
+            cnlp = clz - la;
+        }
         float ssq = 0.f, slog = 0.f, sent = 0.f;
+        if constexpr (CAT) sent = cent;
+        else {
         for (int j = part; j < net.A; j += 16) {
             const float mu = mus[r * ldm + j];
             const float logstd = mu * 0.0f + par[net.par_ls + j];
@@ -1014,7 +1089,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
             sent += logstd + HALF_LOG_2PIE;
         }
         ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
-        const float nlp = 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+        }
+        const float nlp = CAT ? cnlp : 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
         const float adv = live ? rowv[2 * r] : 0.f;
         const float old_nlp = live ? rowv[2 * r + 1] : nlp;
         const float lo = 1.0f - cr, hi = 1.0f + cr;
@@ -1038,6 +1114,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
         // d mu (-> dcur tile, also the dY operand of the head weight gradient) and d logstd rows
         for (int j = part; j < net.Ap; j += 16) {
             float dmu = 0.f, dl = 0.f;
+            if constexpr (CAT) {
+                // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H)   (dl stays 0: no logstd)
+                if (j < net.A && live) {
+                    const float a0 = mus[r * ldm + j] - cm;
+                    const float p = expf(a0) / cz;
+                    dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + net.ent_coef * g * (p * ((a0 - clz) + sent));
+                }
+            } else
             if (j < net.A && live) {
                 const float mu = mus[r * ldm + j];
                 const float sigma = expf(mu * 0.0f + par[net.par_ls + j]);

@@ -1,6 +1,7 @@
 // policies.hpp -- MlpPolicy with the reference's method names (ppo2/policies.hpp:26-82).  The reference wraps
 // tensorflow::Session::Run with fixed feed/fetch names; this one wraps the C-ABI of libppo_hip (include/ppo_hip.h).
-// Results come back as Mats: step -> {actions [n,A], values [n,1], neglogps [n,1]}.
+// Results come back as Mats: step -> {actions [n,A], values [n,1], neglogps [n,1]}; a categorical handle (ppo_create_ex with
+// PPO_ACT_CATEGORICAL, an Env whose action space is SPACE_DISCRETE) returns actions [n,1] holding the category index.
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -11,7 +12,10 @@
 
 class MlpPolicy {
 public:
-    explicit MlpPolicy(ppo_handle* handle, int act_dim) : h_(handle), act_dim_(act_dim) {}
+    explicit MlpPolicy(ppo_handle* handle, int act_dim) : h_(handle), act_dim_(action_width(handle, act_dim)) {}
+    // columns of an action matrix: act_dim (Gaussian) or 1 (categorical: the category index)
+    static int action_width(ppo_handle* handle, int act_dim) { return handle && ppo_action_dist(handle) == PPO_ACT_CATEGORICAL ? 1 : act_dim; }
+    int action_width() const { return act_dim_; }
     virtual ~MlpPolicy() {}
 
     // output/_action, output/_value_flat, output/_neglogp  (policies.hpp:33-46); noise == nullptr: on-device RNG

@@ -32,6 +32,13 @@ public:
           cliprange_vf_(cliprange_vf), tensorboard_log_(std::move(tensorboard_log)), n_envs_(env.get_num_envs()), num_timesteps_(0),
           act_model_(handle, env.get_action_space_size()), episode_reward_(Mat::Zero(n_envs_, 1)) {
         n_batch_ = n_envs_ * n_steps_;
+        // the handle's head must match the Env's action space (env/env.hpp:42-47): a Gaussian head for SPACE_CONTINOUS, a categorical
+        // one (ppo_create_ex with PPO_ACT_CATEGORICAL, act_dim = number of categories) for SPACE_DISCRETE
+        const bool discrete = env.get_action_space() == Env::SPACE_DISCRETE, categorical = ppo_action_dist(handle) == PPO_ACT_CATEGORICAL;
+        if (discrete != categorical)
+            throw std::runtime_error(std::string("PPO2: the Env's action space is '") + env.get_action_space() + "' but the handle's policy head is " +
+                                     (categorical ? "categorical" : "Gaussian") + " (create the handle with ppo_create_ex and " +
+                                     (discrete ? "PPO_ACT_CATEGORICAL" : "PPO_ACT_GAUSSIAN") + ")");
     }
 
     struct UpdateLog { int fps; float losses[5]; double collect_ms, update_ms; float mean_reward; };     // mean_reward: the rollout's un-normalised rewards (the learning curve)
@@ -55,7 +62,7 @@ public:
     // env step after that capture a one-off runtime hiccup)
     double phase_env_ms = 0, phase_act_ms = 0, phase_observe_ms = 0;
 
-    // Checkpoint in the reference's on-disk format (ppo2.hpp:107-166): the 15 model tensors as a TF bundle
+    // Checkpoint in the reference's on-disk format (ppo2.hpp:107-166): the 15 model tensors (14 for a categorical head: no pi/logstd) as a TF bundle
     // (<path>[.<id>].index / .data-00000-of-00001, names "model/<tensor>"; the untrained q/w, q/b ride along so that the
     // reference's restore_all finds every variable) and the JSON side-car with hyper-parameters + Env::serialize.
     void save(std::string save_path, int save_id = -1) {
@@ -74,8 +81,9 @@ public:
         }
         if (!b.count("model/q/w")) {                               // graph variables without gradient
             const int A = env_.get_action_space_size();
-            char name[32]; int32_t rows = 0, cols = 0;
-            check(ppo_tensor_info(h_, nt - 3, name, &rows, &cols));                  // pi/w: [h_last, A]
+            const auto pw = b.find("model/pi/w");                                    // [h_last, A]
+            if (pw == b.end() || pw->second.shape.size() != 2) throw std::runtime_error("PPO2::save: the handle has no pi/w");
+            const int32_t rows = (int32_t)pw->second.shape[0];
             ckpt::Tensor qw; qw.shape = {rows, A}; qw.data.assign((size_t)rows * A, 0.f);
             ckpt::Tensor qb; qb.shape = {A}; qb.data.assign((size_t)A, 0.f);
             b["model/q/w"] = qw; b["model/q/b"] = qb;
@@ -96,6 +104,11 @@ public:
     // restores weights + hyper-parameters + normaliser statistics (ppo2.hpp:169-223); like the reference it does not
     // restore optimiser state (the graph's saver holds no Adam slots, G:32396-32496)
     void load(const std::string& save_path) {
+        const ckpt::Bundle b = ckpt::load_bundle(save_path);
+        const bool categorical = ppo_action_dist(h_) == PPO_ACT_CATEGORICAL;
+        if (categorical == (b.count("model/pi/logstd") != 0))                   // the Gaussian head's checkpoint carries pi/logstd, the categorical one's does not
+            throw std::runtime_error(std::string("PPO2::load: ") + save_path + " holds a " + (categorical ? "Gaussian" : "categorical") + " policy but the handle's head is " +
+                                     (categorical ? "categorical" : "Gaussian"));
         nlohmann::json json = nlohmann::json::parse(ckpt::slurp(save_path + ".json"));
         env_.deserialize(json);
         gamma_ = json["gamma"].get<float>(); n_steps_ = json["n_steps"].get<int>(); vf_coef_ = json["vf_coef"].get<float>();
@@ -104,7 +117,6 @@ public:
         nminibatches_ = json["nminibatches"].get<int>(); noptepochs_ = json["noptepochs"].get<int>();
         cliprange_ = json["cliprange"].get<float>(); cliprange_vf_ = json["cliprange_vf"].get<float>();
         n_batch_ = n_envs_ * n_steps_;
-        const ckpt::Bundle b = ckpt::load_bundle(save_path);
         extra_tensors_.clear();
         const int nt = ppo_num_tensors(h_);
         for (int i = 0; i < nt; ++i) {
@@ -167,13 +179,13 @@ private:
         check(ppo_rollout_reset(h_, raw.reset().data()));                  // EnvNormalize::reset + Runner ctor
         // the logger's env-major [E, T] views are filled once per update from time-major rows (a row per env step is one copy; writing a
         // column of an [E, T] matrix touches E cache lines)
-        Mat actions(E, raw.get_action_space_size()), rew_view(E, T), done_view(E, T), rew_tm(T, E), done_tm(T, E), dones = Mat::Zero(E, 1);
+        Mat actions(E, act_model_.action_width()), rew_view(E, T), done_view(E, T), rew_tm(T, E), done_tm(T, E), dones = Mat::Zero(E, 1);
         for (int update = 1; update <= n_updates; ++update) {
             const auto t0 = clk::now();
             for (int t = 0; t < T; ++t) {
                 std::memcpy(done_tm.data() + (size_t)t * E, dones.data(), sizeof(float) * (size_t)E);
                 const auto p0 = clk::now();
-                const float* eps = explicit_noise ? explicit_noise + ((size_t)(update - 1) * T + t) * E * actions.cols() : nullptr;
+                const float* eps = explicit_noise ? explicit_noise + ((size_t)(update - 1) * T + t) * E * raw.get_action_space_size() : nullptr;
                 check(ppo_rollout_act(h_, t, eps, actions.data()));
                 const auto p1 = clk::now();
                 std::vector<Mat> r = raw.step(actions);

@@ -23,17 +23,18 @@ public:
           dones_(Mat::Zero(num_envs_, 1)) {}
 
     MiniBatch run() {
-        const int E = num_envs_, T = n_steps_, O = env_.get_observation_space_size(), A = env_.get_action_space_size();
+        // A: width of the exploration noise (action dimensions or categories); W: columns of an action (A, or 1 for a category index)
+        const int E = num_envs_, T = n_steps_, O = env_.get_observation_space_size(), A = env_.get_action_space_size(), W = model_.action_width();
         // time-major staging [T, E, .]
-        std::vector<float> obs((size_t)T * E * O), act((size_t)T * E * A);
+        std::vector<float> obs((size_t)T * E * O), act((size_t)T * E * W);
         Mat values(T, E), neglogp(T, E), dones(T, E), rewards(T, E), raw_rewards(T, E);
         for (int t = 0; t < T; ++t) {
             std::memcpy(&obs[(size_t)t * E * O], obs_.data(), sizeof(float) * (size_t)E * O);
             Mat eps;                                                       // explicit exploration noise of this env step [E, A], if any
             if (noise) { eps = Mat(E, A); std::memcpy(eps.data(), noise + (size_t)t * E * A, sizeof(float) * (size_t)E * A); }
             const std::vector<Mat> s = model_.step(obs_, noise ? &eps : nullptr);
-            assert(s[0].rows() == E && s[0].cols() == A && s[1].rows() == E && s[2].rows() == E);
-            std::memcpy(&act[(size_t)t * E * A], s[0].data(), sizeof(float) * (size_t)E * A);
+            assert(s[0].rows() == E && s[0].cols() == W && s[1].rows() == E && s[2].rows() == E);
+            std::memcpy(&act[(size_t)t * E * W], s[0].data(), sizeof(float) * (size_t)E * W);
             mat_set_row(values, t, s[1].data());
             mat_set_row(neglogp, t, s[2].data());
             mat_set_row(dones, t, dones_.data());                         // the done flag that arrived WITH obs_t (runner.hpp:110)
@@ -50,7 +51,7 @@ public:
         model_.gae(rewards, values, dones, last_values, dones_, gamma_, lam_, returns);
         MiniBatch mb;
         mb.obs = flatten(obs.data(), T, E, O);
-        mb.actions = flatten(act.data(), T, E, A);
+        mb.actions = flatten(act.data(), T, E, W);
         mb.returns = flatten(returns.data(), T, E, 1);
         mb.dones = flatten(dones.data(), T, E, 1);
         mb.values = flatten(values.data(), T, E, 1);

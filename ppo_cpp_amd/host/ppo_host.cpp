@@ -165,7 +165,8 @@ struct ppo_host_args {
     int n_envs, n_steps, n_hidden, hidden[8];
     int nminibatches, noptepochs, n_updates;
     float lr, cliprange, gamma, lam;
-    int seeded_env;          // 0: EnvMock(i+1) (degenerate constant data, the reference's stub) ; 1: SeededEnvMock ; 2: TargetEnv (learnable: tests/test_learning.py)
+    int seeded_env;          // 0: EnvMock(i+1) (degenerate constant data, the reference's stub) ; 1: SeededEnvMock ; 2: TargetEnv (learnable: tests/test_learning.py) ;
+                             // 3: DiscreteTargetEnv (act_dim categories, a categorical handle: tests/test_discrete_policy.py)
     int device;
     int max_workers;
     int reference_loop;      // 1: force the literal reference loop (Runner::run + host shuffle + _train_step)
@@ -204,19 +205,21 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
         if ((O != 18 || A != 18) && !a->seeded_env) throw std::runtime_error("EnvMock (the reference's stub) is 18 / 18");
         ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
         cfg.device = a->device;
-        if (ppo_create(&cfg, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        if (ppo_create_ex(&cfg, a->seeded_env == 3 ? PPO_ACT_CATEGORICAL : PPO_ACT_GAUSSIAN, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (x && x->theta_in && ppo_set_flat(h, 0, x->theta_in, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<Env>> envs;
-        for (int i = 0; i < a->n_envs; ++i) {
-            if (a->seeded_env == 2) envs.push_back(std::make_shared<TargetEnv>(1234u, (uint32_t)i, O, A));
-            else if (a->seeded_env) envs.push_back(std::make_shared<SeededEnvMock>(1234u, (uint32_t)i, O, A));
-            else envs.push_back(std::make_shared<EnvMock>(i + 1));
-        }
+        auto make_env = [&](uint32_t i) -> Env* {
+            if (a->seeded_env == 3) return new DiscreteTargetEnv(1234u, i, O, A);
+            if (a->seeded_env == 2) return new TargetEnv(1234u, i, O, A);
+            if (a->seeded_env) return new SeededEnvMock(1234u, i, O, A);
+            return new EnvMock(i + 1);
+        };
+        for (int i = 0; i < a->n_envs; ++i) envs.push_back(std::shared_ptr<Env>(make_env((uint32_t)i)));
         std::unique_ptr<Env> inner;
         VecEnv* pool = nullptr;
         if (a->n_envs > 1) inner.reset(pool = new VecEnv(envs, a->max_workers));
-        else inner.reset(a->seeded_env == 2 ? static_cast<Env*>(new TargetEnv(1234u, 0, O, A)) : a->seeded_env ? static_cast<Env*>(new SeededEnvMock(1234u, 0, O, A)) : static_cast<Env*>(new EnvMock(1)));
+        else inner.reset(make_env(0));
         {
             EnvNormalize env{std::move(inner), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
             PPO2 algorithm{h, env, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange};
@@ -282,6 +285,53 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
 }
 
 int ppo_host_learn(const ppo_host_args* a, ppo_host_result* out) { return run_learn(a, out, nullptr); }
+
+// PPO2::save of a categorical policy (a [64,64] handle behind DiscreteTargetEnv x 4 + EnvNormalize, one short learn()) under `prefix`, then PPO2::load into a
+// FRESH categorical handle: every tensor and the deterministic actions of `n` observations must be identical (actions_out [2][n]: before / after), and
+// loading into a Gaussian handle must fail.  Returns 0; 1 = tensors differ, 2 = the Gaussian load went through; -1 = error (message on stderr).
+int ppo_host_discrete_checkpoint(const char* prefix, const float* obs, int n, float* actions_out) {
+    ppo_handle* h[3] = {nullptr, nullptr, nullptr};
+    int rc = 0;
+    try {
+        ppo_config cfg; const int32_t hidden[2] = {64, 64};
+        ppo_config_default(&cfg, 18, 6, 2, hidden);
+        for (int k = 0; k < 3; ++k)
+            if (ppo_create_ex(&cfg, k < 2 ? PPO_ACT_CATEGORICAL : PPO_ACT_GAUSSIAN, &h[k]) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0)
+                throw std::runtime_error(ppo_last_error(h[k]));
+        std::vector<std::shared_ptr<Env>> envs;
+        for (uint32_t i = 0; i < 4; ++i) envs.push_back(std::make_shared<DiscreteTargetEnv>(1234u, i, 18, 6));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, 1)), h[0], /*training=*/true};
+            PPO2 algo{h[0], env, 0.99f, 16, cfg.ent_coef, 1e-3f, 0.5f, 0.5f, 0.95f, 4, 2, 0.2f};
+            algo.quiet = true;
+            algo.learn(2 * 4 * 16);
+            algo.save(prefix);
+            if (ppo_act_deterministic(h[0], obs, n, actions_out) != 0) throw std::runtime_error(ppo_last_error(h[0]));
+        }
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new DiscreteTargetEnv(1234u, 0, 18, 6)), h[1], /*training=*/false};
+            PPO2 algo{h[1], env};
+            algo.load(prefix);
+            if (ppo_act_deterministic(h[1], obs, n, actions_out + n) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+        }
+        for (int i = 0; i < ppo_num_tensors(h[0]) && !rc; ++i) {
+            int32_t r = 0, c = 0;
+            ppo_tensor_info(h[0], i, nullptr, &r, &c);
+            std::vector<float> x((size_t)r * (c ? c : 1)), y(x.size());
+            if (ppo_get_tensor(h[0], 0, i, x.data(), (int64_t)x.size()) != 0 || ppo_get_tensor(h[1], 0, i, y.data(), (int64_t)y.size()) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+            if (std::memcmp(x.data(), y.data(), sizeof(float) * x.size()) != 0) rc = 1;
+        }
+        if (!rc) {
+            EnvNormalize env{std::unique_ptr<Env>(new EnvMock()), h[2], /*training=*/false};     // (SPACE_CONTINOUS, for the Gaussian handle)
+            PPO2 algo{h[2], env};
+            bool threw = false;
+            try { algo.load(prefix); } catch (const std::exception& e) { threw = true; std::fprintf(stderr, "expected: %s\n", e.what()); }
+            if (!threw) rc = 2;
+        }
+    } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = -1; }
+    for (ppo_handle* x : h) if (x) ppo_destroy(x);
+    return rc;
+}
 
 // PPO2::learn with EXPLICIT exploration noise and epoch permutations on the reference's stack (SeededEnvMock x N -> VecEnv ->
 // EnvNormalize -> PPO2; ppo2.cpp:188-250), through the HBM-resident loop or (reference_loop) the literal one: what

@@ -94,9 +94,10 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                obs_dim=18, act_dim=18):
+                obs_dim=18, act_dim=18, discrete=False):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
-    returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights."""
+    returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
+    discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -105,7 +106,7 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
         a.hidden[i] = h
     a.nminibatches, a.noptepochs, a.n_updates = nminibatches, noptepochs, n_updates
     a.lr, a.cliprange, a.gamma, a.lam = lr, cliprange, gamma, lam
-    a.seeded_env, a.device, a.max_workers, a.reference_loop = 2, device, 0, int(reference_loop)
+    a.seeded_env, a.device, a.max_workers, a.reference_loop = 3 if discrete else 2, device, 0, int(reference_loop)
     a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
     a.obs_dim, a.act_dim = obs_dim, act_dim
     out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32)}
@@ -115,3 +116,15 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
         raise RuntimeError(r.error.decode())
     out["env_steps_per_s"] = r.env_steps_per_s
     return out
+
+
+def discrete_checkpoint(prefix, obs):
+    """PPO2::save of a categorical policy, PPO2::load into a fresh categorical handle and into a Gaussian one (ppo_host_discrete_checkpoint):
+    returns (status, deterministic actions before, after); status 0 = identical tensors and the Gaussian load refused"""
+    import numpy as np
+    lib = load_host_library()
+    obs = np.ascontiguousarray(obs, np.float32)
+    n = obs.shape[0]
+    acts = np.zeros((2, n), np.float32)
+    rc = lib.ppo_host_discrete_checkpoint(prefix.encode(), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)))
+    return rc, acts[0], acts[1]

@@ -1,0 +1,63 @@
+"""tools/prof_categorical.py [out.json] -- categorical vs Gaussian head at configs[2]'s workload (4096 x 16, [256,256], 18 obs, 18 actions / categories): device time per kernel class
+(ppo_prof_read) of one ppo_train_step on a 2048-row minibatch (B / 32) and of one collect_synthetic; the three handles alternate round by round"""
+import os, sys, json
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import ppo_cpp_amd
+
+E, T, M, ROUNDS, REPS = 4096, 16, 2048, 4, 20
+VARIANTS = [("categorical", "categorical", {}), ("gaussian_generic", "gaussian", {"PPO_HIP_NO_T8": "1", "PPO_HIP_NO_DW2": "1"}), ("gaussian_default", "gaussian", {})]
+
+
+def make(dist, env):
+    for k in ("PPO_HIP_NO_T8", "PPO_HIP_NO_DW2"):
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    g = ppo_cpp_amd.PPOHip(18, 18, [256, 256], action_dist=dist)
+    for k in env:
+        os.environ.pop(k)
+    g.init_orthogonal(0); g.norm_init(E); g.rollout_alloc(E, T)
+    return g
+
+
+def batch(g, rng):
+    obs = rng.uniform(-1, 1, (M, 18)).astype(np.float32)
+    if g.action_dist == "categorical":
+        a = rng.randint(0, 18, M).astype(np.float32)
+    else:
+        a = rng.normal(size=(M, 18)).astype(np.float32)
+    nlp, v = g.step(obs)[2], g.value(obs)
+    adv = rng.normal(size=M).astype(np.float32)
+    return obs, a, adv, (v + 0.3).astype(np.float32), nlp, v
+
+
+res = {name: {"train": [], "collect": [], "train_kernels": {}, "counts": None} for name, _, _ in VARIANTS}
+handles = {name: make(d, env) for name, d, env in VARIANTS}
+rng = np.random.RandomState(0)
+batches = {name: batch(handles[name], rng) for name, _, _ in VARIANTS}
+for name, g in handles.items():       # warm-up
+    for _ in range(3):
+        g.train_step(3e-4, 0.2, *batches[name]); g.collect_synthetic(1, 0.99, 0.95)
+for r in range(ROUNDS):
+    for name, g in handles.items():
+        g.prof_enable(True)
+        for _ in range(REPS):
+            g.train_step(3e-4, 0.2, *batches[name])
+        p = g.prof_read()
+        g.prof_enable(True)
+        for _ in range(REPS):
+            g.collect_synthetic(1, 0.99, 0.95, first=False)
+        q = g.prof_read()
+        g.prof_enable(False)
+        train = {k: v[0] / REPS * 1e3 for k, v in p.items() if v[1]}
+        res[name]["train"].append(sum(train.values()))
+        res[name]["train_kernels"] = train
+        res[name]["collect"].append(sum(v[0] for k, v in q.items() if v[1]) / REPS * 1e3)
+for name, g in handles.items():
+    res[name]["counts"] = {k: int(v) for k, v in g.kernel_counts().items() if v}
+    print("%-18s train step %7.1f us (rounds %s)  collect %8.1f us (rounds %s)" % (
+        name, np.median(res[name]["train"]), np.round(res[name]["train"], 1), np.median(res[name]["collect"]), np.round(res[name]["collect"], 1)))
+    print("   train kernels (us):", {k: round(v, 1) for k, v in res[name]["train_kernels"].items()})
+    print("   kernels:", res[name]["counts"])
+if len(sys.argv) > 1:                  # optional: the per-round numbers as JSON
+    json.dump(res, open(sys.argv[1], "w"), indent=1)
