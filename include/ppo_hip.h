@@ -127,6 +127,20 @@ int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, c
                    int32_t n, float losses[5]);
 /* Categorical handle: actions [n], every value an integer in [0, A) (checked on the host before the upload: an error otherwise); the loss
  * is the same surrogate with the softmax cross-entropy as neglogp and the categorical entropy. */
+/* value-function clipping: PPO2's cliprange_vf (ppo2/ppo2.hpp:442-446 feeds loss/clip_range_vf_ph, a node the shipped graph lacks).
+ * Per row, with v the new value, vo the old value, R the return (vf_loss = 1/2 mean over rows, clipfrac stays the policy's):
+ *   PPO_VCLIP_POLICY  max((v-R)^2, (vo + clip(v-vo, +-cliprange) - R)^2): the graph's own loss, bit for bit (the default)
+ *   PPO_VCLIP_RANGE   the same with `range` (finite, >= 0) in place of cliprange
+ *   PPO_VCLIP_OFF     (v-R)^2, unclipped
+ * `range` is ignored in the other two modes.  The setting belongs to the handle and applies from the next ppo_train_step / ppo_update on
+ * (a replayed update graph follows it: the kernels read it from device memory, as they read lr and cliprange).  An unknown mode or a
+ * negative / NaN / infinite range in PPO_VCLIP_RANGE is an error that leaves the previous setting in place. */
+#define PPO_VCLIP_POLICY 0
+#define PPO_VCLIP_RANGE  1
+#define PPO_VCLIP_OFF    2
+int ppo_set_value_clip(ppo_handle* h, int32_t mode, float range);
+/* the handle's current setting; range reads 0 outside PPO_VCLIP_RANGE */
+int ppo_get_value_clip(const ppo_handle* h, int32_t* mode, float* range);
 /* gradient of the last train step (of ppo_train_step, or the last one of ppo_update) BEFORE clipping (debug/parity), dense flat order.
  * PPO_BF16 handles on one GPU do not keep it: it is rebuilt here from the step's partial sums (same bits), which stay valid until the next train step. */
 int ppo_get_last_grad(ppo_handle* h, float* dst, int64_t count, float* global_norm);

@@ -55,6 +55,7 @@ def _f32(a, shape=None):
 
 
 ACTION_DISTS = {"gaussian": 0, "categorical": 1}        # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL
+VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
 class PPOHip:
@@ -177,6 +178,20 @@ class PPOHip:
         losses = np.empty(5, np.float32)
         self._ck(self.lib.ppo_train_step(self.h, C.c_float(lr), C.c_float(cliprange), *[_fp(x) for x in arrs], n, _fp(losses)))
         return losses
+
+    def set_value_clip(self, mode, range=0.0):
+        """Value-function clipping from the next train_step / update on: "policy" (0, the default: clip with cliprange), "range" (1: clip with
+        `range`, finite and >= 0) or "off" (2: the unclipped (v - R)^2).  `range` is ignored outside "range"."""
+        m = VALUE_CLIP_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(mode, str) and mode not in VALUE_CLIP_MODES:
+            raise ValueError("mode must be one of %s or an int, not %r" % (sorted(VALUE_CLIP_MODES), mode))
+        self._ck(self.lib.ppo_set_value_clip(self.h, C.c_int32(int(m)), C.c_float(range)))
+
+    def get_value_clip(self):
+        """(mode name, range): range is 0.0 outside "range" """
+        m, r = C.c_int32(), C.c_float()
+        self._ck(self.lib.ppo_get_value_clip(self.h, C.byref(m), C.byref(r)))
+        return {v: k for k, v in VALUE_CLIP_MODES.items()}[m.value], r.value
 
     def last_grad(self):
         g = np.empty(self.P, np.float32); norm = C.c_float()

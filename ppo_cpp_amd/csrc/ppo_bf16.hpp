@@ -810,7 +810,7 @@ struct LossArgsB {
     const float* head[2]; int ldh; int hsplit; size_t hstride;
     const float* logstd;
     const float* actions; const float* advs; const float* returns; const float* old_values; const float* old_neglogp;
-    const float* hyper;                 // {lr, cliprange}
+    const float* hyper;                 // {lr, cliprange, vclip_range, vclip_off}
     int n, A, Ap, rows_pad; float inv_n, ent_coef, vf_coef;
     bf16_t* dhead[2];                   // [rows_pad][Ap]  (tower 1: only column 0 is ever non-zero)
     float* slots[2]; int slot_w, slot_head, slot_aux, slot_loss;
@@ -830,6 +830,8 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
     const int row = blockIdx.x * BL_ROWS + r;
     const bool live = row < a.n;
     const float cr = a.hyper[1];
+    const float vcr = a.hyper[2];                   // the value tower's clip range and switch (vf_loss_row)
+    const float voff = a.hyper[3];
     const float g = a.inv_n;
     // every load of the lane first: head partials, actions, the row scalars
     float hp[BL_EPT][GB_HEAD_SPLIT], act_[BL_EPT], ls_[BL_EPT];
@@ -904,16 +906,7 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
             float v = vp[0];
 #pragma unroll
             for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < a.hsplit) v += vp[k];
-            const float dvo = v - vo;
-            const float vmin = tf_min(dvo, cr);
-            const float vclip = vo + tf_max(vmin, -cr);
-            const float e1 = v - Rv, e2 = vclip - Rv;
-            const float s1 = e1 * e1, s2 = e2 * e2;
-            lossv = tf_max(s1, s2);
-            const float gv = a.vf_coef * 0.5f * a.inv_n;
-            const float selv = (s1 >= s2) ? 1.0f : 0.0f;
-            const float passv = ((vmin >= -cr) ? 1.0f : 0.0f) * ((dvo <= cr) ? 1.0f : 0.0f);
-            dv = gv * selv * (2.0f * e1) + gv * (1.0f - selv) * (2.0f * e2) * passv;
+            vf_loss_row(v, Rv, vo, vcr, voff, a.vf_coef * 0.5f * a.inv_n, lossv, dv);
         }
         vt[r * 2] = dv; vt[r * 2 + 1] = lossv;
         a.dhead[1][(size_t)row * a.Ap] = (bf16_t)dv;

@@ -90,7 +90,9 @@ struct ppo_handle {
     // parameters + optimiser state (padded layout)
     float *theta = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grad = nullptr, *sumsq = nullptr, *sumsq2 = nullptr;
     float* beta_pow = nullptr;        // {cur b1, cur b2, next b1, next b2}
-    float* hyper = nullptr;           // {lr, cliprange}
+    float* hyper = nullptr;           // {lr, cliprange, vclip_range, vclip_off (0 or +inf)}: what the kernels read at run time (a replayed graph follows every change)
+    int32_t vclip_mode = PPO_VCLIP_POLICY;   // ppo_set_value_clip; set_hyper turns it into hyper[2], hyper[3]
+    float vclip_range = 0.f;
     float* norm_out = nullptr;        // [1]
     GradSrc* grad_src = nullptr;
     int n_tiled = 0; AdamArgs::Tiled tiled[ADAM_MAX_TILED]{};   // matrices whose transposed copy adam_kernel writes tile by tile
@@ -148,7 +150,7 @@ struct ppo_handle {
     uint32_t rng_seed = 0x5EEDu;      // ppo_seed
     int norm_obs_flag = 1, norm_rew_flag = 1;   // EnvNormalize's norm_obs / norm_reward (env_normalize.hpp:75,95)
     float* env_in = nullptr;          // [E*O | E | E] raw obs | raw reward | dones of the current env step, one block: one H2D per env step
-    float* hyper_host = nullptr;      // pinned {lr, cliprange}: the source of set_hyper's asynchronous copy
+    float* hyper_host = nullptr;      // pinned {lr, cliprange, vclip_range, vclip_off}: the source of set_hyper's asynchronous copy
     float* pin_in = nullptr;          // pinned host mirror of env_in (hipHostMalloc, owned by the handle)
     // ONE environment behind a host Env, resident three-wave kernel: the transition ALSO goes straight into device memory through the BAR (posted writes) with its own
     // sequence word, so the kernel polls and reads local memory instead of host memory over PCIe (large-BAR devices; PPO_HIP_NO_VRAM_INBOX=1 keeps the pinned block only)
@@ -1521,8 +1523,11 @@ int set_hyper(ppo_handle* h, float lr, float cr) {
     // tests/test_other_shapes.py::test_two_handles_interleaved_equal_the_same_handles_run_alone, which only failed behind the rest of the suite.)  The two floats
     // live in pinned memory owned by the handle; every API call that sets them synchronises the stream before it returns, so they are never rewritten under a copy.
     if (!h->hyper_host) HIP_OK(h, hipHostMalloc((void**)&h->hyper_host, 64, hipHostMallocDefault));
+    // The value tower's words: PPO_VCLIP_POLICY clips with cliprange itself (the graph's behaviour), PPO_VCLIP_RANGE with its own range, PPO_VCLIP_OFF not at all.
     h->hyper_host[0] = lr; h->hyper_host[1] = cr;
-    HIP_OK(h, hipMemcpyAsync(h->hyper, h->hyper_host, 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    h->hyper_host[2] = h->vclip_mode == PPO_VCLIP_RANGE ? h->vclip_range : h->vclip_mode == PPO_VCLIP_OFF ? 0.f : cr;
+    h->hyper_host[3] = h->vclip_mode == PPO_VCLIP_OFF ? INFINITY : 0.f;          // vf_loss_row: subtracted from the clipped square
+    HIP_OK(h, hipMemcpyAsync(h->hyper, h->hyper_host, 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
@@ -1640,7 +1645,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     if (!attr_ok) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); return bail(0); }
     const size_t P = (size_t)h->P_pad;
     if (dev_alloc(h, &h->par, (size_t)2 * h->net.par_total) || dev_alloc(h, &h->thetaT, (size_t)h->PT) || dev_alloc(h, &h->theta, P) || dev_alloc(h, &h->adam_m, P) || dev_alloc(h, &h->adam_v, P) || dev_alloc(h, &h->grad, P + 256) ||
-        dev_alloc(h, &h->sumsq, (size_t)4 * h->n_blocks) || dev_alloc(h, &h->sumsq2, (size_t)(h->n_blocks + 1023) / 1024) || dev_alloc(h, &h->beta_pow, 4) || dev_alloc(h, &h->hyper, 2) ||
+        dev_alloc(h, &h->sumsq, (size_t)4 * h->n_blocks) || dev_alloc(h, &h->sumsq2, (size_t)(h->n_blocks + 1023) / 1024) || dev_alloc(h, &h->beta_pow, 4) || dev_alloc(h, &h->hyper, 4) ||
         dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8))
         return bail(0);
     build_narrow_layout(h);
@@ -1935,6 +1940,24 @@ int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* act
 }
 
 // ---- train op -------------------------------------------------------------------------------------------------------
+int ppo_set_value_clip(ppo_handle* h, int32_t mode, float range) {
+    if (!h) return fail(nullptr, "ppo_set_value_clip: null handle");
+    if (mode != PPO_VCLIP_POLICY && mode != PPO_VCLIP_RANGE && mode != PPO_VCLIP_OFF)
+        return fail(h, "ppo_set_value_clip: unknown mode %d (PPO_VCLIP_POLICY, PPO_VCLIP_RANGE or PPO_VCLIP_OFF)", (int)mode);
+    if (mode == PPO_VCLIP_RANGE && !(std::isfinite(range) && range >= 0.f))
+        return fail(h, "ppo_set_value_clip: PPO_VCLIP_RANGE needs a finite range >= 0 (got %g)", (double)range);
+    // host state only: the next ppo_train_step / ppo_update writes it into hyper with lr and cliprange, ahead of its launches or graph replay
+    h->vclip_mode = mode;
+    h->vclip_range = mode == PPO_VCLIP_RANGE ? range : 0.f;
+    return 0;
+}
+
+int ppo_get_value_clip(const ppo_handle* h, int32_t* mode, float* range) {
+    if (!h || !mode || !range) return fail(nullptr, "ppo_get_value_clip: null argument");
+    *mode = h->vclip_mode; *range = h->vclip_range;
+    return 0;
+}
+
 int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, const float* actions, const float* advs,
                    const float* returns, const float* old_neglogp, const float* old_values, int32_t n, float losses[5]) {
     ENTER_Q(h);

@@ -78,6 +78,23 @@ struct NormDev {                    // EnvNormalize state for one statistics obj
 __device__ __forceinline__ float tf_min(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float tf_max(float a, float b) { return a > b ? a : b; }
 
+// One row of the value loss and its gradient dv = d loss / d v (G:10213-10837, G:14975-19571), shared by every kernel family.
+// vcr = hyper[2], the value-clip range (= hyper[1], cliprange itself, under PPO_VCLIP_POLICY).  voff = hyper[3]: 0, or +inf under PPO_VCLIP_OFF, which
+// makes the clipped square -inf: every row then takes the unclipped side of the max, lossv = (v - R)^2 and dv = gv 2 (v - R) exactly (the other term of
+// the AddN is 0 * finite), not a clip with an infinite range.  With voff = 0 the arithmetic is the graph's bit for bit (x - 0 == x); it costs one
+// subtraction and no branch, mask or register in kernels that are at their register floor.
+__device__ __forceinline__ void vf_loss_row(float v, float R, float vo, float vcr, float voff, float gv, float& lossv, float& dv) {
+    const float dvo = v - vo;
+    const float vmin = tf_min(dvo, vcr);
+    const float vclip = vo + tf_max(vmin, -vcr);
+    const float e1 = v - R, e2 = vclip - R;
+    const float s1 = e1 * e1, s2 = e2 * e2 - voff;
+    lossv = tf_max(s1, s2);
+    const float selv = (s1 >= s2) ? 1.0f : 0.0f;                                           // G:14975
+    const float passv = ((vmin >= -vcr) ? 1.0f : 0.0f) * ((dvo <= vcr) ? 1.0f : 0.0f);     // G:17477, 18071
+    dv = gv * selv * (2.0f * e1) + gv * (1.0f - selv) * (2.0f * e2) * passv;               // AddN_1 G:19571
+}
+
 __device__ __forceinline__ uint64_t splitmix64_dev(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -933,7 +950,7 @@ struct TrainArgs {
     const float* obs; const float* actions; const float* returns; const float* old_values; const float* old_neglogp;
     const float* advs;           // explicit normalised advantages (indexed like the others) or null
     const float* adv_stats;      // {mean, denom} of this minibatch when advs == null (ppo2.hpp:401-406)
-    const float* hyper;          // {lr, cliprange}
+    const float* hyper;          // {lr, cliprange, vclip_range, vclip_off}
     int n;                       // rows in this minibatch on this rank
     float inv_n;                 // 1 / (global minibatch rows): gradient of the Mean nodes
     // workspaces, row-major with padded leading dimensions
@@ -1166,16 +1183,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
         float dv = 0.f, lossv = 0.f;
         if (live) {
             const float R = rowv[2 * r], vo = rowv[2 * r + 1];
-            const float dvo = v - vo;
-            const float vmin = tf_min(dvo, cr);
-            const float vclip = vo + tf_max(vmin, -cr);
-            const float e1 = v - R, e2 = vclip - R;
-            const float s1 = e1 * e1, s2 = e2 * e2;
-            lossv = tf_max(s1, s2);
-            const float gv = net.vf_coef * 0.5f * a.inv_n;
-            const float selv = (s1 >= s2) ? 1.0f : 0.0f;                                       // G:14975
-            const float passv = ((vmin >= -cr) ? 1.0f : 0.0f) * ((dvo <= cr) ? 1.0f : 0.0f);   // G:17477, 18071
-            dv = gv * selv * (2.0f * e1) + gv * (1.0f - selv) * (2.0f * e2) * passv;           // AddN_1 G:19571
+            vf_loss_row(v, R, vo, a.hyper[2], a.hyper[3], net.vf_coef * 0.5f * a.inv_n, lossv, dv);
         }
         if (part == 0) { misc[r] = dv; misc[16 + r] = lossv; }
         lds_barrier();
@@ -1670,7 +1678,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* grad, floa
 struct AdamArgs {
     float* theta; float* m; float* v; const float* grad; const float* sumsq; int n_blocks;
     float* thetaT; float* par; const GradSrc* src;
-    const float* hyper;          // {lr, cliprange}
+    const float* hyper;          // {lr, cliprange, vclip_range, vclip_off}
     float* beta_pow;             // {cur b1, cur b2, next b1, next b2}
     float beta1, beta2, eps, max_norm;
     float* loss_row;             // [5] destination for this train step (may be null)

@@ -47,7 +47,7 @@ struct NwLayout {
 struct NwTrainArgs {
     const float* img;              // [2][w_total] packed weight images
     const float* obs; const float* actions; const float* advs; const float* returns; const float* old_values; const float* old_neglogp;
-    const float* hyper;            // {lr, cliprange}
+    const float* hyper;            // {lr, cliprange, vclip_range, vclip_off}
     int n; float inv_n;
     float* partials;               // [2 towers][n_groups][part_stride]; a workgroup writes its tower's tensors + 8 tail floats
     int n_groups; int part_stride;
@@ -397,7 +397,9 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
         NSTAMP(2 + l);
     }
     const float* hL = P + lay.x[L]; const int ldh = lay.ldx[L]; const int HpL = S::Hp(net, L - 1);
-    const float cr = a.hyper[1];
+    // this tower's clip range, hyper[1] = cliprange (policy) or hyper[2] = the value-clip range, and hyper[3] (vf_loss_row): requested where the graph's
+    // single cliprange load was, so that the value tower does not wait for them at its loss
+    const float cr = a.hyper[tower == 0 ? 1 : 2], voff = a.hyper[3];
     const int r = ptid >> 4, part = ptid & 15;
     const int row = row0 + 16 * pipe + r;
     const bool live = row < a.n;
@@ -486,16 +488,7 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
         float dv = 0.f, lossv = 0.f;
         if (live) {
             const float R = rowv[2 * r], vo = rowv[2 * r + 1];
-            const float dvo = v - vo;
-            const float vmin = tf_min(dvo, cr);
-            const float vclip = vo + tf_max(vmin, -cr);
-            const float e1 = v - R, e2 = vclip - R;
-            const float s1 = e1 * e1, s2 = e2 * e2;
-            lossv = tf_max(s1, s2);
-            const float gv = net.vf_coef * 0.5f * a.inv_n;
-            const float selv = (s1 >= s2) ? 1.0f : 0.0f;                                       // G:14975
-            const float passv = ((vmin >= -cr) ? 1.0f : 0.0f) * ((dvo <= cr) ? 1.0f : 0.0f);   // G:17477, 18071
-            dv = gv * selv * (2.0f * e1) + gv * (1.0f - selv) * (2.0f * e2) * passv;           // AddN_1 G:19571
+            vf_loss_row(v, R, vo, cr, voff, net.vf_coef * 0.5f * a.inv_n, lossv, dv);
         }
         if (part == 0) { misc[r] = dv; misc[16 + r] = lossv; }
         __syncthreads();

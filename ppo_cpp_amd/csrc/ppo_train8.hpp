@@ -283,7 +283,9 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
     load_w_stage<4, 2>(fr[1], W1T + (size_t)t8_stage_row(1, rot) * 256, off_big);
     __builtin_amdgcn_sched_barrier(0);
 #endif
-    const float cr = a.hyper[1];
+    // this tower's clip range, hyper[1] = cliprange (policy) or hyper[2] = the value-clip range (vf_loss_row): ONE load, issued where the graph's single
+    // cliprange load was (three adjacent words became one dwordx3 whose registers the policy tower then waited for, prefetch included: +4.5 % at configs[2])
+    const float cr = a.hyper[tower == 0 ? 1 : 2];
     const float* h2 = lds + L8::H2;
     float* d2 = lds + L8::D2;
     float* misc = lds + L8::MISC;
@@ -389,6 +391,7 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         }
     } else {
         // ---- value head + clipped value loss (G:10213-10837) and its gradient (G:14975-19571): 32 lanes per row ---------------------
+        const float voff = a.hyper[3];
         const float* wv = par + net.par_wv;
         float s = 0.f;
 #pragma unroll
@@ -397,16 +400,7 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         float dv = 0.f, lossv = 0.f;
         if (erow_live) {
             const float R = lds[L8::ROWV + 2 * er], vo = lds[L8::ROWV + 2 * er + 1];
-            const float dvo = v - vo;
-            const float vmin = tf_min(dvo, cr);
-            const float vclip = vo + tf_max(vmin, -cr);
-            const float e1 = v - R, e2 = vclip - R;
-            const float q1 = e1 * e1, q2 = e2 * e2;
-            lossv = tf_max(q1, q2);
-            const float gv = net.vf_coef * 0.5f * a.inv_n;
-            const float selv = (q1 >= q2) ? 1.0f : 0.0f;                                       // G:14975
-            const float passv = ((vmin >= -cr) ? 1.0f : 0.0f) * ((dvo <= cr) ? 1.0f : 0.0f);   // G:17477, 18071
-            dv = gv * selv * (2.0f * e1) + gv * (1.0f - selv) * (2.0f * e2) * passv;           // AddN_1 G:19571
+            vf_loss_row(v, R, vo, cr, voff, net.vf_coef * 0.5f * a.inv_n, lossv, dv);
         }
         if (ej == 0) { misc[er] = dv; misc[16 + er] = lossv; }
         lds_barrier();

@@ -52,6 +52,7 @@ public:
     }
     bool contains(const std::string& key) const { return kind_ == Object && obj_.count(key); }
     Kind kind() const { return kind_; }
+    bool is_null() const { return kind_ == Null; }
     size_t size() const { return kind_ == Array ? arr_.size() : kind_ == Object ? obj_.size() : 0; }
 
     template <class T>

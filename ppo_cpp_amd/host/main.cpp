@@ -7,6 +7,7 @@
 // children of the same binary (`--rank r --world N --ctl_fd F`, ppo2/dist.hpp), relays rank 0's output and returns the worst exit code.
 // Every rank builds threads / N environments with the global ids rank * E/N + i, joins the communicator (ppo_dist_init; rank 0's
 // ncclUniqueId travels over the launcher's socket pairs) and runs the unchanged PPO2::learn; rank 0 prints the CSV line with the job's fps.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,7 +30,7 @@ struct Flags {
 };
 const char* kAliases[][2] = {{"-d", "dir"}, {"--dir", "dir"}, {"-p", "path"}, {"--path", "path"}, {"--id", "id"}, {"-s", "steps"}, {"--steps", "steps"},
                              {"-l", "lr"}, {"--lr", "lr"}, {"--learning_rate", "lr"}, {"-e", "ent"}, {"--ent", "ent"}, {"--entropy", "ent"},
-                             {"-c", "cr"}, {"--cr", "cr"}, {"--clip_range", "cr"}, {"--cliprange", "cr"}, {"--saves", "saves"}, {"--num_saves", "saves"},
+                             {"-c", "cr"}, {"--cr", "cr"}, {"--clip_range", "cr"}, {"--cliprange", "cr"}, {"--cliprange_vf", "cr_vf"}, {"--cr_vf", "cr_vf"}, {"--saves", "saves"}, {"--num_saves", "saves"},
                              {"--epochs", "epochs"}, {"--num_epochs", "epochs"}, {"--batch_steps", "batch_steps"}, {"--n_steps", "batch_steps"},
                              {"-j", "threads"}, {"--threads", "threads"}, {"--jobs", "threads"}, {"--num_threads", "threads"}, {"--hidden", "hidden"},
                              {"--minibatches", "minibatches"}, {"--seed", "seed"}, {"-g", "graph"}, {"--graph", "graph"}, {"--graph_path", "graph"}, {"--obs", "obs"},
@@ -64,9 +65,11 @@ int main(int argc, char** argv) {
         const std::string a = argv[i];
         bool ok = false;
         if (a == "-h" || a == "--help") {
-            std::printf("usage: ppo_cpp_hip [--steps N] [--lr X] [--ent X] [--cr X] [--epochs N] [--batch_steps N] [--threads N_ENVS] [--minibatches N]\n"
+            std::printf("usage: ppo_cpp_hip [--steps N] [--lr X] [--ent X] [--cr X] [--cliprange_vf X|inf|off] [--epochs N] [--batch_steps N] [--threads N_ENVS]\n"
+                        "                   [--minibatches N]\n"
                         "                   [--hidden 256,256] [--saves N --dir DIR --id ID] [--path CKPT_PREFIX] [--resume] [--seeded] [--seed N]\n"
-                        "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n");
+                        "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n"
+                        "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n");
             return 0;
         }
         for (auto& al : kAliases) if (a == al[0] && i + 1 < argc) { f.kv[al[1]] = argv[++i]; ok = true; break; }
@@ -129,6 +132,14 @@ int main(int argc, char** argv) {
         if (!devs.empty()) cfg.device = devs[(size_t)ctx.rank % devs.size()];
         else if (ctx.world > 1) cfg.device = ctx.rank;
     }
+    float cliprange_vf = -1.f;                                                  // PPO2's cliprange_vf (ppo2.cpp passes none: the constructor's -1)
+    if (f.has("cr_vf")) {
+        const std::string v = f.str("cr_vf", "");
+        char* end = nullptr;
+        const double x = v == "off" ? (double)INFINITY : std::strtod(v.c_str(), &end);
+        if (v != "off" && (v.empty() || *end != '\0')) { std::fprintf(stderr, "--cliprange_vf: expected a number, inf or off, not '%s'\n", v.c_str()); return 1; }
+        cliprange_vf = (float)x;
+    }
     int rc = 0;
     try {
         if (f.has("graph")) {                                                    // -g: shape, constants and initial weights from a reference graph file
@@ -158,7 +169,7 @@ int main(int argc, char** argv) {
         else inner.reset(f.has("seeded") ? static_cast<Env*>(new SeededEnvMock(1234u, (uint32_t)env0, obs_dim, 18)) : static_cast<Env*>(new EnvMock(env0 + 1)));
         EnvNormalize env{std::move(inner), h, training};                          // ppo2.cpp:207
         PPO2 algorithm{h, env, 0.99f, n_steps, cfg.ent_coef, (float)f.num("lr", 1e-3), 0.5f, 0.5f, 0.95f, (int)f.num("minibatches", 32),
-                       (int)f.num("epochs", 10), (float)f.num("cr", 0.2)};         // ppo2.cpp:215-217
+                       (int)f.num("epochs", 10), (float)f.num("cr", 0.2), cliprange_vf};         // ppo2.cpp:215-217
         algorithm.seed = (unsigned long long)f.num("seed", 0);
         algorithm.set_distributed(ctx.world, ctx.rank);
         algorithm.replica_saves = f.has("replica_saves");

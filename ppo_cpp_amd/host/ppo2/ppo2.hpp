@@ -94,7 +94,8 @@ public:
         json["gamma"] = gamma_; json["n_steps"] = n_steps_; json["vf_coef"] = vf_coef_; json["ent_coef"] = ent_coef_;
         json["max_grad_norm"] = max_grad_norm_; json["learning_rate"] = learning_rate_; json["lam"] = lam_;
         json["nminibatches"] = nminibatches_; json["noptepochs"] = noptepochs_; json["cliprange"] = cliprange_;
-        json["cliprange_vf"] = cliprange_vf_; json["observation_space"] = env_.get_observation_space();
+        // (JSON has no NaN or inf: NaN and -inf, both PPO_VCLIP_POLICY, are written as -1; +inf is written as null, which load() reads back as +inf)
+        json["cliprange_vf"] = std::isnan(cliprange_vf_) || cliprange_vf_ == -INFINITY ? -1.f : cliprange_vf_; json["observation_space"] = env_.get_observation_space();
         json["action_space"] = env_.get_action_space(); json["n_envs"] = n_envs_ * world_; json["model_filename"] = model_filename;
         std::ofstream f(save_path + ".json");
         if (!f) throw std::runtime_error("PPO2::save: unable to open " + save_path + ".json");
@@ -115,8 +116,10 @@ public:
         ent_coef_ = json["ent_coef"].get<float>(); max_grad_norm_ = json["max_grad_norm"].get<float>();
         learning_rate_ = json["learning_rate"].get<float>(); lam_ = json["lam"].get<float>();
         nminibatches_ = json["nminibatches"].get<int>(); noptepochs_ = json["noptepochs"].get<int>();
-        cliprange_ = json["cliprange"].get<float>(); cliprange_vf_ = json["cliprange_vf"].get<float>();
+        cliprange_ = json["cliprange"].get<float>();
+        cliprange_vf_ = json.contains("cliprange_vf") && json["cliprange_vf"].is_null() ? INFINITY : json["cliprange_vf"].get<float>();
         n_batch_ = n_envs_ * n_steps_;
+        apply_value_clip();
         extra_tensors_.clear();
         const int nt = ppo_num_tensors(h_);
         for (int i = 0; i < nt; ++i) {
@@ -137,6 +140,7 @@ public:
     // save cadence of the reference (ppo2.hpp:256-262, 361-376): a save every ceil(n_updates / num_saves) updates with
     // ids 0, 1, ..., plus a trailing save when the interval does not divide the number of updates
     void learn(int total_timesteps, int num_saves = 0, const std::string& save_path = "") {
+        apply_value_clip();                                        // every rank: the replicas must train the same loss
         num_timesteps_ = 0;
         updates_this_learn_ = 0;
         if (!seeded_ || seeded_with_ != seed) {                    // exploration noise AND epoch shuffles follow PPO2::seed / --seed; a repeated
@@ -274,6 +278,16 @@ private:
         history_.push_back(log);
         const int update = ++updates_this_learn_;                   // save ids / cadence count from the start of THIS learn() call
         if (save_interval_ > 0 && update % save_interval_ == 0) save(save_path_, update / save_interval_ - 1);
+    }
+
+    // cliprange_vf -> ppo_set_value_clip.  Negative or NaN: PPO_VCLIP_POLICY, the value tower clips with cliprange (the graph's loss; the reference's default
+    // is -1, ppo2.hpp:442-446 feeds no clip_range_vf then).  This differs from stable-baselines, where a negative value switches clipping off.
+    // Finite >= 0: PPO_VCLIP_RANGE with that range.  +inf: PPO_VCLIP_OFF.
+    void apply_value_clip() {
+        const float r = cliprange_vf_;
+        if (std::isnan(r) || r < 0.f) check(ppo_set_value_clip(h_, PPO_VCLIP_POLICY, 0.f));
+        else if (std::isinf(r)) check(ppo_set_value_clip(h_, PPO_VCLIP_OFF, 0.f));
+        else check(ppo_set_value_clip(h_, PPO_VCLIP_RANGE, r));
     }
 
     void check(int rc) { if (rc != 0) throw std::runtime_error(std::string("PPO2: ") + ppo_last_error(h_)); }

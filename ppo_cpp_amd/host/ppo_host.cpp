@@ -173,6 +173,7 @@ struct ppo_host_args {
     int norm_obs, norm_reward;   // EnvNormalize constructor flags (env_normalize.hpp:24-27)
     unsigned long long seed;     // PPO2::seed (exploration noise + epoch shuffles)
     int obs_dim, act_dim;        // SeededEnvMock's shape (0 = 18): 36 / 18 is the hexapod with observed velocities (hexapod_closed_loop_env.hpp:20)
+    float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
 };
 struct ppo_host_result {
     double env_steps_per_s, collect_ms, update_ms;
@@ -222,7 +223,7 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
         else inner.reset(make_env(0));
         {
             EnvNormalize env{std::move(inner), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
-            PPO2 algorithm{h, env, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange};
+            PPO2 algorithm{h, env, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange, a->cliprange_vf};
             algorithm.quiet = true;
             struct Plain : Env {       // hides the EnvNormalize type to force the reference loop
                 Env& e; explicit Plain(Env& x) : e(x) {}
@@ -240,7 +241,7 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
                 void serialize(nlohmann::json& j) override { e.serialize(j); }
                 void deserialize(nlohmann::json& j) override { e.deserialize(j); }
             } plain{env};
-            PPO2 literal{h, plain, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange};
+            PPO2 literal{h, plain, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange, a->cliprange_vf};
             literal.quiet = true;
             PPO2& algo = a->reference_loop ? literal : algorithm;
             algo.seed = a->seed;
@@ -337,5 +338,31 @@ int ppo_host_discrete_checkpoint(const char* prefix, const float* obs, int n, fl
 // EnvNormalize -> PPO2; ppo2.cpp:188-250), through the HBM-resident loop or (reference_loop) the literal one: what
 // tests/test_host_layer.py holds against oracle.collect + oracle.update update by update (ppo2.hpp:264-349).
 int ppo_host_learn_explicit(const ppo_host_args* a, const ppo_host_explicit* x, ppo_host_result* out) { return run_learn(a, out, x); }
+
+// PPO2::save of a [64,64] Gaussian policy built with `cliprange_vf` under `prefix` (no training), then PPO2::load into a FRESH handle behind a PPO2 built with the
+// default -1: reports the value clipping that the load left on the fresh handle (ppo_get_value_clip).  Returns 0; -1 = error (message on stderr).
+int ppo_host_value_clip_checkpoint(const char* prefix, float cliprange_vf, int32_t* mode, float* range) {
+    ppo_handle* h[2] = {nullptr, nullptr};
+    int rc = 0;
+    try {
+        ppo_config cfg; const int32_t hidden[2] = {64, 64};
+        ppo_config_default(&cfg, 18, 18, 2, hidden);
+        for (int k = 0; k < 2; ++k)
+            if (ppo_create(&cfg, &h[k]) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0) throw std::runtime_error(ppo_last_error(h[k]));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new EnvMock()), h[0], /*training=*/false};
+            PPO2 algo{h[0], env, 0.99f, 16, cfg.ent_coef, 1e-3f, 0.5f, 0.5f, 0.95f, 4, 2, 0.2f, cliprange_vf};
+            algo.save(prefix);
+        }
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new EnvMock()), h[1], /*training=*/false};
+            PPO2 algo{h[1], env};
+            algo.load(prefix);
+            if (ppo_get_value_clip(h[1], mode, range) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+        }
+    } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = -1; }
+    for (ppo_handle* x : h) if (x) ppo_destroy(x);
+    return rc;
+}
 
 }  // extern "C"

@@ -11,7 +11,8 @@ class HostArgs(C.Structure):
                 ("nminibatches", C.c_int), ("noptepochs", C.c_int), ("n_updates", C.c_int),
                 ("lr", C.c_float), ("cliprange", C.c_float), ("gamma", C.c_float), ("lam", C.c_float),
                 ("seeded_env", C.c_int), ("device", C.c_int), ("max_workers", C.c_int), ("reference_loop", C.c_int),
-                ("norm_obs", C.c_int), ("norm_reward", C.c_int), ("seed", C.c_ulonglong), ("obs_dim", C.c_int), ("act_dim", C.c_int)]
+                ("norm_obs", C.c_int), ("norm_reward", C.c_int), ("seed", C.c_ulonglong), ("obs_dim", C.c_int), ("act_dim", C.c_int),
+                ("cliprange_vf", C.c_float)]
 
 
 class HostResult(C.Structure):
@@ -36,7 +37,9 @@ def load_host_library(build=True):
 
 
 def learn(n_envs, n_steps, hidden, n_updates, nminibatches=32, noptepochs=10, lr=3.93141e-4, cliprange=0.161023, gamma=0.99,
-          lam=0.95, seeded_env=True, device=-1, max_workers=0, reference_loop=False, norm_obs=True, norm_reward=True, seed=0, obs_dim=18, act_dim=18):
+          lam=0.95, seeded_env=True, device=-1, max_workers=0, reference_loop=False, norm_obs=True, norm_reward=True, seed=0, obs_dim=18, act_dim=18,
+          cliprange_vf=-1.0):
+    """cliprange_vf: PPO2's value clipping: < 0 (the default) clips the value with cliprange, a finite value >= 0 with its own range, inf switches it off"""
     lib = load_host_library()
     a = HostArgs()
     a.n_envs, a.n_steps, a.n_hidden = n_envs, n_steps, len(hidden)
@@ -47,6 +50,7 @@ def learn(n_envs, n_steps, hidden, n_updates, nminibatches=32, noptepochs=10, lr
     a.seeded_env, a.device, a.max_workers, a.reference_loop = int(seeded_env), device, max_workers, int(reference_loop)
     a.norm_obs, a.norm_reward, a.seed = int(norm_obs), int(norm_reward), seed
     a.obs_dim, a.act_dim = obs_dim, act_dim
+    a.cliprange_vf = cliprange_vf
     r = HostResult()
     if lib.ppo_host_learn(C.byref(a), C.byref(r)) != 0:
         raise RuntimeError(r.error.decode())
@@ -63,7 +67,7 @@ class HostExplicit(C.Structure):
 
 
 def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, lr=3.93141e-4, cliprange=0.161023, gamma=0.99, lam=0.95,
-                   reference_loop=False, device=-1, obs_dim=18, act_dim=18):
+                   reference_loop=False, device=-1, obs_dim=18, act_dim=18, cliprange_vf=-1.0):
     """PPO2::learn for perms.shape[0] updates with explicit weights, exploration noise [U,T,E,A] and epoch permutations [U,epochs,B]
     on SeededEnvMock x n_envs behind VecEnv + EnvNormalize.  Returns per-update mean losses [U,5], final weights, obs_rms, ret_rms."""
     import numpy as np
@@ -80,6 +84,7 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
     a.seeded_env, a.device, a.max_workers, a.reference_loop = 1, device, 0, int(reference_loop)
     a.norm_obs, a.norm_reward, a.seed = 1, 1, 0
     a.obs_dim, a.act_dim = obs_dim, act_dim
+    a.cliprange_vf = cliprange_vf
     assert noise.shape[3] == act_dim
     out = {"losses": np.zeros((U, 5), np.float32), "theta": np.zeros(theta.size, np.float32),
            "obs_mean": np.zeros(obs_dim, np.float32), "obs_var": np.zeros(obs_dim, np.float32), "obs_count": np.zeros(1, np.float64),
@@ -94,7 +99,7 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                obs_dim=18, act_dim=18, discrete=False):
+                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle."""
@@ -109,6 +114,7 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     a.seeded_env, a.device, a.max_workers, a.reference_loop = 3 if discrete else 2, device, 0, int(reference_loop)
     a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
     a.obs_dim, a.act_dim = obs_dim, act_dim
+    a.cliprange_vf = cliprange_vf
     out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32)}
     x = HostExplicit(None, None, None, out["losses"].ctypes.data, None, None, None, None, None, None, None, out["reward_curve"].ctypes.data)
     r = HostResult()
@@ -116,6 +122,16 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
         raise RuntimeError(r.error.decode())
     out["env_steps_per_s"] = r.env_steps_per_s
     return out
+
+
+def value_clip_checkpoint(prefix, cliprange_vf):
+    """PPO2::save of a policy built with cliprange_vf, PPO2::load into a fresh handle (ppo_host_value_clip_checkpoint): returns the fresh handle's
+    value clipping as (mode, range), mode 0 / 1 / 2 = PPO_VCLIP_POLICY / RANGE / OFF"""
+    lib = load_host_library()
+    m, r = C.c_int32(), C.c_float()
+    if lib.ppo_host_value_clip_checkpoint(prefix.encode(), C.c_float(cliprange_vf), C.byref(m), C.byref(r)) != 0:
+        raise RuntimeError("ppo_host_value_clip_checkpoint failed (see stderr)")
+    return m.value, r.value
 
 
 def discrete_checkpoint(prefix, obs):
