@@ -152,6 +152,14 @@ int ppo_adv_normalize(ppo_handle* h, const float* returns, const float* values, 
 int ppo_gae(ppo_handle* h, const float* rewards, const float* values, const float* dones,
             const float* last_values, const float* last_dones, int32_t T, int32_t E, float gamma, float lam,
             float* returns);
+/* The same scan with a value bootstrap at time-limit TRUNCATIONS (no reference counterpart: Runner::set_returns treats every done as a terminal state).
+ * terminal_values [T,E]: V(terminal observation) on the rows whose step was cut by a time limit, 0 elsewhere.  The reward of a row becomes
+ * rewards + gamma * terminal_values; the lambda trace is still cut at the episode boundary (stable-baselines3's rule):
+ *   delta_t = (rewards[t] + gamma tv[t]) + gamma V[t+1] (1 - done[t+1]) - V[t]        (done[t+1]: row t+1 holds the done raised by step t; last_dones for t = T-1)
+ * terminal_values == NULL is ppo_gae, bit for bit (the same launch). */
+int ppo_gae_ex(ppo_handle* h, const float* rewards, const float* values, const float* dones, const float* last_values,
+               const float* last_dones, const float* terminal_values, int32_t T, int32_t E, float gamma, float lam,
+               float* returns);
 
 /* EnvNormalize (env/env_normalize.hpp:20-116) + RunningStatistics (common/running_statistics.hpp). */
 int ppo_norm_init(ppo_handle* h, int32_t n_envs, float gamma, float clip_obs, float clip_rew, float epsilon);
@@ -184,16 +192,33 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t n_envs, int32_t n_steps);
 int ppo_rollout_reset(ppo_handle* h, const float* raw_obs);
 int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions_out);
 int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const float* raw_rew, const float* dones);
-/* bootstrap value + GAE (runner.hpp:134, 159-191) */
+/* Time-limit truncations (no reference counterpart).  The `done` of step t of the environments env_ids [count] (int32) was raised by a time limit, not by a
+ * terminal state; terminal_raw_obs [count, O] are the RAW observations those episodes ended on (raw_obs of ppo_rollout_observe holds the observation after the
+ * reset).  Call it after ppo_rollout_observe(h, t, ..) and before the next ppo_rollout_act / ppo_rollout_finish, any number of times.  It only appends to a
+ * host-side list of the handle: nothing is enqueued, and it does not depend on which rollout form serves the handle (a resident kernel keeps running).
+ * ppo_rollout_finish then bootstraps those rows: the terminal observations are scaled and clipped with the observation statistics AS THEY STAND AT THE FINISH
+ * (after the last transition is booked -- exactly like the end-of-rollout bootstrap observation; they never update obs_rms; with norm_obs == 0 they pass through),
+ * valued in one batched pass with the weights the rollout was collected with, and GAE runs in ppo_gae_ex's form.  The stored rewards (after EnvNormalize's
+ * scaling and clip) are the ones that get gamma * V added; the reward normaliser's return accumulator and ret_rms are not touched.  Data parallel: every rank
+ * marks and bootstraps its own rows.
+ * Errors, each leaving the list as it was: no rollout allocated, t out of range or not the step of the last ppo_rollout_observe, an env id out of range or named
+ * twice, (t, env) already marked, an env whose done in step t is 0, count < 0.  count == 0 is a no-op.  The list is emptied by ppo_rollout_finish (after use),
+ * ppo_rollout_reset and ppo_rollout_alloc.  A rollout without marks enqueues exactly the launches it enqueued before this entry point existed. */
+int ppo_rollout_mark_truncated(ppo_handle* h, int32_t t, int32_t count, const int32_t* env_ids, const float* terminal_raw_obs);
+/* bootstrap value + GAE (runner.hpp:134, 159-191); with marked truncations: their value pass, the scatter into the [T,E] table (tval_scatter_kernel) and the
+ * truncation form of GAE (ppo_kernel_counts: "gae_kernel<trunc>" / "gae_long_kernel<trunc>") */
 int ppo_rollout_finish(ppo_handle* h, float gamma, float lam);
 /* device-env path: the whole T-step collect against the on-device seeded synthetic env (obs ~ U(-1,1)^O,
  * reward ~ U(-1,1), done ~ Bernoulli(1/300), keyed by (seed, global env id, step counter)); env ids start at
  * env0 (rank sharding).  first != 0 performs the reset (step counter step0), otherwise continues from the carried
  * obs/dones.  noise [T,E,A] or NULL.  Ends with bootstrap + GAE.
  * Categorical handle: noise [T,E,A] (ppo_collect_synthetic) / [E,A] (ppo_rollout_act) are uniforms, actions_out of ppo_rollout_act is [E]. */
+/* Every done of the seeded device env is a terminal state: it has no terminal observation, ppo_rollout_mark_truncated does not apply to this path. */
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first,
                           const float* noise, float gamma, float lam);
-/* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]); a categorical handle's field 1 is [T,E] */
+/* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]); a categorical handle's field 1 is [T,E].
+ * 7 (download only; an upload is refused): terminal values [T,E] as the last ppo_rollout_finish used them -- V(terminal observation) on the marked rows, 0 elsewhere,
+ * all zeros when that finish had no marks. */
 int ppo_rollout_download(ppo_handle* h, int field, float* dst, int64_t count);
 int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count);
 

@@ -67,6 +67,7 @@ class PPOHip:
     explicit noise keeps the Gaussian's shape and holds the uniforms of the Gumbel-argmax draw."""
 
     FIELDS = {"obs": 0, "actions": 1, "values": 2, "neglogp": 3, "dones": 4, "rewards": 5, "returns": 6}
+    OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", **overrides):
         self.lib = load_library()
@@ -204,11 +205,16 @@ class PPOHip:
         self._ck(self.lib.ppo_adv_normalize(self.h, _fp(r), _fp(v), r.size, _fp(out)))
         return out
 
-    def gae(self, rewards, values, dones, last_values, last_dones, gamma, lam):
+    def gae(self, rewards, values, dones, last_values, last_dones, gamma, lam, terminal_values=None):
+        """terminal_values [T, E]: V(terminal observation) on the rows cut by a time limit, 0 elsewhere (ppo_gae_ex); None = every done is terminal (ppo_gae)"""
         rw, va, dn, lv, ld = [_f32(x) for x in (rewards, values, dones, last_values, last_dones)]
         T, E = rw.shape
         out = np.empty((T, E), np.float32)
-        self._ck(self.lib.ppo_gae(self.h, _fp(rw), _fp(va), _fp(dn), _fp(lv), _fp(ld), T, E, C.c_float(gamma), C.c_float(lam), _fp(out)))
+        if terminal_values is None:
+            self._ck(self.lib.ppo_gae(self.h, _fp(rw), _fp(va), _fp(dn), _fp(lv), _fp(ld), T, E, C.c_float(gamma), C.c_float(lam), _fp(out)))
+        else:
+            tv = _f32(terminal_values, (T, E))
+            self._ck(self.lib.ppo_gae_ex(self.h, _fp(rw), _fp(va), _fp(dn), _fp(lv), _fp(ld), _fp(tv), T, E, C.c_float(gamma), C.c_float(lam), _fp(out)))
         return out
 
     # ---- normaliser -------------------------------------------------------------------------------
@@ -260,6 +266,13 @@ class PPOHip:
         o, r, d = _f32(raw_obs, (self.E, self.O)), _f32(raw_rew).reshape(-1), _f32(dones).reshape(-1)
         self._ck(self.lib.ppo_rollout_observe(self.h, t, _fp(o), _fp(r), _fp(d)))
 
+    def rollout_mark_truncated(self, t, env_ids, terminal_raw_obs):
+        """the dones of step t of `env_ids` were time-limit truncations; terminal_raw_obs [len(env_ids), O] = the raw observations those episodes ended on.
+        Call it after rollout_observe(t, ..) and before the next rollout_act / rollout_finish (include/ppo_hip.h, ppo_rollout_mark_truncated)."""
+        ids = np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        obs = _f32(terminal_raw_obs).reshape(ids.size, self.O)
+        self._ck(self.lib.ppo_rollout_mark_truncated(self.h, int(t), int(ids.size), ids.ctypes.data_as(C.POINTER(C.c_int32)), _fp(obs)))
+
     def rollout_finish(self, gamma, lam):
         self._ck(self.lib.ppo_rollout_finish(self.h, C.c_float(gamma), C.c_float(lam)))
 
@@ -271,12 +284,14 @@ class PPOHip:
     def rollout_get(self, field):
         shape = {"obs": (self.T, self.E, self.O), "actions": (self.T, self.E) + self._act_shape}.get(field, (self.T, self.E))
         out = np.empty(shape, np.float32)
-        self._ck(self.lib.ppo_rollout_download(self.h, self.FIELDS[field], _fp(out), C.c_int64(out.size)))
+        idx = self.FIELDS[field] if field in self.FIELDS else self.OUTPUT_FIELDS[field]
+        self._ck(self.lib.ppo_rollout_download(self.h, idx, _fp(out), C.c_int64(out.size)))
         return out
 
     def rollout_set(self, field, arr):
         a = _f32(arr)
-        self._ck(self.lib.ppo_rollout_upload(self.h, self.FIELDS[field], _fp(a), C.c_int64(a.size)))
+        idx = self.FIELDS[field] if field in self.FIELDS else self.OUTPUT_FIELDS[field]
+        self._ck(self.lib.ppo_rollout_upload(self.h, idx, _fp(a), C.c_int64(a.size)))
 
     def update(self, lr, cliprange, noptepochs, nminibatches, perms=None, seed=0, want_rows=True):
         rows = np.empty((noptepochs * nminibatches, 5), np.float32) if want_rows else None

@@ -51,12 +51,13 @@ const char* kProfNames[PK_COUNT] = {"policy_step", "train_fwd_bwd", "weight_grad
 // which kernel VARIANT a call took (ppo_kernel_counts): the fast paths are chosen by shape, and a test must be able to say which one ran
 enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN, KV_NARROW_STEP_STATIC, KV_NARROW_STEP,
                      KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH,
-                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_COUNT };
+                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
                                        "bf16_train_sequence", "bf16_step_sequence", "bf16_reduce_adam_kernel", "narrow_epoch_kernel",
-                                       "policy_step_kernel<cat>", "train_fwd_bwd_kernel<cat>"};
+                                       "policy_step_kernel<cat>", "train_fwd_bwd_kernel<cat>",
+                                       "gae_kernel<trunc>", "gae_long_kernel<trunc>", "tval_scatter_kernel"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -137,6 +138,13 @@ struct ppo_handle {
     int done_staged = -1;             // ro_done[done_staged] already holds cur_done (written by norm_batch_kernel)
     float *cur_done = nullptr, *raw_obs = nullptr, *raw_rew = nullptr, *raw_done = nullptr, *last_val = nullptr;
     float* ro_noise = nullptr;        // [T,E,A] staging for explicit noise
+    // time-limit truncations (ppo_rollout_mark_truncated): a HOST list of (row, raw terminal observation) that ppo_rollout_finish turns into ro_tval.
+    // tr_pin: pinned [tr_cap * O floats | tr_cap row indices], the K rows packed as [K * O | K] at finish (one H2D copy); tr_mark [T*E]: row already marked
+    float* tr_pin = nullptr; size_t tr_cap = 0; int tr_K = 0; std::vector<int> tr_idx; std::vector<unsigned char> tr_mark;
+    float* tr_dev = nullptr; size_t tr_dev_cap = 0;   // device image of the packed block, then K values of the value pass
+    float* ro_tval = nullptr;         // [T,E] terminal values as the last finish used them (allocated by the first finish that has marks)
+    bool tval_live = false;           // the last finish had marks: ro_tval is what ppo_rollout_download(7) returns (zeros otherwise)
+    int obs_t = -1;                   // step of the last ppo_rollout_observe (-1: none since the reset / finish): the step a mark may name
     // update
     int* d_perms = nullptr; int* d_inv = nullptr; int* d_gidx = nullptr; float* d_advstats = nullptr;
     float *mb_obs = nullptr, *mb_act = nullptr, *mb_adv = nullptr, *mb_ret = nullptr, *mb_val = nullptr, *mb_nlp = nullptr;
@@ -1553,6 +1561,17 @@ void launch_gae(ppo_handle* h, const float* rew, const float* val, const float* 
         hipLaunchKernelGGL(gae_long_kernel, dim3(E), dim3(GAE_LONG_THREADS), (size_t)3 * T * sizeof(float), h->stream, rew, val, done, last_val, last_done, T, E, gamma, lam, ret);
     else hipLaunchKernelGGL(gae_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, rew, val, done, last_val, last_done, T, E, gamma, lam, ret);
 }
+// ... with the terminal values of time-limit truncations (tv [T,E], never null here): the same selection rule, the sibling kernels
+void launch_gae_trunc(ppo_handle* h, const float* rew, const float* val, const float* done, const float* last_val, const float* last_done, const float* tv, int T, int E,
+                      float gamma, float lam, float* ret) {
+    if (E <= 64 && T >= 128 && (size_t)3 * T * sizeof(float) <= 60 * 1024) {
+        ++h->kv[KV_GAE_LONG_TRUNC];
+        hipLaunchKernelGGL(gae_long_trunc_kernel, dim3(E), dim3(GAE_LONG_THREADS), (size_t)3 * T * sizeof(float), h->stream, rew, val, done, last_val, last_done, tv, T, E, gamma, lam, ret);
+    } else {
+        ++h->kv[KV_GAE_TRUNC];
+        hipLaunchKernelGGL(gae_trunc_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, rew, val, done, last_val, last_done, tv, T, E, gamma, lam, ret);
+    }
+}
 
 }  // namespace
 
@@ -1767,6 +1786,9 @@ void ppo_destroy(ppo_handle* h) {
         for (int t = 0; t < 2; ++t) for (int l = 0; l < PPO_MAX_LAYERS; ++l) for (bf16_t* p : {b.hb[t][l], b.dy[t][l]}) if (p) (void)hipFree(p);
     }
     if (h->pin_in) (void)hipHostFree(h->pin_in);
+    if (h->tr_pin) (void)hipHostFree(h->tr_pin);
+    if (h->tr_dev) (void)hipFree(h->tr_dev);
+    if (h->ro_tval) (void)hipFree(h->ro_tval);
     if (h->hyper_host) (void)hipHostFree(h->hyper_host);
     if (h->vram_in) (void)hipFree(h->vram_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -2016,6 +2038,11 @@ int ppo_adv_normalize(ppo_handle* h, const float* returns, const float* values, 
 
 int ppo_gae(ppo_handle* h, const float* rewards, const float* values, const float* dones, const float* last_values,
             const float* last_dones, int32_t T, int32_t E, float gamma, float lam, float* returns) {
+    return ppo_gae_ex(h, rewards, values, dones, last_values, last_dones, nullptr, T, E, gamma, lam, returns);
+}
+
+int ppo_gae_ex(ppo_handle* h, const float* rewards, const float* values, const float* dones, const float* last_values,
+               const float* last_dones, const float* terminal_values, int32_t T, int32_t E, float gamma, float lam, float* returns) {
     ENTER(h);
     if (T < 1 || E < 1) return fail(h, "ppo_gae: bad shape");
     const size_t n = (size_t)T * E;
@@ -2024,9 +2051,12 @@ int ppo_gae(ppo_handle* h, const float* rewards, const float* values, const floa
     const float* src[5] = {rewards, values, dones, last_values, last_dones};
     const size_t cnt[5] = {n, n, n, (size_t)E, (size_t)E};
     for (int i = 0; i < 5; ++i) HIP_OK(h, hipMemcpyAsync(h->st_vec[i], src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    // (the terminal values travel in the observation staging block: at least n * O >= n floats, and no GAE input lives there)
+    if (terminal_values) HIP_OK(h, hipMemcpyAsync(h->st_obs, terminal_values, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     {
         ProfScope ps(h, PK_GAE);
-        launch_gae(h, h->st_vec[0], h->st_vec[1], h->st_vec[2], h->st_vec[3], h->st_vec[4], T, E, gamma, lam, h->st_vec[5]);
+        if (terminal_values) launch_gae_trunc(h, h->st_vec[0], h->st_vec[1], h->st_vec[2], h->st_vec[3], h->st_vec[4], h->st_obs, T, E, gamma, lam, h->st_vec[5]);
+        else launch_gae(h, h->st_vec[0], h->st_vec[1], h->st_vec[2], h->st_vec[3], h->st_vec[4], T, E, gamma, lam, h->st_vec[5]);
         HIP_OK(h, hipGetLastError());
     }
     HIP_OK(h, hipMemcpyAsync(returns, h->st_vec[5], n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2244,6 +2274,12 @@ int ppo_norm_set_stats(ppo_handle* h, int which, const float* mean, const float*
 }
 
 // ---- rollout ----------------------------------------------------------------------------------------------------------
+// forget the marked truncations (host state only)
+static void trunc_clear(ppo_handle* h) {
+    for (int k = 0; k < h->tr_K; ++k) h->tr_mark[(size_t)h->tr_idx[k]] = 0;
+    h->tr_idx.clear(); h->tr_K = 0; h->obs_t = -1;
+}
+
 int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
     ENTER(h);
     if (E < 1 || T < 1) return fail(h, "ppo_rollout_alloc: bad shape");
@@ -2260,6 +2296,8 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
         return -1;
     h->E = E; h->T = T;
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (h->ro_tval) { (void)hipFree(h->ro_tval); h->ro_tval = nullptr; }
+    h->tr_idx.clear(); h->tr_K = 0; h->obs_t = -1; h->tr_mark.assign(B, 0); h->tval_live = false;      // (the list does not survive a new rollout shape)
     return 0;
 }
 
@@ -2291,12 +2329,45 @@ static int enqueue_observe(ppo_handle* h, int t) {
     return 0;
 }
 
-static int enqueue_finish(ppo_handle* h, float gamma, float lam) {
+// tval: the [T,E] terminal values of the rollout's time-limit truncations (enqueue_truncations), or null = none were marked
+static int enqueue_finish(ppo_handle* h, float gamma, float lam, const float* tval = nullptr) {
     StepArgs a{};
     a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.value = h->last_val; a.nz = obs_norm(h); a.n = h->E;
     if (launch_step(h, a)) return -1;
     ProfScope ps(h, PK_GAE);
-    launch_gae(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, h->T, h->E, gamma, lam, h->ro_ret);
+    if (tval) launch_gae_trunc(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, tval, h->T, h->E, gamma, lam, h->ro_ret);
+    else launch_gae(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, h->T, h->E, gamma, lam, h->ro_ret);
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
+// The marked truncations of this rollout -> ro_tval.  Runs behind the last transition's bookkeeping, so the K raw terminal observations are scaled and
+// clipped with the observation statistics as they stand at the finish -- like the end-of-rollout bootstrap observation, and like it through the step
+// machinery's input staging, which never updates the statistics.  One H2D copy of [K * O observations | K row indices], the table zeroed by a kernel, a value-only
+// pass over the K rows with the handle's own step kernels (whichever family it uses), the values scattered to their rows.
+static int enqueue_truncations(ppo_handle* h) {
+    const size_t K = (size_t)h->tr_K, O = (size_t)h->net.O, B = (size_t)h->E * h->T;
+    if (!h->ro_tval && dev_alloc(h, &h->ro_tval, B)) return -1;
+    const size_t words = K * O + 2 * K;                            // observations | indices | values
+    if (words > h->tr_dev_cap) { if (dev_alloc(h, &h->tr_dev, 2 * words)) return -1; h->tr_dev_cap = 2 * words; }
+    memcpy(h->tr_pin + K * O, h->tr_idx.data(), K * sizeof(int));   // (tr_cap * (O + 1) words hold K * O + K)
+    HIP_OK(h, hipMemcpyAsync(h->tr_dev, h->tr_pin, (K * O + K) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const int* idx_dev = (const int*)(h->tr_dev + K * O);
+    float* val_dev = h->tr_dev + K * O + K;
+    {
+        ProfScope ps(h, PK_GAE);
+        hipLaunchKernelGGL(fill_zero_kernel, dim3((unsigned)std::min<size_t>((B + 255) / 256, 1024)), dim3(256), 0, h->stream, h->ro_tval, B);
+        HIP_OK(h, hipGetLastError());
+    }
+    const size_t chunk = h->cfg.max_rows > 0 ? (size_t)h->cfg.max_rows : 65536;
+    for (size_t k0 = 0; k0 < K; k0 += chunk) {
+        StepArgs a{};
+        a.theta = h->theta; a.par = h->par; a.obs = h->tr_dev + k0 * O; a.value = val_dev + k0; a.nz = obs_norm(h); a.n = (int)std::min(chunk, K - k0);
+        if (launch_step(h, a)) return -1;
+    }
+    ProfScope ps(h, PK_GAE);
+    ++h->kv[KV_TVAL_SCATTER];
+    hipLaunchKernelGGL(tval_scatter_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, val_dev, idx_dev, (int)K, (int)B, h->ro_tval);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -2438,6 +2509,7 @@ int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
     if (host_quiesce(h)) return -1;                             // (a transition observed before the reset is still booked, as on the general path)
     if (h->pin_in_busy) HIP_OK(h, hipStreamSynchronize(h->stream));
     h->pin_in_busy = false; h->host_pending = false; h->hp_posted = 0;
+    trunc_clear(h);
     if (h->pin_flag) { __atomic_store_n(hp_ctl(h) + PCTL_H2D, 0u, __ATOMIC_RELEASE); __atomic_store_n(hp_ctl(h) + PCTL_D2H, 0u, __ATOMIC_RELEASE); vram_word(h, 0u); }
     memcpy(h->pin_in, raw_obs, on * sizeof(float));
     HIP_OK(h, hipMemcpyAsync(h->raw_obs, h->pin_in, on * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -2452,6 +2524,7 @@ int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
 int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions_out) {
     if (!h->E || t < 0 || t >= h->T) return fail(h, "ppo_rollout_act: bad step %d", t);
     ENTER(h);
+    h->obs_t = -1;                                               // (the pinned mirror no longer vouches for the last transition's dones)
     const NetDev& n = h->net;
     const size_t cnt = (size_t)h->E * h->Aw;                 // actions out; the noise is [E, A]
     float* nd = nullptr;
@@ -2576,6 +2649,7 @@ int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const fl
     memcpy(h->pin_in, raw_obs, on * sizeof(float));
     memcpy(h->pin_in + on, raw_rew, E * sizeof(float));
     memcpy(h->pin_in + on + E, dones, E * sizeof(float));
+    h->obs_t = t;
     if (host_small(h) && h->host_proto) {                       // the (next or resident) launch reads the block in place
         h->host_pending = true; h->host_pending_t = t; h->hp_posted = t + 1;
         if (h->vram_in) { memcpy(h->vram_in, h->pin_in, (on + 2 * E) * sizeof(float)); vram_word(h, (unsigned)(t + 1)); }      // (posted writes; the data first)
@@ -2603,11 +2677,49 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
         va.obs = h->ro_obs; va.value = h->ro_val; va.n = h->E * h->T; va.nz = no_norm();
         if (launch_step(h, va)) return -1;
     }
-    if (enqueue_finish(h, gamma, lam) || bf16_chain_err_async(h)) return -1;
+    const bool marks = h->tr_K > 0;                                 // none: the launches of a rollout without time limits, nothing else
+    if (marks && enqueue_truncations(h)) { trunc_clear(h); return -1; }
+    h->tval_live = marks;
+    trunc_clear(h);
+    if (enqueue_finish(h, gamma, lam, marks ? h->ro_tval : nullptr) || bf16_chain_err_async(h)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     prof_collect(h);
     if (bf16_chain_err_test(h)) return -1;
     return peer_check(h);
+}
+
+// A host-only call: it appends to the handle's list and enqueues nothing, whichever rollout form serves the handle (a resident kernel keeps running).
+int ppo_rollout_mark_truncated(ppo_handle* h, int32_t t, int32_t count, const int32_t* env_ids, const float* terminal_raw_obs) {
+    if (!h) return fail(nullptr, "ppo_rollout_mark_truncated: null handle");
+    if (!h->E) return fail(h, "ppo_rollout_mark_truncated: call ppo_rollout_alloc first");
+    if (count < 0) return fail(h, "ppo_rollout_mark_truncated: negative count");
+    if (t < 0 || t >= h->T) return fail(h, "ppo_rollout_mark_truncated: bad step %d", t);
+    if (count == 0) return 0;
+    if (t != h->obs_t) return fail(h, "ppo_rollout_mark_truncated: step %d is not the step of the last ppo_rollout_observe (call it after observe(t) and before the next act)", t);
+    if (!env_ids || !terminal_raw_obs) return fail(h, "ppo_rollout_mark_truncated: null argument");
+    ENTER(h);
+    const size_t E = h->E, O = h->net.O;
+    const float* dones = h->pin_in + E * O + E;                     // the pinned mirror still holds step t's transition: obs | rewards | dones
+    // validate everything first: an error leaves the list as it was
+    for (int k = 0; k < count; ++k) {
+        const int e = env_ids[k];
+        if (e < 0 || e >= (int)E) return fail(h, "ppo_rollout_mark_truncated: env id %d out of range", e);
+        if (h->tr_mark[(size_t)t * E + e]) return fail(h, "ppo_rollout_mark_truncated: step %d of env %d is already marked", t, e);
+        for (int j = 0; j < k; ++j) if (env_ids[j] == e) return fail(h, "ppo_rollout_mark_truncated: env %d named twice", e);
+        if (dones[e] == 0.f) return fail(h, "ppo_rollout_mark_truncated: env %d did not end its episode in step %d (done is 0)", e, t);
+    }
+    const size_t need = (size_t)h->tr_K + count;
+    if (need > h->tr_cap) {                                         // grow the pinned block (no copy out of it is in flight: ppo_rollout_finish synchronises before it returns)
+        const size_t cap = std::max<size_t>(std::max<size_t>(2 * h->tr_cap, need), 64);
+        float* p = nullptr;
+        HIP_OK(h, hipHostMalloc((void**)&p, cap * (O + 1) * sizeof(float), hipHostMallocDefault));
+        if (h->tr_pin) { memcpy(p, h->tr_pin, (size_t)h->tr_K * O * sizeof(float)); (void)hipHostFree(h->tr_pin); }
+        h->tr_pin = p; h->tr_cap = cap;
+    }
+    memcpy(h->tr_pin + (size_t)h->tr_K * O, terminal_raw_obs, (size_t)count * O * sizeof(float));
+    for (int k = 0; k < count; ++k) { const int i = t * (int)E + env_ids[k]; h->tr_idx.push_back(i); h->tr_mark[(size_t)i] = 1; }
+    h->tr_K = (int)need;
+    return 0;
 }
 
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first, const float* noise, float gamma, float lam) {
@@ -2768,6 +2880,14 @@ static float* rollout_field(ppo_handle* h, int field, size_t* count) {
 int ppo_rollout_download(ppo_handle* h, int field, float* dst, int64_t count) {
     ENTER_Q(h);
     size_t c = 0;
+    if (h->E && field == 7) {                                       // the terminal values the last ppo_rollout_finish used; zeros when it had no marks
+        c = (size_t)h->E * h->T;
+        if ((size_t)count != c) return fail(h, "ppo_rollout_download: bad field/count");
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        if (h->tval_live) HIP_OK(h, hipMemcpy(dst, h->ro_tval, c * sizeof(float), hipMemcpyDeviceToHost));
+        else memset(dst, 0, c * sizeof(float));
+        return 0;
+    }
     float* p = h->E ? rollout_field(h, field, &c) : nullptr;
     if (!p || (size_t)count != c) return fail(h, "ppo_rollout_download: bad field/count");
     HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -2778,6 +2898,7 @@ int ppo_rollout_download(ppo_handle* h, int field, float* dst, int64_t count) {
 int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count) {
     ENTER_Q(h);
     size_t c = 0;
+    if (field == 7) return fail(h, "ppo_rollout_upload: field 7 (terminal values) is an output of ppo_rollout_finish");
     float* p = h->E ? rollout_field(h, field, &c) : nullptr;
     if (!p || (size_t)count != c) return fail(h, "ppo_rollout_upload: bad field/count");
     HIP_OK(h, hipStreamSynchronize(h->stream));

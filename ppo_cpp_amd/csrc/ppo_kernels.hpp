@@ -14,6 +14,7 @@
 //   adam_kernel          global-norm clip + TF-1.14 ApplyAdam           G:23738-25392, 25426-25704, 30430-31383
 //   epoch_prepare_kernel shuffle -> gather index, advantage statistics  ppo2/ppo2.hpp:274-307, 401-406
 //   gae_kernel           GAE(lambda) / returns scan                     ppo2/runner.hpp:159-191
+//   gae_trunc_kernel     ... with the value bootstrap at time-limit truncations (+ gae_long_trunc_kernel, tval_scatter_kernel); no reference counterpart
 //   running_stats_kernel / reward_norm_kernel  VecNormalize numerics    env/env_normalize.hpp:64-116,
 //                                                                       common/running_statistics.hpp:26-104
 //   seeded_env_kernel    on-device synthetic env (bench / parity data)  stands in for env/env_mock.hpp
@@ -2353,6 +2354,78 @@ __global__ __launch_bounds__(GAE_LONG_THREADS) void gae_long_kernel(const float*
     }
     __syncthreads();
     for (int t = threadIdx.x; t < T; t += GAE_LONG_THREADS) returns[(size_t)t * E + e] = s_delta[t];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// GAE with a value bootstrap at time-limit truncations (no reference counterpart: Runner::set_returns treats every done as
+// terminal).  tv [T,E] holds V(terminal observation) on the rows whose step was cut by a time limit and 0 elsewhere; the reward of
+// such a row becomes rewards + gamma tv, everything else -- nnt = 1 - done, so the lambda trace is still cut at the episode
+// boundary -- is the scan above:
+//   delta_t = (rewards[t] + gamma tv[t]) + gamma V[t+1] (1 - done[t+1]) - V[t]
+// Sibling kernels rather than a template flag on the two above: those keep their code and their names, bit for bit.  With tv == 0
+// the results equal theirs (x + gamma * 0 == x for every finite x, -0 aside).
+// ------------------------------------------------------------------------------------------------------------
+__global__ void gae_trunc_kernel(const float* rewards, const float* values, const float* dones, const float* last_values,
+                                 const float* last_dones, const float* tv, int T, int E, float gamma, float lam, float* returns) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    float last = 0.f;
+    float nv = last_values[e];
+    float nnt = 1.0f - last_dones[e];
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t i = (size_t)t * E + e;
+        const float v = values[i];
+        const float delta = (rewards[i] + gamma * tv[i]) + gamma * (nv * nnt) - v;
+        last = delta + (gamma * lam) * (nnt * last);
+        returns[i] = last + v;
+        nv = v;
+        nnt = 1.0f - dones[i];
+    }
+}
+
+// ... and the LDS form: the bootstrap term is folded into s_delta[t] in the parallel phase, so the serial lane and the 3T floats of LDS are gae_long_kernel's
+__global__ __launch_bounds__(GAE_LONG_THREADS) void gae_long_trunc_kernel(const float* rewards, const float* values, const float* dones, const float* last_values,
+                                                                         const float* last_dones, const float* tv, int T, int E, float gamma, float lam, float* returns) {
+    extern __shared__ __attribute__((aligned(16))) float gl_lds[];
+    float* s_delta = gl_lds; float* s_nnt = gl_lds + T; float* s_v = gl_lds + 2 * T;
+    const int e = blockIdx.x;
+    for (int t = threadIdx.x; t < T; t += GAE_LONG_THREADS) {
+        const size_t i = (size_t)t * E + e;
+        const float v = values[i];
+        const float nv = t == T - 1 ? last_values[e] : values[i + E];
+        const float nnt = 1.0f - (t == T - 1 ? last_dones[e] : dones[i + E]);
+        s_delta[t] = (rewards[i] + gamma * tv[i]) + gamma * (nv * nnt) - v;
+        s_nnt[t] = nnt; s_v[t] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float last = 0.f;
+        const float gl = gamma * lam;
+        int t = T - 1;
+        for (; t >= 7; t -= 8) {
+            float d[8], n[8], v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { d[k] = s_delta[t - k]; n[k] = s_nnt[t - k]; v[k] = s_v[t - k]; }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { last = d[k] + gl * (n[k] * last); s_delta[t - k] = last + v[k]; }
+        }
+        for (; t >= 0; --t) { last = s_delta[t] + gl * (s_nnt[t] * last); s_delta[t] = last + s_v[t]; }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += GAE_LONG_THREADS) returns[(size_t)t * E + e] = s_delta[t];
+}
+
+// the [T,E] table of terminal values: zeroed by a kernel on the stream (the library's rule: no memset command between its launches), then
+// the K values of the batched value pass scattered to their rollout rows, one lane per k.  idx[k] = t * E + e, checked on the host when the
+// row was marked (in range, no row twice); the guard below only keeps a corrupted index from leaving the table.
+__global__ void fill_zero_kernel(float* p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.f;
+}
+__global__ void tval_scatter_kernel(const float* val, const int* idx, int K, int n, float* tval) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const int i = idx[k];
+    if (i >= 0 && i < n) tval[i] = val[k];
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,10 @@
 //                  hexapod's reward curves); this is the environment behind tests/test_learning.py, small enough for the oracle.
 //   DiscreteTargetEnv  the same on a DISCRETE action space (SPACE_DISCRETE, A categories; an action is [1,1] = the category index):
 //                  reward 1 when a == argmax_j (W obs)_j with TargetEnv's W, 0 otherwise; episodes of a fixed length (tests/test_discrete_policy.py).
+//   UnitRewardEnv  SeededEnvMock's observation stream, reward 1 on every step, never done by itself: behind a TimeLimit every episode ends by truncation, and
+//                  the value of every state is 1 / (1 - gamma) -- which a critic only learns when the value is bootstrapped there (tests/test_truncation.py).
+//                  reset() does NOT rewind the stream (it moves one draw on): no observation ever comes twice, so nothing tells a critic how far the
+//                  episode has come, and the observation an episode ends on is a draw like any other.
 #pragma once
 #include <cstdint>
 
@@ -188,4 +192,33 @@ private:
     uint64_t key_;
     int kDim, kAct, len_;
     std::vector<float> w_;          // [category][obs], row-major
+};
+
+class UnitRewardEnv : public Env {
+public:
+    UnitRewardEnv(uint32_t seed, uint32_t env_id, int obs_dim = 18, int act_dim = 18) : step_(0), key_(ppo_detail::ctr_key(seed, env_id)), kDim(obs_dim), kAct(act_dim) {}
+    std::string get_action_space() override { return Env::SPACE_CONTINOUS; }
+    std::string get_observation_space() override { return Env::SPACE_CONTINOUS; }
+    int get_action_space_size() override { return kAct; }
+    int get_observation_space_size() override { return kDim; }
+    Mat reset() override { ++step_; return obs_at(step_); }
+    std::vector<Mat> step(const Mat& /*actions*/) override {
+        ++step_;
+        std::vector<Mat> out;
+        out.reserve(3);
+        out.push_back(obs_at(step_)); out.push_back(Mat::Ones(1, 1)); out.push_back(Mat::Zero(1, 1));
+        return out;
+    }
+    Mat get_original_obs() override { return obs_at(step_); }
+    Mat get_original_rew() override { return Mat::Ones(1, 1); }
+    void serialize(nlohmann::json&) override {}
+    void deserialize(nlohmann::json&) override {}
+    void render() override {}
+    float get_time() override { return 0.f; }
+
+private:
+    Mat obs_at(uint32_t step) const { Mat m(1, kDim); for (int j = 0; j < kDim; ++j) m(0, j) = ppo_detail::sym_unit(ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)j)); return m; }
+    uint32_t step_;
+    uint64_t key_;
+    int kDim, kAct;
 };

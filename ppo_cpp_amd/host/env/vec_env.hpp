@@ -33,6 +33,7 @@
 #endif
 
 #include "env.hpp"
+#include "time_limit.hpp"
 
 // CPUs this process may actually use: hardware threads, narrowed by the affinity mask and by the cgroup CPU quota
 // (a container often sees every core of the host but is throttled to a few; a worker per visible core then only
@@ -62,7 +63,9 @@ inline int usable_cpus() {
     return n;
 }
 
-class VecEnv : public virtual Env {
+// Time-limit truncations (time_limit.hpp): children that carry the ITimeLimit mixin (a TimeLimit wrapper, say) are asked after every step; get_truncated() /
+// get_terminal_obs() gather their answers in environment order, children without the mixin report 0.
+class VecEnv : public virtual Env, public ITimeLimit {
 public:
     explicit VecEnv(const std::vector<std::shared_ptr<Env>>& envs, int max_workers = 0)
         : envs_(envs), n_(static_cast<int>(envs.size())), generation_(0), terminate_(false), actions_(nullptr),
@@ -70,6 +73,10 @@ public:
         assert(!envs.empty());
         const int hw = usable_cpus();
         workers_ = std::max(1, std::min(n_, max_workers > 0 ? max_workers : hw));
+        tl_.resize(n_, nullptr);
+        for (int i = 0; i < n_; ++i) if ((tl_[i] = dynamic_cast<ITimeLimit*>(envs_[i].get()))) any_tl_ = true;
+        truncated_ = Mat::Zero(n_, 1);
+        if (any_tl_) terminal_obs_ = Mat::Zero(n_, obs_dim_);
         // first guess: 8 chunks per thread; recalibrated from measured time per environment after the first steps
         chunk_ = std::max(1, n_ / (8 * workers_));
         per_.reset(new PerThread[workers_]);
@@ -131,6 +138,10 @@ public:
 
     Mat get_original_obs() override { std::cout << "VecEnv::get_original_obs() not implemented\n"; return Mat::Zero(n_, get_observation_space_size()); }
     Mat get_original_rew() override { return original_rewards_; }
+    // of the last step(); all zeros when no child has a time limit
+    Mat get_truncated() override { return truncated_; }
+    Mat get_terminal_obs() override { return any_tl_ ? terminal_obs_ : Mat::Zero(n_, obs_dim_); }
+    bool has_time_limit() override { return any_tl_; }
     void serialize(nlohmann::json&) override {}
     void deserialize(nlohmann::json&) override {}
     void render() override { std::cout << "VecEnv::render() not implemented\n"; }
@@ -205,6 +216,11 @@ private:
                     rewards_(i, 0) = res[1](0, 0);
                     dones_(i, 0) = res[2](0, 0);
                     original_rewards_(i, 0) = envs_[i]->get_original_rew()(0, 0);
+                    if (tl_[i]) {                                    // (rows of their own: no two threads share one)
+                        const bool tr = res[2](0, 0) != 0.f && tl_[i]->get_truncated()(0, 0) != 0.f;
+                        truncated_(i, 0) = tr ? 1.f : 0.f;
+                        if (tr) { const Mat to = tl_[i]->get_terminal_obs(); mat_set_row(terminal_obs_, i, to.data()); }
+                    }
                 }
             }
             // this chunk's share is published BEFORE the decrement that may end the round: the caller reads the shares (calibrate, pool_active) after it
@@ -291,6 +307,9 @@ private:
     const Mat* actions_;
     const int obs_dim_;
     Mat observations_, rewards_, dones_, original_rewards_;
+    std::vector<ITimeLimit*> tl_;      // per child: its time-limit mixin, or null
+    bool any_tl_ = false;
+    Mat truncated_, terminal_obs_;     // [n, 1], [n, obs] of the last step
     int workers_ = 1, chunk_ = 1, n_chunks_ = 1, steps_ = 0;
     Mode mode_ = RESET;
     // the two words every thread hammers live on cache lines of their own; so does each thread's share record

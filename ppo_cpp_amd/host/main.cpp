@@ -16,6 +16,7 @@
 
 #include "env/env_mock.hpp"
 #include "env/env_normalize.hpp"
+#include "env/time_limit.hpp"
 #include "env/vec_env.hpp"
 #include "ppo2/dist.hpp"
 #include "ppo2/graph_spec.hpp"
@@ -35,9 +36,9 @@ const char* kAliases[][2] = {{"-d", "dir"}, {"--dir", "dir"}, {"-p", "path"}, {"
                              {"-j", "threads"}, {"--threads", "threads"}, {"--jobs", "threads"}, {"--num_threads", "threads"}, {"--hidden", "hidden"},
                              {"--minibatches", "minibatches"}, {"--seed", "seed"}, {"-g", "graph"}, {"--graph", "graph"}, {"--graph_path", "graph"}, {"--obs", "obs"},
                              {"--ranks", "ranks"}, {"--rank", "rank"}, {"--world", "world"}, {"--ctl_fd", "ctl_fd"}, {"--devices", "devices"}, {"--collective", "collective"},
-                             {"--explicit_dir", "explicit_dir"}, {"--dump_dir", "dump_dir"}};
+                             {"--explicit_dir", "explicit_dir"}, {"--dump_dir", "dump_dir"}, {"--time_limit", "time_limit"}};
 const char* kSwitches[][2] = {{"-r", "resume"}, {"--resume", "resume"}, {"-v", "verbose"}, {"--verbose", "verbose"}, {"--seeded", "seeded"},
-                              {"--replica_saves", "replica_saves"}, {"--ctl_selftest", "ctl_selftest"}};
+                              {"--replica_saves", "replica_saves"}, {"--ctl_selftest", "ctl_selftest"}, {"--no_bootstrap_truncated", "no_bootstrap_truncated"}};
 
 // raw little-endian arrays: the parity hooks' on-disk format (--explicit_dir / --dump_dir; tests/test_host_dp.py writes and reads them with numpy)
 template <typename T>
@@ -69,7 +70,10 @@ int main(int argc, char** argv) {
                         "                   [--minibatches N]\n"
                         "                   [--hidden 256,256] [--saves N --dir DIR --id ID] [--path CKPT_PREFIX] [--resume] [--seeded] [--seed N]\n"
                         "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n"
-                        "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n");
+                        "                   [--time_limit N] [--no_bootstrap_truncated]\n"
+                        "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n"
+                        "  --time_limit N: every environment ends its episodes after N steps (a TimeLimit wrapper); the value is bootstrapped at those truncations\n"
+                        "  --no_bootstrap_truncated: treat them as terminal states instead (the reference's behaviour)\n");
             return 0;
         }
         for (auto& al : kAliases) if (a == al[0] && i + 1 < argc) { f.kv[al[1]] = argv[++i]; ok = true; break; }
@@ -158,14 +162,18 @@ int main(int argc, char** argv) {
         }
         const bool peer = ctx.init_handle(h, f.str("collective", "rccl") == "peer");                  // before the normaliser and the rollout buffers exist
         if (f.str("collective", "rccl") == "peer" && ctx.world > 1 && !peer) throw std::runtime_error("--collective peer: the peer exchange's probe failed");
+        const int time_limit = (int)f.num("time_limit", 0);                     // --time_limit N: every environment behind a TimeLimit(N)
+        if (f.has("time_limit") && time_limit < 1) throw std::runtime_error("--time_limit: expected a positive number of steps");
+        auto bare_env = [&](int i) -> std::shared_ptr<Env> {
+            if (f.has("seeded")) return std::make_shared<SeededEnvMock>(1234u, (uint32_t)(env0 + i), obs_dim, 18);
+            return std::make_shared<EnvMock>(env0 + i + 1);
+        };
         std::vector<std::shared_ptr<Env>> envs;
-        for (int i = 0; i < n_envs; ++i) {
-            if (f.has("seeded")) envs.push_back(std::make_shared<SeededEnvMock>(1234u, (uint32_t)(env0 + i), obs_dim, 18));
-            else envs.push_back(std::make_shared<EnvMock>(env0 + i + 1));
-        }
+        for (int i = 0; i < n_envs; ++i) envs.push_back(time_limit > 0 ? std::shared_ptr<Env>(std::make_shared<TimeLimit>(bare_env(i), time_limit)) : bare_env(i));
         std::unique_ptr<Env> inner;
         // (the pool sizes itself by the cores this process may use; N ranks on one node share them)
         if (n_envs > 1) inner.reset(new VecEnv(envs, ctx.world > 1 ? std::max(1, usable_cpus() / ctx.world) : 0));          // ppo2.cpp:188-201
+        else if (time_limit > 0) inner.reset(new TimeLimit(bare_env(0), time_limit));
         else inner.reset(f.has("seeded") ? static_cast<Env*>(new SeededEnvMock(1234u, (uint32_t)env0, obs_dim, 18)) : static_cast<Env*>(new EnvMock(env0 + 1)));
         EnvNormalize env{std::move(inner), h, training};                          // ppo2.cpp:207
         PPO2 algorithm{h, env, 0.99f, n_steps, cfg.ent_coef, (float)f.num("lr", 1e-3), 0.5f, 0.5f, 0.95f, (int)f.num("minibatches", 32),
@@ -173,6 +181,7 @@ int main(int argc, char** argv) {
         algorithm.seed = (unsigned long long)f.num("seed", 0);
         algorithm.set_distributed(ctx.world, ctx.rank);
         algorithm.replica_saves = f.has("replica_saves");
+        algorithm.bootstrap_truncated = !f.has("no_bootstrap_truncated");
         if (f.has("path")) algorithm.load(f.str("path", ""));
         if (training) {
             const int steps = (int)f.num("steps", 2e7);

@@ -43,6 +43,12 @@ public:
         check(ppo_gae(h_, rewards.data(), values.data(), dones.data(), last_values.data(), last_dones.data(), static_cast<int>(rewards.rows()),
                       static_cast<int>(rewards.cols()), gamma, lam, returns.data()), "gae");
     }
+    // ... with the value bootstrap at time-limit truncations: terminal_values [T,E] = V(terminal observation) on the truncated rows, 0 elsewhere (ppo_gae_ex)
+    virtual void gae_truncated(const Mat& rewards, const Mat& values, const Mat& dones, const Mat& last_values, const Mat& last_dones, const Mat& terminal_values,
+                               float gamma, float lam, Mat& returns) {
+        check(ppo_gae_ex(h_, rewards.data(), values.data(), dones.data(), last_values.data(), last_dones.data(), terminal_values.data(),
+                         static_cast<int>(rewards.rows()), static_cast<int>(rewards.cols()), gamma, lam, returns.data()), "gae");
+    }
     ppo_handle* handle() const { return h_; }
 
 protected:

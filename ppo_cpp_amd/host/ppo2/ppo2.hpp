@@ -54,6 +54,9 @@ public:
     std::vector<std::pair<int, float>>& episode_rewards() { return episodes_; }
     bool quiet = false;
     unsigned long long seed = 0;
+    // An Env that carries the ITimeLimit mixin (env/time_limit.hpp) reports which dones were time-limit truncations: the value is then bootstrapped at those
+    // steps (ppo_rollout_mark_truncated / ppo_gae_ex).  false: every done is a terminal state, as in the reference.  An Env without the mixin is not affected.
+    bool bootstrap_truncated = true;
     // parity runs (tests): explicit exploration noise [n_updates][n_steps][n_envs][A] and epoch permutations
     // [n_updates][noptepochs][n_batch] (out.row(perm[i]) = in.row(i), ppo2.hpp:291-296) replace the generators of both loops
     const float* explicit_noise = nullptr;
@@ -184,6 +187,10 @@ private:
         // the logger's env-major [E, T] views are filled once per update from time-major rows (a row per env step is one copy; writing a
         // column of an [E, T] matrix touches E cache lines)
         Mat actions(E, act_model_.action_width()), rew_view(E, T), done_view(E, T), rew_tm(T, E), done_tm(T, E), dones = Mat::Zero(E, 1);
+        ITimeLimit* tl = bootstrap_truncated ? dynamic_cast<ITimeLimit*>(&raw) : nullptr;
+        if (tl && !tl->has_time_limit()) tl = nullptr;
+        std::vector<int32_t> tr_ids; std::vector<float> tr_obs;
+        const int O = raw.get_observation_space_size();
         for (int update = 1; update <= n_updates; ++update) {
             const auto t0 = clk::now();
             for (int t = 0; t < T; ++t) {
@@ -195,6 +202,17 @@ private:
                 std::vector<Mat> r = raw.step(actions);
                 const auto p2 = clk::now();
                 check(ppo_rollout_observe(h_, t, r[0].data(), r[1].data(), r[2].data()));
+                if (tl) {                                                   // time-limit truncations of this step: (env, raw terminal observation) -> the handle's list
+                    const Mat tr = tl->get_truncated();
+                    tr_ids.clear();
+                    for (int e = 0; e < E; ++e) if (tr(e, 0) != 0.f && r[2](e, 0) != 0.f) tr_ids.push_back(e);
+                    if (!tr_ids.empty()) {
+                        const Mat to = tl->get_terminal_obs();
+                        tr_obs.resize(tr_ids.size() * (size_t)O);
+                        for (size_t k = 0; k < tr_ids.size(); ++k) std::memcpy(tr_obs.data() + k * O, mat_row_ptr(to, tr_ids[k]), sizeof(float) * (size_t)O);
+                        check(ppo_rollout_mark_truncated(h_, t, (int32_t)tr_ids.size(), tr_ids.data(), tr_obs.data()));
+                    }
+                }
                 const auto p3 = clk::now();
                 if (update > 2) { phase_act_ms += ms(p0, p1); phase_env_ms += ms(p1, p2); phase_observe_ms += ms(p2, p3); }
                 dones = std::move(r[2]);
@@ -218,6 +236,7 @@ private:
 
     void learn_reference_loop(int n_updates) {
         Runner runner{env_, act_model_, n_steps_, gamma_, lam_};
+        runner.bootstrap_truncated = bootstrap_truncated;
         std::mt19937& rng = shuffle_rng_;                           // (a member: reset only when the seed changes, see learn())
         const int batch_size = n_batch_ / nminibatches_;
         for (int update = 1; update <= n_updates; ++update) {

@@ -8,6 +8,8 @@
 #include <memory>
 
 #include "../env/env.hpp"
+#include "../env/env_normalize.hpp"
+#include "../env/time_limit.hpp"
 #include "policies.hpp"
 
 struct MiniBatch {
@@ -20,7 +22,10 @@ class Runner {
 public:
     Runner(Env& env, MlpPolicy& model, int n_steps, float gamma, float lam)
         : env_(env), model_(model), n_steps_(n_steps), gamma_(gamma), lam_(lam), obs_(env.reset()), num_envs_(env.get_num_envs()),
-          dones_(Mat::Zero(num_envs_, 1)) {}
+          dones_(Mat::Zero(num_envs_, 1)) {
+        ITimeLimit* tl = dynamic_cast<ITimeLimit*>(&env_);
+        tl_ = tl && tl->has_time_limit() ? tl : nullptr;
+    }
 
     MiniBatch run() {
         // A: width of the exploration noise (action dimensions or categories); W: columns of an action (A, or 1 for a category index)
@@ -28,6 +33,7 @@ public:
         // time-major staging [T, E, .]
         std::vector<float> obs((size_t)T * E * O), act((size_t)T * E * W);
         Mat values(T, E), neglogp(T, E), dones(T, E), rewards(T, E), raw_rewards(T, E);
+        std::vector<int> trunc_rows; std::vector<float> trunc_obs;
         for (int t = 0; t < T; ++t) {
             std::memcpy(&obs[(size_t)t * E * O], obs_.data(), sizeof(float) * (size_t)E * O);
             Mat eps;                                                       // explicit exploration noise of this env step [E, A], if any
@@ -44,11 +50,33 @@ public:
             dones_ = r[2];
             mat_set_row(rewards, t, r[1].data());
             mat_set_row(raw_rewards, t, env_.get_original_rew().data());
+            if (tl_ && bootstrap_truncated) {                                   // time-limit truncations of this step: keep (row, terminal observation)
+                const Mat tr = tl_->get_truncated();
+                bool any = false;
+                for (int e = 0; e < E; ++e) any = any || (tr(e, 0) != 0.f && dones_(e, 0) != 0.f);
+                if (any) {
+                    Mat to = tl_->get_terminal_obs();
+                    // an EnvNormalize hands the observation over raw: scale it as the policy's inputs are scaled (current statistics, no update)
+                    if (EnvNormalize* nz = dynamic_cast<EnvNormalize*>(&env_)) to = nz->normalize_terminal(to);
+                    for (int e = 0; e < E; ++e)
+                        if (tr(e, 0) != 0.f && dones_(e, 0) != 0.f) { trunc_rows.push_back(t * E + e); trunc_obs.insert(trunc_obs.end(), mat_row_ptr(to, e), mat_row_ptr(to, e) + O); }
+                }
+            }
         }
         // set_returns (runner.hpp:159-191): bootstrap value of the observation after the last step, GAE on the device
         const Mat last_values = model_.value(obs_);
         Mat returns(T, E);
-        model_.gae(rewards, values, dones, last_values, dones_, gamma_, lam_, returns);
+        if (trunc_rows.empty()) model_.gae(rewards, values, dones, last_values, dones_, gamma_, lam_, returns);
+        else {
+            // one value pass over the terminal rows (the weights the rollout was collected with), scattered into [T,E]; the truncation form of GAE
+            const int K = (int)trunc_rows.size();
+            Mat tobs(K, O);
+            std::memcpy(tobs.data(), trunc_obs.data(), sizeof(float) * (size_t)K * O);
+            const Mat tv = model_.value(tobs);
+            Mat tval = Mat::Zero(T, E);
+            for (int k = 0; k < K; ++k) tval.data()[trunc_rows[k]] = tv(k, 0);
+            model_.gae_truncated(rewards, values, dones, last_values, dones_, tval, gamma_, lam_, returns);
+        }
         MiniBatch mb;
         mb.obs = flatten(obs.data(), T, E, O);
         mb.actions = flatten(act.data(), T, E, W);
@@ -64,6 +92,8 @@ public:
     // parity runs: [n_steps, n_envs, A] standard-normal draws used instead of the on-device generator (the reference draws from
     // TF's RandomStandardNormal with seed 0, G:5894, i.e. it is not reproducible; SURVEY 7 "noise is an explicit input")
     const float* noise = nullptr;
+    // bootstrap the value at time-limit truncations when the Env carries the ITimeLimit mixin (env/time_limit.hpp); false: every done is terminal, as in the reference
+    bool bootstrap_truncated = true;
 
     const Mat& current_obs() const { return obs_; }
     const Mat& current_dones() const { return dones_; }
@@ -84,4 +114,5 @@ private:
     Mat obs_;
     int num_envs_;
     Mat dones_;
+    ITimeLimit* tl_ = nullptr;
 };

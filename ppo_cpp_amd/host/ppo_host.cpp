@@ -9,6 +9,7 @@
 
 #include "env/env_mock.hpp"
 #include "env/env_normalize.hpp"
+#include "env/time_limit.hpp"
 #include "env/vec_env.hpp"
 #include "ppo2/checkpoint.hpp"
 #include "ppo2/graph_spec.hpp"
@@ -338,6 +339,59 @@ int ppo_host_discrete_checkpoint(const char* prefix, const float* obs, int n, fl
 // EnvNormalize -> PPO2; ppo2.cpp:188-250), through the HBM-resident loop or (reference_loop) the literal one: what
 // tests/test_host_layer.py holds against oracle.collect + oracle.update update by update (ppo2.hpp:264-349).
 int ppo_host_learn_explicit(const ppo_host_args* a, const ppo_host_explicit* x, ppo_host_result* out) { return run_learn(a, out, x); }
+
+// The learning check of the time-limit bootstrap (tests/test_truncation.py): n_envs x TimeLimit(UnitRewardEnv, time_limit) -> VecEnv -> EnvNormalize -> PPO2::learn
+// through the HBM-resident loop with the library's own sampling and shuffles (args: n_envs, n_steps, hidden, nminibatches, noptepochs, n_updates, lr, cliprange,
+// gamma, lam, norm_obs, norm_reward, seed, obs_dim, act_dim, cliprange_vf, device; the rest is ignored).  bootstrap = PPO2::bootstrap_truncated.  Afterwards the
+// critic is read on `probe_raw` [n_probe, O] (n_probe a multiple of n_envs), scaled with the final observation statistics: probe_values [n_probe].
+// time_limit <= 0: no wrapper (the environment never ends an episode).  losses_out [n_updates][5] may be null.
+int ppo_host_learn_time_limit(const ppo_host_args* a, int time_limit, int bootstrap, const float* probe_raw, int n_probe, float* probe_values, float* losses_out,
+                              ppo_host_result* out) {
+    std::memset(out, 0, sizeof *out);
+    ppo_handle* h = nullptr;
+    try {
+        ppo_config cfg;
+        const int O = a->obs_dim > 0 ? a->obs_dim : 18, A = a->act_dim > 0 ? a->act_dim : 18;
+        if (n_probe < 0 || n_probe % a->n_envs != 0) throw std::runtime_error("n_probe must be a multiple of n_envs");
+        ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
+        cfg.device = a->device;
+        if (ppo_create(&cfg, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        if (ppo_init_orthogonal(h, a->seed) != 0) throw std::runtime_error(ppo_last_error(h));
+        std::vector<std::shared_ptr<Env>> envs;
+        for (int i = 0; i < a->n_envs; ++i) {
+            std::shared_ptr<Env> e = std::make_shared<UnitRewardEnv>(1234u, (uint32_t)i, O, A);
+            envs.push_back(time_limit > 0 ? std::shared_ptr<Env>(std::make_shared<TimeLimit>(e, time_limit)) : e);
+        }
+        {
+            std::unique_ptr<Env> inner;
+            if (a->n_envs > 1) inner.reset(new VecEnv(envs, a->max_workers));
+            else inner.reset(time_limit > 0 ? static_cast<Env*>(new TimeLimit(std::make_shared<UnitRewardEnv>(1234u, 0u, O, A), time_limit)) : static_cast<Env*>(new UnitRewardEnv(1234u, 0u, O, A)));
+            EnvNormalize env{std::move(inner), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
+            PPO2 algo{h, env, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange, a->cliprange_vf};
+            algo.quiet = true;
+            algo.seed = a->seed;
+            algo.bootstrap_truncated = bootstrap != 0;
+            algo.learn(a->n_updates * a->n_envs * a->n_steps);
+            const auto& hist = algo.history();
+            if (hist.empty()) throw std::runtime_error("no update ran");
+            std::memcpy(out->losses, hist.back().losses, sizeof out->losses);
+            out->fps_last = hist.back().fps;
+            if (losses_out) for (size_t i = 0; i < hist.size(); ++i) std::memcpy(losses_out + 5 * i, hist[i].losses, sizeof(float) * 5);
+            for (int r0 = 0; r0 < n_probe; r0 += a->n_envs) {
+                Mat raw(a->n_envs, O);
+                std::memcpy(raw.data(), probe_raw + (size_t)r0 * O, sizeof(float) * (size_t)a->n_envs * O);
+                const Mat x = env.normalize_terminal(raw);
+                if (ppo_value(h, x.data(), a->n_envs, probe_values + r0) != 0) throw std::runtime_error(ppo_last_error(h));
+            }
+        }
+        ppo_destroy(h);
+        return 0;
+    } catch (const std::exception& e) {
+        std::snprintf(out->error, sizeof out->error, "%s", e.what());
+        if (h) ppo_destroy(h);
+        return -1;
+    }
+}
 
 // PPO2::save of a [64,64] Gaussian policy built with `cliprange_vf` under `prefix` (no training), then PPO2::load into a FRESH handle behind a PPO2 built with the
 // default -1: reports the value clipping that the load left on the fresh handle (ppo_get_value_clip).  Returns 0; -1 = error (message on stderr).

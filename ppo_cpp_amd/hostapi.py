@@ -124,6 +124,34 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     return out
 
 
+def learn_time_limit(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, time_limit, probe_raw, bootstrap_truncated=True, gamma=0.99,
+                     lam=0.95, seed=0, norm_obs=True, norm_reward=False, device=-1, obs_dim=18, act_dim=18, cliprange_vf=-1.0):
+    """PPO2::learn on n_envs x TimeLimit(UnitRewardEnv, time_limit) (reward 1 per step, episodes end by the time limit only) behind VecEnv + EnvNormalize, with the
+    library's own exploration noise and shuffles (ppo_host_learn_time_limit).  bootstrap_truncated = PPO2::bootstrap_truncated.  Returns the critic on
+    probe_raw [n, obs_dim] (n a multiple of n_envs; scaled with the final observation statistics) and the per-update mean losses."""
+    import numpy as np
+    lib = load_host_library()
+    a = HostArgs()
+    a.n_envs, a.n_steps, a.n_hidden = n_envs, n_steps, len(hidden)
+    for i, h in enumerate(hidden):
+        a.hidden[i] = h
+    a.nminibatches, a.noptepochs, a.n_updates = nminibatches, noptepochs, n_updates
+    a.lr, a.cliprange, a.gamma, a.lam = lr, cliprange, gamma, lam
+    a.seeded_env, a.device, a.max_workers, a.reference_loop = 0, device, 0, 0
+    a.norm_obs, a.norm_reward, a.seed = int(norm_obs), int(norm_reward), seed
+    a.obs_dim, a.act_dim = obs_dim, act_dim
+    a.cliprange_vf = cliprange_vf
+    probe = np.ascontiguousarray(probe_raw, np.float32)
+    assert probe.ndim == 2 and probe.shape[1] == obs_dim and probe.shape[0] % n_envs == 0, probe.shape
+    out = {"probe_values": np.zeros(probe.shape[0], np.float32), "losses": np.zeros((n_updates, 5), np.float32)}
+    r = HostResult()
+    fp = C.POINTER(C.c_float)
+    if lib.ppo_host_learn_time_limit(C.byref(a), int(time_limit), int(bool(bootstrap_truncated)), probe.ctypes.data_as(fp), probe.shape[0],
+                                     out["probe_values"].ctypes.data_as(fp), out["losses"].ctypes.data_as(fp), C.byref(r)) != 0:
+        raise RuntimeError(r.error.decode())
+    return out
+
+
 def value_clip_checkpoint(prefix, cliprange_vf):
     """PPO2::save of a policy built with cliprange_vf, PPO2::load into a fresh handle (ppo_host_value_clip_checkpoint): returns the fresh handle's
     value clipping as (mode, range), mode 0 / 1 / 2 = PPO_VCLIP_POLICY / RANGE / OFF"""
