@@ -118,6 +118,39 @@ int ppo_value(ppo_handle* h, const float* obs, int32_t n, float* value);
 /* MlpPolicy::get_deterministic_action (ppo2/policies.hpp:49-62) */
 int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* action);
 
+/* ---- action masks of the categorical head (invalid-action masking; no reference counterpart) ---------------
+ * A mask is one float per (row, category), [n, A]: non-zero = allowed, 0 = forbidden.  For a masked row with logits l and allowed set S:
+ *   forbidden categories are EXCLUDED, not pushed down by a constant:  m = max_{j in S} l_j,  z = sum_{j in S} exp(l_j - m),
+ *   p_j = exp(l_j - m) / z for j in S, p_j = 0 otherwise
+ *   sample         argmax_{j in S} (l_j - log(-log u_j)), lowest index on a tie.  The noise layout [n, A] and the counter draw's keys are unchanged:
+ *                  forbidden categories still own their uniforms, a mask does not shift the draws of the others
+ *   deterministic  argmax_{j in S} l_j
+ *   neglogp        log z - (l_a - m)
+ *   entropy        sum_{j in S} p_j (log z - (l_j - m))
+ *   d logits       d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H) for j in S, exactly 0 otherwise: the pi/w columns and pi/b entries of a category
+ *                  that is forbidden in every row of a minibatch receive a zero gradient
+ *   a row of ones gives the SAME BITS as the unmasked kernels in every output (action, neglogp, value, losses, gradient, weights after Adam): the mask is
+ *   read inside policy_step_kernel / train_fwd_bwd_kernel by the lane that owns the category, the lane loops and butterflies are the unmasked ones.
+ * Errors, checked on the HOST before anything is uploaded (like the category-index check; nothing is trained): a row without an allowed category wherever
+ * the mask comes from the host (the three calls below, ppo_rollout_act_masked, ppo_rollout_upload of field 8), and a ppo_train_step_masked row whose action
+ * its own mask forbids.  ppo_update has no host check: if the rollout's action field was uploaded inconsistently with its mask field, the loss values of
+ * such a row are unspecified (the kernels still read and write inside their buffers and terminate).
+ * The three calls need a categorical handle (a Gaussian or PPO_BF16 handle: an error); mask == NULL is the unmasked call, the same launch. */
+int ppo_step_masked(ppo_handle* h, const float* obs, int32_t n, const float* noise, const float* mask, float* action, float* value,
+                    float* neglogp);
+int ppo_act_deterministic_masked(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* action);
+int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float* obs, const float* actions, const float* mask,
+                          const float* advs, const float* returns, const float* old_neglogp, const float* old_values, int32_t n,
+                          float losses[5]);
+/* Masks in the device-resident rollout: a handle setting (default off; turning it on is an error on a handle that is not categorical).  With it on,
+ * ppo_rollout_alloc also allocates a [T, E, A] mask buffer initialised to ones, the epoch gather copies the mask rows into minibatch order beside the
+ * other fields, and ppo_update runs the masked train kernel over them (ppo_kernel_counts: "policy_step_kernel<cat,mask>", "train_fwd_bwd_kernel<cat,mask>").
+ * CHANGING the setting drops an allocated rollout (and the captured update): rollout calls report "no rollout allocated" until the next ppo_rollout_alloc.
+ * A handle that never turns it on enqueues exactly the launches it enqueued before these entry points existed.  Data parallel: every rank masks and
+ * gathers its own rows, nothing new crosses ranks; ppo_dist_global_shuffle(h, 1) together with masking is refused by ppo_update. */
+int ppo_set_action_masking(ppo_handle* h, int on);
+int ppo_get_action_masking(const ppo_handle* h);
+
 /* ---- train op: PPO2::_train_step's Session::Run (ppo2/ppo2.hpp:430-468) ---------------------------------
  * feeds train_model/input/Ob, loss/{action,advs,rewards,old_neglog_pac,old_vpred,learning_rate,clip_range}_ph;
  * target ppo2/_train; losses = {pg_loss, vf_loss, entropy, approxkl, clipfrac}.  `advs` are ALREADY normalised
@@ -191,6 +224,9 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t n_envs, int32_t n_steps);
  * needed), values[t] are available after ppo_rollout_finish, and a host that pauses only costs the kernel a bounded wait. */
 int ppo_rollout_reset(ppo_handle* h, const float* raw_obs);
 int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions_out);
+/* ppo_rollout_act under an action mask [E, A] (needs ppo_set_action_masking on): the mask is stored in row t of the rollout's mask buffer and the step samples
+ * under it.  mask == NULL, and plain ppo_rollout_act on a masking handle, mean an all-ones row (the unmasked kernel; the row is recorded as ones). */
+int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const float* mask, float* actions_out);
 int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const float* raw_rew, const float* dones);
 /* Time-limit truncations (no reference counterpart).  The `done` of step t of the environments env_ids [count] (int32) was raised by a time limit, not by a
  * terminal state; terminal_raw_obs [count, O] are the RAW observations those episodes ended on (raw_obs of ppo_rollout_observe holds the observation after the
@@ -214,11 +250,13 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam);
  * obs/dones.  noise [T,E,A] or NULL.  Ends with bootstrap + GAE.
  * Categorical handle: noise [T,E,A] (ppo_collect_synthetic) / [E,A] (ppo_rollout_act) are uniforms, actions_out of ppo_rollout_act is [E]. */
 /* Every done of the seeded device env is a terminal state: it has no terminal observation, ppo_rollout_mark_truncated does not apply to this path. */
+/* The seeded device env has no notion of legality either: on a masking handle ppo_collect_synthetic samples unmasked and records every row's mask as ones. */
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first,
                           const float* noise, float gamma, float lam);
 /* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]); a categorical handle's field 1 is [T,E].
  * 7 (download only; an upload is refused): terminal values [T,E] as the last ppo_rollout_finish used them -- V(terminal observation) on the marked rows, 0 elsewhere,
- * all zeros when that finish had no marks. */
+ * all zeros when that finish had no marks.
+ * 8: action masks [T,E,A] of a masking handle (refused with masking off; an uploaded row without an allowed category is refused). */
 int ppo_rollout_download(ppo_handle* h, int field, float* dst, int64_t count);
 int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count);
 

@@ -64,9 +64,14 @@ class PPOHip:
 
     action_dist="categorical": act_dim is the number of categories; actions are (n,) float category indices
     (step / act_deterministic / rollout_act return them, train_step takes them, rollout_get("actions") is [T, E]);
-    explicit noise keeps the Gaussian's shape and holds the uniforms of the Gumbel-argmax draw."""
+    explicit noise keeps the Gaussian's shape and holds the uniforms of the Gumbel-argmax draw.
+
+    Action masks (categorical only; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
+    set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
+    and update() train under them."""
 
     FIELDS = {"obs": 0, "actions": 1, "values": 2, "neglogp": 3, "dones": 4, "rewards": 5, "returns": 6}
+    MASK_FIELDS = {"masks": 8}                  # [T, E, A]; a masking handle only (set_action_masking)
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", **overrides):
@@ -151,10 +156,14 @@ class PPOHip:
         self._ck(self.lib.ppo_set_beta_powers(self.h, _fp(a)))
 
     # ---- act model --------------------------------------------------------------------------------
-    def step(self, obs, noise=None):
+    def step(self, obs, noise=None, mask=None):
         obs = _f32(obs); n = obs.shape[0]
         a = np.empty((n,) + self._act_shape, np.float32); v = np.empty(n, np.float32); nlp = np.empty(n, np.float32)
         nz = _f32(noise, (n, self.A)) if noise is not None else None
+        if mask is not None:
+            mk = _f32(mask, (n, self.A))
+            self._ck(self.lib.ppo_step_masked(self.h, _fp(obs), n, _fp(nz) if nz is not None else None, _fp(mk), _fp(a), _fp(v), _fp(nlp)))
+            return a, v, nlp
         self._ck(self.lib.ppo_step(self.h, _fp(obs), n, _fp(nz) if nz is not None else None, _fp(a), _fp(v), _fp(nlp)))
         return a, v, nlp
 
@@ -164,19 +173,27 @@ class PPOHip:
         self._ck(self.lib.ppo_value(self.h, _fp(obs), n, _fp(v)))
         return v
 
-    def act_deterministic(self, obs):
+    def act_deterministic(self, obs, mask=None):
         obs = _f32(obs); n = obs.shape[0]
         a = np.empty((n,) + self._act_shape, np.float32)
+        if mask is not None:
+            mk = _f32(mask, (n, self.A))
+            self._ck(self.lib.ppo_act_deterministic_masked(self.h, _fp(obs), n, _fp(mk), _fp(a)))
+            return a
         self._ck(self.lib.ppo_act_deterministic(self.h, _fp(obs), n, _fp(a)))
         return a
 
     # ---- train ------------------------------------------------------------------------------------
-    def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v):
+    def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v, mask=None):
         arrs = [_f32(x) for x in (obs, actions, advs, returns, old_nlp, old_v)]
         n = arrs[0].shape[0]
         if self.action_dist == "categorical":
             arrs[1] = _f32(arrs[1], (n,))
         losses = np.empty(5, np.float32)
+        if mask is not None:
+            arrs.insert(2, _f32(mask, (n, self.A)))
+            self._ck(self.lib.ppo_train_step_masked(self.h, C.c_float(lr), C.c_float(cliprange), *[_fp(x) for x in arrs], n, _fp(losses)))
+            return losses
         self._ck(self.lib.ppo_train_step(self.h, C.c_float(lr), C.c_float(cliprange), *[_fp(x) for x in arrs], n, _fp(losses)))
         return losses
 
@@ -256,9 +273,21 @@ class PPOHip:
         x = _f32(raw_obs, (self.E, self.O))
         self._ck(self.lib.ppo_rollout_reset(self.h, _fp(x)))
 
-    def rollout_act(self, t, noise=None):
+    def set_action_masking(self, on=True):
+        """Masks in the device-resident rollout and in update() (include/ppo_hip.h, ppo_set_action_masking).  Changing the setting drops an
+        allocated rollout: call rollout_alloc again."""
+        self._ck(self.lib.ppo_set_action_masking(self.h, int(bool(on))))
+
+    def get_action_masking(self):
+        return bool(self.lib.ppo_get_action_masking(self.h))
+
+    def rollout_act(self, t, noise=None, mask=None):
         out = np.empty((self.E,) + self._act_shape, np.float32)
         nz = _f32(noise, (self.E, self.A)) if noise is not None else None
+        if mask is not None:
+            mk = _f32(mask, (self.E, self.A))
+            self._ck(self.lib.ppo_rollout_act_masked(self.h, t, _fp(nz) if nz is not None else None, _fp(mk), _fp(out)))
+            return out
         self._ck(self.lib.ppo_rollout_act(self.h, t, _fp(nz) if nz is not None else None, _fp(out)))
         return out
 
@@ -282,15 +311,15 @@ class PPOHip:
                                                 _fp(nz) if nz is not None else None, C.c_float(gamma), C.c_float(lam)))
 
     def rollout_get(self, field):
-        shape = {"obs": (self.T, self.E, self.O), "actions": (self.T, self.E) + self._act_shape}.get(field, (self.T, self.E))
+        shape = {"obs": (self.T, self.E, self.O), "actions": (self.T, self.E) + self._act_shape, "masks": (self.T, self.E, self.A)}.get(field, (self.T, self.E))
         out = np.empty(shape, np.float32)
-        idx = self.FIELDS[field] if field in self.FIELDS else self.OUTPUT_FIELDS[field]
+        idx = self.FIELDS[field] if field in self.FIELDS else self.MASK_FIELDS[field] if field in self.MASK_FIELDS else self.OUTPUT_FIELDS[field]
         self._ck(self.lib.ppo_rollout_download(self.h, idx, _fp(out), C.c_int64(out.size)))
         return out
 
     def rollout_set(self, field, arr):
         a = _f32(arr)
-        idx = self.FIELDS[field] if field in self.FIELDS else self.OUTPUT_FIELDS[field]
+        idx = self.FIELDS[field] if field in self.FIELDS else self.MASK_FIELDS[field] if field in self.MASK_FIELDS else self.OUTPUT_FIELDS[field]
         self._ck(self.lib.ppo_rollout_upload(self.h, idx, _fp(a), C.c_int64(a.size)))
 
     def update(self, lr, cliprange, noptepochs, nminibatches, perms=None, seed=0, want_rows=True):

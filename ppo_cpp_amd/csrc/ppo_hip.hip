@@ -51,13 +51,15 @@ const char* kProfNames[PK_COUNT] = {"policy_step", "train_fwd_bwd", "weight_grad
 // which kernel VARIANT a call took (ppo_kernel_counts): the fast paths are chosen by shape, and a test must be able to say which one ran
 enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN, KV_NARROW_STEP_STATIC, KV_NARROW_STEP,
                      KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH,
-                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_COUNT };
+                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_POLICY_STEP_CAT_MASK, KV_TRAIN_FB_CAT_MASK, KV_STEP_HOST_ACTION, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
                                        "bf16_train_sequence", "bf16_step_sequence", "bf16_reduce_adam_kernel", "narrow_epoch_kernel",
                                        "policy_step_kernel<cat>", "train_fwd_bwd_kernel<cat>",
-                                       "gae_kernel<trunc>", "gae_long_kernel<trunc>", "tval_scatter_kernel"};
+                                       "gae_kernel<trunc>", "gae_long_kernel<trunc>", "tval_scatter_kernel",
+                                       "policy_step_kernel<cat,mask>", "train_fwd_bwd_kernel<cat,mask>",
+                                       "policy_step_kernel<host_action>" /* launches (of any head) that published their actions to the host themselves */};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -83,6 +85,10 @@ struct ppo_handle {
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian) or 1 (categorical: the category index)
+    // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
+    // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
+    bool masking = false;
+    float *ro_mask = nullptr, *mb_mask = nullptr, *st_mask = nullptr; int st_mask_rows = 0;
     NetDev net{};
     std::vector<Tensor> tensors;
     int P_dense = 0, P_pad = 0, n_blocks = 0, PT = 0;
@@ -1035,7 +1041,7 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 // X(KP0, HP, AP, L) is the launch statement
 #define NW_DISPATCH(h, X) do { if (!(h)->nw_static) { X(0, 0, 0, 0); } else if ((h)->net.Kp0 == 32) { X(32, 64, 32, 2); } else { X(64, 64, 32, 2); } } while (0)
 
-template <int CT, int KS, int CTH, bool WIDE, bool CAT = false>
+template <int CT, int KS, int CTH, bool WIDE, bool CAT = false, bool MASK = false>
 void launch_step_t(ppo_handle* h, const StepArgs& a0) {
     StepArgs a = a0;
     dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
@@ -1043,11 +1049,21 @@ void launch_step_t(ppo_handle* h, const StepArgs& a0) {
     if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
     a.stamps = grid.x <= 256 ? g_stamps + 4096 * 44 : nullptr;
 #endif
-    hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT>), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
+    hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT, MASK>), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
 }
 int launch_step(ppo_handle* h, const StepArgs& a) {
     if (h->bf.on) { ++h->kv[KV_BF16_STEP]; return launch_step_bf16(h, a); }
     ProfScope ps(h, PK_STEP);
+    if (a.mask && h->dist != PPO_ACT_CATEGORICAL) return fail(h, "policy step: an action mask needs a categorical handle");
+    if (a.mask) {
+        ++h->kv[KV_POLICY_STEP_CAT_MASK];
+        if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true, true, true>(h, a); else launch_step_t<1, 1, 0, true, true, true>(h, a); }
+        else if (h->CT == 4 && h->CTH == 2) launch_step_t<4, 2, 2, false, true, true>(h, a);
+        else if (h->CT == 4) launch_step_t<4, 2, 0, false, true, true>(h, a);
+        else launch_step_t<1, 1, 0, false, true, true>(h, a);
+        HIP_OK(h, hipGetLastError());
+        return 0;
+    }
     if (h->dist == PPO_ACT_CATEGORICAL) {
         ++h->kv[KV_POLICY_STEP_CAT];
         if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true, true>(h, a); else launch_step_t<1, 1, 0, true, true>(h, a); }
@@ -1409,8 +1425,18 @@ int enqueue_train(ppo_handle* h, TrainArgs ta, float* loss_row, bool defer = fal
         dim3 grid(n_rb, 2);
         const size_t lds_bytes = (size_t)n.lds_total * sizeof(float);
         const dim3 blk(BLOCK_THREADS);
-        ++h->kv[h->dist == PPO_ACT_CATEGORICAL ? KV_TRAIN_FB_CAT : (h->t8 && !n.wide) ? KV_TRAIN8 : KV_TRAIN_FB];
-        if (h->dist == PPO_ACT_CATEGORICAL) {                    // (no train8 / dw2 for this head: ppo_create_ex)
+        ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : h->dist == PPO_ACT_CATEGORICAL ? KV_TRAIN_FB_CAT : (h->t8 && !n.wide) ? KV_TRAIN8 : KV_TRAIN_FB];
+        if (ta.mask) {                                           // (a categorical handle: the entry points check)
+            if (n.wide) {
+                if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+                else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            }
+            else if (h->CT == 4 && h->CTH == 2 && h->early) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, true, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            else if (h->CT == 4 && h->CTH == 2) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            else if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, false, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+            else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, false, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+        }
+        else if (h->dist == PPO_ACT_CATEGORICAL) {                    // (no train8 / dw2 for this head: ppo_create_ex)
             if (n.wide) {
                 if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
                 else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
@@ -1658,6 +1684,13 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
         set_lds((const void*)policy_step_kernel<1, 1, 0, false, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false, false, true>);
         set_lds((const void*)policy_step_kernel<4, 2, 0, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true, false, true>);
         set_lds((const void*)policy_step_kernel<1, 1, 0, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true, false, true>);
+        // ... and their action-mask forms (ppo_step_masked / ppo_set_action_masking)
+        set_lds((const void*)policy_step_kernel<4, 2, 2, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, false, true, true>);
+        set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, true, true, true>);
+        set_lds((const void*)policy_step_kernel<4, 2, 0, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, false, false, true, true>);
+        set_lds((const void*)policy_step_kernel<1, 1, 0, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false, false, true, true>);
+        set_lds((const void*)policy_step_kernel<4, 2, 0, true, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true, false, true, true>);
+        set_lds((const void*)policy_step_kernel<1, 1, 0, true, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true, false, true, true>);
     }
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
@@ -1775,7 +1808,8 @@ void ppo_destroy(ppo_handle* h) {
                     h->slots[0], h->slots[1], h->slabs, h->dw_tiles, h->st_obs, h->st_act, h->st_noise, h->st_loss, h->obs_rms.mean,
                     h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->stats_xch, h->stats_part, h->stats_counter, h->adv_xch, h->ro_obs, h->ro_act,
                     h->ro_val, h->ro_nlp, h->ro_done, h->ro_rew, h->ro_ret, h->env_in /* raw_obs, raw_rew, cur_done live inside */, h->raw_done,
-                    h->last_val, h->ro_noise, h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp, h->d_perms, h->d_inv, h->d_gidx, h->d_advstats, h->d_keys, h->d_loss_rows, h->d_loss_mean};
+                    h->last_val, h->ro_noise, h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp, h->d_perms, h->d_inv, h->d_gidx, h->d_advstats, h->d_keys, h->d_loss_rows, h->d_loss_mean,
+                    h->ro_mask, h->mb_mask, h->st_mask};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int t = 0; t < 2; ++t) for (int l = 0; l < PPO_MAX_LAYERS; ++l) { if (h->hg[t][l]) (void)hipFree(h->hg[t][l]); if (h->dyg[t][l]) (void)hipFree(h->dyg[t][l]); }
     for (int i = 0; i < 6; ++i) if (h->st_vec[i]) (void)hipFree(h->st_vec[i]);
@@ -1919,12 +1953,40 @@ int ppo_seed(ppo_handle* h, uint64_t seed) {
 }
 
 // ---- act model ----------------------------------------------------------------------------------------------------
+// Host checks of an action mask [rows, A] before it is uploaded: every row allows at least one category and, where `actions` is given (category indices already
+// range-checked), its own action.  `who` names the entry point in the message.
+static int check_masks(ppo_handle* h, const char* who, const float* mask, size_t rows, const float* actions) {
+    const size_t A = (size_t)h->net.A;
+    for (size_t i = 0; i < rows; ++i) {
+        bool any = false;
+        for (size_t j = 0; j < A; ++j) any = any || mask[i * A + j] != 0.f;
+        if (!any) return fail(h, "%s: mask row %lld allows no category", who, (long long)i);
+        if (actions && mask[i * A + (size_t)actions[i]] == 0.f)
+            return fail(h, "%s: actions[%lld] = %d is forbidden by the row's own mask", who, (long long)i, (int)actions[i]);
+    }
+    return 0;
+}
+static int need_categorical(ppo_handle* h, const char* who) {
+    if (h->dist != PPO_ACT_CATEGORICAL || h->bf.on) return fail(h, "%s: action masks need a categorical (PPO_ACT_CATEGORICAL, PPO_F32) handle", who);
+    return 0;
+}
+// staging buffer of the host-pointer calls' masks: allocated by the first masked call, so that a handle that never passes a mask allocates what it always did
+static int ensure_mask_staging(ppo_handle* h, int rows) {
+    if (rows <= h->st_mask_rows) return 0;
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (dev_alloc(h, &h->st_mask, (size_t)rows * h->net.A)) return -1;
+    h->st_mask_rows = rows;
+    return 0;
+}
+
 static int step_common(ppo_handle* h, const float* obs, int n, const float* noise, bool sample, float* action, float* det_action,
-                       float* value, float* neglogp) {
+                       float* value, float* neglogp, const float* mask = nullptr) {
     ENTER_Q(h);
     if (n < 1) return fail(h, "step: n must be positive");
-    if (ensure_staging(h, n)) return -1;
+    if (mask && (need_categorical(h, "step") || check_masks(h, "step", mask, (size_t)n, nullptr))) return -1;
+    if (ensure_staging(h, n) || (mask && ensure_mask_staging(h, n))) return -1;
     const NetDev& net = h->net;
+    if (mask) HIP_OK(h, hipMemcpyAsync(h->st_mask, mask, (size_t)n * net.A * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_OK(h, hipMemcpyAsync(h->st_obs, obs, (size_t)n * net.O * sizeof(float), hipMemcpyHostToDevice, h->stream));
     if (noise) HIP_OK(h, hipMemcpyAsync(h->st_noise, noise, (size_t)n * net.A * sizeof(float), hipMemcpyHostToDevice, h->stream));
     StepArgs a{};
@@ -1933,7 +1995,7 @@ static int step_common(ppo_handle* h, const float* obs, int n, const float* nois
     a.det_action = det_action ? h->st_act : nullptr;
     a.value = value ? h->st_vec[0] : nullptr;
     a.neglogp = neglogp ? h->st_vec[1] : nullptr;
-    a.obs_out = nullptr; a.nz = no_norm(); a.n = n;
+    a.obs_out = nullptr; a.nz = no_norm(); a.n = n; a.mask = mask ? h->st_mask : nullptr;
     // (only a call that actually draws from the counter RNG advances it: ppo_value / ppo_act_deterministic in the middle of a
     // rollout must not shift the rollout's noise)
     a.seed = h->rng_seed; a.rng_step = (sample && action && !noise) ? h->rng_calls++ : h->rng_calls; a.row_base = (uint32_t)h->rank * (uint32_t)(h->nz_envs > 0 ? h->nz_envs : n);
@@ -1946,7 +2008,7 @@ static int step_common(ppo_handle* h, const float* obs, int n, const float* nois
     if (bf16_chain_err_test(h)) {
         // a stateless pass: run it again, layer by layer this time (the handle has switched), and keep the finding on stderr
         fprintf(stderr, "libppo_hip: %s -- the pass was repeated with a launch per layer\n", h->err.c_str());
-        return step_common(h, obs, n, noise, sample, action, det_action, value, neglogp);
+        return step_common(h, obs, n, noise, sample, action, det_action, value, neglogp, mask);
     }
     return 0;
 }
@@ -1959,6 +2021,12 @@ int ppo_value(ppo_handle* h, const float* obs, int32_t n, float* value) {
 }
 int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* action) {
     return step_common(h, obs, n, nullptr, false, nullptr, action, nullptr, nullptr);
+}
+int ppo_step_masked(ppo_handle* h, const float* obs, int32_t n, const float* noise, const float* mask, float* action, float* value, float* neglogp) {
+    return step_common(h, obs, n, noise, true, action, nullptr, value, neglogp, mask);
+}
+int ppo_act_deterministic_masked(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* action) {
+    return step_common(h, obs, n, nullptr, false, nullptr, action, nullptr, nullptr, mask);
 }
 
 // ---- train op -------------------------------------------------------------------------------------------------------
@@ -1982,26 +2050,34 @@ int ppo_get_value_clip(const ppo_handle* h, int32_t* mode, float* range) {
 
 int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, const float* actions, const float* advs,
                    const float* returns, const float* old_neglogp, const float* old_values, int32_t n, float losses[5]) {
+    return ppo_train_step_masked(h, lr, cliprange, obs, actions, nullptr, advs, returns, old_neglogp, old_values, n, losses);
+}
+
+int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float* obs, const float* actions, const float* mask, const float* advs,
+                          const float* returns, const float* old_neglogp, const float* old_values, int32_t n, float losses[5]) {
     ENTER_Q(h);
     if (n < 2) return fail(h, "ppo_train_step: n=%d (the reference asserts more than one row, ppo2.hpp:402)", n);
+    if (mask && need_categorical(h, "ppo_train_step_masked")) return -1;
     if (h->dist == PPO_ACT_CATEGORICAL)
         for (int32_t i = 0; i < n; ++i) {
             const float x = actions[i];
             if (!(x >= 0.f && x < (float)h->net.A && x == floorf(x)))
                 return fail(h, "ppo_train_step: actions[%d] = %g is not a category index in [0, %d)", (int)i, (double)x, h->net.A);
         }
+    if (mask && check_masks(h, "ppo_train_step_masked", mask, (size_t)n, actions)) return -1;
     h->bf.epoch_staged = false;
-    if (ensure_staging(h, n) || ensure_train_ws(h, n)) return -1;
+    if (ensure_staging(h, n) || ensure_train_ws(h, n) || (mask && ensure_mask_staging(h, n))) return -1;
     const NetDev& net = h->net;
     const size_t fb = sizeof(float);
     HIP_OK(h, hipMemcpyAsync(h->st_obs, obs, (size_t)n * net.O * fb, hipMemcpyHostToDevice, h->stream));
     HIP_OK(h, hipMemcpyAsync(h->st_act, actions, (size_t)n * h->Aw * fb, hipMemcpyHostToDevice, h->stream));
+    if (mask) HIP_OK(h, hipMemcpyAsync(h->st_mask, mask, (size_t)n * net.A * fb, hipMemcpyHostToDevice, h->stream));
     const float* vecs[4] = {advs, returns, old_neglogp, old_values};
     for (int i = 0; i < 4; ++i) HIP_OK(h, hipMemcpyAsync(h->st_vec[2 + i], vecs[i], (size_t)n * fb, hipMemcpyHostToDevice, h->stream));
     if (set_hyper(h, lr, cliprange)) return -1;
     TrainArgs ta{};
     ta.obs = h->st_obs; ta.actions = h->st_act; ta.advs = h->st_vec[2]; ta.returns = h->st_vec[3]; ta.old_neglogp = h->st_vec[4];
-    ta.old_values = h->st_vec[5]; ta.adv_stats = nullptr; ta.n = n;
+    ta.old_values = h->st_vec[5]; ta.adv_stats = nullptr; ta.n = n; ta.mask = mask ? h->st_mask : nullptr;
     ta.inv_n = 1.0f / (float)((int64_t)n * h->world);
     if (h->dw2 && zero_words(h, h->dw2_counters, DW2_TILES)) return -1;
     if (enqueue_train(h, ta, h->st_loss)) return -1;
@@ -2280,6 +2356,22 @@ static void trunc_clear(ppo_handle* h) {
     h->tr_idx.clear(); h->tr_K = 0; h->obs_t = -1;
 }
 
+int ppo_set_action_masking(ppo_handle* h, int on) {
+    if (!h) return fail(nullptr, "ppo_set_action_masking: null handle");
+    if (on && need_categorical(h, "ppo_set_action_masking")) return -1;
+    if ((on != 0) == h->masking) return 0;
+    ENTER_Q(h);
+    // the rollout, the gathered epoch and the captured update belong to the old setting: dropped, so that no buffer of the wrong shape is ever read
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    drop_graph(h);
+    h->masking = on != 0;
+    h->E = 0; h->T = 0;
+    h->upd_cap_rows = 0; h->upd_cap_steps = 0;
+    trunc_clear(h);
+    return 0;
+}
+int ppo_get_action_masking(const ppo_handle* h) { return h && h->masking ? 1 : 0; }
+
 int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
     ENTER(h);
     if (E < 1 || T < 1) return fail(h, "ppo_rollout_alloc: bad shape");
@@ -2294,6 +2386,10 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
         dev_alloc(h, &h->ro_done, B) || dev_alloc(h, &h->ro_rew, B) || dev_alloc(h, &h->ro_ret, B) ||
         dev_alloc(h, &h->last_val, E) || dev_alloc(h, &h->ro_noise, B * n.A))
         return -1;
+    if (h->masking) {
+        if (dev_alloc(h, &h->ro_mask, B * n.A)) return -1;
+        HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)h->ro_mask, 0x3f800000 /* 1.0f */, B * n.A, h->stream));
+    }
     h->E = E; h->T = T;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     if (h->ro_tval) { (void)hipFree(h->ro_tval); h->ro_tval = nullptr; }
@@ -2308,15 +2404,16 @@ static ObsNorm obs_norm(ppo_handle* h) { return ObsNorm{h->obs_rms.mean, h->obs_
 
 // policy step on the current observations -> rollout[t]
 // direct: the policy tower also publishes the actions to the host itself (StepArgs::host_action)
-static int enqueue_rollout_act(ppo_handle* h, int t, const float* noise_dev, uint32_t seed, uint32_t rng_step, uint32_t row_base, bool direct = false) {
+// mask_dev: row t of ro_mask when the step samples under a mask (ppo_rollout_act_masked), null: the unmasked kernel
+static int enqueue_rollout_act(ppo_handle* h, int t, const float* noise_dev, uint32_t seed, uint32_t rng_step, uint32_t row_base, bool direct = false, const float* mask_dev = nullptr) {
     const NetDev& n = h->net;
     const size_t E = h->E;
     if (h->done_staged != t) HIP_OK(h, hipMemcpyAsync(h->ro_done + t * E, h->cur_done, E * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     StepArgs a{};
     a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.noise = noise_dev; a.action = h->ro_act + t * E * h->Aw; a.det_action = nullptr;
     a.value = h->ro_val + t * E; a.neglogp = h->ro_nlp + t * E; a.obs_out = h->ro_obs + t * E * n.O; a.nz = obs_norm(h); a.n = (int)E;
-    a.seed = seed; a.rng_step = rng_step; a.row_base = row_base;
-    if (direct) { a.host_action = h->pin_out_dev; a.host_flags = h->pin_wgflag_dev; a.host_seq = ++h->wg_seq; }
+    a.seed = seed; a.rng_step = rng_step; a.row_base = row_base; a.mask = mask_dev;
+    if (direct) { ++h->kv[KV_STEP_HOST_ACTION]; a.host_action = h->pin_out_dev; a.host_flags = h->pin_wgflag_dev; a.host_seq = ++h->wg_seq; }
     return launch_step(h, a);
 }
 
@@ -2503,7 +2600,7 @@ static int host_quiesce(ppo_handle* h) {
 }
 
 int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
-    if (!h->E) return fail(h, "ppo_rollout_reset: call ppo_rollout_alloc first");
+    if (!h->E) return fail(h, "ppo_rollout_reset: no rollout allocated (call ppo_rollout_alloc first)");
     ENTER(h);
     const size_t on = (size_t)h->E * h->net.O;
     if (host_quiesce(h)) return -1;                             // (a transition observed before the reset is still booked, as on the general path)
@@ -2521,9 +2618,22 @@ int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
     return 0;
 }
 
-int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions_out) {
-    if (!h->E || t < 0 || t >= h->T) return fail(h, "ppo_rollout_act: bad step %d", t);
+int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions_out) { return ppo_rollout_act_masked(h, t, noise, nullptr, actions_out); }
+
+int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const float* mask, float* actions_out) {
+    const char* who = mask ? "ppo_rollout_act_masked" : "ppo_rollout_act";
+    if (!h->E) return fail(h, "%s: no rollout allocated (ppo_rollout_alloc)", who);
+    if (t < 0 || t >= h->T) return fail(h, "%s: bad step %d", who, t);
+    if (mask && !h->masking) return fail(h, "ppo_rollout_act_masked: action masking is off for this handle (ppo_set_action_masking)");
+    if (mask && check_masks(h, "ppo_rollout_act_masked", mask, (size_t)h->E, nullptr)) return -1;
     ENTER(h);
+    float* mask_row = nullptr;
+    if (h->masking) {
+        // row t of the mask buffer: what was passed, or ones (the plain call on a masking handle: the unmasked kernel, the same bits)
+        const size_t mc = (size_t)h->E * h->net.A;
+        if (mask) { mask_row = h->ro_mask + (size_t)t * mc; HIP_OK(h, hipMemcpyAsync(mask_row, mask, mc * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
+        else HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ro_mask + (size_t)t * mc), 0x3f800000 /* 1.0f */, mc, h->stream));
+    }
     h->obs_t = -1;                                               // (the pinned mirror no longer vouches for the last transition's dones)
     const NetDev& n = h->net;
     const size_t cnt = (size_t)h->E * h->Aw;                 // actions out; the noise is [E, A]
@@ -2593,7 +2703,7 @@ int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions
     const char* dme = getenv("PPO_HIP_DIRECT_ACT_MAX_BLOCKS");                   // (read per call: a test switches it inside one process)
     const int direct_max = dme ? atoi(dme) : 4;
     const bool direct = !h->opt_no_direct_act && !h->narrow && !h->bf.on && h->pin_wgflag && (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK <= direct_max;
-    if (enqueue_rollout_act(h, t, nd, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), direct)) return -1;
+    if (enqueue_rollout_act(h, t, nd, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), direct, mask_row)) return -1;
     if (direct) {
         // Watch the table: block b's 16 rows are copied out as soon as its word shows this call's sequence number (the copy of the early blocks
         // hides under the kernel's tail).  The policy kernel is stream-ordered behind the H2D copy of the last observation and the statistics
@@ -2640,7 +2750,8 @@ int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions
 }
 
 int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const float* raw_rew, const float* dones) {
-    if (!h->E || t < 0 || t >= h->T) return fail(h, "ppo_rollout_observe: bad step %d", t);
+    if (!h->E) return fail(h, "ppo_rollout_observe: no rollout allocated (call ppo_rollout_alloc first)");
+    if (t < 0 || t >= h->T) return fail(h, "ppo_rollout_observe: bad step %d", t);
     ENTER(h);
     const size_t E = h->E, on = E * h->net.O;
     // obs | reward | dones packed into the pinned mirror, ONE H2D copy; no synchronisation here: nothing of this call is
@@ -2664,7 +2775,7 @@ int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const fl
 
 int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
     ENTER(h);
-    if (!h->E) return fail(h, "ppo_rollout_finish: call ppo_rollout_alloc first");
+    if (!h->E) return fail(h, "ppo_rollout_finish: no rollout allocated (call ppo_rollout_alloc first)");
     if (host_small(h)) {
         if (h->hp_active) {
             // after its last row the resident kernel waits for the last transition, books it and leaves by itself; if the host
@@ -2691,7 +2802,7 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
 // A host-only call: it appends to the handle's list and enqueues nothing, whichever rollout form serves the handle (a resident kernel keeps running).
 int ppo_rollout_mark_truncated(ppo_handle* h, int32_t t, int32_t count, const int32_t* env_ids, const float* terminal_raw_obs) {
     if (!h) return fail(nullptr, "ppo_rollout_mark_truncated: null handle");
-    if (!h->E) return fail(h, "ppo_rollout_mark_truncated: call ppo_rollout_alloc first");
+    if (!h->E) return fail(h, "ppo_rollout_mark_truncated: no rollout allocated (call ppo_rollout_alloc first)");
     if (count < 0) return fail(h, "ppo_rollout_mark_truncated: negative count");
     if (t < 0 || t >= h->T) return fail(h, "ppo_rollout_mark_truncated: bad step %d", t);
     if (count == 0) return 0;
@@ -2724,11 +2835,13 @@ int ppo_rollout_mark_truncated(ppo_handle* h, int32_t t, int32_t count, const in
 
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first, const float* noise, float gamma, float lam) {
     ENTER(h);
-    if (!h->E) return fail(h, "ppo_collect_synthetic: call ppo_rollout_alloc first");
+    if (!h->E) return fail(h, "ppo_collect_synthetic: no rollout allocated (call ppo_rollout_alloc first)");
     const NetDev& n = h->net;
     const int E = h->E, T = h->T;
     const int envW = E * (n.O + 2);
     if (noise) HIP_OK(h, hipMemcpyAsync(h->ro_noise, noise, (size_t)E * T * n.A * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    // a masking handle: the seeded env has no notion of legality, every row is collected (unmasked kernels) and recorded as all allowed
+    if (h->masking) HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)h->ro_mask, 0x3f800000 /* 1.0f */, (size_t)E * T * n.A, h->stream));
     if (first) {
         { ProfScope ps(h, PK_ENV);
           hipLaunchKernelGGL(seeded_env_kernel, dim3((envW + 255) / 256), dim3(256), 0, h->stream, seed, env0, E, step0, n.O, h->raw_obs, (float*)nullptr, (float*)nullptr);
@@ -2873,6 +2986,7 @@ static float* rollout_field(ppo_handle* h, int field, size_t* count) {
         case 4: *count = B; return h->ro_done;
         case 5: *count = B; return h->ro_rew;
         case 6: *count = B; return h->ro_ret;
+        case 8: *count = h->masking ? B * h->net.A : 0; return h->masking ? h->ro_mask : nullptr;
     }
     return nullptr;
 }
@@ -2888,7 +3002,9 @@ int ppo_rollout_download(ppo_handle* h, int field, float* dst, int64_t count) {
         else memset(dst, 0, c * sizeof(float));
         return 0;
     }
-    float* p = h->E ? rollout_field(h, field, &c) : nullptr;
+    if (field == 8 && !h->masking) return fail(h, "ppo_rollout_download: field 8 (masks) needs action masking on (ppo_set_action_masking)");
+    if (!h->E) return fail(h, "ppo_rollout_download: no rollout allocated (ppo_rollout_alloc)");
+    float* p = rollout_field(h, field, &c);
     if (!p || (size_t)count != c) return fail(h, "ppo_rollout_download: bad field/count");
     HIP_OK(h, hipStreamSynchronize(h->stream));
     HIP_OK(h, hipMemcpy(dst, p, c * sizeof(float), hipMemcpyDeviceToHost));
@@ -2899,8 +3015,11 @@ int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count
     ENTER_Q(h);
     size_t c = 0;
     if (field == 7) return fail(h, "ppo_rollout_upload: field 7 (terminal values) is an output of ppo_rollout_finish");
-    float* p = h->E ? rollout_field(h, field, &c) : nullptr;
+    if (field == 8 && !h->masking) return fail(h, "ppo_rollout_upload: field 8 (masks) needs action masking on (ppo_set_action_masking)");
+    if (!h->E) return fail(h, "ppo_rollout_upload: no rollout allocated (ppo_rollout_alloc)");
+    float* p = rollout_field(h, field, &c);
     if (!p || (size_t)count != c) return fail(h, "ppo_rollout_upload: bad field/count");
+    if (field == 8 && check_masks(h, "ppo_rollout_upload", src, (size_t)h->E * h->T, nullptr)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     HIP_OK(h, hipMemcpy(p, src, c * sizeof(float), hipMemcpyHostToDevice));
     return 0;
@@ -2924,6 +3043,7 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
         {"dy_vf_1", ws && n.L > 1 ? h->dyg[1][1] : nullptr, R * n.Hp[n.L > 1 ? 1 : 0]},
         {"slots_pi", ws ? h->slots[0] : nullptr, (R / 16) * n.slot_w}, {"slots_vf", ws ? h->slots[1] : nullptr, (R / 16) * n.slot_w},
         {"slabs", h->narrow ? nullptr : h->slabs, (size_t)h->max_split * P},
+        {"mb_mask", h->masking ? h->mb_mask : nullptr, U * n.A}, {"ro_mask", h->masking ? h->ro_mask : nullptr, (size_t)h->E * h->T * n.A},
         {"mb_obs", h->mb_obs, U * n.O}, {"mb_act", h->mb_act, U * h->Aw}, {"mb_adv", h->mb_adv, U}, {"mb_ret", h->mb_ret, U}, {"mb_val", h->mb_val, U}, {"mb_nlp", h->mb_nlp, U},
         {"gidx", h->d_gidx, U}, {"advstats", h->d_advstats, (size_t)2 * h->upd_cap_steps}, {"keys", h->d_keys, (size_t)2 * h->upd_cap_steps}, {"loss_rows", h->d_loss_rows, (size_t)5 * h->upd_cap_steps},
         {"nw_img", h->nw_img, h->narrow ? (size_t)2 * h->nw.w_total : 0}, {"nw_partials", h->nw_partials, (size_t)4 * h->nw_groups_cap * h->nw_stride},
@@ -2972,7 +3092,11 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
                     if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
                     ga.stamps = g_stamps + 4096 * 32;
 #endif
-                    hipLaunchKernelGGL(epoch_prepare_gather_kernel, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
+                    if (h->masking) {
+                        ga.mask = h->ro_mask; ga.mb_mask = h->mb_mask; ga.Am = h->net.A;
+                        hipLaunchKernelGGL(epoch_prepare_gather_kernel<true>, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
+                    } else
+                    hipLaunchKernelGGL(epoch_prepare_gather_kernel<false>, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
                     HIP_OK(h, hipGetLastError());
                     merged = true;
                 } else {
@@ -2995,14 +3119,19 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
             GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->Aw, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
                           h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp};
             if (h->global_shuffle && h->comm && h->world > 1) { ga.obs = h->gs_obs; ga.act = h->gs_act; ga.ret = h->gs_ret; ga.val = h->gs_val; ga.nlp = h->gs_nlp; }
-            const bool wide4 = h->net.O % 4 == 0 && h->Aw % 4 == 0;
+            // (epoch_gather4_kernel copies no masks: a masking handle is categorical, its action rows are one float, so it never qualifies -- and must not)
+            const bool wide4 = h->net.O % 4 == 0 && h->Aw % 4 == 0 && !h->masking;
             // bf16 path: the epoch's observations become bf16 once; a minibatch is then a row slice.  With 16-byte rows the gather writes them itself
             const bool fuse_stage = wide4 && h->bf.on && M % GB_PAD == 0 && h->bf.xe_rows >= B && h->net.Kp0 % 4 == 0 && !(h->global_shuffle && h->comm && h->world > 1);
             if (wide4) {
                 Gather4Args g4{ga, fuse_stage ? h->bf.xe : nullptr, h->net.Kp0};
                 hipLaunchKernelGGL(epoch_gather4_kernel, dim3((B + 15) / 16), dim3(256), 0, h->stream, g4);
             }
-            else hipLaunchKernelGGL(epoch_gather_kernel, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
+            else if (h->masking) {
+                ga.mask = h->ro_mask; ga.mb_mask = h->mb_mask; ga.Am = h->net.A;
+                hipLaunchKernelGGL(epoch_gather_kernel<true>, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
+            }
+            else hipLaunchKernelGGL(epoch_gather_kernel<false>, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
             HIP_OK(h, hipGetLastError());
             if (h->bf.on && fuse_stage) h->bf.epoch_staged = true;
             else if (h->bf.on) {
@@ -3051,6 +3180,7 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
             const size_t r0 = (size_t)k * M;
             ta.obs = h->mb_obs + r0 * h->net.O; ta.actions = h->mb_act + r0 * h->Aw; ta.returns = h->mb_ret + r0; ta.old_values = h->mb_val + r0;
             ta.old_neglogp = h->mb_nlp + r0; ta.advs = h->mb_adv + r0; ta.adv_stats = nullptr; ta.n = M;
+            ta.mask = h->masking ? h->mb_mask + r0 * h->net.A : nullptr;
             ta.inv_n = 1.0f / (float)((int64_t)M * h->world);
             if (enqueue_train(h, ta, h->d_loss_rows + (size_t)(ep * nmb + k) * 5, /*defer*/ true)) return -1;
         }
@@ -3064,13 +3194,15 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
 int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t nmb, const int32_t* perms, uint64_t seed, float* loss_rows,
                float mean_losses[5]) {
     ENTER_Q(h);
-    if (!h->E) return fail(h, "ppo_update: no rollout (ppo_rollout_alloc + collect first)");
+    if (!h->E) return fail(h, "ppo_update: no rollout allocated (ppo_rollout_alloc + collect first)");
     const int B = h->E * h->T;
     if (epochs < 1 || nmb < 1 || B % nmb) return fail(h, "ppo_update: n_batch %d not divisible by nminibatches %d", B, nmb);
     const int M = B / nmb;
     if (ensure_train_ws(h, M)) return -1;
     const int steps = epochs * nmb;
     const bool gs = h->global_shuffle && h->comm && h->world > 1;
+    if (h->masking && h->global_shuffle)
+        return fail(h, "ppo_update: ppo_dist_global_shuffle(1) together with action masking is not supported (the masks are not all-gathered); switch one of them off");
     const int Bp = gs ? B * h->world : B;                      // rows one permutation covers
     if (gs && Bp > h->gs_rows) {
         HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -3085,6 +3217,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
         const int cr = std::max(Bp, h->upd_cap_rows), cs = std::max(steps, h->upd_cap_steps);
         if (dev_alloc(h, &h->mb_obs, (size_t)cr * h->net.O) || dev_alloc(h, &h->mb_act, (size_t)cr * h->Aw) || dev_alloc(h, &h->mb_adv, cr) ||
             dev_alloc(h, &h->mb_ret, cr) || dev_alloc(h, &h->mb_val, cr) || dev_alloc(h, &h->mb_nlp, cr)) return -1;
+        if (h->masking && dev_alloc(h, &h->mb_mask, (size_t)cr * h->net.A)) return -1;
         if (h->d_perms) { (void)hipFree(h->d_perms); h->d_perms = nullptr; h->upd_cap_epochs = 0; }      // sized on demand below
         if (dev_alloc(h, &h->d_inv, cr) || dev_alloc(h, &h->d_gidx, cr) ||
             dev_alloc(h, &h->d_advstats, (size_t)2 * cs) || dev_alloc(h, &h->d_keys, (size_t)2 * cs) || dev_alloc(h, &h->d_loss_rows, (size_t)5 * cs) ||

@@ -799,6 +799,7 @@ struct StepArgs {
     ObsNorm nz;
     int n;
     uint32_t seed, rng_step, row_base;
+    const float* mask;       // [n,A] action mask of the categorical head (non-zero = allowed); read by the <.., CAT, MASK> instantiations only
     // host-Env rollouts (ppo_rollout_act): the policy tower's workgroup ALSO stores its 16 rows of actions into the handle's pinned landing buffer
     // (16-byte stores) and then raises its own word of a pinned flag table to host_seq; the host watches the table -- no D2H copy command, no
     // stream synchronisation, and the value tower's workgroups are not waited for.  null: off
@@ -817,8 +818,11 @@ struct StepArgs {
 
 // CAT: categorical head (stable-baselines CategoricalProbabilityDistribution over the logits in place of mu): the action is ONE float per row
 // (the category index), `noise` holds the uniforms u [n,A] of the Gumbel-argmax draw, det_action = argmax of the logits
-template <int CT, int KS, int CTH, bool WIDE, bool CAT = false>
+// MASK (with CAT): a.mask [n,A] takes the forbidden categories (0) out of both argmaxes and of the normaliser -- excluded, not pushed down by a constant.  The lane
+// that owns category j reads mask[row][j] beside its logit; the lane loops and butterflies are the unmasked ones, so a row of ones gives the unmasked bits.
+template <int CT, int KS, int CTH, bool WIDE, bool CAT = false, bool MASK = false>
 __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev net, StepArgs a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     PSTAMP(0);
     warm_kernargs<sizeof(NetDev) + sizeof(StepArgs)>();
@@ -865,21 +869,34 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
     const int row = row0 + r;
     if constexpr (CAT) {
         // a = argmax_j (l_j - log(-log u_j)), neglogp = log sum_j exp(l_j - m) - (l_a - m), m = max_j l_j (softmax cross-entropy against one_hot(a))
+        // MASK: a lane's best index starts at net.A ("none yet"), so the first ALLOWED category is taken even when its perturbed logit is -inf (u == 0) and a
+        // lane without an allowed category loses every tie of the butterfly to a real index; a row without any allowed category (which the host checks
+        // refuse) ends at net.A and is brought back inside the tile below
         float bp = -INFINITY, bl = -INFINITY;
-        int ip = 0, il = 0;
+        int ip = MASK ? net.A : 0, il = MASK ? net.A : 0;
         for (int j = part; j < net.A; j += 16) {
             const float l = mus[r * ldm + j];
             float u = 0.5f;
             if (row < a.n) u = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
             const float pl = l - logf(-logf(u));
+            if constexpr (MASK) {
+                const bool mk = row < a.n ? a.mask[(size_t)row * net.A + j] != 0.f : true;
+                if (mk && (pl > bp || ip == net.A)) { bp = pl; ip = j; }
+                if (mk && (l > bl || il == net.A)) { bl = l; il = j; }
+            } else {
             if (pl > bp) { bp = pl; ip = j; }
             if (l > bl) { bl = l; il = j; }
+            }
         }
         group16_argmax(bp, ip);
         group16_argmax(bl, il);
+        if constexpr (MASK) { ip = min(ip, net.A - 1); il = min(il, net.A - 1); }
         const float m = bl;
         float z = 0.f;
-        for (int j = part; j < net.A; j += 16) z += expf(mus[r * ldm + j] - m);
+        for (int j = part; j < net.A; j += 16) {
+            if constexpr (MASK) { if (row < a.n && a.mask[(size_t)row * net.A + j] == 0.f) continue; }
+            z += expf(mus[r * ldm + j] - m);
+        }
         z = group16_sum(z);
         const float la = mus[r * ldm + ip] - m;
         if (part == 0 && row < a.n) {
@@ -950,6 +967,7 @@ struct TrainArgs {
     // minibatch sources (the epoch gather has already put the rows in minibatch order)
     const float* obs; const float* actions; const float* returns; const float* old_values; const float* old_neglogp;
     const float* advs;           // explicit normalised advantages (indexed like the others) or null
+    const float* mask;           // [n][A] action masks in minibatch order (non-zero = allowed); read by the <.., CAT, MASK> instantiations only
     const float* adv_stats;      // {mean, denom} of this minibatch when advs == null (ppo2.hpp:401-406)
     const float* hyper;          // {lr, cliprange, vclip_range, vclip_off}
     int n;                       // rows in this minibatch on this rank
@@ -970,8 +988,12 @@ struct TrainArgs {
 // a SIMD belongs to one wave), and the second layer's first ring stages follow them.  The small phases then pay neither
 // their own weight round trip nor the burst that requests the next product's weights.
 // CAT: categorical head -- `actions` holds ONE float per row (the category index); d logits go where d mu goes, the aux (d logstd) slot gets zeros
-template <int CT, int KS, int CTH, bool WIDE, bool EARLY = false, bool CAT = false>
+// MASK (with CAT): a.mask [n][A]; maximum, normaliser, neglogp and entropy run over the allowed categories, d logits of a forbidden one is exactly 0.  Same lane
+// loops and butterflies as the unmasked form (a row of ones gives its bits).  A row whose action its own mask forbids (only possible through inconsistent
+// device-resident fields) gives unspecified loss values; nothing is indexed with the action or the mask, so nothing leaves the tile.
+template <int CT, int KS, int CTH, bool WIDE, bool EARLY = false, bool CAT = false, bool MASK = false>
 __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net, TrainArgs a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs)>();
     // XCD-aware row mapping: workgroups are dealt round-robin over the 8 XCDs; giving XCD x the CONTIGUOUS row tiles
@@ -1074,23 +1096,27 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
         // categorical: m = max_j l_j, a0 = l - m, z = sum exp(a0); neglogp = log z - a0[act], entropy = sum_j p_j (log z - a0_j)
         float cm = 0.f, cz = 1.f, clz = 0.f, cnlp = 0.f, cent = 0.f;
         int cact = -1;
+        // MASK: is category j of this lane's row allowed (dead rows of the last tile: all allowed, nothing is read); the ONE reader of the mask in this kernel
+        const float* mrow = MASK ? a.mask + (size_t)row * net.A : nullptr;
+        auto allowed = [&](int j) __attribute__((always_inline)) { if constexpr (MASK) return !live || mrow[j] != 0.f; else return true; };
         if constexpr (CAT) {
             cact = live ? (int)acts[r * net.Ap] : -1;
             float bl = -INFINITY;
             int il = 0;
-            for (int j = part; j < net.A; j += 16) { const float l = mus[r * ldm + j]; if (l > bl) { bl = l; il = j; } }
+            for (int j = part; j < net.A; j += 16) { const float l = mus[r * ldm + j]; if (allowed(j) && l > bl) { bl = l; il = j; } }
             group16_argmax(bl, il);
             cm = bl;
             float la = 0.f;
             cz = 0.f;
             for (int j = part; j < net.A; j += 16) {
+                if (!allowed(j)) continue;
                 const float a0 = mus[r * ldm + j] - cm;
                 cz += expf(a0);
                 if (j == cact) la = a0;
             }
             cz = group16_sum(cz); la = group16_sum(la);
             clz = logf(cz);
-            for (int j = part; j < net.A; j += 16) { const float a0 = mus[r * ldm + j] - cm; cent += (expf(a0) / cz) * (clz - a0); }
+            for (int j = part; j < net.A; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - cm; cent += (expf(a0) / cz) * (clz - a0); }
             cent = group16_sum(cent);
             cnlp = clz - la;
         }
@@ -1134,7 +1160,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
             float dmu = 0.f, dl = 0.f;
             if constexpr (CAT) {
                 // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H)   (dl stays 0: no logstd)
-                if (j < net.A && live) {
+                if (j < net.A && live && allowed(j)) {
                     const float a0 = mus[r * ldm + j] - cm;
                     const float p = expf(a0) / cz;
                     dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + net.ent_coef * g * (p * ((a0 - clz) + sent));
@@ -2096,8 +2122,10 @@ struct GatherArgs {
 #ifdef PPO_STAMPS
     unsigned long long* stamps;
 #endif
+    const float* mask; float* mb_mask; int Am;     // action masks [B, Am] -> minibatch order: the <MASK> instantiations only (a masking handle)
 };
 
+template <bool MASK = false>
 __global__ __launch_bounds__(256) void epoch_gather_kernel(GatherArgs a) {
     __shared__ int src[16];
     const int pos0 = blockIdx.x * 16, tid = threadIdx.x;
@@ -2109,6 +2137,12 @@ __global__ __launch_bounds__(256) void epoch_gather_kernel(GatherArgs a) {
         if (pos0 + r >= a.B) continue;
         if (j < a.O) a.mb_obs[(size_t)(pos0 + r) * a.O + j] = a.obs[(size_t)src[r] * a.O + j];
         else a.mb_act[(size_t)(pos0 + r) * a.A + (j - a.O)] = a.act[(size_t)src[r] * a.A + (j - a.O)];
+    }
+    if constexpr (MASK) {
+        for (int i = tid; i < 16 * a.Am; i += 256) {
+            const int r = i / a.Am, j = i - r * a.Am;
+            if (pos0 + r < a.B) a.mb_mask[(size_t)(pos0 + r) * a.Am + j] = a.mask[(size_t)src[r] * a.Am + j];
+        }
     }
     if (tid < 16 && pos0 + tid < a.B) {
         const int p = pos0 + tid, s = src[tid], k = p / a.M;
@@ -2157,6 +2191,7 @@ __global__ __launch_bounds__(256) void epoch_gather4_kernel(Gather4Args q) {
 // memory (the index map) per epoch less: the map never leaves the workgroup's LDS except as this epoch's `gidx` record.
 #define EPG_SPLIT 8
 #define EPG_MAX_M 8192              // rows of a minibatch the LDS copy of the index map holds (32 KB)
+template <bool MASK = false>
 __global__ __launch_bounds__(EP_THREADS) void epoch_prepare_gather_kernel(EpochArgs a, GatherArgs ga) {
     __shared__ float red[EP_THREADS / 64];
     __shared__ float s_mean, s_den;
@@ -2243,6 +2278,12 @@ __global__ __launch_bounds__(EP_THREADS) void epoch_prepare_gather_kernel(EpochA
         else ga.mb_act[(size_t)p * ga.A + (jj - ga.O)] = ga.act[(size_t)s * ga.A + (jj - ga.O)];
         rr += dq; jj += dr;
         if (jj >= W) { jj -= W; ++rr; }
+    }
+    if constexpr (MASK) {
+        for (int i = tid; i < (r1 - r0) * ga.Am; i += EP_THREADS) {
+            const int r = r0 + i / ga.Am, j = i % ga.Am;
+            ga.mb_mask[(size_t)(k * a.M + r) * ga.Am + j] = ga.mask[(size_t)s_idx[r] * ga.Am + j];
+        }
     }
     ESTAMP(5);
     for (int r = r0 + tid; r < r1; r += EP_THREADS) {

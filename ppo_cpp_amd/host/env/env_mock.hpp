@@ -8,6 +8,10 @@
 //                  hexapod's reward curves); this is the environment behind tests/test_learning.py, small enough for the oracle.
 //   DiscreteTargetEnv  the same on a DISCRETE action space (SPACE_DISCRETE, A categories; an action is [1,1] = the category index):
 //                  reward 1 when a == argmax_j (W obs)_j with TargetEnv's W, 0 otherwise; episodes of a fixed length (tests/test_discrete_policy.py).
+//   MaskedTargetEnv  DiscreteTargetEnv's task on the same W with state-dependent LEGALITY (the IActionMask mixin, action_mask.hpp): at every step a seeded subset of
+//                  the categories (about half; keyed like the observations, columns obs_dim + j of the same stream) is forbidden, the target category never.
+//                  Reward 1 for the target, 0 for another allowed category, -1 for a forbidden one; the environment counts the forbidden actions it received
+//                  (tests/test_action_mask.py: a masking policy must never send one).
 //   UnitRewardEnv  SeededEnvMock's observation stream, reward 1 on every step, never done by itself: behind a TimeLimit every episode ends by truncation, and
 //                  the value of every state is 1 / (1 - gamma) -- which a critic only learns when the value is bootstrapped there (tests/test_truncation.py).
 //                  reset() does NOT rewind the stream (it moves one draw on): no observation ever comes twice, so nothing tells a critic how far the
@@ -15,6 +19,7 @@
 #pragma once
 #include <cstdint>
 
+#include "action_mask.hpp"
 #include "env.hpp"
 
 class EnvMock : public Env {
@@ -189,6 +194,71 @@ private:
     Mat obs_at(uint32_t step) const { Mat m(1, kDim); for (int j = 0; j < kDim; ++j) m(0, j) = ppo_detail::sym_unit(ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)j)); return m; }
     uint32_t step_;
     float last_rew_;
+    uint64_t key_;
+    int kDim, kAct, len_;
+    std::vector<float> w_;          // [category][obs], row-major
+};
+
+class MaskedTargetEnv : public Env, public IActionMask {
+public:
+    MaskedTargetEnv(uint32_t seed, uint32_t env_id, int obs_dim = 18, int n_actions = 18, int episode_len = 100)
+        : step_(0), last_rew_(0.f), forbidden_(0), key_(ppo_detail::ctr_key(seed, env_id)), kDim(obs_dim), kAct(n_actions), len_(episode_len), w_((size_t)n_actions * obs_dim) {
+        const uint64_t wkey = ppo_detail::splitmix64(((uint64_t)seed << 32) | 0xffffffffull);       // TargetEnv's W
+        for (int j = 0; j < kAct; ++j)
+            for (int k = 0; k < kDim; ++k) w_[(size_t)j * kDim + k] = 0.5f * ppo_detail::sym_unit((uint32_t)(ppo_detail::splitmix64(wkey ^ (((uint64_t)j << 32) | (uint32_t)k)) >> 32));
+    }
+    std::string get_action_space() override { return Env::SPACE_DISCRETE; }
+    std::string get_observation_space() override { return Env::SPACE_CONTINOUS; }
+    int get_action_space_size() override { return kAct; }
+    int get_observation_space_size() override { return kDim; }
+    Mat reset() override { step_ = 0; return obs_at(0); }
+    std::vector<Mat> step(const Mat& actions) override {
+        const int a = (int)actions(0, 0), best = target_at(step_);     // for the observation the action answers
+        const bool legal = a >= 0 && a < kAct && allowed_at(step_, a, best);
+        if (!legal) ++forbidden_;
+        last_rew_ = !legal ? -1.f : a == best ? 1.f : 0.f;
+        ++step_;
+        Mat rew(1, 1), done(1, 1);
+        rew(0, 0) = last_rew_;
+        done(0, 0) = (step_ % (uint32_t)len_ == 0u) ? 1.f : 0.f;
+        std::vector<Mat> out;
+        out.reserve(3);
+        out.push_back(obs_at(step_)); out.push_back(std::move(rew)); out.push_back(std::move(done));
+        return out;
+    }
+    // legality of the categories for the current observation obs_at(step_)
+    Mat get_action_mask() override {
+        Mat m(1, kAct);
+        const int best = target_at(step_);
+        for (int j = 0; j < kAct; ++j) m(0, j) = allowed_at(step_, j, best) ? 1.f : 0.f;
+        return m;
+    }
+    long forbidden_received() const { return forbidden_; }
+    int target() const { return target_at(step_); }
+    Mat get_original_obs() override { return obs_at(step_); }
+    Mat get_original_rew() override { Mat r(1, 1); r(0, 0) = last_rew_; return r; }
+    void serialize(nlohmann::json&) override {}
+    void deserialize(nlohmann::json&) override {}
+    void render() override {}
+    float get_time() override { return 0.f; }
+
+private:
+    Mat obs_at(uint32_t step) const { Mat m(1, kDim); for (int j = 0; j < kDim; ++j) m(0, j) = ppo_detail::sym_unit(ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)j)); return m; }
+    int target_at(uint32_t step) const {
+        const Mat cur = obs_at(step);
+        int best = 0; float best_v = 0.f;
+        for (int j = 0; j < kAct; ++j) {
+            float tgt = 0.f;
+            for (int k = 0; k < kDim; ++k) tgt += w_[(size_t)j * kDim + k] * cur(0, k);
+            if (j == 0 || tgt > best_v) { best = j; best_v = tgt; }
+        }
+        return best;
+    }
+    // the top bit of the stream's word (step, obs_dim + j) forbids category j; the target is always allowed
+    bool allowed_at(uint32_t step, int j, int best) const { return j == best || (ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)(kDim + j)) >> 31) == 0u; }
+    uint32_t step_;
+    float last_rew_;
+    long forbidden_;
     uint64_t key_;
     int kDim, kAct, len_;
     std::vector<float> w_;          // [category][obs], row-major

@@ -9,16 +9,19 @@
 
 #include "../../../include/ppo_hip.h"
 #include "env.hpp"
+#include "action_mask.hpp"
 #include "time_limit.hpp"
 
 // Time-limit truncations (time_limit.hpp): the mixin is forwarded from the wrapped Env when it has one (zeros otherwise).  The terminal observation is forwarded
 // RAW: the library scales it with the statistics as they stand when the rollout is finished (include/ppo_hip.h, ppo_rollout_mark_truncated), and it never
 // enters obs_rms.  normalize_terminal() is for callers outside the HBM-resident loop (Runner::run): the current statistics, no update.
-class EnvNormalize : public Env, public ITimeLimit {
+// Action masks (action_mask.hpp): forwarded from the wrapped Env unchanged (a mask is no observation: nothing is scaled); all ones when it has none.
+class EnvNormalize : public Env, public ITimeLimit, public IActionMask {
 public:
     EnvNormalize(std::unique_ptr<Env> env, ppo_handle* handle, bool training, bool norm_obs = true, bool norm_reward = true,
                  float clip_reward = 10, float clip_obs = 10, float gamma = 0.99f, float epsilon = 1e-8f)
-        : env_(std::move(env)), h_(handle), training_(training), norm_obs_(norm_obs), norm_reward_(norm_reward), tl_(dynamic_cast<ITimeLimit*>(env_.get())) {
+        : env_(std::move(env)), h_(handle), training_(training), norm_obs_(norm_obs), norm_reward_(norm_reward), tl_(dynamic_cast<ITimeLimit*>(env_.get())),
+          am_(dynamic_cast<IActionMask*>(env_.get())) {
         check(ppo_norm_init(h_, env_->get_num_envs(), gamma, clip_obs, clip_reward, epsilon));
         check(ppo_norm_set_flags(h_, norm_obs_ ? 1 : 0, norm_reward_ ? 1 : 0));     // honoured by the device-resident rollout too
     }
@@ -64,6 +67,8 @@ public:
     Mat get_truncated() override { return tl_ ? tl_->get_truncated() : Mat::Zero(get_num_envs(), 1); }
     Mat get_terminal_obs() override { return tl_ ? tl_->get_terminal_obs() : Mat::Zero(get_num_envs(), get_observation_space_size()); }
     bool has_time_limit() override { return tl_ && tl_->has_time_limit(); }
+    Mat get_action_mask() override { return has_action_mask() ? am_->get_action_mask() : Mat::Ones(get_num_envs(), get_action_space_size()); }
+    bool has_action_mask() override { return am_ && am_->has_action_mask(); }
     // [n_envs, obs] raw -> scaled and clipped with the current statistics, which stay as they are
     Mat normalize_terminal(const Mat& raw) {
         if (!norm_obs_) return raw;
@@ -98,4 +103,5 @@ private:
     ppo_handle* h_;
     bool training_, norm_obs_, norm_reward_;
     ITimeLimit* tl_;                  // the wrapped Env's time-limit mixin, or null
+    IActionMask* am_;                 // ... and its action-mask mixin, or null
 };

@@ -33,6 +33,7 @@
 #endif
 
 #include "env.hpp"
+#include "action_mask.hpp"
 #include "time_limit.hpp"
 
 // CPUs this process may actually use: hardware threads, narrowed by the affinity mask and by the cgroup CPU quota
@@ -65,7 +66,9 @@ inline int usable_cpus() {
 
 // Time-limit truncations (time_limit.hpp): children that carry the ITimeLimit mixin (a TimeLimit wrapper, say) are asked after every step; get_truncated() /
 // get_terminal_obs() gather their answers in environment order, children without the mixin report 0.
-class VecEnv : public virtual Env, public ITimeLimit {
+// Action masks (action_mask.hpp): get_action_mask() gathers the children's current masks in environment order on the caller's thread (between steps: the pool is
+// idle); children without the mixin report every category allowed.
+class VecEnv : public virtual Env, public ITimeLimit, public IActionMask {
 public:
     explicit VecEnv(const std::vector<std::shared_ptr<Env>>& envs, int max_workers = 0)
         : envs_(envs), n_(static_cast<int>(envs.size())), generation_(0), terminate_(false), actions_(nullptr),
@@ -75,6 +78,8 @@ public:
         workers_ = std::max(1, std::min(n_, max_workers > 0 ? max_workers : hw));
         tl_.resize(n_, nullptr);
         for (int i = 0; i < n_; ++i) if ((tl_[i] = dynamic_cast<ITimeLimit*>(envs_[i].get()))) any_tl_ = true;
+        am_.resize(n_, nullptr);
+        for (int i = 0; i < n_; ++i) { am_[i] = dynamic_cast<IActionMask*>(envs_[i].get()); if (am_[i] && !am_[i]->has_action_mask()) am_[i] = nullptr; if (am_[i]) any_am_ = true; }
         truncated_ = Mat::Zero(n_, 1);
         if (any_tl_) terminal_obs_ = Mat::Zero(n_, obs_dim_);
         // first guess: 8 chunks per thread; recalibrated from measured time per environment after the first steps
@@ -142,6 +147,12 @@ public:
     Mat get_truncated() override { return truncated_; }
     Mat get_terminal_obs() override { return any_tl_ ? terminal_obs_ : Mat::Zero(n_, obs_dim_); }
     bool has_time_limit() override { return any_tl_; }
+    Mat get_action_mask() override {
+        Mat m = Mat::Ones(n_, get_action_space_size());
+        for (int i = 0; i < n_; ++i) if (am_[i]) { const Mat r = am_[i]->get_action_mask(); mat_set_row(m, i, r.data()); }
+        return m;
+    }
+    bool has_action_mask() override { return any_am_; }
     void serialize(nlohmann::json&) override {}
     void deserialize(nlohmann::json&) override {}
     void render() override { std::cout << "VecEnv::render() not implemented\n"; }
@@ -309,6 +320,8 @@ private:
     Mat observations_, rewards_, dones_, original_rewards_;
     std::vector<ITimeLimit*> tl_;      // per child: its time-limit mixin, or null
     bool any_tl_ = false;
+    std::vector<IActionMask*> am_;     // per child: its action-mask mixin, or null
+    bool any_am_ = false;
     Mat truncated_, terminal_obs_;     // [n, 1], [n, obs] of the last step
     int workers_ = 1, chunk_ = 1, n_chunks_ = 1, steps_ = 0;
     Mode mode_ = RESET;

@@ -19,16 +19,17 @@ public:
     virtual ~MlpPolicy() {}
 
     // output/_action, output/_value_flat, output/_neglogp  (policies.hpp:33-46); noise == nullptr: on-device RNG
-    virtual std::vector<Mat> step(const Mat& obs, const Mat* noise = nullptr) {
+    // mask [n, categories] (a categorical handle; env/action_mask.hpp): the action is sampled among the allowed categories; nullptr: unmasked
+    virtual std::vector<Mat> step(const Mat& obs, const Mat* noise = nullptr, const Mat* mask = nullptr) {
         const int n = static_cast<int>(obs.rows());
         Mat a(n, act_dim_), v(n, 1), nlp(n, 1);
-        check(ppo_step(h_, obs.data(), n, noise ? noise->data() : nullptr, a.data(), v.data(), nlp.data()), "step");
+        check(ppo_step_masked(h_, obs.data(), n, noise ? noise->data() : nullptr, mask ? mask->data() : nullptr, a.data(), v.data(), nlp.data()), "step");
         return {a, v, nlp};
     }
-    // output/_deterministic_action (policies.hpp:49-62)
-    virtual Mat get_deterministic_action(const Mat& obs) {
+    // output/_deterministic_action (policies.hpp:49-62); mask as in step(): the best ALLOWED category
+    virtual Mat get_deterministic_action(const Mat& obs, const Mat* mask = nullptr) {
         Mat a(obs.rows(), act_dim_);
-        check(ppo_act_deterministic(h_, obs.data(), static_cast<int>(obs.rows()), a.data()), "get_action()");
+        check(ppo_act_deterministic_masked(h_, obs.data(), static_cast<int>(obs.rows()), mask ? mask->data() : nullptr, a.data()), "get_action()");
         return a;
     }
     // output/_value_flat (policies.hpp:64-77)

@@ -39,6 +39,13 @@ public:
             throw std::runtime_error(std::string("PPO2: the Env's action space is '") + env.get_action_space() + "' but the handle's policy head is " +
                                      (categorical ? "categorical" : "Gaussian") + " (create the handle with ppo_create_ex and " +
                                      (discrete ? "PPO_ACT_CATEGORICAL" : "PPO_ACT_GAUSSIAN") + ")");
+        // an Env that carries the IActionMask mixin (env/action_mask.hpp): the handle's rollout carries masks from here on, and both loops and eval() pass them
+        IActionMask* am = dynamic_cast<IActionMask*>(&env_);
+        if (am && am->has_action_mask()) {
+            if (!categorical) throw std::runtime_error("PPO2: the Env reports action masks but its action space is not discrete");
+            am_ = am;
+            check(ppo_set_action_masking(h_, 1));
+        }
     }
 
     struct UpdateLog { int fps; float losses[5]; double collect_ms, update_ms; float mean_reward; };     // mean_reward: the rollout's un-normalised rewards (the learning curve)
@@ -138,7 +145,12 @@ public:
     std::string model_filename;
 
     // deterministic action for one observation row (ppo2.hpp:225-237)
-    Mat eval(const Mat& obs) { return act_model_.get_deterministic_action(obs); }
+    // An Env with the IActionMask mixin: the best category its current mask allows (obs is the Env's current observation).
+    Mat eval(const Mat& obs) {
+        if (!am_) return act_model_.get_deterministic_action(obs);
+        const Mat mask = am_->get_action_mask();
+        return act_model_.get_deterministic_action(obs, &mask);
+    }
 
     // save cadence of the reference (ppo2.hpp:256-262, 361-376): a save every ceil(n_updates / num_saves) updates with
     // ids 0, 1, ..., plus a trailing save when the interval does not divide the number of updates
@@ -165,13 +177,14 @@ public:
     }
 
     // PPO2::_train_step (ppo2.hpp:380-471): advantage normalisation over the minibatch, then the train op
+    // (`masks` is the reference's name for the dones; action_masks [n, categories] are the legality masks of an IActionMask Env, or null)
     Mat _train_step(float lr, float cliprange, const Mat& obs, const Mat& returns, const Mat& /*masks*/, const Mat& actions, const Mat& values,
-                    const Mat& neglogpacs) {
+                    const Mat& neglogpacs, const Mat* action_masks = nullptr) {
         const int n = static_cast<int>(obs.rows());
         Mat advs(n, 1), losses(1, 5);
         check(ppo_adv_normalize(h_, returns.data(), values.data(), n, advs.data()));
-        check(ppo_train_step(h_, lr, cliprange, obs.data(), actions.data(), advs.data(), returns.data(), neglogpacs.data(), values.data(), n,
-                             losses.data()));
+        check(ppo_train_step_masked(h_, lr, cliprange, obs.data(), actions.data(), action_masks ? action_masks->data() : nullptr, advs.data(), returns.data(),
+                                    neglogpacs.data(), values.data(), n, losses.data()));
         return losses;
     }
 
@@ -191,13 +204,16 @@ private:
         if (tl && !tl->has_time_limit()) tl = nullptr;
         std::vector<int32_t> tr_ids; std::vector<float> tr_obs;
         const int O = raw.get_observation_space_size();
+        IActionMask* am = am_ ? dynamic_cast<IActionMask*>(&raw) : nullptr;       // the masks of the environments under the normaliser (the same ones)
+        Mat mask;
         for (int update = 1; update <= n_updates; ++update) {
             const auto t0 = clk::now();
             for (int t = 0; t < T; ++t) {
                 std::memcpy(done_tm.data() + (size_t)t * E, dones.data(), sizeof(float) * (size_t)E);
                 const auto p0 = clk::now();
                 const float* eps = explicit_noise ? explicit_noise + ((size_t)(update - 1) * T + t) * E * raw.get_action_space_size() : nullptr;
-                check(ppo_rollout_act(h_, t, eps, actions.data()));
+                if (am) { mask = am->get_action_mask(); check(ppo_rollout_act_masked(h_, t, eps, mask.data(), actions.data())); }
+                else check(ppo_rollout_act(h_, t, eps, actions.data()));
                 const auto p1 = clk::now();
                 std::vector<Mat> r = raw.step(actions);
                 const auto p2 = clk::now();
@@ -244,7 +260,8 @@ private:
             runner.noise = explicit_noise ? explicit_noise + (size_t)(update - 1) * n_batch_ * env_.get_action_space_size() : nullptr;
             const MiniBatch mb = runner.run();
             const auto t1 = clk::now();
-            const auto all = mb.get_train_input();
+            auto all = mb.get_train_input();
+            if (mb.action_masks) all.push_back(mb.action_masks);         // shuffled and sliced with the rows they belong to
             std::vector<int> perm(n_batch_);
             std::iota(perm.begin(), perm.end(), 0);
             num_timesteps_ += n_batch_;
@@ -265,7 +282,7 @@ private:
                         std::memcpy(s.data(), mat_row_ptr(v, start), sizeof(float) * (size_t)batch_size * v.cols());
                         sl.push_back(s);
                     }
-                    const Mat l = _train_step(learning_rate_, cliprange_, sl[0], sl[1], sl[2], sl[3], sl[4], sl[5]);
+                    const Mat l = _train_step(learning_rate_, cliprange_, sl[0], sl[1], sl[2], sl[3], sl[4], sl[5], sl.size() > 6 ? &sl[6] : nullptr);
                     for (int j = 0; j < 5; ++j) acc[j] += l(0, j);
                 }
             }
@@ -313,6 +330,7 @@ private:
 
     ppo_handle* h_;
     Env& env_;
+    IActionMask* am_ = nullptr;       // the Env's action-mask mixin when it reports masks (env/action_mask.hpp), or null
     int world_ = 1, rank_ = 0;
     float gamma_;
     int n_steps_;

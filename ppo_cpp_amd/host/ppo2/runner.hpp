@@ -9,11 +9,13 @@
 
 #include "../env/env.hpp"
 #include "../env/env_normalize.hpp"
+#include "../env/action_mask.hpp"
 #include "../env/time_limit.hpp"
 #include "policies.hpp"
 
 struct MiniBatch {
     std::shared_ptr<Mat> obs, returns, dones, actions, values, neglogpacs, true_rewards, unnormalized_rewards;
+    std::shared_ptr<Mat> action_masks;      // [n_batch, categories] the mask every action was sampled under (an Env with the IActionMask mixin), or null
     std::vector<std::shared_ptr<Mat>> get_train_input() const { return {obs, returns, dones, actions, values, neglogpacs}; }
     std::vector<std::shared_ptr<Mat>> get_1_dims() const { return {returns, dones, values, neglogpacs, true_rewards, unnormalized_rewards}; }
 };
@@ -25,6 +27,8 @@ public:
           dones_(Mat::Zero(num_envs_, 1)) {
         ITimeLimit* tl = dynamic_cast<ITimeLimit*>(&env_);
         tl_ = tl && tl->has_time_limit() ? tl : nullptr;
+        IActionMask* am = dynamic_cast<IActionMask*>(&env_);
+        am_ = am && am->has_action_mask() ? am : nullptr;
     }
 
     MiniBatch run() {
@@ -34,11 +38,14 @@ public:
         std::vector<float> obs((size_t)T * E * O), act((size_t)T * E * W);
         Mat values(T, E), neglogp(T, E), dones(T, E), rewards(T, E), raw_rewards(T, E);
         std::vector<int> trunc_rows; std::vector<float> trunc_obs;
+        std::vector<float> masks(am_ ? (size_t)T * E * A : 0);
         for (int t = 0; t < T; ++t) {
             std::memcpy(&obs[(size_t)t * E * O], obs_.data(), sizeof(float) * (size_t)E * O);
             Mat eps;                                                       // explicit exploration noise of this env step [E, A], if any
             if (noise) { eps = Mat(E, A); std::memcpy(eps.data(), noise + (size_t)t * E * A, sizeof(float) * (size_t)E * A); }
-            const std::vector<Mat> s = model_.step(obs_, noise ? &eps : nullptr);
+            Mat mask;                                                      // legality of the categories for obs_ (action_mask.hpp), kept with the row
+            if (am_) { mask = am_->get_action_mask(); assert(mask.rows() == E && mask.cols() == A); std::memcpy(&masks[(size_t)t * E * A], mask.data(), sizeof(float) * (size_t)E * A); }
+            const std::vector<Mat> s = model_.step(obs_, noise ? &eps : nullptr, am_ ? &mask : nullptr);
             assert(s[0].rows() == E && s[0].cols() == W && s[1].rows() == E && s[2].rows() == E);
             std::memcpy(&act[(size_t)t * E * W], s[0].data(), sizeof(float) * (size_t)E * W);
             mat_set_row(values, t, s[1].data());
@@ -86,6 +93,7 @@ public:
         mb.neglogpacs = flatten(neglogp.data(), T, E, 1);
         mb.true_rewards = flatten(rewards.data(), T, E, 1);
         mb.unnormalized_rewards = flatten(raw_rewards.data(), T, E, 1);
+        if (am_) mb.action_masks = flatten(masks.data(), T, E, A);
         return mb;
     }
 
@@ -115,4 +123,5 @@ private:
     int num_envs_;
     Mat dones_;
     ITimeLimit* tl_ = nullptr;
+    IActionMask* am_ = nullptr;
 };

@@ -393,6 +393,80 @@ int ppo_host_learn_time_limit(const ppo_host_args* a, int time_limit, int bootst
     }
 }
 
+// The learning check of action masks (tests/test_action_mask.py): n_envs x MaskedTargetEnv -> VecEnv -> EnvNormalize -> PPO2::learn with the library's own sampling and
+// shuffles, through the HBM-resident loop (ppo_rollout_act_masked) or, with args->reference_loop, the literal one (ppo_step_masked / ppo_train_step_masked).  args: n_envs,
+// n_steps, hidden, nminibatches, noptepochs, n_updates, lr, cliprange, gamma, lam, norm_obs, norm_reward, seed, obs_dim, act_dim (categories), cliprange_vf, device,
+// max_workers, reference_loop.  reward_curve [n_updates]: mean un-normalised reward of every update's rollout; *forbidden_received: forbidden actions the environments
+// were sent over the whole run (a masking policy sends none); playback_actions / playback_legal [n_playback] (may be null / 0): PPO2::eval on environment 0's
+// stack for n_playback steps after training, and whether the environment's own mask allowed each action.
+int ppo_host_learn_masked(const ppo_host_args* a, float* reward_curve, long long* forbidden_received, int n_playback, float* playback_actions, float* playback_legal,
+                          ppo_host_result* out) {
+    std::memset(out, 0, sizeof *out);
+    ppo_handle* h = nullptr;
+    try {
+        ppo_config cfg;
+        const int O = a->obs_dim > 0 ? a->obs_dim : 18, A = a->act_dim > 0 ? a->act_dim : 18;
+        ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
+        cfg.device = a->device;
+        if (ppo_create_ex(&cfg, PPO_ACT_CATEGORICAL, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
+        std::vector<std::shared_ptr<MaskedTargetEnv>> kids;
+        std::vector<std::shared_ptr<Env>> envs;
+        for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MaskedTargetEnv>(1234u, (uint32_t)i, O, A)); envs.push_back(kids.back()); }
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, a->max_workers)), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
+            struct Plain : Env, IActionMask {       // hides the EnvNormalize type to force the reference loop; the mask mixin stays visible
+                EnvNormalize& e; explicit Plain(EnvNormalize& x) : e(x) {}
+                std::string get_action_space() override { return e.get_action_space(); }
+                std::string get_observation_space() override { return e.get_observation_space(); }
+                int get_action_space_size() override { return e.get_action_space_size(); }
+                int get_observation_space_size() override { return e.get_observation_space_size(); }
+                int get_num_envs() override { return e.get_num_envs(); }
+                Mat reset() override { return e.reset(); }
+                std::vector<Mat> step(const Mat& x) override { return e.step(x); }
+                void render() override {}
+                float get_time() override { return 0; }
+                Mat get_original_obs() override { return e.get_original_obs(); }
+                Mat get_original_rew() override { return e.get_original_rew(); }
+                void serialize(nlohmann::json& j) override { e.serialize(j); }
+                void deserialize(nlohmann::json& j) override { e.deserialize(j); }
+                Mat get_action_mask() override { return e.get_action_mask(); }
+                bool has_action_mask() override { return e.has_action_mask(); }
+            } plain{env};
+            Env& top = a->reference_loop ? static_cast<Env&>(plain) : static_cast<Env&>(env);
+            PPO2 algo{h, top, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange, a->cliprange_vf};
+            if (ppo_get_action_masking(h) != 1) throw std::runtime_error("PPO2 did not turn action masking on for an Env with the IActionMask mixin");
+            algo.quiet = true;
+            algo.seed = a->seed;
+            algo.learn(a->n_updates * a->n_envs * a->n_steps);
+            const auto& hist = algo.history();
+            if (hist.empty()) throw std::runtime_error("no update ran");
+            std::memcpy(out->losses, hist.back().losses, sizeof out->losses);
+            out->fps_last = hist.back().fps;
+            if (reward_curve) for (size_t i = 0; i < hist.size(); ++i) reward_curve[i] = hist[i].mean_reward;
+            long long total = 0;
+            for (const auto& k : kids) total += k->forbidden_received();
+            if (forbidden_received) *forbidden_received = total;
+            // playback: deterministic actions under the environments' masks (the statistics stay as training left them; EnvNormalize keeps updating them here, which the check does not mind)
+            Mat obs = top.reset();
+            for (int t = 0; t < n_playback; ++t) {
+                const Mat mask = env.get_action_mask();
+                const Mat act = algo.eval(obs);
+                const int c = (int)act(0, 0);
+                if (playback_actions) playback_actions[t] = act(0, 0);
+                if (playback_legal) playback_legal[t] = c >= 0 && c < A && mask(0, c) != 0.f ? 1.f : 0.f;
+                obs = top.step(act)[0];
+            }
+        }
+        ppo_destroy(h);
+        return 0;
+    } catch (const std::exception& e) {
+        std::snprintf(out->error, sizeof out->error, "%s", e.what());
+        if (h) ppo_destroy(h);
+        return -1;
+    }
+}
+
 // PPO2::save of a [64,64] Gaussian policy built with `cliprange_vf` under `prefix` (no training), then PPO2::load into a FRESH handle behind a PPO2 built with the
 // default -1: reports the value clipping that the load left on the fresh handle (ppo_get_value_clip).  Returns 0; -1 = error (message on stderr).
 int ppo_host_value_clip_checkpoint(const char* prefix, float cliprange_vf, int32_t* mode, float* range) {

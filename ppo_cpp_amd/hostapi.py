@@ -152,6 +152,35 @@ def learn_time_limit(n_envs, n_steps, hidden, n_updates, nminibatches, noptepoch
     return out
 
 
+def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
+                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0):
+    """PPO2::learn on MaskedTargetEnv x n_envs (host/env/env_mock.hpp: DiscreteTargetEnv's task with about half of the categories forbidden at every step) behind
+    VecEnv + EnvNormalize, with the library's own exploration noise and shuffles (ppo_host_learn_masked).  PPO2 finds the IActionMask mixin and masks by itself.
+    Returns the mean un-normalised reward of every update's rollout [n_updates], the count of forbidden actions the environments received over the whole run, and
+    n_playback deterministic playback actions with their legality."""
+    import numpy as np
+    lib = load_host_library()
+    a = HostArgs()
+    a.n_envs, a.n_steps, a.n_hidden = n_envs, n_steps, len(hidden)
+    for i, h in enumerate(hidden):
+        a.hidden[i] = h
+    a.nminibatches, a.noptepochs, a.n_updates = nminibatches, noptepochs, n_updates
+    a.lr, a.cliprange, a.gamma, a.lam = lr, cliprange, gamma, lam
+    a.seeded_env, a.device, a.max_workers, a.reference_loop = 0, device, 0, int(reference_loop)
+    a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
+    a.obs_dim, a.act_dim = obs_dim, act_dim
+    a.cliprange_vf = cliprange_vf
+    out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros(n_playback, np.float32), "playback_legal": np.zeros(n_playback, np.float32)}
+    forbidden = C.c_longlong(-1)
+    r = HostResult()
+    fp = C.POINTER(C.c_float)
+    if lib.ppo_host_learn_masked(C.byref(a), out["reward_curve"].ctypes.data_as(fp), C.byref(forbidden), int(n_playback), out["playback_actions"].ctypes.data_as(fp),
+                                 out["playback_legal"].ctypes.data_as(fp), C.byref(r)) != 0:
+        raise RuntimeError(r.error.decode())
+    out["forbidden_received"] = int(forbidden.value)
+    return out
+
+
 def value_clip_checkpoint(prefix, cliprange_vf):
     """PPO2::save of a policy built with cliprange_vf, PPO2::load into a fresh handle (ppo_host_value_clip_checkpoint): returns the fresh handle's
     value clipping as (mode, range), mode 0 / 1 / 2 = PPO_VCLIP_POLICY / RANGE / OFF"""
