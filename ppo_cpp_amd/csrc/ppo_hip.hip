@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -2218,8 +2219,6 @@ int ppo_norm_reset_returns(ppo_handle* h) {
 }
 
 // device-side pieces shared by the host-pointer API and the rollout loop
-static int allreduce_f32(ppo_handle* h, float* buf, size_t count) { return enqueue_allreduce(h, buf, count); }
-
 // EnvNormalize::step's statistics + reward branch for one batch of envs: one multi-block launch; with a communicator
 // the ranks' batch moments are exchanged with ONE all-reduce (slot table = all-gather) and a one-block finish, so the
 // running statistics are over the environments of ALL ranks.  obs_dev / rew_dev may be null (job absent).
@@ -2280,7 +2279,7 @@ static int enqueue_norm_batch(ppo_handle* h, const float* obs_dev, int rows, con
       hipLaunchKernelGGL(norm_batch_kernel, dim3(a.g_obs + a.g_rew), dim3(NB_THREADS), 0, h->stream, a);
       HIP_OK(h, hipGetLastError()); }
     if (h->comm) {
-        if (!a.use_peer && allreduce_f32(h, h->stats_xch, xw * h->world)) return -1;
+        if (!a.use_peer && enqueue_allreduce(h, h->stats_xch, xw * h->world)) return -1;
         ProfScope ps(h, PK_STATS);
         hipLaunchKernelGGL(norm_finalize_kernel, dim3(2), dim3(NB_THREADS), 0, h->stream, a);
         HIP_OK(h, hipGetLastError());
@@ -2356,6 +2355,12 @@ static void trunc_clear(ppo_handle* h) {
     h->tr_idx.clear(); h->tr_K = 0; h->obs_t = -1;
 }
 
+// `words` mask entries set to 1.0f: every category allowed
+static int mask_fill_ones(ppo_handle* h, float* p, size_t words) {
+    HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)p, 0x3f800000 /* 1.0f */, words, h->stream));
+    return 0;
+}
+
 int ppo_set_action_masking(ppo_handle* h, int on) {
     if (!h) return fail(nullptr, "ppo_set_action_masking: null handle");
     if (on && need_categorical(h, "ppo_set_action_masking")) return -1;
@@ -2386,10 +2391,7 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
         dev_alloc(h, &h->ro_done, B) || dev_alloc(h, &h->ro_rew, B) || dev_alloc(h, &h->ro_ret, B) ||
         dev_alloc(h, &h->last_val, E) || dev_alloc(h, &h->ro_noise, B * n.A))
         return -1;
-    if (h->masking) {
-        if (dev_alloc(h, &h->ro_mask, B * n.A)) return -1;
-        HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)h->ro_mask, 0x3f800000 /* 1.0f */, B * n.A, h->stream));
-    }
+    if (h->masking && (dev_alloc(h, &h->ro_mask, B * n.A) || mask_fill_ones(h, h->ro_mask, B * n.A))) return -1;
     h->E = E; h->T = T;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     if (h->ro_tval) { (void)hipFree(h->ro_tval); h->ro_tval = nullptr; }
@@ -2469,25 +2471,101 @@ static int enqueue_truncations(ppo_handle* h) {
     return 0;
 }
 
-// Small host-Env rollouts (narrow path, one rank): up to NW_RO_MAX_E environments are served by the resident kernel
-// (narrow_rollout_kernel in host mode), up to NW_ROWS also by one fused launch per env step (narrow_host_step_kernel).  While
-// either is in use ("protocol" mode) ppo_rollout_observe only fills the pinned block: the transition is booked by the next
-// launch / the resident kernel.
+// values of all T x E rollout rows in one batched pass (the rows are already normalised): behind the forms whose kernels run the policy tower only
+static int enqueue_values_all_rows(ppo_handle* h) {
+    StepArgs va{};
+    va.obs = h->ro_obs; va.value = h->ro_val; va.n = h->E * h->T; va.nz = no_norm();
+    return launch_step(h, va);
+}
+
+// ---- which form serves a rollout --------------------------------------------------------------------------------------------------
+// Decided ONCE per call -- host_form for an env step of a host Env (ppo_rollout_act*), dev_form for a rollout on the device env
+// (ppo_collect_synthetic) -- and everything downstream takes the decided value: the kernel, its LDS size, which memory its input block is.
+// host Env: resident in one wave | resident workgroup | narrow_host_step_kernel per env step | general path, the policy kernel publishes the actions | general path, D2H copy
+enum HostForm { HF_RESIDENT1, HF_RESIDENT, HF_FUSED, HF_DIRECT, HF_COPY };
+// device env: the rollout in one wave | in one workgroup | in ceil(E / 32) workgroups | narrow_collect_kernel per env step | policy, env and statistics kernel per env step
+enum DevForm { DF_ROLLOUT1, DF_PERSISTENT, DF_COOP, DF_FUSED, DF_PER_STEP };
+
+// ONE environment on the reference shape (any observation width up to 64, any action width up to 32): a resident rollout runs in one wave,
+// weights in registers (ppo_rollout1.hpp), not in the 32-row workgroup.  (The switch is read per call: the tests compare both forms in one process.)
+static bool use_rollout1(const ppo_handle* h) {
+    const char* e1 = getenv("PPO_HIP_NO_ROLLOUT1");
+    return h->nw_static && h->E == 1 && !(e1 && e1[0] == '1');
+}
+
+// dynamic LDS of narrow_rollout_kernel for the handle's E environments, and of the kernels that hold one group of 32 rows
+// (narrow_host_step_kernel, narrow_rollout_coop_kernel)
+static size_t rollout_lds(const ppo_handle* h) {
+    return ((size_t)h->nw.lds_total + (h->E > NW_ROWS ? nw_ro_extra(h->E, h->net.O) : NW_RO_EXTRA)) * sizeof(float);
+}
+static size_t one_group_lds(const ppo_handle* h) { return ((size_t)h->nw.lds_total + NW_RO_EXTRA) * sizeof(float); }
+
+// Small host-Env handles (narrow path, one rank): up to NW_RO_MAX_E environments are served by the resident kernel, up to NW_ROWS also by
+// one fused launch per env step.  While either is in use ("protocol" mode, h->host_proto) ppo_rollout_observe only fills the pinned
+// block: the transition is booked by the next launch / the resident kernel.  (The LDS bound covers both kernels, whichever serves the step.)
 static bool host_small(const ppo_handle* h) {
     if (h->opt_no_host_fused) return false;
     const NetDev& n = h->net;
     return h->narrow && !h->comm && !h->bf.on && h->E <= NW_RO_MAX_E && n.O <= 64 && n.A <= 64 && h->pin_flag &&
            ((size_t)h->nw.lds_total + std::max(nw_ro_extra(h->E, n.O), NW_RO_EXTRA)) * sizeof(float) <= 160 * 1024;
 }
-static bool host_fused(const ppo_handle* h) { return host_small(h) && h->E <= NW_ROWS; }
+
+// explicit noise (one [E, A] block per call) cannot feed a kernel that is resident over the whole rollout: it leaves the fused step on
+static HostForm host_form(const ppo_handle* h, bool explicit_noise) {
+    if (host_small(h)) {
+        if (!h->opt_no_host_resident && !explicit_noise) return use_rollout1(h) ? HF_RESIDENT1 : HF_RESIDENT;
+        if (h->E <= NW_ROWS) return HF_FUSED;
+    }
+    // policy_step_kernel (the fp32 families wider than 64) can hand the actions over itself: no copy command, no wait for the value tower.  Used for
+    // up to 64 environments only: shader stores into host memory cost ~1 us per 16-row block once more than a few workgroups publish (measured per
+    // env step, direct | copy engine: 64 envs 25.4 | 31.6 us, 256: 45 | 43, 1024: 55 | 49, 4096: 80 | 66 -- profiles/r05_b_*).
+    // PPO_HIP_DIRECT_ACT_MAX_BLOCKS overrides the limit (tests run the form at 256 blocks).
+    const char* dme = getenv("PPO_HIP_DIRECT_ACT_MAX_BLOCKS");                   // (read per call: a test switches it inside one process)
+    const int direct_max = dme ? atoi(dme) : 4;
+    const bool direct = !h->opt_no_direct_act && !h->narrow && !h->bf.on && h->pin_wgflag && (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK <= direct_max;
+    return direct ? HF_DIRECT : HF_COPY;
+}
+
+static DevForm dev_form(const ppo_handle* h) {
+    const NetDev& n = h->net;
+    const int E = h->E, G = (E + NW_ROWS - 1) / NW_ROWS;
+    const bool small_net = h->narrow && !h->comm && n.O <= 64;
+    const char* npe = getenv("PPO_HIP_NO_PERSISTENT_COLLECT");
+    const bool resident = small_net && n.A <= 64 && !(npe && npe[0] == '1');
+    // the whole rollout in ONE launch of one persistent workgroup: state in LDS, only stores leave the CU
+    // (up to NW_RO_MAX_E environments: the one workgroup walks them in groups of 32 rows)
+    if (resident && E <= NW_RO_MAX_E && rollout_lds(h) <= 160 * 1024) return use_rollout1(h) ? DF_ROLLOUT1 : DF_PERSISTENT;
+    // 65..2048 environments: G = ceil(E / 32) resident workgroups, one per CU, meeting once per env step for the statistics
+    if (resident && E > NW_RO_MAX_E && G <= NW_COOP_MAX_G && one_group_lds(h) <= 160 * 1024 &&
+        G * (2 * n.O + 3) <= h->nw.w_total - h->nw.w_fwd)              // the chunks of a step are staged in the image's unused backward half
+        return DF_COOP;
+    // small environment counts on the narrow path: one fused launch per env step (policy step + env + EnvNormalize bookkeeping)
+    if (small_net && E <= NW_ROWS) return DF_FUSED;
+    return DF_PER_STEP;
+}
+
+// ---- argument blocks ------------------------------------------------------------------------------------------------------------------
+static NwEnvState env_state(const ppo_handle* h) {
+    return NwEnvState{h->raw_obs, h->obs_rms.mean, h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->cur_done};
+}
+
+// what NwRolloutArgs, NwCoopArgs and NwHostStepArgs share: the image, the live state, the normaliser's constants and (the two whole-rollout
+// kernels) the rollout buffers; narrow_host_step_kernel takes one row of them, set by its caller
+extern "C++" template <class Q>
+static Q nw_args(const ppo_handle* h) {
+    Q q{};
+    q.img = h->nw_img;
+    q.st = env_state(h);
+    q.gamma = h->nz_gamma; q.clip_rew = h->nz_clip_rew; q.clip_obs = h->nz_clip_obs; q.eps = h->nz_eps; q.norm_obs = h->norm_obs_flag; q.norm_rew = h->norm_rew_flag;
+    if constexpr (!std::is_same<Q, NwHostStepArgs>::value) { q.ro_obs = h->ro_obs; q.ro_act = h->ro_act; q.ro_nlp = h->ro_nlp; q.ro_rew = h->ro_rew; q.ro_done = h->ro_done; }
+    return q;
+}
 
 // one launch of narrow_host_step_kernel: the pending transition's bookkeeping (if any) and, with act, the policy step of row t
 static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_dev, uint32_t rng_step) {
     const NetDev& n = h->net;
     const size_t E = h->E;
-    NwHostStepArgs q{};
-    q.img = h->nw_img;
-    q.st = NwEnvState{h->raw_obs, h->obs_rms.mean, h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->cur_done};
+    NwHostStepArgs q = nw_args<NwHostStepArgs>(h);
     q.host_in = h->pin_in_dev; q.host_act = h->pin_out_dev; q.host_flag = h->pin_flag_dev; q.flag_value = act ? ++h->act_seq : 0u;
     q.noise = noise_dev;
     if (act) { q.ro_obs = h->ro_obs + t * E * n.O; q.ro_act = h->ro_act + t * E * n.A; q.ro_nlp = h->ro_nlp + t * E; q.ro_done = h->ro_done + t * E; }
@@ -2495,8 +2573,7 @@ static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_
     q.ro_rew_prev = h->host_pending ? h->ro_rew + (size_t)h->host_pending_t * E : nullptr;
     q.E = (int)E; q.act = act ? 1 : 0;
     q.seed = h->rng_seed; q.rng_step = rng_step; q.row_base = (uint32_t)(h->rank * h->E);
-    q.gamma = h->nz_gamma; q.clip_rew = h->nz_clip_rew; q.clip_obs = h->nz_clip_obs; q.eps = h->nz_eps; q.norm_obs = h->norm_obs_flag; q.norm_rew = h->norm_rew_flag;
-    const size_t lds = ((size_t)h->nw.lds_total + NW_RO_EXTRA) * sizeof(float);
+    const size_t lds = one_group_lds(h);
     ProfScope ps(h, PK_STEP);
 #define X(a, b, c, d) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, d>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q)
     NW_DISPATCH(h, X);
@@ -2506,13 +2583,10 @@ static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_
     return 0;
 }
 
-static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, size_t lds) {
+// the resident rollout of q.E == h->E environments: in one wave (DF_ROLLOUT1 / HF_RESIDENT1) or in the 32-row workgroup
+static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, bool one_wave) {
     const NetDev& n = h->net;
-    const bool multi = q.E > NW_ROWS;
-    // ONE environment on the device env, reference shape: the whole rollout in one wave, weights in registers (ppo_rollout1.hpp)
-    const char* e1 = getenv("PPO_HIP_NO_ROLLOUT1");               // (read per call: the tests compare both forms in one process)
-    const bool no_r1 = e1 && e1[0] == '1';
-    if (h->nw_static && q.E == 1 && !no_r1) {                      // (any observation width up to 64, any action width up to 32)
+    if (one_wave) {
         ++h->kv[KV_ROLLOUT1];
         if (q.host_mode) {                                          // the same three waves resident behind a host Env (round 5)
             if (n.Kp0 == 32) hipLaunchKernelGGL((narrow_rollout1_kernel<32, true>), dim3(1), dim3(192), 0, h->stream, n, h->nw, q);
@@ -2522,6 +2596,8 @@ static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, size_t 
         else hipLaunchKernelGGL((narrow_rollout1_kernel<64, false>), dim3(1), dim3(192), 0, h->stream, n, h->nw, q);
         return;
     }
+    const bool multi = q.E > NW_ROWS;
+    const size_t lds = rollout_lds(h);
     ++h->kv[KV_ROLLOUT_PERSISTENT];
 #define X(a, b, c, d) do { if (multi) hipLaunchKernelGGL((narrow_rollout_kernel<a, b, c, d, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q); \
                            else hipLaunchKernelGGL((narrow_rollout_kernel<a, b, c, d, false>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q); } while (0)
@@ -2540,25 +2616,21 @@ static void vram_word(ppo_handle* h, unsigned v) {
 // ---- resident host-Env rollout kernel (see NwRolloutArgs) -----------------------------------------------------------------------
 // control words live at pin_flag + 64 (the first line is the per-launch completion word of narrow_host_step_kernel)
 static unsigned* hp_ctl(ppo_handle* h) { return h->pin_flag + 64; }
-static bool host_resident(const ppo_handle* h) { return host_small(h) && !h->opt_no_host_resident; }
-static int hp_launch(ppo_handle* h, int t0, uint32_t rng_step_t0) {
-    const NetDev& n = h->net;
-    NwRolloutArgs q{};
-    q.img = h->nw_img;
-    q.st = NwEnvState{h->raw_obs, h->obs_rms.mean, h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->cur_done};
-    q.ro_obs = h->ro_obs; q.ro_act = h->ro_act; q.ro_nlp = h->ro_nlp; q.ro_rew = h->ro_rew; q.ro_done = h->ro_done;
+// both sequence words and the VRAM inbox's word back to zero: the next rollout counts from clean words
+static void host_words_reset(ppo_handle* h) {
+    if (h->pin_flag) { __atomic_store_n(hp_ctl(h) + PCTL_H2D, 0u, __ATOMIC_RELEASE); __atomic_store_n(hp_ctl(h) + PCTL_D2H, 0u, __ATOMIC_RELEASE); vram_word(h, 0u); }
+}
+static int hp_launch(ppo_handle* h, HostForm form, int t0, uint32_t rng_step_t0) {
+    NwRolloutArgs q = nw_args<NwRolloutArgs>(h);
     q.E = h->E; q.T = h->T; q.seed = h->rng_seed; q.step0 = rng_step_t0 - (uint32_t)t0; q.env0 = h->rank * h->E;
-    q.gamma = h->nz_gamma; q.clip_rew = h->nz_clip_rew; q.clip_obs = h->nz_clip_obs; q.eps = h->nz_eps; q.norm_obs = h->norm_obs_flag; q.norm_rew = h->norm_rew_flag;
     q.host_mode = 1; q.t0 = t0; q.pending = h->host_pending ? 1 : 0;
     q.host_in = h->pin_in_dev; q.host_act = h->pin_out_dev; q.ctl = h->pin_flag_dev + 64;
-    { const char* e1 = getenv("PPO_HIP_NO_ROLLOUT1");
-      if (h->vram_in && h->E == 1 && h->nw_static && !(e1 && e1[0] == '1')) { q.host_in = h->vram_in; q.h2d = h->vram_h2d; } }     // (narrow_rollout1_kernel<.., HOST>: system-scope loads only)
+    if (form == HF_RESIDENT1 && h->vram_in) { q.host_in = h->vram_in; q.h2d = h->vram_h2d; }      // (narrow_rollout1_kernel<.., HOST>: system-scope loads only)
     const char* pc = getenv("PPO_HIP_HOST_POLLS");
     q.poll_cap = pc ? (unsigned)atol(pc) : 150000u;                 // ~2 us per poll over PCIe: a fraction of a second, then the kernel parks itself
     __atomic_store_n(hp_ctl(h) + PCTL_EXIT, 0u, __ATOMIC_RELEASE);
     __atomic_store_n(hp_ctl(h) + PCTL_STOP, 0u, __ATOMIC_RELEASE);
-    const size_t lds = ((size_t)h->nw.lds_total + (h->E > NW_ROWS ? nw_ro_extra(h->E, n.O) : NW_RO_EXTRA)) * sizeof(float);
-    launch_rollout_kernel(h, q, lds);
+    launch_rollout_kernel(h, q, form == HF_RESIDENT1);
     HIP_OK(h, hipGetLastError());
     h->hp_active = true; h->host_pending = false;
     return 0;
@@ -2607,7 +2679,7 @@ int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
     if (h->pin_in_busy) HIP_OK(h, hipStreamSynchronize(h->stream));
     h->pin_in_busy = false; h->host_pending = false; h->hp_posted = 0;
     trunc_clear(h);
-    if (h->pin_flag) { __atomic_store_n(hp_ctl(h) + PCTL_H2D, 0u, __ATOMIC_RELEASE); __atomic_store_n(hp_ctl(h) + PCTL_D2H, 0u, __ATOMIC_RELEASE); vram_word(h, 0u); }
+    host_words_reset(h);
     memcpy(h->pin_in, raw_obs, on * sizeof(float));
     HIP_OK(h, hipMemcpyAsync(h->raw_obs, h->pin_in, on * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_OK(h, hipMemsetAsync(h->nz_ret, 0, (size_t)h->E * sizeof(float), h->stream));          // env_normalize.hpp:114
@@ -2615,6 +2687,91 @@ int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
     h->done_staged = -1;
     if (h->norm_obs_flag && enqueue_norm_batch(h, h->raw_obs, h->E, nullptr, nullptr, 0, nullptr, nullptr)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- one env step of a host Env, per form: each leaves the actions of row t in pin_out (act_direct: in actions_out) -----------------------
+// Spins until ready() holds.  Every poll_mask + 1 polls it asks whether the stream is still alive; a stream that has drained while ready() still
+// does not hold means that the kernel finished without publishing: msg (which may format arg).
+extern "C++" template <class Ready>
+static int host_spin(ppo_handle* h, unsigned long poll_mask, const char* msg, int arg, Ready ready) {
+    for (unsigned long spins = 1; !ready(); ++spins) {
+        if (spins & poll_mask) continue;
+        const hipError_t qe = hipStreamQuery(h->stream);
+        if (qe != hipSuccess && qe != hipErrorNotReady) return fail(h, "ppo_rollout_act: %s", hipGetErrorString(qe));
+        if (qe == hipSuccess && !ready()) return fail(h, msg, arg);
+    }
+    return 0;
+}
+
+// the kernel stays resident over the rollout: actions and transitions travel through the pinned blocks, sequence words
+// order them; (re)launched here when it is not running (first step, or it parked itself after a long host pause)
+static int act_resident(ppo_handle* h, HostForm form, int t) {
+    unsigned* ctl = hp_ctl(h);
+    const uint32_t rng_step = h->rng_calls++;
+    if (t == 0) {
+        // a rollout abandoned without ppo_rollout_finish / _reset (an env exception, say) leaves its kernel resident and its
+        // sequence words raised: retire it, book what it posted, and start this rollout from clean words -- stale actions
+        // must never be handed out for step 0
+        if (h->hp_active || __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) != 0u || __atomic_load_n(ctl + PCTL_H2D, __ATOMIC_ACQUIRE) != 0u) {
+            if (host_quiesce(h)) return -1;
+            HIP_OK(h, hipStreamSynchronize(h->stream));
+            host_words_reset(h);
+        }
+        h->hp_posted = 0;
+    }
+    auto published = [&] { return __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) >= (unsigned)(t + 1); };
+    for (int attempt = 0; ; ++attempt) {
+        if (!h->hp_active) { if (attempt > 3) return fail(h, "ppo_rollout_act: the resident kernel keeps leaving before step %d", t); if (hp_launch(h, form, t, rng_step)) return -1; }
+        // row t is published, or the kernel has left (every million polls: is the stream still alive?)
+        if (host_spin(h, 0xfffff, "ppo_rollout_act: the resident kernel is gone without a report", 0,
+                      [&] { return published() || __atomic_load_n(ctl + PCTL_EXIT, __ATOMIC_ACQUIRE) != 0u; })) return -1;
+        if (published()) return 0;
+        if (hp_retire(h, false)) return -1;                         // it parked itself before producing row t: relaunch from here
+    }
+}
+
+// <= 32 environments on the narrow path: ONE launch does the pending transition's EnvNormalize bookkeeping (read from the
+// pinned block), the policy tower and the action store into pinned memory; the host spins on the completion word
+static int act_fused(ppo_handle* h, int t, const float* noise_dev) {
+    if (enqueue_host_step(h, t, true, noise_dev, h->rng_calls++)) return -1;
+    const unsigned want = h->act_seq;                            // (every ~quarter million polls: is the stream still alive?)
+    return host_spin(h, 0x3ffff, "ppo_rollout_act: the step kernel finished without publishing", 0, [&] { return __atomic_load_n(h->pin_flag, __ATOMIC_ACQUIRE) == want; });
+}
+
+// Watch the table: block b's 16 rows are copied out as soon as its word shows this call's sequence number (the copy of the early blocks
+// hides under the kernel's tail).  The policy kernel is stream-ordered behind the H2D copy of the last observation and the statistics
+// kernel, so once its last block has published, the pinned input block is free again -- without a stream synchronisation.
+static int act_direct(ppo_handle* h, int t, const float* noise_dev, const float* mask_row, float* actions_out) {
+    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), true, mask_row)) return -1;
+    const unsigned want = h->wg_seq;
+    const int G = (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+    const size_t cnt = (size_t)h->E * h->Aw, blk = (size_t)ROWS_PER_BLOCK * h->Aw;
+    for (int b = 0; b < G; ++b) {
+        if (host_spin(h, 0x3ffff, "ppo_rollout_act: the policy kernel finished without publishing block %d", b,
+                      [&] { return __atomic_load_n(h->pin_wgflag + b, __ATOMIC_ACQUIRE) == want; })) return -1;
+        const size_t off = (size_t)b * blk;
+        memcpy(actions_out + off, h->pin_out + off, std::min(blk, cnt - off) * sizeof(float));
+    }
+    return 0;
+}
+
+// one D2H into the handle's pinned landing buffer and the ONLY stream synchronisation of an env step: the statistics
+// kernel of the previous ppo_rollout_observe, this policy step and the copy drain together.  (Round 6 tried a copy-out KERNEL in its place -- 32 workgroups storing
+// 16 bytes per lane into the pinned buffer, a pinned word per slice, the host polling the words instead of the stream: no gain at 4096 environments, 1.25 vs 1.17 ms
+// per 16 env steps on one box, profiles/r06_c_*: this phase is the H2D copy of the last transition + the statistics kernel + the policy kernel in front of the copy,
+// not the copy command.)
+static int act_copy(ppo_handle* h, int t, const float* noise_dev, const float* mask_row) {
+    const size_t cnt = (size_t)h->E * h->Aw;
+    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), false, mask_row)) return -1;
+    HIP_OK(h, hipMemcpyAsync(h->pin_out, h->ro_act + (size_t)t * cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (bf16_chain_err_async(h)) return -1;
+    // busy-wait on the stream: the blocking synchronise parks the thread on an interrupt and wakes it ~100-200 us late,
+    // several times the whole GPU-side cost of an env step; this thread has nothing else to do until the actions are here
+    hipError_t q;
+    int spins = 0;
+    while ((q = hipStreamQuery(h->stream)) == hipErrorNotReady) { if (++spins > 200000) { HIP_OK(h, hipStreamSynchronize(h->stream)); q = hipSuccess; break; } }
+    if (q != hipSuccess) return fail(h, "hipStreamQuery failed: %s", hipGetErrorString(q));
     return 0;
 }
 
@@ -2632,120 +2789,33 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
         // row t of the mask buffer: what was passed, or ones (the plain call on a masking handle: the unmasked kernel, the same bits)
         const size_t mc = (size_t)h->E * h->net.A;
         if (mask) { mask_row = h->ro_mask + (size_t)t * mc; HIP_OK(h, hipMemcpyAsync(mask_row, mask, mc * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
-        else HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ro_mask + (size_t)t * mc), 0x3f800000 /* 1.0f */, mc, h->stream));
+        else if (mask_fill_ones(h, h->ro_mask + (size_t)t * mc, mc)) return -1;
     }
     h->obs_t = -1;                                               // (the pinned mirror no longer vouches for the last transition's dones)
-    const NetDev& n = h->net;
-    const size_t cnt = (size_t)h->E * h->Aw;                 // actions out; the noise is [E, A]
-    float* nd = nullptr;
-    if (noise) { nd = h->ro_noise; HIP_OK(h, hipMemcpyAsync(nd, noise, (size_t)h->E * n.A * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
-    if (host_resident(h) && !noise) {
-        // the kernel stays resident over the rollout: actions and transitions travel through the pinned blocks, sequence words
-        // order them; (re)launched here when it is not running (first step, or it parked itself after a long host pause)
-        unsigned* ctl = hp_ctl(h);
-        const uint32_t rng_step = h->rng_calls++;
-        if (t == 0) {
-            // a rollout abandoned without ppo_rollout_finish / _reset (an env exception, say) leaves its kernel resident and its
-            // sequence words raised: retire it, book what it posted, and start this rollout from clean words -- stale actions
-            // must never be handed out for step 0
-            if (h->hp_active || __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) != 0u || __atomic_load_n(ctl + PCTL_H2D, __ATOMIC_ACQUIRE) != 0u) {
-                if (host_quiesce(h)) return -1;
-                HIP_OK(h, hipStreamSynchronize(h->stream));
-                __atomic_store_n(ctl + PCTL_H2D, 0u, __ATOMIC_RELEASE);
-                __atomic_store_n(ctl + PCTL_D2H, 0u, __ATOMIC_RELEASE);
-                vram_word(h, 0u);
-            }
-            h->hp_posted = 0;
-        }
-        for (int attempt = 0; ; ++attempt) {
-            if (!h->hp_active) { if (attempt > 3) return fail(h, "ppo_rollout_act: the resident kernel keeps leaving before step %d", t); if (hp_launch(h, t, rng_step)) return -1; }
-            bool have = false;
-            for (unsigned long spins = 1; ; ++spins) {
-                if (__atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) >= (unsigned)(t + 1)) { have = true; break; }
-                if (__atomic_load_n(ctl + PCTL_EXIT, __ATOMIC_ACQUIRE)) { have = __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) >= (unsigned)(t + 1); break; }
-                if ((spins & 0xfffff) == 0) {                       // every million polls: is the stream still alive?
-                    const hipError_t qe = hipStreamQuery(h->stream);
-                    if (qe != hipSuccess && qe != hipErrorNotReady) return fail(h, "ppo_rollout_act: %s", hipGetErrorString(qe));
-                    if (qe == hipSuccess && !__atomic_load_n(ctl + PCTL_EXIT, __ATOMIC_ACQUIRE) && __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) < (unsigned)(t + 1))
-                        return fail(h, "ppo_rollout_act: the resident kernel is gone without a report");
-                }
-            }
-            if (have) break;
-            if (hp_retire(h, false)) return -1;                     // it parked itself before producing row t: relaunch from here
-        }
-        h->pin_in_busy = false; h->done_staged = -1; h->host_proto = true;
-        memcpy(actions_out, h->pin_out, cnt * sizeof(float));
-        return 0;
+    float* nd = nullptr;                                         // the noise is [E, A]
+    if (noise) { nd = h->ro_noise; HIP_OK(h, hipMemcpyAsync(nd, noise, (size_t)h->E * h->net.A * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
+
+    const HostForm form = host_form(h, noise != nullptr);
+    if (form > HF_RESIDENT) {
+        // no resident kernel serves this step: one that still runs is asked to leave, and a transition it left unbooked is booked now
+        // unless the fused step does that itself (both are no-ops on a handle that never ran the resident form)
+        if (hp_retire(h, true)) return -1;
+        if (form != HF_FUSED && host_flush_pending(h)) return -1;
     }
-    if (host_small(h)) { if (hp_retire(h, true)) return -1; if (!host_fused(h) && host_flush_pending(h)) return -1; }
-    h->host_proto = host_fused(h);
-    if (host_fused(h)) {
-        // <= 32 environments on the narrow path: ONE launch does the pending transition's EnvNormalize bookkeeping (read from the
-        // pinned block), the policy tower and the action store into pinned memory; the host spins on the completion word
-        if (enqueue_host_step(h, t, true, nd, h->rng_calls++)) return -1;
-        const unsigned want = h->act_seq;
-        unsigned long spins = 0;
-        while (__atomic_load_n(h->pin_flag, __ATOMIC_ACQUIRE) != want) {
-            if ((++spins & 0x3ffff) == 0) {                     // every ~quarter million polls: is the stream still alive?
-                const hipError_t qe = hipStreamQuery(h->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady) return fail(h, "ppo_rollout_act: %s", hipGetErrorString(qe));
-                if (qe == hipSuccess && __atomic_load_n(h->pin_flag, __ATOMIC_ACQUIRE) != want) return fail(h, "ppo_rollout_act: the step kernel finished without publishing");
-            }
-        }
-        h->pin_in_busy = false; h->done_staged = -1;
-        memcpy(actions_out, h->pin_out, cnt * sizeof(float));
-        return 0;
+    h->host_proto = form <= HF_FUSED;                            // the kernel reads the next transition from the pinned block in place: ppo_rollout_observe only posts it
+    int rc = -1;
+    switch (form) {
+        case HF_RESIDENT1:
+        case HF_RESIDENT: rc = act_resident(h, form, t); break;
+        case HF_FUSED: rc = act_fused(h, t, nd); break;
+        case HF_DIRECT: rc = act_direct(h, t, nd, mask_row, actions_out); break;
+        case HF_COPY: rc = act_copy(h, t, nd, mask_row); break;
     }
-    // policy_step_kernel (the fp32 families wider than 64) can hand the actions over itself: no copy command, no wait for the value tower.  Used for
-    // up to 64 environments only: shader stores into host memory cost ~1 us per 16-row block once more than a few workgroups publish (measured per
-    // env step, direct | copy engine: 64 envs 25.4 | 31.6 us, 256: 45 | 43, 1024: 55 | 49, 4096: 80 | 66 -- profiles/r05_b_*).
-    // PPO_HIP_DIRECT_ACT_MAX_BLOCKS overrides the limit (tests run the form at 256 blocks).
-    const char* dme = getenv("PPO_HIP_DIRECT_ACT_MAX_BLOCKS");                   // (read per call: a test switches it inside one process)
-    const int direct_max = dme ? atoi(dme) : 4;
-    const bool direct = !h->opt_no_direct_act && !h->narrow && !h->bf.on && h->pin_wgflag && (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK <= direct_max;
-    if (enqueue_rollout_act(h, t, nd, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), direct, mask_row)) return -1;
-    if (direct) {
-        // Watch the table: block b's 16 rows are copied out as soon as its word shows this call's sequence number (the copy of the early blocks
-        // hides under the kernel's tail).  The policy kernel is stream-ordered behind the H2D copy of the last observation and the statistics
-        // kernel, so once its last block has published, the pinned input block is free again -- without a stream synchronisation.
-        const unsigned want = h->wg_seq;
-        const int G = (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-        const size_t blk = (size_t)ROWS_PER_BLOCK * h->Aw;
-        unsigned long spins = 0;
-        for (int b = 0; b < G; ) {
-            if (__atomic_load_n(h->pin_wgflag + b, __ATOMIC_ACQUIRE) == want) {
-                const size_t off = (size_t)b * blk, cntb = std::min(blk, cnt - off);
-                memcpy(actions_out + off, h->pin_out + off, cntb * sizeof(float));
-                ++b;
-                continue;
-            }
-            if ((++spins & 0x3ffff) == 0) {                     // every ~quarter million polls: is the stream still alive?
-                const hipError_t qe = hipStreamQuery(h->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady) return fail(h, "ppo_rollout_act: %s", hipGetErrorString(qe));
-                if (qe == hipSuccess && __atomic_load_n(h->pin_wgflag + b, __ATOMIC_ACQUIRE) != want) return fail(h, "ppo_rollout_act: the policy kernel finished without publishing block %d", b);
-            }
-        }
-        h->pin_in_busy = false;
-        return 0;
-    }
-    // one D2H into the handle's pinned landing buffer and the ONLY stream synchronisation of an env step: the statistics
-    // kernel of the previous ppo_rollout_observe, this policy step and the copy drain together.  (Round 6 tried a copy-out KERNEL in its place -- 32 workgroups storing
-    // 16 bytes per lane into the pinned buffer, a pinned word per slice, the host polling the words instead of the stream: no gain at 4096 environments, 1.25 vs 1.17 ms
-    // per 16 env steps on one box, profiles/r06_c_*: this phase is the H2D copy of the last transition + the statistics kernel + the policy kernel in front of the copy,
-    // not the copy command.)
-    HIP_OK(h, hipMemcpyAsync(h->pin_out, h->ro_act + (size_t)t * cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (bf16_chain_err_async(h)) return -1;
-    // busy-wait on the stream: the blocking synchronise parks the thread on an interrupt and wakes it ~100-200 us late,
-    // several times the whole GPU-side cost of an env step; this thread has nothing else to do until the actions are here
-    {
-        hipError_t q;
-        int spins = 0;
-        while ((q = hipStreamQuery(h->stream)) == hipErrorNotReady) { if (++spins > 200000) { HIP_OK(h, hipStreamSynchronize(h->stream)); q = hipSuccess; break; } }
-        if (q != hipSuccess) return fail(h, "hipStreamQuery failed: %s", hipGetErrorString(q));
-    }
-    h->pin_in_busy = false;
+    if (rc) return -1;
+    h->pin_in_busy = false;                                      // whatever read the pinned input block has drained
+    if (h->host_proto) h->done_staged = -1;                      // (row t's dones were written by the kernel)
     if (bf16_chain_err_test(h)) return -1;                       // (row t of the rollout is invalid; the message says what happened and what the handle does from now on)
-    memcpy(actions_out, h->pin_out, cnt * sizeof(float));
+    if (form != HF_DIRECT) memcpy(actions_out, h->pin_out, (size_t)h->E * h->Aw * sizeof(float));
     return 0;
 }
 
@@ -2777,16 +2847,11 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
     ENTER(h);
     if (!h->E) return fail(h, "ppo_rollout_finish: no rollout allocated (call ppo_rollout_alloc first)");
     if (host_small(h)) {
-        if (h->hp_active) {
-            // after its last row the resident kernel waits for the last transition, books it and leaves by itself; if the host
-            // stopped early it is asked to leave
-            if (hp_retire(h, h->hp_posted < h->T)) return -1;
-        }
-        if (h->pin_flag) { __atomic_store_n(hp_ctl(h) + PCTL_H2D, 0u, __ATOMIC_RELEASE); __atomic_store_n(hp_ctl(h) + PCTL_D2H, 0u, __ATOMIC_RELEASE); vram_word(h, 0u); }
-        if (host_flush_pending(h)) return -1;                                              // the last transition's bookkeeping
-        StepArgs va{};                                                                     // values of all T x E normalised rows, batched
-        va.obs = h->ro_obs; va.value = h->ro_val; va.n = h->E * h->T; va.nz = no_norm();
-        if (launch_step(h, va)) return -1;
+        // after its last row the resident kernel waits for the last transition, books it and leaves by itself; if the host
+        // stopped early it is asked to leave
+        if (hp_retire(h, h->hp_posted < h->T)) return -1;
+        host_words_reset(h);
+        if (host_flush_pending(h) || enqueue_values_all_rows(h)) return -1;               // the last transition's bookkeeping, then the values
     }
     const bool marks = h->tr_K > 0;                                 // none: the launches of a rollout without time limits, nothing else
     if (marks && enqueue_truncations(h)) { trunc_clear(h); return -1; }
@@ -2833,144 +2898,150 @@ int ppo_rollout_mark_truncated(ppo_handle* h, int32_t t, int32_t count, const in
     return 0;
 }
 
+// ---- a rollout on the device env, per form (ppo_collect_synthetic): rows 0..T-1 of every rollout buffer but the returns --------------------------
+struct CollectIn { uint32_t seed; int env0; uint32_t step0; const float* noise; };      // noise: [T][E][A] on the device, or null -> counter RNG
+
+// the whole rollout in ONE launch (one wave or one workgroup); the value tower runs afterwards, batched over the T x E normalised rows
+static int collect_persistent(ppo_handle* h, DevForm form, const CollectIn& in) {
+    NwRolloutArgs q = nw_args<NwRolloutArgs>(h);
+    q.noise = in.noise;
+    q.E = h->E; q.T = h->T; q.seed = in.seed; q.step0 = in.step0; q.env0 = in.env0;
+#ifdef PPO_STAMPS
+    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
+    q.stamps = g_stamps;
+#endif
+    { ProfScope ps(h, PK_STEP);
+      launch_rollout_kernel(h, q, form == DF_ROLLOUT1);
+      HIP_OK(h, hipGetLastError()); }
+    return enqueue_values_all_rows(h);
+}
+
+// the cooperative kernel's step words [G][16] and, behind them, its error word
+static unsigned* coop_words(ppo_handle* h) { return reinterpret_cast<unsigned*>(h->nw_coop + (size_t)2 * h->nw_coop_G * NW_COOP_PW); }
+
+static int collect_coop(ppo_handle* h, const CollectIn& in) {
+    const NetDev& n = h->net;
+    const int G = (h->E + NW_ROWS - 1) / NW_ROWS;
+    if (h->nw_coop_G != G) {
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        if (dev_alloc(h, &h->nw_coop, (size_t)2 * G * NW_COOP_PW + 16 * (size_t)(G + 1))) return -1;
+        h->nw_coop_G = G;
+    }
+    unsigned* ctl = coop_words(h);
+    HIP_OK(h, hipMemsetAsync(ctl, 0, 16 * (size_t)(G + 1) * sizeof(unsigned), h->stream));
+    NwCoopArgs q = nw_args<NwCoopArgs>(h);
+    q.noise = in.noise;
+    q.E = h->E; q.T = h->T; q.G = G; q.seed = in.seed; q.step0 = in.step0; q.env0 = in.env0;
+    q.part = h->nw_coop; q.arrive = ctl; q.err = ctl + 16 * (size_t)G; q.spin_limit = 4000000u;
+    const size_t lds = one_group_lds(h);
+    ++h->kv[KV_ROLLOUT_COOP];
+    { ProfScope ps(h, PK_STEP);
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_rollout_coop_kernel<a, b, c, d>), dim3(G), dim3(NW_THREADS), lds, h->stream, n, h->nw, q)
+      NW_DISPATCH(h, X);
+#undef X
+      HIP_OK(h, hipGetLastError()); }
+    return enqueue_values_all_rows(h);
+}
+
+// one fused launch per env step (both towers, the env, the EnvNormalize bookkeeping), the state ping-ponging between two sets
+static int collect_fused(ppo_handle* h, const CollectIn& in) {
+    const NetDev& n = h->net;
+    const int E = h->E, T = h->T;
+    if (h->nw_alt_envs != E) {
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        if (dev_alloc(h, &h->nw_alt, (size_t)E * n.O + 2 * n.O + 2 + 2 * (size_t)E) || dev_alloc(h, &h->nw_alt_counts, 2)) return -1;
+        h->nw_alt_envs = E;
+    }
+    float* alt = h->nw_alt;
+    NwEnvState st[2];
+    st[0] = env_state(h);
+    st[1] = NwEnvState{alt, alt + (size_t)E * n.O, alt + (size_t)E * n.O + n.O, h->nw_alt_counts, alt + (size_t)E * n.O + 2 * n.O, alt + (size_t)E * n.O + 2 * n.O + 1,
+                       h->nw_alt_counts + 1, alt + (size_t)E * n.O + 2 * n.O + 2, alt + (size_t)E * n.O + 2 * n.O + 2 + E};
+    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+    for (int t = 0; t < T; ++t) {
+        const NwEnvState& cur = st[t & 1];
+        StepArgs a{};
+        a.theta = h->nw_img; a.obs = cur.raw_obs; a.noise = in.noise ? in.noise + (size_t)t * E * n.A : nullptr;
+        a.action = h->ro_act + (size_t)t * E * n.A; a.value = h->ro_val + (size_t)t * E; a.neglogp = h->ro_nlp + (size_t)t * E;
+        a.obs_out = h->ro_obs + (size_t)t * E * n.O; a.nz = ObsNorm{cur.obs_mean, cur.obs_var, h->nz_eps, h->nz_clip_obs, h->norm_obs_flag}; a.n = E;
+        a.seed = in.seed; a.rng_step = in.step0 + (uint32_t)t; a.row_base = (uint32_t)in.env0;
+        NwCollectArgs c{cur, st[(t + 1) & 1], in.seed, in.step0 + (uint32_t)t + 1u, in.env0, h->nz_gamma, h->nz_clip_rew, h->nz_eps, h->norm_obs_flag, h->norm_rew_flag,
+                        h->ro_rew + (size_t)t * E, h->ro_done + (size_t)t * E};
+        ProfScope ps(h, PK_STEP);
+        ++h->kv[KV_COLLECT_FUSED];
+#define X(p, q_, r, s_) hipLaunchKernelGGL((narrow_collect_kernel<p, q_, r, s_>), dim3(1, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, a, c)
+        NW_DISPATCH(h, X);
+#undef X
+        HIP_OK(h, hipGetLastError());
+    }
+    if (T & 1) {                                           // the live state sits in the second set: bring it home
+        const NwEnvState& s1 = st[1]; const NwEnvState& s0 = st[0];
+        const size_t fb = sizeof(float);
+        HIP_OK(h, hipMemcpyAsync(s0.raw_obs, s1.raw_obs, (size_t)E * n.O * fb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.obs_mean, s1.obs_mean, n.O * fb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.obs_var, s1.obs_var, n.O * fb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.obs_count, s1.obs_count, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.ret_mean, s1.ret_mean, fb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.ret_var, s1.ret_var, fb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.ret_count, s1.ret_count, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.ret, s1.ret, (size_t)E * fb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_OK(h, hipMemcpyAsync(s0.done, s1.done, (size_t)E * fb, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return 0;
+}
+
+// seeded_env_kernel over the handle's environments: the observations of env step `step`, and (rew, done non-null) the transition that led to them
+static int launch_seeded_env(ppo_handle* h, const CollectIn& in, uint32_t step, float* rew, float* done) {
+    const int envW = h->E * (h->net.O + 2);
+    ProfScope ps(h, PK_ENV);
+    hipLaunchKernelGGL(seeded_env_kernel, dim3((envW + 255) / 256), dim3(256), 0, h->stream, in.seed, in.env0, h->E, step, h->net.O, h->raw_obs, rew, done);
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
+// the general path: policy step, env kernel and statistics kernel per env step
+static int collect_per_step(ppo_handle* h, const CollectIn& in) {
+    const size_t EA = (size_t)h->E * h->net.A;
+    for (int t = 0; t < h->T; ++t) {
+        if (enqueue_rollout_act(h, t, in.noise ? in.noise + (size_t)t * EA : nullptr, in.seed, in.step0 + t, (uint32_t)in.env0)) return -1;
+        if (launch_seeded_env(h, in, in.step0 + (uint32_t)t + 1u, h->raw_rew, h->cur_done) || enqueue_observe(h, t)) return -1;
+    }
+    return 0;
+}
+
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first, const float* noise, float gamma, float lam) {
     ENTER(h);
     if (!h->E) return fail(h, "ppo_collect_synthetic: no rollout allocated (call ppo_rollout_alloc first)");
-    const NetDev& n = h->net;
-    const int E = h->E, T = h->T;
-    const int envW = E * (n.O + 2);
-    if (noise) HIP_OK(h, hipMemcpyAsync(h->ro_noise, noise, (size_t)E * T * n.A * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const size_t E = h->E, BA = E * h->T * h->net.A;
+    if (noise) HIP_OK(h, hipMemcpyAsync(h->ro_noise, noise, BA * sizeof(float), hipMemcpyHostToDevice, h->stream));
     // a masking handle: the seeded env has no notion of legality, every row is collected (unmasked kernels) and recorded as all allowed
-    if (h->masking) HIP_OK(h, hipMemsetD32Async((hipDeviceptr_t)h->ro_mask, 0x3f800000 /* 1.0f */, (size_t)E * T * n.A, h->stream));
+    if (h->masking && mask_fill_ones(h, h->ro_mask, BA)) return -1;
+    const CollectIn in{seed, env0, step0, noise ? h->ro_noise : nullptr};
     if (first) {
-        { ProfScope ps(h, PK_ENV);
-          hipLaunchKernelGGL(seeded_env_kernel, dim3((envW + 255) / 256), dim3(256), 0, h->stream, seed, env0, E, step0, n.O, h->raw_obs, (float*)nullptr, (float*)nullptr);
-          HIP_OK(h, hipGetLastError()); }
-        HIP_OK(h, hipMemsetAsync(h->nz_ret, 0, (size_t)E * sizeof(float), h->stream));
-        HIP_OK(h, hipMemsetAsync(h->cur_done, 0, (size_t)E * sizeof(float), h->stream));
+        if (launch_seeded_env(h, in, step0, nullptr, nullptr)) return -1;
+        HIP_OK(h, hipMemsetAsync(h->nz_ret, 0, E * sizeof(float), h->stream));
+        HIP_OK(h, hipMemsetAsync(h->cur_done, 0, E * sizeof(float), h->stream));
         h->done_staged = -1;
-        if (enqueue_norm_batch(h, h->raw_obs, E, nullptr, nullptr, 0, nullptr, nullptr)) return -1;
+        if (enqueue_norm_batch(h, h->raw_obs, (int)E, nullptr, nullptr, 0, nullptr, nullptr)) return -1;
     }
-    // small environment counts on the narrow path: one fused launch per env step (policy step + env + EnvNormalize bookkeeping)
-    const bool fused = h->narrow && !h->comm && E <= NW_ROWS && n.O <= 64;
-    // ... and on top of that the whole rollout in ONE launch of one persistent workgroup (narrow_rollout_kernel): state in LDS,
-    // only stores leave the CU; the value tower runs afterwards, batched over the T x E normalised rows
-    const char* npe = getenv("PPO_HIP_NO_PERSISTENT_COLLECT");
-    const bool no_persist = npe && npe[0] == '1';
-    // (up to NW_RO_MAX_E environments: the one workgroup walks them in groups of 32 rows)
-    const size_t ro_lds = ((size_t)h->nw.lds_total + (E > NW_ROWS ? nw_ro_extra(E, n.O) : NW_RO_EXTRA)) * sizeof(float);
-    const bool persistent = h->narrow && !h->comm && !no_persist && E <= NW_RO_MAX_E && n.O <= 64 && n.A <= 64 && ro_lds <= 160 * 1024;
-    if (persistent) {
-        NwRolloutArgs q{};
-        q.img = h->nw_img;
-        q.st = NwEnvState{h->raw_obs, h->obs_rms.mean, h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->cur_done};
-        q.noise = noise ? h->ro_noise : nullptr;
-        q.ro_obs = h->ro_obs; q.ro_act = h->ro_act; q.ro_nlp = h->ro_nlp; q.ro_rew = h->ro_rew; q.ro_done = h->ro_done;
-        q.E = E; q.T = T; q.seed = seed; q.step0 = step0; q.env0 = env0;
-        q.gamma = h->nz_gamma; q.clip_rew = h->nz_clip_rew; q.clip_obs = h->nz_clip_obs; q.eps = h->nz_eps; q.norm_obs = h->norm_obs_flag; q.norm_rew = h->norm_rew_flag;
-#ifdef PPO_STAMPS
-        if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-        q.stamps = g_stamps;
-#endif
-        { ProfScope ps(h, PK_STEP);
-          launch_rollout_kernel(h, q, ro_lds);
-          HIP_OK(h, hipGetLastError()); }
-        StepArgs va{};                                         // values of all T x E rows: the rows are already normalised
-        va.obs = h->ro_obs; va.value = h->ro_val; va.n = E * T; va.nz = no_norm();
-        if (launch_step(h, va)) return -1;
-        h->done_staged = -1;
+    const DevForm form = dev_form(h);
+    int rc = -1;
+    switch (form) {
+        case DF_ROLLOUT1:
+        case DF_PERSISTENT: rc = collect_persistent(h, form, in); break;
+        case DF_COOP: rc = collect_coop(h, in); break;
+        case DF_FUSED: rc = collect_fused(h, in); break;
+        case DF_PER_STEP: rc = collect_per_step(h, in); break;
     }
-    // 65..2048 environments: G = ceil(E / 32) resident workgroups, one per CU, meeting once per env step for the statistics
-    const int coopG = (E + NW_ROWS - 1) / NW_ROWS;
-    const bool coop = !persistent && h->narrow && !h->comm && !no_persist && E > NW_RO_MAX_E && coopG <= NW_COOP_MAX_G && n.O <= 64 && n.A <= 64 &&
-                      ((size_t)h->nw.lds_total + NW_RO_EXTRA) * sizeof(float) <= 160 * 1024 &&
-                      coopG * (2 * n.O + 3) <= h->nw.w_total - h->nw.w_fwd;             // the chunks of a step are staged in the image's unused backward half
-    if (coop) {
-        const size_t pf = (size_t)2 * coopG * NW_COOP_PW;
-        if (h->nw_coop_G != coopG) {
-            HIP_OK(h, hipStreamSynchronize(h->stream));
-            if (dev_alloc(h, &h->nw_coop, pf + 16 * (size_t)(coopG + 1))) return -1;
-            h->nw_coop_G = coopG;
-        }
-        unsigned* ctl = reinterpret_cast<unsigned*>(h->nw_coop + pf);       // [G][16] step words, then the error word
-        HIP_OK(h, hipMemsetAsync(ctl, 0, 16 * (size_t)(coopG + 1) * sizeof(unsigned), h->stream));
-        NwCoopArgs q{};
-        q.img = h->nw_img;
-        q.st = NwEnvState{h->raw_obs, h->obs_rms.mean, h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->cur_done};
-        q.noise = noise ? h->ro_noise : nullptr;
-        q.ro_obs = h->ro_obs; q.ro_act = h->ro_act; q.ro_nlp = h->ro_nlp; q.ro_rew = h->ro_rew; q.ro_done = h->ro_done;
-        q.E = E; q.T = T; q.G = coopG; q.seed = seed; q.step0 = step0; q.env0 = env0;
-        q.gamma = h->nz_gamma; q.clip_rew = h->nz_clip_rew; q.clip_obs = h->nz_clip_obs; q.eps = h->nz_eps; q.norm_obs = h->norm_obs_flag; q.norm_rew = h->norm_rew_flag;
-        q.part = h->nw_coop; q.arrive = ctl; q.err = ctl + 16 * (size_t)coopG; q.spin_limit = 4000000u;
-        const size_t lds = ((size_t)h->nw.lds_total + NW_RO_EXTRA) * sizeof(float);
-        ++h->kv[KV_ROLLOUT_COOP];
-        { ProfScope ps(h, PK_STEP);
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_rollout_coop_kernel<a, b, c, d>), dim3(coopG), dim3(NW_THREADS), lds, h->stream, n, h->nw, q)
-          NW_DISPATCH(h, X);
-#undef X
-          HIP_OK(h, hipGetLastError()); }
-        StepArgs va{};
-        va.obs = h->ro_obs; va.value = h->ro_val; va.n = E * T; va.nz = no_norm();
-        if (launch_step(h, va)) return -1;
-        h->done_staged = -1;
-    }
-    if (fused && !persistent) {
-        if (h->nw_alt_envs != E) {
-            HIP_OK(h, hipStreamSynchronize(h->stream));
-            if (dev_alloc(h, &h->nw_alt, (size_t)E * n.O + 2 * n.O + 2 + 2 * (size_t)E) || dev_alloc(h, &h->nw_alt_counts, 2)) return -1;
-            h->nw_alt_envs = E;
-        }
-        float* alt = h->nw_alt;
-        NwEnvState st[2];
-        st[0] = NwEnvState{h->raw_obs, h->obs_rms.mean, h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->cur_done};
-        st[1] = NwEnvState{alt, alt + (size_t)E * n.O, alt + (size_t)E * n.O + n.O, h->nw_alt_counts, alt + (size_t)E * n.O + 2 * n.O, alt + (size_t)E * n.O + 2 * n.O + 1,
-                           h->nw_alt_counts + 1, alt + (size_t)E * n.O + 2 * n.O + 2, alt + (size_t)E * n.O + 2 * n.O + 2 + E};
-        const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-        for (int t = 0; t < T; ++t) {
-            const NwEnvState& in = st[t & 1];
-            StepArgs a{};
-            a.theta = h->nw_img; a.obs = in.raw_obs; a.noise = noise ? h->ro_noise + (size_t)t * E * n.A : nullptr;
-            a.action = h->ro_act + (size_t)t * E * n.A; a.value = h->ro_val + (size_t)t * E; a.neglogp = h->ro_nlp + (size_t)t * E;
-            a.obs_out = h->ro_obs + (size_t)t * E * n.O; a.nz = ObsNorm{in.obs_mean, in.obs_var, h->nz_eps, h->nz_clip_obs, h->norm_obs_flag}; a.n = E;
-            a.seed = seed; a.rng_step = step0 + (uint32_t)t; a.row_base = (uint32_t)env0;
-            NwCollectArgs c{in, st[(t + 1) & 1], seed, step0 + (uint32_t)t + 1u, env0, h->nz_gamma, h->nz_clip_rew, h->nz_eps, h->norm_obs_flag, h->norm_rew_flag,
-                            h->ro_rew + (size_t)t * E, h->ro_done + (size_t)t * E};
-            ProfScope ps(h, PK_STEP);
-            ++h->kv[KV_COLLECT_FUSED];
-#define X(p, q_, r, s_) hipLaunchKernelGGL((narrow_collect_kernel<p, q_, r, s_>), dim3(1, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, a, c)
-            NW_DISPATCH(h, X);
-#undef X
-            HIP_OK(h, hipGetLastError());
-        }
-        if (T & 1) {                                           // the live state sits in the second set: bring it home
-            const NwEnvState& s1 = st[1]; const NwEnvState& s0 = st[0];
-            const size_t fb = sizeof(float);
-            HIP_OK(h, hipMemcpyAsync(s0.raw_obs, s1.raw_obs, (size_t)E * n.O * fb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.obs_mean, s1.obs_mean, n.O * fb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.obs_var, s1.obs_var, n.O * fb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.obs_count, s1.obs_count, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.ret_mean, s1.ret_mean, fb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.ret_var, s1.ret_var, fb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.ret_count, s1.ret_count, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.ret, s1.ret, (size_t)E * fb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(h, hipMemcpyAsync(s0.done, s1.done, (size_t)E * fb, hipMemcpyDeviceToDevice, h->stream));
-        }
-        h->done_staged = -1;
-    }
-    for (int t = 0; t < T && !fused && !persistent && !coop; ++t) {
-        if (enqueue_rollout_act(h, t, noise ? h->ro_noise + (size_t)t * E * n.A : nullptr, seed, step0 + t, (uint32_t)env0)) return -1;
-        { ProfScope ps(h, PK_ENV);
-          hipLaunchKernelGGL(seeded_env_kernel, dim3((envW + 255) / 256), dim3(256), 0, h->stream, seed, env0, E, step0 + (uint32_t)t + 1u, n.O, h->raw_obs, h->raw_rew, h->cur_done);
-          HIP_OK(h, hipGetLastError()); }
-        if (enqueue_observe(h, t)) return -1;
-    }
+    if (rc) return -1;
+    h->done_staged = -1;                                         // (no row of the next rollout's dones is staged)
     if (enqueue_finish(h, gamma, lam) || bf16_chain_err_async(h)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     prof_collect(h);
     if (bf16_chain_err_test(h)) return -1;                       // (the rollout is invalid)
-    if (coop) {
+    if (form == DF_COOP) {
         unsigned e = 0;
-        HIP_OK(h, hipMemcpy(&e, reinterpret_cast<unsigned*>(h->nw_coop + (size_t)2 * coopG * NW_COOP_PW) + 16 * (size_t)coopG, sizeof e, hipMemcpyDeviceToHost));
+        HIP_OK(h, hipMemcpy(&e, coop_words(h) + 16 * (size_t)h->nw_coop_G, sizeof e, hipMemcpyDeviceToHost));
         if (e) return fail(h, "ppo_collect_synthetic: workgroup %u of the cooperative rollout gave up waiting for the others", e - 1);
     }
     return peer_check(h);
@@ -3109,8 +3180,8 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
                     ea.phase = phase;
                     hipLaunchKernelGGL(epoch_prepare_kernel, dim3(nmb), dim3(EP_THREADS), 0, h->stream, ea);
                     HIP_OK(h, hipGetLastError());
-                    if (phase == 1 && allreduce_f32(h, h->adv_xch, (size_t)nmb)) return -1;
-                    if (phase == 2 && allreduce_f32(h, h->adv_xch + ru(nmb, 4), (size_t)nmb)) return -1;
+                    if (phase == 1 && enqueue_allreduce(h, h->adv_xch, (size_t)nmb)) return -1;
+                    if (phase == 2 && enqueue_allreduce(h, h->adv_xch + ru(nmb, 4), (size_t)nmb)) return -1;
                 }
             }
         }
