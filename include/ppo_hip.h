@@ -73,9 +73,18 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
  *                        logits l = h_L W_pi + b_pi, a = argmax_j (l_j - log(-log u_j)), neglogp = softmax cross-entropy against one_hot(a)).
  *                        An action is ONE float per row holding the category index ("categorical handle" below).  PPO_F32 only: PPO_BF16
  *                        is refused.  It runs the generic fp32 kernel families.  Errors: act_dim < 2, an unknown
- *                        action_dist, PPO_BF16. */
+ *                        action_dist, PPO_BF16.
+ * A flag may be OR-ed into action_dist:
+ *   PPO_ACT_SHAPE_KERNELS  PPO_ACT_CATEGORICAL | PPO_ACT_SHAPE_KERNELS lets a categorical PPO_F32 handle take the narrow LDS-resident family when its
+ *                        shape qualifies as a Gaussian handle's would (every hidden width <= 64, padded observation and category widths <= 64, the
+ *                        image fits 160 KB, PPO_HIP_NO_NARROW unset): one policy-step launch per env step ("narrow_step_kernel<cat>",
+ *                        "narrow_step_kernel<cat,mask>") and narrow_train_kernel<cat[,mask]> + narrow_reduce_kernel + adam_kernel per train step.  A
+ *                        shape that does not qualify runs the generic categorical kernels, as without the flag.  With PPO_ACT_GAUSSIAN the flag is
+ *                        accepted and changes nothing.  Not the default (opt-in); data parallel is not available to such a handle: ppo_dist_init
+ *                        refuses it.  ppo_action_dist reports the low bits only. */
 #define PPO_ACT_GAUSSIAN    0
 #define PPO_ACT_CATEGORICAL 1
+#define PPO_ACT_SHAPE_KERNELS 0x100
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out);
 int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL */
 void ppo_destroy(ppo_handle* h);
@@ -274,6 +283,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t noptepochs, int
  * ppo_train_step / ppo_update all-reduce (sum) the flat gradient + loss sums across ranks between the backward
  * and the clip+Adam launches, and ppo_norm_* merge their batch moments across ranks. */
 int ppo_dist_unique_id(char uid[128]);
+/* (a categorical handle created with PPO_ACT_SHAPE_KERNELS is refused: "... data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
 int ppo_dist_world(const ppo_handle* h);
 /* What a reader of a scaling run needs in order to check the ranks (all out-pointers optional): the number of ranks the
@@ -326,7 +336,7 @@ int ppo_prof_read(ppo_handle* h, int max, char names[][32], double* total_ms, in
 int ppo_sync(ppo_handle* h);
 /* which kernel VARIANT the calls so far took: the library picks its kernels from the shape, and a caller or a
  * test can ask which ones were ENQUEUED since ppo_create (a hipGraph capture counts once, its replays do not).  names: e.g.
- * "train8_kernel", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
+ * "train8_kernel", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
 int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued);
 
 /* ---- debug: a raw device buffer by name, padding included (the getters above copy the dense part of every tensor) ----------------

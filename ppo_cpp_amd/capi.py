@@ -55,6 +55,7 @@ def _f32(a, shape=None):
 
 
 ACTION_DISTS = {"gaussian": 0, "categorical": 1}        # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL
+ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS, OR-ed into ppo_create_ex's action_dist
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -65,6 +66,8 @@ class PPOHip:
     action_dist="categorical": act_dim is the number of categories; actions are (n,) float category indices
     (step / act_deterministic / rollout_act return them, train_step takes them, rollout_get("actions") is [T, E]);
     explicit noise keeps the Gaussian's shape and holds the uniforms of the Gumbel-argmax draw.
+    shape_kernels=True (PPO_ACT_SHAPE_KERNELS; default False): a categorical handle whose shape qualifies (every hidden width <= 64, ...)
+    runs the narrow LDS-resident kernels instead of the generic ones; any other shape, and a Gaussian handle, are not affected.
 
     Action masks (categorical only; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -74,7 +77,7 @@ class PPOHip:
     MASK_FIELDS = {"masks": 8}                  # [T, E, A]; a masking handle only (set_action_masking)
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
-    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", **overrides):
+    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, **overrides):
         self.lib = load_library()
         cfg = PPOConfig()
         hid = (C.c_int32 * len(hidden))(*hidden)
@@ -87,9 +90,10 @@ class PPOHip:
         if action_dist not in ACTION_DISTS:
             raise ValueError("action_dist must be one of %s, not %r" % (sorted(ACTION_DISTS), action_dist))
         self.action_dist = action_dist
+        self.shape_kernels = bool(shape_kernels)
         self._act_shape = (act_dim,) if action_dist == "gaussian" else ()      # per row
         h = C.c_void_p()
-        if self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist], C.byref(h)) != 0:
+        if self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)

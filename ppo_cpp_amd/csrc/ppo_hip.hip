@@ -52,7 +52,8 @@ const char* kProfNames[PK_COUNT] = {"policy_step", "train_fwd_bwd", "weight_grad
 // which kernel VARIANT a call took (ppo_kernel_counts): the fast paths are chosen by shape, and a test must be able to say which one ran
 enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN, KV_NARROW_STEP_STATIC, KV_NARROW_STEP,
                      KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH,
-                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_POLICY_STEP_CAT_MASK, KV_TRAIN_FB_CAT_MASK, KV_STEP_HOST_ACTION, KV_COUNT };
+                     KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_POLICY_STEP_CAT_MASK, KV_TRAIN_FB_CAT_MASK, KV_STEP_HOST_ACTION,
+                     KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -60,7 +61,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "policy_step_kernel<cat>", "train_fwd_bwd_kernel<cat>",
                                        "gae_kernel<trunc>", "gae_long_kernel<trunc>", "tval_scatter_kernel",
                                        "policy_step_kernel<cat,mask>", "train_fwd_bwd_kernel<cat,mask>",
-                                       "policy_step_kernel<host_action>" /* launches (of any head) that published their actions to the host themselves */};
+                                       "policy_step_kernel<host_action>" /* launches (of any head) that published their actions to the host themselves */,
+                                       // a categorical handle created with PPO_ACT_SHAPE_KERNELS on a narrow shape (static and runtime-shape instantiations share a name)
+                                       "narrow_step_kernel<cat>", "narrow_step_kernel<cat,mask>", "narrow_train_kernel<cat>", "narrow_train_kernel<cat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -85,6 +88,7 @@ struct ppo_handle {
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
+    bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical handle may take the narrow family (build_narrow_layout)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian) or 1 (categorical: the category index)
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
     // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
@@ -518,7 +522,7 @@ int build_layout(ppo_handle* h) {
 void build_narrow_layout(ppo_handle* h) {
     const NetDev& n = h->net;
     h->narrow = false;
-    if (h->bf.on || h->dist != PPO_ACT_GAUSSIAN || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
+    if (h->bf.on || (h->dist != PPO_ACT_GAUSSIAN && !h->shape_kernels) || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
     for (int l = 0; l < n.L; ++l) if (n.Hp[l] > 64) return;
     const char* off = getenv("PPO_HIP_NO_NARROW");
     if (off && off[0] == '1') return;
@@ -540,8 +544,10 @@ void build_narrow_layout(ppo_handle* h) {
     lay.ldm = n.Ap + NW_XPAD;
     lay.mu = p; p += 16 * lay.ldm;
     lay.dmu = p; p += 16 * lay.ldm;
-    lay.acts = p; p += 16 * n.Ap;
-    lay.dls = p; p += 16 * n.Ap;
+    // actions and d logstd share ONE tile: element (r, j) of both belongs to the same lane of the loss block, which reads its action in the first pass (and keeps what
+    // it needs in registers) and stores d logstd there in the second; the next rows' actions arrive behind the train body's last read of the tile (nw_stage before it,
+    // narrow_epoch_kernel behind its barrier).  16 Ap floats per pipe less: 50 observations with 40 categories ([64,64]) fit the 160 KB with it
+    lay.acts = p; lay.dls = p; p += 16 * n.Ap;
     lay.rowv = p; p += 32;
     lay.misc = p; p += 64;
     lay.pipe_total = ru(p, 4);
@@ -1042,6 +1048,12 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 // X(KP0, HP, AP, L) is the launch statement
 #define NW_DISPATCH(h, X) do { if (!(h)->nw_static) { X(0, 0, 0, 0); } else if ((h)->net.Kp0 == 32) { X(32, 64, 32, 2); } else { X(64, 64, 32, 2); } } while (0)
 
+// a categorical handle on the narrow family (created with PPO_ACT_SHAPE_KERNELS, qualifying shape).  It runs narrow_step_kernel / narrow_train_kernel<cat[,mask]>
+// only: every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the fused host step) asks
+// nw_gauss() where it is decided.
+static bool nw_cat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_CATEGORICAL; }
+static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
+
 template <int CT, int KS, int CTH, bool WIDE, bool CAT = false, bool MASK = false>
 void launch_step_t(ppo_handle* h, const StepArgs& a0) {
     StepArgs a = a0;
@@ -1056,6 +1068,20 @@ int launch_step(ppo_handle* h, const StepArgs& a) {
     if (h->bf.on) { ++h->kv[KV_BF16_STEP]; return launch_step_bf16(h, a); }
     ProfScope ps(h, PK_STEP);
     if (a.mask && h->dist != PPO_ACT_CATEGORICAL) return fail(h, "policy step: an action mask needs a categorical handle");
+    if (nw_cat(h)) {                                              // narrow family, categorical head (PPO_ACT_SHAPE_KERNELS)
+        ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : KV_NARROW_STEP_CAT];
+        dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
+        StepArgs sa = a;
+        sa.theta = h->nw_img;
+        const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, true, true>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
+#define Y(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, true>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
+        if (sa.mask) NW_DISPATCH(h, X); else NW_DISPATCH(h, Y);
+#undef X
+#undef Y
+        HIP_OK(h, hipGetLastError());
+        return 0;
+    }
     if (a.mask) {
         ++h->kv[KV_POLICY_STEP_CAT_MASK];
         if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true, true, true>(h, a); else launch_step_t<1, 1, 0, true, true, true>(h, a); }
@@ -1322,15 +1348,22 @@ int enqueue_train(ppo_handle* h, TrainArgs ta, float* loss_row, bool defer = fal
         {
             ProfScope ps(h, PK_TRAIN_FB);
             NwTrainArgs na{h->nw_img, ta.obs, ta.actions, ta.advs, ta.returns, ta.old_values, ta.old_neglogp, h->hyper, ta.n, ta.inv_n,
-                           h->nw_partials, groups, h->nw_stride, nullptr};
+                           h->nw_partials, groups, h->nw_stride, nullptr, ta.mask};
 #ifdef PPO_STAMPS
             if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
             na.stamps = g_stamps;
 #endif
             const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
             NwLazyArgs z{};
-            ++h->kv[h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
-            if (h->nw_pending) {
+            ++h->kv[nw_cat(h) ? (ta.mask ? KV_NARROW_TRAIN_CAT_MASK : KV_NARROW_TRAIN_CAT) : h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
+            if (nw_cat(h)) {                                      // (never deferred: nw_lazy is a Gaussian handle's)
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z)
+#define Y(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z)
+                if (na.mask) NW_DISPATCH(h, X); else NW_DISPATCH(h, Y);
+#undef X
+#undef Y
+            }
+            else if (h->nw_pending) {
                 // the previous step's clip + Adam rides in this launch: read set nw_cur, write the other one
                 float* set[2][3] = {{h->theta, h->adam_m, h->adam_v}, {h->nw_theta1, h->nw_m1, h->nw_v1}};
                 const int ci = h->nw_cur, co = ci ^ 1;
@@ -1636,8 +1669,10 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     *out = nullptr;
     if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
     if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
+    const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the one flag; whatever else is left must be a distribution
+    action_dist &= ~(int32_t)PPO_ACT_SHAPE_KERNELS;
     if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL)
-        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL)", (int)action_dist);
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16)
@@ -1650,6 +1685,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     ppo_handle* h = new ppo_handle();
     h->cfg = *cfg;
     h->dist = action_dist;
+    h->shape_kernels = shape_kernels && action_dist == PPO_ACT_CATEGORICAL;       // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
     h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : cfg->act_dim;
     int dev = cfg->device;
     if (dev < 0) { const char* lr = getenv("LOCAL_RANK"); dev = lr ? atoi(lr) % ndev : 0; }
@@ -1746,6 +1782,12 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
                            big_lds((const void*)narrow_rollout_coop_kernel<a, b, c, d>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d>); } while (0)
         X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
+        if (nw_cat(h)) {
+#define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true>); \
+                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true>); } while (0)
+            X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
+#undef X
+        }
         big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true>);
         big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true, true>);
         big_lds((const void*)narrow_epoch_kernel<32, false>); big_lds((const void*)narrow_epoch_kernel<64, false>);
@@ -1756,7 +1798,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
         { const char* e1 = getenv("PPO_HIP_NO_HOST_FUSED"); const char* e2 = getenv("PPO_HIP_NO_HOST_RESIDENT");
           h->opt_no_host_fused = e1 && e1[0] == '1'; h->opt_no_host_resident = e2 && e2[0] == '1'; }
         const char* nl = getenv("PPO_HIP_NO_LAZY_ADAM");
-        if (h->nw_static && !(nl && nl[0] == '1')) {       // (the static shapes: [64,64] behind a 32- or 64-column observation tile -- 18 / 36 observations -- and 32 action columns)
+        if (h->nw_static && nw_gauss(h) && !(nl && nl[0] == '1')) {       // (the static shapes: [64,64] behind a 32- or 64-column observation tile -- 18 / 36 observations -- and 32 action columns)
             // second parameter / moment set of the deferred Adam (zero-filled: the padding elements are never written and must read 0)
             if (dev_alloc(h, &h->nw_theta1, P) || dev_alloc(h, &h->nw_m1, P) || dev_alloc(h, &h->nw_v1, P)) return bail(0);
             h->nw_lazy = true;
@@ -2187,7 +2229,7 @@ int ppo_norm_init(ppo_handle* h, int32_t n_envs, float gamma, float clip_obs, fl
         if (h->vram_in) { (void)hipFree(h->vram_in); h->vram_in = nullptr; h->vram_h2d = nullptr; }
         int large_bar = 0;
         const char* nv = getenv("PPO_HIP_NO_VRAM_INBOX");
-        if (n_envs == 1 && h->narrow && h->nw_static && !(nv && nv[0] == '1') &&
+        if (n_envs == 1 && nw_gauss(h) && h->nw_static && !(nv && nv[0] == '1') &&
             hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) == hipSuccess && large_bar) {
             const size_t words = ru((int)in_n, 32) + 64;
             float* box = nullptr;
@@ -2490,7 +2532,7 @@ enum DevForm { DF_ROLLOUT1, DF_PERSISTENT, DF_COOP, DF_FUSED, DF_PER_STEP };
 // weights in registers (ppo_rollout1.hpp), not in the 32-row workgroup.  (The switch is read per call: the tests compare both forms in one process.)
 static bool use_rollout1(const ppo_handle* h) {
     const char* e1 = getenv("PPO_HIP_NO_ROLLOUT1");
-    return h->nw_static && h->E == 1 && !(e1 && e1[0] == '1');
+    return h->nw_static && nw_gauss(h) && h->E == 1 && !(e1 && e1[0] == '1');
 }
 
 // dynamic LDS of narrow_rollout_kernel for the handle's E environments, and of the kernels that hold one group of 32 rows
@@ -2506,7 +2548,7 @@ static size_t one_group_lds(const ppo_handle* h) { return ((size_t)h->nw.lds_tot
 static bool host_small(const ppo_handle* h) {
     if (h->opt_no_host_fused) return false;
     const NetDev& n = h->net;
-    return h->narrow && !h->comm && !h->bf.on && h->E <= NW_RO_MAX_E && n.O <= 64 && n.A <= 64 && h->pin_flag &&
+    return nw_gauss(h) && !h->comm && !h->bf.on && h->E <= NW_RO_MAX_E && n.O <= 64 && n.A <= 64 && h->pin_flag &&
            ((size_t)h->nw.lds_total + std::max(nw_ro_extra(h->E, n.O), NW_RO_EXTRA)) * sizeof(float) <= 160 * 1024;
 }
 
@@ -2529,7 +2571,7 @@ static HostForm host_form(const ppo_handle* h, bool explicit_noise) {
 static DevForm dev_form(const ppo_handle* h) {
     const NetDev& n = h->net;
     const int E = h->E, G = (E + NW_ROWS - 1) / NW_ROWS;
-    const bool small_net = h->narrow && !h->comm && n.O <= 64;
+    const bool small_net = nw_gauss(h) && !h->comm && n.O <= 64;          // (the resident / fused rollout kernels keep a Gaussian head)
     const char* npe = getenv("PPO_HIP_NO_PERSISTENT_COLLECT");
     const bool resident = small_net && n.A <= 64 && !(npe && npe[0] == '1');
     // the whole rollout in ONE launch of one persistent workgroup: state in LDS, only stores leave the CU
@@ -3428,6 +3470,7 @@ struct UidByValue { char b[128]; };
 
 int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128]) {
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
+    if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (load_rccl(h->rccl, h->err)) return -1;
     HIP_OK(h, hipSetDevice(h->device));
     UidByValue u;

@@ -52,6 +52,7 @@ struct NwTrainArgs {
     float* partials;               // [2 towers][n_groups][part_stride]; a workgroup writes its tower's tensors + 8 tail floats
     int n_groups; int part_stride;
     unsigned long long* stamps;    // diagnostic builds only (-DPPO_STAMPS): [workgroups][32] cycle stamps
+    const float* mask;             // [n][A] action masks in minibatch order (non-zero = allowed); read by the <.., CAT, MASK> instantiations only
 };
 #ifdef PPO_STAMPS
 #define NSTAMP(i) do { if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 32 + (i)] = __builtin_readcyclecounter(); } while (0)
@@ -112,11 +113,18 @@ __device__ __forceinline__ void nw_dense(const float* Xs, int ldx, int K, const 
 
 // block prologue: the tower's packed weight image (flat copy) + this workgroup's rows, every global load issued before the
 // first LDS store: one memory round trip
-template <class S>
+// CAT (mode 1, the train kernel's policy tower): `actions` is ONE float per row (the category index); it lands in the first padding column of the row in the pipe's
+// `mu` tile (column Ap of ldm = Ap + NW_XPAD: no product reads or writes it), requested with the row values.  MASK: the [rows][A] tile the Gaussian head fills with
+// actions holds the rows' action masks instead (same loads, same tile: `acts`).  Neither costs LDS.
+template <class S, bool CAT = false, bool MASK = false>
 __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay, const float* __restrict__ img, int n_img, float* lds,
                                          const float* __restrict__ obs, int row0, int nrows, ObsNorm nz, float* __restrict__ obs_out, int tower,
-                                         const float* __restrict__ actions, const float* __restrict__ v0, const float* __restrict__ v1, int mode, const int tidx = (int)threadIdx.x) {
+                                         const float* __restrict__ actions, const float* __restrict__ v0, const float* __restrict__ v1, int mode, const int tidx = (int)threadIdx.x,
+                                         const float* __restrict__ mask = nullptr) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     const int tid = tidx;
+    const float* __restrict__ tile_src = MASK ? mask : actions;   // what fills the [rows][A] tile
+    constexpr bool TILE = !CAT || MASK;
     constexpr int WV = 16 / NW_PIPES;                       // float4 loads per thread: 64 KB in flight covers the image
     float4 wv[WV];
     const int n4 = n_img / 4;
@@ -127,7 +135,7 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
         if (e < n4) wv[k] = reinterpret_cast<const float4*>(img)[e];
     }
     constexpr int OV = 2;
-    float ov[OV], av[OV], r0 = 0.f, r1 = 0.f;
+    float ov[OV], av[OV], r0 = 0.f, r1 = 0.f, r2 = 0.f;
     const int O = net.O, A = net.A, Kp0 = S::Kp0(net), Ap = S::Ap(net);
 #pragma unroll
     for (int k = 0; k < OV; ++k) {
@@ -136,16 +144,19 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
         ov[k] = 0.f;
         if (i < NW_ROWS * Kp0 && row < nrows && j < O) ov[k] = obs[(size_t)row * O + j];
     }
-    if (mode == 1) {
+    if (TILE && mode == 1) {
 #pragma unroll
         for (int k = 0; k < OV; ++k) {
             const int i = tid + NW_THREADS * k;
             const int r = i / Ap, j = i - r * Ap, row = row0 + r;
             av[k] = 0.f;
-            if (i < NW_ROWS * Ap && row < nrows && j < A) av[k] = actions[(size_t)row * A + j];
+            if (i < NW_ROWS * Ap && row < nrows && j < A) av[k] = tile_src[(size_t)row * A + j];
         }
     }
-    if (mode && tid < NW_ROWS && row0 + tid < nrows) { r0 = v0[row0 + tid]; r1 = v1[row0 + tid]; }
+    if (mode && tid < NW_ROWS && row0 + tid < nrows) {
+        r0 = v0[row0 + tid]; r1 = v1[row0 + tid];
+        if constexpr (CAT) { if (mode == 1) r2 = actions[row0 + tid]; }
+    }
     // ---- consume ---------------------------------------------------------------------------------------------------------
 #pragma unroll
     for (int k = 0; k < WV; ++k) {
@@ -170,7 +181,7 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
         const int r = i / Kp0, j = i - r * Kp0, row = row0 + r;
         put_obs(i, (row < nrows && j < O) ? obs[(size_t)row * O + j] : 0.f);
     }
-    if (mode == 1) {
+    if (TILE && mode == 1) {
         auto put_act = [&](int i, float x) __attribute__((always_inline)) {
             const int r = i / Ap, j = i - r * Ap;
             lds[lay.w_total + (r >> 4) * lay.pipe_total + lay.acts + (r & 15) * Ap + j] = x;
@@ -179,7 +190,7 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
         for (int k = 0; k < OV; ++k) { const int i = tid + NW_THREADS * k; if (i < NW_ROWS * Ap) put_act(i, av[k]); }
         for (int i = tid + NW_THREADS * OV; i < NW_ROWS * Ap; i += NW_THREADS) {
             const int r = i / Ap, j = i - r * Ap, row = row0 + r;
-            put_act(i, (row < nrows && j < A) ? actions[(size_t)row * A + j] : 0.f);
+            put_act(i, (row < nrows && j < A) ? tile_src[(size_t)row * A + j] : 0.f);
         }
     }
     if (mode && tid < NW_ROWS) {
@@ -187,6 +198,7 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
         float* rv = lds + lay.w_total + (tid >> 4) * lay.pipe_total + lay.rowv;
         rv[2 * (tid & 15)] = live ? r0 : 0.f;
         rv[2 * (tid & 15) + 1] = live ? r1 : 0.f;
+        if constexpr (CAT) { if (mode == 1) lds[lay.w_total + (tid >> 4) * lay.pipe_total + lay.mu + (tid & 15) * lay.ldm + Ap] = live ? r2 : -1.f; }
     }
 }
 
@@ -371,7 +383,10 @@ __device__ __forceinline__ void nw_lazy_apply(const NetDev& net, const NwLayout&
 // ------------------------------------------------------------------------------------------------------------------------
 // The train step of one workgroup behind its prologue (weight image and this workgroup's rows in LDS): forward, loss, backward, weight gradients ->
 // one partial gradient vector.  Called by narrow_train_kernel and, once per minibatch, by narrow_epoch_kernel.
-template <int KP0, int HP, int AP, int LL, bool WT = true>
+// CAT: categorical head (the arithmetic of train_fwd_bwd_kernel<.., CAT>, in its order): the logits are the head product in the `mu` tile, the row's category index
+// waits in the padding column of its `mu` row and, with MASK, its mask row in the `acts` tile (nw_stage); d logits go where d mu goes, so the head-backward product and the pi/w, pi/b gradients
+// run unchanged.  The padded logstd slot has no gradient source: its partial is written as 0.  Nothing is indexed with the action or with the mask.
+template <int KP0, int HP, int AP, int LL, bool WT = true, bool CAT = false, bool MASK = false>
 __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout& lay, const NwTrainArgs& a, float* lds, const int tower, const int grp,
                                               const int tidx = (int)threadIdx.x) {
     typedef NwShape<KP0, HP, AP, LL> S;
@@ -420,6 +435,48 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
         // (an exp and a division per element) -- same values, same results
         float ssq = 0.f, slog = 0.f, sent = 0.f;
         float zk[4], sk[4];
+        // categorical: m = max_j l_j, a0 = l - m, z = sum exp(a0); neglogp = log z - a0[act], entropy = sum_j p_j (log z - a0_j); a lane keeps its categories' a0
+        // (in zk) and whether they count (ok: inside A and, MASK, allowed -- dead rows of the last group: all allowed)
+        float cz = 1.f, clz = 0.f, cnlp = 0.f;
+        int cact = -1;
+        bool ok[4];
+        if constexpr (CAT) {
+            cact = live ? (int)mus[r * ldm + Ap] : -1;
+            float bl = -INFINITY;
+            int il = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = part + 16 * k;
+                ok[k] = j < net.A;
+                zk[k] = 0.f;
+                if (j < net.A) {
+                    if constexpr (MASK) ok[k] = !live || acts[r * Ap + j] != 0.f;
+                    const float l = mus[r * ldm + j];
+                    zk[k] = l;
+                    if (ok[k] && l > bl) { bl = l; il = j; }
+                }
+            }
+            group16_argmax(bl, il);
+            const float cm = bl;
+            float la = 0.f;
+            cz = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = part + 16 * k;
+                if (ok[k]) {
+                    const float a0 = zk[k] - cm;
+                    zk[k] = a0;
+                    cz += expf(a0);
+                    if (j == cact) la = a0;
+                }
+            }
+            cz = group16_sum(cz); la = group16_sum(la);
+            clz = logf(cz);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (ok[k]) sent += (expf(zk[k]) / cz) * (clz - zk[k]);
+            sent = group16_sum(sent);
+            cnlp = clz - la;
+        } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                                 // (compile-time k: the kept values stay in registers)
             const int j = part + 16 * k;
@@ -435,7 +492,8 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             }
         }
         ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
-        const float nlp = 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+        }
+        const float nlp = CAT ? cnlp : 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
         const float adv = live ? rowv[2 * r] : 0.f;
         const float old_nlp = live ? rowv[2 * r + 1] : nlp;
         const float lo = 1.0f - cr, hi = 1.0f + cr;
@@ -462,6 +520,15 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             const int j = part + 16 * k;
             if (j < Ap) {
                 float dmu = 0.f, dl = 0.f;
+                if constexpr (CAT) {
+                    // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H); a forbidden or padded category, a dead row: 0
+                    if (ok[k] && live) {
+                        const float a0 = zk[k];
+                        const float p = expf(a0) / cz;
+                        dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + net.ent_coef * gg * (p * ((a0 - clz) + sent));
+                    }
+                    dmu_t[r * ldm + j] = dmu;                                                   // (no d logstd: the shared acts / dls tile keeps the mask rows)
+                } else {
                 if (j < net.A && live) {
                     const float z = zk[k], sigma = sk[k];
                     dl = d_nlp * (1.0f - z * z) - net.ent_coef * gg;                          // AddN_2 G:21299
@@ -469,6 +536,7 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
                 }
                 dmu_t[r * ldm + j] = dmu;
                 dls[r * Ap + j] = dl;
+                }
             }
         }
         __syncthreads();
@@ -562,7 +630,7 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
     if (vec < L) { if (lane < S::Hp(net, vec)) pst(out + (net.b_off[tower][vec] + lane), colsum(lay.dy[vec], lay.ldy[vec], lane)); }
     if (tower == 0) {
         if (vec == L) { if (lane < Ap) pst(out + (net.bmu_off + lane), colsum(lay.dmu, lay.ldm, lane)); }
-        if (vec == L + 1) { if (lane < Ap) pst(out + (net.ls_off + lane), colsum(lay.dls, Ap, lane)); }
+        if (vec == L + 1) { if (lane < Ap) pst(out + (net.ls_off + lane), CAT ? 0.f : colsum(lay.dls, Ap, lane)); }       // (CAT: the padded logstd slot has no gradient)
         if (vec == L + 2 && lane < 4) {                               // pg, entropy, kl, clipfrac sums
             const float s4 = colsum(lay.misc, 4, lane);
             pst(out + (net.n_theta + lane), s4);
@@ -584,8 +652,10 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
     NSTAMP(11);
 }
 
-template <int KP0, int HP, int AP, int LL, bool LAZY = false, bool EXACT = false>
+template <int KP0, int HP, int AP, int LL, bool LAZY = false, bool EXACT = false, bool CAT = false, bool MASK = false>
 __global__ __launch_bounds__(NW_THREADS) void narrow_train_kernel(NetDev net, NwLayout lay, NwTrainArgs a, NwLazyArgs z) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(!(CAT && LAZY), "the deferred Adam keeps a Gaussian head");
     typedef NwShape<KP0, HP, AP, LL> S;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwTrainArgs) + sizeof(NwLazyArgs)>();
@@ -608,10 +678,10 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_train_kernel(NetDev net, Nw
                       );
         NSTAMP(14);
     } else {
-        nw_stage<S>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
-                    a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2);
+        nw_stage<S, CAT, MASK>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
+                    a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2, (int)threadIdx.x, a.mask);
     }
-    nw_train_body<KP0, HP, AP, LL>(net, lay, a, lds, tower, grp);
+    nw_train_body<KP0, HP, AP, LL, true, CAT, MASK>(net, lay, a, lds, tower, grp);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -919,9 +989,13 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_epoch_kernel(NetDev net, Nw
 // ------------------------------------------------------------------------------------------------------------------------
 // Act model for narrow nets: the same forward on 32 rows per workgroup and tower, weights from the packed image.
 // `img` rides in StepArgs::theta (the narrow launch passes the image instead of the padded parameter vector).
+// CAT / MASK: the categorical head of policy_step_kernel<.., CAT[, MASK]> behind the head product, same arithmetic in the same order, same counter keys for the
+// uniforms (the same seed and rows draw what the generic step draws).  A lane owns the categories part, part + 16, ... (at most four: A <= 64); their uniforms and
+// mask entries are requested BEFORE the head product and wait in registers under it.  Nothing is indexed with the sampled category or with the mask.
 // ------------------------------------------------------------------------------------------------------------------------
-template <int KP0, int HP, int AP, int LL>
+template <int KP0, int HP, int AP, int LL, bool CAT = false, bool MASK = false>
 __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwLayout lay, StepArgs a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     typedef NwShape<KP0, HP, AP, LL> S;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(StepArgs)>();
@@ -959,12 +1033,69 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwL
         return;
     }
     float* mus = P + lay.mu; const int ldm = lay.ldm;
+    float uk[4]; bool mk[4];
+    if constexpr (CAT) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = part + 16 * k;
+            uk[k] = 0.5f; mk[k] = true;
+            if (j < net.A && row < a.n) {
+                uk[k] = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+                if constexpr (MASK) mk[k] = a.mask[(size_t)row * net.A + j] != 0.f;
+            }
+        }
+    }
     nw_dense<HP>(hL, ldh, HpL, lds + lay.wh, lay.wh_ld, Ap, [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
         const float b = par[net.par_bmu + col];
 #pragma unroll
         for (int q = 0; q < 4; ++q) mus[(4 * g + q) * ldm + col] = acc[q] + b;
     });
     __syncthreads();
+    if constexpr (CAT) {
+        // a = argmax_j (l_j - log(-log u_j)), neglogp = log sum_j exp(l_j - m) - (l_a - m), m = max_j l_j.  MASK: a lane's best index starts at net.A ("none
+        // yet"), so the first ALLOWED category is taken even when its perturbed logit is -inf, and a lane without an allowed category loses every tie of the
+        // butterfly to a real index; a row without any allowed category (refused by the host checks) ends at net.A and is brought back inside the tile
+        float bp = -INFINITY, bl = -INFINITY;
+        int ip = MASK ? net.A : 0, il = MASK ? net.A : 0;
+        float lk[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = part + 16 * k;
+            lk[k] = 0.f;
+            if (j < net.A) {
+                const float l = mus[r * ldm + j];
+                lk[k] = l;
+                const float pl = l - logf(-logf(uk[k]));
+                if constexpr (MASK) {
+                    if (mk[k] && (pl > bp || ip == net.A)) { bp = pl; ip = j; }
+                    if (mk[k] && (l > bl || il == net.A)) { bl = l; il = j; }
+                } else {
+                    if (pl > bp) { bp = pl; ip = j; }
+                    if (l > bl) { bl = l; il = j; }
+                }
+            }
+        }
+        group16_argmax(bp, ip);
+        group16_argmax(bl, il);
+        if constexpr (MASK) { ip = min(ip, net.A - 1); il = min(il, net.A - 1); }
+        const float m = bl;
+        float z = 0.f, la = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = part + 16 * k;
+            if (j < net.A) {
+                if (j == ip) la = lk[k] - m;                  // (one lane of the row holds it; the others add zeros)
+                if (mk[k]) z += expf(lk[k] - m);
+            }
+        }
+        z = group16_sum(z); la = group16_sum(la);
+        if (part == 0 && row < a.n) {
+            if (a.action) a.action[row] = (float)ip;
+            if (a.det_action) a.det_action[row] = (float)il;
+            if (a.neglogp) a.neglogp[row] = logf(z) - la;
+        }
+        return;
+    }
     float ssq = 0.f, slog = 0.f;
     for (int j = part; j < net.A; j += 16) {
         const float mu = mus[r * ldm + j];

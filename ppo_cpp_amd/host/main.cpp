@@ -36,7 +36,8 @@ const char* kAliases[][2] = {{"-d", "dir"}, {"--dir", "dir"}, {"-p", "path"}, {"
                              {"-j", "threads"}, {"--threads", "threads"}, {"--jobs", "threads"}, {"--num_threads", "threads"}, {"--hidden", "hidden"},
                              {"--minibatches", "minibatches"}, {"--seed", "seed"}, {"-g", "graph"}, {"--graph", "graph"}, {"--graph_path", "graph"}, {"--obs", "obs"},
                              {"--ranks", "ranks"}, {"--rank", "rank"}, {"--world", "world"}, {"--ctl_fd", "ctl_fd"}, {"--devices", "devices"}, {"--collective", "collective"},
-                             {"--explicit_dir", "explicit_dir"}, {"--dump_dir", "dump_dir"}, {"--time_limit", "time_limit"}};
+                             {"--explicit_dir", "explicit_dir"}, {"--dump_dir", "dump_dir"}, {"--time_limit", "time_limit"},
+                             {"--discrete_kernels", "discrete_kernels"}};
 const char* kSwitches[][2] = {{"-r", "resume"}, {"--resume", "resume"}, {"-v", "verbose"}, {"--verbose", "verbose"}, {"--seeded", "seeded"},
                               {"--replica_saves", "replica_saves"}, {"--ctl_selftest", "ctl_selftest"}, {"--no_bootstrap_truncated", "no_bootstrap_truncated"}};
 
@@ -70,10 +71,12 @@ int main(int argc, char** argv) {
                         "                   [--minibatches N]\n"
                         "                   [--hidden 256,256] [--saves N --dir DIR --id ID] [--path CKPT_PREFIX] [--resume] [--seeded] [--seed N]\n"
                         "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n"
-                        "                   [--time_limit N] [--no_bootstrap_truncated]\n"
+                        "                   [--time_limit N] [--no_bootstrap_truncated] [--discrete_kernels narrow|generic]\n"
                         "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n"
                         "  --time_limit N: every environment ends its episodes after N steps (a TimeLimit wrapper); the value is bootstrapped at those truncations\n"
-                        "  --no_bootstrap_truncated: treat them as terminal states instead (the reference's behaviour)\n");
+                        "  --no_bootstrap_truncated: treat them as terminal states instead (the reference's behaviour)\n"
+                        "  --discrete_kernels: kernels of a discrete environment's categorical policy; narrow = the LDS-resident family where the network's shape\n"
+                        "                      qualifies (hidden widths <= 64), generic = the generic fp32 family (the default).  Continuous environments: no effect\n");
             return 0;
         }
         for (auto& al : kAliases) if (a == al[0] && i + 1 < argc) { f.kv[al[1]] = argv[++i]; ok = true; break; }
@@ -144,6 +147,8 @@ int main(int argc, char** argv) {
         if (v != "off" && (v.empty() || *end != '\0')) { std::fprintf(stderr, "--cliprange_vf: expected a number, inf or off, not '%s'\n", v.c_str()); return 1; }
         cliprange_vf = (float)x;
     }
+    const std::string dk = f.str("discrete_kernels", "generic");
+    if (dk != "narrow" && dk != "generic") { std::fprintf(stderr, "--discrete_kernels: expected narrow or generic, not '%s'\n", dk.c_str()); return 1; }
     int rc = 0;
     try {
         if (f.has("graph")) {                                                    // -g: shape, constants and initial weights from a reference graph file
@@ -152,7 +157,9 @@ int main(int argc, char** argv) {
             cfg = g.config;
             h = graphspec::create_from_graph(g);
         } else {
-            if (ppo_create(&cfg, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+            // the head follows the environment's action space (the mock environments here are continuous: a Gaussian head, whatever --discrete_kernels says)
+            const std::unique_ptr<Env> probe(f.has("seeded") ? static_cast<Env*>(new SeededEnvMock(1234u, (uint32_t)env0, obs_dim, 18)) : static_cast<Env*>(new EnvMock(env0 + 1)));
+            if (ppo_create_ex(&cfg, PPO2::action_dist_for(*probe, dk == "narrow"), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
             if (ppo_init_orthogonal(h, (uint64_t)f.num("seed", 0)) != 0) throw std::runtime_error(ppo_last_error(h));     // same seed on every rank: replicated weights
         }
         const std::string xdir = f.str("explicit_dir", ""), ddir = f.str("dump_dir", "");

@@ -48,6 +48,14 @@ public:
         }
     }
 
+    // The action_dist argument of ppo_create_ex for a handle that will serve `env`: PPO_ACT_GAUSSIAN for SPACE_CONTINOUS, PPO_ACT_CATEGORICAL for SPACE_DISCRETE.
+    // discrete_shape_kernels (default off): a discrete Env's handle is created with PPO_ACT_SHAPE_KERNELS -- the narrow LDS-resident kernels when the network's
+    // shape qualifies (include/ppo_hip.h); a continuous Env is not affected.
+    static int32_t action_dist_for(Env& env, bool discrete_shape_kernels = false) {
+        if (env.get_action_space() != Env::SPACE_DISCRETE) return PPO_ACT_GAUSSIAN;
+        return PPO_ACT_CATEGORICAL | (discrete_shape_kernels ? PPO_ACT_SHAPE_KERNELS : 0);
+    }
+
     struct UpdateLog { int fps; float losses[5]; double collect_ms, update_ms; float mean_reward; };     // mean_reward: the rollout's un-normalised rewards (the learning curve)
     // Data parallel (no reference counterpart): this PPO2 is rank `rank` of `world` processes, one per GPU, whose handles share a
     // communicator (ppo_dist_init, see dist.hpp).  `env` holds THIS rank's share of the environments; n_batch, total_timesteps, the fps of the

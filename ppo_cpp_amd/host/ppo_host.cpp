@@ -175,6 +175,7 @@ struct ppo_host_args {
     unsigned long long seed;     // PPO2::seed (exploration noise + epoch shuffles)
     int obs_dim, act_dim;        // SeededEnvMock's shape (0 = 18): 36 / 18 is the hexapod with observed velocities (hexapod_closed_loop_env.hpp:20)
     float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
+    int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for)
 };
 struct ppo_host_result {
     double env_steps_per_s, collect_ms, update_ms;
@@ -207,7 +208,14 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
         if ((O != 18 || A != 18) && !a->seeded_env) throw std::runtime_error("EnvMock (the reference's stub) is 18 / 18");
         ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
         cfg.device = a->device;
-        if (ppo_create_ex(&cfg, a->seeded_env == 3 ? PPO_ACT_CATEGORICAL : PPO_ACT_GAUSSIAN, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        auto make_probe = [&]() -> Env* {        // (what the handle's head is chosen from: one environment of the kind the run uses)
+            if (a->seeded_env == 3) return new DiscreteTargetEnv(1234u, 0, O, A);
+            if (a->seeded_env == 2) return new TargetEnv(1234u, 0, O, A);
+            if (a->seeded_env) return new SeededEnvMock(1234u, 0, O, A);
+            return new EnvMock(1);
+        };
+        { std::unique_ptr<Env> probe(make_probe());
+          if (ppo_create_ex(&cfg, PPO2::action_dist_for(*probe, a->discrete_kernels != 0), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (x && x->theta_in && ppo_set_flat(h, 0, x->theta_in, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<Env>> envs;
@@ -408,7 +416,8 @@ int ppo_host_learn_masked(const ppo_host_args* a, float* reward_curve, long long
         const int O = a->obs_dim > 0 ? a->obs_dim : 18, A = a->act_dim > 0 ? a->act_dim : 18;
         ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
         cfg.device = a->device;
-        if (ppo_create_ex(&cfg, PPO_ACT_CATEGORICAL, &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        { MaskedTargetEnv probe(1234u, 0, O, A);
+          if (ppo_create_ex(&cfg, PPO2::action_dist_for(probe, a->discrete_kernels != 0), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<MaskedTargetEnv>> kids;
         std::vector<std::shared_ptr<Env>> envs;

@@ -12,7 +12,13 @@ class HostArgs(C.Structure):
                 ("lr", C.c_float), ("cliprange", C.c_float), ("gamma", C.c_float), ("lam", C.c_float),
                 ("seeded_env", C.c_int), ("device", C.c_int), ("max_workers", C.c_int), ("reference_loop", C.c_int),
                 ("norm_obs", C.c_int), ("norm_reward", C.c_int), ("seed", C.c_ulonglong), ("obs_dim", C.c_int), ("act_dim", C.c_int),
-                ("cliprange_vf", C.c_float)]
+                ("cliprange_vf", C.c_float), ("discrete_kernels", C.c_int)]
+
+
+def _discrete_kernels(name):
+    if name not in ("generic", "narrow"):
+        raise ValueError("discrete_kernels must be 'generic' or 'narrow', not %r" % (name,))
+    return int(name == "narrow")
 
 
 class HostResult(C.Structure):
@@ -99,10 +105,11 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0):
+                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic"):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
-    discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle."""
+    discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
+    PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "generic" (the default): without."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -115,6 +122,7 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
     a.obs_dim, a.act_dim = obs_dim, act_dim
     a.cliprange_vf = cliprange_vf
+    a.discrete_kernels = _discrete_kernels(discrete_kernels)
     out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32)}
     x = HostExplicit(None, None, None, out["losses"].ctypes.data, None, None, None, None, None, None, None, out["reward_curve"].ctypes.data)
     r = HostResult()
@@ -153,11 +161,11 @@ def learn_time_limit(n_envs, n_steps, hidden, n_updates, nminibatches, noptepoch
 
 
 def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0):
+                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic"):
     """PPO2::learn on MaskedTargetEnv x n_envs (host/env/env_mock.hpp: DiscreteTargetEnv's task with about half of the categories forbidden at every step) behind
     VecEnv + EnvNormalize, with the library's own exploration noise and shuffles (ppo_host_learn_masked).  PPO2 finds the IActionMask mixin and masks by itself.
     Returns the mean un-normalised reward of every update's rollout [n_updates], the count of forbidden actions the environments received over the whole run, and
-    n_playback deterministic playback actions with their legality."""
+    n_playback deterministic playback actions with their legality.  discrete_kernels: as in learn_curve."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -170,6 +178,7 @@ def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, l
     a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
     a.obs_dim, a.act_dim = obs_dim, act_dim
     a.cliprange_vf = cliprange_vf
+    a.discrete_kernels = _discrete_kernels(discrete_kernels)
     out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros(n_playback, np.float32), "playback_legal": np.zeros(n_playback, np.float32)}
     forbidden = C.c_longlong(-1)
     r = HostResult()

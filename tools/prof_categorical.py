@@ -1,19 +1,31 @@
 """tools/prof_categorical.py [out.json] -- categorical vs Gaussian head at configs[2]'s workload (4096 x 16, [256,256], 18 obs, 18 actions / categories): device time per kernel class
-(ppo_prof_read) of one ppo_train_step on a 2048-row minibatch (B / 32) and of one collect_synthetic; the three handles alternate round by round"""
+(ppo_prof_read) of one ppo_train_step on a 2048-row minibatch (B / 32) and of one collect_synthetic; the three handles alternate round by round.
+--shape_kernels adds a categorical handle created with PPO_ACT_SHAPE_KERNELS ("categorical_narrow"); --hidden 64,64 [--envs E --steps T] picks a shape where that
+flag selects the narrow kernels (tools/prof_action_mask.py has the same options and also times the policy step and an update epoch)"""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import ppo_cpp_amd
 
-E, T, M, ROUNDS, REPS = 4096, 16, 2048, 4, 20
-VARIANTS = [("categorical", "categorical", {}), ("gaussian_generic", "gaussian", {"PPO_HIP_NO_T8": "1", "PPO_HIP_NO_DW2": "1"}), ("gaussian_default", "gaussian", {})]
+ARGV = sys.argv[1:]
+def _opt(name, default):
+    if name in ARGV:
+        i = ARGV.index(name); v = ARGV[i + 1]; del ARGV[i:i + 2]; return v
+    return default
+HIDDEN = [int(x) for x in _opt("--hidden", "256,256").split(",")]
+E, T = int(_opt("--envs", 4096)), int(_opt("--steps", 16))
+SHAPE_KERNELS = "--shape_kernels" in ARGV
+if SHAPE_KERNELS:
+    ARGV.remove("--shape_kernels")
+M, ROUNDS, REPS = E * T // 32, 4, 20
+VARIANTS = ([("categorical_narrow", "categorical+", {})] if SHAPE_KERNELS else []) + [("categorical", "categorical", {}), ("gaussian_generic", "gaussian", {"PPO_HIP_NO_T8": "1", "PPO_HIP_NO_DW2": "1"}), ("gaussian_default", "gaussian", {})]
 
 
 def make(dist, env):
     for k in ("PPO_HIP_NO_T8", "PPO_HIP_NO_DW2"):
         os.environ.pop(k, None)
     os.environ.update(env)
-    g = ppo_cpp_amd.PPOHip(18, 18, [256, 256], action_dist=dist)
+    g = ppo_cpp_amd.PPOHip(18, 18, HIDDEN, action_dist=dist.rstrip("+"), shape_kernels=dist.endswith("+"))
     for k in env:
         os.environ.pop(k)
     g.init_orthogonal(0); g.norm_init(E); g.rollout_alloc(E, T)
@@ -59,5 +71,5 @@ for name, g in handles.items():
         name, np.median(res[name]["train"]), np.round(res[name]["train"], 1), np.median(res[name]["collect"]), np.round(res[name]["collect"], 1)))
     print("   train kernels (us):", {k: round(v, 1) for k, v in res[name]["train_kernels"].items()})
     print("   kernels:", res[name]["counts"])
-if len(sys.argv) > 1:                  # optional: the per-round numbers as JSON
-    json.dump(res, open(sys.argv[1], "w"), indent=1)
+if ARGV:                               # optional: the per-round numbers as JSON
+    json.dump(res, open(ARGV[0], "w"), indent=1)
