@@ -342,7 +342,14 @@ int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueue
 /* ---- debug: a raw device buffer by name, padding included (the getters above copy the dense part of every tensor) ----------------
  * "theta" "adam_m" "adam_v" (padded), "thetaT" / "par" (the transposed and small-parameter mirrors the train kernels read), "grad" (+ its tail), "sumsq", "beta_pow", "hyper",
  * "norm_out", "dw2_parts", the last train step's workspaces ("x0g" "dmug" "h_pi_0" ... "slots_pi" "slabs"), the gathered epoch ("mb_obs" ... "gidx" "advstats" "keys"), the
- * narrow path's packed image and second weight set ("nw_img" "nw_theta1" ...), the normaliser's state.  *count = the buffer's length in 4-byte words (0: not used by this shape);
+ * narrow path's packed image and second weight set ("nw_img" "nw_theta1" ...), the normaliser's state.
+ * A PPO_BF16 handle's workspaces (0 words on every other handle; "slots_pi" / "slots_vf", "slabs", "theta" and "grad" are shared with the fp32 path): "bf_theta" (bf16 operand
+ * mirror of "theta", same padded offsets), "bf_x0" (staged observations, bf16 [Rcap][Kp0]), "bf_h_pi_<l>" / "bf_h_vf_<l>" (tanh outputs of hidden layer l = 0 .. PPO_MAX_LAYERS - 1,
+ * bf16 [Rcap][Hp_l]), "bf_dy_pi_<l>" / "bf_dy_vf_<l>" (gradients w.r.t. the pre-activations, same shape), "bf_head_pi" / "bf_head_vf" (fp32 [4][Rcap][Ap]: the head GEMM's partial
+ * products per reduction range, bias in range 0; the value is column 0), "bf_dhead_pi" / "bf_dhead_vf" (bf16 [Rcap][Ap]: loss gradient w.r.t. the head outputs) and "bf_dbias" (fp32
+ * [row tiles][sum of Hp_l over towers and layers]: per-row-tile bias-gradient sums; tower-major, then layer).  Rcap = the largest row count seen so far rounded up to 128; a bf16
+ * buffer of N elements reads as N / 2 words (view the words as uint16 for the bit patterns).  tests/test_bf16_stages.py checks every stage of the path through them.
+ * *count = the buffer's length in 4-byte words (0: not used by this shape);
  * at most max_count words are copied.  Two runs that must agree bit for bit are compared buffer by buffer with it (tests/test_other_shapes.py).  No reference counterpart. */
 int ppo_debug_buffer(ppo_handle* h, const char* name, float* dst, int64_t max_count, int64_t* count);
 /* debug: leave `word` in every LDS word of every CU (a launch of whole-CU workgroups on the handle's stream, synchronised).  A kernel that reads LDS it never wrote sees

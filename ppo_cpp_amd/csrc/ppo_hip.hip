@@ -3145,7 +3145,25 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
     const NetDev& n = h->net;
     const size_t P = (size_t)h->P_pad, R = (size_t)h->ws_rows, U = (size_t)h->upd_cap_rows;
     const bool ws = !(h->narrow || h->bf.on);                 // the fp32 wide path's train workspaces
-    return {
+    // the bf16 path's workspaces (null on every other handle): bf16 buffers count two elements per word; every layer up to PPO_MAX_LAYERS by name
+    const ppo_handle::Bf16& b = h->bf;
+    const size_t RB = b.on ? (size_t)b.Rcap : 0;
+    static const std::vector<std::string> bf_names = [] {
+        std::vector<std::string> v;
+        for (const char* kind : {"h", "dy"}) for (const char* tw : {"pi", "vf"}) for (int l = 0; l < PPO_MAX_LAYERS; ++l) v.push_back(std::string("bf_") + kind + "_" + tw + "_" + std::to_string(l));
+        return v;
+    }();
+    std::vector<DbgEnt> bfe = {
+        {"bf_theta", b.on ? b.theta_bf : nullptr, P / 2}, {"bf_x0", b.on ? b.x0 : nullptr, RB * n.Kp0 / 2},
+        {"bf_head_pi", b.on ? b.head_out[0] : nullptr, (size_t)GB_HEAD_SPLIT * RB * n.Ap}, {"bf_head_vf", b.on ? b.head_out[1] : nullptr, (size_t)GB_HEAD_SPLIT * RB * n.Ap},
+        {"bf_dhead_pi", b.on ? b.dhead[0] : nullptr, RB * n.Ap / 2}, {"bf_dhead_vf", b.on ? b.dhead[1] : nullptr, RB * n.Ap / 2},
+        {"bf_dbias", b.on ? b.dbias : nullptr, (size_t)b.db_tiles * b.n_dbias},
+    };
+    for (int k = 0; k < 2; ++k) for (int t = 0; t < 2; ++t) for (int l = 0; l < PPO_MAX_LAYERS; ++l) {
+        const bool have = b.on && l < n.L;
+        bfe.push_back({bf_names[(size_t)(k * 2 + t) * PPO_MAX_LAYERS + l].c_str(), have ? (k ? b.dy[t][l] : b.hb[t][l]) : nullptr, have ? RB * n.Hp[l] / 2 : 0});
+    }
+    std::vector<DbgEnt> tab = {
         {"theta", h->theta, P}, {"adam_m", h->adam_m, P}, {"adam_v", h->adam_v, P}, {"thetaT", h->thetaT, (size_t)h->PT}, {"par", h->par, (size_t)2 * n.par_total},
         {"grad", h->grad, P + 256}, {"sumsq", h->sumsq, (size_t)4 * h->n_blocks}, {"beta_pow", h->beta_pow, 4}, {"hyper", h->hyper, 2}, {"norm_out", h->norm_out, 1},
         {"dw2_parts", h->dw2_parts, (size_t)DW2_TILES + DW2_GRID}, {"dw2_counters", h->dw2_counters, (size_t)DW2_TILES},
@@ -3154,7 +3172,7 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
         {"dy_pi_0", ws ? h->dyg[0][0] : nullptr, R * n.Hp[0]}, {"dy_vf_0", ws ? h->dyg[1][0] : nullptr, R * n.Hp[0]},
         {"h_pi_1", ws && n.L > 1 ? h->hg[0][1] : nullptr, R * n.Hp[n.L > 1 ? 1 : 0]}, {"dy_pi_1", ws && n.L > 1 ? h->dyg[0][1] : nullptr, R * n.Hp[n.L > 1 ? 1 : 0]},
         {"dy_vf_1", ws && n.L > 1 ? h->dyg[1][1] : nullptr, R * n.Hp[n.L > 1 ? 1 : 0]},
-        {"slots_pi", ws ? h->slots[0] : nullptr, (R / 16) * n.slot_w}, {"slots_vf", ws ? h->slots[1] : nullptr, (R / 16) * n.slot_w},
+        {"slots_pi", ws || b.on ? h->slots[0] : nullptr, ((b.on ? RB : R) / 16) * n.slot_w}, {"slots_vf", ws || b.on ? h->slots[1] : nullptr, ((b.on ? RB : R) / 16) * n.slot_w},
         {"slabs", h->narrow ? nullptr : h->slabs, (size_t)h->max_split * P},
         {"mb_mask", h->masking ? h->mb_mask : nullptr, U * n.A}, {"ro_mask", h->masking ? h->ro_mask : nullptr, (size_t)h->E * h->T * n.A},
         {"mb_obs", h->mb_obs, U * n.O}, {"mb_act", h->mb_act, U * h->Aw}, {"mb_adv", h->mb_adv, U}, {"mb_ret", h->mb_ret, U}, {"mb_val", h->mb_val, U}, {"mb_nlp", h->mb_nlp, U},
@@ -3163,6 +3181,8 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
         {"nw_theta1", h->nw_theta1, P}, {"nw_m1", h->nw_m1, P}, {"nw_v1", h->nw_v1, P}, {"nw_epoch_words", h->nw_epoch_words, NW_EPOCH_WORDS},
         {"obs_mean", h->obs_rms.mean, (size_t)n.O}, {"obs_var", h->obs_rms.var, (size_t)n.O}, {"nz_ret", h->nz_ret, (size_t)h->nz_envs}, {"cur_done", h->cur_done, (size_t)h->nz_envs},
     };
+    tab.insert(tab.end(), bfe.begin(), bfe.end());
+    return tab;
 }
 
 static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perms) {

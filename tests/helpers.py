@@ -31,14 +31,15 @@ def ckpt71_stats():
     return json.load(open(os.path.join(GOLDEN, "ckpt71_stats.json")))
 
 
-def synth_minibatch(orc, n, seed, adv_normalized=True, cr=0.16102319955825806):
-    """A seeded minibatch that exercises BOTH clip branches: old_neglogp/old_values are perturbed copies of the
-    current model's outputs so that ratio and v - v_old straddle the clip range."""
+def synth_minibatch_from(obs, act, v, nlp, seed, adv_normalized=True, cr=0.16102319955825806, rng=None, vf_ranges=None):
+    """The minibatch of synth_minibatch around GIVEN model outputs: `act`, `v`, `nlp` are what some model (the fp32 oracle, or a bf16 handle's own step())
+    returned for `obs`; old_neglogp / old_values / returns are perturbed copies of them and every row is pushed CLEAR of the loss's discontinuities
+    relative to THOSE outputs.  rng: the generator to draw the perturbations from (default: a fresh RandomState(seed)).  vf_ranges: value-clip ranges
+    to stay clear of beside cr (a handle under PPO_VCLIP_RANGE)."""
     from oracle import oracle as o
-    rng = np.random.RandomState(seed)
-    obs = rng.uniform(-1, 1, (n, orc.O)).astype(np.float32)
-    noise = rng.normal(size=(n, orc.A)).astype(np.float32)
-    act, v, nlp = orc.step(obs, noise)
+    if rng is None:
+        rng = np.random.RandomState(seed)
+    n = obs.shape[0]
     old_nlp = (nlp + rng.normal(scale=0.15, size=n)).astype(np.float32)
     old_v = (v + rng.normal(scale=0.2, size=n)).astype(np.float32)
     ret = (v + rng.normal(scale=0.5, size=n)).astype(np.float32)
@@ -57,8 +58,29 @@ def synth_minibatch(orc, n, seed, adv_normalized=True, cr=0.16102319955825806):
     s1, s2 = (v - ret.astype(np.float64)) ** 2, (vclip - ret) ** 2
     near = (np.abs(dvo) > cr) & (np.abs(s1 - s2) < 1e-3 * np.maximum(s1, 1e-6))
     ret[near] += np.float32(0.05)
+    if vf_ranges:                                              # further clip ranges: the same two rules per range, repeated until they hold for all of them
+        for _ in range(4):
+            for r in tuple(vf_ranges) + (cr,):
+                dvo = v.astype(np.float64) - old_v
+                near = np.abs(np.abs(dvo) - r) < 1e-3
+                old_v[near] -= np.float32(0.004) * np.sign(dvo[near]).astype(np.float32)
+                dvo = v.astype(np.float64) - old_v
+                vclip = old_v + np.clip(dvo, -r, r)
+                s1, s2 = (v - ret.astype(np.float64)) ** 2, (vclip - ret) ** 2
+                near = (np.abs(dvo) > r) & (np.abs(s1 - s2) < 1e-3 * np.maximum(s1, 1e-6))
+                ret[near] += np.float32(0.05)
     adv = o.adv_normalize(ret, old_v) if adv_normalized else (ret - old_v).astype(np.float32)
     return dict(obs=obs, actions=act, advs=adv, returns=ret, old_neglogp=old_nlp, old_values=old_v)
+
+
+def synth_minibatch(orc, n, seed, adv_normalized=True, cr=0.16102319955825806):
+    """A seeded minibatch that exercises BOTH clip branches: old_neglogp/old_values are perturbed copies of the
+    current model's outputs so that ratio and v - v_old straddle the clip range (synth_minibatch_from, around the oracle's outputs)."""
+    rng = np.random.RandomState(seed)
+    obs = rng.uniform(-1, 1, (n, orc.O)).astype(np.float32)
+    noise = rng.normal(size=(n, orc.A)).astype(np.float32)
+    act, v, nlp = orc.step(obs, noise)
+    return synth_minibatch_from(obs, act, v, nlp, seed, adv_normalized, cr, rng=rng)
 
 
 G_TENSORS = ["pi_fc0/w", "pi_fc0/b", "vf_fc0/w", "vf_fc0/b", "pi_fc1/w", "pi_fc1/b", "vf_fc1/w", "vf_fc1/b", "vf/w", "vf/b", "pi/w", "pi/b", "pi/logstd"]
