@@ -30,8 +30,17 @@
 namespace {
 
 std::string g_create_error;
+// diagnostic builds (-DPPO_STAMPS): the kernels' cycle stamps land in one buffer, each family `offset` words in.  SET_STAMPS(field, cond, offset) points an argument
+// block's stamps member there (null when its launch is too large for its share); without PPO_STAMPS it compiles to nothing -- most of the members do not exist then
 #ifdef PPO_STAMPS
 unsigned long long* g_stamps = nullptr;
+unsigned long long* stamps(size_t offset) {
+    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
+    return g_stamps + offset;
+}
+#define SET_STAMPS(field, cond, offset) ((field) = (cond) ? stamps(offset) : nullptr)
+#else
+#define SET_STAMPS(field, cond, offset) ((void)0)
 #endif
 
 int ru(int x, int m) { return (x + m - 1) / m * m; }
@@ -78,6 +87,9 @@ struct Rccl {
 };
 
 }  // namespace
+
+// the assembled gradient of a train step whose launch did not write it: how to rebuild it (bf16_materialize_grad)
+struct LazyGrad { bool on = false; ReduceArgs ra{}; int n_old = 0; };     // n_old: workgroups of bf16_grad_reduce_kernel
 
 struct ppo_handle {
     ppo_config cfg{};
@@ -205,10 +217,10 @@ struct ppo_handle {
         float* head_out[2]{};                           // [GB_HEAD_SPLIT][Rcap][Ap] fp32 partial products of the head GEMM's reduction ranges
         int head_split = 1;                             // ranges the last bf16_forward used
         // the fused assembly + Adam launch does not write the assembled gradient: whoever asks for it (ppo_get_last_grad, ppo_debug_buffer) has it rebuilt
-        // from the last train step's slabs first (bf16_materialize_grad).  lazy_last: the last train step ENQUEUED was of that kind (a replayed graph keeps
-        // what it captured: g_lazy); grad_lazy: h->grad is behind the last train step that RAN
-        bool lazy_last = false, g_lazy = false, grad_lazy = false;
-        ReduceArgs lazy_ra{}; int lazy_n_old = 0;
+        // from the last train step's slabs first (bf16_materialize_grad).  enqueued: the last train step ENQUEUED; captured: the last step of the captured update
+        // graph (the host code of a train step does not run on a replay, so the whole value is restored after one); ran: the last train step that RAN -- on: h->grad
+        // is behind it
+        struct { LazyGrad enqueued, captured, ran; } lazy;
         bf16_t *dhead[2]{};
         float* dbias = nullptr; int db_off[2][PPO_MAX_LAYERS]{}; int n_dbias = 0;
         DwTileB* dw_tiles = nullptr; int n_dw_tiles = 0; int dw_wm = 4;
@@ -808,11 +820,11 @@ int bf16_chain_err_test(ppo_handle* h) {                        // (after the st
 // the assembled gradient of the last train step, when the launch that applied it did not write it (bf16_reduce_adam_kernel): the slabs, slot rows and bias-gradient
 // rows it was summed from are still the last step's, and bf16_grad_reduce_kernel adds them exactly as the fused launch did (same bits)
 int bf16_materialize_grad(ppo_handle* h) {
-    ppo_handle::Bf16& b = h->bf;
-    if (!b.grad_lazy) return 0;
-    hipLaunchKernelGGL(bf16_grad_reduce_kernel, dim3(b.lazy_n_old), dim3(64 * BGR_WAVES), 0, h->stream, b.lazy_ra);
+    LazyGrad& g = h->bf.lazy.ran;
+    if (!g.on) return 0;
+    hipLaunchKernelGGL(bf16_grad_reduce_kernel, dim3(g.n_old), dim3(64 * BGR_WAVES), 0, h->stream, g.ra);
     HIP_OK(h, hipGetLastError());
-    b.grad_lazy = false;
+    g.on = false;
     return 0;
 }
 
@@ -857,10 +869,7 @@ int bf16_ensure_ws(ppo_handle* h, int rows) {
 template <int EPI>
 int bf16_gemm(ppo_handle* h, const GemmArgs& a, int I, int J) {
     GemmArgs g = a;
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    g.stamps = (I / 256) * (J / GB_N) <= 256 ? g_stamps : nullptr;
-#endif
+    SET_STAMPS(g.stamps, (I / 256) * (J / GB_N) <= 256, 0);
     if (I % 256 == 0) {                                      // 256 x 128 tiles, 8 waves
         g.tiles_i = I / 256;
         hipLaunchKernelGGL((gemm_nt_bf16_kernel<4, EPI>), dim3((I / 256) * (J / GB_N), 2), dim3(GB_THREADS(4)), GB_LDS_BYTES(4), h->stream, g);
@@ -1033,10 +1042,7 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
     }
     if (per_out) *per_out = per;
     DwArgsB da{tiles, nst, per, nt * nst, h->slabs, (size_t)h->P_pad, er >= 0 ? b.xe + (size_t)er * h->net.Kp0 : nullptr, h->net.Kp0};
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    da.stamps = groups <= 512 ? g_stamps + 4096 * 16 : nullptr;
-#endif
+    SET_STAMPS(da.stamps, groups <= 512, 4096 * 16);
     if (b.dw_wm == 4) hipLaunchKernelGGL(gemm_dw_bf16_kernel<4>, dim3(groups), dim3(GB_THREADS(4)), GB_LDS_BYTES(4), h->stream, da);
     else hipLaunchKernelGGL(gemm_dw_bf16_kernel<2>, dim3(groups), dim3(GB_THREADS(2)), GB_LDS_BYTES(2), h->stream, da);
     HIP_OK(h, hipGetLastError());
@@ -1047,6 +1053,9 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 // narrow kernels: compile-time shapes <32, 64, 32, 2> / <64, 64, 32, 2> (observation tile of 32 / 64 columns) or the runtime-shape form;
 // X(KP0, HP, AP, L) is the launch statement
 #define NW_DISPATCH(h, X) do { if (!(h)->nw_static) { X(0, 0, 0, 0); } else if ((h)->net.Kp0 == 32) { X(32, 64, 32, 2); } else { X(64, 64, 32, 2); } } while (0)
+// the [256,256] pair (train8_kernel, weight_grad_assemble[_peer]_kernel): one instantiation per (observation tile, action tile) width; X(KP0, AP) is the statement
+#define PAIR_DISPATCH(h, X) do { const int kp_ = (h)->net.Kp0, ap_ = (h)->net.Ap; \
+    if (kp_ == 32 && ap_ == 32) { X(32, 32); } else if (kp_ == 64 && ap_ == 32) { X(64, 32); } else if (kp_ == 32 && ap_ == 64) { X(32, 64); } else { X(64, 64); } } while (0)
 
 // a categorical handle on the narrow family (created with PPO_ACT_SHAPE_KERNELS, qualifying shape).  It runs narrow_step_kernel / narrow_train_kernel<cat[,mask]>
 // only: every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the fused host step) asks
@@ -1054,68 +1063,43 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 static bool nw_cat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_CATEGORICAL; }
 static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
 
-template <int CT, int KS, int CTH, bool WIDE, bool CAT = false, bool MASK = false>
+// policy_step_kernel: the (CT, KS, CTH, WIDE) ladder of the handle's layout, once; the caller picks the head
+template <bool CAT, bool MASK>
 void launch_step_t(ppo_handle* h, const StepArgs& a0) {
     StepArgs a = a0;
-    dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    a.stamps = grid.x <= 256 ? g_stamps + 4096 * 44 : nullptr;
-#endif
-    hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT, MASK>), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
+    const dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
+    SET_STAMPS(a.stamps, grid.x <= 256, 4096 * 44);
+    const size_t lds = (size_t)h->lds_step_total * sizeof(float);
+#define X(CT, KS, CTH, WIDE) hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT, MASK>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, a)
+    if (h->net.wide) { if (h->CT == 4) X(4, 2, 0, true); else X(1, 1, 0, true); }
+    else if (h->CT == 4 && h->CTH == 2) X(4, 2, 2, false);
+    else if (h->CT == 4) X(4, 2, 0, false);
+    else X(1, 1, 0, false);
+#undef X
+}
+// narrow_step_kernel: the packed weight image stands in for the padded parameter vector
+template <bool CAT, bool MASK>
+void launch_narrow_step(ppo_handle* h, const StepArgs& a) {
+    const dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
+    StepArgs sa = a;
+    sa.theta = h->nw_img;
+    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, CAT, MASK>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
+    NW_DISPATCH(h, X);
+#undef X
 }
 int launch_step(ppo_handle* h, const StepArgs& a) {
     if (h->bf.on) { ++h->kv[KV_BF16_STEP]; return launch_step_bf16(h, a); }
     ProfScope ps(h, PK_STEP);
-    if (a.mask && h->dist != PPO_ACT_CATEGORICAL) return fail(h, "policy step: an action mask needs a categorical handle");
-    if (nw_cat(h)) {                                              // narrow family, categorical head (PPO_ACT_SHAPE_KERNELS)
-        ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : KV_NARROW_STEP_CAT];
-        dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
-        StepArgs sa = a;
-        sa.theta = h->nw_img;
-        const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, true, true>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
-#define Y(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, true>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
-        if (sa.mask) NW_DISPATCH(h, X); else NW_DISPATCH(h, Y);
-#undef X
-#undef Y
-        HIP_OK(h, hipGetLastError());
-        return 0;
+    const bool cat = h->dist == PPO_ACT_CATEGORICAL;
+    if (a.mask && !cat) return fail(h, "policy step: an action mask needs a categorical handle");
+    if (h->narrow) {                                              // (a categorical handle here: created with PPO_ACT_SHAPE_KERNELS)
+        ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : cat ? KV_NARROW_STEP_CAT : h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP];
+        if (a.mask) launch_narrow_step<true, true>(h, a); else if (cat) launch_narrow_step<true, false>(h, a); else launch_narrow_step<false, false>(h, a);
+    } else {
+        ++h->kv[a.mask ? KV_POLICY_STEP_CAT_MASK : cat ? KV_POLICY_STEP_CAT : KV_POLICY_STEP];
+        if (a.mask) launch_step_t<true, true>(h, a); else if (cat) launch_step_t<true, false>(h, a); else launch_step_t<false, false>(h, a);
     }
-    if (a.mask) {
-        ++h->kv[KV_POLICY_STEP_CAT_MASK];
-        if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true, true, true>(h, a); else launch_step_t<1, 1, 0, true, true, true>(h, a); }
-        else if (h->CT == 4 && h->CTH == 2) launch_step_t<4, 2, 2, false, true, true>(h, a);
-        else if (h->CT == 4) launch_step_t<4, 2, 0, false, true, true>(h, a);
-        else launch_step_t<1, 1, 0, false, true, true>(h, a);
-        HIP_OK(h, hipGetLastError());
-        return 0;
-    }
-    if (h->dist == PPO_ACT_CATEGORICAL) {
-        ++h->kv[KV_POLICY_STEP_CAT];
-        if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true, true>(h, a); else launch_step_t<1, 1, 0, true, true>(h, a); }
-        else if (h->CT == 4 && h->CTH == 2) launch_step_t<4, 2, 2, false, true>(h, a);
-        else if (h->CT == 4) launch_step_t<4, 2, 0, false, true>(h, a);
-        else launch_step_t<1, 1, 0, false, true>(h, a);
-        HIP_OK(h, hipGetLastError());
-        return 0;
-    }
-    ++h->kv[h->narrow ? (h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP) : KV_POLICY_STEP];
-    if (h->narrow) {
-        dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
-        StepArgs sa = a;
-        sa.theta = h->nw_img;                                  // the packed weight image stands in for the padded parameter vector
-        const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
-        NW_DISPATCH(h, X);
-#undef X
-        HIP_OK(h, hipGetLastError());
-        return 0;
-    }
-    if (h->net.wide) { if (h->CT == 4) launch_step_t<4, 2, 0, true>(h, a); else launch_step_t<1, 1, 0, true>(h, a); }
-    else if (h->CT == 4 && h->CTH == 2) launch_step_t<4, 2, 2, false>(h, a);
-    else if (h->CT == 4) launch_step_t<4, 2, 0, false>(h, a);
-    else launch_step_t<1, 1, 0, false>(h, a);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1227,10 +1211,7 @@ int enqueue_adam(ppo_handle* h, float* loss_row, int n_sumsq = 0, const float* p
                 h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm, loss_row, h->norm_out, parts, n_parts,
                 0, {}, h->bf.on ? h->bf.theta_bf : nullptr, h->narrow ? h->nw_img : nullptr, nullptr, nullptr, nullptr};
     aa.n_tiled = h->n_tiled; for (int q = 0; q < h->n_tiled; ++q) aa.tiled[q] = h->tiled[q];
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    aa.stamps = g_stamps + 4096 * 40;
-#endif
+    SET_STAMPS(aa.stamps, true, 4096 * 40);
     if (h->nw_cur == 1) { aa.theta_in = h->nw_theta1; aa.m_in = h->nw_m1; aa.v_in = h->nw_v1; h->nw_cur = 0; }   // (always writes set 0)
     const dim3 grid((h->n_blocks + 3) / 4);
     if (meet) {
@@ -1248,28 +1229,83 @@ int enqueue_adam(ppo_handle* h, float* loss_row, int n_sumsq = 0, const float* p
     return 0;
 }
 
-// the [256,256] pair: one instantiation per (observation tile, action tile) width
-template <int KP0, int AP>
-void launch_train8(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
-    const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL;
-    hipLaunchKernelGGL((train8_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta);
+// the [256,256] pair's launches (PAIR_DISPATCH picks the instantiation)
+static void launch_train8(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+#define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL; \
+                        hipLaunchKernelGGL((train8_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+    PAIR_DISPATCH(h, X);
+#undef X
 }
-template <int KP0, int AP>
-void launch_dw2(ppo_handle* h, const Dw2Args& da) {
-    const size_t lds = sizeof(float) * Dw2L<KP0, AP>::LDS_FLOATS;
-    hipLaunchKernelGGL((weight_grad_assemble_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da);
+// peer: the tiles' finishers push to the peers' regions themselves
+static void launch_dw2(ppo_handle* h, const Dw2Args& da, bool peer) {
+#define X(KP0, AP) do { const size_t lds = sizeof(float) * Dw2L<KP0, AP>::LDS_FLOATS; \
+                        if (peer) hipLaunchKernelGGL((weight_grad_assemble_peer_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da, h->peer.dev); \
+                        else hipLaunchKernelGGL((weight_grad_assemble_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da); } while (0)
+    PAIR_DISPATCH(h, X);
+#undef X
 }
-template <int KP0, int AP>
-void launch_dw2_peer(ppo_handle* h, const Dw2Args& da) {
-    const size_t lds = sizeof(float) * Dw2L<KP0, AP>::LDS_FLOATS;
-    hipLaunchKernelGGL((weight_grad_assemble_peer_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da, h->peer.dev);
+// the dynamic LDS of the handle's three pair kernels (ppo_create_ex)
+static bool set_lds_pair(const ppo_handle* h) {
+    bool ok = true;
+    auto set = [&](const void* f, size_t floats) { ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * floats)) == hipSuccess; };
+#define X(KP0, AP) do { set((const void*)weight_grad_assemble_peer_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
+                        set((const void*)weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); } while (0)
+    PAIR_DISPATCH(h, X);
+#undef X
+    return ok;
 }
-template <int KP0, int AP>
-bool set_lds_pair() {
-    return hipFuncSetAttribute((const void*)weight_grad_assemble_peer_kernel<KP0, AP>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * Dw2L<KP0, AP>::LDS_FLOATS) == hipSuccess &&
-           hipFuncSetAttribute((const void*)train8_kernel<KP0, AP>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * T8L<KP0, AP>::TOTAL) == hipSuccess &&
-           hipFuncSetAttribute((const void*)weight_grad_assemble_kernel<KP0, AP>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * Dw2L<KP0, AP>::LDS_FLOATS) == hipSuccess;
+
+// ---- one train step: which form, its argument blocks -----------------------------------------------------------------------
+// narrow: narrow_train_kernel + narrow_reduce_kernel | bf16, data parallel over the collective library: a gradient bucket per backward link | bf16: one assembly
+// (with clip + Adam in the same launch on one GPU) | the [256,256] pair with the tiles pushed to the peers | the pair (train8_kernel or train_fwd_bwd_kernel, then
+// weight_grad_assemble_kernel) | any other fp32 shape: train_fwd_bwd_kernel, weight_grad_kernel, grad_reduce_kernel
+enum TrainForm { TF_NARROW, TF_BF16_BUCKETED, TF_BF16, TF_PAIR_PEER, TF_PAIR, TF_GENERIC };
+
+// switches that are read per call: tests compare the forms in one process (a graph keeps what it captured)
+static bool env_set(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+static bool use_peer_tiles() { return !env_set("PPO_HIP_NO_PEER_TILES"); }
+// bf16, one GPU: assembly, clip and Adam in one persistent launch (ppo_bf16.hpp, bf16_reduce_adam_kernel)
+static bool use_reduce_adam(const ppo_handle* h) { return !h->comm && h->bf.fuse_ra && !h->adam_fast && !env_set("PPO_HIP_NO_REDUCE_ADAM"); }
+// (read at ppo_create_ex, where the form's buffers are allocated, and again when an update is enqueued: a test compares both forms on handles of one process)
+static bool use_narrow_epoch() { return !env_set("PPO_HIP_NO_NARROW_EPOCH"); }
+
+// weight_grad_assemble_kernel walks the minibatch in 64-row chunks.  train8_kernel writes zeros for every row >= n of every tile
+// it is launched on, so its grid is simply padded to whole chunks (ANY row count stays on the fast pair); behind the round-2
+// train kernel the pair needs a minibatch that is a whole number of chunks by itself.
+static bool use_dw2(const ppo_handle* h, int n) { return h->dw2 && (h->t8 || n % DW2_CH == 0) && ru(n, DW2_CH) / ROWS_PER_BLOCK <= 32 * DW2_SLOTK; }
+
+static TrainForm train_form(const ppo_handle* h, int n) {
+    if (h->narrow) return TF_NARROW;
+    if (h->bf.on) {
+        const bool bucketed = h->comm && !h->peer.on && h->net.L >= 2 && (h->bf.bucketed_any_world || (h->world > 1 && h->bf.bucketed));
+        return bucketed ? TF_BF16_BUCKETED : TF_BF16;
+    }
+    if (!use_dw2(h, n)) return TF_GENERIC;
+    // data parallel over peer regions: the tiles' finishers push to the peers themselves and adam_kernel adds the ranks up (no push / sum launches)
+    const bool peer_tiles = h->comm && h->peer.on && use_peer_tiles() && adam_can_meet(h) && (size_t)h->P_pad + 8 <= h->peer.cap;
+    return peer_tiles ? TF_PAIR_PEER : TF_PAIR;
 }
+
+// what enqueue_adam sums for the global norm: n entries of `from` (0: one per 256-element chunk; null: h->sumsq)
+struct AdamParts { int n = 0; const float* from = nullptr; };
+// a form's function returns -1 (error), 0 (the gradient is assembled in h->grad: the shared tail follows) or TRAIN_DONE (it applied the step itself)
+enum { TRAIN_DONE = 1 };
+
+// the assembly's arguments every form shares; the bf16 callers add their sk_*, direct* and chunk_* fields, the generic one its split
+static ReduceArgs reduce_args(const ppo_handle* h, const TrainArgs& ta, int n_rowblocks) {
+    ReduceArgs ra{};
+    ra.src = h->grad_src; ra.n_blocks = h->n_blocks; ra.slabs = h->slabs; ra.slab_stride = (size_t)h->P_pad; ra.nsplit = 0;
+    ra.slots[0] = h->slots[0]; ra.slots[1] = h->slots[1]; ra.n_rowblocks = n_rowblocks; ra.slot_w = h->net.slot_w; ra.slot_loss = h->net.slot_loss;
+    ra.grad = h->grad; ra.sumsq = h->sumsq; ra.n_local = (float)ta.n; ra.beta_pow = h->beta_pow;
+    return ra;
+}
+static ReduceArgs bf16_reduce_args(const ppo_handle* h, const TrainArgs& ta, int Rp) {
+    ReduceArgs ra = reduce_args(h, ta, Rp / BL_ROWS);
+    ra.sk_bm = GB_BM(h->bf.dw_wm); ra.direct = h->bf.dbias; ra.n_direct = Rp / (Rp % 256 == 0 ? 256 : 128); ra.direct_stride = h->bf.n_dbias;
+    return ra;
+}
+// workgroups of bf16_grad_reduce_kernel over the whole vector (+ the tail block)
+static int bf16_reduce_groups(const ppo_handle* h) { return (h->n_blocks + 1 + BGR_WAVES - 1) / BGR_WAVES; }
 
 // Data parallel over the collective library, bf16 path (BASELINE configs[4]: 19 MB of gradient per train step): the gradient leaves in BUCKETS, last layer + heads first.
 // Backward link k (a launch of its own here; the single-rank step chains them) is followed by the weight-gradient GEMM of exactly the matrices it completed (a contiguous
@@ -1290,23 +1326,18 @@ int bf16_train_bucketed(ppo_handle* h, const TrainArgs& ta, int Rp, float* loss_
     GemmArgs bl[PPO_MAX_LAYERS];
     int outw[PPO_MAX_LAYERS];
     (void)bf16_backward_links(h, bl, outw);
-    int nst, per_all, groups_all;
-    bf16_dw_split(h, Rp, nst, per_all, groups_all);
+    int per_all, groups_all;
+    ReduceArgs ra = bf16_reduce_args(h, ta, Rp);
+    bf16_dw_split(h, Rp, ra.sk_nst, per_all, groups_all);
     for (int k = 0; k < n.L; ++k) {
         const int l = n.L - 1 - k;                           // the layer whose pre-activation gradient this link completes
         { ProfScope ps(h, PK_TRAIN_FB); if (bf16_gemm<GEPI_TANHGRAD>(h, bl[k], Rp, outw[k])) return -1; }
         const int t0 = b.layer_tile0[l], t1 = k == 0 ? b.layer_tile0[n.L + 1] : b.layer_tile0[l + 1];
-        int per = 0;
-        { ProfScope ps(h, PK_DW); if (bf16_weight_grads(h, ta, Rp, t0, t1 - t0, &per)) return -1; }
+        { ProfScope ps(h, PK_DW); if (bf16_weight_grads(h, ta, Rp, t0, t1 - t0, &ra.sk_per)) return -1; }
         const int c0 = n.w_off[0][l] / 256, c1 = k == 0 ? h->n_blocks : n.w_off[0][l + 1] / 256;
         {
             ProfScope ps(h, PK_REDUCE);
-            ReduceArgs ra{};
-            ra.sk_nst = nst; ra.sk_per = per; ra.sk_bm = GB_BM(b.dw_wm); ra.sk_tile_base = t0; ra.chunk_lo = c0; ra.chunk_hi = c1;
-            ra.src = h->grad_src; ra.n_blocks = h->n_blocks; ra.slabs = h->slabs; ra.slab_stride = (size_t)h->P_pad; ra.nsplit = 0;
-            ra.slots[0] = h->slots[0]; ra.slots[1] = h->slots[1]; ra.n_rowblocks = Rp / BL_ROWS; ra.slot_w = n.slot_w; ra.slot_loss = n.slot_loss;
-            ra.grad = h->grad; ra.sumsq = h->sumsq; ra.n_local = (float)ta.n; ra.beta_pow = h->beta_pow; ra.direct = b.dbias;
-            ra.n_direct = Rp / (Rp % 256 == 0 ? 256 : 128); ra.direct_stride = b.n_dbias;
+            ra.sk_tile_base = t0; ra.chunk_lo = c0; ra.chunk_hi = c1;
             const int chunks = c1 - c0 + (k == 0 ? 1 : 0);     // (+ the tail block: loss sums, row count, the powers' cur <- next, with the bucket at the vector's end)
             hipLaunchKernelGGL(bf16_grad_reduce_kernel, dim3((chunks + BGR_WAVES - 1) / BGR_WAVES), dim3(64 * BGR_WAVES), 0, h->stream, ra);
             HIP_OK(h, hipGetLastError());
@@ -1328,210 +1359,150 @@ int bf16_train_bucketed(ppo_handle* h, const TrainArgs& ta, int Rp, float* loss_
     return enqueue_adam(h, loss_row);
 }
 
-// the per-minibatch launch sequence: fwd+loss+bwd -> weight grads -> reduce [-> all-reduce] -> clip+Adam
-// defer (narrow reference shape, inside ppo_update only): leave this step's clip + Adam to the next train kernel's prologue
-// (flush_pending_adam after the last step)
-int enqueue_train(ppo_handle* h, TrainArgs ta, float* loss_row, bool defer = false) {
-    const NetDev& n = h->net;
-    ta.theta = h->theta; ta.thetaT = h->thetaT; ta.par = h->par; ta.hyper = h->hyper;
-    ta.x0g = h->x0g; ta.dmug = h->dmug;
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    ta.stamps = g_stamps;
-#endif
-    for (int t = 0; t < 2; ++t) {
-        ta.slots[t] = h->slots[t];
-        for (int l = 0; l < n.L; ++l) { ta.hg[t][l] = h->hg[t][l]; ta.dyg[t][l] = h->dyg[t][l]; }
-    }
-    if (h->narrow) {
-        const int groups = (ta.n + NW_ROWS - 1) / NW_ROWS;
-        {
-            ProfScope ps(h, PK_TRAIN_FB);
-            NwTrainArgs na{h->nw_img, ta.obs, ta.actions, ta.advs, ta.returns, ta.old_values, ta.old_neglogp, h->hyper, ta.n, ta.inv_n,
-                           h->nw_partials, groups, h->nw_stride, nullptr, ta.mask};
-#ifdef PPO_STAMPS
-            if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-            na.stamps = g_stamps;
-#endif
-            const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-            NwLazyArgs z{};
-            ++h->kv[nw_cat(h) ? (ta.mask ? KV_NARROW_TRAIN_CAT_MASK : KV_NARROW_TRAIN_CAT) : h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
-            if (nw_cat(h)) {                                      // (never deferred: nw_lazy is a Gaussian handle's)
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z)
-#define Y(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z)
-                if (na.mask) NW_DISPATCH(h, X); else NW_DISPATCH(h, Y);
+// assembly + clip + Adam as ONE persistent launch; the assembled gradient is not written (LazyGrad)
+static int bf16_reduce_adam(ppo_handle* h, const ReduceArgs& ra, int n_old, float* loss_row) {
+    h->bf.lazy.enqueued = LazyGrad{true, ra, n_old};
+    ReduceAdamArgs fa{ra, h->theta, h->adam_m, h->adam_v, h->bf.theta_bf, h->hyper, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm,
+                      loss_row, h->norm_out, h->bf.ra_ent, n_old, /*store_grad*/ 0};
+    const int rounds = (n_old + BRA_GRID - 1) / BRA_GRID;
+    const dim3 g(BRA_GRID), blk(64 * BGR_WAVES);
+    ++h->kv[KV_BF16_REDUCE_ADAM];
+    if (rounds <= 1) hipLaunchKernelGGL(bf16_reduce_adam_kernel<1>, g, blk, 0, h->stream, fa);
+    else if (rounds <= 2) hipLaunchKernelGGL(bf16_reduce_adam_kernel<2>, g, blk, 0, h->stream, fa);
+    else if (rounds <= 3) hipLaunchKernelGGL(bf16_reduce_adam_kernel<3>, g, blk, 0, h->stream, fa);
+    else if (rounds <= 5) hipLaunchKernelGGL(bf16_reduce_adam_kernel<5>, g, blk, 0, h->stream, fa);
+    else hipLaunchKernelGGL(bf16_reduce_adam_kernel<8>, g, blk, 0, h->stream, fa);
+    HIP_OK(h, hipGetLastError());
+    return TRAIN_DONE;
+}
+
+static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool bucketed, AdamParts& parts) {
+    const int Rp = ru(ta.n, GB_PAD);
+    ++h->kv[KV_BF16_TRAIN];
+    h->bf.lazy.enqueued.on = false;
+    if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
+    { ProfScope ps(h, PK_TRAIN_FB); if (bf16_train_fwd_bwd(h, ta, Rp)) return -1; }
+    { ProfScope ps(h, PK_DW); if (bf16_weight_grads(h, ta, Rp)) return -1; }
+    ProfScope ps(h, PK_REDUCE);
+    ReduceArgs ra = bf16_reduce_args(h, ta, Rp);
+    int groups;
+    bf16_dw_split(h, Rp, ra.sk_nst, ra.sk_per, groups);
+    const int n_old = bf16_reduce_groups(h);
+    if (use_reduce_adam(h)) return bf16_reduce_adam(h, ra, n_old, loss_row);
+    hipLaunchKernelGGL(bf16_grad_reduce_kernel, dim3(n_old), dim3(64 * BGR_WAVES), 0, h->stream, ra);
+    HIP_OK(h, hipGetLastError());
+    parts = AdamParts{n_old, nullptr};                            // one partial per assembly workgroup (adam_kernel keeps the bf16 copy of the weights current)
+    return 0;
+}
+
+// narrow_train_kernel: LAZY (the previous step's clip + Adam in the prologue) exists for the static shapes only
+template <bool LAZY, bool EXACT, bool CAT, bool MASK>
+static void launch_narrow_train(ppo_handle* h, int groups, const NwTrainArgs& na, const NwLazyArgs& z) {
+    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, LAZY, EXACT, CAT, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, z)
+    if constexpr (LAZY) { if (h->net.Kp0 == 32) X(32, 64, 32, 2); else X(64, 64, 32, 2); }
+    else NW_DISPATCH(h, X);
 #undef X
-#undef Y
-            }
-            else if (h->nw_pending) {
-                // the previous step's clip + Adam rides in this launch: read set nw_cur, write the other one
-                float* set[2][3] = {{h->theta, h->adam_m, h->adam_v}, {h->nw_theta1, h->nw_m1, h->nw_v1}};
-                const int ci = h->nw_cur, co = ci ^ 1;
-                z = NwLazyArgs{h->grad, h->sumsq, h->nw_pending_parts, set[ci][0], set[ci][1], set[ci][2], set[co][0], set[co][1], set[co][2], h->beta_pow,
-                               h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm, h->nw_pending_loss, h->norm_out};
-                if (h->adam_exact) {
-                    if (n.Kp0 == 32) hipLaunchKernelGGL((narrow_train_kernel<32, 64, 32, 2, true, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z);
-                    else hipLaunchKernelGGL((narrow_train_kernel<64, 64, 32, 2, true, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z);
-                }
-                else if (n.Kp0 == 32) hipLaunchKernelGGL((narrow_train_kernel<32, 64, 32, 2, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z);
-                else hipLaunchKernelGGL((narrow_train_kernel<64, 64, 32, 2, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z);
-                h->nw_cur = co; h->nw_pending = false;
-            }
-            else {
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, n, h->nw, na, z)
-                NW_DISPATCH(h, X);
-#undef X
-            }
-            HIP_OK(h, hipGetLastError());
-        }
-        const int n_chunks = h->P_pad / 64;
-        {
-            ProfScope ps(h, PK_REDUCE);
-            NwReduceArgs ra{h->grad_src, n_chunks, h->nw_partials, groups, h->nw_stride, h->P_pad, h->grad, h->sumsq, (float)ta.n, h->beta_pow};
-            hipLaunchKernelGGL(narrow_reduce_kernel, dim3(n_chunks + 1), dim3(256), 0, h->stream, ra);
-            HIP_OK(h, hipGetLastError());
-        }
-        if (h->comm && enqueue_grad_allreduce(h)) return -1;
-        const int n_parts = h->comm ? 0 : n_chunks;               // after an all-reduce: one partial per 256-element chunk (grad_sumsq_kernel's)
-        if (defer && h->nw_lazy) { h->nw_pending = true; h->nw_pending_loss = loss_row; h->nw_pending_parts = n_parts ? n_parts : h->n_blocks; return 0; }
-        return enqueue_adam(h, loss_row, n_parts);
-    }
-    if (h->bf.on) {
-        const int Rp = ru(ta.n, GB_PAD);
-        ++h->kv[KV_BF16_TRAIN];
-        h->bf.lazy_last = false;
-        if (h->comm && !h->peer.on && h->net.L >= 2 && (h->bf.bucketed_any_world || (h->world > 1 && h->bf.bucketed))) return bf16_train_bucketed(h, ta, Rp, loss_row);
-        { ProfScope ps(h, PK_TRAIN_FB); if (bf16_train_fwd_bwd(h, ta, Rp)) return -1; }
-        { ProfScope ps(h, PK_DW); if (bf16_weight_grads(h, ta, Rp)) return -1; }
-        {
-            ProfScope ps(h, PK_REDUCE);
-            ReduceArgs ra{};
-            int groups;
-            bf16_dw_split(h, Rp, ra.sk_nst, ra.sk_per, groups); ra.sk_bm = GB_BM(h->bf.dw_wm);
-            ra.src = h->grad_src; ra.n_blocks = h->n_blocks; ra.slabs = h->slabs; ra.slab_stride = (size_t)h->P_pad; ra.nsplit = 0;
-            ra.slots[0] = h->slots[0]; ra.slots[1] = h->slots[1]; ra.n_rowblocks = Rp / BL_ROWS; ra.slot_w = n.slot_w; ra.slot_loss = n.slot_loss;
-            ra.grad = h->grad; ra.sumsq = h->sumsq; ra.n_local = (float)ta.n; ra.beta_pow = h->beta_pow; ra.direct = h->bf.dbias;
-            ra.n_direct = Rp / (Rp % 256 == 0 ? 256 : 128); ra.direct_stride = h->bf.n_dbias;
-            const int n_old = (h->n_blocks + 1 + BGR_WAVES - 1) / BGR_WAVES;
-            const char* e1 = getenv("PPO_HIP_NO_REDUCE_ADAM");                  // (read per call: a test compares the forms in one process; a graph keeps what it captured)
-            if (!h->comm && h->bf.fuse_ra && !h->adam_fast && !(e1 && e1[0] == '1')) {
-                // ... and clip + Adam in the same persistent launch (ppo_bf16.hpp, bf16_reduce_adam_kernel)
-                h->bf.lazy_ra = ra; h->bf.lazy_n_old = n_old; h->bf.lazy_last = true;
-                ReduceAdamArgs fa{ra, h->theta, h->adam_m, h->adam_v, h->bf.theta_bf, h->hyper, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm,
-                                  loss_row, h->norm_out, h->bf.ra_ent, n_old, /*store_grad*/ 0};
-                const int rounds = (n_old + BRA_GRID - 1) / BRA_GRID;
-                const dim3 g(BRA_GRID), blk(64 * BGR_WAVES);
-                ++h->kv[KV_BF16_REDUCE_ADAM];
-                if (rounds <= 1) hipLaunchKernelGGL(bf16_reduce_adam_kernel<1>, g, blk, 0, h->stream, fa);
-                else if (rounds <= 2) hipLaunchKernelGGL(bf16_reduce_adam_kernel<2>, g, blk, 0, h->stream, fa);
-                else if (rounds <= 3) hipLaunchKernelGGL(bf16_reduce_adam_kernel<3>, g, blk, 0, h->stream, fa);
-                else if (rounds <= 5) hipLaunchKernelGGL(bf16_reduce_adam_kernel<5>, g, blk, 0, h->stream, fa);
-                else hipLaunchKernelGGL(bf16_reduce_adam_kernel<8>, g, blk, 0, h->stream, fa);
-                HIP_OK(h, hipGetLastError());
-                return 0;
-            }
-            hipLaunchKernelGGL(bf16_grad_reduce_kernel, dim3(n_old), dim3(64 * BGR_WAVES), 0, h->stream, ra);
-            HIP_OK(h, hipGetLastError());
-        }
-        if (h->comm) return enqueue_grad_allreduce(h) ? -1 : enqueue_adam(h, loss_row);      // (the exchange recomputes the per-chunk sums of squares)
-        return enqueue_adam(h, loss_row, (h->n_blocks + 1 + BGR_WAVES - 1) / BGR_WAVES);       // one partial per assembly workgroup (adam_kernel keeps the bf16 copy of the weights current)
-    }
-    // weight_grad_assemble_kernel walks the minibatch in 64-row chunks.  train8_kernel writes zeros for every row >= n of every tile
-    // it is launched on, so its grid is simply padded to whole chunks (ANY row count stays on the fast pair); behind the round-2
-    // train kernel the pair needs a minibatch that is a whole number of chunks by itself.
-    const bool use_dw2 = h->dw2 && (h->t8 || ta.n % DW2_CH == 0) && ru(ta.n, DW2_CH) / ROWS_PER_BLOCK <= 32 * DW2_SLOTK;
-    const int n_pad = use_dw2 ? ru(ta.n, DW2_CH) : ru(ta.n, ROWS_PER_BLOCK);            // the train kernel zero-fills the rows of its last partial tile
-    const int n_rb = n_pad / ROWS_PER_BLOCK;
-    ta.xcd_map = use_dw2 ? 1 : 0;
-    Dw2Args da{};
-    if (use_dw2) {
-        da.x0g = h->x0g; da.h2pi = h->hg[0][1]; da.dmug = h->dmug;
-        for (int t = 0; t < 2; ++t) { da.h1[t] = h->hg[t][0]; da.dy0[t] = h->dyg[t][0]; da.dy1[t] = h->dyg[t][1]; da.w0_off[t] = n.w_off[t][0]; da.w1_off[t] = n.w_off[t][1]; da.slots[t] = h->slots[t]; }
-        da.wmu_off = n.wmu_off; da.n = n_pad; da.slabs = h->slabs; da.slab_stride = (unsigned long long)h->P_pad; da.counters = h->dw2_counters;
-        da.grad = h->grad; da.parts = h->dw2_parts; da.jobs = h->dw2_jobs; da.n_jobs = h->dw2_n_jobs; da.jobs_per_wg = h->dw2_jpw;
-#ifdef PPO_STAMPS
-        da.stamps = g_stamps + 4096 * 16;
-#endif
-        da.n_rowblocks = n_rb; da.slot_w = n.slot_w; da.n_local = (float)ta.n; da.beta_pow = h->beta_pow; da.tail_off = h->P_pad;
-    }
+}
+
+static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
+    const int groups = (ta.n + NW_ROWS - 1) / NW_ROWS;
     {
         ProfScope ps(h, PK_TRAIN_FB);
-        dim3 grid(n_rb, 2);
-        const size_t lds_bytes = (size_t)n.lds_total * sizeof(float);
-        const dim3 blk(BLOCK_THREADS);
-        ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : h->dist == PPO_ACT_CATEGORICAL ? KV_TRAIN_FB_CAT : (h->t8 && !n.wide) ? KV_TRAIN8 : KV_TRAIN_FB];
-        if (ta.mask) {                                           // (a categorical handle: the entry points check)
-            if (n.wide) {
-                if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
-                else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            }
-            else if (h->CT == 4 && h->CTH == 2 && h->early) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, true, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else if (h->CT == 4 && h->CTH == 2) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, false, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, false, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
+        NwTrainArgs na{h->nw_img, ta.obs, ta.actions, ta.advs, ta.returns, ta.old_values, ta.old_neglogp, h->hyper, ta.n, ta.inv_n,
+                       h->nw_partials, groups, h->nw_stride, nullptr, ta.mask};
+        SET_STAMPS(na.stamps, true, 0);
+        NwLazyArgs z{};
+        ++h->kv[nw_cat(h) ? (ta.mask ? KV_NARROW_TRAIN_CAT_MASK : KV_NARROW_TRAIN_CAT) : h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
+        if (nw_cat(h)) {                                          // (never deferred: nw_lazy is a Gaussian handle's)
+            if (na.mask) launch_narrow_train<false, false, true, true>(h, groups, na, z); else launch_narrow_train<false, false, true, false>(h, groups, na, z);
         }
-        else if (h->dist == PPO_ACT_CATEGORICAL) {                    // (no train8 / dw2 for this head: ppo_create_ex)
-            if (n.wide) {
-                if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
-                else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            }
-            else if (h->CT == 4 && h->CTH == 2 && h->early) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, true, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else if (h->CT == 4 && h->CTH == 2) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, false, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, false, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
+        else if (h->nw_pending) {
+            // the previous step's clip + Adam rides in this launch: read set nw_cur, write the other one
+            float* set[2][3] = {{h->theta, h->adam_m, h->adam_v}, {h->nw_theta1, h->nw_m1, h->nw_v1}};
+            const int ci = h->nw_cur, co = ci ^ 1;
+            z = NwLazyArgs{h->grad, h->sumsq, h->nw_pending_parts, set[ci][0], set[ci][1], set[ci][2], set[co][0], set[co][1], set[co][2], h->beta_pow,
+                           h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm, h->nw_pending_loss, h->norm_out};
+            if (h->adam_exact) launch_narrow_train<true, true, false, false>(h, groups, na, z); else launch_narrow_train<true, false, false, false>(h, groups, na, z);
+            h->nw_cur = co; h->nw_pending = false;
         }
-        else if (n.wide) {
-            if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, true>), grid, blk, lds_bytes, h->stream, n, ta);
-            else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, true>), grid, blk, lds_bytes, h->stream, n, ta);
-        }
-        else if (h->t8) {
-            if (n.Kp0 == 32 && n.Ap == 32) launch_train8<32, 32>(h, grid, ta);
-            else if (n.Kp0 == 64 && n.Ap == 32) launch_train8<64, 32>(h, grid, ta);
-            else if (n.Kp0 == 32 && n.Ap == 64) launch_train8<32, 64>(h, grid, ta);
-            else launch_train8<64, 64>(h, grid, ta);
-        }
-        else if (h->CT == 4 && h->CTH == 2 && h->early) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false, true>), grid, blk, lds_bytes, h->stream, n, ta);
-        else if (h->CT == 4 && h->CTH == 2) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 2, false>), grid, blk, lds_bytes, h->stream, n, ta);
-        else if (h->CT == 4) hipLaunchKernelGGL((train_fwd_bwd_kernel<4, 2, 0, false>), grid, blk, lds_bytes, h->stream, n, ta);
-        else hipLaunchKernelGGL((train_fwd_bwd_kernel<1, 1, 0, false>), grid, blk, lds_bytes, h->stream, n, ta);
+        else launch_narrow_train<false, false, false, false>(h, groups, na, z);
         HIP_OK(h, hipGetLastError());
     }
-    // data parallel over peer regions: the tiles' finishers push to the peers themselves and adam_kernel adds the ranks up (no push / sum launches)
-    const char* npt = getenv("PPO_HIP_NO_PEER_TILES");           // (read per call: a test compares the two forms in one process; a graph keeps what it captured)
-    const bool no_peer_tiles = npt && npt[0] == '1';
-    if (use_dw2 && h->comm && h->peer.on && !no_peer_tiles && adam_can_meet(h) && (size_t)h->P_pad + 8 <= h->peer.cap) {
-        {
-            ProfScope ps(h, PK_DW);
-            ++h->kv[KV_DW2];
-            if (n.Kp0 == 32 && n.Ap == 32) launch_dw2_peer<32, 32>(h, da);
-            else if (n.Kp0 == 64 && n.Ap == 32) launch_dw2_peer<64, 32>(h, da);
-            else if (n.Kp0 == 32 && n.Ap == 64) launch_dw2_peer<32, 64>(h, da);
-            else launch_dw2_peer<64, 64>(h, da);
-            HIP_OK(h, hipGetLastError());
-        }
-        return enqueue_adam(h, loss_row, 0, nullptr, 2);
+    const int n_chunks = h->P_pad / 64;
+    ProfScope ps(h, PK_REDUCE);
+    NwReduceArgs ra{h->grad_src, n_chunks, h->nw_partials, groups, h->nw_stride, h->P_pad, h->grad, h->sumsq, (float)ta.n, h->beta_pow};
+    hipLaunchKernelGGL(narrow_reduce_kernel, dim3(n_chunks + 1), dim3(256), 0, h->stream, ra);
+    HIP_OK(h, hipGetLastError());
+    parts = AdamParts{n_chunks, nullptr};
+    return 0;
+}
+
+// train_fwd_bwd_kernel: the (CT, KS, CTH, WIDE, EARLY) ladder of the handle's layout, once; the caller picks the head
+template <bool CAT, bool MASK>
+static void launch_train_fb(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+    const size_t lds = (size_t)h->net.lds_total * sizeof(float);
+#define X(CT, KS, CTH, WIDE, EARLY) hipLaunchKernelGGL((train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, CAT, MASK>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, ta)
+    if (h->net.wide) { if (h->CT == 4) X(4, 2, 0, true, false); else X(1, 1, 0, true, false); }
+    else if (h->CT == 4 && h->CTH == 2 && h->early) X(4, 2, 2, false, true);
+    else if (h->CT == 4 && h->CTH == 2) X(4, 2, 2, false, false);
+    else if (h->CT == 4) X(4, 2, 0, false, false);
+    else X(1, 1, 0, false, false);
+#undef X
+}
+
+// fp32 forward + loss + backward over n_pad rows (the kernels zero-fill the rows of their last partial tile)
+static int enqueue_train_fb(ppo_handle* h, const TrainArgs& ta, int n_pad) {
+    ProfScope ps(h, PK_TRAIN_FB);
+    const dim3 grid(n_pad / ROWS_PER_BLOCK, 2);
+    const bool cat = h->dist == PPO_ACT_CATEGORICAL;              // (a mask: a categorical handle, the entry points check; t8: Gaussian and not wide, ppo_create_ex)
+    ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : cat ? KV_TRAIN_FB_CAT : h->t8 ? KV_TRAIN8 : KV_TRAIN_FB];
+    if (ta.mask) launch_train_fb<true, true>(h, grid, ta);
+    else if (cat) launch_train_fb<true, false>(h, grid, ta);
+    else if (h->t8) launch_train8(h, grid, ta);
+    else launch_train_fb<false, false>(h, grid, ta);
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
+static Dw2Args dw2_args(const ppo_handle* h, int n_rows, int n_pad) {
+    const NetDev& n = h->net;
+    Dw2Args da{};
+    da.x0g = h->x0g; da.h2pi = h->hg[0][1]; da.dmug = h->dmug;
+    for (int t = 0; t < 2; ++t) { da.h1[t] = h->hg[t][0]; da.dy0[t] = h->dyg[t][0]; da.dy1[t] = h->dyg[t][1]; da.w0_off[t] = n.w_off[t][0]; da.w1_off[t] = n.w_off[t][1]; da.slots[t] = h->slots[t]; }
+    da.wmu_off = n.wmu_off; da.n = n_pad; da.slabs = h->slabs; da.slab_stride = (unsigned long long)h->P_pad; da.counters = h->dw2_counters;
+    da.grad = h->grad; da.parts = h->dw2_parts; da.jobs = h->dw2_jobs; da.n_jobs = h->dw2_n_jobs; da.jobs_per_wg = h->dw2_jpw;
+    SET_STAMPS(da.stamps, true, 4096 * 16);
+    da.n_rowblocks = n_pad / ROWS_PER_BLOCK; da.slot_w = n.slot_w; da.n_local = (float)n_rows; da.beta_pow = h->beta_pow; da.tail_off = h->P_pad;
+    return da;
+}
+
+// the [256,256] pair: weight gradients + slab / slot sums + partial sums of squares in ONE launch (ppo_dw2.hpp): no grad_reduce_kernel
+static int train_pair(ppo_handle* h, TrainArgs ta, float* loss_row, bool peer_tiles, AdamParts& parts) {
+    const int n_pad = ru(ta.n, DW2_CH);
+    ta.xcd_map = 1;
+    if (enqueue_train_fb(h, ta, n_pad)) return -1;
+    const Dw2Args da = dw2_args(h, ta.n, n_pad);
+    {
+        ProfScope ps(h, PK_DW);
+        ++h->kv[KV_DW2];
+        launch_dw2(h, da, peer_tiles);
+        HIP_OK(h, hipGetLastError());
     }
-    if (use_dw2) {
-        // weight gradients + slab / slot sums + partial sums of squares in ONE launch (ppo_dw2.hpp): no grad_reduce_kernel
-        {
-            ProfScope ps(h, PK_DW);
-            ++h->kv[KV_DW2];
-            if (n.Kp0 == 32 && n.Ap == 32) launch_dw2<32, 32>(h, da);
-            else if (n.Kp0 == 64 && n.Ap == 32) launch_dw2<64, 32>(h, da);
-            else if (n.Kp0 == 32 && n.Ap == 64) launch_dw2<32, 64>(h, da);
-            else launch_dw2<64, 64>(h, da);
-            HIP_OK(h, hipGetLastError());
-        }
-        if (h->comm) { if (enqueue_grad_allreduce(h)) return -1; return enqueue_adam(h, loss_row); }
-        return enqueue_adam(h, loss_row, DW2_TILES + DW2_GRID, h->dw2_parts);
-    }
+    if (peer_tiles) return enqueue_adam(h, loss_row, 0, nullptr, 2) ? -1 : TRAIN_DONE;
+    parts = AdamParts{DW2_TILES + DW2_GRID, h->dw2_parts};
+    return 0;
+}
+
+static int train_generic(ppo_handle* h, TrainArgs ta) {
+    const int n_pad = ru(ta.n, ROWS_PER_BLOCK);
+    ta.xcd_map = 0;
+    if (enqueue_train_fb(h, ta, n_pad)) return -1;
     const int split = pick_split(h, n_pad);
     {
         ProfScope ps(h, PK_DW);
         DwArgs da{h->dw_tiles, n_pad, split, h->slabs, (size_t)h->P_pad, nullptr};
-#ifdef PPO_STAMPS
-        da.stamps = g_stamps + 4096 * 16;
-#endif
+        SET_STAMPS(da.stamps, true, 4096 * 16);
         const size_t lds = (h->dw_has_big ? 4 * (64 * 64 + 1024) : 4 * 32 * 32) * sizeof(float);     // 4 waves x (tile + strips)
         const int rows_per_wave = n_pad / split / 4;
         ++h->kv[KV_DW]; ++h->kv[KV_GRAD_REDUCE];
@@ -1539,17 +1510,42 @@ int enqueue_train(ppo_handle* h, TrainArgs ta, float* loss_row, bool defer = fal
         else hipLaunchKernelGGL(weight_grad_kernel<1>, dim3(h->n_dw_tiles * split), dim3(BLOCK_THREADS), lds, h->stream, da);
         HIP_OK(h, hipGetLastError());
     }
-    {
-        ProfScope ps(h, PK_REDUCE);
-        ReduceArgs ra{};
-        ra.src = h->grad_src; ra.n_blocks = h->n_blocks; ra.slabs = h->slabs; ra.slab_stride = (size_t)h->P_pad; ra.nsplit = split;
-        ra.slots[0] = h->slots[0]; ra.slots[1] = h->slots[1]; ra.n_rowblocks = n_rb; ra.slot_w = n.slot_w; ra.slot_loss = n.slot_loss;
-        ra.grad = h->grad; ra.sumsq = h->sumsq; ra.n_local = (float)ta.n; ra.beta_pow = h->beta_pow;
-        hipLaunchKernelGGL(grad_reduce_kernel, dim3(h->n_blocks + 1), dim3(256), 0, h->stream, ra);
-        HIP_OK(h, hipGetLastError());
+    ProfScope ps(h, PK_REDUCE);
+    ReduceArgs ra = reduce_args(h, ta, n_pad / ROWS_PER_BLOCK);
+    ra.nsplit = split;
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3(h->n_blocks + 1), dim3(256), 0, h->stream, ra);
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
+// the per-minibatch launch sequence: fwd+loss+bwd -> weight grads -> reduce [-> all-reduce] -> clip+Adam
+// defer (narrow reference shape, inside ppo_update only): leave this step's clip + Adam to the next train kernel's prologue
+// (flush_pending_adam after the last step)
+int enqueue_train(ppo_handle* h, TrainArgs ta, float* loss_row, bool defer = false) {
+    const NetDev& n = h->net;
+    ta.theta = h->theta; ta.thetaT = h->thetaT; ta.par = h->par; ta.hyper = h->hyper;
+    ta.x0g = h->x0g; ta.dmug = h->dmug;
+    SET_STAMPS(ta.stamps, true, 0);
+    for (int t = 0; t < 2; ++t) {
+        ta.slots[t] = h->slots[t];
+        for (int l = 0; l < n.L; ++l) { ta.hg[t][l] = h->hg[t][l]; ta.dyg[t][l] = h->dyg[t][l]; }
     }
-    if (h->comm && enqueue_grad_allreduce(h)) return -1;         // also with a 1-rank communicator: same code path as N ranks
-    return enqueue_adam(h, loss_row);
+    AdamParts parts;
+    int rc = -1;
+    const TrainForm form = train_form(h, ta.n);
+    switch (form) {
+        case TF_NARROW: rc = train_narrow(h, ta, parts); break;
+        case TF_BF16_BUCKETED:
+        case TF_BF16: rc = train_bf16(h, ta, loss_row, form == TF_BF16_BUCKETED, parts); break;
+        case TF_PAIR_PEER:
+        case TF_PAIR: rc = train_pair(h, ta, loss_row, form == TF_PAIR_PEER, parts); break;
+        case TF_GENERIC: rc = train_generic(h, ta); break;
+    }
+    if (rc) return rc == TRAIN_DONE ? 0 : -1;
+    // the shared tail.  Data parallel (also with a 1-rank communicator: same code path as N ranks): the exchange recomputes one sum of squares per 256-element chunk
+    if (h->comm) { if (enqueue_grad_allreduce(h)) return -1; parts = AdamParts{}; }
+    if (defer && h->nw_lazy) { h->nw_pending = true; h->nw_pending_loss = loss_row; h->nw_pending_parts = parts.n ? parts.n : h->n_blocks; return 0; }
+    return enqueue_adam(h, loss_row, parts.n, parts.from);
 }
 
 // the clip + Adam of the last deferred step, as a launch of its own (also brings the weights home to set 0 and refreshes the
@@ -1744,7 +1740,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     { const char* e = getenv("PPO_HIP_NO_T8"); const NetDev& nn = h->net;
       // any observation / action width up to 64 (tiles of 32 or 64 columns) in front of hidden [256,256]
       h->t8 = !(e && e[0] == '1') && h->dist == PPO_ACT_GAUSSIAN && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64;
-      if ((h->t8 || h->dw2) && !(set_lds_pair<32, 32>() && set_lds_pair<64, 32>() && set_lds_pair<32, 64>() && set_lds_pair<64, 64>())) {
+      if ((h->t8 || h->dw2) && !set_lds_pair(h)) {
           fail(h, "hipFuncSetAttribute failed for train8_kernel / weight_grad_assemble_kernel"); return bail(0); } }
     if (h->dw2) {
         // slot jobs: every element the train kernel leaves as per-row-block partial sums (bias / logstd / value-head gradients), then the loss sums
@@ -1805,8 +1801,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
             // the deferred / resident forms compute TF's quotient with the correctly rounded square root and division by DEFAULT since round 6 (no deviation from the
             // reference's arithmetic; 6 - 9 % of this shape's train step); PPO_HIP_ADAM_FAST=1 (below) opts into the hardware's 1-ulp reciprocal / square root
             h->adam_exact = true; h->adam_fast = false;
-            const char* ne = getenv("PPO_HIP_NO_NARROW_EPOCH");
-            h->nw_epoch = !(ne && ne[0] == '1') && prop.multiProcessorCount >= 2 * 2 * NW_EPOCH_MAX_G;
+            h->nw_epoch = use_narrow_epoch() && prop.multiProcessorCount >= 2 * 2 * NW_EPOCH_MAX_G;
             if (h->nw_epoch && dev_alloc(h, &h->nw_epoch_words, NW_EPOCH_WORDS)) return bail(0);
             { const char* nx = getenv("PPO_HIP_NO_NARROW_EPOCH_XL"); h->nw_epoch_xl = h->nw_epoch && !(nx && nx[0] == '1') && prop.multiProcessorCount >= 64; }
         }
@@ -2124,7 +2119,7 @@ int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float*
     ta.inv_n = 1.0f / (float)((int64_t)n * h->world);
     if (h->dw2 && zero_words(h, h->dw2_counters, DW2_TILES)) return -1;
     if (enqueue_train(h, ta, h->st_loss)) return -1;
-    h->bf.grad_lazy = h->bf.lazy_last;
+    h->bf.lazy.ran = h->bf.lazy.enqueued;
     HIP_OK(h, hipMemcpyAsync(losses, h->st_loss, 5 * fb, hipMemcpyDeviceToHost, h->stream));
     HIP_OK(h, hipStreamSynchronize(h->stream));
     prof_collect(h);
@@ -2313,10 +2308,7 @@ static int enqueue_norm_batch(ppo_handle* h, const float* obs_dev, int rows, con
         a.xch = h->stats_xch;
         if (!a.use_peer) HIP_OK(h, hipMemsetAsync(h->stats_xch, 0, xw * h->world * sizeof(float), h->stream));
     }
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    a.stamps = g_stamps + 4096 * 32;
-#endif
+    SET_STAMPS(a.stamps, true, 4096 * 32);
     { ProfScope ps(h, PK_STATS);
       hipLaunchKernelGGL(norm_batch_kernel, dim3(a.g_obs + a.g_rew), dim3(NB_THREADS), 0, h->stream, a);
       HIP_OK(h, hipGetLastError()); }
@@ -2948,10 +2940,7 @@ static int collect_persistent(ppo_handle* h, DevForm form, const CollectIn& in) 
     NwRolloutArgs q = nw_args<NwRolloutArgs>(h);
     q.noise = in.noise;
     q.E = h->E; q.T = h->T; q.seed = in.seed; q.step0 = in.step0; q.env0 = in.env0;
-#ifdef PPO_STAMPS
-    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-    q.stamps = g_stamps;
-#endif
+    SET_STAMPS(q.stamps, true, 0);
     { ProfScope ps(h, PK_STEP);
       launch_rollout_kernel(h, q, form == DF_ROLLOUT1);
       HIP_OK(h, hipGetLastError()); }
@@ -3185,127 +3174,143 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
     return tab;
 }
 
+// literal data-parallel sampling is in effect: one permutation over the rows of all ranks (ppo_dist_global_shuffle)
+static bool global_shuffle_on(const ppo_handle* h) { return h->global_shuffle && h->comm && h->world > 1; }
+
+// the gather of an epoch into minibatch order (M rows per minibatch); under the global shuffle out of the all-gathered rows
+static GatherArgs gather_args(const ppo_handle* h, int M) {
+    GatherArgs ga{h->d_gidx, h->d_advstats, h->E * h->T, M, h->net.O, h->Aw, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
+                  h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp};
+    if (global_shuffle_on(h)) { ga.obs = h->gs_obs; ga.act = h->gs_act; ga.ret = h->gs_ret; ga.val = h->gs_val; ga.nlp = h->gs_nlp; }
+    if (h->masking) { ga.mask = h->ro_mask; ga.mb_mask = h->mb_mask; ga.Am = h->net.A; }      // (read by the <true> instantiations only)
+    return ga;
+}
+
+// every minibatch of an epoch in ONE resident launch (narrow_epoch_kernel), and its XCD-local form: the terms its two users share.  ensure_update_ws sizes the
+// XCD-local form's partial vectors on these alone; enqueue_update adds what the launch itself needs (the deferred Adam, the switch, the capacities) -- the two
+// sites never tested the same thing and are not merged further
+static bool narrow_epoch_shape(const ppo_handle* h, int M) { return h->narrow && h->nw_epoch && !h->comm && (M + NW_ROWS - 1) / NW_ROWS <= NW_EPOCH_MAX_G; }
+static bool narrow_epoch_xl_shape(const ppo_handle* h, int M) { return narrow_epoch_shape(h, M) && h->nw_epoch_xl; }
+
+// index map and advantage statistics of epoch ep; *merged: the same launch gathered the epoch as well
+static int enqueue_epoch_index(ppo_handle* h, int ep, int nmb, bool explicit_perms, bool* merged) {
+    const int B = h->E * h->T, M = B / nmb;
+    const bool gs = global_shuffle_on(h);
+    *merged = false;
+    if (explicit_perms) {
+        const int Bp = gs ? B * h->world : B;
+        hipLaunchKernelGGL(invert_perm_kernel, dim3((Bp + 255) / 256), dim3(256), 0, h->stream, h->d_perms + (size_t)ep * Bp, h->d_inv, Bp);
+        HIP_OK(h, hipGetLastError());
+    }
+    ProfScope ps(h, PK_EPOCH);
+    uint32_t bits = 1;
+    while ((1u << bits) < (uint32_t)B * (gs ? (uint32_t)h->world : 1u)) ++bits;
+    EpochArgs ea{};
+    ea.inv_perm = explicit_perms ? h->d_inv : nullptr; ea.keys = h->d_keys + 2 * ep; ea.bits = bits;
+    ea.B = B; ea.M = M; ea.T = h->T; ea.E = h->E; ea.returns = h->ro_ret; ea.values = h->ro_val; ea.gidx = h->d_gidx; ea.stats = h->d_advstats;
+    ea.xch = h->adv_xch; ea.xch2 = ru(nmb, 4); ea.n_global = (float)((int64_t)M * h->world);
+    if (h->comm && !gs) {
+        // the advantage statistics are over the whole (all-rank) minibatch (ppo2.hpp:401-406)
+        for (int phase = 1; phase <= 3; ++phase) {
+            ea.phase = phase;
+            hipLaunchKernelGGL(epoch_prepare_kernel, dim3(nmb), dim3(EP_THREADS), 0, h->stream, ea);
+            HIP_OK(h, hipGetLastError());
+            if (phase == 1 && enqueue_allreduce(h, h->adv_xch, (size_t)nmb)) return -1;
+            if (phase == 2 && enqueue_allreduce(h, h->adv_xch + ru(nmb, 4), (size_t)nmb)) return -1;
+        }
+        return 0;
+    }
+    ea.phase = 0;
+    if (gs) {
+        // ONE permutation over the rows of all ranks; the gathered returns / values are local, so the statistics of the whole
+        // minibatch need no exchange
+        ea.world = h->world; ea.rank = h->rank; ea.returns = h->gs_ret; ea.values = h->gs_val;
+    } else if (!h->bf.on && M <= EPG_MAX_M) {
+        // index map, advantage statistics AND the gather of the epoch in one launch (fp32 paths; the bf16 path stages its epoch separately)
+        GatherArgs ga = gather_args(h, M);
+        SET_STAMPS(ga.stamps, true, 4096 * 32);
+        if (h->masking) hipLaunchKernelGGL(epoch_prepare_gather_kernel<true>, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
+        else hipLaunchKernelGGL(epoch_prepare_gather_kernel<false>, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
+        HIP_OK(h, hipGetLastError());
+        *merged = true;
+        return 0;
+    }
+    hipLaunchKernelGGL(epoch_prepare_kernel, dim3(nmb), dim3(EP_THREADS), 0, h->stream, ea);
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
+// the gather of the epoch as a launch of its own, and the bf16 path's epoch staging
+static int enqueue_epoch_gather(ppo_handle* h, int nmb) {
+    ProfScope ps(h, PK_EPOCH);
+    const int B = h->E * h->T, M = B / nmb;
+    const GatherArgs ga = gather_args(h, M);
+    // (epoch_gather4_kernel copies no masks: a masking handle is categorical, its action rows are one float, so it never qualifies -- and must not)
+    const bool wide4 = h->net.O % 4 == 0 && h->Aw % 4 == 0 && !h->masking;
+    // bf16 path: the epoch's observations become bf16 once; a minibatch is then a row slice.  With 16-byte rows the gather writes them itself
+    const bool fuse_stage = wide4 && h->bf.on && M % GB_PAD == 0 && h->bf.xe_rows >= B && h->net.Kp0 % 4 == 0 && !global_shuffle_on(h);
+    if (wide4) {
+        Gather4Args g4{ga, fuse_stage ? h->bf.xe : nullptr, h->net.Kp0};
+        hipLaunchKernelGGL(epoch_gather4_kernel, dim3((B + 15) / 16), dim3(256), 0, h->stream, g4);
+    }
+    else if (h->masking) hipLaunchKernelGGL(epoch_gather_kernel<true>, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
+    else hipLaunchKernelGGL(epoch_gather_kernel<false>, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
+    HIP_OK(h, hipGetLastError());
+    if (!h->bf.on) return 0;
+    ppo_handle::Bf16& bb = h->bf;
+    bb.epoch_staged = fuse_stage || (M % GB_PAD == 0 && bb.xe_rows >= B);
+    if (bb.epoch_staged && !fuse_stage) {
+        StageArgsB sa{h->mb_obs, B, h->net.O, h->net.Kp0, B, no_norm(), nullptr, bb.xe};
+        const size_t cnt = (size_t)B * h->net.Kp0;
+        if (h->net.O % 4 == 0 && h->net.Kp0 % 4 == 0) hipLaunchKernelGGL(bf16_stage4_kernel, dim3(bf16_stage4_grid(h->net.Kp0, cnt / 4)), dim3(256), 0, h->stream, sa);
+        else hipLaunchKernelGGL(bf16_stage_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, sa);
+        HIP_OK(h, hipGetLastError());
+    }
+    return 0;
+}
+
+static int enqueue_epoch_prepare(ppo_handle* h, int ep, int nmb, bool explicit_perms) {
+    bool merged = false;
+    if (enqueue_epoch_index(h, ep, nmb, explicit_perms, &merged)) return -1;
+    return merged ? 0 : enqueue_epoch_gather(h, nmb);
+}
+
+// every minibatch of epoch ep in ONE resident launch (ppo_narrow.hpp, narrow_epoch_kernel)
+static int enqueue_narrow_epoch(ppo_handle* h, int ep, int nmb, bool xl) {
+    ProfScope ps(h, PK_TRAIN_FB);
+    const NetDev& n = h->net;
+    const int M = h->E * h->T / nmb, egroups = (M + NW_ROWS - 1) / NW_ROWS;
+    NwEpochArgs ea{h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp, M, nmb, 1.0f / (float)M, h->nw_img, xl ? h->nw_epoch_partials : h->nw_partials, h->nw_stride,
+                   h->theta, h->adam_m, h->adam_v, h->grad, h->hyper, h->beta_pow, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm,
+                   h->d_loss_rows + (size_t)ep * nmb * 5, h->norm_out, h->nw_epoch_words, h->P_pad / 64, nullptr};
+    SET_STAMPS(ea.stamps, true, 0);
+    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+    ++h->kv[KV_NARROW_EPOCH];
+    const dim3 grid = xl ? dim3(16 * egroups) : dim3(egroups, 2);
+#define EPOCH_LAUNCH(K, X, EX) hipLaunchKernelGGL((narrow_epoch_kernel<K, X, EX>), grid, dim3(NW_THREADS), lds, h->stream, n, h->nw, ea)
+#define EPOCH_KP0(X, EX) do { if (n.Kp0 == 32) EPOCH_LAUNCH(32, X, EX); else EPOCH_LAUNCH(64, X, EX); } while (0)
+    if (xl) { if (h->adam_exact) EPOCH_KP0(true, true); else EPOCH_KP0(true, false); }
+    else { if (h->adam_exact) EPOCH_KP0(false, true); else EPOCH_KP0(false, false); }
+#undef EPOCH_KP0
+#undef EPOCH_LAUNCH
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
 static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perms) {
     const int B = h->E * h->T, M = B / nmb;
     // the per-tile arrival counters of weight_grad_assemble_kernel are reset by their last arriver; an update that was cut short
     // (a failed launch) must not leave them half-counted for the next one: zeroed here, a memset node of the replayed graph
     if (h->dw2 && zero_words(h, h->dw2_counters, DW2_TILES)) return -1;
     h->nw_pending = false; h->nw_cur = 0;                      // outside an update the weights always live in set 0
-    uint32_t bits = 1;
-    while ((1u << bits) < (uint32_t)B) ++bits;
+    // the resident epoch launch: beside the shared terms, the deferred Adam it continues, the switch, and the partial vectors' capacities
+    const int egroups = (M + NW_ROWS - 1) / NW_ROWS;
+    const bool resident = narrow_epoch_shape(h, M) && h->nw_lazy && egroups <= h->nw_groups_cap && use_narrow_epoch();
+    const bool xl = narrow_epoch_xl_shape(h, M) && h->nw_epoch_partials && (size_t)nmb * 2 * egroups * h->nw_stride <= h->nw_epoch_cap;
     for (int ep = 0; ep < epochs; ++ep) {
-        if (explicit_perms) {
-            const int Bp = (h->global_shuffle && h->comm && h->world > 1) ? B * h->world : B;
-            hipLaunchKernelGGL(invert_perm_kernel, dim3((Bp + 255) / 256), dim3(256), 0, h->stream, h->d_perms + (size_t)ep * Bp, h->d_inv, Bp);
-            HIP_OK(h, hipGetLastError());
-        }
-        bool merged = false;
-        {
-            ProfScope ps(h, PK_EPOCH);
-            EpochArgs ea{};
-            ea.inv_perm = explicit_perms ? h->d_inv : nullptr; ea.keys = h->d_keys + 2 * ep; ea.bits = bits;
-            ea.B = B; ea.M = M; ea.T = h->T; ea.E = h->E; ea.returns = h->ro_ret; ea.values = h->ro_val; ea.gidx = h->d_gidx; ea.stats = h->d_advstats;
-            ea.xch = h->adv_xch; ea.xch2 = ru(nmb, 4); ea.n_global = (float)((int64_t)M * h->world);
-            const bool gs = h->global_shuffle && h->comm && h->world > 1;
-            if (gs) {
-                // ONE permutation over the rows of all ranks; the gathered returns / values are local, so the statistics of the whole
-                // minibatch need no exchange
-                uint32_t gb = 1;
-                while ((1u << gb) < (uint32_t)B * (uint32_t)h->world) ++gb;
-                ea.bits = gb; ea.world = h->world; ea.rank = h->rank; ea.returns = h->gs_ret; ea.values = h->gs_val; ea.phase = 0;
-                hipLaunchKernelGGL(epoch_prepare_kernel, dim3(nmb), dim3(EP_THREADS), 0, h->stream, ea);
-                HIP_OK(h, hipGetLastError());
-            } else if (!h->comm) {
-                ea.phase = 0;
-                if (!h->bf.on && M <= EPG_MAX_M) {
-                    // index map, advantage statistics AND the gather of the epoch in one launch (fp32 paths; the bf16 path stages its epoch separately)
-                    GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->Aw, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
-                                  h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp};
-#ifdef PPO_STAMPS
-                    if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-                    ga.stamps = g_stamps + 4096 * 32;
-#endif
-                    if (h->masking) {
-                        ga.mask = h->ro_mask; ga.mb_mask = h->mb_mask; ga.Am = h->net.A;
-                        hipLaunchKernelGGL(epoch_prepare_gather_kernel<true>, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
-                    } else
-                    hipLaunchKernelGGL(epoch_prepare_gather_kernel<false>, dim3(nmb * EPG_SPLIT), dim3(EP_THREADS), 0, h->stream, ea, ga);
-                    HIP_OK(h, hipGetLastError());
-                    merged = true;
-                } else {
-                    hipLaunchKernelGGL(epoch_prepare_kernel, dim3(nmb), dim3(EP_THREADS), 0, h->stream, ea);
-                    HIP_OK(h, hipGetLastError());
-                }
-            } else {
-                // the advantage statistics are over the whole (all-rank) minibatch (ppo2.hpp:401-406)
-                for (int phase = 1; phase <= 3; ++phase) {
-                    ea.phase = phase;
-                    hipLaunchKernelGGL(epoch_prepare_kernel, dim3(nmb), dim3(EP_THREADS), 0, h->stream, ea);
-                    HIP_OK(h, hipGetLastError());
-                    if (phase == 1 && enqueue_allreduce(h, h->adv_xch, (size_t)nmb)) return -1;
-                    if (phase == 2 && enqueue_allreduce(h, h->adv_xch + ru(nmb, 4), (size_t)nmb)) return -1;
-                }
-            }
-        }
-        if (!merged) {
-            ProfScope ps(h, PK_EPOCH);
-            GatherArgs ga{h->d_gidx, h->d_advstats, B, M, h->net.O, h->Aw, h->ro_obs, h->ro_act, h->ro_ret, h->ro_val, h->ro_nlp,
-                          h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp};
-            if (h->global_shuffle && h->comm && h->world > 1) { ga.obs = h->gs_obs; ga.act = h->gs_act; ga.ret = h->gs_ret; ga.val = h->gs_val; ga.nlp = h->gs_nlp; }
-            // (epoch_gather4_kernel copies no masks: a masking handle is categorical, its action rows are one float, so it never qualifies -- and must not)
-            const bool wide4 = h->net.O % 4 == 0 && h->Aw % 4 == 0 && !h->masking;
-            // bf16 path: the epoch's observations become bf16 once; a minibatch is then a row slice.  With 16-byte rows the gather writes them itself
-            const bool fuse_stage = wide4 && h->bf.on && M % GB_PAD == 0 && h->bf.xe_rows >= B && h->net.Kp0 % 4 == 0 && !(h->global_shuffle && h->comm && h->world > 1);
-            if (wide4) {
-                Gather4Args g4{ga, fuse_stage ? h->bf.xe : nullptr, h->net.Kp0};
-                hipLaunchKernelGGL(epoch_gather4_kernel, dim3((B + 15) / 16), dim3(256), 0, h->stream, g4);
-            }
-            else if (h->masking) {
-                ga.mask = h->ro_mask; ga.mb_mask = h->mb_mask; ga.Am = h->net.A;
-                hipLaunchKernelGGL(epoch_gather_kernel<true>, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
-            }
-            else hipLaunchKernelGGL(epoch_gather_kernel<false>, dim3((B + 15) / 16), dim3(256), 0, h->stream, ga);
-            HIP_OK(h, hipGetLastError());
-            if (h->bf.on && fuse_stage) h->bf.epoch_staged = true;
-            else if (h->bf.on) {
-                ppo_handle::Bf16& bb = h->bf;
-                bb.epoch_staged = M % GB_PAD == 0 && bb.xe_rows >= B;
-                if (bb.epoch_staged) {
-                    StageArgsB sa{h->mb_obs, B, h->net.O, h->net.Kp0, B, no_norm(), nullptr, bb.xe};
-                    const size_t cnt = (size_t)B * h->net.Kp0;
-                    if (h->net.O % 4 == 0 && h->net.Kp0 % 4 == 0) hipLaunchKernelGGL(bf16_stage4_kernel, dim3(bf16_stage4_grid(h->net.Kp0, cnt / 4)), dim3(256), 0, h->stream, sa);
-                    else hipLaunchKernelGGL(bf16_stage_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, sa);
-                    HIP_OK(h, hipGetLastError());
-                }
-            }
-        }
-        const int egroups = (M + NW_ROWS - 1) / NW_ROWS;
-        const char* ne = getenv("PPO_HIP_NO_NARROW_EPOCH");     // (read when the update is captured: the test compares both forms)
-        if (h->narrow && h->nw_lazy && h->nw_epoch && !h->comm && egroups <= NW_EPOCH_MAX_G && egroups <= h->nw_groups_cap && !(ne && ne[0] == '1')) {
-            // every minibatch of the epoch in ONE resident launch (ppo_narrow.hpp, narrow_epoch_kernel)
-            ProfScope ps(h, PK_TRAIN_FB);
-            const NetDev& n = h->net;
-            const bool xl = h->nw_epoch_xl && h->nw_epoch_partials && (size_t)nmb * 2 * egroups * h->nw_stride <= h->nw_epoch_cap;
-            NwEpochArgs ea{h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp, M, nmb, 1.0f / (float)M, h->nw_img, xl ? h->nw_epoch_partials : h->nw_partials, h->nw_stride,
-                           h->theta, h->adam_m, h->adam_v, h->grad, h->hyper, h->beta_pow, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm,
-                           h->d_loss_rows + (size_t)ep * nmb * 5, h->norm_out, h->nw_epoch_words, h->P_pad / 64, nullptr};
-#ifdef PPO_STAMPS
-            if (!g_stamps) (void)hipMalloc((void**)&g_stamps, 4096 * 48 * sizeof(unsigned long long));
-            ea.stamps = g_stamps;
-#endif
-            const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-            ++h->kv[KV_NARROW_EPOCH];
-#define EPOCH_LAUNCH(K, X, EX, GRID) hipLaunchKernelGGL((narrow_epoch_kernel<K, X, EX>), GRID, dim3(NW_THREADS), lds, h->stream, n, h->nw, ea)
-            const dim3 gx(16 * egroups), gw(egroups, 2);
-            if (xl) {
-                if (h->adam_exact) { if (n.Kp0 == 32) EPOCH_LAUNCH(32, true, true, gx); else EPOCH_LAUNCH(64, true, true, gx); }
-                else if (n.Kp0 == 32) EPOCH_LAUNCH(32, true, false, gx); else EPOCH_LAUNCH(64, true, false, gx);
-            } else {
-                if (h->adam_exact) { if (n.Kp0 == 32) EPOCH_LAUNCH(32, false, true, gw); else EPOCH_LAUNCH(64, false, true, gw); }
-                else if (n.Kp0 == 32) EPOCH_LAUNCH(32, false, false, gw); else EPOCH_LAUNCH(64, false, false, gw);
-            }
-#undef EPOCH_LAUNCH
-            HIP_OK(h, hipGetLastError());
+        if (enqueue_epoch_prepare(h, ep, nmb, explicit_perms)) return -1;
+        if (resident) {
+            if (enqueue_narrow_epoch(h, ep, nmb, xl)) return -1;
             continue;
         }
         for (int k = 0; k < nmb; ++k) {
@@ -3324,20 +3329,9 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
     return 0;
 }
 
-int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t nmb, const int32_t* perms, uint64_t seed, float* loss_rows,
-               float mean_losses[5]) {
-    ENTER_Q(h);
-    if (!h->E) return fail(h, "ppo_update: no rollout allocated (ppo_rollout_alloc + collect first)");
-    const int B = h->E * h->T;
-    if (epochs < 1 || nmb < 1 || B % nmb) return fail(h, "ppo_update: n_batch %d not divisible by nminibatches %d", B, nmb);
-    const int M = B / nmb;
-    if (ensure_train_ws(h, M)) return -1;
-    const int steps = epochs * nmb;
-    const bool gs = h->global_shuffle && h->comm && h->world > 1;
-    if (h->masking && h->global_shuffle)
-        return fail(h, "ppo_update: ppo_dist_global_shuffle(1) together with action masking is not supported (the masks are not all-gathered); switch one of them off");
-    const int Bp = gs ? B * h->world : B;                      // rows one permutation covers
-    if (gs && Bp > h->gs_rows) {
+// the update's buffers for permutations over Bp rows, minibatches of M rows and `steps` train steps; growing one drops the captured graph
+static int ensure_update_ws(ppo_handle* h, int Bp, int M, int steps, int nmb) {
+    if (global_shuffle_on(h) && Bp > h->gs_rows) {
         HIP_OK(h, hipStreamSynchronize(h->stream));
         drop_graph(h);
         if (dev_alloc(h, &h->gs_obs, (size_t)Bp * h->net.O) || dev_alloc(h, &h->gs_act, (size_t)Bp * h->Aw) || dev_alloc(h, &h->gs_ret, Bp) ||
@@ -3351,7 +3345,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
         if (dev_alloc(h, &h->mb_obs, (size_t)cr * h->net.O) || dev_alloc(h, &h->mb_act, (size_t)cr * h->Aw) || dev_alloc(h, &h->mb_adv, cr) ||
             dev_alloc(h, &h->mb_ret, cr) || dev_alloc(h, &h->mb_val, cr) || dev_alloc(h, &h->mb_nlp, cr)) return -1;
         if (h->masking && dev_alloc(h, &h->mb_mask, (size_t)cr * h->net.A)) return -1;
-        if (h->d_perms) { (void)hipFree(h->d_perms); h->d_perms = nullptr; h->upd_cap_epochs = 0; }      // sized on demand below
+        if (h->d_perms) { (void)hipFree(h->d_perms); h->d_perms = nullptr; h->upd_cap_epochs = 0; }      // sized on demand (upload_perms)
         if (dev_alloc(h, &h->d_inv, cr) || dev_alloc(h, &h->d_gidx, cr) ||
             dev_alloc(h, &h->d_advstats, (size_t)2 * cs) || dev_alloc(h, &h->d_keys, (size_t)2 * cs) || dev_alloc(h, &h->d_loss_rows, (size_t)5 * cs) ||
             dev_alloc(h, &h->d_loss_mean, 8) || dev_alloc(h, &h->adv_xch, (size_t)2 * ru(cs, 4)))
@@ -3362,7 +3356,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
             h->bf.xe_rows = cr;
         }
     }
-    if (h->narrow && h->nw_epoch && h->nw_epoch_xl && !h->comm && (M + NW_ROWS - 1) / NW_ROWS <= NW_EPOCH_MAX_G) {
+    if (narrow_epoch_xl_shape(h, M)) {
         // the XCD-local epoch kernel's partial gradient vectors: one set per minibatch of an epoch (zero-filled: padding elements are never written and must read 0)
         const size_t need = (size_t)nmb * 2 * ((M + NW_ROWS - 1) / NW_ROWS) * h->nw_stride;
         if (need > h->nw_epoch_cap && need <= ((size_t)256 << 20) / sizeof(float)) {      // (thousands of tiny minibatches: the write-through form's two sets instead)
@@ -3372,81 +3366,114 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
             h->nw_epoch_cap = need;
         }
     }
-    if (set_hyper(h, lr, cliprange)) return -1;
-    const bool explicit_perms = perms != nullptr;
-    if (explicit_perms) {
-        // every epoch's row must be a permutation of [0, Bp): invert_perm_kernel scatters inv[perm[i]] = i
-        std::vector<unsigned char> seen((size_t)Bp);
-        for (int ep = 0; ep < epochs; ++ep) {
-            std::fill(seen.begin(), seen.end(), 0);
-            const int32_t* pe = perms + (size_t)ep * Bp;
-            for (int i = 0; i < Bp; ++i) {
-                const int32_t d = pe[i];
-                if (d < 0 || d >= Bp || seen[(size_t)d]) return fail(h, "ppo_update: perms[%d] is not a permutation of [0,%d) (entry %d = %d)", ep, Bp, i, (int)d);
-                seen[(size_t)d] = 1;
-            }
-        }
-        // [epochs, Bp] ints, allocated only when explicit permutations are used (on-device shuffles need none)
-        if (!h->d_perms || epochs > h->upd_cap_epochs) {
-            HIP_OK(h, hipStreamSynchronize(h->stream));
-            drop_graph(h);
-            if (dev_alloc(h, &h->d_perms, (size_t)epochs * h->upd_cap_rows)) return -1;
-            h->upd_cap_epochs = epochs;
-        }
-        HIP_OK(h, hipMemcpyAsync(h->d_perms, perms, (size_t)epochs * Bp * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    }
-    if (gs) {
-        // the rollout rows of all ranks, rank-major [world][T][E][.], once per update (10 MB per rank at config 3), outside the graph
-        if (!h->rccl.AllGather) return fail(h, "ppo_update: the collective library has no ncclAllGather (needed by ppo_dist_global_shuffle)");
-        const size_t rows = (size_t)B;
-        struct { const float* src; float* dst; size_t w; } gl[5] = {{h->ro_obs, h->gs_obs, (size_t)h->net.O}, {h->ro_act, h->gs_act, (size_t)h->Aw},
-                                                                    {h->ro_ret, h->gs_ret, 1}, {h->ro_val, h->gs_val, 1}, {h->ro_nlp, h->gs_nlp, 1}};
-        for (auto& x : gl) {
-            const int rc = h->rccl.AllGather(x.src, x.dst, rows * x.w, /*ncclFloat32*/ 7, h->comm, h->stream);
-            if (rc != 0) return fail(h, "ncclAllGather failed: %s", h->rccl.GetErrorString ? h->rccl.GetErrorString(rc) : "?");
+    return 0;
+}
+
+// every epoch's row must be a permutation of [0, Bp): invert_perm_kernel scatters inv[perm[i]] = i
+static int upload_perms(ppo_handle* h, const int32_t* perms, int epochs, int Bp) {
+    std::vector<unsigned char> seen((size_t)Bp);
+    for (int ep = 0; ep < epochs; ++ep) {
+        std::fill(seen.begin(), seen.end(), 0);
+        const int32_t* pe = perms + (size_t)ep * Bp;
+        for (int i = 0; i < Bp; ++i) {
+            const int32_t d = pe[i];
+            if (d < 0 || d >= Bp || seen[(size_t)d]) return fail(h, "ppo_update: perms[%d] is not a permutation of [0,%d) (entry %d = %d)", ep, Bp, i, (int)d);
+            seen[(size_t)d] = 1;
         }
     }
-    std::vector<uint32_t> keys(2 * (size_t)epochs);
+    // [epochs, Bp] ints, allocated only when explicit permutations are used (on-device shuffles need none)
+    if (!h->d_perms || epochs > h->upd_cap_epochs) {
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        drop_graph(h);
+        if (dev_alloc(h, &h->d_perms, (size_t)epochs * h->upd_cap_rows)) return -1;
+        h->upd_cap_epochs = epochs;
+    }
+    HIP_OK(h, hipMemcpyAsync(h->d_perms, perms, (size_t)epochs * Bp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// global shuffle: the rollout rows of all ranks, rank-major [world][T][E][.], once per update (10 MB per rank at config 3), outside the graph
+static int allgather_rollout(ppo_handle* h) {
+    if (!h->rccl.AllGather) return fail(h, "ppo_update: the collective library has no ncclAllGather (needed by ppo_dist_global_shuffle)");
+    const size_t rows = (size_t)h->E * h->T;
+    struct { const float* src; float* dst; size_t w; } gl[5] = {{h->ro_obs, h->gs_obs, (size_t)h->net.O}, {h->ro_act, h->gs_act, (size_t)h->Aw},
+                                                                {h->ro_ret, h->gs_ret, 1}, {h->ro_val, h->gs_val, 1}, {h->ro_nlp, h->gs_nlp, 1}};
+    for (auto& x : gl) {
+        const int rc = h->rccl.AllGather(x.src, x.dst, rows * x.w, /*ncclFloat32*/ 7, h->comm, h->stream);
+        if (rc != 0) return fail(h, "ncclAllGather failed: %s", h->rccl.GetErrorString ? h->rccl.GetErrorString(rc) : "?");
+    }
+    return 0;
+}
+
+// the epochs' shuffle keys (splitmix64 of the seed); `keys` is the caller's: the copy reads it until the stream is synchronised
+static int upload_epoch_keys(ppo_handle* h, int epochs, uint64_t seed, std::vector<uint32_t>& keys) {
+    keys.resize(2 * (size_t)epochs);
     for (int ep = 0; ep < epochs; ++ep) {
         uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(ep + 1);
         z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
         keys[2 * ep] = (uint32_t)z; keys[2 * ep + 1] = (uint32_t)(z >> 32);
     }
     HIP_OK(h, hipMemcpyAsync(h->d_keys, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    // hipGraph replay of the whole update; RCCL calls and event-bracketed profiling run eagerly
-    // With a communicator the sequence runs eagerly by default (the host enqueues a step faster than the GPU runs it);
-    // PPO_HIP_GRAPH_RCCL=1 opts into capturing the ncclAllReduce calls as well.
+    return 0;
+}
+
+// hipGraph replay of the whole update; RCCL calls and event-bracketed profiling run eagerly
+// With a communicator the sequence runs eagerly by default (the host enqueues a step faster than the GPU runs it);
+// PPO_HIP_GRAPH_RCCL=1 opts into capturing the ncclAllReduce calls as well.
+static int run_update(ppo_handle* h, int epochs, int nmb, bool explicit_perms) {
     const bool graph_ok = h->use_graph && !h->prof && (!h->comm || h->graph_rccl || h->peer.on);
-    if (graph_ok) {
-        const bool same = h->upd_graph && h->g_epochs == epochs && h->g_nmb == nmb && h->g_E == h->E && h->g_T == h->T &&
-                          h->g_explicit == (int)explicit_perms && h->g_world == (gs ? -h->world : h->world);
-        if (!same) {
-            drop_graph(h);
-            HIP_OK(h, hipStreamSynchronize(h->stream));
-            hipGraph_t graph = nullptr;
-            // a runtime that cannot capture or instantiate this sequence is not fatal: the same launches run eagerly
-            // (nothing has executed yet -- capture only records)
-            bool ok = hipStreamBeginCapture(h->stream, h->comm ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                const int rc = enqueue_update(h, epochs, nmb, explicit_perms);
-                const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-                ok = rc == 0 && ce == hipSuccess && graph != nullptr && hipGraphInstantiate(&h->upd_graph, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (ok) { h->upd_graph_tmpl = graph; h->bf.g_lazy = h->bf.lazy_last; }            // (kept alive beside the executable graph: drop_graph)
-                else if (graph) (void)hipGraphDestroy(graph);
-            }
-            if (!ok) {
-                (void)hipGetLastError();
-                h->upd_graph = nullptr;
-                h->use_graph = false;
-                fprintf(stderr, "libppo_hip: hipGraph capture of the update failed (%s); continuing with eager launches\n", h->err.c_str());
-            } else {
-                h->g_epochs = epochs; h->g_nmb = nmb; h->g_E = h->E; h->g_T = h->T; h->g_explicit = (int)explicit_perms; h->g_world = gs ? -h->world : h->world;
-            }
+    if (!graph_ok) return enqueue_update(h, epochs, nmb, explicit_perms);
+    const int world_key = global_shuffle_on(h) ? -h->world : h->world;
+    const bool same = h->upd_graph && h->g_epochs == epochs && h->g_nmb == nmb && h->g_E == h->E && h->g_T == h->T &&
+                      h->g_explicit == (int)explicit_perms && h->g_world == world_key;
+    if (!same) {
+        drop_graph(h);
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        hipGraph_t graph = nullptr;
+        // a runtime that cannot capture or instantiate this sequence is not fatal: the same launches run eagerly
+        // (nothing has executed yet -- capture only records)
+        bool ok = hipStreamBeginCapture(h->stream, h->comm ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal) == hipSuccess;
+        if (ok) {
+            const int rc = enqueue_update(h, epochs, nmb, explicit_perms);
+            const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
+            ok = rc == 0 && ce == hipSuccess && graph != nullptr && hipGraphInstantiate(&h->upd_graph, graph, nullptr, nullptr, 0) == hipSuccess;
+            if (ok) { h->upd_graph_tmpl = graph; h->bf.lazy.captured = h->bf.lazy.enqueued; }     // (kept alive beside the executable graph: drop_graph)
+            else if (graph) (void)hipGraphDestroy(graph);
         }
-        if (h->upd_graph) { HIP_OK(h, hipGraphLaunch(h->upd_graph, h->stream)); h->bf.lazy_last = h->bf.g_lazy; }
-        else if (enqueue_update(h, epochs, nmb, explicit_perms)) return -1;
-    } else if (enqueue_update(h, epochs, nmb, explicit_perms)) return -1;
-    h->bf.grad_lazy = h->bf.lazy_last;
+        if (!ok) {
+            (void)hipGetLastError();
+            h->upd_graph = nullptr;
+            h->use_graph = false;
+            fprintf(stderr, "libppo_hip: hipGraph capture of the update failed (%s); continuing with eager launches\n", h->err.c_str());
+        } else {
+            h->g_epochs = epochs; h->g_nmb = nmb; h->g_E = h->E; h->g_T = h->T; h->g_explicit = (int)explicit_perms; h->g_world = world_key;
+        }
+    }
+    if (!h->upd_graph) return enqueue_update(h, epochs, nmb, explicit_perms);
+    HIP_OK(h, hipGraphLaunch(h->upd_graph, h->stream));
+    h->bf.lazy.enqueued = h->bf.lazy.captured;                  // (the host code of a train step does not run on a replay: the graph's last step is what it captured)
+    return 0;
+}
+
+int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t nmb, const int32_t* perms, uint64_t seed, float* loss_rows,
+               float mean_losses[5]) {
+    ENTER_Q(h);
+    if (!h->E) return fail(h, "ppo_update: no rollout allocated (ppo_rollout_alloc + collect first)");
+    const int B = h->E * h->T;
+    if (epochs < 1 || nmb < 1 || B % nmb) return fail(h, "ppo_update: n_batch %d not divisible by nminibatches %d", B, nmb);
+    const int M = B / nmb;
+    if (ensure_train_ws(h, M)) return -1;
+    const int steps = epochs * nmb;
+    const bool gs = global_shuffle_on(h);
+    if (h->masking && h->global_shuffle)
+        return fail(h, "ppo_update: ppo_dist_global_shuffle(1) together with action masking is not supported (the masks are not all-gathered); switch one of them off");
+    const int Bp = gs ? B * h->world : B;                      // rows one permutation covers
+    if (ensure_update_ws(h, Bp, M, steps, nmb) || set_hyper(h, lr, cliprange)) return -1;
+    if (perms && upload_perms(h, perms, epochs, Bp)) return -1;
+    if (gs && allgather_rollout(h)) return -1;
+    std::vector<uint32_t> keys;
+    if (upload_epoch_keys(h, epochs, seed, keys) || run_update(h, epochs, nmb, perms != nullptr)) return -1;
+    h->bf.lazy.ran = h->bf.lazy.enqueued;
     if (loss_rows) HIP_OK(h, hipMemcpyAsync(loss_rows, h->d_loss_rows, (size_t)steps * 5 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(h, hipMemcpyAsync(mean_losses, h->d_loss_mean, 5 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(h, hipStreamSynchronize(h->stream));

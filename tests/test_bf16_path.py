@@ -231,6 +231,55 @@ def test_gradient_behind_an_update_is_rebuilt_on_demand(monkeypatch):
         np.testing.assert_array_equal(a, b)
 
 
+@pytest.mark.parametrize("n", [64, 300])
+def test_gradient_behind_a_replayed_update_after_a_train_step_of_another_row_count(n, monkeypatch):
+    """update (captured), train_step of n rows (not the update's M = 128), update (a REPLAY), last_grad: the host code of a train step does not run on a replay, so what
+    the gradient is rebuilt with has to be what the GRAPH's last step was enqueued with, whole -- not the train step's in between.  Same BITS as a handle whose every
+    step wrote its gradient (PPO_HIP_NO_REDUCE_ADAM=1).
+    The rollout and the update alone size the workspaces for 128 rows (64 rows per env step, 128 per minibatch), and a train step of more rows would reallocate them and
+    drop the graph: an act call of 512 rows grows them BEFORE the first update, so neither train step reallocates and the second update is a replay -- asserted from
+    kernel_counts(), which counts a capture once and a replay not at all.
+    n = 64 pads to the minibatches' 128 rows: the two steps' assembly arguments differ in the row count alone, which lands in a tail word last_grad does not return; this
+    case cannot show the defect.  n = 300 pads to 384 rows: another split of the weight-gradient GEMM, 24 slot rows instead of 8, 3 bias-gradient rows instead of 1.
+    Recorded, not asserted: the library before the three loose members became one value (cfb6d2a), run through this test: n = 64 passes (norm 4.023751258850098 either
+    way, 601637 gradient elements equal); n = 300 fails on the fused handle -- the rebuilt gradient's own norm is 4.040394162895795 against the 3.866426944732666 the
+    update reported (the gradient was rebuilt from the 384-row step's split and slot rows)."""
+    hidden, O, A, E, T, nmb, epochs = (512, 512), 64, 18, 64, 8, 4, 2
+    rng = np.random.RandomState(3)
+    noise = rng.normal(size=(T, E, A)).astype(np.float32)
+    perms = np.stack([rng.permutation(E * T) for _ in range(epochs)]).astype(np.int32)
+    big_obs = rng.normal(size=(512, O)).astype(np.float32)
+    outs = []
+    for two in ("0", "1"):
+        monkeypatch.setenv("PPO_HIP_NO_REDUCE_ADAM", two)
+        orc, g = pair_bf16(hidden, O, A)
+        mb = H.synth_minibatch(orc, n, seed=9)
+        g.norm_init(E, GAMMA); g.rollout_alloc(E, T)
+        g.value(big_obs)                                    # workspaces for 512 rows from here on
+        g.collect_synthetic(100, GAMMA, LAM, noise)
+        c0 = g.kernel_counts()
+        acc = [g.update(LR, CR, epochs, nmb, perms)[0].copy()]
+        c1 = g.kernel_counts()
+        assert c1["bf16_train_sequence"] - c0.get("bf16_train_sequence", 0) == epochs * nmb          # the capture
+        acc.append(np.asarray(g.train_step(LR, CR, mb["obs"], mb["actions"], mb["advs"], mb["returns"], mb["old_neglogp"], mb["old_values"])).copy())
+        g.collect_synthetic(101, GAMMA, LAM, noise)
+        c2 = g.kernel_counts()
+        acc.append(g.update(LR, CR, epochs, nmb, perms)[0].copy())
+        c3 = g.kernel_counts()
+        assert c3["bf16_train_sequence"] == c2["bf16_train_sequence"] == c1["bf16_train_sequence"] + 1, "the second update was not a replay"
+        gr, nrm = g.last_grad()
+        print("n", n, "NO_REDUCE_ADAM", two, "norm", repr(nrm))
+        assert np.sqrt(np.sum(gr.astype(np.float64) ** 2)) == pytest.approx(nrm, rel=1e-5)
+        acc += [gr.copy(), np.float32(nrm), g.get_flat(0)]
+        g.close()
+        outs.append(acc)
+    monkeypatch.delenv("PPO_HIP_NO_REDUCE_ADAM", raising=False)
+    assert np.abs(outs[0][3]).max() > 0
+    print("n", n, "gradient elements differing between the handles:", int((outs[0][3] != outs[1][3]).sum()), "of", outs[0][3].size)
+    for a, b in zip(*outs):
+        np.testing.assert_array_equal(a, b)
+
+
 def test_chained_launches_of_two_row_counts_on_one_handle(monkeypatch):
     """One handle alternating between 4096-row and 2048-row train steps (32 and 16 row groups per chained launch -- as the act path's row count and the minibatch's
     do in a rollout + update): every shape has its own table of workgroup words (a shared table means a slot is different (link, row group) pairs under different
