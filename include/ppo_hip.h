@@ -71,20 +71,34 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
  *   PPO_ACT_GAUSSIAN     SPACE_CONTINOUS: cfg->act_dim = action dimensions
  *   PPO_ACT_CATEGORICAL  SPACE_DISCRETE: cfg->act_dim = number of categories A >= 2 (stable-baselines' CategoricalProbabilityDistribution:
  *                        logits l = h_L W_pi + b_pi, a = argmax_j (l_j - log(-log u_j)), neglogp = softmax cross-entropy against one_hot(a)).
- *                        An action is ONE float per row holding the category index ("categorical handle" below).  PPO_F32 only: PPO_BF16
- *                        is refused.  It runs the generic fp32 kernel families.  Errors: act_dim < 2, an unknown
- *                        action_dist, PPO_BF16.
- * A flag may be OR-ed into action_dist:
+ *                        An action is ONE float per row holding the category index ("categorical handle" below).  With PPO_F32 it runs the
+ *                        generic fp32 kernel families.  With PPO_BF16 it needs the flag PPO_ACT_BF16_HEAD below; without the flag
+ *                        that combination is refused.  Errors: act_dim < 2, an unknown action_dist, PPO_BF16 without PPO_ACT_BF16_HEAD, PPO_BF16 with
+ *                        more than 128 categories.
+ * Flags may be OR-ed into action_dist:
  *   PPO_ACT_SHAPE_KERNELS  PPO_ACT_CATEGORICAL | PPO_ACT_SHAPE_KERNELS lets a categorical PPO_F32 handle take the narrow LDS-resident family when its
  *                        shape qualifies as a Gaussian handle's would (every hidden width <= 64, padded observation and category widths <= 64, the
  *                        image fits 160 KB, PPO_HIP_NO_NARROW unset): one policy-step launch per env step ("narrow_step_kernel<cat>",
  *                        "narrow_step_kernel<cat,mask>") and narrow_train_kernel<cat[,mask]> + narrow_reduce_kernel + adam_kernel per train step.  A
  *                        shape that does not qualify runs the generic categorical kernels, as without the flag.  With PPO_ACT_GAUSSIAN the flag is
  *                        accepted and changes nothing.  Not the default (opt-in); data parallel is not available to such a handle: ppo_dist_init
- *                        refuses it.  ppo_action_dist reports the low bits only. */
+ *                        refuses it.  ppo_action_dist reports the low bits only.
+ *   PPO_ACT_BF16_HEAD    PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD with compute_dtype PPO_BF16 creates a categorical handle on the bf16 path: the GEMMs, the
+ *                        head kernel, the backward chain, the weight-gradient GEMM and the assembly are the Gaussian handle's; the logits are the head's
+ *                        fp32 partial products added in range order, and bf16_sample_kernel / bf16_loss_kernel run their <cat> / <cat,mask> forms (one
+ *                        wave per row, lane l owns categories l and l + 64) with the arithmetic stated under "action masks of the categorical head"
+ *                        below.  At most 128 categories: act_dim > 128 is an error of ppo_create_ex that names the limit.  Action masks, the masked
+ *                        rollout and ppo_update work as on a PPO_F32 categorical handle.  ppo_kernel_counts names, counted INSTEAD of
+ *                        "bf16_step_sequence" / "bf16_train_sequence": "bf16_step_sequence<cat>", "bf16_step_sequence<cat,mask>",
+ *                        "bf16_train_sequence<cat>", "bf16_train_sequence<cat,mask>".  The tensor list has 4L+4 entries (no pi/logstd); the padded
+ *                        logstd region keeps its place and is never moved.  With PPO_F32, or with PPO_ACT_GAUSSIAN, the flag is accepted and changes
+ *                        nothing (same bits, same ppo_kernel_counts); PPO_ACT_SHAPE_KERNELS beside it on a PPO_BF16 handle is accepted and ignored (a
+ *                        PPO_BF16 handle is never narrow).  Not the default (opt-in); data parallel is not available to such a handle: ppo_dist_init
+ *                        refuses it ("... not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") and leaves it usable. */
 #define PPO_ACT_GAUSSIAN    0
 #define PPO_ACT_CATEGORICAL 1
 #define PPO_ACT_SHAPE_KERNELS 0x100
+#define PPO_ACT_BF16_HEAD 0x200
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out);
 int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL */
 void ppo_destroy(ppo_handle* h);
@@ -144,7 +158,7 @@ int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* act
  * the mask comes from the host (the three calls below, ppo_rollout_act_masked, ppo_rollout_upload of field 8), and a ppo_train_step_masked row whose action
  * its own mask forbids.  ppo_update has no host check: if the rollout's action field was uploaded inconsistently with its mask field, the loss values of
  * such a row are unspecified (the kernels still read and write inside their buffers and terminate).
- * The three calls need a categorical handle (a Gaussian or PPO_BF16 handle: an error); mask == NULL is the unmasked call, the same launch. */
+ * The three calls need a categorical handle (a Gaussian handle, PPO_F32 or PPO_BF16: an error); mask == NULL is the unmasked call, the same launch. */
 int ppo_step_masked(ppo_handle* h, const float* obs, int32_t n, const float* noise, const float* mask, float* action, float* value,
                     float* neglogp);
 int ppo_act_deterministic_masked(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* action);
@@ -283,7 +297,8 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t noptepochs, int
  * ppo_train_step / ppo_update all-reduce (sum) the flat gradient + loss sums across ranks between the backward
  * and the clip+Adam launches, and ppo_norm_* merge their batch moments across ranks. */
 int ppo_dist_unique_id(char uid[128]);
-/* (a categorical handle created with PPO_ACT_SHAPE_KERNELS is refused: "... data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS") */
+/* (a categorical handle created with PPO_ACT_SHAPE_KERNELS is refused: "... data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS";
+ *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
 int ppo_dist_world(const ppo_handle* h);
 /* What a reader of a scaling run needs in order to check the ranks (all out-pointers optional): the number of ranks the

@@ -56,6 +56,7 @@ def _f32(a, shape=None):
 
 ACTION_DISTS = {"gaussian": 0, "categorical": 1}        # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL
 ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS, OR-ed into ppo_create_ex's action_dist
+ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, likewise
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -68,6 +69,9 @@ class PPOHip:
     explicit noise keeps the Gaussian's shape and holds the uniforms of the Gumbel-argmax draw.
     shape_kernels=True (PPO_ACT_SHAPE_KERNELS; default False): a categorical handle whose shape qualifies (every hidden width <= 64, ...)
     runs the narrow LDS-resident kernels instead of the generic ones; any other shape, and a Gaussian handle, are not affected.
+    bf16_head=True (PPO_ACT_BF16_HEAD; default False): with action_dist="categorical" and compute_dtype=1 (PPO_BF16) the handle runs the bf16
+    matrix-core path with a categorical head (at most 128 categories; masks included; no data parallel).  Without it that combination is
+    refused; on a compute_dtype=0 or Gaussian handle it changes nothing.
 
     Action masks (categorical only; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -77,7 +81,7 @@ class PPOHip:
     MASK_FIELDS = {"masks": 8}                  # [T, E, A]; a masking handle only (set_action_masking)
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
-    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, **overrides):
+    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, **overrides):
         self.lib = load_library()
         cfg = PPOConfig()
         hid = (C.c_int32 * len(hidden))(*hidden)
@@ -91,9 +95,10 @@ class PPOHip:
             raise ValueError("action_dist must be one of %s, not %r" % (sorted(ACTION_DISTS), action_dist))
         self.action_dist = action_dist
         self.shape_kernels = bool(shape_kernels)
+        self.bf16_head = bool(bf16_head)
         self._act_shape = (act_dim,) if action_dist == "gaussian" else ()      # per row
         h = C.c_void_p()
-        if self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0), C.byref(h)) != 0:
+        if self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)
@@ -399,8 +404,8 @@ class PPOHip:
 
     def kernel_counts(self):
         """{kernel variant: times enqueued since creation} -- which of the shape-selected kernels the calls so far took"""
-        names = ((C.c_char * 32) * 32)(); cnt = (C.c_int64 * 32)()
-        n = self.lib.ppo_kernel_counts(self.h, 32, names, cnt)
+        names = ((C.c_char * 32) * 64)(); cnt = (C.c_int64 * 64)()
+        n = self.lib.ppo_kernel_counts(self.h, 64, names, cnt)
         return {names[i].value.decode(): cnt[i] for i in range(n)}
 
     def debug_buffer(self, name):

@@ -768,15 +768,87 @@ struct SampleArgsB {
     const float* logstd;                // fp32 master
     const float* noise; float* action; float* det_action; float* value; float* neglogp;
     int n, A; uint32_t seed, rng_step, row_base;
+    const float* mask;                  // [n, A] action mask of the categorical head (non-zero = allowed); read by the <CAT, MASK> instantiation only
 };
+
+// ---- categorical head (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD): the arithmetic of policy_step_kernel<.., CAT, MASK> / train_fwd_bwd_kernel<.., CAT, MASK> in the
+// geometry of the two kernels below -- one wave per row, lane l owns categories l and l + 64 -- with 64-lane __shfl_xor butterflies where those kernels reduce over 16 lanes.
+// (value, index) argmax over the wave: the larger value wins, a tie goes to the lower index; every lane ends with the same pair
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+    for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(i, o); argmax_step(v, i, ov, oi); }
+}
+__device__ __forceinline__ float wave_sum_all(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+// The row statistics BOTH kernels need, in ONE shape (the sample kernel's neglogp and the loss kernel's are then the same bits on the same weights): maximum m and its
+// index over the allowed categories (ok[e]: category lane + 64 e exists and is allowed), a0 = l - m, ex = exp(a0), z = sum of ex over the allowed ones.
+// MASK: the index starts at A ("none yet"), so a lane without an allowed category loses every tie of the butterfly to a real index.
+template <bool MASK>
+__device__ __forceinline__ void cat_row_norm(const float (&lg)[2], const bool (&ok)[2], int lane, int A, int& il, float (&a0)[2], float (&ex)[2], float& z) {
+    float bl = -INFINITY;
+    il = MASK ? A : 0;
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+        if (ok[e] && (lg[e] > bl || (MASK && il == A))) { bl = lg[e]; il = lane + 64 * e; }
+    wave_argmax(bl, il);
+    float zs = 0.f;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) { a0[e] = lg[e] - bl; ex[e] = expf(a0[e]); if (ok[e]) zs += ex[e]; }
+    z = wave_sum_all(zs);
+}
+// a0 of category `act` (held by exactly one lane; the others add zeros)
+__device__ __forceinline__ float cat_row_pick(const float (&a0)[2], const bool (&ok)[2], int lane, int act) {
+    float la = 0.f;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) if (ok[e] && lane + 64 * e == act) la = a0[e];
+    return wave_sum_all(la);
+}
 
 // one wave per row, one lane per action (two past 64 actions): the row sums take the SAME shape as in bf16_loss_kernel, so the act model's
 // neglogp and the train model's are the same bits on the same weights (first-epoch ratio exactly 1)
+// CAT: the head's columns are logits; action / det_action are ONE float per row (the category index).  MASK (with CAT): a.mask [n, A] takes the forbidden
+// categories out of both argmaxes and of the normaliser; the lane that owns category j reads the mask entry next to its logit.
 #define BS_ROWS 4
+template <bool CAT = false, bool MASK = false>
 __global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(SampleArgsB a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * BS_ROWS + r;
     const bool live = row < a.n;
+    if constexpr (CAT) {
+        if (!live) return;                                   // (a row is a whole wave and the kernel has no barrier)
+        float lg[2], u[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = lane + 64 * e;
+            lg[e] = 0.f; u[e] = 0.5f; ok[e] = j < a.A;
+            if (j < a.A) {
+                lg[e] = head_sum(a.head[0], (size_t)row * a.ldh + j, a.hsplit, a.hstride);
+                if constexpr (MASK) ok[e] = a.mask[(size_t)row * a.A + j] != 0.f;
+                u[e] = a.noise ? a.noise[(size_t)row * a.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);     // (a forbidden category keeps its uniform)
+            }
+        }
+        // a = argmax_j (l_j - log(-log u_j)) over the allowed set: the first allowed category is taken even when its perturbed logit is -inf (u == 0)
+        float bp = -INFINITY;
+        int ip = MASK ? a.A : 0;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float pl = lg[e] - logf(-logf(u[e]));
+            if (ok[e] && (pl > bp || (MASK && ip == a.A))) { bp = pl; ip = lane + 64 * e; }
+        }
+        wave_argmax(bp, ip);
+        int il;
+        float a0[2], ex[2], z;
+        cat_row_norm<MASK>(lg, ok, lane, a.A, il, a0, ex, z);
+        ip = min(ip, a.A - 1); il = min(il, a.A - 1);        // (a row without an allowed category, which the host checks refuse, ends at A)
+        const float la = cat_row_pick(a0, ok, lane, ip);
+        if (lane == 0) {
+            if (a.action) a.action[row] = (float)ip;
+            if (a.det_action) a.det_action[row] = (float)il;
+            if (a.neglogp) a.neglogp[row] = logf(z) - la;
+            if (a.value) a.value[row] = head_sum(a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride);
+        }
+        return;
+    }
     float ssq = 0.f, slog = 0.f;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
@@ -814,6 +886,7 @@ struct LossArgsB {
     int n, A, Ap, rows_pad; float inv_n, ent_coef, vf_coef;
     bf16_t* dhead[2];                   // [rows_pad][Ap]  (tower 1: only column 0 is ever non-zero)
     float* slots[2]; int slot_w, slot_head, slot_aux, slot_loss;
+    const float* mask;                  // [n][A] action masks in minibatch order (non-zero = allowed); read by the <CAT, MASK> instantiation only
 };
 
 #ifndef BL_ROWS
@@ -823,7 +896,12 @@ struct LossArgsB {
 // One wave per row, one lane per action: every lane requests its element's partial products at once and the row sums are wave
 // reductions.  (Rounds 2-3: 16 lanes per row walking the actions in a loop of dependent loads, 32 rows per block = 128 workgroups of
 // latency: 11.7 us for 8.8 MB.)
+// CAT: `actions` holds ONE float per row (the category index, read once and compared with the lane's j: nothing is indexed with it); d logits go where d mu goes, the
+// aux (d logstd) slot words are zeros, pt[1] is the row's categorical entropy.  MASK (with CAT): a.mask [n][A]; maximum, normaliser, neglogp and entropy run over the
+// allowed categories, d logits of a forbidden one is exactly +0.  Same lane loops and butterflies as <CAT>: an all-ones mask gives its bits.
+template <bool CAT = false, bool MASK = false>
 __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     extern __shared__ __attribute__((aligned(16))) float ls[];      // [R][Ap] dmu | [R][Ap] dlogstd | [R][4] pi terms | [R][2] vf terms
     float* dmu_s = ls; float* dls_s = ls + BL_ROWS * a.Ap; float* pt = dls_s + BL_ROWS * a.Ap; float* vt = pt + 4 * BL_ROWS;
     const int tid = threadIdx.x, r = tid >> 6, lane = tid & 63;
@@ -835,14 +913,22 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
     const float g = a.inv_n;
     // every load of the lane first: head partials, actions, the row scalars
     float hp[BL_EPT][GB_HEAD_SPLIT], act_[BL_EPT], ls_[BL_EPT];
+    bool ok[BL_EPT];                                // CAT: category j exists and is allowed (dead rows of the last block: all allowed, nothing is read)
 #pragma unroll
     for (int e = 0; e < BL_EPT; ++e) {
         const int j = lane + 64 * e;
 #pragma unroll
         for (int k = 0; k < GB_HEAD_SPLIT; ++k) hp[e][k] = (j < a.A && k < a.hsplit) ? a.head[0][(size_t)k * a.hstride + (size_t)row * a.ldh + j] : 0.f;
+        if constexpr (CAT) {
+            act_[e] = 0.f; ls_[e] = 0.f; ok[e] = j < a.A;
+            if constexpr (MASK) { if (j < a.A && live) ok[e] = a.mask[(size_t)row * a.A + j] != 0.f; }
+        } else {
         act_[e] = (j < a.A && live) ? a.actions[(size_t)row * a.A + j] : 0.f;
         ls_[e] = j < a.A ? a.logstd[j] : 0.f;
+        }
     }
+    int cact = -1;                                  // CAT: the row's category index
+    if constexpr (CAT) { if (live) cact = (int)a.actions[row]; }
     float vp[GB_HEAD_SPLIT];
 #pragma unroll
     for (int k = 0; k < GB_HEAD_SPLIT; ++k) vp[k] = (lane == 0 && live && k < a.hsplit) ? a.head[1][(size_t)k * a.hstride + (size_t)row * a.ldh] : 0.f;
@@ -851,8 +937,27 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
     float Rv = 0.f, vo = 0.f;
     if (lane == 0 && live) { Rv = a.returns[row]; vo = a.old_values[row]; }
     // policy tower
-    float mu[BL_EPT], z[BL_EPT], sigma[BL_EPT];
+    float mu[BL_EPT], z[BL_EPT], sigma[BL_EPT];       // CAT: mu = a0 = l - m, z = exp(a0), sigma unused
     float ssq = 0.f, slog = 0.f, sent = 0.f;
+    float cz = 1.f, clz = 0.f, cnlp = 0.f;          // CAT: normaliser, its log, neglogp
+    if constexpr (CAT) {
+        float lg[BL_EPT];
+#pragma unroll
+        for (int e = 0; e < BL_EPT; ++e) {
+            float m = hp[e][0];
+#pragma unroll
+            for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < a.hsplit) m += hp[e][k];   // the partial products in range order (head_sum)
+            lg[e] = live ? m : 0.f;
+        }
+        int il;
+        cat_row_norm<MASK>(lg, ok, lane, a.A, il, mu, z, cz);
+        clz = logf(cz);
+        const float la = cat_row_pick(mu, ok, lane, cact);
+#pragma unroll
+        for (int e = 0; e < BL_EPT; ++e) if (ok[e]) sent += (z[e] / cz) * (clz - mu[e]);
+        sent = wave_sum_all(sent);
+        cnlp = clz - la;
+    } else {
 #pragma unroll
     for (int e = 0; e < BL_EPT; ++e) {
         const int j = lane + 64 * e;
@@ -867,7 +972,8 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
         if (j < a.A) { ssq += z[e] * z[e]; slog += logstd; sent += logstd + HALF_LOG_2PIE; }
     }
     for (int o = 32; o > 0; o >>= 1) { ssq += __shfl_xor(ssq, o); slog += __shfl_xor(slog, o); sent += __shfl_xor(sent, o); }
-    const float nlp = 0.5f * ssq + HALF_LOG_2PI * (float)a.A + slog;
+    }
+    const float nlp = CAT ? cnlp : 0.5f * ssq + HALF_LOG_2PI * (float)a.A + slog;
     const float old_nlp = live ? old_nlp_in : nlp;
     const float lo = 1.0f - cr, hi = 1.0f + cr;
     const float ratio = expf(old_nlp - nlp);
@@ -891,6 +997,13 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
         const int j = lane + 64 * e;
         if (j < a.Ap) {
             float dmu = 0.f, dl = 0.f;
+            if constexpr (CAT) {
+                // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H)   (dl stays 0: no logstd; forbidden and padding columns: +0)
+                if (live && ok[e]) {
+                    const float p = z[e] / cz;
+                    dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + a.ent_coef * g * (p * ((mu[e] - clz) + sent));
+                }
+            } else
             if (j < a.A && live) {
                 dl = d_nlp * (1.0f - z[e] * z[e]) - a.ent_coef * g;                      // AddN_2 G:21299
                 dmu = d_nlp * (-(z[e] / sigma[e])) + dl * 0.0f;                          // AddN_3 G:22656

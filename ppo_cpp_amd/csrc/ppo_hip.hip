@@ -62,7 +62,8 @@ const char* kProfNames[PK_COUNT] = {"policy_step", "train_fwd_bwd", "weight_grad
 enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN, KV_NARROW_STEP_STATIC, KV_NARROW_STEP,
                      KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH,
                      KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_POLICY_STEP_CAT_MASK, KV_TRAIN_FB_CAT_MASK, KV_STEP_HOST_ACTION,
-                     KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_COUNT };
+                     KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK,
+                     KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -72,7 +73,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "policy_step_kernel<cat,mask>", "train_fwd_bwd_kernel<cat,mask>",
                                        "policy_step_kernel<host_action>" /* launches (of any head) that published their actions to the host themselves */,
                                        // a categorical handle created with PPO_ACT_SHAPE_KERNELS on a narrow shape (static and runtime-shape instantiations share a name)
-                                       "narrow_step_kernel<cat>", "narrow_step_kernel<cat,mask>", "narrow_train_kernel<cat>", "narrow_train_kernel<cat,mask>"};
+                                       "narrow_step_kernel<cat>", "narrow_step_kernel<cat,mask>", "narrow_train_kernel<cat>", "narrow_train_kernel<cat,mask>",
+                                       // a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence"
+                                       "bf16_step_sequence<cat>", "bf16_step_sequence<cat,mask>", "bf16_train_sequence<cat>", "bf16_train_sequence<cat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -101,6 +104,7 @@ struct ppo_handle {
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical handle may take the narrow family (build_narrow_layout)
+    bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian) or 1 (categorical: the category index)
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
     // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
@@ -946,8 +950,12 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     sa.head[0] = h->bf.head_out[0]; sa.head[1] = h->bf.head_out[1]; sa.ldh = n.Ap; sa.hsplit = h->bf.head_split; sa.hstride = (size_t)h->bf.Rcap * n.Ap; sa.logstd = h->theta + n.ls_off;
     sa.noise = a.noise; sa.action = a.action; sa.det_action = a.det_action; sa.value = a.value; sa.neglogp = a.neglogp;
     sa.n = a.n; sa.A = n.A; sa.seed = a.seed; sa.rng_step = a.rng_step; sa.row_base = a.row_base;
+    sa.mask = a.mask;
     if (n.A > 128) return fail(h, "bf16 path: more than 128 actions");
-    hipLaunchKernelGGL(bf16_sample_kernel, dim3((a.n + BS_ROWS - 1) / BS_ROWS), dim3(64 * BS_ROWS), 0, h->stream, sa);
+    const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
+    if (a.mask) hipLaunchKernelGGL((bf16_sample_kernel<true, true>), grid, blk, 0, h->stream, sa);
+    else if (h->dist == PPO_ACT_CATEGORICAL) hipLaunchKernelGGL((bf16_sample_kernel<true, false>), grid, blk, 0, h->stream, sa);
+    else hipLaunchKernelGGL((bf16_sample_kernel<false, false>), grid, blk, 0, h->stream, sa);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -973,8 +981,13 @@ int bf16_train_fwd_bwd(ppo_handle* h, const TrainArgs& ta, int Rp, bool links_on
     la.ldh = n.Ap; la.hsplit = b.head_split; la.hstride = (size_t)b.Rcap * n.Ap; la.logstd = h->theta + n.ls_off; la.actions = ta.actions; la.advs = ta.advs; la.returns = ta.returns; la.old_values = ta.old_values;
     la.old_neglogp = ta.old_neglogp; la.hyper = h->hyper; la.n = ta.n; la.A = n.A; la.Ap = n.Ap; la.rows_pad = b.Rcap; la.inv_n = ta.inv_n;
     la.ent_coef = n.ent_coef; la.vf_coef = n.vf_coef; la.slot_w = n.slot_w; la.slot_head = n.slot_head; la.slot_aux = n.slot_aux; la.slot_loss = n.slot_loss;
+    la.mask = ta.mask;
     if (n.A > 64 * BL_EPT) return fail(h, "bf16 path: more than %d actions", 64 * BL_EPT);
-    hipLaunchKernelGGL(bf16_loss_kernel, dim3(Rp / BL_ROWS), dim3(64 * BL_ROWS), (size_t)(2 * BL_ROWS * n.Ap + 6 * BL_ROWS) * sizeof(float), h->stream, la);
+    const dim3 lgrid(Rp / BL_ROWS), lblk(64 * BL_ROWS);
+    const size_t llds = (size_t)(2 * BL_ROWS * n.Ap + 6 * BL_ROWS) * sizeof(float);
+    if (ta.mask) hipLaunchKernelGGL((bf16_loss_kernel<true, true>), lgrid, lblk, llds, h->stream, la);
+    else if (h->dist == PPO_ACT_CATEGORICAL) hipLaunchKernelGGL((bf16_loss_kernel<true, false>), lgrid, lblk, llds, h->stream, la);
+    else hipLaunchKernelGGL((bf16_loss_kernel<false, false>), lgrid, lblk, llds, h->stream, la);
     HIP_OK(h, hipGetLastError());
     if (links_only) return 0;
     GemmArgs bl[PPO_MAX_LAYERS];
@@ -1089,10 +1102,10 @@ void launch_narrow_step(ppo_handle* h, const StepArgs& a) {
 #undef X
 }
 int launch_step(ppo_handle* h, const StepArgs& a) {
-    if (h->bf.on) { ++h->kv[KV_BF16_STEP]; return launch_step_bf16(h, a); }
-    ProfScope ps(h, PK_STEP);
     const bool cat = h->dist == PPO_ACT_CATEGORICAL;
     if (a.mask && !cat) return fail(h, "policy step: an action mask needs a categorical handle");
+    if (h->bf.on) { ++h->kv[a.mask ? KV_BF16_STEP_CAT_MASK : cat ? KV_BF16_STEP_CAT : KV_BF16_STEP]; return launch_step_bf16(h, a); }
+    ProfScope ps(h, PK_STEP);
     if (h->narrow) {                                              // (a categorical handle here: created with PPO_ACT_SHAPE_KERNELS)
         ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : cat ? KV_NARROW_STEP_CAT : h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP];
         if (a.mask) launch_narrow_step<true, true>(h, a); else if (cat) launch_narrow_step<true, false>(h, a); else launch_narrow_step<false, false>(h, a);
@@ -1378,7 +1391,8 @@ static int bf16_reduce_adam(ppo_handle* h, const ReduceArgs& ra, int n_old, floa
 
 static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool bucketed, AdamParts& parts) {
     const int Rp = ru(ta.n, GB_PAD);
-    ++h->kv[KV_BF16_TRAIN];
+    if (ta.mask && h->dist != PPO_ACT_CATEGORICAL) return fail(h, "train step: an action mask needs a categorical handle");
+    ++h->kv[ta.mask ? KV_BF16_TRAIN_CAT_MASK : h->dist == PPO_ACT_CATEGORICAL ? KV_BF16_TRAIN_CAT : KV_BF16_TRAIN];
     h->bf.lazy.enqueued.on = false;
     if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
     { ProfScope ps(h, PK_TRAIN_FB); if (bf16_train_fwd_bwd(h, ta, Rp)) return -1; }
@@ -1665,14 +1679,17 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     *out = nullptr;
     if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
     if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
-    const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the one flag; whatever else is left must be a distribution
-    action_dist &= ~(int32_t)PPO_ACT_SHAPE_KERNELS;
+    const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the two flags; whatever else is left must be a distribution
+    const bool bf16_head = (action_dist & PPO_ACT_BF16_HEAD) != 0;
+    action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD);
     if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL)
-        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS)", (int)action_dist);
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
-    if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16)
-        return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported (the categorical head runs on the PPO_F32 path only)");
+    if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && !bf16_head)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
+    if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && cfg->act_dim > 128)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
     for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -1682,6 +1699,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     h->cfg = *cfg;
     h->dist = action_dist;
     h->shape_kernels = shape_kernels && action_dist == PPO_ACT_CATEGORICAL;       // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
+    h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
     h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : cfg->act_dim;
     int dev = cfg->device;
     if (dev < 0) { const char* lr = getenv("LOCAL_RANK"); dev = lr ? atoi(lr) % ndev : 0; }
@@ -2005,7 +2023,7 @@ static int check_masks(ppo_handle* h, const char* who, const float* mask, size_t
     return 0;
 }
 static int need_categorical(ppo_handle* h, const char* who) {
-    if (h->dist != PPO_ACT_CATEGORICAL || h->bf.on) return fail(h, "%s: action masks need a categorical (PPO_ACT_CATEGORICAL, PPO_F32) handle", who);
+    if (h->dist != PPO_ACT_CATEGORICAL) return fail(h, "%s: action masks need a categorical (PPO_ACT_CATEGORICAL) handle", who);
     return 0;
 }
 // staging buffer of the host-pointer calls' masks: allocated by the first masked call, so that a handle that never passes a mask allocates what it always did
@@ -3517,6 +3535,7 @@ struct UidByValue { char b[128]; };
 
 int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128]) {
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
+    if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (load_rccl(h->rccl, h->err)) return -1;
     HIP_OK(h, hipSetDevice(h->device));

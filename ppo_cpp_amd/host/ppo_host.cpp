@@ -176,7 +176,13 @@ struct ppo_host_args {
     int obs_dim, act_dim;        // SeededEnvMock's shape (0 = 18): 36 / 18 is the hexapod with observed velocities (hexapod_closed_loop_env.hpp:20)
     float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
     int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for)
+    int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD)
 };
+// the handle's action_dist for `env`: PPO2's choice, plus the opt-in a categorical head needs on the bf16 path
+static int32_t host_action_dist(Env& env, const ppo_host_args* a) {
+    const int32_t d = PPO2::action_dist_for(env, a->discrete_kernels != 0);
+    return (a->compute_dtype == PPO_BF16 && (d & 0xff) == PPO_ACT_CATEGORICAL) ? (d | PPO_ACT_BF16_HEAD) : d;
+}
 struct ppo_host_result {
     double env_steps_per_s, collect_ms, update_ms;
     float losses[5];
@@ -197,6 +203,7 @@ struct ppo_host_explicit {
     float* obs_mean; float* obs_var; double* obs_count;      // obs_rms [18], [18], [1]
     float* ret_mean; float* ret_var; double* ret_count;      // ret_rms [1], [1], [1]
     float* reward_curve;         // [n_updates] mean un-normalised reward of every update's rollout
+    char (*count_names)[32]; long long* counts; int* n_counts;     // ppo_kernel_counts of the run's handle after learn(): up to 64 entries (all three or none)
 };
 
 static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_host_explicit* x) {
@@ -215,7 +222,8 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
             return new EnvMock(1);
         };
         { std::unique_ptr<Env> probe(make_probe());
-          if (ppo_create_ex(&cfg, PPO2::action_dist_for(*probe, a->discrete_kernels != 0), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
+          cfg.compute_dtype = a->compute_dtype;
+          if (ppo_create_ex(&cfg, host_action_dist(*probe, a), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (x && x->theta_in && ppo_set_flat(h, 0, x->theta_in, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<Env>> envs;
@@ -283,6 +291,12 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
                 if (x->theta_out && ppo_get_flat(h, 0, x->theta_out, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
                 if (x->obs_mean && ppo_norm_get_stats(h, 0, x->obs_mean, x->obs_var, x->obs_count) != 0) throw std::runtime_error(ppo_last_error(h));
                 if (x->ret_mean && ppo_norm_get_stats(h, 1, x->ret_mean, x->ret_var, x->ret_count) != 0) throw std::runtime_error(ppo_last_error(h));
+                if (x->count_names && x->counts && x->n_counts) {
+                    int64_t c64[64];
+                    const int nc = ppo_kernel_counts(h, 64, x->count_names, c64);
+                    for (int i = 0; i < nc; ++i) x->counts[i] = (long long)c64[i];
+                    *x->n_counts = nc;
+                }
             }
         }
         ppo_destroy(h);
@@ -417,7 +431,8 @@ int ppo_host_learn_masked(const ppo_host_args* a, float* reward_curve, long long
         ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
         cfg.device = a->device;
         { MaskedTargetEnv probe(1234u, 0, O, A);
-          if (ppo_create_ex(&cfg, PPO2::action_dist_for(probe, a->discrete_kernels != 0), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
+          cfg.compute_dtype = a->compute_dtype;
+          if (ppo_create_ex(&cfg, host_action_dist(probe, a), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<MaskedTargetEnv>> kids;
         std::vector<std::shared_ptr<Env>> envs;

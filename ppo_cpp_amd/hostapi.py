@@ -12,7 +12,7 @@ class HostArgs(C.Structure):
                 ("lr", C.c_float), ("cliprange", C.c_float), ("gamma", C.c_float), ("lam", C.c_float),
                 ("seeded_env", C.c_int), ("device", C.c_int), ("max_workers", C.c_int), ("reference_loop", C.c_int),
                 ("norm_obs", C.c_int), ("norm_reward", C.c_int), ("seed", C.c_ulonglong), ("obs_dim", C.c_int), ("act_dim", C.c_int),
-                ("cliprange_vf", C.c_float), ("discrete_kernels", C.c_int)]
+                ("cliprange_vf", C.c_float), ("discrete_kernels", C.c_int), ("compute_dtype", C.c_int)]
 
 
 def _discrete_kernels(name):
@@ -69,7 +69,8 @@ def learn(n_envs, n_steps, hidden, n_updates, nminibatches=32, noptepochs=10, lr
 class HostExplicit(C.Structure):
     _fields_ = [("theta_in", C.c_void_p), ("noise", C.c_void_p), ("perms", C.c_void_p), ("losses_out", C.c_void_p), ("theta_out", C.c_void_p),
                 ("obs_mean", C.c_void_p), ("obs_var", C.c_void_p), ("obs_count", C.c_void_p),
-                ("ret_mean", C.c_void_p), ("ret_var", C.c_void_p), ("ret_count", C.c_void_p), ("reward_curve", C.c_void_p)]
+                ("ret_mean", C.c_void_p), ("ret_var", C.c_void_p), ("ret_count", C.c_void_p), ("reward_curve", C.c_void_p),
+                ("count_names", C.c_void_p), ("counts", C.c_void_p), ("n_counts", C.c_void_p)]
 
 
 def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, lr=3.93141e-4, cliprange=0.161023, gamma=0.99, lam=0.95,
@@ -105,11 +106,13 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic"):
+                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
-    PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "generic" (the default): without."""
+    PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "generic" (the default): without.
+    compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD.
+    "kernel_counts": the handle's ppo_kernel_counts after the run."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -123,11 +126,15 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     a.obs_dim, a.act_dim = obs_dim, act_dim
     a.cliprange_vf = cliprange_vf
     a.discrete_kernels = _discrete_kernels(discrete_kernels)
+    a.compute_dtype = int(compute_dtype)
     out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32)}
-    x = HostExplicit(None, None, None, out["losses"].ctypes.data, None, None, None, None, None, None, None, out["reward_curve"].ctypes.data)
+    names = ((C.c_char * 32) * 64)(); cnt = (C.c_longlong * 64)(); ncnt = C.c_int(0)
+    x = HostExplicit(None, None, None, out["losses"].ctypes.data, None, None, None, None, None, None, None, out["reward_curve"].ctypes.data,
+                     C.addressof(names), C.addressof(cnt), C.addressof(ncnt))
     r = HostResult()
     if lib.ppo_host_learn_explicit(C.byref(a), C.byref(x), C.byref(r)) != 0:
         raise RuntimeError(r.error.decode())
+    out["kernel_counts"] = {names[i].value.decode(): int(cnt[i]) for i in range(ncnt.value)}
     out["env_steps_per_s"] = r.env_steps_per_s
     return out
 
@@ -161,11 +168,11 @@ def learn_time_limit(n_envs, n_steps, hidden, n_updates, nminibatches, noptepoch
 
 
 def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic"):
+                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0):
     """PPO2::learn on MaskedTargetEnv x n_envs (host/env/env_mock.hpp: DiscreteTargetEnv's task with about half of the categories forbidden at every step) behind
     VecEnv + EnvNormalize, with the library's own exploration noise and shuffles (ppo_host_learn_masked).  PPO2 finds the IActionMask mixin and masks by itself.
     Returns the mean un-normalised reward of every update's rollout [n_updates], the count of forbidden actions the environments received over the whole run, and
-    n_playback deterministic playback actions with their legality.  discrete_kernels: as in learn_curve."""
+    n_playback deterministic playback actions with their legality.  discrete_kernels, compute_dtype: as in learn_curve."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -179,6 +186,7 @@ def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, l
     a.obs_dim, a.act_dim = obs_dim, act_dim
     a.cliprange_vf = cliprange_vf
     a.discrete_kernels = _discrete_kernels(discrete_kernels)
+    a.compute_dtype = int(compute_dtype)
     out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros(n_playback, np.float32), "playback_legal": np.zeros(n_playback, np.float32)}
     forbidden = C.c_longlong(-1)
     r = HostResult()
