@@ -34,6 +34,7 @@ extern "C" {
 #endif
 
 #define PPO_MAX_LAYERS 8
+#define PPO_MAX_COMPONENTS 16
 #define PPO_ABI_VERSION 3
 
 typedef struct ppo_handle ppo_handle;
@@ -100,7 +101,33 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
 #define PPO_ACT_SHAPE_KERNELS 0x100
 #define PPO_ACT_BF16_HEAD 0x200
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out);
-int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL */
+int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_CATEGORICAL */
+/* ---- multi-categorical head: several independent choices per step (stable-baselines' MultiCategoricalProbabilityDistribution; env side: a multi-discrete space) ----
+ * K components over ONE logits vector l = h_L W_pi + b_pi of width A = cfg->act_dim = n_0 + .. + n_{K-1}; component k owns columns S_k = [o_k, o_k + n_k), o_k the
+ * running sum of the widths before it.  Tensor list, flat vector, orthogonal init and checkpoint tensors are those of a categorical handle with act_dim = A (4L+4
+ * tensors, no pi/logstd).  An action is K floats per row, column k = the index WITHIN component k, in [0, n_k): every buffer that holds action rows is K wide
+ * (ppo_step / ppo_act_deterministic [n,K], ppo_train_step actions [n,K], ppo_rollout_act actions_out [E,K], rollout field 1 [T,E,K]).  Noise stays [n,A] uniforms,
+ * column j perturbs logit j; the counter draw stays keyed by (seed, global row, call counter, GLOBAL logit index j).  Per component, over its allowed set (all of it
+ * when unmasked), the arithmetic is the categorical head's:
+ *   sample a_k = argmax_{j in S_k} (l_j - log(-log u_j)) - o_k (lowest index on a tie), deterministic a_k = argmax_{j in S_k} l_j - o_k,
+ *   m_k = max l_j, z_k = sum exp(l_j - m_k), neglogp_k = log z_k - (l_{a_k} - m_k), H_k = sum p_j (log z_k - (l_j - m_k));
+ *   neglogp = sum_k neglogp_k and entropy = sum_k H_k, added in component order starting from the first component's value; the surrogate, value loss, approxkl and
+ *   clipfrac see the row's total neglogp;  d logits_j = d_nlp (p_j - [j == o_k + a_k]) + ent_coef g p_j (log p_j + H_k) with H_k of j's OWN component.
+ * A handle with ONE component nvec = {A} gives the SAME BITS as a PPO_ACT_CATEGORICAL handle with act_dim = A in every output.
+ * Masks are [n, A] as for the categorical head and exclude per component; a row of ones gives the unmasked bits.  The host checks (before anything is uploaded;
+ * each message names row and component): every COMPONENT of every mask row allows a category; a ppo_train_step_masked row's action k is allowed by its
+ * component's mask; every action value of ppo_train_step / of an uploaded rollout field 1 is an integer in [0, n_k).
+ * Runs the generic PPO_F32 kernel family only (never the narrow, train8 or bf16 forms).  ppo_kernel_counts names, counted INSTEAD of the <cat> ones:
+ * "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>".  Data parallel and both shuffles work as
+ * for a categorical PPO_F32 handle.
+ * Errors of ppo_create_multi, each naming the limit: n_components outside 1..PPO_MAX_COMPONENTS, a component with fewer than 2 categories, cfg->act_dim != sum of
+ * nvec, compute_dtype PPO_BF16.  ppo_create_ex(cfg, PPO_ACT_MULTI_CATEGORICAL, ..) stays an "unknown action_dist" error: the table has to come with the call. */
+#define PPO_ACT_MULTI_CATEGORICAL 2
+int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out);
+/* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian handle, 1 with nvec[0] = A for a categorical one */
+int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec);
+/* columns of one action row: A (Gaussian), 1 (categorical) or K (multi-categorical) */
+int ppo_action_width(const ppo_handle* h);
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);
@@ -158,7 +185,7 @@ int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* act
  * the mask comes from the host (the three calls below, ppo_rollout_act_masked, ppo_rollout_upload of field 8), and a ppo_train_step_masked row whose action
  * its own mask forbids.  ppo_update has no host check: if the rollout's action field was uploaded inconsistently with its mask field, the loss values of
  * such a row are unspecified (the kernels still read and write inside their buffers and terminate).
- * The three calls need a categorical handle (a Gaussian handle, PPO_F32 or PPO_BF16: an error); mask == NULL is the unmasked call, the same launch. */
+ * The three calls need a categorical or multi-categorical handle (a Gaussian handle, PPO_F32 or PPO_BF16: an error); mask == NULL is the unmasked call, the same launch. */
 int ppo_step_masked(ppo_handle* h, const float* obs, int32_t n, const float* noise, const float* mask, float* action, float* value,
                     float* neglogp);
 int ppo_act_deterministic_masked(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* action);
@@ -276,7 +303,7 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam);
 /* The seeded device env has no notion of legality either: on a masking handle ppo_collect_synthetic samples unmasked and records every row's mask as ones. */
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first,
                           const float* noise, float gamma, float lam);
-/* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]); a categorical handle's field 1 is [T,E].
+/* field: 0 obs[T,E,O] 1 actions[T,E,A] 2 values 3 neglogp 4 dones 5 rewards 6 returns (all [T,E]); a categorical handle's field 1 is [T,E], a multi-categorical one's [T,E,K].
  * 7 (download only; an upload is refused): terminal values [T,E] as the last ppo_rollout_finish used them -- V(terminal observation) on the marked rows, 0 elsewhere,
  * all zeros when that finish had no marks.
  * 8: action masks [T,E,A] of a masking handle (refused with masking off; an uploaded row without an allowed category is refused). */

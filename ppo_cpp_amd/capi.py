@@ -54,7 +54,8 @@ def _f32(a, shape=None):
     return a
 
 
-ACTION_DISTS = {"gaussian": 0, "categorical": 1}        # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL
+ACTION_DISTS = {"gaussian": 0, "categorical": 1, "multi_categorical": 2}   # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL / PPO_ACT_MULTI_CATEGORICAL
+MAX_COMPONENTS = 16                                     # PPO_MAX_COMPONENTS
 ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS, OR-ed into ppo_create_ex's action_dist
 ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, likewise
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
@@ -73,7 +74,11 @@ class PPOHip:
     matrix-core path with a categorical head (at most 128 categories; masks included; no data parallel).  Without it that combination is
     refused; on a compute_dtype=0 or Gaussian handle it changes nothing.
 
-    Action masks (categorical only; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
+    action_dist="multi_categorical", nvec=[n_0, .., n_{K-1}] (ppo_create_multi): K independent categorical components over sum(nvec) logits;
+    act_dim may be None or must equal sum(nvec).  Actions are (n, K) float arrays, column k the index within component k; noise and masks keep
+    their (n, A) shape with A = sum(nvec).  `.nvec` reads the widths back from the handle (ppo_action_nvec).
+
+    Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
     and update() train under them."""
 
@@ -81,7 +86,18 @@ class PPOHip:
     MASK_FIELDS = {"masks": 8}                  # [T, E, A]; a masking handle only (set_action_masking)
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
-    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, **overrides):
+    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, **overrides):
+        multi = action_dist == "multi_categorical"
+        if nvec is not None and not multi:
+            raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
+        if multi:
+            if nvec is None:
+                raise ValueError("action_dist='multi_categorical' needs nvec")
+            nvec = [int(x) for x in nvec]
+            if act_dim is None:
+                act_dim = sum(nvec)
+            elif act_dim != sum(nvec):
+                raise ValueError("act_dim %r is not sum(nvec) = %d" % (act_dim, sum(nvec)))
         self.lib = load_library()
         cfg = PPOConfig()
         hid = (C.c_int32 * len(hidden))(*hidden)
@@ -96,9 +112,13 @@ class PPOHip:
         self.action_dist = action_dist
         self.shape_kernels = bool(shape_kernels)
         self.bf16_head = bool(bf16_head)
-        self._act_shape = (act_dim,) if action_dist == "gaussian" else ()      # per row
+        self._act_shape = (act_dim,) if action_dist == "gaussian" else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
-        if self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0), C.byref(h)) != 0:
+        if multi:
+            nv = (C.c_int32 * max(len(nvec), 1))(*nvec)
+            if self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h)) != 0:
+                raise PPOHipError(self.lib.ppo_last_error(None).decode())
+        elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)
@@ -110,6 +130,17 @@ class PPOHip:
             self.tensors.append((name.value.decode(), (r.value, c.value) if c.value else (r.value,)))
         self.E = self.T = 0
         self.world, self._global_shuffle = 1, False
+
+    @property
+    def nvec(self):
+        """component widths as the handle reports them (ppo_action_nvec): [] Gaussian, [A] categorical, the K widths multi-categorical"""
+        out = (C.c_int32 * MAX_COMPONENTS)()
+        k = self.lib.ppo_action_nvec(self.h, MAX_COMPONENTS, out)
+        return [int(out[i]) for i in range(max(k, 0))]
+
+    @property
+    def action_width(self):
+        return int(self.lib.ppo_action_width(self.h))
 
     def close(self):
         if getattr(self, "h", None):
@@ -196,8 +227,8 @@ class PPOHip:
     def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v, mask=None):
         arrs = [_f32(x) for x in (obs, actions, advs, returns, old_nlp, old_v)]
         n = arrs[0].shape[0]
-        if self.action_dist == "categorical":
-            arrs[1] = _f32(arrs[1], (n,))
+        if self.action_dist != "gaussian":
+            arrs[1] = _f32(arrs[1], (n,) + self._act_shape)
         losses = np.empty(5, np.float32)
         if mask is not None:
             arrs.insert(2, _f32(mask, (n, self.A)))

@@ -63,7 +63,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_POLICY_STEP, KV_ROLLOUT1, KV_ROLLOUT_PERSISTENT, KV_ROLLOUT_COOP, KV_COLLECT_FUSED, KV_BF16_TRAIN, KV_BF16_STEP, KV_BF16_REDUCE_ADAM, KV_NARROW_EPOCH,
                      KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_POLICY_STEP_CAT_MASK, KV_TRAIN_FB_CAT_MASK, KV_STEP_HOST_ACTION,
                      KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK,
-                     KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_COUNT };
+                     KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK,
+                     KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -75,7 +76,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a categorical handle created with PPO_ACT_SHAPE_KERNELS on a narrow shape (static and runtime-shape instantiations share a name)
                                        "narrow_step_kernel<cat>", "narrow_step_kernel<cat,mask>", "narrow_train_kernel<cat>", "narrow_train_kernel<cat,mask>",
                                        // a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence"
-                                       "bf16_step_sequence<cat>", "bf16_step_sequence<cat,mask>", "bf16_train_sequence<cat>", "bf16_train_sequence<cat,mask>"};
+                                       "bf16_step_sequence<cat>", "bf16_step_sequence<cat,mask>", "bf16_train_sequence<cat>", "bf16_train_sequence<cat,mask>",
+                                       // a multi-categorical handle (ppo_create_multi): counted INSTEAD of the <cat> names of the generic fp32 family
+                                       "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -105,7 +108,8 @@ struct ppo_handle {
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical handle may take the narrow family (build_narrow_layout)
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
-    int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian) or 1 (categorical: the category index)
+    int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian), 1 (categorical: the category index) or K (multi-categorical)
+    CompTable comp{};                 // multi-categorical (ppo_create_multi): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
     // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
     bool masking = false;
@@ -433,10 +437,10 @@ int build_layout(ppo_handle* h) {
     n.bv_off = op;  add_tensor(h, "vf/b", 1, 0, 1, bf ? n.Ap : 1, od, op);
     add_tensor(h, "pi/w", HL, n.A, HpL, n.Ap, od, op, !bf); n.wmu_off = h->tensors.back().off_pad;
     n.bmu_off = op; add_tensor(h, "pi/b", n.A, 0, 1, n.Ap, od, op);
-    // categorical: the logstd slot stays in the padded vector (the weight-gradient, reduce and Adam kernels keep their layout) but is no tensor:
+    // categorical and multi-categorical: the logstd slot stays in the padded vector (the weight-gradient, reduce and Adam kernels keep their layout) but is no tensor:
     // no gradient source, so its gradient is 0 and Adam never moves it; it is not in the tensor list, the flat vector or a checkpoint
     n.ls_off = op;
-    if (h->dist == PPO_ACT_CATEGORICAL) op += ru(n.Ap, 256);
+    if (h->dist != PPO_ACT_GAUSSIAN) op += ru(n.Ap, 256);
     else add_tensor(h, "pi/logstd", 1, n.A, 1, n.Ap, od, op);
     h->P_dense = od; h->P_pad = op; h->n_blocks = op / 256;
     // transposed copies streamed by the backward pass
@@ -1077,13 +1081,15 @@ static bool nw_cat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT
 static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
 
 // policy_step_kernel: the (CT, KS, CTH, WIDE) ladder of the handle's layout, once; the caller picks the head
-template <bool CAT, bool MASK>
+template <bool CAT, bool MASK, bool MULTI = false>
 void launch_step_t(ppo_handle* h, const StepArgs& a0) {
-    StepArgs a = a0;
+    std::conditional_t<MULTI, StepArgsM, StepArgs> a;
+    static_cast<StepArgs&>(a) = a0;
+    if constexpr (MULTI) a.comp = h->comp;                          // (the component table rides behind the arguments every other head takes)
     const dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
     SET_STAMPS(a.stamps, grid.x <= 256, 4096 * 44);
     const size_t lds = (size_t)h->lds_step_total * sizeof(float);
-#define X(CT, KS, CTH, WIDE) hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT, MASK>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, a)
+#define X(CT, KS, CTH, WIDE) hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT, MASK, MULTI>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, a)
     if (h->net.wide) { if (h->CT == 4) X(4, 2, 0, true); else X(1, 1, 0, true); }
     else if (h->CT == 4 && h->CTH == 2) X(4, 2, 2, false);
     else if (h->CT == 4) X(4, 2, 0, false);
@@ -1102,16 +1108,19 @@ void launch_narrow_step(ppo_handle* h, const StepArgs& a) {
 #undef X
 }
 int launch_step(ppo_handle* h, const StepArgs& a) {
+    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (never bf16, never narrow: ppo_create_multi, build_narrow_layout)
     const bool cat = h->dist == PPO_ACT_CATEGORICAL;
-    if (a.mask && !cat) return fail(h, "policy step: an action mask needs a categorical handle");
+    if (a.mask && !cat && !multi) return fail(h, "policy step: an action mask needs a categorical handle");
     if (h->bf.on) { ++h->kv[a.mask ? KV_BF16_STEP_CAT_MASK : cat ? KV_BF16_STEP_CAT : KV_BF16_STEP]; return launch_step_bf16(h, a); }
     ProfScope ps(h, PK_STEP);
     if (h->narrow) {                                              // (a categorical handle here: created with PPO_ACT_SHAPE_KERNELS)
         ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : cat ? KV_NARROW_STEP_CAT : h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP];
         if (a.mask) launch_narrow_step<true, true>(h, a); else if (cat) launch_narrow_step<true, false>(h, a); else launch_narrow_step<false, false>(h, a);
     } else {
-        ++h->kv[a.mask ? KV_POLICY_STEP_CAT_MASK : cat ? KV_POLICY_STEP_CAT : KV_POLICY_STEP];
-        if (a.mask) launch_step_t<true, true>(h, a); else if (cat) launch_step_t<true, false>(h, a); else launch_step_t<false, false>(h, a);
+        if (multi) ++h->kv[a.mask ? KV_POLICY_STEP_MCAT_MASK : KV_POLICY_STEP_MCAT];
+        else ++h->kv[a.mask ? KV_POLICY_STEP_CAT_MASK : cat ? KV_POLICY_STEP_CAT : KV_POLICY_STEP];
+        if (multi) { if (a.mask) launch_step_t<true, true, true>(h, a); else launch_step_t<true, false, true>(h, a); }
+        else if (a.mask) launch_step_t<true, true>(h, a); else if (cat) launch_step_t<true, false>(h, a); else launch_step_t<false, false>(h, a);
     }
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1453,10 +1462,13 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
 }
 
 // train_fwd_bwd_kernel: the (CT, KS, CTH, WIDE, EARLY) ladder of the handle's layout, once; the caller picks the head
-template <bool CAT, bool MASK>
-static void launch_train_fb(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+template <bool CAT, bool MASK, bool MULTI = false>
+static void launch_train_fb(ppo_handle* h, dim3 grid, const TrainArgs& ta0) {
     const size_t lds = (size_t)h->net.lds_total * sizeof(float);
-#define X(CT, KS, CTH, WIDE, EARLY) hipLaunchKernelGGL((train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, CAT, MASK>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, ta)
+    std::conditional_t<MULTI, TrainArgsM, TrainArgs> ta;
+    static_cast<TrainArgs&>(ta) = ta0;
+    if constexpr (MULTI) ta.comp = h->comp;
+#define X(CT, KS, CTH, WIDE, EARLY) hipLaunchKernelGGL((train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, CAT, MASK, MULTI>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, ta)
     if (h->net.wide) { if (h->CT == 4) X(4, 2, 0, true, false); else X(1, 1, 0, true, false); }
     else if (h->CT == 4 && h->CTH == 2 && h->early) X(4, 2, 2, false, true);
     else if (h->CT == 4 && h->CTH == 2) X(4, 2, 2, false, false);
@@ -1470,8 +1482,11 @@ static int enqueue_train_fb(ppo_handle* h, const TrainArgs& ta, int n_pad) {
     ProfScope ps(h, PK_TRAIN_FB);
     const dim3 grid(n_pad / ROWS_PER_BLOCK, 2);
     const bool cat = h->dist == PPO_ACT_CATEGORICAL;              // (a mask: a categorical handle, the entry points check; t8: Gaussian and not wide, ppo_create_ex)
-    ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : cat ? KV_TRAIN_FB_CAT : h->t8 ? KV_TRAIN8 : KV_TRAIN_FB];
-    if (ta.mask) launch_train_fb<true, true>(h, grid, ta);
+    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;
+    if (multi) ++h->kv[ta.mask ? KV_TRAIN_FB_MCAT_MASK : KV_TRAIN_FB_MCAT];
+    else ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : cat ? KV_TRAIN_FB_CAT : h->t8 ? KV_TRAIN8 : KV_TRAIN_FB];
+    if (multi) { if (ta.mask) launch_train_fb<true, true, true>(h, grid, ta); else launch_train_fb<true, false, true>(h, grid, ta); }
+    else if (ta.mask) launch_train_fb<true, true>(h, grid, ta);
     else if (cat) launch_train_fb<true, false>(h, grid, ta);
     else if (h->t8) launch_train8(h, grid, ta);
     else launch_train_fb<false, false>(h, grid, ta);
@@ -1674,7 +1689,39 @@ const char* ppo_last_error(const ppo_handle* h) { return h ? h->err.c_str() : g_
 
 int ppo_create(const ppo_config* cfg, ppo_handle** out) { return ppo_create_ex(cfg, PPO_ACT_GAUSSIAN, out); }
 
-int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) {
+static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, ppo_handle** out);
+
+int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) { return create_handle(cfg, action_dist, nullptr, 0, out); }
+
+// K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns
+int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out) {
+    if (!cfg || !out) return fail(nullptr, "ppo_create_multi: null argument");
+    *out = nullptr;
+    if (n_components < 1 || n_components > PPO_MAX_COMPONENTS)
+        return fail(nullptr, "ppo_create_multi: n_components must be 1..%d (PPO_MAX_COMPONENTS), got %d", PPO_MAX_COMPONENTS, (int)n_components);
+    if (!nvec) return fail(nullptr, "ppo_create_multi: null nvec");
+    int64_t sum = 0;
+    for (int k = 0; k < n_components; ++k) {
+        if (nvec[k] < 2) return fail(nullptr, "ppo_create_multi: component %d has %d categories (every component needs at least 2)", k, (int)nvec[k]);
+        sum += nvec[k];
+    }
+    if (sum != cfg->act_dim) return fail(nullptr, "ppo_create_multi: act_dim %d is not the sum of nvec (%lld)", (int)cfg->act_dim, (long long)sum);
+    if (cfg->compute_dtype == PPO_BF16)
+        return fail(nullptr, "ppo_create_multi: compute_dtype PPO_BF16 is not supported (the multi-categorical head runs on the PPO_F32 path)");
+    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL, nvec, n_components, out);
+}
+
+int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {
+    if (!h) return -1;
+    if (h->dist == PPO_ACT_GAUSSIAN) return 0;
+    if (h->dist == PPO_ACT_CATEGORICAL) { if (max > 0 && nvec) nvec[0] = h->net.A; return 1; }
+    for (int k = 0; k < h->comp.K && k < max && nvec; ++k) nvec[k] = h->comp.off[k + 1] - h->comp.off[k];
+    return h->comp.K;
+}
+int ppo_action_width(const ppo_handle* h) { return h ? h->Aw : -1; }
+
+// nvec != null: a multi-categorical handle (ppo_create_multi has checked the table)
+static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, ppo_handle** out) {
     if (!cfg || !out) return fail(nullptr, "ppo_create: null argument");
     *out = nullptr;
     if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
@@ -1682,8 +1729,9 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the two flags; whatever else is left must be a distribution
     const bool bf16_head = (action_dist & PPO_ACT_BF16_HEAD) != 0;
     action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD);
-    if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL)
-        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD)", (int)action_dist);
+    if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD; "
+                             "a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && !bf16_head)
@@ -1700,7 +1748,11 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
     h->dist = action_dist;
     h->shape_kernels = shape_kernels && action_dist == PPO_ACT_CATEGORICAL;       // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
-    h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : cfg->act_dim;
+    h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : action_dist == PPO_ACT_MULTI_CATEGORICAL ? n_components : cfg->act_dim;
+    if (action_dist == PPO_ACT_MULTI_CATEGORICAL) {
+        h->comp.K = n_components;
+        for (int k = 0; k < n_components; ++k) h->comp.off[k + 1] = h->comp.off[k] + nvec[k];
+    }
     int dev = cfg->device;
     if (dev < 0) { const char* lr = getenv("LOCAL_RANK"); dev = lr ? atoi(lr) % ndev : 0; }
     h->device = dev;
@@ -1742,6 +1794,15 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
         set_lds((const void*)policy_step_kernel<1, 1, 0, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false, false, true, true>);
         set_lds((const void*)policy_step_kernel<4, 2, 0, true, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true, false, true, true>);
         set_lds((const void*)policy_step_kernel<1, 1, 0, true, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true, false, true, true>);
+    }
+    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {
+        // every (CT, KS, CTH, WIDE[, EARLY]) combination of launch_step_t / launch_train_fb, unmasked and masked
+#define XS(CT, KS, CTH, WIDE) do { set_lds((const void*)policy_step_kernel<CT, KS, CTH, WIDE, true, false, true>); set_lds((const void*)policy_step_kernel<CT, KS, CTH, WIDE, true, true, true>); } while (0)
+#define XT(CT, KS, CTH, WIDE, EARLY) do { set_lds((const void*)train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, true, false, true>); set_lds((const void*)train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, true, true, true>); } while (0)
+        XS(4, 2, 2, false); XS(4, 2, 0, false); XS(1, 1, 0, false); XS(4, 2, 0, true); XS(1, 1, 0, true);
+        XT(4, 2, 2, false, true); XT(4, 2, 2, false, false); XT(4, 2, 0, false, false); XT(1, 1, 0, false, false); XT(4, 2, 0, true, false); XT(1, 1, 0, true, false);
+#undef XS
+#undef XT
     }
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
@@ -2013,6 +2074,18 @@ int ppo_seed(ppo_handle* h, uint64_t seed) {
 // range-checked), its own action.  `who` names the entry point in the message.
 static int check_masks(ppo_handle* h, const char* who, const float* mask, size_t rows, const float* actions) {
     const size_t A = (size_t)h->net.A;
+    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {                      // the same two rules per component; actions [rows, K] hold the index within the component
+        const CompTable& c = h->comp;
+        for (size_t i = 0; i < rows; ++i)
+            for (int k = 0; k < c.K; ++k) {
+                bool any = false;
+                for (int j = c.off[k]; j < c.off[k + 1]; ++j) any = any || mask[i * A + j] != 0.f;
+                if (!any) return fail(h, "%s: mask row %lld allows no category of component %d", who, (long long)i, k);
+                if (actions && mask[i * A + c.off[k] + (size_t)actions[i * c.K + k]] == 0.f)
+                    return fail(h, "%s: row %lld, component %d: action %d is forbidden by the row's own mask", who, (long long)i, k, (int)actions[i * c.K + k]);
+            }
+        return 0;
+    }
     for (size_t i = 0; i < rows; ++i) {
         bool any = false;
         for (size_t j = 0; j < A; ++j) any = any || mask[i * A + j] != 0.f;
@@ -2022,8 +2095,20 @@ static int check_masks(ppo_handle* h, const char* who, const float* mask, size_t
     }
     return 0;
 }
+// every action value of a multi-categorical handle's rows [rows, K] is an integer in [0, n_k)
+static int check_multi_actions(ppo_handle* h, const char* who, const float* actions, size_t rows) {
+    const CompTable& c = h->comp;
+    for (size_t i = 0; i < rows; ++i)
+        for (int k = 0; k < c.K; ++k) {
+            const float x = actions[i * c.K + k];
+            const int nk = c.off[k + 1] - c.off[k];
+            if (!(x >= 0.f && x < (float)nk && x == floorf(x)))
+                return fail(h, "%s: row %lld, component %d: action %g is not a category index in [0, %d)", who, (long long)i, k, (double)x, nk);
+        }
+    return 0;
+}
 static int need_categorical(ppo_handle* h, const char* who) {
-    if (h->dist != PPO_ACT_CATEGORICAL) return fail(h, "%s: action masks need a categorical (PPO_ACT_CATEGORICAL) handle", who);
+    if (h->dist != PPO_ACT_CATEGORICAL && h->dist != PPO_ACT_MULTI_CATEGORICAL) return fail(h, "%s: action masks need a categorical (PPO_ACT_CATEGORICAL) handle", who);
     return 0;
 }
 // staging buffer of the host-pointer calls' masks: allocated by the first masked call, so that a handle that never passes a mask allocates what it always did
@@ -2114,6 +2199,7 @@ int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float*
     ENTER_Q(h);
     if (n < 2) return fail(h, "ppo_train_step: n=%d (the reference asserts more than one row, ppo2.hpp:402)", n);
     if (mask && need_categorical(h, "ppo_train_step_masked")) return -1;
+    if (h->dist == PPO_ACT_MULTI_CATEGORICAL && check_multi_actions(h, "ppo_train_step", actions, (size_t)n)) return -1;
     if (h->dist == PPO_ACT_CATEGORICAL)
         for (int32_t i = 0; i < n; ++i) {
             const float x = actions[i];
@@ -3140,6 +3226,7 @@ int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count
     float* p = rollout_field(h, field, &c);
     if (!p || (size_t)count != c) return fail(h, "ppo_rollout_upload: bad field/count");
     if (field == 8 && check_masks(h, "ppo_rollout_upload", src, (size_t)h->E * h->T, nullptr)) return -1;
+    if (field == 1 && h->dist == PPO_ACT_MULTI_CATEGORICAL && check_multi_actions(h, "ppo_rollout_upload", src, (size_t)h->E * h->T)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     HIP_OK(h, hipMemcpy(p, src, c * sizeof(float), hipMemcpyHostToDevice));
     return 0;
@@ -3263,7 +3350,8 @@ static int enqueue_epoch_gather(ppo_handle* h, int nmb) {
     ProfScope ps(h, PK_EPOCH);
     const int B = h->E * h->T, M = B / nmb;
     const GatherArgs ga = gather_args(h, M);
-    // (epoch_gather4_kernel copies no masks: a masking handle is categorical, its action rows are one float, so it never qualifies -- and must not)
+    // (epoch_gather4_kernel copies no masks: !masking keeps a masking handle off it.  A categorical handle's action rows are one float and never qualify; an unmasked
+    // multi-categorical handle whose K is a multiple of 4 does, like a Gaussian one)
     const bool wide4 = h->net.O % 4 == 0 && h->Aw % 4 == 0 && !h->masking;
     // bf16 path: the epoch's observations become bf16 once; a minibatch is then a row slice.  With 16-byte rows the gather writes them itself
     const bool fuse_stage = wide4 && h->bf.on && M % GB_PAD == 0 && h->bf.xe_rows >= B && h->net.Kp0 % 4 == 0 && !global_shuffle_on(h);

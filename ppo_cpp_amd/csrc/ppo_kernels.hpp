@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "ppo_peer.hpp"      // PeerDev: the data-parallel statistics exchange rides in norm_batch_kernel / norm_finalize_kernel
 
@@ -657,23 +658,25 @@ struct ObsNorm { const float* mean; const float* var; float eps; float clip; int
 // train kernel, the rows' actions and scalars -- is fetched with ALL loads issued before the first LDS store, i.e. in
 // ONE memory round trip (separate load->store loops cost one dependent round trip each, ~1 us apiece, and each wait
 // also drains the in-order queue behind the weight prefetch).
-struct RowScalars { const float* actions; const float* v0a; const float* v0b; const float* v1; const float* stats; int mode; };
+struct RowScalars { const float* actions; const float* v0a; const float* v0b; const float* v1; const float* stats; int mode; int acols; };
 // mode 0: none ; 1 (policy): v0 = advs[src] (v0b null) or ((v0a - v0b) - stats[0]) / stats[1], v1 = old_neglogp
 // mode 2 (value) : v0 = returns, v1 = old_values
+// acols: action columns per row of the multi-categorical head (HEAD == 2 only: one category index per component)
 
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 
 // `after_issue` runs right after this block's loads have been issued and before the first of them is consumed: loads the
 // caller issues there queue BEHIND the inputs (the inputs are needed first) but ahead of the wait, so they are in flight
 // during the staging round trip.
-// CAT: the categorical head's actions, ONE column per row (the category index), land in column 0 of the action tile
-template <bool CAT = false, class Hook = NoHook>
+// HEAD 1: the categorical head's actions, ONE column per row (the category index), land in column 0 of the action tile
+// HEAD 2: the multi-categorical head's, rs.acols columns per row (the index within each component), in the row's first columns
+template <int HEAD = 0, class Hook = NoHook>
 __device__ __forceinline__ void stage_block_inputs(const NetDev& net, const float* __restrict__ par_src, float* par, float* Xs, int ldx,
                                                    const float* __restrict__ obs, int row0, int nrows,
                                                    ObsNorm nz, float* __restrict__ obs_out, float* __restrict__ x0g, RowScalars rs,
                                                    float* acts, float* rowv, Hook&& after_issue = Hook()) {
     const int tid = threadIdx.x;
-    const int Kp0 = net.Kp0, O = net.O, A = CAT ? 1 : net.A, Ap = net.Ap;
+    const int Kp0 = net.Kp0, O = net.O, A = HEAD == 1 ? 1 : HEAD == 2 ? rs.acols : net.A, Ap = net.Ap;
     constexpr int PK = 4, OK = 2, AK = 2;
     float pv[PK], ov[OK], av[AK], r0 = 0.f, r1 = 0.f, r2 = 0.f, s0 = 0.f, s1 = 1.f;
     // element i = tid + 256 k of a [16][W] tile is (row, col) = (i / W, i % W): one division per tile width instead of
@@ -810,6 +813,11 @@ struct StepArgs {
     unsigned long long* stamps;   // diagnostic builds only: [tower][block][8]
 #endif
 };
+// Component table of the multi-categorical head: component k owns logits [off[k], off[k + 1]) of the row; off[0] = 0, off[K] = A.  It travels in the kernel
+// arguments of the <.., MULTI> instantiations only (wave-uniform: scalar loads), behind the struct every other instantiation takes unchanged.
+#define PPO_MAX_COMPONENTS_DEV 16
+struct CompTable { int K; int off[PPO_MAX_COMPONENTS_DEV + 1]; };
+struct StepArgsM : StepArgs { CompTable comp; };
 #ifdef PPO_STAMPS
 #define PSTAMP(i) do { if (a.stamps && threadIdx.x == 0) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -820,12 +828,18 @@ struct StepArgs {
 // (the category index), `noise` holds the uniforms u [n,A] of the Gumbel-argmax draw, det_action = argmax of the logits
 // MASK (with CAT): a.mask [n,A] takes the forbidden categories (0) out of both argmaxes and of the normaliser -- excluded, not pushed down by a constant.  The lane
 // that owns category j reads mask[row][j] beside its logit; the lane loops and butterflies are the unmasked ones, so a row of ones gives the unmasked bits.
-template <int CT, int KS, int CTH, bool WIDE, bool CAT = false, bool MASK = false>
-__global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev net, StepArgs a) {
+// MULTI (with CAT): K independent categorical components over the one logits row (stable-baselines MultiCategoricalProbabilityDistribution).  The row's 16 lanes
+// walk the components one after another -- lane `part` owns columns off[k] + part, + 16, .. of component k -- with the categorical arithmetic and first-index rules
+// per component ("none yet" of the masked form = one past the component's end); the action is K floats per row (the index WITHIN each component), neglogp the sum
+// over the components in component order starting from the first one's value, so that one component gives the categorical bits.  Noise and counter draw stay
+// keyed by the global logit index j.
+template <int CT, int KS, int CTH, bool WIDE, bool CAT = false, bool MASK = false, bool MULTI = false>
+__global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev net, std::conditional_t<MULTI, StepArgsM, StepArgs> a) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     PSTAMP(0);
-    warm_kernargs<sizeof(NetDev) + sizeof(StepArgs)>();
+    warm_kernargs<sizeof(NetDev) + sizeof(a)>();
     const int tower = blockIdx.y;
     if (tower == 1 && !a.value) return;
     if (tower == 0 && !a.action && !a.det_action && !a.neglogp && !a.obs_out) return;
@@ -867,7 +881,48 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
     // sampling + neglogp (G:5894-6672): 16 lanes per row, each lane owns actions j = part, part+16, ...
     const int r = threadIdx.x >> 4, part = threadIdx.x & 15;
     const int row = row0 + r;
-    if constexpr (CAT) {
+    if constexpr (MULTI) {
+        float nlp = 0.f, my_a = 0.f, my_d = 0.f;                         // lane k of the row keeps component k's two indices until every logit has been read
+        for (int k = 0; k < a.comp.K; ++k) {
+            const int o = a.comp.off[k], e = a.comp.off[k + 1];
+            float bp = -INFINITY, bl = -INFINITY;
+            int ip = MASK ? e : o, il = MASK ? e : o;
+            for (int j = o + part; j < e; j += 16) {
+                const float l = mus[r * ldm + j];
+                float u = 0.5f;
+                if (row < a.n) u = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+                const float pl = l - logf(-logf(u));
+                if constexpr (MASK) {
+                    const bool mk = row < a.n ? a.mask[(size_t)row * net.A + j] != 0.f : true;
+                    if (mk && (pl > bp || ip == e)) { bp = pl; ip = j; }
+                    if (mk && (l > bl || il == e)) { bl = l; il = j; }
+                } else {
+                    if (pl > bp) { bp = pl; ip = j; }
+                    if (l > bl) { bl = l; il = j; }
+                }
+            }
+            group16_argmax(bp, ip);
+            group16_argmax(bl, il);
+            if constexpr (MASK) { ip = min(ip, e - 1); il = min(il, e - 1); }
+            const float m = bl;
+            float z = 0.f;
+            for (int j = o + part; j < e; j += 16) {
+                if constexpr (MASK) { if (row < a.n && a.mask[(size_t)row * net.A + j] == 0.f) continue; }
+                z += expf(mus[r * ldm + j] - m);
+            }
+            z = group16_sum(z);
+            const float la = mus[r * ldm + ip] - m;
+            const float nk = logf(z) - la;
+            nlp = k == 0 ? nk : nlp + nk;
+            if (part == k) { my_a = (float)(ip - o); my_d = (float)(il - o); }
+        }
+        if (part < a.comp.K && row < a.n) {
+            if (a.action) a.action[(size_t)row * a.comp.K + part] = my_a;
+            if (a.det_action) a.det_action[(size_t)row * a.comp.K + part] = my_d;
+        }
+        if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = nlp;
+        if (a.host_action && part < a.comp.K) lds[net.lds_mu + r * ldm + part] = my_a;   // (after every lane of the row has read the tile: one wave, program order)
+    } else if constexpr (CAT) {
         // a = argmax_j (l_j - log(-log u_j)), neglogp = log sum_j exp(l_j - m) - (l_a - m), m = max_j l_j (softmax cross-entropy against one_hot(a))
         // MASK: a lane's best index starts at net.A ("none yet"), so the first ALLOWED category is taken even when its perturbed logit is -inf (u == 0) and a
         // lane without an allowed category loses every tie of the butterfly to a real index; a row without any allowed category (which the host checks
@@ -932,7 +987,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
         // elements one by one.  Pinned host memory is uncached on the device: a store leaves for the host at once.  Every storing thread waits for
         // its stores to be acknowledged, the barrier collects the waves, then ONE word: the host reads the block only after that word shows host_seq.
         lds_barrier();
-        const int Aw = CAT ? 1 : net.A;                                  // action columns per row
+        int Aw = CAT ? 1 : net.A;                                        // action columns per row
+        if constexpr (MULTI) Aw = a.comp.K;
         const int live = min(ROWS_PER_BLOCK, a.n - row0) * Aw;          // elements of this block
         float* dst = a.host_action + (size_t)row0 * Aw;
         const float* tile = lds + net.lds_mu;
@@ -981,6 +1037,7 @@ struct TrainArgs {
     unsigned long long* stamps;  // diagnostic builds only (-DPPO_STAMPS): [blocks][16] s_memtime stamps
     int xcd_map;                 // workgroup -> (tower, row tile) placement, see the kernel (speed only)
 };
+struct TrainArgsM : TrainArgs { CompTable comp; };   // the <.., MULTI> instantiations' arguments
 
 // EARLY (18-obs / [256, 256-multiple] shape only: Kp0 == Ap == 16*KS, Hp[0] == Hp[L-1] == 256, L >= 2): the weights of the three
 // SMALL products -- first layer, policy head, policy head transposed, 32 registers each -- are requested at kernel entry
@@ -991,11 +1048,16 @@ struct TrainArgs {
 // MASK (with CAT): a.mask [n][A]; maximum, normaliser, neglogp and entropy run over the allowed categories, d logits of a forbidden one is exactly 0.  Same lane
 // loops and butterflies as the unmasked form (a row of ones gives its bits).  A row whose action its own mask forbids (only possible through inconsistent
 // device-resident fields) gives unspecified loss values; nothing is indexed with the action or the mask, so nothing leaves the tile.
-template <int CT, int KS, int CTH, bool WIDE, bool EARLY = false, bool CAT = false, bool MASK = false>
-__global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net, TrainArgs a) {
+// MULTI (with CAT): `actions` holds K floats per row (the index within each component, TrainArgsM::comp); neglogp and entropy are the sums of the components'
+// in component order starting from the first one's value; d logits of column j carries the entropy H_k of j's OWN component.  Two passes over the components:
+// the first forms every component's maximum, normaliser and entropy (lane k of the row keeps component k's), the second -- the row's d_nlp needs all of them --
+// hands them back to the row's lanes and writes the gradient.  One component gives the categorical bits.
+template <int CT, int KS, int CTH, bool WIDE, bool EARLY = false, bool CAT = false, bool MASK = false, bool MULTI = false>
+__global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net, std::conditional_t<MULTI, TrainArgsM, TrainArgs> a) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs)>();
+    warm_kernargs<sizeof(NetDev) + sizeof(a)>();
     // XCD-aware row mapping: workgroups are dealt round-robin over the 8 XCDs; giving XCD x the CONTIGUOUS row tiles
     // [x*G/8, (x+1)*G/8) makes the activations / gradients this kernel leaves in that XCD's L2 exactly the rows the
     // weight-gradient kernel's row split x (also on XCD x) streams next.  xcd_map 1 (weight_grad_assemble_kernel follows, 4 row
@@ -1026,7 +1088,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
     RowScalars rs;
     if (tower == 0) rs = RowScalars{a.actions, a.advs ? a.advs : a.returns, a.advs ? nullptr : a.old_values, a.old_neglogp, a.adv_stats, 1};
     else rs = RowScalars{nullptr, a.returns, nullptr, a.old_values, nullptr, 2};
-    stage_block_inputs<CAT>(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, nz, nullptr,
+    if constexpr (MULTI) rs.acols = a.comp.K;
+    stage_block_inputs<MULTI ? 2 : CAT ? 1 : 0>(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, nz, nullptr,
                        tower == 0 ? a.x0g : nullptr, rs, acts, rowv, [&]() __attribute__((always_inline)) {
                            if constexpr (EARLY) {
                                load_frag<CT, KS>(wl0, a.theta + net.w_off[tower][0], net.Hp[0]);
@@ -1099,7 +1162,34 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
         // MASK: is category j of this lane's row allowed (dead rows of the last tile: all allowed, nothing is read); the ONE reader of the mask in this kernel
         const float* mrow = MASK ? a.mask + (size_t)row * net.A : nullptr;
         auto allowed = [&](int j) __attribute__((always_inline)) { if constexpr (MASK) return !live || mrow[j] != 0.f; else return true; };
-        if constexpr (CAT) {
+        float k_m = 0.f, k_z = 1.f, k_h = 0.f;                          // MULTI: lane k of the row keeps component k's maximum, normaliser, entropy ...
+        int k_act = -1;                                                   // ... and the action's column
+        if constexpr (MULTI) {
+            for (int k = 0; k < a.comp.K; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                const int act = live ? o + (int)acts[r * net.Ap + k] : -1;
+                float bl = -INFINITY;
+                int il = o;
+                for (int j = o + part; j < e; j += 16) { const float l = mus[r * ldm + j]; if (allowed(j) && l > bl) { bl = l; il = j; } }
+                group16_argmax(bl, il);
+                const float m = bl;
+                float la = 0.f, z = 0.f, ent = 0.f;
+                for (int j = o + part; j < e; j += 16) {
+                    if (!allowed(j)) continue;
+                    const float a0 = mus[r * ldm + j] - m;
+                    z += expf(a0);
+                    if (j == act) la = a0;
+                }
+                z = group16_sum(z); la = group16_sum(la);
+                const float lz = logf(z);
+                for (int j = o + part; j < e; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - m; ent += (expf(a0) / z) * (lz - a0); }
+                ent = group16_sum(ent);
+                const float nk = lz - la;
+                cnlp = k == 0 ? nk : cnlp + nk;
+                cent = k == 0 ? ent : cent + ent;
+                if (part == k) { k_m = m; k_z = z; k_h = ent; k_act = act; }
+            }
+        } else if constexpr (CAT) {
             cact = live ? (int)acts[r * net.Ap] : -1;
             float bl = -INFINITY;
             int il = 0;
@@ -1156,6 +1246,30 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
             misc[r * 4 + 3] = (live && fabsf(ratio - 1.0f) > cr) ? 1.0f : 0.f;
         }
         // d mu (-> dcur tile, also the dY operand of the head weight gradient) and d logstd rows
+        if constexpr (MULTI) {
+            // d loss / d l_j = d_nlp (p_j - [j == o_k + a_k]) + ent_coef g p_j (log p_j + H_k), k = j's component; forbidden and padding columns: exactly 0
+            auto put = [&](int j, float dmu) __attribute__((always_inline)) {
+                dcur[r * ldm + j] = dmu;
+                dls[r * net.Ap + j] = 0.f;
+                a.dmug[(size_t)row * net.Ap + j] = dmu;            // dead rows of the last tile: zeros
+            };
+            for (int k = 0; k < a.comp.K; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                const float m = __shfl(k_m, k, 16), z = __shfl(k_z, k, 16), hk = __shfl(k_h, k, 16);
+                const int act = __shfl(k_act, k, 16);
+                const float lz = logf(z);
+                for (int j = o + part; j < e; j += 16) {
+                    float dmu = 0.f;
+                    if (live && allowed(j)) {
+                        const float a0 = mus[r * ldm + j] - m;
+                        const float p = expf(a0) / z;
+                        dmu = d_nlp * (p - (j == act ? 1.0f : 0.0f)) + net.ent_coef * g * (p * ((a0 - lz) + hk));
+                    }
+                    put(j, dmu);
+                }
+            }
+            for (int j = net.A + part; j < net.Ap; j += 16) put(j, 0.f);
+        } else
         for (int j = part; j < net.Ap; j += 16) {
             float dmu = 0.f, dl = 0.f;
             if constexpr (CAT) {

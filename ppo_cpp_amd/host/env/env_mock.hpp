@@ -12,6 +12,12 @@
 //                  the categories (about half; keyed like the observations, columns obs_dim + j of the same stream) is forbidden, the target category never.
 //                  Reward 1 for the target, 0 for another allowed category, -1 for a forbidden one; the environment counts the forbidden actions it received
 //                  (tests/test_action_mask.py: a masking policy must never send one).
+//   MultiDiscreteTargetEnv  DiscreteTargetEnv's task on a MULTI-DISCRETE action space (the IMultiDiscrete mixin, multi_discrete.hpp): K components of nvec[k] categories,
+//                  an action is [1, K]; component k's target is argmax_j (W_k obs)_j with W_k hashed like TargetEnv's W under a per-component key; reward = the
+//                  fraction of components whose action hits its target; episodes of a fixed length (tests/test_multi_discrete.py).  With masked = true it also
+//                  carries IActionMask like MaskedTargetEnv: at every step a seeded subset (about half; the top bit of the stream's word (step, obs_dim + j) for
+//                  global column j) of each component's categories is forbidden, the component's target never; the reward is -1 when any component's action is
+//                  forbidden, and the environment counts the steps on which it received one.
 //   UnitRewardEnv  SeededEnvMock's observation stream, reward 1 on every step, never done by itself: behind a TimeLimit every episode ends by truncation, and
 //                  the value of every state is 1 / (1 - gamma) -- which a critic only learns when the value is bootstrapped there (tests/test_truncation.py).
 //                  reset() does NOT rewind the stream (it moves one draw on): no observation ever comes twice, so nothing tells a critic how far the
@@ -21,6 +27,7 @@
 
 #include "action_mask.hpp"
 #include "env.hpp"
+#include "multi_discrete.hpp"
 
 class EnvMock : public Env {
 public:
@@ -262,6 +269,92 @@ private:
     uint64_t key_;
     int kDim, kAct, len_;
     std::vector<float> w_;          // [category][obs], row-major
+};
+
+class MultiDiscreteTargetEnv : public Env, public IMultiDiscrete, public IActionMask {
+public:
+    MultiDiscreteTargetEnv(uint32_t seed, uint32_t env_id, int obs_dim, const std::vector<int>& nvec, int episode_len = 100, bool masked = false)
+        : step_(0), last_rew_(0.f), forbidden_(0), key_(ppo_detail::ctr_key(seed, env_id)), kDim(obs_dim), len_(episode_len), masked_(masked), nvec_(nvec), off_(nvec.size() + 1, 0) {
+        for (size_t k = 0; k < nvec_.size(); ++k) off_[k + 1] = off_[k] + nvec_[k];
+        w_.resize((size_t)off_.back() * kDim);
+        const uint64_t wkey = ppo_detail::splitmix64(((uint64_t)seed << 32) | 0xffffffffull);       // TargetEnv's key; component k hashes under wkey ^ ((k + 1) << 48)
+        for (size_t k = 0; k < nvec_.size(); ++k) {
+            const uint64_t ck = ppo_detail::splitmix64(wkey ^ ((uint64_t)(k + 1) << 48));
+            for (int j = 0; j < nvec_[k]; ++j)
+                for (int i = 0; i < kDim; ++i)
+                    w_[(size_t)(off_[k] + j) * kDim + i] = 0.5f * ppo_detail::sym_unit((uint32_t)(ppo_detail::splitmix64(ck ^ (((uint64_t)j << 32) | (uint32_t)i)) >> 32));
+        }
+    }
+    std::string get_action_space() override { return Env::SPACE_DISCRETE; }
+    std::string get_observation_space() override { return Env::SPACE_CONTINOUS; }
+    int get_action_space_size() override { return off_.back(); }           // A = sum of the components' widths
+    int get_observation_space_size() override { return kDim; }
+    std::vector<int> get_action_nvec() override { return nvec_; }
+    Mat reset() override { step_ = 0; return obs_at(0); }
+    std::vector<Mat> step(const Mat& actions) override {
+        const int K = (int)nvec_.size();
+        const std::vector<int> best = targets_at(step_);      // for the observation the action answers
+        int hits = 0; bool legal = true;
+        for (int k = 0; k < K; ++k) {
+            const int a = (int)actions(0, k);
+            if (a == best[k]) ++hits;
+            if (masked_ && !(a >= 0 && a < nvec_[k] && allowed_at(step_, off_[k] + a, off_[k] + best[k]))) legal = false;
+        }
+        if (!legal) ++forbidden_;
+        last_rew_ = legal ? (float)hits / (float)K : -1.f;
+        ++step_;
+        Mat rew(1, 1), done(1, 1);
+        rew(0, 0) = last_rew_;
+        done(0, 0) = (step_ % (uint32_t)len_ == 0u) ? 1.f : 0.f;
+        std::vector<Mat> out;
+        out.reserve(3);
+        out.push_back(obs_at(step_)); out.push_back(std::move(rew)); out.push_back(std::move(done));
+        return out;
+    }
+    // legality of every column for the current observation obs_at(step_): [1, A]
+    Mat get_action_mask() override {
+        Mat m = Mat::Ones(1, off_.back());
+        if (!masked_) return m;
+        const std::vector<int> best = targets_at(step_);
+        for (size_t k = 0; k < nvec_.size(); ++k)
+            for (int j = off_[k]; j < off_[k + 1]; ++j) m(0, j) = allowed_at(step_, j, off_[k] + best[k]) ? 1.f : 0.f;
+        return m;
+    }
+    bool has_action_mask() override { return masked_; }
+    long forbidden_received() const { return forbidden_; }
+    std::vector<int> targets() const { return targets_at(step_); }
+    Mat get_original_obs() override { return obs_at(step_); }
+    Mat get_original_rew() override { Mat r(1, 1); r(0, 0) = last_rew_; return r; }
+    void serialize(nlohmann::json&) override {}
+    void deserialize(nlohmann::json&) override {}
+    void render() override {}
+    float get_time() override { return 0.f; }
+
+private:
+    Mat obs_at(uint32_t step) const { Mat m(1, kDim); for (int j = 0; j < kDim; ++j) m(0, j) = ppo_detail::sym_unit(ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)j)); return m; }
+    std::vector<int> targets_at(uint32_t step) const {
+        const Mat cur = obs_at(step);
+        std::vector<int> best(nvec_.size(), 0);
+        for (size_t k = 0; k < nvec_.size(); ++k) {
+            float best_v = 0.f;
+            for (int j = 0; j < nvec_[k]; ++j) {
+                float tgt = 0.f;
+                for (int i = 0; i < kDim; ++i) tgt += w_[(size_t)(off_[k] + j) * kDim + i] * cur(0, i);
+                if (j == 0 || tgt > best_v) { best[k] = j; best_v = tgt; }
+            }
+        }
+        return best;
+    }
+    // the top bit of the stream's word (step, obs_dim + column) forbids the column; a component's target is always allowed
+    bool allowed_at(uint32_t step, int col, int best_col) const { return col == best_col || (ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)(kDim + col)) >> 31) == 0u; }
+    uint32_t step_;
+    float last_rew_;
+    long forbidden_;
+    uint64_t key_;
+    int kDim, len_;
+    bool masked_;
+    std::vector<int> nvec_, off_;
+    std::vector<float> w_;          // [column][obs], row-major; component k's rows start at off_[k]
 };
 
 class UnitRewardEnv : public Env {

@@ -10,13 +10,15 @@
 #include "../../../include/ppo_hip.h"
 #include "env.hpp"
 #include "action_mask.hpp"
+#include "multi_discrete.hpp"
 #include "time_limit.hpp"
 
 // Time-limit truncations (time_limit.hpp): the mixin is forwarded from the wrapped Env when it has one (zeros otherwise).  The terminal observation is forwarded
 // RAW: the library scales it with the statistics as they stand when the rollout is finished (include/ppo_hip.h, ppo_rollout_mark_truncated), and it never
 // enters obs_rms.  normalize_terminal() is for callers outside the HBM-resident loop (Runner::run): the current statistics, no update.
 // Action masks (action_mask.hpp): forwarded from the wrapped Env unchanged (a mask is no observation: nothing is scaled); all ones when it has none.
-class EnvNormalize : public Env, public ITimeLimit, public IActionMask {
+// Multi-discrete action spaces (multi_discrete.hpp): the components are forwarded from the wrapped Env.
+class EnvNormalize : public Env, public ITimeLimit, public IActionMask, public IMultiDiscrete {
 public:
     EnvNormalize(std::unique_ptr<Env> env, ppo_handle* handle, bool training, bool norm_obs = true, bool norm_reward = true,
                  float clip_reward = 10, float clip_obs = 10, float gamma = 0.99f, float epsilon = 1e-8f)
@@ -69,6 +71,8 @@ public:
     bool has_time_limit() override { return tl_ && tl_->has_time_limit(); }
     Mat get_action_mask() override { return has_action_mask() ? am_->get_action_mask() : Mat::Ones(get_num_envs(), get_action_space_size()); }
     bool has_action_mask() override { return am_ && am_->has_action_mask(); }
+    std::vector<int> get_action_nvec() override { return action_nvec_of(env_.get()); }
+    bool has_action_nvec() override { return !action_nvec_of(env_.get()).empty(); }
     // [n_envs, obs] raw -> scaled and clipped with the current statistics, which stay as they are
     Mat normalize_terminal(const Mat& raw) {
         if (!norm_obs_) return raw;

@@ -27,6 +27,8 @@
 #include <iostream>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
+#include <string>
 #include <thread>
 #if defined(__linux__)
 #include <sched.h>
@@ -34,6 +36,7 @@
 
 #include "env.hpp"
 #include "action_mask.hpp"
+#include "multi_discrete.hpp"
 #include "time_limit.hpp"
 
 // CPUs this process may actually use: hardware threads, narrowed by the affinity mask and by the cgroup CPU quota
@@ -68,7 +71,9 @@ inline int usable_cpus() {
 // get_terminal_obs() gather their answers in environment order, children without the mixin report 0.
 // Action masks (action_mask.hpp): get_action_mask() gathers the children's current masks in environment order on the caller's thread (between steps: the pool is
 // idle); children without the mixin report every category allowed.
-class VecEnv : public virtual Env, public ITimeLimit, public IActionMask {
+// Multi-discrete action spaces (multi_discrete.hpp): the children's components are forwarded; children that disagree (or only some of which are multi-discrete)
+// are refused at construction.
+class VecEnv : public virtual Env, public ITimeLimit, public IActionMask, public IMultiDiscrete {
 public:
     explicit VecEnv(const std::vector<std::shared_ptr<Env>>& envs, int max_workers = 0)
         : envs_(envs), n_(static_cast<int>(envs.size())), generation_(0), terminate_(false), actions_(nullptr),
@@ -80,6 +85,9 @@ public:
         for (int i = 0; i < n_; ++i) if ((tl_[i] = dynamic_cast<ITimeLimit*>(envs_[i].get()))) any_tl_ = true;
         am_.resize(n_, nullptr);
         for (int i = 0; i < n_; ++i) { am_[i] = dynamic_cast<IActionMask*>(envs_[i].get()); if (am_[i] && !am_[i]->has_action_mask()) am_[i] = nullptr; if (am_[i]) any_am_ = true; }
+        nvec_ = action_nvec_of(envs_[0].get());
+        for (int i = 1; i < n_; ++i)
+            if (action_nvec_of(envs_[i].get()) != nvec_) throw std::runtime_error("VecEnv: environment " + std::to_string(i) + " reports other action components (get_action_nvec) than environment 0");
         truncated_ = Mat::Zero(n_, 1);
         if (any_tl_) terminal_obs_ = Mat::Zero(n_, obs_dim_);
         // first guess: 8 chunks per thread; recalibrated from measured time per environment after the first steps
@@ -153,6 +161,8 @@ public:
         return m;
     }
     bool has_action_mask() override { return any_am_; }
+    std::vector<int> get_action_nvec() override { return nvec_; }
+    bool has_action_nvec() override { return !nvec_.empty(); }
     void serialize(nlohmann::json&) override {}
     void deserialize(nlohmann::json&) override {}
     void render() override { std::cout << "VecEnv::render() not implemented\n"; }
@@ -322,6 +332,7 @@ private:
     bool any_tl_ = false;
     std::vector<IActionMask*> am_;     // per child: its action-mask mixin, or null
     bool any_am_ = false;
+    std::vector<int> nvec_;            // the children's action components (multi_discrete.hpp), empty: not multi-discrete
     Mat truncated_, terminal_obs_;     // [n, 1], [n, obs] of the last step
     int workers_ = 1, chunk_ = 1, n_chunks_ = 1, steps_ = 0;
     Mode mode_ = RESET;

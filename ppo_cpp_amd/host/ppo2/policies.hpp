@@ -1,7 +1,8 @@
 // policies.hpp -- MlpPolicy with the reference's method names (ppo2/policies.hpp:26-82).  The reference wraps
 // tensorflow::Session::Run with fixed feed/fetch names; this one wraps the C-ABI of libppo_hip (include/ppo_hip.h).
 // Results come back as Mats: step -> {actions [n,A], values [n,1], neglogps [n,1]}; a categorical handle (ppo_create_ex with
-// PPO_ACT_CATEGORICAL, an Env whose action space is SPACE_DISCRETE) returns actions [n,1] holding the category index.
+// PPO_ACT_CATEGORICAL, an Env whose action space is SPACE_DISCRETE) returns actions [n,1] holding the category index, a multi-categorical one (ppo_create_multi, an
+// Env with the IMultiDiscrete mixin) actions [n,K] holding the index within every component.
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -13,8 +14,8 @@
 class MlpPolicy {
 public:
     explicit MlpPolicy(ppo_handle* handle, int act_dim) : h_(handle), act_dim_(action_width(handle, act_dim)) {}
-    // columns of an action matrix: act_dim (Gaussian) or 1 (categorical: the category index)
-    static int action_width(ppo_handle* handle, int act_dim) { return handle && ppo_action_dist(handle) == PPO_ACT_CATEGORICAL ? 1 : act_dim; }
+    // columns of an action matrix: act_dim (Gaussian), 1 (categorical: the category index) or K (multi-categorical) -- what the handle reports (ppo_action_width)
+    static int action_width(ppo_handle* handle, int act_dim) { return handle ? ppo_action_width(handle) : act_dim; }
     int action_width() const { return act_dim_; }
     virtual ~MlpPolicy() {}
 

@@ -34,11 +34,18 @@ public:
         n_batch_ = n_envs_ * n_steps_;
         // the handle's head must match the Env's action space (env/env.hpp:42-47): a Gaussian head for SPACE_CONTINOUS, a categorical
         // one (ppo_create_ex with PPO_ACT_CATEGORICAL, act_dim = number of categories) for SPACE_DISCRETE
-        const bool discrete = env.get_action_space() == Env::SPACE_DISCRETE, categorical = ppo_action_dist(handle) == PPO_ACT_CATEGORICAL;
+        // an Env with the IMultiDiscrete mixin (env/multi_discrete.hpp) needs a multi-categorical handle (ppo_create_multi) with the Env's own components
+        const std::vector<int> env_nvec = action_nvec_of(&env);
+        const int dist = ppo_action_dist(handle);
+        const bool discrete = env.get_action_space() == Env::SPACE_DISCRETE, multi = dist == PPO_ACT_MULTI_CATEGORICAL;
+        const bool categorical = dist == PPO_ACT_CATEGORICAL || multi;                  // (a head over logits: what masks and SPACE_DISCRETE need)
         if (discrete != categorical)
             throw std::runtime_error(std::string("PPO2: the Env's action space is '") + env.get_action_space() + "' but the handle's policy head is " +
                                      (categorical ? "categorical" : "Gaussian") + " (create the handle with ppo_create_ex and " +
                                      (discrete ? "PPO_ACT_CATEGORICAL" : "PPO_ACT_GAUSSIAN") + ")");
+        if (multi != !env_nvec.empty() || (multi && handle_nvec(handle) != env_nvec))
+            throw std::runtime_error("PPO2: the Env's action components " + nvec_text(env_nvec) + " are not the handle's " + nvec_text(multi ? handle_nvec(handle) : std::vector<int>()) +
+                                     " (an Env with the IMultiDiscrete mixin needs a handle from ppo_create_multi with the same nvec: PPO2::create_handle)");
         // an Env that carries the IActionMask mixin (env/action_mask.hpp): the handle's rollout carries masks from here on, and both loops and eval() pass them
         IActionMask* am = dynamic_cast<IActionMask*>(&env_);
         if (am && am->has_action_mask()) {
@@ -51,9 +58,31 @@ public:
     // The action_dist argument of ppo_create_ex for a handle that will serve `env`: PPO_ACT_GAUSSIAN for SPACE_CONTINOUS, PPO_ACT_CATEGORICAL for SPACE_DISCRETE.
     // discrete_shape_kernels (default off): a discrete Env's handle is created with PPO_ACT_SHAPE_KERNELS -- the narrow LDS-resident kernels when the network's
     // shape qualifies (include/ppo_hip.h); a continuous Env is not affected.
+    // An Env with the IMultiDiscrete mixin: PPO_ACT_MULTI_CATEGORICAL (no flags: that head has the generic PPO_F32 kernels only) -- a value for ppo_create_multi,
+    // which ppo_create_ex refuses; create_handle below makes the right call.
     static int32_t action_dist_for(Env& env, bool discrete_shape_kernels = false) {
         if (env.get_action_space() != Env::SPACE_DISCRETE) return PPO_ACT_GAUSSIAN;
+        if (!action_nvec_of(&env).empty()) return PPO_ACT_MULTI_CATEGORICAL;
         return PPO_ACT_CATEGORICAL | (discrete_shape_kernels ? PPO_ACT_SHAPE_KERNELS : 0);
+    }
+    // The handle that will serve `env`: ppo_create_multi with the Env's components for an IMultiDiscrete Env (cfg.act_dim must be their sum), otherwise
+    // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  Returns the library's status; ppo_last_error(nullptr) has the message.
+    static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
+        const std::vector<int> nvec = action_nvec_of(&env);
+        if (nvec.empty()) return ppo_create_ex(&cfg, action_dist_for(env, discrete_shape_kernels) | extra_flags, out);
+        const std::vector<int32_t> nv(nvec.begin(), nvec.end());
+        return ppo_create_multi(&cfg, nv.data(), (int32_t)nv.size(), out);
+    }
+    // the handle's component widths (ppo_action_nvec): empty for a Gaussian handle, {A} for a categorical one
+    static std::vector<int> handle_nvec(const ppo_handle* handle) {
+        int32_t nv[PPO_MAX_COMPONENTS] = {0};
+        const int k = ppo_action_nvec(handle, PPO_MAX_COMPONENTS, nv);
+        return std::vector<int>(nv, nv + (k > 0 ? k : 0));
+    }
+    static std::string nvec_text(const std::vector<int>& v) {
+        std::string s = "[";
+        for (size_t i = 0; i < v.size(); ++i) s += (i ? ", " : "") + std::to_string(v[i]);
+        return s + "]";
     }
 
     struct UpdateLog { int fps; float losses[5]; double collect_ms, update_ms; float mean_reward; };     // mean_reward: the rollout's un-normalised rewards (the learning curve)
@@ -115,6 +144,7 @@ public:
         // (JSON has no NaN or inf: NaN and -inf, both PPO_VCLIP_POLICY, are written as -1; +inf is written as null, which load() reads back as +inf)
         json["cliprange_vf"] = std::isnan(cliprange_vf_) || cliprange_vf_ == -INFINITY ? -1.f : cliprange_vf_; json["observation_space"] = env_.get_observation_space();
         json["action_space"] = env_.get_action_space(); json["n_envs"] = n_envs_ * world_; json["model_filename"] = model_filename;
+        if (ppo_action_dist(h_) == PPO_ACT_MULTI_CATEGORICAL) json["action_nvec"] = handle_nvec(h_);        // a multi-categorical policy: "discrete" plus its components
         std::ofstream f(save_path + ".json");
         if (!f) throw std::runtime_error("PPO2::save: unable to open " + save_path + ".json");
         f << json.dump();
@@ -124,11 +154,16 @@ public:
     // restore optimiser state (the graph's saver holds no Adam slots, G:32396-32496)
     void load(const std::string& save_path) {
         const ckpt::Bundle b = ckpt::load_bundle(save_path);
-        const bool categorical = ppo_action_dist(h_) == PPO_ACT_CATEGORICAL;
+        const bool categorical = ppo_action_dist(h_) != PPO_ACT_GAUSSIAN;       // (categorical or multi-categorical: no pi/logstd)
         if (categorical == (b.count("model/pi/logstd") != 0))                   // the Gaussian head's checkpoint carries pi/logstd, the categorical one's does not
             throw std::runtime_error(std::string("PPO2::load: ") + save_path + " holds a " + (categorical ? "Gaussian" : "categorical") + " policy but the handle's head is " +
                                      (categorical ? "categorical" : "Gaussian"));
         nlohmann::json json = nlohmann::json::parse(ckpt::slurp(save_path + ".json"));
+        // "action_nvec": the components of a multi-categorical policy; a side-car without the key holds a plain categorical (or Gaussian) one
+        const std::vector<int> saved_nvec = json.contains("action_nvec") ? json["action_nvec"].get<std::vector<int>>() : std::vector<int>();
+        const std::vector<int> mine = ppo_action_dist(h_) == PPO_ACT_MULTI_CATEGORICAL ? handle_nvec(h_) : std::vector<int>();
+        if (saved_nvec != mine)
+            throw std::runtime_error("PPO2::load: " + save_path + " holds a policy with action components " + nvec_text(saved_nvec) + " but the handle's are " + nvec_text(mine));
         env_.deserialize(json);
         gamma_ = json["gamma"].get<float>(); n_steps_ = json["n_steps"].get<int>(); vf_coef_ = json["vf_coef"].get<float>();
         ent_coef_ = json["ent_coef"].get<float>(); max_grad_norm_ = json["max_grad_norm"].get<float>();
@@ -153,7 +188,7 @@ public:
     std::string model_filename;
 
     // deterministic action for one observation row (ppo2.hpp:225-237)
-    // An Env with the IActionMask mixin: the best category its current mask allows (obs is the Env's current observation).
+    // An Env with the IActionMask mixin: the best category its current mask allows (obs is the Env's current observation); per component on a multi-categorical handle.
     Mat eval(const Mat& obs) {
         if (!am_) return act_model_.get_deterministic_action(obs);
         const Mat mask = am_->get_action_mask();

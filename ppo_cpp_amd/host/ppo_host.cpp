@@ -177,6 +177,8 @@ struct ppo_host_args {
     float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
     int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for)
     int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD)
+    int n_components, nvec[16];  // ppo_host_learn_multi: the components of MultiDiscreteTargetEnv (act_dim is their sum)
+    int multi_masked;            // ppo_host_learn_multi: the environments also carry IActionMask
 };
 // the handle's action_dist for `env`: PPO2's choice, plus the opt-in a categorical head needs on the bf16 path
 static int32_t host_action_dist(Env& env, const ppo_host_args* a) {
@@ -351,6 +353,151 @@ int ppo_host_discrete_checkpoint(const char* prefix, const float* obs, int n, fl
             bool threw = false;
             try { algo.load(prefix); } catch (const std::exception& e) { threw = true; std::fprintf(stderr, "expected: %s\n", e.what()); }
             if (!threw) rc = 2;
+        }
+    } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = -1; }
+    for (ppo_handle* x : h) if (x) ppo_destroy(x);
+    return rc;
+}
+
+// The learning check of the multi-categorical head (tests/test_multi_discrete.py): n_envs x MultiDiscreteTargetEnv(nvec) -> VecEnv -> EnvNormalize -> PPO2::learn with the
+// library's own sampling and shuffles, through the HBM-resident loop or, with args->reference_loop, the literal one.  The handle comes from PPO2::create_handle (the Env
+// carries IMultiDiscrete: ppo_create_multi).  args as for ppo_host_learn_masked plus n_components / nvec / multi_masked (the environments also carry IActionMask: PPO2 masks
+// by itself).  reward_curve [n_updates]; *forbidden_received: steps on which an environment was sent a forbidden action; playback_actions [n_playback][K] /
+// playback_legal [n_playback] (may be null / 0): PPO2::eval on the stack for n_playback steps after training (environment 0's row) and whether the environment's own mask
+// allowed every component's action.  count_names / counts / n_counts (all three or none): ppo_kernel_counts of the run's handle, up to 64 entries.
+int ppo_host_learn_multi(const ppo_host_args* a, float* reward_curve, long long* forbidden_received, int n_playback, float* playback_actions, float* playback_legal,
+                         char (*count_names)[32], long long* counts, int* n_counts, ppo_host_result* out) {
+    std::memset(out, 0, sizeof *out);
+    ppo_handle* h = nullptr;
+    try {
+        if (a->n_components < 1 || a->n_components > 16) throw std::runtime_error("n_components must be 1..16");
+        const std::vector<int> nvec(a->nvec, a->nvec + a->n_components);
+        const int K = a->n_components, O = a->obs_dim > 0 ? a->obs_dim : 18;
+        int A = 0;
+        for (int n : nvec) A += n;
+        ppo_config cfg;
+        ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
+        cfg.device = a->device;
+        cfg.compute_dtype = a->compute_dtype;
+        std::vector<std::shared_ptr<MultiDiscreteTargetEnv>> kids;
+        std::vector<std::shared_ptr<Env>> envs;
+        for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MultiDiscreteTargetEnv>(1234u, (uint32_t)i, O, nvec, 100, a->multi_masked != 0)); envs.push_back(kids.back()); }
+        if (PPO2::create_handle(cfg, *envs[0], &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, a->max_workers)), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
+            struct Plain : Env, IActionMask, IMultiDiscrete {       // hides the EnvNormalize type to force the reference loop; the two mixins stay visible
+                EnvNormalize& e; explicit Plain(EnvNormalize& x) : e(x) {}
+                std::string get_action_space() override { return e.get_action_space(); }
+                std::string get_observation_space() override { return e.get_observation_space(); }
+                int get_action_space_size() override { return e.get_action_space_size(); }
+                int get_observation_space_size() override { return e.get_observation_space_size(); }
+                int get_num_envs() override { return e.get_num_envs(); }
+                Mat reset() override { return e.reset(); }
+                std::vector<Mat> step(const Mat& x) override { return e.step(x); }
+                void render() override {}
+                float get_time() override { return 0; }
+                Mat get_original_obs() override { return e.get_original_obs(); }
+                Mat get_original_rew() override { return e.get_original_rew(); }
+                void serialize(nlohmann::json& j) override { e.serialize(j); }
+                void deserialize(nlohmann::json& j) override { e.deserialize(j); }
+                Mat get_action_mask() override { return e.get_action_mask(); }
+                bool has_action_mask() override { return e.has_action_mask(); }
+                std::vector<int> get_action_nvec() override { return e.get_action_nvec(); }
+                bool has_action_nvec() override { return e.has_action_nvec(); }
+            } plain{env};
+            Env& top = a->reference_loop ? static_cast<Env&>(plain) : static_cast<Env&>(env);
+            PPO2 algo{h, top, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange, a->cliprange_vf};
+            if (ppo_get_action_masking(h) != (a->multi_masked ? 1 : 0)) throw std::runtime_error("PPO2 set action masking wrongly for this Env");
+            algo.quiet = true;
+            algo.seed = a->seed;
+            algo.learn(a->n_updates * a->n_envs * a->n_steps);
+            const auto& hist = algo.history();
+            if (hist.empty()) throw std::runtime_error("no update ran");
+            std::memcpy(out->losses, hist.back().losses, sizeof out->losses);
+            out->fps_last = hist.back().fps;
+            if (reward_curve) for (size_t i = 0; i < hist.size(); ++i) reward_curve[i] = hist[i].mean_reward;
+            long long total = 0;
+            for (const auto& k : kids) total += k->forbidden_received();
+            if (forbidden_received) *forbidden_received = total;
+            Mat obs = top.reset();
+            for (int t = 0; t < n_playback; ++t) {
+                const Mat mask = env.get_action_mask();
+                const Mat act = algo.eval(obs);
+                if (act.cols() != K) throw std::runtime_error("PPO2::eval did not return K action columns");
+                bool legal = true;
+                for (int k = 0, o = 0; k < K; o += nvec[k], ++k) {
+                    const int c = (int)act(0, k);
+                    if (playback_actions) playback_actions[(size_t)t * K + k] = act(0, k);
+                    legal = legal && c >= 0 && c < nvec[k] && mask(0, o + c) != 0.f;
+                }
+                if (playback_legal) playback_legal[t] = legal ? 1.f : 0.f;
+                obs = top.step(act)[0];
+            }
+            if (count_names && counts && n_counts) {
+                int64_t c64[64];
+                const int nc = ppo_kernel_counts(h, 64, count_names, c64);
+                for (int i = 0; i < nc; ++i) counts[i] = (long long)c64[i];
+                *n_counts = nc;
+            }
+        }
+        ppo_destroy(h);
+        return 0;
+    } catch (const std::exception& e) {
+        std::snprintf(out->error, sizeof out->error, "%s", e.what());
+        if (h) ppo_destroy(h);
+        return -1;
+    }
+}
+
+// PPO2::save of a multi-categorical policy (a [64,64] handle with components nvec behind MultiDiscreteTargetEnv x 4 + EnvNormalize, one short learn()) under `prefix`,
+// then PPO2::load into a FRESH handle with the same components: every tensor and the deterministic actions of `n` observations must be identical (actions_out
+// [2][n][K]: before / after).  Loading into a handle with ANOTHER split of the same width (other_nvec, same sum) and into a plain categorical handle of that width must
+// both fail.  Returns 0; 1 = tensors differ, 2 = the other split's load went through, 3 = the categorical handle's; -1 = error (message on stderr).
+int ppo_host_multi_checkpoint(const char* prefix, const int* nvec_in, const int* other_nvec_in, int K, int K_other, const float* obs, int n, float* actions_out) {
+    ppo_handle* h[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    try {
+        const std::vector<int> nvec(nvec_in, nvec_in + K), other(other_nvec_in, other_nvec_in + K_other);
+        int A = 0;
+        for (int x : nvec) A += x;
+        ppo_config cfg; const int32_t hidden[2] = {64, 64};
+        ppo_config_default(&cfg, 18, A, 2, hidden);
+        MultiDiscreteTargetEnv probe(1234u, 0, 18, nvec), probe_other(1234u, 0, 18, other);
+        DiscreteTargetEnv probe_cat(1234u, 0, 18, A);
+        Env* probes[4] = {&probe, &probe, &probe_other, &probe_cat};
+        for (int k = 0; k < 4; ++k)
+            if (PPO2::create_handle(cfg, *probes[k], &h[k]) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0) throw std::runtime_error(ppo_last_error(h[k]));
+        std::vector<std::shared_ptr<Env>> envs;
+        for (uint32_t i = 0; i < 4; ++i) envs.push_back(std::make_shared<MultiDiscreteTargetEnv>(1234u, i, 18, nvec));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, 1)), h[0], /*training=*/true};
+            PPO2 algo{h[0], env, 0.99f, 16, cfg.ent_coef, 1e-3f, 0.5f, 0.5f, 0.95f, 4, 2, 0.2f};
+            algo.quiet = true;
+            algo.learn(2 * 4 * 16);
+            algo.save(prefix);
+            if (ppo_act_deterministic(h[0], obs, n, actions_out) != 0) throw std::runtime_error(ppo_last_error(h[0]));
+        }
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new MultiDiscreteTargetEnv(1234u, 0, 18, nvec)), h[1], /*training=*/false};
+            PPO2 algo{h[1], env};
+            algo.load(prefix);
+            if (ppo_act_deterministic(h[1], obs, n, actions_out + (size_t)n * K) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+        }
+        for (int i = 0; i < ppo_num_tensors(h[0]) && !rc; ++i) {
+            int32_t r = 0, c = 0;
+            ppo_tensor_info(h[0], i, nullptr, &r, &c);
+            std::vector<float> x((size_t)r * (c ? c : 1)), y(x.size());
+            if (ppo_get_tensor(h[0], 0, i, x.data(), (int64_t)x.size()) != 0 || ppo_get_tensor(h[1], 0, i, y.data(), (int64_t)y.size()) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+            if (std::memcmp(x.data(), y.data(), sizeof(float) * x.size()) != 0) rc = 1;
+        }
+        for (int k = 2; k < 4 && !rc; ++k) {
+            std::unique_ptr<Env> e(k == 2 ? static_cast<Env*>(new MultiDiscreteTargetEnv(1234u, 0, 18, other)) : static_cast<Env*>(new DiscreteTargetEnv(1234u, 0, 18, A)));
+            EnvNormalize env{std::move(e), h[k], /*training=*/false};
+            PPO2 algo{h[k], env};
+            bool threw = false;
+            try { algo.load(prefix); } catch (const std::exception& ex) { threw = true; std::fprintf(stderr, "expected: %s\n", ex.what()); }
+            if (!threw) rc = k;
         }
     } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = -1; }
     for (ppo_handle* x : h) if (x) ppo_destroy(x);

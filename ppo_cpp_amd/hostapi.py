@@ -12,7 +12,8 @@ class HostArgs(C.Structure):
                 ("lr", C.c_float), ("cliprange", C.c_float), ("gamma", C.c_float), ("lam", C.c_float),
                 ("seeded_env", C.c_int), ("device", C.c_int), ("max_workers", C.c_int), ("reference_loop", C.c_int),
                 ("norm_obs", C.c_int), ("norm_reward", C.c_int), ("seed", C.c_ulonglong), ("obs_dim", C.c_int), ("act_dim", C.c_int),
-                ("cliprange_vf", C.c_float), ("discrete_kernels", C.c_int), ("compute_dtype", C.c_int)]
+                ("cliprange_vf", C.c_float), ("discrete_kernels", C.c_int), ("compute_dtype", C.c_int),
+                ("n_components", C.c_int), ("nvec", C.c_int * 16), ("multi_masked", C.c_int)]
 
 
 def _discrete_kernels(name):
@@ -106,16 +107,44 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0):
+                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, nvec=None, masked=False, n_playback=0):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
     PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "generic" (the default): without.
     compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD.
+    nvec=[n_0, ..]: MultiDiscreteTargetEnv with these components (act_dim is ignored: their sum) and a multi-categorical handle (PPO2::create_handle ->
+    ppo_create_multi), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)
+    and the result carries "forbidden_received"; n_playback: that many PPO2::eval steps afterwards, "playback_actions" [n_playback, K] and "playback_legal".
     "kernel_counts": the handle's ppo_kernel_counts after the run."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
+    if nvec is not None:
+        nvec = [int(x) for x in nvec]
+        a.n_envs, a.n_steps, a.n_hidden = n_envs, n_steps, len(hidden)
+        for i, h in enumerate(hidden):
+            a.hidden[i] = h
+        a.nminibatches, a.noptepochs, a.n_updates = nminibatches, noptepochs, n_updates
+        a.lr, a.cliprange, a.gamma, a.lam = lr, cliprange, gamma, lam
+        a.device, a.max_workers, a.reference_loop = device, 0, int(reference_loop)
+        a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
+        a.obs_dim, a.act_dim, a.cliprange_vf, a.compute_dtype = obs_dim, sum(nvec), cliprange_vf, int(compute_dtype)
+        a.n_components, a.multi_masked = len(nvec), int(bool(masked))
+        for i, x in enumerate(nvec):
+            a.nvec[i] = x
+        out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros((n_playback, len(nvec)), np.float32),
+               "playback_legal": np.zeros(n_playback, np.float32)}
+        names = ((C.c_char * 32) * 64)(); cnt = (C.c_longlong * 64)(); ncnt = C.c_int(0)
+        forbidden = C.c_longlong(-1)
+        r = HostResult()
+        fp = C.POINTER(C.c_float)
+        if lib.ppo_host_learn_multi(C.byref(a), out["reward_curve"].ctypes.data_as(fp), C.byref(forbidden), int(n_playback), out["playback_actions"].ctypes.data_as(fp),
+                                    out["playback_legal"].ctypes.data_as(fp), names, cnt, C.byref(ncnt), C.byref(r)) != 0:
+            raise RuntimeError(r.error.decode())
+        out["forbidden_received"] = int(forbidden.value)
+        out["kernel_counts"] = {names[i].value.decode(): int(cnt[i]) for i in range(ncnt.value)}
+        return out
     a.n_envs, a.n_steps, a.n_hidden = n_envs, n_steps, len(hidden)
     for i, h in enumerate(hidden):
         a.hidden[i] = h
@@ -206,6 +235,21 @@ def value_clip_checkpoint(prefix, cliprange_vf):
     if lib.ppo_host_value_clip_checkpoint(prefix.encode(), C.c_float(cliprange_vf), C.byref(m), C.byref(r)) != 0:
         raise RuntimeError("ppo_host_value_clip_checkpoint failed (see stderr)")
     return m.value, r.value
+
+
+def multi_checkpoint(prefix, obs, nvec, other_nvec):
+    """PPO2::save of a multi-categorical policy with components nvec, PPO2::load into a fresh handle with the same components, into one with other_nvec (another
+    split of the same width) and into a plain categorical one (ppo_host_multi_checkpoint): returns (status, deterministic actions before [n, K], after);
+    status 0 = identical tensors and both foreign loads refused"""
+    import numpy as np
+    lib = load_host_library()
+    obs = np.ascontiguousarray(obs, np.float32)
+    n, K = obs.shape[0], len(nvec)
+    assert sum(nvec) == sum(other_nvec)
+    acts = np.zeros((2, n, K), np.float32)
+    nv, ov = (C.c_int * K)(*nvec), (C.c_int * len(other_nvec))(*other_nvec)
+    rc = lib.ppo_host_multi_checkpoint(prefix.encode(), nv, ov, K, len(other_nvec), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)))
+    return rc, acts[0], acts[1]
 
 
 def discrete_checkpoint(prefix, obs):
