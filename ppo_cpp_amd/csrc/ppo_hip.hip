@@ -2869,10 +2869,14 @@ static int act_resident(ppo_handle* h, HostForm form, int t) {
     }
 }
 
+// the counter step of one host-Env act: as in step_common, only a call that draws from the counter RNG advances it (a rollout given explicit noise leaves the
+// next rollout's draws where they were)
+static uint32_t host_rng_step(ppo_handle* h, const float* noise_dev) { return noise_dev ? h->rng_calls : h->rng_calls++; }
+
 // <= 32 environments on the narrow path: ONE launch does the pending transition's EnvNormalize bookkeeping (read from the
 // pinned block), the policy tower and the action store into pinned memory; the host spins on the completion word
 static int act_fused(ppo_handle* h, int t, const float* noise_dev) {
-    if (enqueue_host_step(h, t, true, noise_dev, h->rng_calls++)) return -1;
+    if (enqueue_host_step(h, t, true, noise_dev, host_rng_step(h, noise_dev))) return -1;
     const unsigned want = h->act_seq;                            // (every ~quarter million polls: is the stream still alive?)
     return host_spin(h, 0x3ffff, "ppo_rollout_act: the step kernel finished without publishing", 0, [&] { return __atomic_load_n(h->pin_flag, __ATOMIC_ACQUIRE) == want; });
 }
@@ -2881,7 +2885,7 @@ static int act_fused(ppo_handle* h, int t, const float* noise_dev) {
 // hides under the kernel's tail).  The policy kernel is stream-ordered behind the H2D copy of the last observation and the statistics
 // kernel, so once its last block has published, the pinned input block is free again -- without a stream synchronisation.
 static int act_direct(ppo_handle* h, int t, const float* noise_dev, const float* mask_row, float* actions_out) {
-    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), true, mask_row)) return -1;
+    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, host_rng_step(h, noise_dev), (uint32_t)(h->rank * h->E), true, mask_row)) return -1;
     const unsigned want = h->wg_seq;
     const int G = (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     const size_t cnt = (size_t)h->E * h->Aw, blk = (size_t)ROWS_PER_BLOCK * h->Aw;
@@ -2901,7 +2905,7 @@ static int act_direct(ppo_handle* h, int t, const float* noise_dev, const float*
 // not the copy command.)
 static int act_copy(ppo_handle* h, int t, const float* noise_dev, const float* mask_row) {
     const size_t cnt = (size_t)h->E * h->Aw;
-    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, h->rng_calls++, (uint32_t)(h->rank * h->E), false, mask_row)) return -1;
+    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, host_rng_step(h, noise_dev), (uint32_t)(h->rank * h->E), false, mask_row)) return -1;
     HIP_OK(h, hipMemcpyAsync(h->pin_out, h->ro_act + (size_t)t * cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (bf16_chain_err_async(h)) return -1;
     // busy-wait on the stream: the blocking synchronise parks the thread on an interrupt and wakes it ~100-200 us late,

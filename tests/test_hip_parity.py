@@ -475,8 +475,9 @@ def test_deferred_adam_is_bitwise_the_adam_launch(E, T, nmb, epochs, O, monkeypa
 
 
 def test_update_with_device_permutation_is_a_valid_shuffle():
-    """perms=NULL: the keyed bijection must visit every row exactly once per epoch (sum of per-minibatch means of a
-    permutation-invariant quantity) and runs must be reproducible for a fixed seed."""
+    """perms=NULL: the update runs, reports the initial policy's analytic entropy in every minibatch (which, for a Gaussian policy, does not depend on
+    the rows visited), is reproducible for a fixed seed and changes with the seed.  That the map is the documented permutation, epoch by epoch, and that the
+    rows gathered are the rows it names: tests/test_counter_draws.py (test_device_shuffle_is_the_documented_map, test_rows_gathered_follow_the_map)."""
     orc, g, nz, ro, noise = _rollout_pair((64, 64), 16, 16, 24)
     g.collect_synthetic(1234, GAMMA, LAM, noise)
     theta0 = g.get_flat()

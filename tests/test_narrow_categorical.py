@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import counter_draws_ref as draws_ref
 from tests import truncation_ref as tr
 from tests.categorical_ref import CatRef, gumbel_argmax, softmax_stats
 from tests.masked_categorical_ref import masked_softmax_stats, random_masks
@@ -51,27 +52,9 @@ def assert_only_narrow_cat(kc, step=None, train=None):
             assert cnt == 0, (name, kc)
 
 
-# ---- the counter draw of policy_step_kernel<cat> / narrow_step_kernel<cat> in NumPy (csrc/ppo_kernels.hpp: ctr_hash, ctr_uniform; ppo_seed) ------------------
-M64 = (1 << 64) - 1
-
-
-def _splitmix(x):
-    x = (x + 0x9E3779B97F4A7C15) & M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
+# ---- the counter draw of policy_step_kernel<cat> / narrow_step_kernel<cat>: the NumPy model of tests/counter_draws_ref.py, rounded to the kernels' float32 ------
 def counter_uniforms(seed, n, A, step=0):
-    z = _splitmix(seed)
-    key = ((z ^ (z >> 32)) & 0xFFFFFFFF) ^ 0x3C5A96C3
-    u = np.empty((n, A), np.float32)
-    for row in range(n):
-        a = _splitmix((key << 32) | row)
-        for j in range(A):
-            h = _splitmix(a ^ ((step << 32) | j)) >> 32
-            u[row, j] = np.float32((np.float32(h >> 8) + np.float32(0.5)) * np.float32(1.0 / 16777216.0))
-    return u
+    return draws_ref.counter_uniforms(draws_ref.seed_key(seed), np.arange(n), step, A).astype(np.float32)
 
 
 def clear_margin_share(logits, u, tol):
