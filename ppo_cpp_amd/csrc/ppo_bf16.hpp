@@ -771,7 +771,7 @@ struct SampleArgsB {
     const float* mask;                  // [n, A] action mask of the categorical head (non-zero = allowed); read by the <CAT, MASK> instantiation only
 };
 
-// ---- categorical head (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD): the arithmetic of policy_step_kernel<.., CAT, MASK> / train_fwd_bwd_kernel<.., CAT, MASK> in the
+// ---- categorical head (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD): the arithmetic of policy_step_kernel<.., CAT, MASK> / train_fwd_bwd_kernel<.., CAT, MASK> (ppo_head.hpp) in the
 // geometry of the two kernels below -- one wave per row, lane l owns categories l and l + 64 -- with 64-lane __shfl_xor butterflies where those kernels reduce over 16 lanes.
 // (value, index) argmax over the wave: the larger value wins, a tie goes to the lower index; every lane ends with the same pair
 __device__ __forceinline__ void wave_argmax(float& v, int& i) {
@@ -787,7 +787,7 @@ __device__ __forceinline__ void cat_row_norm(const float (&lg)[2], const bool (&
     il = MASK ? A : 0;
 #pragma unroll
     for (int e = 0; e < 2; ++e)
-        if (ok[e] && (lg[e] > bl || (MASK && il == A))) { bl = lg[e]; il = lane + 64 * e; }
+        if (ok[e]) cat_take<MASK>(lg[e], lane + 64 * e, A, bl, il);
     wave_argmax(bl, il);
     float zs = 0.f;
 #pragma unroll
@@ -827,12 +827,12 @@ __global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(SampleArgsB a
                 u[e] = a.noise ? a.noise[(size_t)row * a.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);     // (a forbidden category keeps its uniform)
             }
         }
-        // a = argmax_j (l_j - log(-log u_j)) over the allowed set: the first allowed category is taken even when its perturbed logit is -inf (u == 0)
+        // the Gumbel argmax over the allowed set (gumbel, cat_take)
         float bp = -INFINITY;
         int ip = MASK ? a.A : 0;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const float pl = lg[e] - logf(-logf(u[e]));
+            const float pl = gumbel(lg[e], u[e]);
             if (ok[e] && (pl > bp || (MASK && ip == a.A))) { bp = pl; ip = lane + 64 * e; }
         }
         wave_argmax(bp, ip);
@@ -855,6 +855,7 @@ __global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(SampleArgsB a
         const int j = lane + 64 * e;
         if (j < a.A) {
             const float mu = live ? head_sum(a.head[0], (size_t)row * a.ldh + j, a.hsplit, a.hstride) : 0.f;
+            // gauss_std, gauss_sample and gauss_z of ppo_head.hpp, written out: through the calls the compiler pairs the two row sums up the other way round
             const float logstd = mu * 0.0f + a.logstd[j];
             const float sigma = expf(logstd);
             float eps = 0.f;
@@ -870,13 +871,13 @@ __global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(SampleArgsB a
     }
     for (int o = 32; o > 0; o >>= 1) { ssq += __shfl_xor(ssq, o); slog += __shfl_xor(slog, o); }
     if (lane == 0 && live) {
-        if (a.neglogp) a.neglogp[row] = 0.5f * ssq + HALF_LOG_2PI * (float)a.A + slog;
+        if (a.neglogp) a.neglogp[row] = gauss_nlp(ssq, slog, a.A);
         if (a.value) a.value[row] = head_sum(a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride);
     }
 }
 
 // ---- loss + its gradient w.r.t. the head outputs (G:9428-11290, G:12609-22656): the arithmetic of
-// train_fwd_bwd_kernel's middle section, 16 lanes per row, fp32; writes d mu / d v as bf16 and the
+// train_fwd_bwd_kernel's middle section (the pieces of ppo_head.hpp), one wave per row, fp32; writes d mu / d v as bf16 and the
 // per-block partial sums (bias / logstd gradients, loss terms) the gradient assembly adds up in a fixed order ---------
 struct LossArgsB {
     const float* head[2]; int ldh; int hsplit; size_t hstride;
@@ -954,43 +955,30 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
         clz = logf(cz);
         const float la = cat_row_pick(mu, ok, lane, cact);
 #pragma unroll
-        for (int e = 0; e < BL_EPT; ++e) if (ok[e]) sent += (z[e] / cz) * (clz - mu[e]);
+        for (int e = 0; e < BL_EPT; ++e) if (ok[e]) sent += cat_entropy_term(z[e], cz, clz, mu[e]);
         sent = wave_sum_all(sent);
         cnlp = clz - la;
     } else {
 #pragma unroll
-    for (int e = 0; e < BL_EPT; ++e) {
-        const int j = lane + 64 * e;
-        float m = hp[e][0];
+        for (int e = 0; e < BL_EPT; ++e) {
+            const int j = lane + 64 * e;
+            float m = hp[e][0];
 #pragma unroll
-        for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < a.hsplit) m += hp[e][k];       // the partial products in range order (head_sum)
-        mu[e] = m;
-        const float logstd = m * 0.0f + ls_[e];
-        sigma[e] = expf(logstd);
-        const float act = live ? act_[e] : m;
-        z[e] = (act - m) / sigma[e];
-        if (j < a.A) { ssq += z[e] * z[e]; slog += logstd; sent += logstd + HALF_LOG_2PIE; }
+            for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < a.hsplit) m += hp[e][k];   // the partial products in range order (head_sum)
+            mu[e] = m;
+            const GaussStd gs = gauss_std(m, ls_[e]);
+            sigma[e] = gs.sigma;
+            z[e] = gauss_z(live ? act_[e] : m, m, sigma[e]);
+            if (j < a.A) { ssq += z[e] * z[e]; slog += gs.logstd; sent += gauss_entropy_elem(gs.logstd); }
+        }
+        for (int o = 32; o > 0; o >>= 1) { ssq += __shfl_xor(ssq, o); slog += __shfl_xor(slog, o); sent += __shfl_xor(sent, o); }
     }
-    for (int o = 32; o > 0; o >>= 1) { ssq += __shfl_xor(ssq, o); slog += __shfl_xor(slog, o); sent += __shfl_xor(sent, o); }
-    }
-    const float nlp = CAT ? cnlp : 0.5f * ssq + HALF_LOG_2PI * (float)a.A + slog;
+    const float nlp = CAT ? cnlp : gauss_nlp(ssq, slog, a.A);
     const float old_nlp = live ? old_nlp_in : nlp;
-    const float lo = 1.0f - cr, hi = 1.0f + cr;
-    const float ratio = expf(old_nlp - nlp);
-    const float rmin = tf_min(ratio, hi);
-    const float rclip = tf_max(rmin, lo);
-    const float m1 = -adv * ratio, m2 = -adv * rclip;
-    const float sel = (m1 >= m2) ? 1.0f : 0.0f;                                       // G:12609
-    const float pass = ((rmin >= lo) ? 1.0f : 0.0f) * ((ratio <= hi) ? 1.0f : 0.0f);  // G:15357, 16113
-    float d_ratio = (-adv) * g * sel;
-    d_ratio += (-adv) * g * (1.0f - sel) * pass;
-    const float d_nlp = live ? -(d_ratio * ratio) : 0.0f;
+    const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
+    const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
     if (lane == 0) {
-        const float dk = nlp - old_nlp;
-        pt[r * 4 + 0] = live ? tf_max(m1, m2) : 0.f;
-        pt[r * 4 + 1] = live ? sent : 0.f;
-        pt[r * 4 + 2] = live ? dk * dk : 0.f;
-        pt[r * 4 + 3] = (live && fabsf(ratio - 1.0f) > cr) ? 1.0f : 0.f;
+        surrogate_terms(sr, nlp, old_nlp, sent, cr, live, pt, r);
     }
 #pragma unroll
     for (int e = 0; e < BL_EPT; ++e) {
@@ -998,16 +986,9 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
         if (j < a.Ap) {
             float dmu = 0.f, dl = 0.f;
             if constexpr (CAT) {
-                // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H)   (dl stays 0: no logstd; forbidden and padding columns: +0)
-                if (live && ok[e]) {
-                    const float p = z[e] / cz;
-                    dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + a.ent_coef * g * (p * ((mu[e] - clz) + sent));
-                }
-            } else
-            if (j < a.A && live) {
-                dl = d_nlp * (1.0f - z[e] * z[e]) - a.ent_coef * g;                      // AddN_2 G:21299
-                dmu = d_nlp * (-(z[e] / sigma[e])) + dl * 0.0f;                          // AddN_3 G:22656
-            }
+                // cat_grad_elem with the row's entropy (dl stays 0: no logstd; forbidden and padding columns: +0)
+                if (live && ok[e]) dmu = cat_grad_elem(d_nlp, z[e], cz, mu[e], clz, sent, j, cact, a.ent_coef, g);
+            } else if (j < a.A && live) gauss_grad_elem(d_nlp, z[e], sigma[e], a.ent_coef, g, dmu, dl);
             dmu_s[r * a.Ap + j] = dmu; dls_s[r * a.Ap + j] = dl;
             a.dhead[0][(size_t)row * a.Ap + j] = (bf16_t)dmu;
         }

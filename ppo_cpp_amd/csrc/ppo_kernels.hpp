@@ -80,6 +80,8 @@ struct NormDev {                    // EnvNormalize state for one statistics obj
 __device__ __forceinline__ float tf_min(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float tf_max(float a, float b) { return a > b ? a : b; }
 
+#include "ppo_head.hpp"      // the policy head's and the surrogate loss's per-row arithmetic, shared by every kernel family like vf_loss_row below
+
 // One row of the value loss and its gradient dv = d loss / d v (G:10213-10837, G:14975-19571), shared by every kernel family.
 // vcr = hyper[2], the value-clip range (= hyper[1], cliprange itself, under PPO_VCLIP_POLICY).  voff = hyper[3]: 0, or +inf under PPO_VCLIP_OFF, which
 // makes the clipped square -inf: every row then takes the unclipped side of the max, lossv = (v - R)^2 and dv = gv 2 (v - R) exactly (the other term of
@@ -769,9 +771,6 @@ __device__ __forceinline__ void stage_block_inputs(const NetDev& net, const floa
 #define STAMP(i) do { } while (0)
 #endif
 
-#define HALF_LOG_2PI 0.9189385175704956f   /* G:6531 */
-#define HALF_LOG_2PIE 1.4189385175704956f  /* G:10021-10180 */
-
 // policy head dispatch shared by the act and train kernels (CTH = Ap/16 for the split-K form, 0 = generic):
 // fills mus[16][Ap+PAD]; ends with a barrier
 template <int CTH> struct HeadFrag { WFrag<(CTH > 0 ? CTH : 1), HEAD_KS> w; };
@@ -891,15 +890,10 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
                 const float l = mus[r * ldm + j];
                 float u = 0.5f;
                 if (row < a.n) u = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
-                const float pl = l - logf(-logf(u));
-                if constexpr (MASK) {
-                    const bool mk = row < a.n ? a.mask[(size_t)row * net.A + j] != 0.f : true;
-                    if (mk && (pl > bp || ip == e)) { bp = pl; ip = j; }
-                    if (mk && (l > bl || il == e)) { bl = l; il = j; }
-                } else {
-                    if (pl > bp) { bp = pl; ip = j; }
-                    if (l > bl) { bl = l; il = j; }
-                }
+                const float pl = gumbel(l, u);
+                bool mk = true;
+                if constexpr (MASK) mk = row < a.n ? a.mask[(size_t)row * net.A + j] != 0.f : true;
+                if (mk) { cat_take<MASK>(pl, j, e, bp, ip); cat_take<MASK>(l, j, e, bl, il); }
             }
             group16_argmax(bp, ip);
             group16_argmax(bl, il);
@@ -923,25 +917,18 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
         if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = nlp;
         if (a.host_action && part < a.comp.K) lds[net.lds_mu + r * ldm + part] = my_a;   // (after every lane of the row has read the tile: one wave, program order)
     } else if constexpr (CAT) {
-        // a = argmax_j (l_j - log(-log u_j)), neglogp = log sum_j exp(l_j - m) - (l_a - m), m = max_j l_j (softmax cross-entropy against one_hot(a))
-        // MASK: a lane's best index starts at net.A ("none yet"), so the first ALLOWED category is taken even when its perturbed logit is -inf (u == 0) and a
-        // lane without an allowed category loses every tie of the butterfly to a real index; a row without any allowed category (which the host checks
-        // refuse) ends at net.A and is brought back inside the tile below
+        // the categorical arithmetic of ppo_head.hpp (gumbel, cat_take: the MASKed pair starts at net.A, "none yet"); a row without any allowed category (which
+        // the host checks refuse) ends at net.A and is brought back inside the tile below
         float bp = -INFINITY, bl = -INFINITY;
         int ip = MASK ? net.A : 0, il = MASK ? net.A : 0;
         for (int j = part; j < net.A; j += 16) {
             const float l = mus[r * ldm + j];
             float u = 0.5f;
             if (row < a.n) u = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
-            const float pl = l - logf(-logf(u));
-            if constexpr (MASK) {
-                const bool mk = row < a.n ? a.mask[(size_t)row * net.A + j] != 0.f : true;
-                if (mk && (pl > bp || ip == net.A)) { bp = pl; ip = j; }
-                if (mk && (l > bl || il == net.A)) { bl = l; il = j; }
-            } else {
-            if (pl > bp) { bp = pl; ip = j; }
-            if (l > bl) { bl = l; il = j; }
-            }
+            const float pl = gumbel(l, u);
+            bool mk = true;
+            if constexpr (MASK) mk = row < a.n ? a.mask[(size_t)row * net.A + j] != 0.f : true;
+            if (mk) { cat_take<MASK>(pl, j, net.A, bp, ip); cat_take<MASK>(l, j, net.A, bl, il); }
         }
         group16_argmax(bp, ip);
         group16_argmax(bl, il);
@@ -961,26 +948,24 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
         }
         if (a.host_action && part == 0) lds[net.lds_mu + r * ldm] = (float)ip;   // (after every lane of the row has read the tile: one wave, program order)
     } else {
-    float ssq = 0.f, slog = 0.f;
-    for (int j = part; j < net.A; j += 16) {
-        const float mu = mus[r * ldm + j];
-        const float logstd = mu * 0.0f + par[net.par_ls + j];
-        const float sigma = expf(logstd);
-        float eps = 0.f;
-        if (row < a.n) eps = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_normal(a.seed, a.row_base + row, a.rng_step, j);
-        const float act = mu + sigma * eps;
-        const float z = (act - mu) / sigma;
-        ssq += z * z;
-        slog += logstd;
-        if (row < a.n) {
-            if (a.action) a.action[(size_t)row * net.A + j] = act;
-            if (a.det_action) a.det_action[(size_t)row * net.A + j] = mu;
+        float ssq = 0.f, slog = 0.f;
+        for (int j = part; j < net.A; j += 16) {
+            const float mu = mus[r * ldm + j];
+            const GaussStd gs = gauss_std(mu, par[net.par_ls + j]);
+            float eps = 0.f;
+            if (row < a.n) eps = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_normal(a.seed, a.row_base + row, a.rng_step, j);
+            const float act = gauss_sample(mu, gs.sigma, eps), z = gauss_z(act, mu, gs.sigma);
+            ssq += z * z;
+            slog += gs.logstd;
+            if (row < a.n) {
+                if (a.action) a.action[(size_t)row * net.A + j] = act;
+                if (a.det_action) a.det_action[(size_t)row * net.A + j] = mu;
+            }
+            if (a.host_action) lds[net.lds_mu + r * ldm + j] = act;   // (this lane owns element (r, j): mu has been read)
         }
-        if (a.host_action) lds[net.lds_mu + r * ldm + j] = act;      // (this lane owns element (r, j): mu has been read)
-    }
-    ssq = group16_sum(ssq);
-    slog = group16_sum(slog);
-    if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+        ssq = group16_sum(ssq);
+        slog = group16_sum(slog);
+        if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = gauss_nlp(ssq, slog, net.A);
     }
     if (a.host_action) {
         // The block's rows are contiguous in the landing buffer ([16][A] floats from byte 64 A blockIdx.x): whole 16-byte pieces, the last rows' odd
@@ -1182,7 +1167,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
                 }
                 z = group16_sum(z); la = group16_sum(la);
                 const float lz = logf(z);
-                for (int j = o + part; j < e; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - m; ent += (expf(a0) / z) * (lz - a0); }
+                for (int j = o + part; j < e; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - m; ent += cat_entropy_term(expf(a0), z, lz, a0); }
                 ent = group16_sum(ent);
                 const float nk = lz - la;
                 cnlp = k == 0 ? nk : cnlp + nk;
@@ -1206,48 +1191,41 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
             }
             cz = group16_sum(cz); la = group16_sum(la);
             clz = logf(cz);
-            for (int j = part; j < net.A; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - cm; cent += (expf(a0) / cz) * (clz - a0); }
+            for (int j = part; j < net.A; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - cm; cent += cat_entropy_term(expf(a0), cz, clz, a0); }
             cent = group16_sum(cent);
             cnlp = clz - la;
         }
         float ssq = 0.f, slog = 0.f, sent = 0.f;
         if constexpr (CAT) sent = cent;
         else {
-        for (int j = part; j < net.A; j += 16) {
-            const float mu = mus[r * ldm + j];
-            const float logstd = mu * 0.0f + par[net.par_ls + j];
-            const float act = live ? acts[r * net.Ap + j] : mu;
-            const float z = (act - mu) / expf(logstd);
-            ssq += z * z;
-            slog += logstd;
-            sent += logstd + HALF_LOG_2PIE;
+            for (int j = part; j < net.A; j += 16) {
+                const float mu = mus[r * ldm + j];
+                const float ls = par[net.par_ls + j], act = live ? acts[r * net.Ap + j] : mu;
+                const GaussStd gs = gauss_std(mu, ls);
+                const float z = gauss_z(act, mu, gs.sigma);
+                ssq += z * z;
+                slog += gs.logstd;
+                sent += gauss_entropy_elem(gs.logstd);
+            }
+            ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
         }
-        ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
-        }
-        const float nlp = CAT ? cnlp : 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+        const float nlp = CAT ? cnlp : gauss_nlp(ssq, slog, net.A);
         const float adv = live ? rowv[2 * r] : 0.f;
         const float old_nlp = live ? rowv[2 * r + 1] : nlp;
-        const float lo = 1.0f - cr, hi = 1.0f + cr;
-        const float ratio = expf(old_nlp - nlp);
-        const float rmin = tf_min(ratio, hi);
-        const float rclip = tf_max(rmin, lo);
-        const float m1 = -adv * ratio, m2 = -adv * rclip;
+        const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
         const float g = a.inv_n;
-        const float sel = (m1 >= m2) ? 1.0f : 0.0f;                                   // Maximum tie rule G:12609
-        const float pass = ((rmin >= lo) ? 1.0f : 0.0f) * ((ratio <= hi) ? 1.0f : 0.0f); // G:15357, 16113
-        float d_ratio = (-adv) * g * sel;
-        d_ratio += (-adv) * g * (1.0f - sel) * pass;
-        const float d_nlp = live ? -(d_ratio * ratio) : 0.0f;
+        const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
         if (part == 0) {
+            // surrogate_terms of ppo_head.hpp, written out: through the call the <.., MASK> instantiations' two first stores come out in the other order
             const float dk = nlp - old_nlp;
-            misc[r * 4 + 0] = live ? tf_max(m1, m2) : 0.f;
+            misc[r * 4 + 0] = live ? tf_max(sr.m1, sr.m2) : 0.f;
             misc[r * 4 + 1] = live ? sent : 0.f;
             misc[r * 4 + 2] = live ? dk * dk : 0.f;
-            misc[r * 4 + 3] = (live && fabsf(ratio - 1.0f) > cr) ? 1.0f : 0.f;
+            misc[r * 4 + 3] = (live && fabsf(sr.ratio - 1.0f) > cr) ? 1.0f : 0.f;
         }
         // d mu (-> dcur tile, also the dY operand of the head weight gradient) and d logstd rows
         if constexpr (MULTI) {
-            // d loss / d l_j = d_nlp (p_j - [j == o_k + a_k]) + ent_coef g p_j (log p_j + H_k), k = j's component; forbidden and padding columns: exactly 0
+            // cat_grad_elem with the entropy H_k of j's own component; forbidden and padding columns: exactly 0
             auto put = [&](int j, float dmu) __attribute__((always_inline)) {
                 dcur[r * ldm + j] = dmu;
                 dls[r * net.Ap + j] = 0.f;
@@ -1262,34 +1240,30 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
                     float dmu = 0.f;
                     if (live && allowed(j)) {
                         const float a0 = mus[r * ldm + j] - m;
-                        const float p = expf(a0) / z;
-                        dmu = d_nlp * (p - (j == act ? 1.0f : 0.0f)) + net.ent_coef * g * (p * ((a0 - lz) + hk));
+                        dmu = cat_grad_elem(d_nlp, expf(a0), z, a0, lz, hk, j, act, net.ent_coef, g);
                     }
                     put(j, dmu);
                 }
             }
             for (int j = net.A + part; j < net.Ap; j += 16) put(j, 0.f);
-        } else
-        for (int j = part; j < net.Ap; j += 16) {
-            float dmu = 0.f, dl = 0.f;
-            if constexpr (CAT) {
-                // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H)   (dl stays 0: no logstd)
-                if (j < net.A && live && allowed(j)) {
-                    const float a0 = mus[r * ldm + j] - cm;
-                    const float p = expf(a0) / cz;
-                    dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + net.ent_coef * g * (p * ((a0 - clz) + sent));
+        } else {
+            for (int j = part; j < net.Ap; j += 16) {
+                float dl = 0.f, dmu = 0.f;
+                if constexpr (CAT) {
+                    // cat_grad_elem with the row's entropy (dl stays 0: no logstd)
+                    if (j < net.A && live && allowed(j)) {
+                        const float a0 = mus[r * ldm + j] - cm;
+                        dmu = cat_grad_elem(d_nlp, expf(a0), cz, a0, clz, sent, j, cact, net.ent_coef, g);
+                    }
+                } else if (j < net.A && live) {
+                    const float mu = mus[r * ldm + j], ls = par[net.par_ls + j], act = acts[r * net.Ap + j];
+                    const float sigma = gauss_std(mu, ls).sigma;
+                    gauss_grad_elem(d_nlp, gauss_z(act, mu, sigma), sigma, net.ent_coef, g, dmu, dl);
                 }
-            } else
-            if (j < net.A && live) {
-                const float mu = mus[r * ldm + j];
-                const float sigma = expf(mu * 0.0f + par[net.par_ls + j]);
-                const float z = (acts[r * net.Ap + j] - mu) / sigma;
-                dl = d_nlp * (1.0f - z * z) - net.ent_coef * g;                    // AddN_2 G:21299
-                dmu = d_nlp * (-(z / sigma)) + dl * 0.0f;                          // AddN_3 G:22656
+                dcur[r * ldm + j] = dmu;
+                dls[r * net.Ap + j] = dl;
+                a.dmug[(size_t)row * net.Ap + j] = dmu;         // dead rows of the last tile: zeros
             }
-            dcur[r * ldm + j] = dmu;
-            dls[r * net.Ap + j] = dl;
-            a.dmug[(size_t)row * net.Ap + j] = dmu;                // dead rows of the last tile: zeros
         }
         lds_barrier();
         // per-block partial sums: db_mu, dlogstd (over the 16 rows, fixed order), loss terms

@@ -383,7 +383,7 @@ __device__ __forceinline__ void nw_lazy_apply(const NetDev& net, const NwLayout&
 // ------------------------------------------------------------------------------------------------------------------------
 // The train step of one workgroup behind its prologue (weight image and this workgroup's rows in LDS): forward, loss, backward, weight gradients ->
 // one partial gradient vector.  Called by narrow_train_kernel and, once per minibatch, by narrow_epoch_kernel.
-// CAT: categorical head (the arithmetic of train_fwd_bwd_kernel<.., CAT>, in its order): the logits are the head product in the `mu` tile, the row's category index
+// CAT: categorical head (the arithmetic of train_fwd_bwd_kernel<.., CAT>, in its order; the formulas themselves are ppo_head.hpp's): the logits are the head product in the `mu` tile, the row's category index
 // waits in the padding column of its `mu` row and, with MASK, its mask row in the `acts` tile (nw_stage); d logits go where d mu goes, so the head-backward product and the pi/w, pi/b gradients
 // run unchanged.  The padded logstd slot has no gradient source: its partial is written as 0.  Nothing is indexed with the action or with the mask.
 template <int KP0, int HP, int AP, int LL, bool WT = true, bool CAT = false, bool MASK = false>
@@ -473,46 +473,34 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             cz = group16_sum(cz); la = group16_sum(la);
             clz = logf(cz);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) if (ok[k]) sent += (expf(zk[k]) / cz) * (clz - zk[k]);
+            for (int k = 0; k < 4; ++k) if (ok[k]) sent += cat_entropy_term(expf(zk[k]), cz, clz, zk[k]);
             sent = group16_sum(sent);
             cnlp = clz - la;
         } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {                                 // (compile-time k: the kept values stay in registers)
-            const int j = part + 16 * k;
-            zk[k] = 0.f; sk[k] = 1.f;
-            if (j < net.A) {
-                const float mu = mus[r * ldm + j];
-                const float logstd = mu * 0.0f + par[net.par_ls + j];
-                const float act = live ? acts[r * Ap + j] : mu;
-                const float sigma = expf(logstd);
-                const float z = (act - mu) / sigma;
-                zk[k] = z; sk[k] = sigma;
-                ssq += z * z; slog += logstd; sent += logstd + HALF_LOG_2PIE;
+            for (int k = 0; k < 4; ++k) {                             // (compile-time k: the kept values stay in registers)
+                const int j = part + 16 * k;
+                zk[k] = 0.f; sk[k] = 1.f;
+                if (j < net.A) {
+                    const float mu = mus[r * ldm + j];
+                    const float logstd = gauss_logstd(mu, par[net.par_ls + j]);
+                    const float act = live ? acts[r * Ap + j] : mu;
+                    const float sigma = expf(logstd);
+                    const float z = gauss_z(act, mu, sigma);
+                    zk[k] = z; sk[k] = sigma;
+                    ssq += z * z; slog += logstd; sent += gauss_entropy_elem(logstd);
+                }
             }
+            ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
         }
-        ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
-        }
-        const float nlp = CAT ? cnlp : 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+        const float nlp = CAT ? cnlp : gauss_nlp(ssq, slog, net.A);
         const float adv = live ? rowv[2 * r] : 0.f;
         const float old_nlp = live ? rowv[2 * r + 1] : nlp;
-        const float lo = 1.0f - cr, hi = 1.0f + cr;
-        const float ratio = expf(old_nlp - nlp);
-        const float rmin = tf_min(ratio, hi);
-        const float rclip = tf_max(rmin, lo);
-        const float m1 = -adv * ratio, m2 = -adv * rclip;
+        const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
         const float gg = a.inv_n;
-        const float sel = (m1 >= m2) ? 1.0f : 0.0f;                                       // G:12609
-        const float pass = ((rmin >= lo) ? 1.0f : 0.0f) * ((ratio <= hi) ? 1.0f : 0.0f);  // G:15357, 16113
-        float d_ratio = (-adv) * gg * sel;
-        d_ratio += (-adv) * gg * (1.0f - sel) * pass;
-        const float d_nlp = live ? -(d_ratio * ratio) : 0.0f;
+        const float d_nlp = surrogate_d_nlp(sr, adv, gg, live);
         if (part == 0) {
-            const float dk = nlp - old_nlp;
-            misc[r * 4 + 0] = live ? tf_max(m1, m2) : 0.f;
-            misc[r * 4 + 1] = live ? sent : 0.f;
-            misc[r * 4 + 2] = live ? dk * dk : 0.f;
-            misc[r * 4 + 3] = (live && fabsf(ratio - 1.0f) > cr) ? 1.0f : 0.f;
+            surrogate_terms(sr, nlp, old_nlp, sent, cr, live, misc, r);
         }
         float* dmu_t = P + lay.dmu;
 #pragma unroll
@@ -521,21 +509,21 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             if (j < Ap) {
                 float dmu = 0.f, dl = 0.f;
                 if constexpr (CAT) {
-                    // d loss / d l_j = d_nlp (p_j - [j == a]) + ent_coef g p_j (log p_j + H); a forbidden or padded category, a dead row: 0
+                    // cat_grad_elem (and below gauss_grad_elem) of ppo_head.hpp, written out: through the calls this kernel's loads and registers change order; forbidden / padded / dead: 0
                     if (ok[k] && live) {
                         const float a0 = zk[k];
                         const float p = expf(a0) / cz;
                         dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + net.ent_coef * gg * (p * ((a0 - clz) + sent));
                     }
-                    dmu_t[r * ldm + j] = dmu;                                                   // (no d logstd: the shared acts / dls tile keeps the mask rows)
+                    dmu_t[r * ldm + j] = dmu;                                                // (no d logstd: the shared acts / dls tile keeps the mask rows)
                 } else {
-                if (j < net.A && live) {
-                    const float z = zk[k], sigma = sk[k];
-                    dl = d_nlp * (1.0f - z * z) - net.ent_coef * gg;                          // AddN_2 G:21299
-                    dmu = d_nlp * (-(z / sigma)) + dl * 0.0f;                                 // AddN_3 G:22656
-                }
-                dmu_t[r * ldm + j] = dmu;
-                dls[r * Ap + j] = dl;
+                    if (j < net.A && live) {
+                        const float z = zk[k], sigma = sk[k];
+                        dl = d_nlp * (1.0f - z * z) - net.ent_coef * gg;                      // AddN_2 G:21299
+                        dmu = d_nlp * (-(z / sigma)) + dl * 0.0f;                             // AddN_3 G:22656
+                    }
+                    dmu_t[r * ldm + j] = dmu;
+                    dls[r * Ap + j] = dl;
                 }
             }
         }
@@ -1052,9 +1040,8 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwL
     });
     __syncthreads();
     if constexpr (CAT) {
-        // a = argmax_j (l_j - log(-log u_j)), neglogp = log sum_j exp(l_j - m) - (l_a - m), m = max_j l_j.  MASK: a lane's best index starts at net.A ("none
-        // yet"), so the first ALLOWED category is taken even when its perturbed logit is -inf, and a lane without an allowed category loses every tie of the
-        // butterfly to a real index; a row without any allowed category (refused by the host checks) ends at net.A and is brought back inside the tile
+        // the categorical arithmetic of ppo_head.hpp (gumbel, cat_take: the MASKed pair starts at net.A, "none yet"); a row without any allowed category
+        // (refused by the host checks) ends at net.A and is brought back inside the tile
         float bp = -INFINITY, bl = -INFINITY;
         int ip = MASK ? net.A : 0, il = MASK ? net.A : 0;
         float lk[4];
@@ -1065,7 +1052,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwL
             if (j < net.A) {
                 const float l = mus[r * ldm + j];
                 lk[k] = l;
-                const float pl = l - logf(-logf(uk[k]));
+                const float pl = gumbel(l, uk[k]);
                 if constexpr (MASK) {
                     if (mk[k] && (pl > bp || ip == net.A)) { bp = pl; ip = j; }
                     if (mk[k] && (l > bl || il == net.A)) { bl = l; il = j; }
@@ -1099,20 +1086,18 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwL
     float ssq = 0.f, slog = 0.f;
     for (int j = part; j < net.A; j += 16) {
         const float mu = mus[r * ldm + j];
-        const float logstd = mu * 0.0f + par[net.par_ls + j];
-        const float sigma = expf(logstd);
+        const GaussStd gs = gauss_std(mu, par[net.par_ls + j]);
         float eps = 0.f;
         if (row < a.n) eps = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_normal(a.seed, a.row_base + row, a.rng_step, j);
-        const float act = mu + sigma * eps;
-        const float z = (act - mu) / sigma;
-        ssq += z * z; slog += logstd;
+        const float act = gauss_sample(mu, gs.sigma, eps), z = gauss_z(act, mu, gs.sigma);
+        ssq += z * z; slog += gs.logstd;
         if (row < a.n) {
             if (a.action) a.action[(size_t)row * net.A + j] = act;
             if (a.det_action) a.det_action[(size_t)row * net.A + j] = mu;
         }
     }
     ssq = group16_sum(ssq); slog = group16_sum(slog);
-    if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+    if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = gauss_nlp(ssq, slog, net.A);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1181,17 +1166,15 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_collect_kernel(NetDev net, 
     float ssq = 0.f, slog = 0.f;
     for (int j = part; j < net.A; j += 16) {
         const float mu = mus[r * ldm + j];
-        const float logstd = mu * 0.0f + par[net.par_ls + j];
-        const float sigma = expf(logstd);
+        const GaussStd gs = gauss_std(mu, par[net.par_ls + j]);
         float eps = 0.f;
         if (row < E) eps = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_normal(a.seed, a.row_base + row, a.rng_step, j);
-        const float act = mu + sigma * eps;
-        const float z = (act - mu) / sigma;
-        ssq += z * z; slog += logstd;
+        const float act = gauss_sample(mu, gs.sigma, eps), z = gauss_z(act, mu, gs.sigma);
+        ssq += z * z; slog += gs.logstd;
         if (row < E && a.action) a.action[(size_t)row * net.A + j] = act;
     }
     ssq = group16_sum(ssq); slog = group16_sum(slog);
-    if (part == 0 && row < E) a.neglogp[row] = 0.5f * ssq + HALF_LOG_2PI * (float)net.A + slog;
+    if (part == 0 && row < E) a.neglogp[row] = gauss_nlp(ssq, slog, net.A);
     if (tid < E) c.done_row[tid] = c.in.done[tid];
     // ---- env transition + EnvNormalize::step bookkeeping -> S_out (the tiles of the forward pass are free now) -------------
     __syncthreads();
@@ -1466,6 +1449,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
                 int k = 0;
                 for (int j = part; j < A; j += 16, ++k) {
                     const float mu = mus[r * ldm + j];
+                    // gauss_std, gauss_sample and gauss_z of ppo_head.hpp, written out: through the calls this kernel's scalar-register allocation changes
                     const float logstd = mu * 0.0f + par[net.par_ls + j];
                     const float sigma = expf(logstd);
                     float eps = 0.f;
@@ -1682,17 +1666,15 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net
         int k = 0;
         for (int j = part; j < A; j += 16, ++k) {
             const float mu = mus[r * ldm + j];
-            const float logstd = mu * 0.0f + par[net.par_ls + j];
-            const float sigma = expf(logstd);
+            const GaussStd gs = gauss_std(mu, par[net.par_ls + j]);
             float eps = 0.f;
             if (row < E) eps = q.noise ? nz_eps[k & 3] : ctr_normal(q.seed, q.row_base + row, q.rng_step, j);
-            const float act = mu + sigma * eps;
-            const float z = (act - mu) / sigma;
-            ssq += z * z; slog += logstd;
+            const float act = gauss_sample(mu, gs.sigma, eps), z = gauss_z(act, mu, gs.sigma);
+            ssq += z * z; slog += gs.logstd;
             if (row < E) { q.ro_act[(size_t)row * A + j] = act; q.host_act[(size_t)row * A + j] = act; }
         }
         ssq = group16_sum(ssq); slog = group16_sum(slog);
-        if (part == 0 && row < E) q.ro_nlp[row] = 0.5f * ssq + HALF_LOG_2PI * (float)A + slog;
+        if (part == 0 && row < E) q.ro_nlp[row] = gauss_nlp(ssq, slog, A);
     }
     // ---- publish: the host's actions have landed, then the completion word ------------------------------------------------------------
     __threadfence_system();
@@ -1819,16 +1801,14 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
             int k = 0;
             for (int j = part_; j < A; j += 16, ++k) {
                 const float mu = mus[r * ldm + j];
-                const float logstd = mu * 0.0f + par[net.par_ls + j];
-                const float sigma = expf(logstd);
+                const GaussStd gs = gauss_std(mu, par[net.par_ls + j]);
                 const float eps = row < El ? nz_eps[k & 3] : 0.f;
-                const float act = mu + sigma * eps;
-                const float z = (act - mu) / sigma;
-                ssq += z * z; slog += logstd;
+                const float act = gauss_sample(mu, gs.sigma, eps), z = gauss_z(act, mu, gs.sigma);
+                ssq += z * z; slog += gs.logstd;
                 if (row < El) q.ro_act[((size_t)t * q.E + e0 + row) * A + j] = act;
             }
             ssq = group16_sum(ssq); slog = group16_sum(slog);
-            if (part_ == 0 && row < El) q.ro_nlp[(size_t)t * q.E + e0 + row] = 0.5f * ssq + HALF_LOG_2PI * (float)A + slog;
+            if (part_ == 0 && row < El) q.ro_nlp[(size_t)t * q.E + e0 + row] = gauss_nlp(ssq, slog, A);
         }
         // ---- env transition (counter hash) of this workgroup's environments ---------------------------------------------------------
         const uint32_t env_step = q.step0 + (uint32_t)t + 1u;

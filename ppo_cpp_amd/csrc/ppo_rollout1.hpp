@@ -234,10 +234,8 @@ __global__ __launch_bounds__(192) void narrow_rollout1_kernel(NetDev net, NwLayo
         { float c[4] = {0.f, 0.f, 0.f, 0.f}; R1_CHAIN(c, h1, w1, 64); h2 = fast_tanh(((c[0] + c[1]) + (c[2] + c[3])) + b1); }
         { float c[4] = {0.f, 0.f, 0.f, 0.f}; R1_CHAIN(c, h2, wm, 64); mu = ((c[0] + c[1]) + (c[2] + c[3])) + bmu; }
         // ---- sample + neglogp (G:5894-6672) -----------------------------------------------------------------------------------------------
-        const float logstd = mu * 0.0f + lsj;
-        const float sigma = expf(logstd);
-        const float act = mu + sigma * eps;
-        const float z = (act - mu) / sigma;
+        const GaussStd gs = gauss_std(mu, lsj);
+        const float logstd = gs.logstd, act = gauss_sample(mu, gs.sigma, eps), z = gauss_z(act, mu, gs.sigma);
         if constexpr (HOST) {
             // the action goes out FIRST (system-scope write-through stores into pinned host memory, drained, then the sequence word): the host steps its Env
             // while this wave finishes the row
@@ -252,6 +250,6 @@ __global__ __launch_bounds__(192) void narrow_rollout1_kernel(NetDev net, NwLayo
         float ssq = 0.f + zz, slog = 0.f + sl;
         if (lane + 16 < A) { ssq += zz_hi; slog += sl_hi; }
         ssq = group16_sum(ssq); slog = group16_sum(slog);
-        if (lane == 0) q.ro_nlp[t] = 0.5f * ssq + HALF_LOG_2PI * (float)A + slog;
+        if (lane == 0) q.ro_nlp[t] = gauss_nlp(ssq, slog, A);
     }
 }

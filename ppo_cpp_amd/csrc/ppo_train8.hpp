@@ -322,44 +322,28 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
 #pragma unroll
         for (int q = 0; q < NA; ++q) {
             const bool lj = ej + 32 * q < nA;
-            const float logstd = mu[q] * 0.0f + par[net.par_ls + ej + 32 * q];
-            sigma[q] = expf(logstd);
-            const float act = live ? lds[L8::ACT + er * AP + ej + 32 * q] : mu[q];
-            z[q] = (act - mu[q]) / sigma[q];
-            zz += lj ? z[q] * z[q] : 0.f; sl_ += lj ? logstd : 0.f; se_ += lj ? logstd + HALF_LOG_2PIE : 0.f;
+            const GaussStd gs = gauss_std(mu[q], par[net.par_ls + ej + 32 * q]);
+            sigma[q] = gs.sigma;
+            z[q] = gauss_z(live ? lds[L8::ACT + er * AP + ej + 32 * q] : mu[q], mu[q], sigma[q]);
+            zz += lj ? z[q] * z[q] : 0.f; sl_ += lj ? gs.logstd : 0.f; se_ += lj ? gauss_entropy_elem(gs.logstd) : 0.f;
         }
         const float ssq = t8_sum32(zz), slog = t8_sum32(sl_), sent = t8_sum32(se_);
-        const float nlp = 0.5f * ssq + HALF_LOG_2PI * (float)nA + slog;
+        const float nlp = gauss_nlp(ssq, slog, nA);
         const float adv = live ? lds[L8::ROWV + 2 * er] : 0.f;
         const float old_nlp = live ? lds[L8::ROWV + 2 * er + 1] : nlp;
-        const float lo = 1.0f - cr, hi = 1.0f + cr;
-        const float ratio = expf(old_nlp - nlp);
-        const float rmin = tf_min(ratio, hi);
-        const float rclip = tf_max(rmin, lo);
-        const float m1 = -adv * ratio, m2 = -adv * rclip;
+        const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
         const float gi = a.inv_n;
-        const float sel = (m1 >= m2) ? 1.0f : 0.0f;                                   // Maximum tie rule G:12609
-        const float pass = ((rmin >= lo) ? 1.0f : 0.0f) * ((ratio <= hi) ? 1.0f : 0.0f); // G:15357, 16113
-        float d_ratio = (-adv) * gi * sel;
-        d_ratio += (-adv) * gi * (1.0f - sel) * pass;
-        const float d_nlp = live ? -(d_ratio * ratio) : 0.0f;
+        const float d_nlp = surrogate_d_nlp(sr, adv, gi, live);
         if (ej == 0) {
-            const float dk = nlp - old_nlp;
-            misc[er * 4 + 0] = live ? tf_max(m1, m2) : 0.f;
-            misc[er * 4 + 1] = live ? sent : 0.f;
-            misc[er * 4 + 2] = live ? dk * dk : 0.f;
-            misc[er * 4 + 3] = (live && fabsf(ratio - 1.0f) > cr) ? 1.0f : 0.f;
+            surrogate_terms(sr, nlp, old_nlp, sent, cr, live, misc, er);
         }
 #pragma unroll
         for (int q = 0; q < NA; ++q) {
-            float dmu = 0.f, dl = 0.f;
-            if (ej + 32 * q < nA && live) {
-                dl = d_nlp * (1.0f - z[q] * z[q]) - net.ent_coef * gi;                 // AddN_2 G:21299
-                dmu = d_nlp * (-(z[q] / sigma[q])) + dl * 0.0f;                        // AddN_3 G:22656
-            }
-            lds[L8::MU + er * L8::LDM + ej + 32 * q] = dmu;                            // the d mu tile: A operand of the head's backward product
+            float dl = 0.f, dmu = 0.f;
+            if (ej + 32 * q < nA && live) gauss_grad_elem(d_nlp, z[q], sigma[q], net.ent_coef, gi, dmu, dl);
+            lds[L8::MU + er * L8::LDM + ej + 32 * q] = dmu;                         // the d mu tile: A operand of the head's backward product
             lds[L8::DLS + er * AP + ej + 32 * q] = dl;
-            st_wt<false>(a.dmug + (size_t)(row0 + er) * AP + ej + 32 * q, dmu);                      // dead rows / padding columns: zeros
+            st_wt<false>(a.dmug + (size_t)(row0 + er) * AP + ej + 32 * q, dmu);                   // dead rows / padding columns: zeros
         }
         lds_barrier();
         if (tid < AP) {

@@ -64,3 +64,50 @@ def test_the_pytest_tail_carries_the_finding_of_a_failed_and_an_xfailed_test(tmp
     assert "findings (tests/conftest.py)" in text
     assert any(l.startswith("FAILED") and "first differing buffer: thetaT" in l for l in tail), text
     assert any(l.startswith("XFAILED") and "handle 1 differs first at iteration 1: loss rows" in l for l in tail), text
+
+
+def _listing(kernels):
+    """A made-up device listing in the compiler's layout: {name: (body lines, vgpr_count)}."""
+    out = ["\t.amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"", "\t.text"]
+    for i, (name, (body, _)) in enumerate(kernels.items()):
+        out += ["\t.globl\t%s" % name, "\t.type\t%s,@function" % name, "%s:    ; @%s" % (name, name), "; %bb.0:"] + body
+        out += ["\t.section\t.rodata,\"a\",@progbits", "\t.amdhsa_kernel %s" % name, "\t\t.amdhsa_next_free_vgpr 8", "\t.end_amdhsa_kernel", "\t.text",
+                ".Lfunc_end%d:" % i, "\t.size\t%s, .Lfunc_end%d-%s" % (name, i, name)]
+    out += ["\t.amdgpu_metadata", "---", "amdhsa.kernels:"]
+    for name, (_, vgpr) in kernels.items():
+        out += ["  - .agpr_count:     0", "    .args:", "      - .offset:         0", "        .size:           8", "    .group_segment_fixed_size: 0",
+                "    .kernarg_segment_size: 8", "    .name:           %s" % name, "    .private_segment_fixed_size: 0", "    .sgpr_count:     10",
+                "    .sgpr_spill_count: 0", "    .symbol:         %s.kd" % name, "    .vgpr_count:     %d" % vgpr, "    .vgpr_spill_count: 0"]
+    out += ["amdhsa.target:   amdgcn-amd-amdhsa--gfx950", "...", "\t.end_amdgpu_metadata"]
+    return "\n".join(out) + "\n"
+
+
+def _body(bb, comment="", swap=False):
+    ins = ["\tv_add_f32_e32 v1, v0, v0", "\tv_mul_f32_e32 v2, v1, v1"]
+    return ["\ts_load_dwordx2 s[0:1], s[4:5], 0x0", "\ts_cbranch_scc1 .LBB%d_2%s" % (bb, comment), "; %bb.1:"] + ins[::-1 if swap else 1] + \
+           [".LBB%d_2:%s" % (bb, comment), "\ts_endpgm"]
+
+
+def test_kernel_code_diff_on_made_up_listings():
+    """tools/kernel_code_diff.py: label numbers and comments do not count; a swapped instruction, a missing kernel and a changed metadata figure are each reported."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_code_diff", os.path.join(ROOT, "tools", "kernel_code_diff.py"))
+    kcd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kcd)
+    base = kcd.parse(_listing({"_Z3fooPf": (_body(0), 8), "_Z3barPf": (_body(1), 8)}))
+    assert set(base) == {"_Z3fooPf", "_Z3barPf"} and len(base["_Z3fooPf"][0]) == 6 and base["_Z3fooPf"][1]["vgpr_count"] == 8
+
+    def diff(kernels):
+        rep = kcd.compare(base, kcd.parse(_listing(kernels)))
+        return rep, kcd.report(rep, len(base), len(kernels))
+    # the same code behind other label numbers (another kernel order) and other comments
+    rep, text = diff({"_Z3barPf": (_body(0, " ; =>This Inner Loop Header"), 8), "_Z3fooPf": (_body(1), 8)})
+    assert rep["same"] == 2 and not (rep["only_a"] or rep["only_b"] or rep["code"] or rep["meta"]), text
+    rep, text = diff({"_Z3fooPf": (_body(0, swap=True), 8), "_Z3barPf": (_body(1), 8)})
+    assert list(rep["code"]) == ["_Z3fooPf"] and rep["same"] == 1 and not rep["meta"], text
+    d = rep["code"]["_Z3fooPf"]
+    assert d["instructions"] == (5, 5) and d["same_opcodes"] and d["removed"] == d["added"] == 1 and "code differs: foo" in text, text
+    rep, text = diff({"_Z3fooPf": (_body(0), 8)})
+    assert rep["only_a"] == ["_Z3barPf"] and not rep["only_b"] and rep["same"] == 1 and "only in A: bar" in text, text
+    rep, text = diff({"_Z3fooPf": (_body(0), 8), "_Z3barPf": (_body(1), 12)})
+    assert rep["meta"] == {"_Z3barPf": {"vgpr_count": (8, 12)}} and not rep["code"] and rep["same"] == 1, text
