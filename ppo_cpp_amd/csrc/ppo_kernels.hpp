@@ -128,6 +128,8 @@ __device__ __forceinline__ float ctr_uniform(uint32_t seed, uint32_t row, uint32
     return ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
 }
 
+#include "ppo_envnorm.hpp"   // EnvNormalize / RunningStatistics arithmetic and the seeded env's transition, shared by every rollout kernel like ppo_head.hpp above
+
 // tanh on the hardware exp2 / rcp units: 1 - 2/(e^{2|x|}+1) with the sign restored, and the odd Taylor polynomial for
 // |x| < 1/16 where that form would cancel.  Absolute error <= 2 ulp of 1.0 (~1.2e-7) everywhere, ~10 instructions
 // (ocml tanhf costs ~100 per element; a 256-wide layer epilogue has 16 per lane).
@@ -2749,15 +2751,8 @@ __device__ __forceinline__ void combine_group(const float* sets, int K, int stri
 // RunningStatistics::update's merge of a batch (mean, M2, n) into column c (common/running_statistics.hpp:88-104)
 // (old_mean / old_var: the column's statistics before the merge, read by the caller ahead of the combine)
 __device__ __forceinline__ float merge_column(NormDev st, int c, double cnt, float bmean, float bM2, float nbf, float old_mean, float old_var) {
-    const double nb = (double)nbf;
-    const double tot = cnt + nb;
-    const float bvar = bM2 / (float)nb;                                        // :51-54
-    const float delta = bmean - old_mean;                                      // :90
-    const float new_mean = old_mean + (delta * (float)nb) / (float)tot;        // :94
-    const float m_a = old_var * (float)cnt;                                    // :97
-    const float m_b = bvar * (float)nb;                                        // :98
-    const float M2 = m_a + m_b + (((delta * delta) * (float)cnt) * (float)nb) / (float)tot;  // :100
-    const float v = M2 / (float)tot;                                           // :101
+    float new_mean, v;
+    rs_merge(old_mean, old_var, cnt, bmean, bM2, nbf, new_mean, v);
     st.mean[c] = new_mean;
     st.var[c] = v;
     return v;
@@ -3075,21 +3070,18 @@ __global__ void obs_normalize_kernel(const float* in, int rows, int D, NormDev s
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * D) return;
     const int j = i % D;
-    float x = (in[i] - st.mean[j]) * (1.0f / sqrtf(st.var[j] + eps));
-    x = tf_min(tf_max(x, -clip), clip);
-    out[i] = x;
+    out[i] = obs_scale_var(in[i], st.mean[j], st.var[j], eps, clip);
 }
 
 // on-device seeded synthetic env (oracle/ppo_oracle.c orc_seeded_env_step): thread per (env, lane)
 __global__ void seeded_env_kernel(uint32_t seed, int env0, int n_envs, uint32_t step, int O, float* obs, float* rew, float* dones) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int W = O + 2;
-    if (i >= n_envs * W) return;
-    const int e = i / W, j = i - e * W;
-    const uint32_t h = ctr_hash(seed, (uint32_t)(env0 + e), step, (uint32_t)j);
-    if (j < O) obs[(size_t)e * O + j] = u32_to_sym_unit(h);
-    else if (j == O) { if (rew) rew[e] = u32_to_sym_unit(h); }
-    else if (dones) dones[e] = (h % 300u == 0u) ? 1.0f : 0.0f;
+    if (i >= n_envs * (O + 2)) return;
+    int e, j;
+    const uint32_t h = seeded_env_elem(seed, env0, step, i, O, e, j);
+    if (j < O) obs[(size_t)e * O + j] = seeded_value(h);
+    else if (j == O) { if (rew) rew[e] = seeded_value(h); }
+    else if (dones) dones[e] = seeded_done(h);
 }
 
 __global__ void fill_kernel(float* p, float v, size_t n) {

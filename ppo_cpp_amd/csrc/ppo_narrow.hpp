@@ -1181,23 +1181,14 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_collect_kernel(NetDev net, 
     float* xs = lds + lay.w_total;                          // [E][O] raw observations of the NEW state
     float* rs = xs + NW_ROWS * 64;                          // [E] rewards | [E] dones | [E] returns
     for (int i = tid; i < E * (O + 2); i += NW_THREADS) {
-        const int e = i / (O + 2), j = i - e * (O + 2);
-        const uint32_t hsh = ctr_hash(c.seed, (uint32_t)(c.env0 + e), c.env_step, (uint32_t)j);
-        if (j < O) { const float x = u32_to_sym_unit(hsh); xs[e * O + j] = x; c.out.raw_obs[(size_t)e * O + j] = x; }
-        else if (j == O) rs[e] = u32_to_sym_unit(hsh);
-        else { const float d = (hsh % 300u == 0u) ? 1.0f : 0.0f; rs[NW_ROWS + e] = d; c.out.done[e] = d; }
+        int e, j;
+        const uint32_t hsh = seeded_env_elem(c.seed, c.env0, c.env_step, i, O, e, j);
+        if (j < O) { const float x = seeded_value(hsh); xs[e * O + j] = x; c.out.raw_obs[(size_t)e * O + j] = x; }
+        else if (j == O) rs[e] = seeded_value(hsh);
+        else { const float d = seeded_done(hsh); rs[NW_ROWS + e] = d; c.out.done[e] = d; }
     }
     __syncthreads();
-    // RunningStatistics::update's merge of a batch (mean, M2, n) (common/running_statistics.hpp:88-104), reading S_in, writing S_out
-    auto merge = [&](float mean0, float var0, double cnt, float bmean, float bM2, float nbf, float& mean1, float& var1) __attribute__((always_inline)) {
-        const double nb = (double)nbf, tot = cnt + nb;
-        const float bvar = bM2 / (float)nb;                                        // :51-54
-        const float delta = bmean - mean0;                                         // :90
-        mean1 = mean0 + (delta * (float)nb) / (float)tot;                          // :94
-        const float m_a = var0 * (float)cnt, m_b = bvar * (float)nb;               // :97-98
-        const float M2 = m_a + m_b + (((delta * delta) * (float)cnt) * (float)nb) / (float)tot;   // :100
-        var1 = M2 / (float)tot;                                                    // :101
-    };
+    // obs_rms.update and ret_rms.update (rs_merge) read S_in and write S_out
     if (tid < O) {
         float m1 = c.in.obs_mean[tid], v1 = c.in.obs_var[tid];
         if (c.norm_obs) {
@@ -1206,7 +1197,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_collect_kernel(NetDev net, 
             const float bmean = sum / (float)E;                                    // colwise().mean()  (:38-39)
             float m2 = 0.f;
             for (int e = 0; e < E; ++e) { const float d = xs[e * O + tid] - bmean; m2 += d * d; }
-            merge(c.in.obs_mean[tid], c.in.obs_var[tid], *c.in.obs_count, bmean, m2, (float)E, m1, v1);
+            rs_merge(c.in.obs_mean[tid], c.in.obs_var[tid], *c.in.obs_count, bmean, m2, (float)E, m1, v1);
         }
         c.out.obs_mean[tid] = m1; c.out.obs_var[tid] = v1;
         if (tid == 0) *c.out.obs_count = c.norm_obs ? (double)(float)E + *c.in.obs_count : *c.in.obs_count;     // :103
@@ -1220,16 +1211,14 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_collect_kernel(NetDev net, 
             const float bmean = sum / (float)E;
             float m2 = 0.f;
             for (int e = 0; e < E; ++e) { const float d = ret[e] - bmean; m2 += d * d; }
-            merge(*c.in.ret_mean, *c.in.ret_var, *c.in.ret_count, bmean, m2, (float)E, m1, v1);
+            rs_merge(*c.in.ret_mean, *c.in.ret_var, *c.in.ret_count, bmean, m2, (float)E, m1, v1);
         }
         *c.out.ret_mean = m1; *c.out.ret_var = v1;
         *c.out.ret_count = c.norm_rew ? (double)(float)E + *c.in.ret_count : *c.in.ret_count;
-        const float inv = 1.0f / sqrtf(v1 + c.eps);                                                    // :79
+        const float inv = en_istd(v1, c.eps);                                                    // :79
         for (int e = 0; e < E; ++e) {
-            float y = rs[e];
-            if (c.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -c.clip_rew), c.clip_rew); }
-            c.rew_out[e] = y;
-            c.out.ret[e] = ret[e] * (1.0f - rs[NW_ROWS + e]);                                          // :88-91
+            c.rew_out[e] = en_reward(rs[e], inv, c.norm_rew, c.clip_rew);
+            c.out.ret[e] = en_ret_reset(ret[e], rs[NW_ROWS + e]);                                          // :88-91
         }
     }
 }
@@ -1239,7 +1228,8 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_collect_kernel(NetDev net, 
 // rollout in ONE launch of ONE workgroup.  The policy tower's forward image is copied into LDS once; the raw observations,
 // the running statistics (EnvNormalize: obs_rms, ret_rms, the discounted returns, the done flags) live in LDS / registers
 // for the whole rollout; per env step the workgroup normalises, runs the forward pass, samples, steps the env and merges the
-// statistics -- the arithmetic of narrow_collect_kernel, statement for statement -- and only STORES leave the CU (the rollout
+// statistics -- narrow_collect_kernel's loops around the same pieces of ppo_envnorm.hpp (rs_merge, en_istd, obs_scale, en_reward,
+// en_ret_reset, seeded_env_elem) -- and only STORES leave the CU (the rollout
 // rows).  Nothing of a step waits on memory or on a launch: 7.5 us per env step (one launch each) becomes 4.4 us.
 // The value tower is not needed inside the loop (values are consumed by the GAE scan only): the host runs it afterwards as
 // one batched launch of narrow_step_kernel over the T x E normalised rows this kernel stored.
@@ -1299,7 +1289,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
         const int n4 = lay.w_fwd / 4;
         for (int e = tid; e < n4; e += NW_THREADS) reinterpret_cast<float4*>(lds)[e] = reinterpret_cast<const float4*>(q.img)[e];
         for (int i = tid; i < E * O; i += NW_THREADS) xs[i] = q.st.raw_obs[i];
-        if (tid < O) { s_mean[tid] = q.st.obs_mean[tid]; const float v0 = q.st.obs_var[tid]; s_var[tid] = v0; s_istd[tid] = 1.0f / sqrtf(v0 + q.eps); }
+        if (tid < O) { s_mean[tid] = q.st.obs_mean[tid]; const float v0 = q.st.obs_var[tid]; s_var[tid] = v0; s_istd[tid] = en_istd(v0, q.eps); }
         if (tid < E) { rs[ES + tid] = q.st.done[tid]; rs[2 * ES + tid] = q.st.ret[tid]; }
         if (tid == 0) { s_retstat[0] = *q.st.ret_mean; s_retstat[1] = *q.st.ret_var; }
     }
@@ -1311,15 +1301,6 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
     const int row = 16 * pipe + r;
     const bool have_helper = NW_PIPES == 2 && E <= 16, helper = have_helper && pipe == 1;
     float* s_eps = s_istd + 64;                             // [16][A] counter-RNG draws of the current step (written by the helper pipe)
-    auto merge = [&](float mean0, float var0, double cnt, float bmean, float bM2, float nbf, float& mean1, float& var1) __attribute__((always_inline)) {
-        const double nb = (double)nbf, tot = cnt + nb;
-        const float bvar = bM2 / (float)nb;                                        // running_statistics.hpp:51-54
-        const float delta = bmean - mean0;                                         // :90
-        mean1 = mean0 + (delta * (float)nb) / (float)tot;                          // :94
-        const float m_a = var0 * (float)cnt, m_b = bvar * (float)nb;               // :97-98
-        const float M2 = m_a + m_b + (((delta * delta) * (float)cnt) * (float)nb) / (float)tot;   // :100
-        var1 = M2 / (float)tot;                                                    // :101
-    };
 #ifdef PPO_STAMPS
 #define RSTAMP(i) do { if (q.stamps && tid == 0 && t == q.T - 1) q.stamps[i] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -1341,8 +1322,8 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
                 float m2 = 0.f;
                 for (int e = 0; e < E; ++e) { const float d = xs[e * O + tid] - bmean; m2 += d * d; }
                 float m1, v1;
-                merge(s_mean[tid], s_var[tid], obs_cnt, bmean, m2, (float)E, m1, v1);
-                s_mean[tid] = m1; s_var[tid] = v1; s_istd[tid] = 1.0f / sqrtf(v1 + q.eps);
+                rs_merge(s_mean[tid], s_var[tid], obs_cnt, bmean, m2, (float)E, m1, v1);
+                s_mean[tid] = m1; s_var[tid] = v1; s_istd[tid] = en_istd(v1, q.eps);
                 obs_cnt = (double)(float)E + obs_cnt;                                   // :103
             }
         }
@@ -1355,16 +1336,14 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
                 const float bmean = sum / (float)E;
                 float m2 = 0.f;
                 for (int e = 0; e < E; ++e) { const float d = ret[e] - bmean; m2 += d * d; }
-                merge(s_retstat[0], s_retstat[1], ret_cnt, bmean, m2, (float)E, m1, v1);
+                rs_merge(s_retstat[0], s_retstat[1], ret_cnt, bmean, m2, (float)E, m1, v1);
                 ret_cnt = (double)(float)E + ret_cnt;
             }
             s_retstat[0] = m1; s_retstat[1] = v1;
-            const float inv = 1.0f / sqrtf(v1 + q.eps);                                                    // :79
+            const float inv = en_istd(v1, q.eps);                                                    // :79
             for (int e = 0; e < E; ++e) {
-                float y = rs[e];
-                if (q.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -q.clip_rew), q.clip_rew); }
-                q.ro_rew[(size_t)tr * E + e] = y;
-                ret[e] = ret[e] * (1.0f - rs[ES + e]);                                                // :88-91
+                q.ro_rew[(size_t)tr * E + e] = en_reward(rs[e], inv, q.norm_rew, q.clip_rew);
+                ret[e] = en_ret_reset(ret[e], rs[ES + e]);                                                // :88-91
             }
         }
     };
@@ -1408,17 +1387,15 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
                 float x = 0.f;
                 if (ge < E && j < O) {
                     x = xs[ge * O + j];
-                    if (q.norm_obs) {
-                        x = (x - s_mean[j]) * s_istd[j];
-                        x = tf_min(tf_max(x, -q.clip_obs), q.clip_obs);
-                    }
+                    if (q.norm_obs) x = obs_scale(x, s_mean[j], s_istd[j], q.clip_obs);
                     q.ro_obs[((size_t)t * E + ge) * O + j] = x;
                 }
                 lds[lay.w_total + (rr >> 4) * lay.pipe_total + lay.x[0] + (rr & 15) * lay.ldx[0] + j] = x;
             }
             lds_barrier();
             RSTAMP(1);
-            // ---- forward + head (narrow_step_kernel's code) -----------------------------------------------------------------
+            // ---- forward + head: narrow_step_kernel's, written out in every kernel (as a shared piece the layer loop is shaped before it is inlined and
+            // every kernel tried came out in other machine code: profiles/EXPERIMENTS.md) ------------------------------------------------------
             for (int l = 0; l < L; ++l) {
                 const float* bias = par + net.par_b[l];
                 float* Ys = P + lay.x[l + 1]; const int ldy = lay.ldx[l + 1];
@@ -1485,11 +1462,11 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
             // ---- env transition (counter hash) -> new raw observations, rewards, dones -------------------------------------------
             const uint32_t env_step = q.step0 + (uint32_t)t + 1u;
             for (int i = tid; i < E * (O + 2); i += NW_THREADS) {
-                const int e = i / (O + 2), j = i - e * (O + 2);
-                const uint32_t hsh = ctr_hash(q.seed, (uint32_t)(q.env0 + e), env_step, (uint32_t)j);
-                if (j < O) xs[e * O + j] = u32_to_sym_unit(hsh);
-                else if (j == O) rs[e] = u32_to_sym_unit(hsh);
-                else rs[ES + e] = (hsh % 300u == 0u) ? 1.0f : 0.0f;
+                int e, j;
+                const uint32_t hsh = seeded_env_elem(q.seed, q.env0, env_step, i, O, e, j);
+                if (j < O) xs[e * O + j] = seeded_value(hsh);
+                else if (j == O) rs[e] = seeded_value(hsh);
+                else rs[ES + e] = seeded_done(hsh);
             }
         }
         lds_barrier();
@@ -1517,8 +1494,8 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
 // Host-Env rollout step for small environment counts (n_envs <= 32; BASELINE configs[1]: ONE environment stepped on the
 // host): one launch per env step instead of {H2D copy, statistics kernel, policy step of both towers, D2H copy}.
 // The kernel reads the transition the host's Env::step produced STRAIGHT from the handle's pinned host block (zero-copy over
-// PCIe: 80 bytes at one environment), does EnvNormalize::step's bookkeeping for it (env_normalize.hpp:64-116, the statements
-// of narrow_collect_kernel), then normalises the new observations, runs the policy tower, samples, stores the actions
+// PCIe: 80 bytes at one environment), does EnvNormalize::step's bookkeeping for it (env_normalize.hpp:64-116: narrow_collect_kernel's
+// loops around the pieces of ppo_envnorm.hpp), then normalises the new observations, runs the policy tower, samples, stores the actions
 // STRAIGHT into pinned host memory and raises a completion word there; the host spins on that word.  No copy-engine
 // operation and no stream query sits between the host's env step and the next action (34.6 -> ~16 us per env step at one
 // environment).  The value tower is not needed per step: one batched launch at ppo_rollout_finish.
@@ -1571,15 +1548,6 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net
     __syncthreads();
     // ---- EnvNormalize::step bookkeeping for the transition that arrived (env_normalize.hpp:64-116) ------------------------------
     if (q.has_transition) {
-        auto merge = [&](float mean0, float var0, double cnt, float bmean, float bM2, float nbf, float& mean1, float& var1) __attribute__((always_inline)) {
-            const double nb = (double)nbf, tot = cnt + nb;
-            const float bvar = bM2 / (float)nb;                                        // running_statistics.hpp:51-54
-            const float delta = bmean - mean0;                                         // :90
-            mean1 = mean0 + (delta * (float)nb) / (float)tot;                          // :94
-            const float m_a = var0 * (float)cnt, m_b = bvar * (float)nb;               // :97-98
-            const float M2 = m_a + m_b + (((delta * delta) * (float)cnt) * (float)nb) / (float)tot;   // :100
-            var1 = M2 / (float)tot;                                                    // :101
-        };
         if (tid < O && q.norm_obs) {
             const double cnt = *q.st.obs_count;
             float sum = 0.f;
@@ -1588,7 +1556,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net
             float m2 = 0.f;
             for (int e = 0; e < E; ++e) { const float d = xs[e * O + tid] - bmean; m2 += d * d; }
             float m1, v1;
-            merge(s_mean[tid], s_var[tid], cnt, bmean, m2, (float)E, m1, v1);
+            rs_merge(s_mean[tid], s_var[tid], cnt, bmean, m2, (float)E, m1, v1);
             s_mean[tid] = m1; s_var[tid] = v1;
             q.st.obs_mean[tid] = m1; q.st.obs_var[tid] = v1;
         }
@@ -1602,15 +1570,13 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net
                 const float bmean = sum / (float)E;
                 float m2 = 0.f;
                 for (int e = 0; e < E; ++e) { const float d = ret[e] - bmean; m2 += d * d; }
-                merge(*q.st.ret_mean, *q.st.ret_var, cnt, bmean, m2, (float)E, m1, v1);
+                rs_merge(*q.st.ret_mean, *q.st.ret_var, cnt, bmean, m2, (float)E, m1, v1);
                 *q.st.ret_mean = m1; *q.st.ret_var = v1; *q.st.ret_count = (double)(float)E + cnt;
             }
-            const float inv = 1.0f / sqrtf(v1 + q.eps);                                                    // :79
+            const float inv = en_istd(v1, q.eps);                                                    // :79
             for (int e = 0; e < E; ++e) {
-                float y = rs[e];
-                if (q.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -q.clip_rew), q.clip_rew); }
-                q.ro_rew_prev[e] = y;
-                q.st.ret[e] = ret[e] * (1.0f - rs[NW_ROWS + e]);                                           // :88-91
+                q.ro_rew_prev[e] = en_reward(rs[e], inv, q.norm_rew, q.clip_rew);
+                q.st.ret[e] = en_ret_reset(ret[e], rs[NW_ROWS + e]);                                           // :88-91
                 q.st.done[e] = rs[NW_ROWS + e];
             }
         }
@@ -1626,10 +1592,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net
         float x = 0.f;
         if (rr < E && j < O) {
             x = xs[rr * O + j];
-            if (q.norm_obs) {
-                x = (x - s_mean[j]) * (1.0f / sqrtf(s_var[j] + q.eps));
-                x = tf_min(tf_max(x, -q.clip_obs), q.clip_obs);
-            }
+            if (q.norm_obs) x = obs_scale_var(x, s_mean[j], s_var[j], q.eps, q.clip_obs);
             q.ro_obs[(size_t)rr * O + j] = x;
         }
         lds[lay.w_total + (rr >> 4) * lay.pipe_total + lay.x[0] + (rr & 15) * lay.ldx[0] + j] = x;
@@ -1725,7 +1688,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
         const int n4 = lay.w_fwd / 4;
         for (int e = tid; e < n4; e += NW_THREADS) reinterpret_cast<float4*>(lds)[e] = reinterpret_cast<const float4*>(q.img)[e];
         for (int i = tid; i < El * O; i += NW_THREADS) xs[i] = q.st.raw_obs[(size_t)e0 * O + i];
-        if (tid < O) { s_mean[tid] = q.st.obs_mean[tid]; const float v0 = q.st.obs_var[tid]; s_var[tid] = v0; s_istd[tid] = 1.0f / sqrtf(v0 + q.eps); }
+        if (tid < O) { s_mean[tid] = q.st.obs_mean[tid]; const float v0 = q.st.obs_var[tid]; s_var[tid] = v0; s_istd[tid] = en_istd(v0, q.eps); }
         if (tid < El) { rs[NW_ROWS + tid] = q.st.done[e0 + tid]; rs[2 * NW_ROWS + tid] = q.st.ret[e0 + tid]; }
         if (tid == 0) { s_retstat[0] = *q.st.ret_mean; s_retstat[1] = *q.st.ret_var; }
     }
@@ -1739,15 +1702,6 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
     int* s_ok = reinterpret_cast<int*>(s_retstat + 4);
     const int pw = 2 * O + 3;                               // published chunk: n | mean[O] | M2[O] | ret mean | ret M2
     float* lp = lds + lay.w_fwd;                            // all G chunks of a step, staged in LDS (the image's backward half is unused here)
-    auto merge = [&](float mean0, float var0, double cnt, float bmean, float bM2, float nbf, float& mean1, float& var1) __attribute__((always_inline)) {
-        const double nb = (double)nbf, tot = cnt + nb;
-        const float bvar = bM2 / (float)nb;                                        // running_statistics.hpp:51-54
-        const float delta = bmean - mean0;                                         // :90
-        mean1 = mean0 + (delta * (float)nb) / (float)tot;                          // :94
-        const float m_a = var0 * (float)cnt, m_b = bvar * (float)nb;               // :97-98
-        const float M2 = m_a + m_b + (((delta * delta) * (float)cnt) * (float)nb) / (float)tot;   // :100
-        var1 = M2 / (float)tot;                                                    // :101
-    };
     bool dead = false;
     for (int t = 0; t < q.T && !dead; ++t) {
         float nz_eps[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1764,10 +1718,7 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
             float x = 0.f;
             if (rr < El && j < O) {
                 x = xs[rr * O + j];
-                if (q.norm_obs) {
-                    x = (x - s_mean[j]) * s_istd[j];
-                    x = tf_min(tf_max(x, -q.clip_obs), q.clip_obs);
-                }
+                if (q.norm_obs) x = obs_scale(x, s_mean[j], s_istd[j], q.clip_obs);
                 q.ro_obs[((size_t)t * q.E + e0 + rr) * O + j] = x;
             }
             lds[lay.w_total + (rr >> 4) * lay.pipe_total + lay.x[0] + (rr & 15) * lay.ldx[0] + j] = x;
@@ -1813,11 +1764,11 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
         // ---- env transition (counter hash) of this workgroup's environments ---------------------------------------------------------
         const uint32_t env_step = q.step0 + (uint32_t)t + 1u;
         for (int i = tid; i < El * (O + 2); i += NW_THREADS) {
-            const int e = i / (O + 2), j = i - e * (O + 2);
-            const uint32_t hsh = ctr_hash(q.seed, (uint32_t)(q.env0 + e0 + e), env_step, (uint32_t)j);
-            if (j < O) xs[e * O + j] = u32_to_sym_unit(hsh);
-            else if (j == O) rs[e] = u32_to_sym_unit(hsh);
-            else rs[NW_ROWS + e] = (hsh % 300u == 0u) ? 1.0f : 0.0f;
+            int e, j;
+            const uint32_t hsh = seeded_env_elem(q.seed, q.env0 + e0, env_step, i, O, e, j);
+            if (j < O) xs[e * O + j] = seeded_value(hsh);
+            else if (j == O) rs[e] = seeded_value(hsh);
+            else rs[NW_ROWS + e] = seeded_done(hsh);
         }
         lds_barrier();
         // ---- chunk moments of my rows -> published (agent-scope stores: visible to the other XCDs without a cache-wide fence) ------
@@ -1871,8 +1822,8 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
             float m2 = 0.f;
             for (int k = 0; k < G; ++k) { const float nk = lp[k * pw], d = lp[k * pw + 1 + tid] - bmean; m2 += lp[k * pw + 1 + O + tid] + nk * (d * d); }
             float m1, v1;
-            merge(s_mean[tid], s_var[tid], obs_cnt, bmean, m2, ntot, m1, v1);
-            s_mean[tid] = m1; s_var[tid] = v1; s_istd[tid] = 1.0f / sqrtf(v1 + q.eps);
+            rs_merge(s_mean[tid], s_var[tid], obs_cnt, bmean, m2, ntot, m1, v1);
+            s_mean[tid] = m1; s_var[tid] = v1; s_istd[tid] = en_istd(v1, q.eps);
             obs_cnt = (double)ntot + obs_cnt;                                       // :103
         }
         if (tid == 64) {
@@ -1884,16 +1835,14 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_coop_kernel(NetDev 
                 const float bmean = acc / ntot;
                 float m2 = 0.f;
                 for (int k = 0; k < G; ++k) { const float nk = lp[k * pw], d = lp[k * pw + 1 + 2 * O] - bmean; m2 += lp[k * pw + 2 + 2 * O] + nk * (d * d); }
-                merge(s_retstat[0], s_retstat[1], ret_cnt, bmean, m2, ntot, m1, v1);
+                rs_merge(s_retstat[0], s_retstat[1], ret_cnt, bmean, m2, ntot, m1, v1);
                 ret_cnt = (double)ntot + ret_cnt;
             }
             s_retstat[0] = m1; s_retstat[1] = v1;
-            const float inv = 1.0f / sqrtf(v1 + q.eps);                                                    // :79
+            const float inv = en_istd(v1, q.eps);                                                    // :79
             for (int e = 0; e < El; ++e) {
-                float y = rs[e];
-                if (q.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -q.clip_rew), q.clip_rew); }
-                q.ro_rew[(size_t)t * q.E + e0 + e] = y;
-                ret[e] = ret[e] * (1.0f - rs[NW_ROWS + e]);                                                // :88-91
+                q.ro_rew[(size_t)t * q.E + e0 + e] = en_reward(rs[e], inv, q.norm_rew, q.clip_rew);
+                ret[e] = en_ret_reset(ret[e], rs[NW_ROWS + e]);                                                // :88-91
             }
         }
         lds_barrier();

@@ -5,12 +5,12 @@
 // workgroup barriers: 10.5 k cycles = 4.4 us per env step, for ONE live row.  Here the policy tower's forward weights live in
 // registers (lane n holds column n of W0, W1 and W_mu: 160 registers), an activation vector is one register per lane, and a layer
 // is a k-ordered chain of `v_readlane` + `v_fma` -- no LDS, no barrier, nothing but the rollout-row stores leaves the wave.
-// The arithmetic is narrow_collect_kernel's statement for statement, so every rollout field, the running statistics and the state
+// The arithmetic is narrow_collect_kernel's -- the env side through the same pieces of ppo_envnorm.hpp --, so every rollout field, the running statistics and the state
 // handed to the next rollout are bit-identical to the per-step launches (test_persistent_rollout_is_bitwise_the_per_step_launches):
 //   * a dense layer reproduces nw_dense<CK>: four accumulator chains, chain q taking the k-steps s = q, q+4, ... of four k values
 //     each in k order (an exact-fp32 16x16x4 matrix instruction IS that fmaf chain), combined as (c0 + c1) + (c2 + c3);
 //   * the sums over actions reproduce the 16-lanes-per-row loop (elements j and j + 16 added in that order, then group16_sum's tree);
-//   * EnvNormalize::step / RunningStatistics::update for a batch of one row (env_normalize.hpp:64-116, running_statistics.hpp:26-104).
+//   * EnvNormalize::step / RunningStatistics::update for a batch of one row (book_obs / book_reward_of below: rs_merge, en_istd, obs_scale, en_ret_reset).
 // Two more waves run AHEAD of the main wave, on their own SIMDs: the noise wave draws the counter-RNG noise of step t + 1 (two 64-bit hashes,
 // a log, a cos and a square root per draw), the env wave owns the whole environment side -- the transition that follows step t, the
 // running-statistics recurrences (four dependent divisions and a square root per step), the reward branch and the normalised
@@ -59,25 +59,48 @@ __global__ __launch_bounds__(192) void narrow_rollout1_kernel(NetDev net, NwLayo
         // ---- env wave: transition, EnvNormalize::step / RunningStatistics::update for a batch of ONE row, rollout rows obs / rewards / dones ----
         float raw = lj ? q.st.raw_obs[lane] : 0.f;
         float mean = lj ? q.st.obs_mean[lane] : 0.f, var = lj ? q.st.obs_var[lane] : 1.f;
-        float istd = 1.0f / sqrtf(var + q.eps);
+        float istd = en_istd(var, q.eps);
         float done = q.st.done[0], ret = q.st.ret[0];
         float ret_mean = *q.st.ret_mean, ret_var = *q.st.ret_var;
         double obs_cnt = *q.st.obs_count, ret_cnt = *q.st.ret_count;
-        auto merge = [&](float mean0, float var0, double cnt, float bmean, float bM2, float nbf, float& mean1, float& var1) __attribute__((always_inline)) {
-            const double nb = (double)nbf, tot = cnt + nb;
-            const float bvar = bM2 / (float)nb;                                        // running_statistics.hpp:51-54
-            const float delta = bmean - mean0;                                         // :90
-            mean1 = mean0 + (delta * (float)nb) / (float)tot;                          // :94
-            const float m_a = var0 * (float)cnt, m_b = bvar * (float)nb;               // :97-98
-            const float M2 = m_a + m_b + (((delta * delta) * (float)cnt) * (float)nb) / (float)tot;   // :100
-            var1 = M2 / (float)tot;                                                    // :101
+        // EnvNormalize::step bookkeeping for a batch of ONE row (the pieces of ppo_envnorm.hpp; the two passes over the batch with their literal `sum / 1.0f`):
+        // the observation side ...
+        auto book_obs = [&]() __attribute__((always_inline)) {
+            if (q.norm_obs) {
+                float sum = 0.f; sum += raw;
+                const float bmean = sum / 1.0f;                                        // colwise().mean()
+                float m2 = 0.f; { const float d = raw - bmean; m2 += d * d; }
+                float m1, v1;
+                rs_merge(mean, var, obs_cnt, bmean, m2, 1.0f, m1, v1);
+                mean = m1; var = v1; istd = en_istd(v1, q.eps);
+                obs_cnt = (double)1.0f + obs_cnt;                                      // :103
+            }
+        };
+        // ... and the reward side of a transition (rew, flag); its reward is rollout row t's
+        auto book_reward_of = [&](float rew, float flag, int t) __attribute__((always_inline)) {
+            ret = ret * q.gamma + rew;                                                 // env_normalize.hpp:66
+            float sum = 0.f; sum += ret;
+            float m1 = ret_mean, v1 = ret_var;
+            if (q.norm_rew) {                                                          // :75-77 (training)
+                const float bmean = sum / 1.0f;
+                float m2 = 0.f; { const float d = ret - bmean; m2 += d * d; }
+                rs_merge(ret_mean, ret_var, ret_cnt, bmean, m2, 1.0f, m1, v1);
+                ret_cnt = (double)1.0f + ret_cnt;
+            }
+            ret_mean = m1; ret_var = v1;
+            const float inv = en_istd(v1, q.eps);                                      // :79
+            // en_reward of ppo_envnorm.hpp, written out: through the call this kernel needs two more scalar registers
+            float y = rew;
+            if (q.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -q.clip_rew), q.clip_rew); }
+            if (lane == 0) q.ro_rew[t] = y;
+            ret = en_ret_reset(ret, flag);                                             // :88-91
         };
         // rollout row t: the flag that arrived with obs_t, the observation normalised with the statistics that already include it
         auto publish = [&](int t) __attribute__((always_inline)) {
             if (lane == 0) q.ro_done[t] = done;
             if (lj) {
                 float x = raw;
-                if (q.norm_obs) { x = (x - mean) * istd; x = tf_min(tf_max(x, -q.clip_obs), q.clip_obs); }   // env_normalize.hpp:99-104
+                if (q.norm_obs) x = obs_scale(x, mean, istd, q.clip_obs);
                 q.ro_obs[(size_t)t * O + lane] = x;
                 s_hand[t & 1][32 + lane] = x;
             }
@@ -97,41 +120,16 @@ __global__ __launch_bounds__(192) void narrow_rollout1_kernel(NetDev net, NwLayo
             // (hash lanes 0..O-1 = the observation, O = the reward, O+1 = the done flag: with O up to 64 the last two need lanes of their
             // own, so lanes 0 and 1 draw them in a second call)
             float tv = 0.f, tw = 0.f;
-            if (lj) tv = u32_to_sym_unit(ctr_hash(q.seed, (uint32_t)q.env0, q.step0 + (uint32_t)t + 1u, (uint32_t)lane));
+            if (lj) tv = seeded_value(seeded_env_word(q.seed, q.env0, q.step0 + (uint32_t)t + 1u, lane));
             if (lane < 2) {
-                const uint32_t hs = ctr_hash(q.seed, (uint32_t)q.env0, q.step0 + (uint32_t)t + 1u, (uint32_t)(O + lane));
-                tw = lane == 0 ? u32_to_sym_unit(hs) : ((hs % 300u == 0u) ? 1.0f : 0.0f);
+                const uint32_t hs = seeded_env_word(q.seed, q.env0, q.step0 + (uint32_t)t + 1u, O + lane);
+                tw = lane == 0 ? seeded_value(hs) : seeded_done(hs);
             }
             raw = tv;
             const float rew = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tw), 0));
             done = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tw), 1));
-            // ---- EnvNormalize::step bookkeeping for a batch of ONE row ----------------------------------------------------------------------------
-            if (q.norm_obs) {
-                float sum = 0.f; sum += raw;
-                const float bmean = sum / 1.0f;                                        // colwise().mean()
-                float m2 = 0.f; { const float d = raw - bmean; m2 += d * d; }
-                float m1, v1;
-                merge(mean, var, obs_cnt, bmean, m2, 1.0f, m1, v1);
-                mean = m1; var = v1; istd = 1.0f / sqrtf(v1 + q.eps);
-                obs_cnt = (double)1.0f + obs_cnt;                                      // :103
-            }
-            {
-                ret = ret * q.gamma + rew;                                             // env_normalize.hpp:66
-                float sum = 0.f; sum += ret;
-                float m1 = ret_mean, v1 = ret_var;
-                if (q.norm_rew) {                                                      // :75-77 (training)
-                    const float bmean = sum / 1.0f;
-                    float m2 = 0.f; { const float d = ret - bmean; m2 += d * d; }
-                    merge(ret_mean, ret_var, ret_cnt, bmean, m2, 1.0f, m1, v1);
-                    ret_cnt = (double)1.0f + ret_cnt;
-                }
-                ret_mean = m1; ret_var = v1;
-                const float inv = 1.0f / sqrtf(v1 + q.eps);                            // :79
-                float y = rew;
-                if (q.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -q.clip_rew), q.clip_rew); }
-                if (lane == 0) q.ro_rew[t] = y;
-                ret = ret * (1.0f - done);                                             // :88-91
-            }
+            book_obs();
+            book_reward_of(rew, done, t);
             if (t + 1 < q.T) publish(t + 1);
         }
         } else {
@@ -143,22 +141,7 @@ __global__ __launch_bounds__(192) void narrow_rollout1_kernel(NetDev net, NwLayo
         auto book_reward = [&]() __attribute__((always_inline)) {
             if (!owe) return;
             owe = false;
-            const float rew = owe_rew;
-            ret = ret * q.gamma + rew;                                             // env_normalize.hpp:66
-            float sum = 0.f; sum += ret;
-            float m1 = ret_mean, v1 = ret_var;
-            if (q.norm_rew) {                                                      // :75-77 (training)
-                const float bmean = sum / 1.0f;
-                float m2 = 0.f; { const float d = ret - bmean; m2 += d * d; }
-                merge(ret_mean, ret_var, ret_cnt, bmean, m2, 1.0f, m1, v1);
-                ret_cnt = (double)1.0f + ret_cnt;
-            }
-            ret_mean = m1; ret_var = v1;
-            const float inv = 1.0f / sqrtf(v1 + q.eps);                            // :79
-            float y = rew;
-            if (q.norm_rew) { y = y * inv; y = tf_min(tf_max(y, -q.clip_rew), q.clip_rew); }
-            if (lane == 0) q.ro_rew[owe_t] = y;
-            ret = ret * (1.0f - owe_done);                                         // :88-91
+            book_reward_of(owe_rew, owe_done, owe_t);
         };
         if (lane == 0) s_stop = 0;
         for (int t = q.pending ? q.t0 - 1 : q.t0; t < q.T; ++t) {
@@ -182,16 +165,7 @@ __global__ __launch_bounds__(192) void narrow_rollout1_kernel(NetDev net, NwLayo
                 if (!ok) { if (lane == 0) s_stop = 1; stopped = true; continue; }       // (one more barrier: the other waves see the flag there)
                 read_host(rew);
             }
-            // ---- EnvNormalize::step bookkeeping for a batch of ONE row: the observation side now ... ------------------------------------------------
-            if (q.norm_obs) {
-                float sum = 0.f; sum += raw;
-                const float bmean = sum / 1.0f;                                        // colwise().mean()
-                float m2 = 0.f; { const float d = raw - bmean; m2 += d * d; }
-                float m1, v1;
-                merge(mean, var, obs_cnt, bmean, m2, 1.0f, m1, v1);
-                mean = m1; var = v1; istd = 1.0f / sqrtf(v1 + q.eps);
-                obs_cnt = (double)1.0f + obs_cnt;                                      // :103
-            }
+            book_obs();                                                                // the observation side now ...
             owe = true; owe_rew = rew; owe_done = done; owe_t = t;                     // ... the reward side behind the next barrier (or at the exit)
             booked = t + 1;
             if (t + 1 < q.T) publish(t + 1);
