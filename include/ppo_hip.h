@@ -95,11 +95,28 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
  *                        logstd region keeps its place and is never moved.  With PPO_F32, or with PPO_ACT_GAUSSIAN, the flag is accepted and changes
  *                        nothing (same bits, same ppo_kernel_counts); PPO_ACT_SHAPE_KERNELS beside it on a PPO_BF16 handle is accepted and ignored (a
  *                        PPO_BF16 handle is never narrow).  Not the default (opt-in); data parallel is not available to such a handle: ppo_dist_init
- *                        refuses it ("... not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") and leaves it usable. */
+ *                        refuses it ("... not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") and leaves it usable.
+ *   PPO_ACT_PAIR_KERNELS PPO_ACT_CATEGORICAL | PPO_ACT_PAIR_KERNELS lets a categorical PPO_F32 handle take the [256,256] kernel pair when its shape qualifies as a
+ *                        Gaussian handle's would (not wide, two hidden layers of 256, padded observation and category widths <= 64 -- at most 64 categories):
+ *                        train8_kernel<cat[,mask]> + weight_grad_assemble_kernel + adam_kernel per train step instead of the generic four launches.  The head's
+ *                        arithmetic is train_fwd_bwd_kernel<cat[,mask]>'s, stated under "action masks of the categorical head" below, in train8_kernel's geometry
+ *                        (32 lanes per row; lane j owns categories j and j + 32): the d logits go where the Gaussian handle's d mu goes, the d logstd tile and
+ *                        slot words are zeros, and the padded logstd region of the weights, the gradient and both Adam slots is never moved.  A row of ones as
+ *                        mask gives the unmasked bits.  The act side is unchanged (policy_step_kernel<cat[,mask]>), and so are the epoch gather, ppo_update's
+ *                        captured graph (kernel nodes only) and the Adam launch.  ppo_kernel_counts names, counted INSTEAD of "train8_kernel":
+ *                        "train8_kernel<cat>", "train8_kernel<cat,mask>"; "weight_grad_assemble_kernel" keeps its one name.  PPO_HIP_NO_T8 and PPO_HIP_NO_DW2
+ *                        act exactly as on a Gaussian handle: with PPO_HIP_NO_T8=1 the handle runs train_fwd_bwd_kernel<cat[,mask]> in front of
+ *                        weight_grad_assemble_kernel (minibatches that are whole 64-row chunks), with PPO_HIP_NO_DW2=1 train8_kernel<cat[,mask]> in front of
+ *                        weight_grad_kernel + grad_reduce_kernel.  A shape that does not qualify runs the generic categorical kernels, as without the flag
+ *                        (same bits, same ppo_kernel_counts); with PPO_ACT_GAUSSIAN, with PPO_BF16, or beside PPO_ACT_SHAPE_KERNELS on a narrow shape the flag
+ *                        is accepted and changes nothing.  ppo_create_multi takes no flags: a multi-categorical handle stays on the generic kernels.  Not the
+ *                        default (opt-in); data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... not
+ *                        supported for a categorical handle created with PPO_ACT_PAIR_KERNELS") and leaves it usable.  ppo_action_dist reports the low bits only. */
 #define PPO_ACT_GAUSSIAN    0
 #define PPO_ACT_CATEGORICAL 1
 #define PPO_ACT_SHAPE_KERNELS 0x100
 #define PPO_ACT_BF16_HEAD 0x200
+#define PPO_ACT_PAIR_KERNELS 0x400
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out);
 int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_CATEGORICAL */
 /* ---- multi-categorical head: several independent choices per step (stable-baselines' MultiCategoricalProbabilityDistribution; env side: a multi-discrete space) ----
@@ -325,6 +342,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t noptepochs, int
  * and the clip+Adam launches, and ppo_norm_* merge their batch moments across ranks. */
 int ppo_dist_unique_id(char uid[128]);
 /* (a categorical handle created with PPO_ACT_SHAPE_KERNELS is refused: "... data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS";
+ *  one on which PPO_ACT_PAIR_KERNELS took effect likewise: "... data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
 int ppo_dist_world(const ppo_handle* h);
@@ -378,7 +396,7 @@ int ppo_prof_read(ppo_handle* h, int max, char names[][32], double* total_ms, in
 int ppo_sync(ppo_handle* h);
 /* which kernel VARIANT the calls so far took: the library picks its kernels from the shape, and a caller or a
  * test can ask which ones were ENQUEUED since ppo_create (a hipGraph capture counts once, its replays do not).  names: e.g.
- * "train8_kernel", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
+ * "train8_kernel", "train8_kernel<cat>", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
 int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued);
 
 /* ---- debug: a raw device buffer by name, padding included (the getters above copy the dense part of every tensor) ----------------

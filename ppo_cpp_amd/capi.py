@@ -58,6 +58,7 @@ ACTION_DISTS = {"gaussian": 0, "categorical": 1, "multi_categorical": 2}   # PPO
 MAX_COMPONENTS = 16                                     # PPO_MAX_COMPONENTS
 ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS, OR-ed into ppo_create_ex's action_dist
 ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, likewise
+ACT_PAIR_KERNELS = 0x400                                # PPO_ACT_PAIR_KERNELS, likewise
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -73,6 +74,9 @@ class PPOHip:
     bf16_head=True (PPO_ACT_BF16_HEAD; default False): with action_dist="categorical" and compute_dtype=1 (PPO_BF16) the handle runs the bf16
     matrix-core path with a categorical head (at most 128 categories; masks included; no data parallel).  Without it that combination is
     refused; on a compute_dtype=0 or Gaussian handle it changes nothing.
+    pair_kernels=True (PPO_ACT_PAIR_KERNELS; default False): a categorical compute_dtype=0 handle with hidden [256, 256] and at most 64 observations /
+    categories trains with train8_kernel<cat[,mask]> + weight_grad_assemble_kernel instead of the generic kernels (no data parallel); any other
+    shape, a Gaussian handle and a compute_dtype=1 handle are not affected.
 
     action_dist="multi_categorical", nvec=[n_0, .., n_{K-1}] (ppo_create_multi): K independent categorical components over sum(nvec) logits;
     act_dim may be None or must equal sum(nvec).  Actions are (n, K) float arrays, column k the index within component k; noise and masks keep
@@ -86,7 +90,7 @@ class PPOHip:
     MASK_FIELDS = {"masks": 8}                  # [T, E, A]; a masking handle only (set_action_masking)
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
-    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, **overrides):
+    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, **overrides):
         multi = action_dist == "multi_categorical"
         if nvec is not None and not multi:
             raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
@@ -112,13 +116,15 @@ class PPOHip:
         self.action_dist = action_dist
         self.shape_kernels = bool(shape_kernels)
         self.bf16_head = bool(bf16_head)
+        self.pair_kernels = bool(pair_kernels)
         self._act_shape = (act_dim,) if action_dist == "gaussian" else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
             nv = (C.c_int32 * max(len(nvec), 1))(*nvec)
             if self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h)) != 0:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())
-        elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0), C.byref(h)) != 0:
+        elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)
+                                    | (ACT_PAIR_KERNELS if pair_kernels else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)

@@ -64,7 +64,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_POLICY_STEP_CAT, KV_TRAIN_FB_CAT, KV_GAE_TRUNC, KV_GAE_LONG_TRUNC, KV_TVAL_SCATTER, KV_POLICY_STEP_CAT_MASK, KV_TRAIN_FB_CAT_MASK, KV_STEP_HOST_ACTION,
                      KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK,
                      KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK,
-                     KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK, KV_COUNT };
+                     KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK,
+                     KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -78,7 +79,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence"
                                        "bf16_step_sequence<cat>", "bf16_step_sequence<cat,mask>", "bf16_train_sequence<cat>", "bf16_train_sequence<cat,mask>",
                                        // a multi-categorical handle (ppo_create_multi): counted INSTEAD of the <cat> names of the generic fp32 family
-                                       "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>"};
+                                       "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>",
+                                       // a categorical handle created with PPO_ACT_PAIR_KERNELS on a [256,256] shape: counted INSTEAD of "train8_kernel"
+                                       "train8_kernel<cat>", "train8_kernel<cat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -108,6 +111,7 @@ struct ppo_handle {
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical handle may take the narrow family (build_narrow_layout)
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
+    bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
@@ -1258,6 +1262,14 @@ static void launch_train8(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
     PAIR_DISPATCH(h, X);
 #undef X
 }
+// its categorical forms (a handle created with PPO_ACT_PAIR_KERNELS): the same carve, the same dynamic LDS
+template <bool MASK>
+static void launch_train8_cat(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+#define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL; \
+                        hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+    PAIR_DISPATCH(h, X);
+#undef X
+}
 // peer: the tiles' finishers push to the peers' regions themselves
 static void launch_dw2(ppo_handle* h, const Dw2Args& da, bool peer) {
 #define X(KP0, AP) do { const size_t lds = sizeof(float) * Dw2L<KP0, AP>::LDS_FLOATS; \
@@ -1271,7 +1283,9 @@ static bool set_lds_pair(const ppo_handle* h) {
     bool ok = true;
     auto set = [&](const void* f, size_t floats) { ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * floats)) == hipSuccess; };
 #define X(KP0, AP) do { set((const void*)weight_grad_assemble_peer_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
-                        set((const void*)weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); } while (0)
+                        set((const void*)weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); \
+                        if (h->dist == PPO_ACT_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false>, T8L<KP0, AP>::TOTAL); \
+                                                              set((const void*)train8_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); } } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
     return ok;
@@ -1481,11 +1495,14 @@ static void launch_train_fb(ppo_handle* h, dim3 grid, const TrainArgs& ta0) {
 static int enqueue_train_fb(ppo_handle* h, const TrainArgs& ta, int n_pad) {
     ProfScope ps(h, PK_TRAIN_FB);
     const dim3 grid(n_pad / ROWS_PER_BLOCK, 2);
-    const bool cat = h->dist == PPO_ACT_CATEGORICAL;              // (a mask: a categorical handle, the entry points check; t8: Gaussian and not wide, ppo_create_ex)
+    const bool cat = h->dist == PPO_ACT_CATEGORICAL;              // (a mask: a categorical handle, the entry points check; t8: not wide, Gaussian or categorical with PPO_ACT_PAIR_KERNELS, ppo_create_ex)
     const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;
+    const bool cat8 = cat && h->t8;
     if (multi) ++h->kv[ta.mask ? KV_TRAIN_FB_MCAT_MASK : KV_TRAIN_FB_MCAT];
+    else if (cat8) ++h->kv[ta.mask ? KV_TRAIN8_CAT_MASK : KV_TRAIN8_CAT];
     else ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : cat ? KV_TRAIN_FB_CAT : h->t8 ? KV_TRAIN8 : KV_TRAIN_FB];
     if (multi) { if (ta.mask) launch_train_fb<true, true, true>(h, grid, ta); else launch_train_fb<true, false, true>(h, grid, ta); }
+    else if (cat8) { if (ta.mask) launch_train8_cat<true>(h, grid, ta); else launch_train8_cat<false>(h, grid, ta); }
     else if (ta.mask) launch_train_fb<true, true>(h, grid, ta);
     else if (cat) launch_train_fb<true, false>(h, grid, ta);
     else if (h->t8) launch_train8(h, grid, ta);
@@ -1726,11 +1743,12 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     *out = nullptr;
     if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
     if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
-    const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the two flags; whatever else is left must be a distribution
+    const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the flags; whatever else is left must be a distribution
     const bool bf16_head = (action_dist & PPO_ACT_BF16_HEAD) != 0;
-    action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD);
+    const bool pair_kernels = (action_dist & PPO_ACT_PAIR_KERNELS) != 0;
+    action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS);
     if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
-        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD; "
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
                              "a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
@@ -1748,6 +1766,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     h->dist = action_dist;
     h->shape_kernels = shape_kernels && action_dist == PPO_ACT_CATEGORICAL;       // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
+    h->pair_kernels = pair_kernels && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
     h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : action_dist == PPO_ACT_MULTI_CATEGORICAL ? n_components : cfg->act_dim;
     if (action_dist == PPO_ACT_MULTI_CATEGORICAL) {
         h->comp.K = n_components;
@@ -1814,11 +1833,12 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
         return bail(0);
     build_narrow_layout(h);
     if (upload_grad_src(h)) return bail(0);
+    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels;        // the heads train8_kernel has; a categorical one only where the flag asks for it
     { const char* e = getenv("PPO_HIP_NO_DW2"); const NetDev& nn = h->net;
-      h->dw2 = !(e && e[0] == '1') && h->dist == PPO_ACT_GAUSSIAN && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
+      h->dw2 = !(e && e[0] == '1') && pair_head && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
     { const char* e = getenv("PPO_HIP_NO_T8"); const NetDev& nn = h->net;
       // any observation / action width up to 64 (tiles of 32 or 64 columns) in front of hidden [256,256]
-      h->t8 = !(e && e[0] == '1') && h->dist == PPO_ACT_GAUSSIAN && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64;
+      h->t8 = !(e && e[0] == '1') && pair_head && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64;
       if ((h->t8 || h->dw2) && !set_lds_pair(h)) {
           fail(h, "hipFuncSetAttribute failed for train8_kernel / weight_grad_assemble_kernel"); return bail(0); } }
     if (h->dw2) {
@@ -1848,6 +1868,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
             HIP_OK(h, hipStreamSynchronize(h->stream));
         }
     }
+    if (h->dist == PPO_ACT_CATEGORICAL) h->pair_kernels = h->t8 || h->dw2;        // from here on: the flag took effect (a shape that does not qualify, both switches set: it did not)
     if (h->bf.on && bf16_create(h)) return bail(0);
     if (h->narrow) {
         attr_ok = true;
@@ -3629,6 +3650,7 @@ int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
     if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
+    if (h->pair_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS (create it without the flag)");
     if (load_rccl(h->rccl, h->err)) return -1;
     HIP_OK(h, hipSetDevice(h->device));
     UidByValue u;

@@ -49,6 +49,11 @@ __device__ __forceinline__ void t8_st_wt2(float* p, float x, float y) {
 }
 // sum over the 32 lanes of a half-wave
 __device__ __forceinline__ float t8_sum32(float v) { v = group16_sum(v); v += __shfl_xor(v, 16); return v; }
+// maximum over the same 32 lanes, the same butterfly (the categorical head's row maximum; -inf marks a lane without an allowed category)
+__device__ __forceinline__ float t8_max32(float v) {
+    v = tf_max(v, dpp_move<0xB1>(v)); v = tf_max(v, dpp_move<0x4E>(v)); v = tf_max(v, dpp_move<0x141>(v)); v = tf_max(v, dpp_move<0x140>(v));
+    return tf_max(v, __shfl_xor(v, 16));
+}
 
 // one 32-deep stage of a [16 x 64] output chunk: 8 k-steps x 4 column tiles
 __device__ __forceinline__ void t8_mma_stage(const WFrag<4, 2>& f, f32x4 (&acc)[4]) {
@@ -132,8 +137,16 @@ __device__ __forceinline__ void t8_exchange(const f32x4 (&acc)[4], float* xch, i
 // The kernel's body.  The big workspaces leave write-through (T8_WT: they drain while the kernel computes); the small outputs -- x0g, dmug, slots -- are plain
 // stores left to the kernel boundary.  (Round 5 also called this body as the first phase of a fused train + weight-gradient launch; measured slower twice and removed
 // in round 6: profiles/r05_a_*, branch experiments-r05.)  bx / by / gx: the launch's block index (x, y) and grid width.
-template <int KP0, int AP>
+// CAT: categorical head (a handle created with PPO_ACT_CATEGORICAL | PPO_ACT_PAIR_KERNELS) -- train_fwd_bwd_kernel<.., CAT>'s arithmetic in this kernel's geometry.
+// `actions` holds ONE float per row, the category index: the prologue parks it in MISC[64 + row] (the loss terms use MISC[0, 64)).  The logits are mu[q]; lane ej of a
+// row owns categories ej and, with a 64-column tile, ej + 32; maximum, normaliser, the action's logit and the entropy meet over the row's 32 lanes.  d logits go where
+// d mu goes (the MU tile, dmug); the DLS tile and the slot_aux words are zeros (no pi/logstd).  Only the prologue's action load and the head block differ.
+// MASK (with CAT): thread (er, ej) requests a.mask[(row0 + er) nA + ej + 32 q] where the Gaussian form requests its action elements and parks them in the ACT tile; the
+// same lane reads them back.  Forbidden categories are excluded from maximum, normaliser, neglogp and entropy and their d logits are exactly +0; a dead row reads nothing
+// and counts every category as allowed.  A row of ones gives the unmasked form's bits.  Nothing is indexed with the action or the mask.
+template <int KP0, int AP, bool CAT = false, bool MASK = false>
 __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& a, float* lds, const unsigned bx, const unsigned by, const unsigned gx) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
     typedef T8L<KP0, AP> L8;
     constexpr int KS0 = KP0 / 16, KSA = AP / 16;       // k-steps of 16 in the first layer / in the head's backward product
     constexpr int CTA = AP / 16;                       // column tiles of the policy head (all AP columns in every wave)
@@ -169,14 +182,19 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
 #pragma unroll
     for (int q = 0; q < NX; ++q) { ov[q] = 0.f; if (erow_live && ej + 32 * q < nO) ov[q] = a.obs[(size_t)(row0 + er) * nO + ej + 32 * q]; }
 #pragma unroll
-    for (int q = 0; q < NA; ++q) { av_[q] = 0.f; if (tower == 0 && erow_live && ej + 32 * q < nA) av_[q] = a.actions[(size_t)(row0 + er) * nA + ej + 32 * q]; }
-    float r0 = 0.f, r1 = 0.f, r2 = 0.f, s0 = 0.f, s1 = 1.f;
+    for (int q = 0; q < NA; ++q) {
+        av_[q] = 0.f;
+        if constexpr (MASK) { if (tower == 0 && erow_live && ej + 32 * q < nA) av_[q] = a.mask[(size_t)(row0 + er) * nA + ej + 32 * q]; }
+        else if constexpr (!CAT) { if (tower == 0 && erow_live && ej + 32 * q < nA) av_[q] = a.actions[(size_t)(row0 + er) * nA + ej + 32 * q]; }
+    }
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f, s0 = 0.f, s1 = 1.f, rc = 0.f;
     const bool explicit_adv = a.advs != nullptr;
     if (tid < 16 && row0 + tid < a.n) {
         const int src = row0 + tid;
         if (tower == 0) {
             r0 = explicit_adv ? a.advs[src] : a.returns[src]; r2 = a.old_neglogp[src];
             if (!explicit_adv) { r1 = a.old_values[src]; s0 = a.adv_stats[0]; s1 = a.adv_stats[1]; }
+            if constexpr (CAT) rc = a.actions[src];                                      // the row's category index
         } else { r0 = a.returns[src]; r2 = a.old_values[src]; }
     }
     const float* W0 = uni(a.theta + net.w_off[tower][0]);
@@ -206,7 +224,7 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         lds[L8::X0 + er * L8::LD0 + ej + 32 * q] = ov[q];
         if (tower == 0) st_wt<false>(a.x0g + (size_t)(row0 + er) * KP0 + ej + 32 * q, ov[q]);         // rows >= n and padding columns: zeros
     }
-    if (tower == 0) {
+    if (tower == 0 && (MASK || !CAT)) {                                                  // (CAT without MASK: the ACT tile is not used)
 #pragma unroll
         for (int q = 0; q < NA; ++q) lds[L8::ACT + er * AP + ej + 32 * q] = av_[q];
     }
@@ -216,6 +234,7 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         const bool live = row0 + tid < a.n;
         lds[L8::ROWV + 2 * tid] = live ? v0 : 0.f;
         lds[L8::ROWV + 2 * tid + 1] = live ? r2 : 0.f;
+        if constexpr (CAT) { if (tower == 0) lds[L8::MISC + 64 + tid] = rc; }
     }
     STAMP(22);
     lds_barrier();
@@ -318,17 +337,50 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         STAMP(6);                                                                      // (the scratch lies over d2, which the head's backward product writes: behind the barrier that follows the d mu tile)
         // ---- surrogate loss (G:9428-11290) and its gradient (G:12609-22656): one lane per (row, action) ---------------------------
         const bool live = erow_live;
-        float z[NA], sigma[NA], zz = 0.f, sl_ = 0.f, se_ = 0.f;
+        float z[NA], sigma[NA], nlp, sent;
+        // categorical: ok = the category exists and is allowed; over those, m = max l, a0 = l - m, ex = exp(a0), cz = sum ex, clz = log cz
+        bool ok[NA];
+        float a0[NA], ex[NA], cz = 1.f, clz = 0.f;
+        int cact = -1;
+        if constexpr (CAT) {
+            cact = live ? (int)lds[L8::MISC + 64 + er] : -1;
+            float bl = -INFINITY;
 #pragma unroll
-        for (int q = 0; q < NA; ++q) {
-            const bool lj = ej + 32 * q < nA;
-            const GaussStd gs = gauss_std(mu[q], par[net.par_ls + ej + 32 * q]);
-            sigma[q] = gs.sigma;
-            z[q] = gauss_z(live ? lds[L8::ACT + er * AP + ej + 32 * q] : mu[q], mu[q], sigma[q]);
-            zz += lj ? z[q] * z[q] : 0.f; sl_ += lj ? gs.logstd : 0.f; se_ += lj ? gauss_entropy_elem(gs.logstd) : 0.f;
+            for (int q = 0; q < NA; ++q) {
+                ok[q] = ej + 32 * q < nA;
+                if constexpr (MASK) ok[q] = ok[q] && (!live || lds[L8::ACT + er * AP + ej + 32 * q] != 0.f);
+                bl = ok[q] ? tf_max(bl, mu[q]) : bl;
+            }
+            const float cm = t8_max32(bl);
+            float zs = 0.f, las = 0.f, es = 0.f;
+#pragma unroll
+            for (int q = 0; q < NA; ++q) {
+                a0[q] = mu[q] - cm;
+                ex[q] = expf(a0[q]);
+                zs += ok[q] ? ex[q] : 0.f;
+                las += (ok[q] && ej + 32 * q == cact) ? a0[q] : 0.f;                       // the action's a0: one lane's element, zeros elsewhere
+            }
+            cz = t8_sum32(zs);
+            const float la = t8_sum32(las);
+            clz = logf(cz);
+#pragma unroll
+            for (int q = 0; q < NA; ++q) es += ok[q] ? cat_entropy_term(ex[q], cz, clz, a0[q]) : 0.f;
+            sent = t8_sum32(es);
+            nlp = clz - la;
+        } else {
+            float zz = 0.f, sl_ = 0.f, se_ = 0.f;
+#pragma unroll
+            for (int q = 0; q < NA; ++q) {
+                const bool lj = ej + 32 * q < nA;
+                const GaussStd gs = gauss_std(mu[q], par[net.par_ls + ej + 32 * q]);
+                sigma[q] = gs.sigma;
+                z[q] = gauss_z(live ? lds[L8::ACT + er * AP + ej + 32 * q] : mu[q], mu[q], sigma[q]);
+                zz += lj ? z[q] * z[q] : 0.f; sl_ += lj ? gs.logstd : 0.f; se_ += lj ? gauss_entropy_elem(gs.logstd) : 0.f;
+            }
+            const float ssq = t8_sum32(zz), slog = t8_sum32(sl_);
+            sent = t8_sum32(se_);
+            nlp = gauss_nlp(ssq, slog, nA);
         }
-        const float ssq = t8_sum32(zz), slog = t8_sum32(sl_), sent = t8_sum32(se_);
-        const float nlp = gauss_nlp(ssq, slog, nA);
         const float adv = live ? lds[L8::ROWV + 2 * er] : 0.f;
         const float old_nlp = live ? lds[L8::ROWV + 2 * er + 1] : nlp;
         const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
@@ -340,7 +392,8 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
 #pragma unroll
         for (int q = 0; q < NA; ++q) {
             float dl = 0.f, dmu = 0.f;
-            if (ej + 32 * q < nA && live) gauss_grad_elem(d_nlp, z[q], sigma[q], net.ent_coef, gi, dmu, dl);
+            if constexpr (CAT) { if (ok[q] && live) dmu = cat_grad_elem(d_nlp, ex[q], cz, a0[q], clz, sent, ej + 32 * q, cact, net.ent_coef, gi); }   // d l_j; forbidden / padding columns, dead rows: +0
+            else if (ej + 32 * q < nA && live) gauss_grad_elem(d_nlp, z[q], sigma[q], net.ent_coef, gi, dmu, dl);
             lds[L8::MU + er * L8::LDM + ej + 32 * q] = dmu;                         // the d mu tile: A operand of the head's backward product
             lds[L8::DLS + er * AP + ej + 32 * q] = dl;
             st_wt<false>(a.dmug + (size_t)(row0 + er) * AP + ej + 32 * q, dmu);                   // dead rows / padding columns: zeros
@@ -454,4 +507,12 @@ __global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArg
     extern __shared__ __attribute__((aligned(16))) float lds[];
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs)>();
     train8_body<KP0, AP>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}
+// the categorical forms, train8_kernel<KP0, AP, CAT, MASK>: an OVERLOAD, not two defaulted parameters of the template above -- the Gaussian kernels keep their
+// symbols (and tools/kernel_code_diff.py pairs them with every earlier build's)
+template <int KP0, int AP, bool CAT, bool MASK>
+__global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs)>();
+    train8_body<KP0, AP, CAT, MASK>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
 }

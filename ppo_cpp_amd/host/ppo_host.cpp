@@ -175,14 +175,15 @@ struct ppo_host_args {
     unsigned long long seed;     // PPO2::seed (exploration noise + epoch shuffles)
     int obs_dim, act_dim;        // SeededEnvMock's shape (0 = 18): 36 / 18 is the hexapod with observed velocities (hexapod_closed_loop_env.hpp:20)
     float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
-    int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for)
+    int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), 2 = PPO_ACT_PAIR_KERNELS
     int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD)
     int n_components, nvec[16];  // ppo_host_learn_multi: the components of MultiDiscreteTargetEnv (act_dim is their sum)
     int multi_masked;            // ppo_host_learn_multi: the environments also carry IActionMask
 };
-// the handle's action_dist for `env`: PPO2's choice, plus the opt-in a categorical head needs on the bf16 path
+// the handle's action_dist for `env`: PPO2's choice, plus the opt-ins: the [256,256] pair for a categorical head, the one such a head needs on the bf16 path
 static int32_t host_action_dist(Env& env, const ppo_host_args* a) {
-    const int32_t d = PPO2::action_dist_for(env, a->discrete_kernels != 0);
+    int32_t d = PPO2::action_dist_for(env, a->discrete_kernels == 1);
+    if (a->discrete_kernels == 2 && (d & 0xff) == PPO_ACT_CATEGORICAL) d |= PPO_ACT_PAIR_KERNELS;
     return (a->compute_dtype == PPO_BF16 && (d & 0xff) == PPO_ACT_CATEGORICAL) ? (d | PPO_ACT_BF16_HEAD) : d;
 }
 struct ppo_host_result {

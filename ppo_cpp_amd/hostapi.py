@@ -17,9 +17,10 @@ class HostArgs(C.Structure):
 
 
 def _discrete_kernels(name):
-    if name not in ("generic", "narrow"):
-        raise ValueError("discrete_kernels must be 'generic' or 'narrow', not %r" % (name,))
-    return int(name == "narrow")
+    """ppo_host_args::discrete_kernels: 0 = the generic categorical kernels, 1 = PPO_ACT_SHAPE_KERNELS, 2 = PPO_ACT_PAIR_KERNELS"""
+    if name not in ("generic", "narrow", "pair"):
+        raise ValueError("discrete_kernels must be 'generic', 'narrow' or 'pair', not %r" % (name,))
+    return {"generic": 0, "narrow": 1, "pair": 2}[name]
 
 
 class HostResult(C.Structure):
@@ -111,7 +112,8 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
-    PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "generic" (the default): without.
+    PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "pair": with PPO_ACT_PAIR_KERNELS (hidden [256, 256]: train8_kernel<cat[,mask]> +
+    weight_grad_assemble_kernel), "generic" (the default): without either.
     compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD.
     nvec=[n_0, ..]: MultiDiscreteTargetEnv with these components (act_dim is ignored: their sum) and a multi-categorical handle (PPO2::create_handle ->
     ppo_create_multi), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)

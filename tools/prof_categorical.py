@@ -2,6 +2,8 @@
 (ppo_prof_read) of one ppo_train_step on a 2048-row minibatch (B / 32) and of one collect_synthetic; the three handles alternate round by round.
 --shape_kernels adds a categorical handle created with PPO_ACT_SHAPE_KERNELS ("categorical_narrow"); --hidden 64,64 [--envs E --steps T] picks a shape where that
 flag selects the narrow kernels (tools/prof_action_mask.py has the same options and also times the policy step and an update epoch).
+--pair adds categorical handles created with PPO_ACT_PAIR_KERNELS ("categorical_pair": train8_kernel<cat> + weight_grad_assemble_kernel) and the masked train step of
+both the flagged and the generic categorical handle (half of the categories forbidden), all alternated with the Gaussian default in the same rounds.
 --bf16: the categorical head of the bf16 path instead (PPO_ACT_BF16_HEAD) at configs[4]'s shape (256 obs, 64 actions / categories, [1024,1024,1024], 8192 x 16: 4096-row
 minibatches; --hidden / --envs / --steps still apply): bf16 Gaussian, bf16 categorical, bf16 categorical under a random mask (the train step; the seeded device env's collect
 samples unmasked) and the wide fp32 categorical form, in alternating rounds"""
@@ -25,8 +27,14 @@ SHAPE_KERNELS = "--shape_kernels" in ARGV
 if SHAPE_KERNELS:
     ARGV.remove("--shape_kernels")
 M, ROUNDS, REPS = E * T // 32, 4, 20
+PAIR = "--pair" in ARGV
+if PAIR:
+    ARGV.remove("--pair")
 MASKED = set()
 VARIANTS = ([("categorical_narrow", "categorical+", {})] if SHAPE_KERNELS else []) + [("categorical", "categorical", {}), ("gaussian_generic", "gaussian", {"PPO_HIP_NO_T8": "1", "PPO_HIP_NO_DW2": "1"}), ("gaussian_default", "gaussian", {})]
+if PAIR:      # "%" = PPO_ACT_PAIR_KERNELS
+    VARIANTS = [("categorical_pair", "categorical%", {}), ("categorical_pair_masked", "categorical%", {}), ("categorical_masked", "categorical", {})] + VARIANTS
+    MASKED = {"categorical_pair_masked", "categorical_masked"}
 if BF16:      # (name, distribution, creation-time environment): "*" = compute_dtype PPO_BF16 (+ PPO_ACT_BF16_HEAD on a categorical handle)
     VARIANTS = [("bf16_gaussian", "gaussian*", {}), ("bf16_categorical", "categorical*", {}), ("bf16_categorical_masked", "categorical*", {}), ("f32_categorical_wide", "categorical", {})]
     MASKED = {"bf16_categorical_masked"}
@@ -37,7 +45,8 @@ def make(dist, env):
         os.environ.pop(k, None)
     os.environ.update(env)
     bf = dist.endswith("*")
-    g = ppo_cpp_amd.PPOHip(O, A, HIDDEN, action_dist=dist.rstrip("+*"), shape_kernels=dist.endswith("+"), bf16_head=bf and dist.startswith("categorical"), compute_dtype=int(bf))
+    g = ppo_cpp_amd.PPOHip(O, A, HIDDEN, action_dist=dist.rstrip("+*%"), shape_kernels=dist.endswith("+"), bf16_head=bf and dist.startswith("categorical"), compute_dtype=int(bf),
+                           pair_kernels=dist.endswith("%"))
     for k in env:
         os.environ.pop(k)
     g.init_orthogonal(0); g.norm_init(E); g.rollout_alloc(E, T)
