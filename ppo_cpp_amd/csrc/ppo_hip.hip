@@ -937,10 +937,10 @@ int bf16_forward(ppo_handle* h, int Rp, const bf16_t* x0_override = nullptr) {
     return 0;
 }
 
-int bf16_stage(ppo_handle* h, const float* obs, int nrows, int Rp, ObsNorm nz, float* obs_out) {
-    ppo_handle::Bf16& b = h->bf;
+// nrows observation rows -> Rp bf16 operand rows at X (null: the step's own block, x0)
+int bf16_stage(ppo_handle* h, const float* obs, int nrows, int Rp, ObsNorm nz, float* obs_out, bf16_t* X = nullptr) {
     const NetDev& n = h->net;
-    StageArgsB sa{obs, nrows, n.O, n.Kp0, Rp, nz, obs_out, b.x0};
+    StageArgsB sa{obs, nrows, n.O, n.Kp0, Rp, nz, obs_out, X ? X : h->bf.x0};
     const size_t cnt = (size_t)Rp * n.Kp0;
     if (n.O % 4 == 0 && n.Kp0 % 4 == 0) hipLaunchKernelGGL(bf16_stage4_kernel, dim3(bf16_stage4_grid(n.Kp0, cnt / 4)), dim3(256), 0, h->stream, sa);
     else hipLaunchKernelGGL(bf16_stage_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, sa);
@@ -1656,23 +1656,17 @@ float* which_buf(ppo_handle* h, int which) { return which == 0 ? h->theta : whic
 
 ObsNorm no_norm() { return ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}; }
 
-// GAE scan: one lane per env (coalesced across envs); few envs x long rollouts take the LDS form (bit-identical)
-void launch_gae(ppo_handle* h, const float* rew, const float* val, const float* done, const float* last_val, const float* last_done, int T, int E,
+// GAE scan: one lane per env (coalesced across envs); few envs x long rollouts take the LDS form (bit-identical).  tv: the terminal values of time-limit
+// truncations [T,E], or null for the plain scan
+void launch_gae(ppo_handle* h, const float* rew, const float* val, const float* done, const float* last_val, const float* last_done, const float* tv, int T, int E,
                 float gamma, float lam, float* ret) {
-    if (E <= 64 && T >= 128 && (size_t)3 * T * sizeof(float) <= 60 * 1024)
-        hipLaunchKernelGGL(gae_long_kernel, dim3(E), dim3(GAE_LONG_THREADS), (size_t)3 * T * sizeof(float), h->stream, rew, val, done, last_val, last_done, T, E, gamma, lam, ret);
-    else hipLaunchKernelGGL(gae_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, rew, val, done, last_val, last_done, T, E, gamma, lam, ret);
-}
-// ... with the terminal values of time-limit truncations (tv [T,E], never null here): the same selection rule, the sibling kernels
-void launch_gae_trunc(ppo_handle* h, const float* rew, const float* val, const float* done, const float* last_val, const float* last_done, const float* tv, int T, int E,
-                      float gamma, float lam, float* ret) {
-    if (E <= 64 && T >= 128 && (size_t)3 * T * sizeof(float) <= 60 * 1024) {
-        ++h->kv[KV_GAE_LONG_TRUNC];
-        hipLaunchKernelGGL(gae_long_trunc_kernel, dim3(E), dim3(GAE_LONG_THREADS), (size_t)3 * T * sizeof(float), h->stream, rew, val, done, last_val, last_done, tv, T, E, gamma, lam, ret);
-    } else {
-        ++h->kv[KV_GAE_TRUNC];
-        hipLaunchKernelGGL(gae_trunc_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, rew, val, done, last_val, last_done, tv, T, E, gamma, lam, ret);
-    }
+    const bool lds = E <= 64 && T >= 128 && (size_t)3 * T * sizeof(float) <= 60 * 1024;
+    const dim3 grid(lds ? E : (E + 255) / 256), block(lds ? GAE_LONG_THREADS : 256);
+    const size_t shm = lds ? (size_t)3 * T * sizeof(float) : 0;
+    if (tv) {
+        ++h->kv[lds ? KV_GAE_LONG_TRUNC : KV_GAE_TRUNC];
+        hipLaunchKernelGGL(lds ? gae_long_trunc_kernel : gae_trunc_kernel, grid, block, shm, h->stream, rew, val, done, last_val, last_done, tv, T, E, gamma, lam, ret);
+    } else hipLaunchKernelGGL(lds ? gae_long_kernel : gae_kernel, grid, block, shm, h->stream, rew, val, done, last_val, last_done, T, E, gamma, lam, ret);
 }
 
 }  // namespace
@@ -2294,8 +2288,7 @@ int ppo_gae_ex(ppo_handle* h, const float* rewards, const float* values, const f
     if (terminal_values) HIP_OK(h, hipMemcpyAsync(h->st_obs, terminal_values, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     {
         ProfScope ps(h, PK_GAE);
-        if (terminal_values) launch_gae_trunc(h, h->st_vec[0], h->st_vec[1], h->st_vec[2], h->st_vec[3], h->st_vec[4], h->st_obs, T, E, gamma, lam, h->st_vec[5]);
-        else launch_gae(h, h->st_vec[0], h->st_vec[1], h->st_vec[2], h->st_vec[3], h->st_vec[4], T, E, gamma, lam, h->st_vec[5]);
+        launch_gae(h, h->st_vec[0], h->st_vec[1], h->st_vec[2], h->st_vec[3], h->st_vec[4], terminal_values ? h->st_obs : nullptr, T, E, gamma, lam, h->st_vec[5]);
         HIP_OK(h, hipGetLastError());
     }
     HIP_OK(h, hipMemcpyAsync(returns, h->st_vec[5], n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2593,8 +2586,7 @@ static int enqueue_finish(ppo_handle* h, float gamma, float lam, const float* tv
     a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.value = h->last_val; a.nz = obs_norm(h); a.n = h->E;
     if (launch_step(h, a)) return -1;
     ProfScope ps(h, PK_GAE);
-    if (tval) launch_gae_trunc(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, tval, h->T, h->E, gamma, lam, h->ro_ret);
-    else launch_gae(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, h->T, h->E, gamma, lam, h->ro_ret);
+    launch_gae(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, tval, h->T, h->E, gamma, lam, h->ro_ret);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -3390,14 +3382,7 @@ static int enqueue_epoch_gather(ppo_handle* h, int nmb) {
     if (!h->bf.on) return 0;
     ppo_handle::Bf16& bb = h->bf;
     bb.epoch_staged = fuse_stage || (M % GB_PAD == 0 && bb.xe_rows >= B);
-    if (bb.epoch_staged && !fuse_stage) {
-        StageArgsB sa{h->mb_obs, B, h->net.O, h->net.Kp0, B, no_norm(), nullptr, bb.xe};
-        const size_t cnt = (size_t)B * h->net.Kp0;
-        if (h->net.O % 4 == 0 && h->net.Kp0 % 4 == 0) hipLaunchKernelGGL(bf16_stage4_kernel, dim3(bf16_stage4_grid(h->net.Kp0, cnt / 4)), dim3(256), 0, h->stream, sa);
-        else hipLaunchKernelGGL(bf16_stage_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, sa);
-        HIP_OK(h, hipGetLastError());
-    }
-    return 0;
+    return bb.epoch_staged && !fuse_stage ? bf16_stage(h, h->mb_obs, B, B, no_norm(), nullptr, bb.xe) : 0;
 }
 
 static int enqueue_epoch_prepare(ppo_handle* h, int ep, int nmb, bool explicit_perms) {

@@ -1,6 +1,6 @@
 """Every on-device random draw of the library as an exact function of integers, in NumPy (uint64 / float64), written from the definitions in
-csrc/ppo_kernels.hpp (splitmix64_dev, ctr_hash, ctr_normal, ctr_uniform, keyed_bijection, epoch_prepare_kernel) and csrc/ppo_hip.hip (ppo_seed,
-upload_epoch_keys, enqueue_epoch_index) -- and the comparison rules tests/test_counter_draws.py holds the device to.
+csrc/ppo_kernels.hpp (splitmix64_dev, ctr_hash, ctr_normal, ctr_uniform), csrc/ppo_epoch.hpp (keyed_bijection, shuffle_row, storage_row /
+storage_row_gathered, epoch_prepare_kernel) and csrc/ppo_hip.hip (ppo_seed, upload_epoch_keys, enqueue_epoch_index) -- and the comparison rules tests/test_counter_draws.py holds the device to.
 
 Exploration noise.  A draw is keyed by (key, row, step, lane):
     ctr_hash(key, row, step, lane) = splitmix64(splitmix64(key << 32 | row) ^ (step << 32 | lane)) >> 32

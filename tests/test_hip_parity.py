@@ -137,6 +137,32 @@ def test_gae_and_advantage_normalisation_kernels():
         close(g.adv_normalize(r, v), o.adv_normalize(r, v), rtol=2e-5, atol=2e-6)
 
 
+@pytest.mark.parametrize("E,T,nmb", [(3, 37, 3),        # M = 37: fewer rows than threads; B = 111 of 128, so the permutation walks cycles
+                                     (8, 320, 2),       # M = 1280: more than one stride of the 1024 threads
+                                     (3, 2731, 1)])     # M = 8193 > EPG_MAX_M: epoch_prepare_kernel + epoch_gather_kernel, two launches
+def test_epoch_advantages_are_bitwise_adv_normalize(E, T, nmb, monkeypatch):
+    """The epoch kernels and adv_normalize_kernel take their two-pass statistics through the same pieces (csrc/ppo_epoch.hpp) in the same order: after one single-rank
+    update every minibatch's advantages are adv_normalize of the returns and values gathered beside them, as bytes, and advstats holds the mean and the
+    denominator that reproduce them."""
+    import ppo_cpp_amd
+    monkeypatch.setenv("PPO_HIP_NO_NARROW", "1")
+    g = ppo_cpp_amd.PPOHip(18, 18, [16, 8, 8])
+    g.init_orthogonal(2)
+    g.norm_init(E); g.rollout_alloc(E, T)
+    g.collect_synthetic(1234, GAMMA, LAM, None)
+    g.update(LR, CR, 1, nmb, None, seed=7)
+    B, M = E * T, E * T // nmb
+    adv, ret, val = [g.debug_buffer(nm)[:B].view(np.float32) for nm in ("mb_adv", "mb_ret", "mb_val")]
+    stats = g.debug_buffer("advstats")[:2 * nmb].view(np.float32)
+    assert adv.size == B and np.isfinite(adv).all() and np.isfinite(stats).all() and np.abs(adv).max() > 0
+    for k in range(nmb):
+        R, V = ret[k * M:(k + 1) * M], val[k * M:(k + 1) * M]
+        np.testing.assert_array_equal(adv[k * M:(k + 1) * M].view(np.uint32), g.adv_normalize(R, V).view(np.uint32), err_msg="minibatch %d" % k)
+        mean, den = stats[2 * k], stats[2 * k + 1]
+        np.testing.assert_array_equal(adv[k * M:(k + 1) * M].view(np.uint32), (((R - V) - mean) / den).view(np.uint32), err_msg="advstats of minibatch %d" % k)
+    g.close()
+
+
 @pytest.mark.parametrize("E", [1, 7, 64, 4096, 5000, 150000])      # 5000: the reward job's apply pass takes a second batch; 150000: chunks longer than a thread keeps in registers
 def test_running_statistics_and_normalisation(E):
     _, g = pair((4, 5), "ginit")
