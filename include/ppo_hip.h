@@ -109,7 +109,7 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
  *                        weight_grad_assemble_kernel (minibatches that are whole 64-row chunks), with PPO_HIP_NO_DW2=1 train8_kernel<cat[,mask]> in front of
  *                        weight_grad_kernel + grad_reduce_kernel.  A shape that does not qualify runs the generic categorical kernels, as without the flag
  *                        (same bits, same ppo_kernel_counts); with PPO_ACT_GAUSSIAN, with PPO_BF16, or beside PPO_ACT_SHAPE_KERNELS on a narrow shape the flag
- *                        is accepted and changes nothing.  ppo_create_multi takes no flags: a multi-categorical handle stays on the generic kernels.  Not the
+ *                        is accepted and changes nothing.  A multi-categorical handle has no such kernels: ppo_create_multi_ex accepts the flag and ignores it.  Not the
  *                        default (opt-in); data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... not
  *                        supported for a categorical handle created with PPO_ACT_PAIR_KERNELS") and leaves it usable.  ppo_action_dist reports the low bits only. */
 #define PPO_ACT_GAUSSIAN    0
@@ -134,13 +134,30 @@ int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_
  * Masks are [n, A] as for the categorical head and exclude per component; a row of ones gives the unmasked bits.  The host checks (before anything is uploaded;
  * each message names row and component): every COMPONENT of every mask row allows a category; a ppo_train_step_masked row's action k is allowed by its
  * component's mask; every action value of ppo_train_step / of an uploaded rollout field 1 is an integer in [0, n_k).
- * Runs the generic PPO_F32 kernel family only (never the narrow, train8 or bf16 forms).  ppo_kernel_counts names, counted INSTEAD of the <cat> ones:
- * "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>".  Data parallel and both shuffles work as
- * for a categorical PPO_F32 handle.
+ * Runs the generic PPO_F32 kernel family (never the train8 or bf16 forms; the narrow family only through ppo_create_multi_ex's flag, below).  ppo_kernel_counts names,
+ * counted INSTEAD of the <cat> ones: "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>".
+ * Data parallel and both shuffles work as for a categorical PPO_F32 handle.
  * Errors of ppo_create_multi, each naming the limit: n_components outside 1..PPO_MAX_COMPONENTS, a component with fewer than 2 categories, cfg->act_dim != sum of
  * nvec, compute_dtype PPO_BF16.  ppo_create_ex(cfg, PPO_ACT_MULTI_CATEGORICAL, ..) stays an "unknown action_dist" error: the table has to come with the call. */
 #define PPO_ACT_MULTI_CATEGORICAL 2
 int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out);
+/* ppo_create_multi with flags (ppo_create_multi(cfg, nvec, K, out) is ppo_create_multi_ex(cfg, nvec, K, 0, out): same checks, same messages, same bits).
+ *   PPO_ACT_SHAPE_KERNELS  lets the handle take the narrow LDS-resident family under the rule of a flagged categorical handle: PPO_F32, every hidden width <= 64,
+ *                        at most 4 hidden layers, padded observation and logit widths <= 64 (so sum of nvec <= 64), the image fits 160 KB, PPO_HIP_NO_NARROW
+ *                        unset.  Then step, deterministic act, value, train step, update, rollout (device env and host Env, copy form, [E, K] action rows),
+ *                        masks and the truncation bootstrap run narrow_step_kernel<mcat[,mask]> (one launch per env step) and
+ *                        narrow_train_kernel<mcat[,mask]> + narrow_reduce_kernel + adam_kernel per train step, with the arithmetic stated above per component.
+ *                        One component gives the bits of a flagged categorical handle; a row of ones as mask gives the unmasked bits; the same seed draws what
+ *                        the generic <mcat> kernels draw.  ppo_kernel_counts names, counted INSTEAD of the <cat> and the generic names:
+ *                        "narrow_step_kernel<mcat>", "narrow_step_kernel<mcat,mask>", "narrow_train_kernel<mcat>", "narrow_train_kernel<mcat,mask>".  A shape
+ *                        that does not qualify runs the generic <mcat> kernels, as without the flag (data parallel included).  Not the default (opt-in).
+ *                        Measured at (18, (6, 6, 6), [64,64]): train step 0.76 / 0.71 of the generic one's time at 64 / 2048 rows, policy step 0.90 / 0.95 at
+ *                        16 / 1024 rows; it lost at no row count measured.  A shape whose plain image exceeds 160 KB takes a compact tile layout.
+ *                        Data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... not supported for a
+ *                        multi-categorical handle created with PPO_ACT_SHAPE_KERNELS") and leaves it usable.
+ *   PPO_ACT_PAIR_KERNELS, PPO_ACT_BF16_HEAD  accepted, nothing to select (the head has no such kernels); compute_dtype PPO_BF16 stays refused.
+ * Any other bit is an error ("ppo_create_multi_ex: unknown flag bit 0x.."). */
+int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out);
 /* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian handle, 1 with nvec[0] = A for a categorical one */
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec);
 /* columns of one action row: A (Gaussian), 1 (categorical) or K (multi-categorical) */
@@ -342,6 +359,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t noptepochs, int
  * and the clip+Adam launches, and ppo_norm_* merge their batch moments across ranks. */
 int ppo_dist_unique_id(char uid[128]);
 /* (a categorical handle created with PPO_ACT_SHAPE_KERNELS is refused: "... data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS";
+ *  a multi-categorical one on which that flag took effect (ppo_create_multi_ex) likewise: "... for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS";
  *  one on which PPO_ACT_PAIR_KERNELS took effect likewise: "... data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);

@@ -65,7 +65,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK,
                      KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK,
                      KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK,
-                     KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_COUNT };
+                     KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK,
+                     KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -81,7 +82,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a multi-categorical handle (ppo_create_multi): counted INSTEAD of the <cat> names of the generic fp32 family
                                        "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>",
                                        // a categorical handle created with PPO_ACT_PAIR_KERNELS on a [256,256] shape: counted INSTEAD of "train8_kernel"
-                                       "train8_kernel<cat>", "train8_kernel<cat,mask>"};
+                                       "train8_kernel<cat>", "train8_kernel<cat,mask>",
+                                       // a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (ppo_create_multi_ex) on a narrow shape: counted INSTEAD of the <cat> and the generic names
+                                       "narrow_step_kernel<mcat>", "narrow_step_kernel<mcat,mask>", "narrow_train_kernel<mcat>", "narrow_train_kernel<mcat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -109,11 +112,11 @@ struct ppo_handle {
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
-    bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical handle may take the narrow family (build_narrow_layout)
+    bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
     bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian), 1 (categorical: the category index) or K (multi-categorical)
-    CompTable comp{};                 // multi-categorical (ppo_create_multi): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
+    CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
     // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
     bool masking = false;
@@ -561,22 +564,29 @@ void build_narrow_layout(ppo_handle* h) {
     for (int l = 1; l < n.L; ++l) region(n.Hp[l], n.Hp[l - 1], NW_WPAD, lay.wt[l], lay.wt_ld[l]);
     region(n.Ap, n.Hp[n.L - 1], NW_WPAD, lay.wht, lay.wht_ld);
     lay.w_total = ru(o, 4);
-    int p = 0;
-    lay.x[0] = p; lay.ldx[0] = n.Kp0 + NW_XPAD; p += 16 * lay.ldx[0];
-    for (int l = 0; l < n.L; ++l) { lay.x[l + 1] = p; lay.ldx[l + 1] = n.Hp[l] + NW_XPAD; p += 16 * lay.ldx[l + 1]; }
-    for (int l = 0; l < n.L; ++l) { lay.dy[l] = p; lay.ldy[l] = n.Hp[l] + NW_XPAD; p += 16 * lay.ldy[l]; }
-    lay.ldm = n.Ap + NW_XPAD;
-    lay.mu = p; p += 16 * lay.ldm;
-    lay.dmu = p; p += 16 * lay.ldm;
-    // actions and d logstd share ONE tile: element (r, j) of both belongs to the same lane of the loss block, which reads its action in the first pass (and keeps what
-    // it needs in registers) and stores d logstd there in the second; the next rows' actions arrive behind the train body's last read of the tile (nw_stage before it,
-    // narrow_epoch_kernel behind its barrier).  16 Ap floats per pipe less: 50 observations with 40 categories ([64,64]) fit the 160 KB with it
-    lay.acts = p; lay.dls = p; p += 16 * n.Ap;
-    lay.rowv = p; p += 32;
-    lay.misc = p; p += 64;
-    lay.pipe_total = ru(p, 4);
-    lay.lds_total = lay.w_total + NW_PIPES * lay.pipe_total;
-    if ((size_t)lay.lds_total * sizeof(float) > 160 * 1024) return;
+    // compact (a multi-categorical handle whose plain image does not fit, L >= 2): two tiles of the loss block share their floats with tiles that are first
+    // written behind the block's barrier.  The logits (`mu`) are read for the last time in the head block and lie over dy[0], which the hidden-layer backward
+    // loop writes first; the mask rows (`acts`; a categorical head has no d logstd rows) lie over dy[L-1], which the head-backward product writes first.  Both
+    // writers stand behind the __syncthreads() that ends the head block, and the step kernel has no dy tiles at all.  Offsets only: the kernels are the same code.
+    auto tiles = [&](bool compact) {
+        int p = 0;
+        lay.x[0] = p; lay.ldx[0] = n.Kp0 + NW_XPAD; p += 16 * lay.ldx[0];
+        for (int l = 0; l < n.L; ++l) { lay.x[l + 1] = p; lay.ldx[l + 1] = n.Hp[l] + NW_XPAD; p += 16 * lay.ldx[l + 1]; }
+        for (int l = 0; l < n.L; ++l) { lay.dy[l] = p; lay.ldy[l] = n.Hp[l] + NW_XPAD; p += 16 * lay.ldy[l]; }
+        lay.ldm = n.Ap + NW_XPAD;
+        if (compact && 16 * lay.ldm <= 16 * lay.ldy[0]) lay.mu = lay.dy[0]; else { lay.mu = p; p += 16 * lay.ldm; }
+        lay.dmu = p; p += 16 * lay.ldm;
+        // actions and d logstd share ONE tile: element (r, j) of both belongs to the same lane of the loss block, which reads its action in the first pass (and keeps what
+        // it needs in registers) and stores d logstd there in the second; the next rows' actions arrive behind the train body's last read of the tile (nw_stage before it,
+        // narrow_epoch_kernel behind its barrier).  16 Ap floats per pipe less: 50 observations with 40 categories ([64,64]) fit the 160 KB with it
+        if (compact && 16 * n.Ap <= 16 * lay.ldy[n.L - 1]) { lay.acts = lay.dy[n.L - 1]; lay.dls = lay.acts; } else { lay.acts = p; lay.dls = p; p += 16 * n.Ap; }
+        lay.rowv = p; p += 32;
+        lay.misc = p; p += 64;
+        lay.pipe_total = ru(p, 4);
+        lay.lds_total = lay.w_total + NW_PIPES * lay.pipe_total;
+        return (size_t)lay.lds_total * sizeof(float) <= 160 * 1024;
+    };
+    if (!tiles(false) && !(h->dist == PPO_ACT_MULTI_CATEGORICAL && n.L >= 2 && tiles(true))) return;
     h->nw = lay;
     h->nw_stride = ru(h->P_pad + 8, 64);
     // compile-time shape of the reference's own network (18 obs / 18 act padded to 32, [64,64]); anything else runs the
@@ -1082,6 +1092,8 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 // only: every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the fused host step) asks
 // nw_gauss() where it is decided.
 static bool nw_cat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_CATEGORICAL; }
+// ... and a multi-categorical one (ppo_create_multi_ex with the flag): narrow_step_kernel / narrow_train_kernel<mcat[,mask]> only, under the same rule
+static bool nw_mcat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_MULTI_CATEGORICAL; }
 static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
 
 // policy_step_kernel: the (CT, KS, CTH, WIDE) ladder of the handle's layout, once; the caller picks the head
@@ -1111,13 +1123,29 @@ void launch_narrow_step(ppo_handle* h, const StepArgs& a) {
     NW_DISPATCH(h, X);
 #undef X
 }
+// its multi-categorical forms: the component table rides behind the arguments, as in launch_step_t
+template <bool MASK>
+void launch_narrow_step_multi(ppo_handle* h, const StepArgs& a) {
+    const dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
+    StepArgsM sa;
+    static_cast<StepArgs&>(sa) = a;
+    sa.theta = h->nw_img;
+    sa.comp = h->comp;
+    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, true, MASK, true>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
+    NW_DISPATCH(h, X);
+#undef X
+}
 int launch_step(ppo_handle* h, const StepArgs& a) {
-    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (never bf16, never narrow: ppo_create_multi, build_narrow_layout)
+    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (never bf16; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
     const bool cat = h->dist == PPO_ACT_CATEGORICAL;
     if (a.mask && !cat && !multi) return fail(h, "policy step: an action mask needs a categorical handle");
     if (h->bf.on) { ++h->kv[a.mask ? KV_BF16_STEP_CAT_MASK : cat ? KV_BF16_STEP_CAT : KV_BF16_STEP]; return launch_step_bf16(h, a); }
     ProfScope ps(h, PK_STEP);
-    if (h->narrow) {                                              // (a categorical handle here: created with PPO_ACT_SHAPE_KERNELS)
+    if (nw_mcat(h)) {
+        ++h->kv[a.mask ? KV_NARROW_STEP_MCAT_MASK : KV_NARROW_STEP_MCAT];
+        if (a.mask) launch_narrow_step_multi<true>(h, a); else launch_narrow_step_multi<false>(h, a);
+    } else if (h->narrow) {                                       // (a categorical handle here: created with PPO_ACT_SHAPE_KERNELS)
         ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : cat ? KV_NARROW_STEP_CAT : h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP];
         if (a.mask) launch_narrow_step<true, true>(h, a); else if (cat) launch_narrow_step<true, false>(h, a); else launch_narrow_step<false, false>(h, a);
     } else {
@@ -1442,6 +1470,18 @@ static void launch_narrow_train(ppo_handle* h, int groups, const NwTrainArgs& na
 #undef X
 }
 
+// its multi-categorical forms (never deferred): the component table rides behind the arguments
+template <bool MASK>
+static void launch_narrow_train_multi(ppo_handle* h, int groups, const NwTrainArgs& na0) {
+    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+    NwTrainArgsM na;
+    static_cast<NwTrainArgs&>(na) = na0;
+    na.comp = h->comp;
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true, MASK, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na)
+    NW_DISPATCH(h, X);
+#undef X
+}
+
 static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
     const int groups = (ta.n + NW_ROWS - 1) / NW_ROWS;
     {
@@ -1450,8 +1490,10 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
                        h->nw_partials, groups, h->nw_stride, nullptr, ta.mask};
         SET_STAMPS(na.stamps, true, 0);
         NwLazyArgs z{};
-        ++h->kv[nw_cat(h) ? (ta.mask ? KV_NARROW_TRAIN_CAT_MASK : KV_NARROW_TRAIN_CAT) : h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
-        if (nw_cat(h)) {                                          // (never deferred: nw_lazy is a Gaussian handle's)
+        ++h->kv[nw_mcat(h) ? (ta.mask ? KV_NARROW_TRAIN_MCAT_MASK : KV_NARROW_TRAIN_MCAT) : nw_cat(h) ? (ta.mask ? KV_NARROW_TRAIN_CAT_MASK : KV_NARROW_TRAIN_CAT) :
+                h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
+        if (nw_mcat(h)) { if (na.mask) launch_narrow_train_multi<true>(h, groups, na); else launch_narrow_train_multi<false>(h, groups, na); }
+        else if (nw_cat(h)) {                                          // (never deferred: nw_lazy is a Gaussian handle's)
             if (na.mask) launch_narrow_train<false, false, true, true>(h, groups, na, z); else launch_narrow_train<false, false, true, false>(h, groups, na, z);
         }
         else if (h->nw_pending) {
@@ -1704,8 +1746,11 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
 
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) { return create_handle(cfg, action_dist, nullptr, 0, out); }
 
-// K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns
-int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out) {
+int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out) { return ppo_create_multi_ex(cfg, nvec, n_components, 0, out); }
+
+// K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns; flags: PPO_ACT_SHAPE_KERNELS (the narrow family on a
+// qualifying shape), PPO_ACT_PAIR_KERNELS / PPO_ACT_BF16_HEAD (accepted, nothing to select: this head has no such kernels)
+int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out) {
     if (!cfg || !out) return fail(nullptr, "ppo_create_multi: null argument");
     *out = nullptr;
     if (n_components < 1 || n_components > PPO_MAX_COMPONENTS)
@@ -1719,7 +1764,10 @@ int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_compo
     if (sum != cfg->act_dim) return fail(nullptr, "ppo_create_multi: act_dim %d is not the sum of nvec (%lld)", (int)cfg->act_dim, (long long)sum);
     if (cfg->compute_dtype == PPO_BF16)
         return fail(nullptr, "ppo_create_multi: compute_dtype PPO_BF16 is not supported (the multi-categorical head runs on the PPO_F32 path)");
-    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL, nvec, n_components, out);
+    const int32_t known = PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_HEAD;
+    if (flags & ~known)
+        return fail(nullptr, "ppo_create_multi_ex: unknown flag bit 0x%x (PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS or PPO_ACT_BF16_HEAD)", (unsigned)(flags & ~known));
+    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & PPO_ACT_SHAPE_KERNELS), nvec, n_components, out);
 }
 
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {
@@ -1758,7 +1806,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     ppo_handle* h = new ppo_handle();
     h->cfg = *cfg;
     h->dist = action_dist;
-    h->shape_kernels = shape_kernels && action_dist == PPO_ACT_CATEGORICAL;       // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
+    h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN;          // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
     h->pair_kernels = pair_kernels && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
     h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : action_dist == PPO_ACT_MULTI_CATEGORICAL ? n_components : cfg->act_dim;
@@ -1826,6 +1874,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
         dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8))
         return bail(0);
     build_narrow_layout(h);
+    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) h->shape_kernels = h->narrow;       // from here on: the flag took effect (a shape that does not qualify runs the generic <mcat> kernels, data parallel included)
     if (upload_grad_src(h)) return bail(0);
     const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels;        // the heads train8_kernel has; a categorical one only where the flag asks for it
     { const char* e = getenv("PPO_HIP_NO_DW2"); const NetDev& nn = h->net;
@@ -1875,6 +1924,12 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
         if (nw_cat(h)) {
 #define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true>); \
                            big_lds((const void*)narrow_step_kernel<a, b, c, d, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true>); } while (0)
+            X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
+#undef X
+        }
+        if (nw_mcat(h)) {
+#define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true, true>); \
+                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true, false, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true, true>); } while (0)
             X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
         }
@@ -3634,6 +3689,8 @@ struct UidByValue { char b[128]; };
 int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128]) {
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
     if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
+    if (h->shape_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (h->pair_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS (create it without the flag)");
     if (load_rccl(h->rccl, h->err)) return -1;

@@ -54,6 +54,7 @@ struct NwTrainArgs {
     unsigned long long* stamps;    // diagnostic builds only (-DPPO_STAMPS): [workgroups][32] cycle stamps
     const float* mask;             // [n][A] action masks in minibatch order (non-zero = allowed); read by the <.., CAT, MASK> instantiations only
 };
+struct NwTrainArgsM : NwTrainArgs { CompTable comp; };   // the <.., MULTI> instantiations' arguments (`actions`: K floats per row, the index within each component)
 #ifdef PPO_STAMPS
 #define NSTAMP(i) do { if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 32 + (i)] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -116,12 +117,16 @@ __device__ __forceinline__ void nw_dense(const float* Xs, int ldx, int K, const 
 // CAT (mode 1, the train kernel's policy tower): `actions` is ONE float per row (the category index); it lands in the first padding column of the row in the pipe's
 // `mu` tile (column Ap of ldm = Ap + NW_XPAD: no product reads or writes it), requested with the row values.  MASK: the [rows][A] tile the Gaussian head fills with
 // actions holds the rows' action masks instead (same loads, same tile: `acts`).  Neither costs LDS.
-template <class S, bool CAT = false, bool MASK = false>
+// MULTI (with CAT): the K floats of a row's action are not staged at all -- lane k of the row's 16 holds component k's index in a register (narrow_train_kernel
+// requests it ahead of this prologue's loads) -- so the padding column stays unused and the `acts` tile is the masks' alone.
+template <class S, bool CAT = false, bool MASK = false, bool MULTI = false>
 __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay, const float* __restrict__ img, int n_img, float* lds,
                                          const float* __restrict__ obs, int row0, int nrows, ObsNorm nz, float* __restrict__ obs_out, int tower,
                                          const float* __restrict__ actions, const float* __restrict__ v0, const float* __restrict__ v1, int mode, const int tidx = (int)threadIdx.x,
                                          const float* __restrict__ mask = nullptr) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
+    constexpr bool ACT1 = CAT && !MULTI;                    // the row's ONE category index rides in the `mu` tile's padding column
     const int tid = tidx;
     const float* __restrict__ tile_src = MASK ? mask : actions;   // what fills the [rows][A] tile
     constexpr bool TILE = !CAT || MASK;
@@ -155,7 +160,7 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
     }
     if (mode && tid < NW_ROWS && row0 + tid < nrows) {
         r0 = v0[row0 + tid]; r1 = v1[row0 + tid];
-        if constexpr (CAT) { if (mode == 1) r2 = actions[row0 + tid]; }
+        if constexpr (ACT1) { if (mode == 1) r2 = actions[row0 + tid]; }
     }
     // ---- consume ---------------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -198,7 +203,7 @@ __device__ __forceinline__ void nw_stage(const NetDev& net, const NwLayout& lay,
         float* rv = lds + lay.w_total + (tid >> 4) * lay.pipe_total + lay.rowv;
         rv[2 * (tid & 15)] = live ? r0 : 0.f;
         rv[2 * (tid & 15) + 1] = live ? r1 : 0.f;
-        if constexpr (CAT) { if (mode == 1) lds[lay.w_total + (tid >> 4) * lay.pipe_total + lay.mu + (tid & 15) * lay.ldm + Ap] = live ? r2 : -1.f; }
+        if constexpr (ACT1) { if (mode == 1) lds[lay.w_total + (tid >> 4) * lay.pipe_total + lay.mu + (tid & 15) * lay.ldm + Ap] = live ? r2 : -1.f; }
     }
 }
 
@@ -386,9 +391,16 @@ __device__ __forceinline__ void nw_lazy_apply(const NetDev& net, const NwLayout&
 // CAT: categorical head (the arithmetic of train_fwd_bwd_kernel<.., CAT>, in its order; the formulas themselves are ppo_head.hpp's): the logits are the head product in the `mu` tile, the row's category index
 // waits in the padding column of its `mu` row and, with MASK, its mask row in the `acts` tile (nw_stage); d logits go where d mu goes, so the head-backward product and the pi/w, pi/b gradients
 // run unchanged.  The padded logstd slot has no gradient source: its partial is written as 0.  Nothing is indexed with the action or with the mask.
-template <int KP0, int HP, int AP, int LL, bool WT = true, bool CAT = false, bool MASK = false>
-__device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout& lay, const NwTrainArgs& a, float* lds, const int tower, const int grp,
-                                              const int tidx = (int)threadIdx.x) {
+// MULTI (with CAT): K categorical components over the one logits row (NwTrainArgsM::comp), the walk of train_fwd_bwd_kernel<.., MULTI> in this kernel's geometry: the
+// row's 16 lanes go through the components one after another (lane `part` owns columns off[k] + part, + 16, ..), lane k of the row keeps component k's maximum,
+// normaliser and entropy, and a second walk -- the row's d_nlp needs every component -- hands them back and writes d logits with the entropy of the column's OWN
+// component.  neglogp and entropy are added in component order from the first one's value, so one component gives the <CAT> bits.  The action row never touches
+// LDS: `act_k` is component `part`'s index within its component, in the register of lane `part` of the row (requested by the kernel ahead of the prologue's loads) and
+// broadcast inside the row's wave, so no lane can see a half-written row and NwLayout is the categorical handle's.
+template <int KP0, int HP, int AP, int LL, bool WT = true, bool CAT = false, bool MASK = false, bool MULTI = false>
+__device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout& lay, const std::conditional_t<MULTI, NwTrainArgsM, NwTrainArgs>& a, float* lds, const int tower, const int grp,
+                                              const int tidx = (int)threadIdx.x, const float act_k = 0.f) {
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
     typedef NwShape<KP0, HP, AP, LL> S;
     const int tid = tidx, pipe = uni(tid >> 8), ptid = tid & 255;
     const int row0 = grp * NW_ROWS;
@@ -440,7 +452,36 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
         float cz = 1.f, clz = 0.f, cnlp = 0.f;
         int cact = -1;
         bool ok[4];
-        if constexpr (CAT) {
+        float k_m = 0.f, k_z = 1.f, k_h = 0.f;                       // MULTI: lane k of the row keeps component k's maximum, normaliser, entropy
+        const int k_col = live ? (int)act_k : -1;                     // ... and came with its index within the component
+        auto allowed = [&](int j) __attribute__((always_inline)) { if constexpr (MASK) return !live || acts[r * Ap + j] != 0.f; else return true; };
+        if constexpr (MULTI) {
+            for (int k = 0; k < a.comp.K; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                const int ck = __shfl(k_col, k, 16);
+                const int act = live ? o + ck : -1;
+                float bl = -INFINITY;
+                int il = o;
+                for (int j = o + part; j < e; j += 16) { const float l = mus[r * ldm + j]; if (allowed(j) && l > bl) { bl = l; il = j; } }
+                group16_argmax(bl, il);
+                const float m = bl;
+                float la = 0.f, z = 0.f, ent = 0.f;
+                for (int j = o + part; j < e; j += 16) {
+                    if (!allowed(j)) continue;
+                    const float a0 = mus[r * ldm + j] - m;
+                    z += expf(a0);
+                    if (j == act) la = a0;
+                }
+                z = group16_sum(z); la = group16_sum(la);
+                const float lz = logf(z);
+                for (int j = o + part; j < e; j += 16) { if (!allowed(j)) continue; const float a0 = mus[r * ldm + j] - m; ent += cat_entropy_term(expf(a0), z, lz, a0); }
+                ent = group16_sum(ent);
+                const float nk = lz - la;
+                cnlp = k == 0 ? nk : cnlp + nk;
+                sent = k == 0 ? ent : sent + ent;
+                if (part == k) { k_m = m; k_z = z; k_h = ent; }
+            }
+        } else if constexpr (CAT) {
             cact = live ? (int)mus[r * ldm + Ap] : -1;
             float bl = -INFINITY;
             int il = 0;
@@ -503,6 +544,25 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             surrogate_terms(sr, nlp, old_nlp, sent, cr, live, misc, r);
         }
         float* dmu_t = P + lay.dmu;
+        if constexpr (MULTI) {
+            // cat_grad_elem with the entropy H_k of j's own component; forbidden columns, padding columns and dead rows: exactly +0
+            for (int k = 0; k < a.comp.K; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                const float m = __shfl(k_m, k, 16), z = __shfl(k_z, k, 16), hk = __shfl(k_h, k, 16);
+                const int ck = __shfl(k_col, k, 16);
+                const int act = live ? o + ck : -1;
+                const float lz = logf(z);
+                for (int j = o + part; j < e; j += 16) {
+                    float dmu = 0.f;
+                    if (live && allowed(j)) {
+                        const float a0 = mus[r * ldm + j] - m;
+                        dmu = cat_grad_elem(d_nlp, expf(a0), z, a0, lz, hk, j, act, net.ent_coef, gg);
+                    }
+                    dmu_t[r * ldm + j] = dmu;
+                }
+            }
+            for (int j = net.A + part; j < Ap; j += 16) dmu_t[r * ldm + j] = 0.f;
+        } else
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int j = part + 16 * k;
@@ -670,6 +730,25 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_train_kernel(NetDev net, Nw
                     a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2, (int)threadIdx.x, a.mask);
     }
     nw_train_body<KP0, HP, AP, LL, true, CAT, MASK>(net, lay, a, lds, tower, grp);
+}
+// the multi-categorical forms, narrow_train_kernel<KP0, HP, AP, LL, false, false, true, MASK, true>: an OVERLOAD with the component table behind the plain arguments, not one more
+// defaulted parameter of the template above -- every other instantiation keeps its symbol and its kernarg layout (tools/kernel_code_diff.py pairs them with every
+// earlier build's).  Never deferred.  Lane k of a row's 16 requests component k's index of the row's action ahead of the prologue's loads: one round trip with them.
+template <int KP0, int HP, int AP, int LL, bool LAZY, bool EXACT, bool CAT, bool MASK, bool MULTI>
+__global__ __launch_bounds__(NW_THREADS) void narrow_train_kernel(NetDev net, NwLayout lay, NwTrainArgsM a) {
+    static_assert(MULTI && CAT && !LAZY && !EXACT, "the multi-categorical overload: a form of the categorical head, never deferred");
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwTrainArgsM)>();
+    const int tower = blockIdx.y, grp = blockIdx.x;
+    const int row0 = grp * NW_ROWS;
+    NSTAMP(0);
+    const int arow = row0 + ((int)threadIdx.x >> 4), ak = (int)threadIdx.x & 15;           // (row, lane of the row) of the loss block: NW_THREADS = 16 NW_ROWS
+    float act_k = 0.f;
+    if (tower == 0 && arow < a.n && ak < a.comp.K) act_k = a.actions[(size_t)arow * a.comp.K + ak];
+    nw_stage<S, true, MASK, true>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
+                a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2, (int)threadIdx.x, a.mask);
+    nw_train_body<KP0, HP, AP, LL, true, true, MASK, true>(net, lay, a, lds, tower, grp, (int)threadIdx.x, act_k);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1098,6 +1177,113 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwL
     }
     ssq = group16_sum(ssq); slog = group16_sum(slog);
     if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = gauss_nlp(ssq, slog, net.A);
+}
+
+// MULTI (with CAT): K categorical components over the one logits row (StepArgsM::comp), policy_step_kernel<.., MULTI>'s rules per component ("none yet" of the masked
+// form = the component's end, clamped back inside it; noise, counter draws and mask entries keyed by the GLOBAL logit index; neglogp added in component order from
+// the first one's value).  A lane keeps the ownership above -- columns part + 16 k, their logits, uniforms and mask entries in registers, requested before the head
+// product -- and walks the components over those four: a column counts for the component whose range holds it.  Both argmaxes are order-free (larger value, lower
+// index) and one component is the <CAT> form bit for bit.  Lane k of the row keeps component k's two indices and stores them behind the walk: by then every lane of
+// the row has read its last logit.
+// An OVERLOAD with the component table behind the plain arguments (see narrow_train_kernel's), not a seventh defaulted parameter of the template above: every other
+// instantiation keeps its symbol, its kernarg layout and its machine code; the forward pass is narrow_step_kernel's, written out (as a shared piece it changed the
+// machine code of every instantiation above: profiles/EXPERIMENTS.md).
+template <int KP0, int HP, int AP, int LL, bool CAT, bool MASK, bool MULTI>
+__global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwLayout lay, StepArgsM a) {
+    static_assert(MULTI && CAT, "the multi-categorical overload: a form of the categorical head");
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(StepArgsM)>();
+    const int tower = blockIdx.y;
+    if (tower == 1 && !a.value) return;
+    if (tower == 0 && !a.action && !a.det_action && !a.neglogp && !a.obs_out) return;
+    const int tid = threadIdx.x, pipe = tid >> 8, ptid = tid & 255;
+    const int row0 = blockIdx.x * NW_ROWS;
+    const int L = S::L(net), Kp0 = S::Kp0(net), Ap = S::Ap(net);
+    nw_stage<S>(net, lay, a.theta + (size_t)tower * lay.w_total, lay.w_fwd, lds, a.obs, row0, a.n, a.nz, a.obs_out, tower, nullptr, nullptr, nullptr, 0);
+    __syncthreads();
+    float* P = lds + lay.w_total + pipe * lay.pipe_total;
+    const float* par = lds + lay.par;
+    for (int l = 0; l < L; ++l) {
+        const float* bias = par + net.par_b[l];
+        float* Ys = P + lay.x[l + 1]; const int ldy = lay.ldx[l + 1];
+        auto ep = [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+            const float b = bias[col];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Ys[(4 * g + r) * ldy + col] = fast_tanh(acc[r] + b);
+        };
+        if (l == 0) nw_dense<KP0>(P + lay.x[0], lay.ldx[0], Kp0, lds + lay.wf[0], lay.wf_ld[0], S::Hp(net, 0), ep);
+        else nw_dense<HP>(P + lay.x[l], lay.ldx[l], S::Hp(net, l - 1), lds + lay.wf[l], lay.wf_ld[l], S::Hp(net, l), ep);
+        __syncthreads();
+    }
+    const float* hL = P + lay.x[L]; const int ldh = lay.ldx[L]; const int HpL = S::Hp(net, L - 1);
+    const int r = ptid >> 4, part = ptid & 15;
+    const int row = row0 + 16 * pipe + r;
+    if (tower == 1) {
+        const float* wv = par + net.par_wv;
+        float s = 0.f;
+        for (int k = part; k < HpL; k += 16) s = fmaf(hL[r * ldh + k], wv[k], s);
+        s = group16_sum(s);
+        if (part == 0 && row < a.n) a.value[row] = s + par[net.par_bv];
+        return;
+    }
+    float* mus = P + lay.mu; const int ldm = lay.ldm;
+    float uk[4]; bool mk[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = part + 16 * k;
+        uk[k] = 0.5f; mk[k] = true;
+        if (j < net.A && row < a.n) {
+            uk[k] = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+            if constexpr (MASK) mk[k] = a.mask[(size_t)row * net.A + j] != 0.f;
+        }
+    }
+    nw_dense<HP>(hL, ldh, HpL, lds + lay.wh, lay.wh_ld, Ap, [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+        const float b = par[net.par_bmu + col];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mus[(4 * g + q) * ldm + col] = acc[q] + b;
+    });
+    __syncthreads();
+    float lk[4], pk[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = part + 16 * k;
+        lk[k] = j < net.A ? mus[r * ldm + j] : 0.f;
+        pk[k] = gumbel(lk[k], uk[k]);
+    }
+    float nlp = 0.f, my_a = 0.f, my_d = 0.f;
+    for (int c = 0; c < a.comp.K; ++c) {
+        const int o = a.comp.off[c], e = a.comp.off[c + 1];
+        float bp = -INFINITY, bl = -INFINITY;
+        int ip = MASK ? e : o, il = MASK ? e : o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = part + 16 * k;
+            if (j >= o && j < e && mk[k]) { cat_take<MASK>(pk[k], j, e, bp, ip); cat_take<MASK>(lk[k], j, e, bl, il); }
+        }
+        group16_argmax(bp, ip);
+        group16_argmax(bl, il);
+        if constexpr (MASK) { ip = min(ip, e - 1); il = min(il, e - 1); }
+        const float m = bl;
+        float z = 0.f, la = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = part + 16 * k;
+            if (j >= o && j < e) {
+                if (j == ip) la = lk[k] - m;              // (one lane of the row holds it; the others add zeros)
+                if (mk[k]) z += expf(lk[k] - m);
+            }
+        }
+        z = group16_sum(z); la = group16_sum(la);
+        const float nk = logf(z) - la;
+        nlp = c == 0 ? nk : nlp + nk;
+        if (part == c) { my_a = (float)(ip - o); my_d = (float)(il - o); }
+    }
+    if (part < a.comp.K && row < a.n) {
+        if (a.action) a.action[(size_t)row * a.comp.K + part] = my_a;
+        if (a.det_action) a.det_action[(size_t)row * a.comp.K + part] = my_d;
+    }
+    if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = nlp;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -76,7 +76,8 @@ int main(int argc, char** argv) {
                         "  --time_limit N: every environment ends its episodes after N steps (a TimeLimit wrapper); the value is bootstrapped at those truncations\n"
                         "  --no_bootstrap_truncated: treat them as terminal states instead (the reference's behaviour)\n"
                         "  --discrete_kernels: kernels of a discrete environment's categorical policy; narrow = the LDS-resident family where the network's shape\n"
-                        "                      qualifies (hidden widths <= 64), generic = the generic fp32 family (the default).  Continuous environments: no effect\n");
+                        "                      qualifies (hidden widths <= 64), generic = the generic fp32 family (the default).  A multi-discrete environment's\n"
+                        "                      multi-categorical policy likewise (at most 64 logits in all).  Continuous environments: no effect\n");
             return 0;
         }
         for (auto& al : kAliases) if (a == al[0] && i + 1 < argc) { f.kv[al[1]] = argv[++i]; ok = true; break; }

@@ -58,20 +58,21 @@ public:
     // The action_dist argument of ppo_create_ex for a handle that will serve `env`: PPO_ACT_GAUSSIAN for SPACE_CONTINOUS, PPO_ACT_CATEGORICAL for SPACE_DISCRETE.
     // discrete_shape_kernels (default off): a discrete Env's handle is created with PPO_ACT_SHAPE_KERNELS -- the narrow LDS-resident kernels when the network's
     // shape qualifies (include/ppo_hip.h); a continuous Env is not affected.
-    // An Env with the IMultiDiscrete mixin: PPO_ACT_MULTI_CATEGORICAL (no flags: that head has the generic PPO_F32 kernels only) -- a value for ppo_create_multi,
-    // which ppo_create_ex refuses; create_handle below makes the right call.
+    // An Env with the IMultiDiscrete mixin: the bare PPO_ACT_MULTI_CATEGORICAL -- a value for ppo_create_multi[_ex], which ppo_create_ex refuses and which takes its
+    // flags as an argument of their own; create_handle below makes the right call (and passes PPO_ACT_SHAPE_KERNELS there).
     static int32_t action_dist_for(Env& env, bool discrete_shape_kernels = false) {
         if (env.get_action_space() != Env::SPACE_DISCRETE) return PPO_ACT_GAUSSIAN;
         if (!action_nvec_of(&env).empty()) return PPO_ACT_MULTI_CATEGORICAL;
         return PPO_ACT_CATEGORICAL | (discrete_shape_kernels ? PPO_ACT_SHAPE_KERNELS : 0);
     }
-    // The handle that will serve `env`: ppo_create_multi with the Env's components for an IMultiDiscrete Env (cfg.act_dim must be their sum), otherwise
+    // The handle that will serve `env`: ppo_create_multi_ex with the Env's components for an IMultiDiscrete Env (cfg.act_dim must be their sum; flags:
+    // PPO_ACT_SHAPE_KERNELS with discrete_shape_kernels -- the narrow kernels where the shape qualifies -- | extra_flags), otherwise
     // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);
         if (nvec.empty()) return ppo_create_ex(&cfg, action_dist_for(env, discrete_shape_kernels) | extra_flags, out);
         const std::vector<int32_t> nv(nvec.begin(), nvec.end());
-        return ppo_create_multi(&cfg, nv.data(), (int32_t)nv.size(), out);
+        return ppo_create_multi_ex(&cfg, nv.data(), (int32_t)nv.size(), (discrete_shape_kernels ? PPO_ACT_SHAPE_KERNELS : 0) | extra_flags, out);
     }
     // the handle's component widths (ppo_action_nvec): empty for a Gaussian handle, {A} for a categorical one
     static std::vector<int> handle_nvec(const ppo_handle* handle) {
