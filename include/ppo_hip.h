@@ -109,7 +109,7 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
  *                        weight_grad_assemble_kernel (minibatches that are whole 64-row chunks), with PPO_HIP_NO_DW2=1 train8_kernel<cat[,mask]> in front of
  *                        weight_grad_kernel + grad_reduce_kernel.  A shape that does not qualify runs the generic categorical kernels, as without the flag
  *                        (same bits, same ppo_kernel_counts); with PPO_ACT_GAUSSIAN, with PPO_BF16, or beside PPO_ACT_SHAPE_KERNELS on a narrow shape the flag
- *                        is accepted and changes nothing.  A multi-categorical handle has no such kernels: ppo_create_multi_ex accepts the flag and ignores it.  Not the
+ *                        is accepted and changes nothing.  A multi-categorical handle takes the pair through ppo_create_multi_ex's flag of the same name (below).  Not the
  *                        default (opt-in); data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... not
  *                        supported for a categorical handle created with PPO_ACT_PAIR_KERNELS") and leaves it usable.  ppo_action_dist reports the low bits only. */
 #define PPO_ACT_GAUSSIAN    0
@@ -134,7 +134,7 @@ int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_
  * Masks are [n, A] as for the categorical head and exclude per component; a row of ones gives the unmasked bits.  The host checks (before anything is uploaded;
  * each message names row and component): every COMPONENT of every mask row allows a category; a ppo_train_step_masked row's action k is allowed by its
  * component's mask; every action value of ppo_train_step / of an uploaded rollout field 1 is an integer in [0, n_k).
- * Runs the generic PPO_F32 kernel family (never the train8 or bf16 forms; the narrow family only through ppo_create_multi_ex's flag, below).  ppo_kernel_counts names,
+ * Runs the generic PPO_F32 kernel family (never the bf16 forms; the narrow family and the [256,256] train8 pair only through ppo_create_multi_ex's flags, below).  ppo_kernel_counts names,
  * counted INSTEAD of the <cat> ones: "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>".
  * Data parallel and both shuffles work as for a categorical PPO_F32 handle.
  * Errors of ppo_create_multi, each naming the limit: n_components outside 1..PPO_MAX_COMPONENTS, a component with fewer than 2 categories, cfg->act_dim != sum of
@@ -155,7 +155,28 @@ int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_compo
  *                        16 / 1024 rows; it lost at no row count measured.  A shape whose plain image exceeds 160 KB takes a compact tile layout.
  *                        Data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... not supported for a
  *                        multi-categorical handle created with PPO_ACT_SHAPE_KERNELS") and leaves it usable.
- *   PPO_ACT_PAIR_KERNELS, PPO_ACT_BF16_HEAD  accepted, nothing to select (the head has no such kernels); compute_dtype PPO_BF16 stays refused.
+ *   PPO_ACT_PAIR_KERNELS   lets the handle take the [256,256] kernel pair under the rule of a flagged categorical handle: PPO_F32, not wide, two hidden layers
+ *                        of 256, padded observation and logit widths <= 64 (so sum of nvec <= 64).  A train step then runs train8_kernel<mcat[,mask]> +
+ *                        weight_grad_assemble_kernel + adam_kernel instead of the generic four launches, with the arithmetic stated above per component in
+ *                        train8_kernel's geometry (32 lanes per row; lane j owns logit columns j and j + 32, which may belong to two components; a row's K
+ *                        action indices wait in a region of their own behind the other instantiations' LDS carve).  The d logits go where d mu goes, the
+ *                        d logstd tile and slot words are zeros, and the padded logstd region of the weights, the gradient and both Adam slots is never moved.
+ *                        One component gives the bits of a categorical handle created with PPO_ACT_PAIR_KERNELS; a row of ones as mask gives the unmasked
+ *                        bits.  The act side is unchanged (policy_step_kernel<mcat[,mask]>), and so are the epoch gather ([.., K] action rows), the masked
+ *                        rollout, the truncation bootstrap, ppo_update's captured graph (kernel nodes only) and the Adam launch.  ppo_kernel_counts names,
+ *                        counted INSTEAD of "train_fwd_bwd_kernel<mcat>" / "train_fwd_bwd_kernel<mcat,mask>": "train8_kernel<mcat>",
+ *                        "train8_kernel<mcat,mask>"; "weight_grad_assemble_kernel" keeps its one name.  PPO_HIP_NO_T8 and PPO_HIP_NO_DW2 act as on a flagged
+ *                        categorical handle: with PPO_HIP_NO_T8=1 train_fwd_bwd_kernel<mcat[,mask]> in front of weight_grad_assemble_kernel (minibatches that
+ *                        are whole 64-row chunks), with PPO_HIP_NO_DW2=1 train8_kernel<mcat[,mask]> in front of weight_grad_kernel + grad_reduce_kernel.  A
+ *                        shape that does not qualify runs the generic <mcat> kernels, as without the flag (same bits, same ppo_kernel_counts, data parallel
+ *                        included).  Beside PPO_ACT_SHAPE_KERNELS the two rules never both hold (hidden widths <= 64 against two layers of 256): each flag
+ *                        acts where its own rule holds.  Not the default (opt-in).  Measured at (18, (6, 6, 6), [256,256]) against the unflagged handle in one process: train step 40.9 against 50.1 us at 64 rows (0.82) and
+ *                        49.7 against 58.1 us at 2048 rows (0.85), beside 39.6 / 49.3 us for train8_kernel<cat> at act_dim = 18; at (50, (4,) x 16), K = 16, 52.4
+ *                        against 74.8 and 62.2 against 88.3 us (0.70), 9 us above train8_kernel<cat> at 64 categories: the component walk costs about half a
+ *                        microsecond per component.  It lost to the generic form at no row count measured.
+ *                        Data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... data parallel is not
+ *                        supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS") and leaves it usable.
+ *   PPO_ACT_BF16_HEAD    accepted, nothing to select (the head has no bf16 kernels); compute_dtype PPO_BF16 stays refused.
  * Any other bit is an error ("ppo_create_multi_ex: unknown flag bit 0x.."). */
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out);
 /* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian handle, 1 with nvec[0] = A for a categorical one */
@@ -361,6 +382,7 @@ int ppo_dist_unique_id(char uid[128]);
 /* (a categorical handle created with PPO_ACT_SHAPE_KERNELS is refused: "... data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS";
  *  a multi-categorical one on which that flag took effect (ppo_create_multi_ex) likewise: "... for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS";
  *  one on which PPO_ACT_PAIR_KERNELS took effect likewise: "... data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS";
+ *  a multi-categorical one on which PPO_ACT_PAIR_KERNELS took effect: "... data parallel is not supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
 int ppo_dist_world(const ppo_handle* h);
@@ -414,7 +436,7 @@ int ppo_prof_read(ppo_handle* h, int max, char names[][32], double* total_ms, in
 int ppo_sync(ppo_handle* h);
 /* which kernel VARIANT the calls so far took: the library picks its kernels from the shape, and a caller or a
  * test can ask which ones were ENQUEUED since ppo_create (a hipGraph capture counts once, its replays do not).  names: e.g.
- * "train8_kernel", "train8_kernel<cat>", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
+ * "train8_kernel", "train8_kernel<cat>", "train8_kernel<mcat>", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
 int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued);
 
 /* ---- debug: a raw device buffer by name, padding included (the getters above copy the dense part of every tensor) ----------------

@@ -83,7 +83,11 @@ class PPOHip:
     their (n, A) shape with A = sum(nvec).  `.nvec` reads the widths back from the handle (ppo_action_nvec).
     shape_kernels=True with it (ppo_create_multi_ex with PPO_ACT_SHAPE_KERNELS): the narrow LDS-resident kernels (narrow_step_kernel<mcat[,mask]>,
     narrow_train_kernel<mcat[,mask]>) where the shape qualifies as a categorical handle's would (hidden widths <= 64, sum(nvec) <= 64); any other
-    shape runs the generic <mcat> kernels.  No data parallel on a handle the flag took effect on.  bf16_head / pair_kernels: nothing for this head.
+    shape runs the generic <mcat> kernels.  No data parallel on a handle the flag took effect on.
+    pair_kernels=True with it (ppo_create_multi_ex with PPO_ACT_PAIR_KERNELS): hidden [256, 256] with at most 64 observations and sum(nvec) <= 64 trains with
+    train8_kernel<mcat[,mask]> + weight_grad_assemble_kernel instead of train_fwd_bwd_kernel<mcat[,mask]> and its two followers (the act side is
+    unchanged; no data parallel on a handle the flag took effect on); any other shape runs the generic <mcat> kernels.  shape_kernels and pair_kernels
+    may be given together: their shape rules never both hold, each flag acts where its own rule holds.  bf16_head: nothing for this head.
 
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -124,7 +128,8 @@ class PPOHip:
         h = C.c_void_p()
         if multi:
             nv = (C.c_int32 * max(len(nvec), 1))(*nvec)
-            if (self.lib.ppo_create_multi_ex(C.byref(cfg), nv, len(nvec), ACT_SHAPE_KERNELS, C.byref(h)) if shape_kernels
+            flags = (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_PAIR_KERNELS if pair_kernels else 0)
+            if (self.lib.ppo_create_multi_ex(C.byref(cfg), nv, len(nvec), flags, C.byref(h)) if flags
                     else self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h))) != 0:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())
         elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)

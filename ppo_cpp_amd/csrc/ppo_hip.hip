@@ -66,7 +66,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK,
                      KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK,
                      KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK,
-                     KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_COUNT };
+                     KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK,
+                     KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK, KV_COUNT };
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -84,7 +85,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a categorical handle created with PPO_ACT_PAIR_KERNELS on a [256,256] shape: counted INSTEAD of "train8_kernel"
                                        "train8_kernel<cat>", "train8_kernel<cat,mask>",
                                        // a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (ppo_create_multi_ex) on a narrow shape: counted INSTEAD of the <cat> and the generic names
-                                       "narrow_step_kernel<mcat>", "narrow_step_kernel<mcat,mask>", "narrow_train_kernel<mcat>", "narrow_train_kernel<mcat,mask>"};
+                                       "narrow_step_kernel<mcat>", "narrow_step_kernel<mcat,mask>", "narrow_train_kernel<mcat>", "narrow_train_kernel<mcat,mask>",
+                                       // a multi-categorical handle created with PPO_ACT_PAIR_KERNELS (ppo_create_multi_ex) on a [256,256] shape: counted INSTEAD of "train_fwd_bwd_kernel<mcat[,mask]>"
+                                       "train8_kernel<mcat>", "train8_kernel<mcat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -114,7 +117,7 @@ struct ppo_handle {
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
-    bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
+    bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical or multi-categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
@@ -1298,6 +1301,17 @@ static void launch_train8_cat(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
     PAIR_DISPATCH(h, X);
 #undef X
 }
+// its multi-categorical forms (ppo_create_multi_ex with PPO_ACT_PAIR_KERNELS): the component table rides behind the arguments, the action rows' region behind the carve
+template <bool MASK>
+static void launch_train8_multi(ppo_handle* h, dim3 grid, const TrainArgs& ta0) {
+    TrainArgsM ta;
+    static_cast<TrainArgs&>(ta) = ta0;
+    ta.comp = h->comp;
+#define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL_M; \
+                        hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK, true>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+    PAIR_DISPATCH(h, X);
+#undef X
+}
 // peer: the tiles' finishers push to the peers' regions themselves
 static void launch_dw2(ppo_handle* h, const Dw2Args& da, bool peer) {
 #define X(KP0, AP) do { const size_t lds = sizeof(float) * Dw2L<KP0, AP>::LDS_FLOATS; \
@@ -1313,7 +1327,9 @@ static bool set_lds_pair(const ppo_handle* h) {
 #define X(KP0, AP) do { set((const void*)weight_grad_assemble_peer_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
                         set((const void*)weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); \
                         if (h->dist == PPO_ACT_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false>, T8L<KP0, AP>::TOTAL); \
-                                                              set((const void*)train8_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); } } while (0)
+                                                              set((const void*)train8_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); } \
+                        if (h->dist == PPO_ACT_MULTI_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false, true>, T8L<KP0, AP>::TOTAL_M); \
+                                                                    set((const void*)train8_kernel<KP0, AP, true, true, true>, T8L<KP0, AP>::TOTAL_M); } } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
     return ok;
@@ -1539,11 +1555,13 @@ static int enqueue_train_fb(ppo_handle* h, const TrainArgs& ta, int n_pad) {
     const dim3 grid(n_pad / ROWS_PER_BLOCK, 2);
     const bool cat = h->dist == PPO_ACT_CATEGORICAL;              // (a mask: a categorical handle, the entry points check; t8: not wide, Gaussian or categorical with PPO_ACT_PAIR_KERNELS, ppo_create_ex)
     const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;
-    const bool cat8 = cat && h->t8;
-    if (multi) ++h->kv[ta.mask ? KV_TRAIN_FB_MCAT_MASK : KV_TRAIN_FB_MCAT];
+    const bool cat8 = cat && h->t8, multi8 = multi && h->t8;      // (a multi-categorical handle: t8 only with PPO_ACT_PAIR_KERNELS, ppo_create_multi_ex)
+    if (multi8) ++h->kv[ta.mask ? KV_TRAIN8_MCAT_MASK : KV_TRAIN8_MCAT];
+    else if (multi) ++h->kv[ta.mask ? KV_TRAIN_FB_MCAT_MASK : KV_TRAIN_FB_MCAT];
     else if (cat8) ++h->kv[ta.mask ? KV_TRAIN8_CAT_MASK : KV_TRAIN8_CAT];
     else ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : cat ? KV_TRAIN_FB_CAT : h->t8 ? KV_TRAIN8 : KV_TRAIN_FB];
-    if (multi) { if (ta.mask) launch_train_fb<true, true, true>(h, grid, ta); else launch_train_fb<true, false, true>(h, grid, ta); }
+    if (multi8) { if (ta.mask) launch_train8_multi<true>(h, grid, ta); else launch_train8_multi<false>(h, grid, ta); }
+    else if (multi) { if (ta.mask) launch_train_fb<true, true, true>(h, grid, ta); else launch_train_fb<true, false, true>(h, grid, ta); }
     else if (cat8) { if (ta.mask) launch_train8_cat<true>(h, grid, ta); else launch_train8_cat<false>(h, grid, ta); }
     else if (ta.mask) launch_train_fb<true, true>(h, grid, ta);
     else if (cat) launch_train_fb<true, false>(h, grid, ta);
@@ -1749,7 +1767,7 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
 int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out) { return ppo_create_multi_ex(cfg, nvec, n_components, 0, out); }
 
 // K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns; flags: PPO_ACT_SHAPE_KERNELS (the narrow family on a
-// qualifying shape), PPO_ACT_PAIR_KERNELS / PPO_ACT_BF16_HEAD (accepted, nothing to select: this head has no such kernels)
+// qualifying shape), PPO_ACT_PAIR_KERNELS (the [256,256] pair on a qualifying shape), PPO_ACT_BF16_HEAD (accepted, nothing to select: this head has no bf16 kernels)
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out) {
     if (!cfg || !out) return fail(nullptr, "ppo_create_multi: null argument");
     *out = nullptr;
@@ -1767,7 +1785,7 @@ int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_co
     const int32_t known = PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_HEAD;
     if (flags & ~known)
         return fail(nullptr, "ppo_create_multi_ex: unknown flag bit 0x%x (PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS or PPO_ACT_BF16_HEAD)", (unsigned)(flags & ~known));
-    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & PPO_ACT_SHAPE_KERNELS), nvec, n_components, out);
+    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & (PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS)), nvec, n_components, out);
 }
 
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {
@@ -1808,7 +1826,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     h->dist = action_dist;
     h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN;          // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
-    h->pair_kernels = pair_kernels && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
+    h->pair_kernels = pair_kernels && (action_dist == PPO_ACT_CATEGORICAL || action_dist == PPO_ACT_MULTI_CATEGORICAL) && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
     h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : action_dist == PPO_ACT_MULTI_CATEGORICAL ? n_components : cfg->act_dim;
     if (action_dist == PPO_ACT_MULTI_CATEGORICAL) {
         h->comp.K = n_components;
@@ -1876,7 +1894,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     build_narrow_layout(h);
     if (h->dist == PPO_ACT_MULTI_CATEGORICAL) h->shape_kernels = h->narrow;       // from here on: the flag took effect (a shape that does not qualify runs the generic <mcat> kernels, data parallel included)
     if (upload_grad_src(h)) return bail(0);
-    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels;        // the heads train8_kernel has; a categorical one only where the flag asks for it
+    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels;        // the heads train8_kernel has; a categorical or multi-categorical one only where the flag asks for it
     { const char* e = getenv("PPO_HIP_NO_DW2"); const NetDev& nn = h->net;
       h->dw2 = !(e && e[0] == '1') && pair_head && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
     { const char* e = getenv("PPO_HIP_NO_T8"); const NetDev& nn = h->net;
@@ -1911,7 +1929,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
             HIP_OK(h, hipStreamSynchronize(h->stream));
         }
     }
-    if (h->dist == PPO_ACT_CATEGORICAL) h->pair_kernels = h->t8 || h->dw2;        // from here on: the flag took effect (a shape that does not qualify, both switches set: it did not)
+    if (h->dist != PPO_ACT_GAUSSIAN) h->pair_kernels = h->t8 || h->dw2;        // from here on: the flag took effect (a shape that does not qualify, both switches set: it did not)
     if (h->bf.on && bf16_create(h)) return bail(0);
     if (h->narrow) {
         attr_ok = true;
@@ -3692,6 +3710,8 @@ int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128
     if (h->shape_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
+    if (h->pair_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS (create it without the flag)");
     if (h->pair_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS (create it without the flag)");
     if (load_rccl(h->rccl, h->err)) return -1;
     HIP_OK(h, hipSetDevice(h->device));

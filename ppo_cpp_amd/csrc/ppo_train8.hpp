@@ -28,6 +28,8 @@ struct T8L {
     static constexpr int X0 = 0, H1 = X0 + 16 * LD0, H2 = H1 + 16 * T8_LD, D2 = H2 + 16 * T8_LD, D1 = D2 + 16 * T8_LD,
                          MU = D1 + 16 * T8_LD, PAR = MU + 16 * LDM, ACT = PAR + NPAR + 4, DLS = ACT + 16 * AP, ROWV = DLS + 16 * AP,
                          MISC = ROWV + 32, TOTAL = MISC + 128;
+    // the <.., MULTI> instantiations only: a row's K action indices, [16][PPO_MAX_COMPONENTS_DEV], behind the carve every other instantiation keeps
+    static constexpr int MACT = TOTAL, TOTAL_M = MACT + 16 * PPO_MAX_COMPONENTS_DEV;
 };
 
 #ifndef T8_PRO
@@ -144,9 +146,17 @@ __device__ __forceinline__ void t8_exchange(const f32x4 (&acc)[4], float* xch, i
 // MASK (with CAT): thread (er, ej) requests a.mask[(row0 + er) nA + ej + 32 q] where the Gaussian form requests its action elements and parks them in the ACT tile; the
 // same lane reads them back.  Forbidden categories are excluded from maximum, normaliser, neglogp and entropy and their d logits are exactly +0; a dead row reads nothing
 // and counts every category as allowed.  A row of ones gives the unmasked form's bits.  Nothing is indexed with the action or the mask.
-template <int KP0, int AP, bool CAT = false, bool MASK = false>
-__device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& a, float* lds, const unsigned bx, const unsigned by, const unsigned gx) {
+// MULTI (with CAT): K categorical components over the one logits row (TrainArgsM::comp), train_fwd_bwd_kernel<.., MULTI>'s arithmetic in this kernel's geometry.
+// `actions` holds K floats per row: threads 0..255 request element (row tid >> 4, component tid & 15) with the other inputs and park it in the MACT region (the
+// MISC words hold one index per row; the ACT tile is the mask's).  Two wave-uniform walks over the components, every lane taking part in every reduction with -inf / 0
+// for the elements outside the component: the first leaves each element its own component's maximum, so a0 and exp are formed ONCE per element; the second forms
+// the component's normaliser, action a0 and entropy, adds neglogp and entropy up in component order and leaves each element its own component's z, log z, H and
+// action column for the gradient.  A lane's two elements may belong to two components (or both to one that spans column 32): every select is per element.
+// One component is the <cat> form statement by statement.  No barrier beyond the <cat> form's; nothing is indexed with an action or a mask value.
+template <int KP0, int AP, bool CAT = false, bool MASK = false, bool MULTI = false>
+__device__ __forceinline__ void train8_body(const NetDev& net, const std::conditional_t<MULTI, TrainArgsM, TrainArgs>& a, float* lds, const unsigned bx, const unsigned by, const unsigned gx) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
     typedef T8L<KP0, AP> L8;
     constexpr int KS0 = KP0 / 16, KSA = AP / 16;       // k-steps of 16 in the first layer / in the head's backward product
     constexpr int CTA = AP / 16;                       // column tiles of the policy head (all AP columns in every wave)
@@ -188,13 +198,17 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         else if constexpr (!CAT) { if (tower == 0 && erow_live && ej + 32 * q < nA) av_[q] = a.actions[(size_t)(row0 + er) * nA + ej + 32 * q]; }
     }
     float r0 = 0.f, r1 = 0.f, r2 = 0.f, s0 = 0.f, s1 = 1.f, rc = 0.f;
+    float mk = 0.f;                                                                     // MULTI: action index of (row tid >> 4, component tid & 15)
+    if constexpr (MULTI) {
+        if (tower == 0 && tid < 16 * PPO_MAX_COMPONENTS_DEV && row0 + (tid >> 4) < a.n && (tid & 15) < a.comp.K) mk = a.actions[(size_t)(row0 + (tid >> 4)) * a.comp.K + (tid & 15)];
+    }
     const bool explicit_adv = a.advs != nullptr;
     if (tid < 16 && row0 + tid < a.n) {
         const int src = row0 + tid;
         if (tower == 0) {
             r0 = explicit_adv ? a.advs[src] : a.returns[src]; r2 = a.old_neglogp[src];
             if (!explicit_adv) { r1 = a.old_values[src]; s0 = a.adv_stats[0]; s1 = a.adv_stats[1]; }
-            if constexpr (CAT) rc = a.actions[src];                                      // the row's category index
+            if constexpr (CAT && !MULTI) rc = a.actions[src];                            // the row's category index
         } else { r0 = a.returns[src]; r2 = a.old_values[src]; }
     }
     const float* W0 = uni(a.theta + net.w_off[tower][0]);
@@ -234,8 +248,9 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         const bool live = row0 + tid < a.n;
         lds[L8::ROWV + 2 * tid] = live ? v0 : 0.f;
         lds[L8::ROWV + 2 * tid + 1] = live ? r2 : 0.f;
-        if constexpr (CAT) { if (tower == 0) lds[L8::MISC + 64 + tid] = rc; }
+        if constexpr (CAT && !MULTI) { if (tower == 0) lds[L8::MISC + 64 + tid] = rc; }
     }
+    if constexpr (MULTI) { if (tower == 0 && tid < 16 * PPO_MAX_COMPONENTS_DEV) lds[L8::MACT + tid] = mk; }    // dead rows, components >= K: zeros, never read
     STAMP(22);
     lds_barrier();
     STAMP(1);
@@ -342,7 +357,56 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
         bool ok[NA];
         float a0[NA], ex[NA], cz = 1.f, clz = 0.f;
         int cact = -1;
-        if constexpr (CAT) {
+        float zq[NA], lzq[NA], hq[NA];                                                 // MULTI: z, log z and H of the element's OWN component ...
+        int actq[NA];                                                                  // ... and that component's action column
+        if constexpr (MULTI) {
+            const int nK = a.comp.K;
+            const float* arow = lds + L8::MACT + er * PPO_MAX_COMPONENTS_DEV;
+            float mq[NA];
+#pragma unroll
+            for (int q = 0; q < NA; ++q) {
+                ok[q] = ej + 32 * q < nA;
+                if constexpr (MASK) ok[q] = ok[q] && (!live || lds[L8::ACT + er * AP + ej + 32 * q] != 0.f);
+                mq[q] = 0.f; zq[q] = 1.f; lzq[q] = 0.f; hq[q] = 0.f; actq[q] = -1;
+            }
+            for (int k = 0; k < nK; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                float bl = -INFINITY;
+#pragma unroll
+                for (int q = 0; q < NA; ++q) bl = (ok[q] && ej + 32 * q >= o && ej + 32 * q < e) ? tf_max(bl, mu[q]) : bl;
+                const float cm = t8_max32(bl);
+#pragma unroll
+                for (int q = 0; q < NA; ++q) mq[q] = (ej + 32 * q >= o && ej + 32 * q < e) ? cm : mq[q];
+            }
+#pragma unroll
+            for (int q = 0; q < NA; ++q) { a0[q] = mu[q] - mq[q]; ex[q] = expf(a0[q]); }
+            nlp = 0.f; sent = 0.f;
+            for (int k = 0; k < nK; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                const int act = live ? o + (int)arow[k] : -1;                              // compared with column indices only
+                float zs = 0.f, las = 0.f, es = 0.f;
+#pragma unroll
+                for (int q = 0; q < NA; ++q) {
+                    const bool in = ok[q] && ej + 32 * q >= o && ej + 32 * q < e;
+                    zs += in ? ex[q] : 0.f;
+                    las += (in && ej + 32 * q == act) ? a0[q] : 0.f;
+                }
+                const float kz = t8_sum32(zs);
+                const float la = t8_sum32(las);
+                const float klz = logf(kz);
+#pragma unroll
+                for (int q = 0; q < NA; ++q) es += (ok[q] && ej + 32 * q >= o && ej + 32 * q < e) ? cat_entropy_term(ex[q], kz, klz, a0[q]) : 0.f;
+                const float hk = t8_sum32(es);
+                const float nk = klz - la;
+                nlp = k == 0 ? nk : nlp + nk;
+                sent = k == 0 ? hk : sent + hk;
+#pragma unroll
+                for (int q = 0; q < NA; ++q) {
+                    const bool mine = ej + 32 * q >= o && ej + 32 * q < e;
+                    zq[q] = mine ? kz : zq[q]; lzq[q] = mine ? klz : lzq[q]; hq[q] = mine ? hk : hq[q]; actq[q] = mine ? act : actq[q];
+                }
+            }
+        } else if constexpr (CAT) {
             cact = live ? (int)lds[L8::MISC + 64 + er] : -1;
             float bl = -INFINITY;
 #pragma unroll
@@ -392,7 +456,8 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const TrainArgs& 
 #pragma unroll
         for (int q = 0; q < NA; ++q) {
             float dl = 0.f, dmu = 0.f;
-            if constexpr (CAT) { if (ok[q] && live) dmu = cat_grad_elem(d_nlp, ex[q], cz, a0[q], clz, sent, ej + 32 * q, cact, net.ent_coef, gi); }   // d l_j; forbidden / padding columns, dead rows: +0
+            if constexpr (MULTI) { if (ok[q] && live) dmu = cat_grad_elem(d_nlp, ex[q], zq[q], a0[q], lzq[q], hq[q], ej + 32 * q, actq[q], net.ent_coef, gi); }   // H of j's own component
+            else if constexpr (CAT) { if (ok[q] && live) dmu = cat_grad_elem(d_nlp, ex[q], cz, a0[q], clz, sent, ej + 32 * q, cact, net.ent_coef, gi); }   // d l_j; forbidden / padding columns, dead rows: +0
             else if (ej + 32 * q < nA && live) gauss_grad_elem(d_nlp, z[q], sigma[q], net.ent_coef, gi, dmu, dl);
             lds[L8::MU + er * L8::LDM + ej + 32 * q] = dmu;                         // the d mu tile: A operand of the head's backward product
             lds[L8::DLS + er * AP + ej + 32 * q] = dl;
@@ -515,4 +580,13 @@ __global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArg
     extern __shared__ __attribute__((aligned(16))) float lds[];
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs)>();
     train8_body<KP0, AP, CAT, MASK>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}
+// the multi-categorical forms, train8_kernel<KP0, AP, CAT, MASK, MULTI>: a further overload that takes the component table behind the arguments; T8L::TOTAL_M floats
+// of dynamic LDS (the action rows' region lies behind the carve of the other forms)
+template <int KP0, int AP, bool CAT, bool MASK, bool MULTI>
+__global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArgsM a) {
+    static_assert(MULTI && CAT, "the multi-categorical overload: a form of the categorical head");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsM)>();
+    train8_body<KP0, AP, CAT, MASK, MULTI>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
 }

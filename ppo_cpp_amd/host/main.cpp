@@ -71,13 +71,14 @@ int main(int argc, char** argv) {
                         "                   [--minibatches N]\n"
                         "                   [--hidden 256,256] [--saves N --dir DIR --id ID] [--path CKPT_PREFIX] [--resume] [--seeded] [--seed N]\n"
                         "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n"
-                        "                   [--time_limit N] [--no_bootstrap_truncated] [--discrete_kernels narrow|generic]\n"
+                        "                   [--time_limit N] [--no_bootstrap_truncated] [--discrete_kernels narrow|pair|generic]\n"
                         "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n"
                         "  --time_limit N: every environment ends its episodes after N steps (a TimeLimit wrapper); the value is bootstrapped at those truncations\n"
                         "  --no_bootstrap_truncated: treat them as terminal states instead (the reference's behaviour)\n"
                         "  --discrete_kernels: kernels of a discrete environment's categorical policy; narrow = the LDS-resident family where the network's shape\n"
-                        "                      qualifies (hidden widths <= 64), generic = the generic fp32 family (the default).  A multi-discrete environment's\n"
-                        "                      multi-categorical policy likewise (at most 64 logits in all).  Continuous environments: no effect\n");
+                        "                      qualifies (hidden widths <= 64), pair = the [256,256] train kernel pair where it qualifies (--hidden 256,256),\n"
+                        "                      generic = the generic fp32 family (the default).  A multi-discrete environment's multi-categorical policy\n"
+                        "                      likewise (at most 64 logits in all).  Continuous environments: no effect\n");
             return 0;
         }
         for (auto& al : kAliases) if (a == al[0] && i + 1 < argc) { f.kv[al[1]] = argv[++i]; ok = true; break; }
@@ -149,7 +150,7 @@ int main(int argc, char** argv) {
         cliprange_vf = (float)x;
     }
     const std::string dk = f.str("discrete_kernels", "generic");
-    if (dk != "narrow" && dk != "generic") { std::fprintf(stderr, "--discrete_kernels: expected narrow or generic, not '%s'\n", dk.c_str()); return 1; }
+    if (dk != "narrow" && dk != "pair" && dk != "generic") { std::fprintf(stderr, "--discrete_kernels: expected narrow, pair or generic, not '%s'\n", dk.c_str()); return 1; }
     int rc = 0;
     try {
         if (f.has("graph")) {                                                    // -g: shape, constants and initial weights from a reference graph file
@@ -160,7 +161,7 @@ int main(int argc, char** argv) {
         } else {
             // the head follows the environment's action space (the mock environments here are continuous: a Gaussian head, whatever --discrete_kernels says)
             const std::unique_ptr<Env> probe(f.has("seeded") ? static_cast<Env*>(new SeededEnvMock(1234u, (uint32_t)env0, obs_dim, 18)) : static_cast<Env*>(new EnvMock(env0 + 1)));
-            if (ppo_create_ex(&cfg, PPO2::action_dist_for(*probe, dk == "narrow"), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+            if (PPO2::create_handle(cfg, *probe, &h, dk == "narrow", dk == "pair" ? PPO_ACT_PAIR_KERNELS : 0) != 0) throw std::runtime_error(ppo_last_error(nullptr));
             if (ppo_init_orthogonal(h, (uint64_t)f.num("seed", 0)) != 0) throw std::runtime_error(ppo_last_error(h));     // same seed on every rank: replicated weights
         }
         const std::string xdir = f.str("explicit_dir", ""), ddir = f.str("dump_dir", "");

@@ -66,7 +66,8 @@ public:
         return PPO_ACT_CATEGORICAL | (discrete_shape_kernels ? PPO_ACT_SHAPE_KERNELS : 0);
     }
     // The handle that will serve `env`: ppo_create_multi_ex with the Env's components for an IMultiDiscrete Env (cfg.act_dim must be their sum; flags:
-    // PPO_ACT_SHAPE_KERNELS with discrete_shape_kernels -- the narrow kernels where the shape qualifies -- | extra_flags), otherwise
+    // PPO_ACT_SHAPE_KERNELS with discrete_shape_kernels -- the narrow kernels where the shape qualifies -- | extra_flags, e.g. PPO_ACT_PAIR_KERNELS: the
+    // [256,256] train kernel pair where that shape qualifies), otherwise
     // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);

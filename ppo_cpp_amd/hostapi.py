@@ -116,8 +116,8 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     weight_grad_assemble_kernel), "generic" (the default): without either.
     compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD.
     nvec=[n_0, ..]: MultiDiscreteTargetEnv with these components (act_dim is ignored: their sum) and a multi-categorical handle (PPO2::create_handle ->
-    ppo_create_multi_ex; discrete_kernels="narrow": with PPO_ACT_SHAPE_KERNELS, the narrow <mcat> kernels where the shape qualifies; "pair": nothing for this
-    head), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)
+    ppo_create_multi_ex; discrete_kernels="narrow": with PPO_ACT_SHAPE_KERNELS, the narrow <mcat> kernels where the shape qualifies; "pair": with
+    PPO_ACT_PAIR_KERNELS, train8_kernel<mcat[,mask]> + weight_grad_assemble_kernel where hidden is [256, 256] and sum(nvec) <= 64), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)
     and the result carries "forbidden_received"; n_playback: that many PPO2::eval steps afterwards, "playback_actions" [n_playback, K] and "playback_legal".
     "kernel_counts": the handle's ppo_kernel_counts after the run."""
     import numpy as np
