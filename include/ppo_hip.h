@@ -332,6 +332,21 @@ int ppo_rollout_act(ppo_handle* h, int32_t t, const float* noise, float* actions
 /* ppo_rollout_act under an action mask [E, A] (needs ppo_set_action_masking on): the mask is stored in row t of the rollout's mask buffer and the step samples
  * under it.  mask == NULL, and plain ppo_rollout_act on a masking handle, mean an all-ones row (the unmasked kernel; the row is recorded as ones). */
 int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const float* mask, float* actions_out);
+/* One launch per env step for a NARROW DISCRETE handle behind a host Env (default off; opt-in per handle).  It takes effect on a categorical or multi-categorical
+ * handle on which PPO_ACT_SHAPE_KERNELS took effect, without a communicator, with at most 32 environments, at most 64 observations and logits, the image + one row
+ * group within 160 KB of LDS, and PPO_HIP_NO_HOST_FUSED unset.  Then ppo_rollout_act[_masked] runs narrow_host_step_kernel<cat|mcat[,mask]>: ONE launch reads the
+ * last transition from the handle's pinned block, books EnvNormalize::step for it, normalises, runs the policy tower, samples with narrow_step_kernel<cat|mcat[,mask]>'s
+ * head arithmetic (same uniforms for the same seed or explicit noise), stores the [E, 1 | K] actions into pinned memory and raises a completion word; the mask of
+ * ppo_rollout_act_masked is copied into a pinned [E, A] block that the kernel reads in place and stores into row t of the mask buffer (the plain call on a masking
+ * handle: the unmasked form, a row of ones).  ppo_rollout_observe only posts the transition; values[t] are computed by one batched pass at ppo_rollout_finish.
+ * With or without explicit noise; never a resident form.  ppo_kernel_counts names, one per act launch, counted INSTEAD of the act launches of
+ * "narrow_step_kernel<cat|mcat[,mask]>": "narrow_host_step<cat>", "narrow_host_step<cat,mask>", "narrow_host_step<mcat>", "narrow_host_step<mcat,mask>".
+ * Anywhere else -- a Gaussian handle (its own fused and resident forms are not affected), a discrete handle that is not on the narrow family, more than 32
+ * environments, data parallel -- the call is accepted and nothing changes: same bits, same ppo_kernel_counts.  Against the per-step form of the same handle the
+ * normalised observations differ by rounding (the fused step scales with the variance in place of the per-step form's standard deviation pass), as the Gaussian
+ * fused form does against its general path; with normalisation off the two forms give the same bits.  Measured per env step: DESIGN.md section 5. */
+int ppo_set_host_step_fused(ppo_handle* h, int32_t on);   /* before ppo_rollout_alloc; changing it drops an allocated rollout, like ppo_set_action_masking */
+int ppo_host_step_fused(const ppo_handle* h);             /* the setting (0 / 1), not whether it took effect: ppo_kernel_counts says that */
 int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const float* raw_rew, const float* dones);
 /* Time-limit truncations (no reference counterpart).  The `done` of step t of the environments env_ids [count] (int32) was raised by a time limit, not by a
  * terminal state; terminal_raw_obs [count, O] are the RAW observations those episodes ended on (raw_obs of ppo_rollout_observe holds the observation after the

@@ -336,6 +336,17 @@ class PPOHip:
     def get_action_masking(self):
         return bool(self.lib.ppo_get_action_masking(self.h))
 
+    def set_host_step_fused(self, on=True):
+        """One launch per env step behind a host Env for a narrow categorical / multi-categorical handle (include/ppo_hip.h, ppo_set_host_step_fused): takes effect
+        with shape_kernels on a qualifying shape, at most 32 environments, no communicator; any other handle accepts it and nothing changes (kernel_counts says
+        which ran).  Call it before rollout_alloc: changing the setting drops an allocated rollout."""
+        self._ck(self.lib.ppo_set_host_step_fused(self.h, int(bool(on))))
+
+    @property
+    def host_step_fused(self):
+        """the setting, not whether it took effect"""
+        return bool(self.lib.ppo_host_step_fused(self.h))
+
     def rollout_act(self, t, noise=None, mask=None):
         out = np.empty((self.E,) + self._act_shape, np.float32)
         nz = _f32(noise, (self.E, self.A)) if noise is not None else None

@@ -67,7 +67,9 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK,
                      KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK,
                      KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK,
-                     KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK, KV_COUNT };
+                     KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK,
+                     KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK, KV_COUNT };
+static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
@@ -87,7 +89,10 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (ppo_create_multi_ex) on a narrow shape: counted INSTEAD of the <cat> and the generic names
                                        "narrow_step_kernel<mcat>", "narrow_step_kernel<mcat,mask>", "narrow_train_kernel<mcat>", "narrow_train_kernel<mcat,mask>",
                                        // a multi-categorical handle created with PPO_ACT_PAIR_KERNELS (ppo_create_multi_ex) on a [256,256] shape: counted INSTEAD of "train_fwd_bwd_kernel<mcat[,mask]>"
-                                       "train8_kernel<mcat>", "train8_kernel<mcat,mask>"};
+                                       "train8_kernel<mcat>", "train8_kernel<mcat,mask>",
+                                       // a narrow categorical / multi-categorical handle with ppo_set_host_step_fused on, <= 32 environments behind a host Env: one per act
+                                       // launch, counted INSTEAD of the act launches of "narrow_step_kernel<cat|mcat[,mask]>" (a bookkeeping-only launch is not counted)
+                                       "narrow_host_step<cat>", "narrow_host_step<cat,mask>", "narrow_host_step<mcat>", "narrow_host_step<mcat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -210,6 +215,9 @@ struct ppo_handle {
     unsigned* pin_flag = nullptr;     // pinned host word the step kernel raises when the actions are in pin_out
     unsigned act_seq = 0;
     bool host_pending = false; int host_pending_t = 0;   // a transition sits in pin_in, its bookkeeping rides in the next launch
+    // ... its discrete forms (ppo_set_host_step_fused on a narrow categorical / multi-categorical handle; host_fused_discrete() says whether it took effect):
+    // pin_mask = pinned host [E, A], the mask of the current env step, read by the kernel in place (a masking handle on which the form took effect)
+    bool host_step_fused = false; float* pin_mask = nullptr; float* pin_mask_dev = nullptr;
     // ... and the RESIDENT form (narrow_rollout_kernel in host mode): one launch serves many env steps, host and kernel talk
     // through sequence words in pinned memory (pin_flag[PCTL_*])
     bool opt_no_host_fused = false, opt_no_host_resident = false;     // PPO_HIP_NO_HOST_FUSED / _RESIDENT, read once in ppo_create
@@ -1092,8 +1100,8 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
     if (kp_ == 32 && ap_ == 32) { X(32, 32); } else if (kp_ == 64 && ap_ == 32) { X(64, 32); } else if (kp_ == 32 && ap_ == 64) { X(32, 64); } else { X(64, 64); } } while (0)
 
 // a categorical handle on the narrow family (created with PPO_ACT_SHAPE_KERNELS, qualifying shape).  It runs narrow_step_kernel / narrow_train_kernel<cat[,mask]>
-// only: every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the fused host step) asks
-// nw_gauss() where it is decided.
+// only: every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the resident host step) asks
+// nw_gauss() where it is decided.  The fused host step has discrete forms of its own, opt-in per handle: host_fused_discrete().
 static bool nw_cat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_CATEGORICAL; }
 // ... and a multi-categorical one (ppo_create_multi_ex with the flag): narrow_step_kernel / narrow_train_kernel<mcat[,mask]> only, under the same rule
 static bool nw_mcat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_MULTI_CATEGORICAL; }
@@ -1941,13 +1949,15 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
 #undef X
         if (nw_cat(h)) {
 #define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true>); \
-                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true>); } while (0)
+                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true>); \
+                           big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, false>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, true>); } while (0)
             X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
         }
         if (nw_mcat(h)) {
 #define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true, true>); \
-                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true, false, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true, true>); } while (0)
+                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true, false, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true, true>); \
+                           big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, false, true>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, true, true>); } while (0)
             X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
         }
@@ -2032,6 +2042,7 @@ void ppo_destroy(ppo_handle* h) {
     if (h->vram_in) (void)hipFree(h->vram_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
     if (h->pin_flag) (void)hipHostFree(h->pin_flag);
+    if (h->pin_mask) (void)hipHostFree(h->pin_mask);
     if (h->pin_wgflag) (void)hipHostFree(h->pin_wgflag);
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -2602,6 +2613,27 @@ int ppo_set_action_masking(ppo_handle* h, int on) {
 }
 int ppo_get_action_masking(const ppo_handle* h) { return h && h->masking ? 1 : 0; }
 
+static bool host_fused_discrete(const ppo_handle* h);           // (with the form decisions below)
+// The fused host-Env step of a narrow discrete handle (host_fused_discrete).  Any handle accepts the call; on a Gaussian handle, or a discrete one that is not on
+// the narrow family, only the bit is recorded: the rollout stays, same launches, same bits.
+int ppo_set_host_step_fused(ppo_handle* h, int32_t on) {
+    if (!h) return fail(nullptr, "ppo_set_host_step_fused: null handle");
+    if ((on != 0) == h->host_step_fused) return 0;
+    if (nw_cat(h) || nw_mcat(h)) {
+        // the rollout belongs to the old form (a posted transition, the pinned mask block): dropped, as ppo_set_action_masking does
+        ENTER_Q(h);                                                 // (a posted transition is booked first)
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        drop_graph(h);
+        h->E = 0; h->T = 0;
+        h->upd_cap_rows = 0; h->upd_cap_steps = 0;
+        h->host_proto = false; h->pin_in_busy = false;
+        trunc_clear(h);
+    }
+    h->host_step_fused = on != 0;
+    return 0;
+}
+int ppo_host_step_fused(const ppo_handle* h) { return h && h->host_step_fused ? 1 : 0; }
+
 int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
     ENTER(h);
     if (E < 1 || T < 1) return fail(h, "ppo_rollout_alloc: bad shape");
@@ -2619,6 +2651,13 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
     if (h->masking && (dev_alloc(h, &h->ro_mask, B * n.A) || mask_fill_ones(h, h->ro_mask, B * n.A))) return -1;
     h->E = E; h->T = T;
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    // the pinned mask block of the fused discrete host-Env step (only while masking is on and that form took effect)
+    if (h->pin_mask) { (void)hipHostFree(h->pin_mask); h->pin_mask = nullptr; h->pin_mask_dev = nullptr; }
+    if (h->masking && host_fused_discrete(h)) {
+        void* d = nullptr;
+        HIP_OK(h, hipHostMalloc((void**)&h->pin_mask, (size_t)E * n.A * sizeof(float), hipHostMallocDefault));
+        HIP_OK(h, hipHostGetDevicePointer(&d, h->pin_mask, 0)); h->pin_mask_dev = (float*)d;
+    }
     if (h->ro_tval) { (void)hipFree(h->ro_tval); h->ro_tval = nullptr; }
     h->tr_idx.clear(); h->tr_K = 0; h->obs_t = -1; h->tr_mark.assign(B, 0); h->tval_live = false;      // (the list does not survive a new rollout shape)
     return 0;
@@ -2727,8 +2766,18 @@ static size_t one_group_lds(const ppo_handle* h) { return ((size_t)h->nw.lds_tot
 // Small host-Env handles (narrow path, one rank): up to NW_RO_MAX_E environments are served by the resident kernel, up to NW_ROWS also by
 // one fused launch per env step.  While either is in use ("protocol" mode, h->host_proto) ppo_rollout_observe only fills the pinned
 // block: the transition is booked by the next launch / the resident kernel.  (The LDS bound covers both kernels, whichever serves the step.)
+// The discrete forms of the fused step (narrow_host_step_kernel<cat|mcat[,mask]>) are opt-in per handle, ppo_set_host_step_fused; this says whether the setting
+// TOOK EFFECT: a narrow categorical / multi-categorical handle (created with PPO_ACT_SHAPE_KERNELS on a qualifying shape), one rank, one row group.  Anywhere else
+// the handle runs the per-step form, silently.  Such a handle never takes a resident form: those keep a Gaussian head and have no channel for a per-step mask.
+static bool host_fused_discrete(const ppo_handle* h) {
+    const NetDev& n = h->net;
+    return h->host_step_fused && (nw_cat(h) || nw_mcat(h)) && !h->opt_no_host_fused && !h->comm && h->E <= NW_ROWS && n.O <= 64 && n.A <= 64 && h->pin_flag &&
+           one_group_lds(h) <= 160 * 1024;
+}
+
 static bool host_small(const ppo_handle* h) {
     if (h->opt_no_host_fused) return false;
+    if (host_fused_discrete(h)) return true;
     const NetDev& n = h->net;
     return nw_gauss(h) && !h->comm && !h->bf.on && h->E <= NW_RO_MAX_E && n.O <= 64 && n.A <= 64 && h->pin_flag &&
            ((size_t)h->nw.lds_total + std::max(nw_ro_extra(h->E, n.O), NW_RO_EXTRA)) * sizeof(float) <= 160 * 1024;
@@ -2736,6 +2785,7 @@ static bool host_small(const ppo_handle* h) {
 
 // explicit noise (one [E, A] block per call) cannot feed a kernel that is resident over the whole rollout: it leaves the fused step on
 static HostForm host_form(const ppo_handle* h, bool explicit_noise) {
+    if (host_fused_discrete(h)) return HF_FUSED;                 // (with or without explicit noise; never a resident form)
     if (host_small(h)) {
         if (!h->opt_no_host_resident && !explicit_noise) return use_rollout1(h) ? HF_RESIDENT1 : HF_RESIDENT;
         if (h->E <= NW_ROWS) return HF_FUSED;
@@ -2786,22 +2836,42 @@ static Q nw_args(const ppo_handle* h) {
 }
 
 // one launch of narrow_host_step_kernel: the pending transition's bookkeeping (if any) and, with act, the policy step of row t
-static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_dev, uint32_t rng_step) {
+// masked: (a discrete handle) the step samples under the mask in the pinned mask block
+static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_dev, uint32_t rng_step, bool masked = false) {
     const NetDev& n = h->net;
     const size_t E = h->E;
     NwHostStepArgs q = nw_args<NwHostStepArgs>(h);
     q.host_in = h->pin_in_dev; q.host_act = h->pin_out_dev; q.host_flag = h->pin_flag_dev; q.flag_value = act ? ++h->act_seq : 0u;
     q.noise = noise_dev;
-    if (act) { q.ro_obs = h->ro_obs + t * E * n.O; q.ro_act = h->ro_act + t * E * n.A; q.ro_nlp = h->ro_nlp + t * E; q.ro_done = h->ro_done + t * E; }
+    if (act) { q.ro_obs = h->ro_obs + t * E * n.O; q.ro_act = h->ro_act + t * E * h->Aw; q.ro_nlp = h->ro_nlp + t * E; q.ro_done = h->ro_done + t * E; }
     q.has_transition = h->host_pending ? 1 : 0;
     q.ro_rew_prev = h->host_pending ? h->ro_rew + (size_t)h->host_pending_t * E : nullptr;
     q.E = (int)E; q.act = act ? 1 : 0;
     q.seed = h->rng_seed; q.rng_step = rng_step; q.row_base = (uint32_t)(h->rank * h->E);
     const size_t lds = one_group_lds(h);
     ProfScope ps(h, PK_STEP);
+    if (nw_gauss(h)) {
 #define X(a, b, c, d) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, d>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q)
-    NW_DISPATCH(h, X);
+        NW_DISPATCH(h, X);
 #undef X
+    } else {
+        // the discrete forms: the mask block and row t of the mask buffer behind the arguments above, the component table behind those
+        const bool multi = nw_mcat(h);
+        NwHostStepArgsDM d{};
+        static_cast<NwHostStepArgs&>(d) = q;
+        d.host_mask = masked ? h->pin_mask_dev : nullptr;
+        d.ro_mask = (act && h->masking) ? h->ro_mask + t * E * n.A : nullptr;
+        d.Aw = h->Aw;
+        d.comp = h->comp;
+        const NwHostStepArgsD& dc = d;
+        if (act) ++h->kv[multi ? (masked ? KV_NARROW_HOST_STEP_MCAT_MASK : KV_NARROW_HOST_STEP_MCAT) : (masked ? KV_NARROW_HOST_STEP_CAT_MASK : KV_NARROW_HOST_STEP_CAT)];
+#define X(a, b, c, e) do { if (multi) { if (masked) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, true, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, d); \
+                                        else hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, false, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, d); } \
+                           else if (masked) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, dc); \
+                           else hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, false>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, dc); } while (0)
+        NW_DISPATCH(h, X);
+#undef X
+    }
     HIP_OK(h, hipGetLastError());
     h->host_pending = false;
     return 0;
@@ -2961,8 +3031,8 @@ static uint32_t host_rng_step(ppo_handle* h, const float* noise_dev) { return no
 
 // <= 32 environments on the narrow path: ONE launch does the pending transition's EnvNormalize bookkeeping (read from the
 // pinned block), the policy tower and the action store into pinned memory; the host spins on the completion word
-static int act_fused(ppo_handle* h, int t, const float* noise_dev) {
-    if (enqueue_host_step(h, t, true, noise_dev, host_rng_step(h, noise_dev))) return -1;
+static int act_fused(ppo_handle* h, int t, const float* noise_dev, bool masked) {
+    if (enqueue_host_step(h, t, true, noise_dev, host_rng_step(h, noise_dev), masked)) return -1;
     const unsigned want = h->act_seq;                            // (every ~quarter million polls: is the stream still alive?)
     return host_spin(h, 0x3ffff, "ppo_rollout_act: the step kernel finished without publishing", 0, [&] { return __atomic_load_n(h->pin_flag, __ATOMIC_ACQUIRE) == want; });
 }
@@ -3013,7 +3083,12 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
     if (mask && check_masks(h, "ppo_rollout_act_masked", mask, (size_t)h->E, nullptr)) return -1;
     ENTER(h);
     float* mask_row = nullptr;
-    if (h->masking) {
+    const bool fused_mask = h->masking && host_fused_discrete(h);
+    if (fused_mask) {
+        // the fused discrete step reads the mask from the pinned block in place and stores row t of the mask buffer itself (the plain call: ones);
+        // the block is free: the launch that read it last was waited for
+        if (mask) memcpy(h->pin_mask, mask, (size_t)h->E * h->net.A * sizeof(float));
+    } else if (h->masking) {
         // row t of the mask buffer: what was passed, or ones (the plain call on a masking handle: the unmasked kernel, the same bits)
         const size_t mc = (size_t)h->E * h->net.A;
         if (mask) { mask_row = h->ro_mask + (size_t)t * mc; HIP_OK(h, hipMemcpyAsync(mask_row, mask, mc * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
@@ -3035,7 +3110,7 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
     switch (form) {
         case HF_RESIDENT1:
         case HF_RESIDENT: rc = act_resident(h, form, t); break;
-        case HF_FUSED: rc = act_fused(h, t, nd); break;
+        case HF_FUSED: rc = act_fused(h, t, nd, fused_mask && mask); break;
         case HF_DIRECT: rc = act_direct(h, t, nd, mask_row, actions_out); break;
         case HF_COPY: rc = act_copy(h, t, nd, mask_row); break;
     }

@@ -1831,6 +1831,237 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net
     if (tid == 0) __hip_atomic_store(q.host_flag, q.flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The DISCRETE forms of the host-Env step (a narrow categorical / multi-categorical handle with ppo_set_host_step_fused on): the kernel above with
+// narrow_step_kernel<cat[,mask]>'s / <mcat[,mask]>'s head behind the head product.  Everything in front of the head -- the one-pass request of image, transition
+// and state, EnvNormalize::step's bookkeeping, the normalise-into-tile loop, the live_pipe layers -- is the Gaussian kernel's, statement for statement; a lane
+// owns the logit columns part + 16 k (four: A <= 64) and requests their uniforms (explicit noise [E, A], or the counter draw keyed by the GLOBAL logit index: the
+// per-step form's keys, so the same seed draws the same uniforms) and, MASK, their mask entries with that first pass -- the mask comes zero-copy from the pinned
+// block the host filled, and the row read is stored into row t of the rollout's mask buffer, so the update trains every row under the mask it was sampled under
+// (the unmasked form of a masking handle records ones).  Nothing is indexed with the sampled category or with the mask.  Actions are [E, Aw] (Aw = 1, or K) in
+// the rollout row and in the pinned landing buffer.  The publish sequence is unchanged; no waits on the device.
+// OVERLOADS behind a new argument struct (see narrow_step_kernel's), not defaulted parameters of the template above: the Gaussian instantiations keep their
+// symbols, their kernarg layout and their machine code.
+struct NwHostStepArgsD : NwHostStepArgs {
+    const float* host_mask;      // pinned host [E][A] (MASK forms)
+    float* ro_mask;              // row t of the rollout's mask buffer (a masking handle; null otherwise)
+    int Aw;                      // action columns per row: 1 (categorical) or K
+};
+struct NwHostStepArgsDM : NwHostStepArgsD { CompTable comp; };
+
+template <int KP0, int HP, int AP, int LL, bool MASK, bool MULTI>
+__device__ __forceinline__ void nw_host_step_discrete(const NetDev& net, const NwLayout& lay, const NwHostStepArgsD& q, const CompTable& comp) {
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, pipe = tid >> 8, ptid = tid & 255;
+    const int L = S::L(net), Kp0 = S::Kp0(net), Ap = S::Ap(net);
+    const int E = q.E, O = net.O, A = net.A;
+    float* xs = lds + lay.lds_total;                        // [E][O] raw observations
+    float* s_mean = xs + NW_RO_XS; float* s_var = s_mean + 64;
+    float* rs = s_var + 64;                                 // [32] rewards | [32] dones | [32] returns
+    // ---- everything this launch reads, requested together: image, transition (host memory) or current observations, state ----
+    {
+        const int n4 = q.act ? lay.w_fwd / 4 : 0;
+        for (int e = tid; e < n4; e += NW_THREADS) reinterpret_cast<float4*>(lds)[e] = reinterpret_cast<const float4*>(q.img)[e];
+        const float* src = q.has_transition ? q.host_in : q.st.raw_obs;
+        for (int i = tid; i < E * O; i += NW_THREADS) xs[i] = src[i];
+        if (tid < O) { s_mean[tid] = q.st.obs_mean[tid]; s_var[tid] = q.st.obs_var[tid]; }
+        if (tid < E) {
+            rs[2 * NW_ROWS + tid] = q.st.ret[tid];
+            if (q.has_transition) { rs[tid] = q.host_in[(size_t)E * O + tid]; rs[NW_ROWS + tid] = q.host_in[(size_t)E * O + E + tid]; }
+            else rs[NW_ROWS + tid] = q.st.done[tid];
+        }
+    }
+    const int r = ptid >> 4, part = ptid & 15;
+    const int row = 16 * pipe + r;
+    float uk[4], mv[4]; bool mk[4];                         // the lane's uniforms and mask entries (mv: the words as the host wrote them)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = part + 16 * k;
+        uk[k] = 0.5f; mk[k] = true; mv[k] = 1.0f;
+        if (q.act && j < A && row < E) {
+            uk[k] = q.noise ? q.noise[(size_t)row * A + j] : ctr_uniform(q.seed, q.row_base + row, q.rng_step, j);
+            if constexpr (MASK) { mv[k] = q.host_mask[(size_t)row * A + j]; mk[k] = mv[k] != 0.f; }
+        }
+    }
+    __syncthreads();
+    // ---- EnvNormalize::step bookkeeping for the transition that arrived (env_normalize.hpp:64-116) ------------------------------
+    if (q.has_transition) {
+        if (tid < O && q.norm_obs) {
+            const double cnt = *q.st.obs_count;
+            float sum = 0.f;
+            for (int e = 0; e < E; ++e) sum += xs[e * O + tid];
+            const float bmean = sum / (float)E;
+            float m2 = 0.f;
+            for (int e = 0; e < E; ++e) { const float d = xs[e * O + tid] - bmean; m2 += d * d; }
+            float m1, v1;
+            rs_merge(s_mean[tid], s_var[tid], cnt, bmean, m2, (float)E, m1, v1);
+            s_mean[tid] = m1; s_var[tid] = v1;
+            q.st.obs_mean[tid] = m1; q.st.obs_var[tid] = v1;
+        }
+        if (tid == 64) {
+            float* ret = rs + 2 * NW_ROWS;
+            float sum = 0.f;
+            for (int e = 0; e < E; ++e) { ret[e] = ret[e] * q.gamma + rs[e]; sum += ret[e]; }            // :66
+            float m1 = *q.st.ret_mean, v1 = *q.st.ret_var;
+            if (q.norm_rew) {
+                const double cnt = *q.st.ret_count;
+                const float bmean = sum / (float)E;
+                float m2 = 0.f;
+                for (int e = 0; e < E; ++e) { const float d = ret[e] - bmean; m2 += d * d; }
+                rs_merge(*q.st.ret_mean, *q.st.ret_var, cnt, bmean, m2, (float)E, m1, v1);
+                *q.st.ret_mean = m1; *q.st.ret_var = v1; *q.st.ret_count = (double)(float)E + cnt;
+            }
+            const float inv = en_istd(v1, q.eps);                                                    // :79
+            for (int e = 0; e < E; ++e) {
+                q.ro_rew_prev[e] = en_reward(rs[e], inv, q.norm_rew, q.clip_rew);
+                q.st.ret[e] = en_ret_reset(ret[e], rs[NW_ROWS + e]);                                           // :88-91
+                q.st.done[e] = rs[NW_ROWS + e];
+            }
+        }
+        for (int i = tid; i < E * O; i += NW_THREADS) q.st.raw_obs[i] = xs[i];       // the device copy ppo_rollout_finish bootstraps from
+        __syncthreads();
+        // (the count is bumped after every column has read it)
+        if (tid == 0 && q.norm_obs) *q.st.obs_count = (double)(float)E + *q.st.obs_count;              // :103
+    }
+    if (!q.act) return;
+    // ---- normalise (env_normalize.hpp:99-104) -> input tile + rollout row -----------------------------------------------------------
+    for (int i = tid; i < NW_ROWS * Kp0; i += NW_THREADS) {
+        const int rr = i / Kp0, j = i - rr * Kp0;
+        float x = 0.f;
+        if (rr < E && j < O) {
+            x = xs[rr * O + j];
+            if (q.norm_obs) x = obs_scale_var(x, s_mean[j], s_var[j], q.eps, q.clip_obs);
+            q.ro_obs[(size_t)rr * O + j] = x;
+        }
+        lds[lay.w_total + (rr >> 4) * lay.pipe_total + lay.x[0] + (rr & 15) * lay.ldx[0] + j] = x;
+    }
+    if (tid < E) q.ro_done[tid] = rs[NW_ROWS + tid];
+    lds_barrier();
+    float* P = lds + lay.w_total + pipe * lay.pipe_total;
+    const float* par = lds + lay.par;
+    const bool live_pipe = 16 * pipe < E;
+    for (int l = 0; l < L; ++l) {
+        const float* bias = par + net.par_b[l];
+        float* Ys = P + lay.x[l + 1]; const int ldy = lay.ldx[l + 1];
+        auto ep = [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+            const float b = bias[col];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) Ys[(4 * g + rr) * ldy + col] = fast_tanh(acc[rr] + b);
+        };
+        if (live_pipe) {
+            if (l == 0) nw_dense<KP0>(P + lay.x[0], lay.ldx[0], Kp0, lds + lay.wf[0], lay.wf_ld[0], S::Hp(net, 0), ep);
+            else nw_dense<HP>(P + lay.x[l], lay.ldx[l], S::Hp(net, l - 1), lds + lay.wf[l], lay.wf_ld[l], S::Hp(net, l), ep);
+        }
+        lds_barrier();
+    }
+    const float* hL = P + lay.x[L]; const int ldh = lay.ldx[L]; const int HpL = S::Hp(net, L - 1);
+    float* mus = P + lay.mu; const int ldm = lay.ldm;
+    if (live_pipe) nw_dense<HP>(hL, ldh, HpL, lds + lay.wh, lay.wh_ld, Ap, [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+        const float b = par[net.par_bmu + col];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mus[(4 * g + k) * ldm + col] = acc[k] + b;
+    });
+    lds_barrier();
+    if (live_pipe) {
+        if (q.ro_mask && row < E) {                           // the mask row this step samples under (the unmasked form of a masking handle: ones)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int j = part + 16 * k; if (j < A) q.ro_mask[(size_t)row * A + j] = mv[k]; }
+        }
+        if constexpr (!MULTI) {
+            // narrow_step_kernel<cat[,mask]>'s head: the MASKed pair starts at A ("none yet"); a row without any allowed category (refused by the host checks)
+            // ends at A and is brought back inside the tile
+            float bp = -INFINITY, bl = -INFINITY;
+            int ip = MASK ? A : 0, il = MASK ? A : 0;
+            float lk[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = part + 16 * k;
+                lk[k] = 0.f;
+                if (j < A) {
+                    const float l = mus[r * ldm + j];
+                    lk[k] = l;
+                    const float pl = gumbel(l, uk[k]);
+                    if (mk[k]) { cat_take<MASK>(pl, j, A, bp, ip); cat_take<MASK>(l, j, A, bl, il); }
+                }
+            }
+            group16_argmax(bp, ip);
+            group16_argmax(bl, il);
+            if constexpr (MASK) ip = min(ip, A - 1);
+            const float m = bl;
+            float z = 0.f, la = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = part + 16 * k;
+                if (j < A) {
+                    if (j == ip) la = lk[k] - m;                  // (one lane of the row holds it; the others add zeros)
+                    if (mk[k]) z += expf(lk[k] - m);
+                }
+            }
+            z = group16_sum(z); la = group16_sum(la);
+            if (part == 0 && row < E) {
+                q.ro_act[row] = (float)ip; q.host_act[row] = (float)ip;
+                q.ro_nlp[row] = logf(z) - la;
+            }
+        } else {
+            // narrow_step_kernel<mcat[,mask]>'s head: the components walked over the lane's four columns; lane k of the row keeps component k's index
+            float lk[4], pk[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = part + 16 * k;
+                lk[k] = j < A ? mus[r * ldm + j] : 0.f;
+                pk[k] = gumbel(lk[k], uk[k]);
+            }
+            float nlp = 0.f, my_a = 0.f;
+            for (int c = 0; c < comp.K; ++c) {
+                const int o = comp.off[c], e = comp.off[c + 1];
+                float bp = -INFINITY, bl = -INFINITY;
+                int ip = MASK ? e : o, il = MASK ? e : o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = part + 16 * k;
+                    if (j >= o && j < e && mk[k]) { cat_take<MASK>(pk[k], j, e, bp, ip); cat_take<MASK>(lk[k], j, e, bl, il); }
+                }
+                group16_argmax(bp, ip);
+                group16_argmax(bl, il);
+                if constexpr (MASK) ip = min(ip, e - 1);
+                const float m = bl;
+                float z = 0.f, la = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = part + 16 * k;
+                    if (j >= o && j < e) {
+                        if (j == ip) la = lk[k] - m;              // (one lane of the row holds it; the others add zeros)
+                        if (mk[k]) z += expf(lk[k] - m);
+                    }
+                }
+                z = group16_sum(z); la = group16_sum(la);
+                const float nk = logf(z) - la;
+                nlp = c == 0 ? nk : nlp + nk;
+                if (part == c) my_a = (float)(ip - o);
+            }
+            if (part < comp.K && row < E) { q.ro_act[(size_t)row * q.Aw + part] = my_a; q.host_act[(size_t)row * q.Aw + part] = my_a; }
+            if (part == 0 && row < E) q.ro_nlp[row] = nlp;
+        }
+    }
+    // ---- publish: the host's actions have landed, then the completion word ------------------------------------------------------------
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(q.host_flag, q.flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <int KP0, int HP, int AP, int LL, bool CAT, bool MASK>
+__global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net, NwLayout lay, NwHostStepArgsD q) {
+    static_assert(CAT, "the discrete overloads: a form of the categorical head");
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwHostStepArgsD)>();
+    nw_host_step_discrete<KP0, HP, AP, LL, MASK, false>(net, lay, q, CompTable{});
+}
+template <int KP0, int HP, int AP, int LL, bool CAT, bool MASK, bool MULTI>
+__global__ __launch_bounds__(NW_THREADS) void narrow_host_step_kernel(NetDev net, NwLayout lay, NwHostStepArgsDM q) {
+    static_assert(MULTI && CAT, "the multi-categorical overload: a form of the categorical head");
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwHostStepArgsDM)>();
+    nw_host_step_discrete<KP0, HP, AP, LL, MASK, true>(net, lay, q, q.comp);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // Cooperative persistent rollout for 65..2048 environments on the device env (BASELINE configs[3]: 1024): G = ceil(E / 32)
 // workgroups, each resident on its own CU for the whole rollout and owning 32 environments (image, raw observations, returns

@@ -179,6 +179,7 @@ struct ppo_host_args {
     int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD)
     int n_components, nvec[16];  // ppo_host_learn_multi: the components of MultiDiscreteTargetEnv (act_dim is their sum)
     int multi_masked;            // ppo_host_learn_multi: the environments also carry IActionMask
+    int host_step_fused;         // ppo_set_host_step_fused(h, 1) on the created handle before PPO2 sees it: the one-launch host-Env step of a narrow discrete handle (discrete_kernels == 1, <= 32 environments); nothing changes anywhere else
 };
 // the handle's action_dist for `env`: PPO2's choice, plus the opt-ins: the [256,256] pair for a categorical head, the one such a head needs on the bf16 path
 static int32_t host_action_dist(Env& env, const ppo_host_args* a) {
@@ -228,6 +229,7 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
           cfg.compute_dtype = a->compute_dtype;
           if (ppo_create_ex(&cfg, host_action_dist(*probe, a), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
+        if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         if (x && x->theta_in && ppo_set_flat(h, 0, x->theta_in, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<Env>> envs;
         auto make_env = [&](uint32_t i) -> Env* {
@@ -385,6 +387,7 @@ int ppo_host_learn_multi(const ppo_host_args* a, float* reward_curve, long long*
         for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MultiDiscreteTargetEnv>(1234u, (uint32_t)i, O, nvec, 100, a->multi_masked != 0)); envs.push_back(kids.back()); }
         if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : 0) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
+        if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         {
             EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, a->max_workers)), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
             struct Plain : Env, IActionMask, IMultiDiscrete {       // hides the EnvNormalize type to force the reference loop; the two mixins stay visible
@@ -582,6 +585,7 @@ int ppo_host_learn_masked(const ppo_host_args* a, float* reward_curve, long long
           cfg.compute_dtype = a->compute_dtype;
           if (ppo_create_ex(&cfg, host_action_dist(probe, a), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
+        if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<MaskedTargetEnv>> kids;
         std::vector<std::shared_ptr<Env>> envs;
         for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MaskedTargetEnv>(1234u, (uint32_t)i, O, A)); envs.push_back(kids.back()); }

@@ -13,7 +13,7 @@ class HostArgs(C.Structure):
                 ("seeded_env", C.c_int), ("device", C.c_int), ("max_workers", C.c_int), ("reference_loop", C.c_int),
                 ("norm_obs", C.c_int), ("norm_reward", C.c_int), ("seed", C.c_ulonglong), ("obs_dim", C.c_int), ("act_dim", C.c_int),
                 ("cliprange_vf", C.c_float), ("discrete_kernels", C.c_int), ("compute_dtype", C.c_int),
-                ("n_components", C.c_int), ("nvec", C.c_int * 16), ("multi_masked", C.c_int)]
+                ("n_components", C.c_int), ("nvec", C.c_int * 16), ("multi_masked", C.c_int), ("host_step_fused", C.c_int)]
 
 
 def _discrete_kernels(name):
@@ -108,7 +108,8 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, nvec=None, masked=False, n_playback=0):
+                obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, nvec=None, masked=False, n_playback=0,
+                host_step_fused=False):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
@@ -119,7 +120,9 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     ppo_create_multi_ex; discrete_kernels="narrow": with PPO_ACT_SHAPE_KERNELS, the narrow <mcat> kernels where the shape qualifies; "pair": with
     PPO_ACT_PAIR_KERNELS, train8_kernel<mcat[,mask]> + weight_grad_assemble_kernel where hidden is [256, 256] and sum(nvec) <= 64), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)
     and the result carries "forbidden_received"; n_playback: that many PPO2::eval steps afterwards, "playback_actions" [n_playback, K] and "playback_legal".
-    "kernel_counts": the handle's ppo_kernel_counts after the run."""
+    "kernel_counts": the handle's ppo_kernel_counts after the run.
+    host_step_fused=True: ppo_set_host_step_fused(h, 1) on the created handle (ppo_host_args::host_step_fused): with discrete_kernels="narrow" and at most 32
+    environments the act side runs narrow_host_step_kernel<cat|mcat[,mask]>, one launch per env step; nothing changes anywhere else."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -135,6 +138,7 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
         a.obs_dim, a.act_dim, a.cliprange_vf, a.compute_dtype = obs_dim, sum(nvec), cliprange_vf, int(compute_dtype)
         a.n_components, a.multi_masked = len(nvec), int(bool(masked))
         a.discrete_kernels = _discrete_kernels(discrete_kernels)
+        a.host_step_fused = int(bool(host_step_fused))
         for i, x in enumerate(nvec):
             a.nvec[i] = x
         out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros((n_playback, len(nvec)), np.float32),
@@ -160,6 +164,7 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     a.cliprange_vf = cliprange_vf
     a.discrete_kernels = _discrete_kernels(discrete_kernels)
     a.compute_dtype = int(compute_dtype)
+    a.host_step_fused = int(bool(host_step_fused))
     out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32)}
     names = ((C.c_char * 32) * 64)(); cnt = (C.c_longlong * 64)(); ncnt = C.c_int(0)
     x = HostExplicit(None, None, None, out["losses"].ctypes.data, None, None, None, None, None, None, None, out["reward_curve"].ctypes.data,
@@ -201,11 +206,11 @@ def learn_time_limit(n_envs, n_steps, hidden, n_updates, nminibatches, noptepoch
 
 
 def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0):
+                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, host_step_fused=False):
     """PPO2::learn on MaskedTargetEnv x n_envs (host/env/env_mock.hpp: DiscreteTargetEnv's task with about half of the categories forbidden at every step) behind
     VecEnv + EnvNormalize, with the library's own exploration noise and shuffles (ppo_host_learn_masked).  PPO2 finds the IActionMask mixin and masks by itself.
     Returns the mean un-normalised reward of every update's rollout [n_updates], the count of forbidden actions the environments received over the whole run, and
-    n_playback deterministic playback actions with their legality.  discrete_kernels, compute_dtype: as in learn_curve."""
+    n_playback deterministic playback actions with their legality.  discrete_kernels, compute_dtype, host_step_fused: as in learn_curve."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -220,6 +225,7 @@ def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, l
     a.cliprange_vf = cliprange_vf
     a.discrete_kernels = _discrete_kernels(discrete_kernels)
     a.compute_dtype = int(compute_dtype)
+    a.host_step_fused = int(bool(host_step_fused))
     out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros(n_playback, np.float32), "playback_legal": np.zeros(n_playback, np.float32)}
     forbidden = C.c_longlong(-1)
     r = HostResult()
