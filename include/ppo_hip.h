@@ -134,11 +134,11 @@ int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_
  * Masks are [n, A] as for the categorical head and exclude per component; a row of ones gives the unmasked bits.  The host checks (before anything is uploaded;
  * each message names row and component): every COMPONENT of every mask row allows a category; a ppo_train_step_masked row's action k is allowed by its
  * component's mask; every action value of ppo_train_step / of an uploaded rollout field 1 is an integer in [0, n_k).
- * Runs the generic PPO_F32 kernel family (never the bf16 forms; the narrow family and the [256,256] train8 pair only through ppo_create_multi_ex's flags, below).  ppo_kernel_counts names,
+ * Runs the generic PPO_F32 kernel family (the narrow family, the [256,256] train8 pair and the bf16 path only through ppo_create_multi_ex's flags, below).  ppo_kernel_counts names,
  * counted INSTEAD of the <cat> ones: "policy_step_kernel<mcat>", "policy_step_kernel<mcat,mask>", "train_fwd_bwd_kernel<mcat>", "train_fwd_bwd_kernel<mcat,mask>".
  * Data parallel and both shuffles work as for a categorical PPO_F32 handle.
  * Errors of ppo_create_multi, each naming the limit: n_components outside 1..PPO_MAX_COMPONENTS, a component with fewer than 2 categories, cfg->act_dim != sum of
- * nvec, compute_dtype PPO_BF16.  ppo_create_ex(cfg, PPO_ACT_MULTI_CATEGORICAL, ..) stays an "unknown action_dist" error: the table has to come with the call. */
+ * nvec, compute_dtype PPO_BF16 (without ppo_create_multi_ex's PPO_ACT_BF16_MULTI_HEAD).  ppo_create_ex(cfg, PPO_ACT_MULTI_CATEGORICAL, ..) stays an "unknown action_dist" error: the table has to come with the call. */
 #define PPO_ACT_MULTI_CATEGORICAL 2
 int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out);
 /* ppo_create_multi with flags (ppo_create_multi(cfg, nvec, K, out) is ppo_create_multi_ex(cfg, nvec, K, 0, out): same checks, same messages, same bits).
@@ -176,8 +176,30 @@ int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_compo
  *                        microsecond per component.  It lost to the generic form at no row count measured.
  *                        Data parallel is not available to a handle on which the flag took effect: ppo_dist_init refuses it ("... data parallel is not
  *                        supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS") and leaves it usable.
- *   PPO_ACT_BF16_HEAD    accepted, nothing to select (the head has no bf16 kernels); compute_dtype PPO_BF16 stays refused.
+ *   PPO_ACT_BF16_HEAD    accepted, nothing to select (the flag belongs to ppo_create_ex's categorical head; this head's bf16 forms are asked for with
+ *                        PPO_ACT_BF16_MULTI_HEAD); compute_dtype PPO_BF16 stays refused with it.
+ *   PPO_ACT_BF16_MULTI_HEAD  with compute_dtype PPO_BF16 creates the handle on the bf16 path (wide nets): staging, the hidden-layer GEMMs, bf16_heads_kernel, the
+ *                        backward links, the weight-gradient GEMM and the assembly + clip + Adam launch are those of every PPO_BF16 handle; the logits are the head
+ *                        GEMM's fp32 partial products added in range order, and bf16_sample_kernel / bf16_loss_kernel run their <mcat> / <mcat,mask> forms: one
+ *                        wave per row, lane l owns logits l and l + 64 (so sum of nvec <= 128; more is an error that names the limit), and the lanes walk the K
+ *                        components with the arithmetic stated above, 64-lane butterflies per component ("none yet" of a masked component = one past its end).
+ *                        The d logits go where d mu goes (forbidden and padding columns exactly +0), the d logstd slot words are zeros.  One component gives the
+ *                        bits of a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) in every output; a row of ones as mask gives the unmasked bits; the act
+ *                        model's neglogp is the train model's.  Every entry point of a multi-categorical handle works: step / act (masked too), train step,
+ *                        the rollout calls with ppo_set_action_masking and field 8, ppo_update (kernel nodes only in its captured graph), ppo_collect_synthetic,
+ *                        ppo_get_last_grad, checkpoints (the tensors of an fp32 handle of the same nvec).  PPO_HIP_NO_BF16_CHAIN and PPO_HIP_NO_REDUCE_ADAM act
+ *                        as on every PPO_BF16 handle.  ppo_kernel_counts names, counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence":
+ *                        "bf16_step_sequence<mcat>", "bf16_step_sequence<mcat,mask>", "bf16_train_sequence<mcat>", "bf16_train_sequence<mcat,mask>".  Without
+ *                        the flag PPO_BF16 stays refused; with PPO_F32 the flag is accepted and changes nothing (same bits, same ppo_kernel_counts);
+ *                        PPO_ACT_SHAPE_KERNELS / PPO_ACT_PAIR_KERNELS beside it on a PPO_BF16 handle are accepted and ignored.  ppo_create_ex rejects the bit.
+ *                        Measured at (256 observations, [1024,1024,1024], nvec = (16,) x 4) against the generic fp32 <mcat> handle in one process: train step 242.1
+ *                        against 1275.8 us at 4096 rows (0.19) and 170.8 against 524.5 us at 256 rows, policy step 153.2 against 850.9 us at 8192 rows; with 128 logits
+ *                        the generic family cannot hold that net.  Sixteen components cost 1.09 of the categorical PPO_BF16 handle's train step and 1.36 of its policy
+ *                        step: about 1.7 us per component of dependent butterflies.
+ *                        Not the default (opt-in).  Data parallel is not available: ppo_dist_init refuses the handle ("... data parallel is not supported for a
+ *                        multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD") and leaves it usable.
  * Any other bit is an error ("ppo_create_multi_ex: unknown flag bit 0x.."). */
+#define PPO_ACT_BF16_MULTI_HEAD 0x1000
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out);
 /* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian handle, 1 with nvec[0] = A for a categorical one */
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec);
@@ -398,7 +420,8 @@ int ppo_dist_unique_id(char uid[128]);
  *  a multi-categorical one on which that flag took effect (ppo_create_multi_ex) likewise: "... for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS";
  *  one on which PPO_ACT_PAIR_KERNELS took effect likewise: "... data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a multi-categorical one on which PPO_ACT_PAIR_KERNELS took effect: "... data parallel is not supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS";
- *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD") */
+ *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD";
+ *  a multi-categorical PPO_BF16 handle (PPO_ACT_BF16_MULTI_HEAD): "... data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
 int ppo_dist_world(const ppo_handle* h);
 /* What a reader of a scaling run needs in order to check the ranks (all out-pointers optional): the number of ranks the

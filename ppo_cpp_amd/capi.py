@@ -59,6 +59,7 @@ MAX_COMPONENTS = 16                                     # PPO_MAX_COMPONENTS
 ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS, OR-ed into ppo_create_ex's action_dist
 ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, likewise
 ACT_PAIR_KERNELS = 0x400                                # PPO_ACT_PAIR_KERNELS, likewise
+ACT_BF16_MULTI_HEAD = 0x1000                            # PPO_ACT_BF16_MULTI_HEAD, a flag of ppo_create_multi_ex only
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -87,7 +88,11 @@ class PPOHip:
     pair_kernels=True with it (ppo_create_multi_ex with PPO_ACT_PAIR_KERNELS): hidden [256, 256] with at most 64 observations and sum(nvec) <= 64 trains with
     train8_kernel<mcat[,mask]> + weight_grad_assemble_kernel instead of train_fwd_bwd_kernel<mcat[,mask]> and its two followers (the act side is
     unchanged; no data parallel on a handle the flag took effect on); any other shape runs the generic <mcat> kernels.  shape_kernels and pair_kernels
-    may be given together: their shape rules never both hold, each flag acts where its own rule holds.  bf16_head: nothing for this head.
+    may be given together: their shape rules never both hold, each flag acts where its own rule holds.
+    bf16_head=True with it and compute_dtype=1 (ppo_create_multi_ex with PPO_ACT_BF16_MULTI_HEAD): the bf16 matrix-core path with the multi-categorical
+    head (bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>; sum(nvec) <= 128; masks included; no data parallel), e.g.
+    PPOHip(O, None, hidden, action_dist="multi_categorical", nvec=[..], compute_dtype=1, bf16_head=True).  Without it that combination is refused; on a
+    compute_dtype=0 handle bf16_head changes nothing (no flag is passed).
 
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -129,6 +134,8 @@ class PPOHip:
         if multi:
             nv = (C.c_int32 * max(len(nvec), 1))(*nvec)
             flags = (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_PAIR_KERNELS if pair_kernels else 0)
+            if bf16_head and cfg.compute_dtype == 1:
+                flags |= ACT_BF16_MULTI_HEAD
             if (self.lib.ppo_create_multi_ex(C.byref(cfg), nv, len(nvec), flags, C.byref(h)) if flags
                     else self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h))) != 0:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())

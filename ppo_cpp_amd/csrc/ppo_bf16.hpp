@@ -770,6 +770,7 @@ struct SampleArgsB {
     int n, A; uint32_t seed, rng_step, row_base;
     const float* mask;                  // [n, A] action mask of the categorical head (non-zero = allowed); read by the <CAT, MASK> instantiation only
 };
+struct SampleArgsBM : SampleArgsB { CompTable comp; };   // the <.., MULTI> instantiations' arguments (action / det_action: K floats per row, the index within each component)
 
 // ---- categorical head (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD): the arithmetic of policy_step_kernel<.., CAT, MASK> / train_fwd_bwd_kernel<.., CAT, MASK> (ppo_head.hpp) in the
 // geometry of the two kernels below -- one wave per row, lane l owns categories l and l + 64 -- with 64-lane __shfl_xor butterflies where those kernels reduce over 16 lanes.
@@ -781,10 +782,11 @@ __device__ __forceinline__ float wave_sum_all(float v) { for (int o = 32; o > 0;
 // The row statistics BOTH kernels need, in ONE shape (the sample kernel's neglogp and the loss kernel's are then the same bits on the same weights): maximum m and its
 // index over the allowed categories (ok[e]: category lane + 64 e exists and is allowed), a0 = l - m, ex = exp(a0), z = sum of ex over the allowed ones.
 // MASK: the index starts at A ("none yet"), so a lane without an allowed category loses every tie of the butterfly to a real index.
+// A component [first, A) of the multi-categorical head: ok[e] says membership too, a lane without a member holds the identity (-inf at `first`, or "none yet" = A).
 template <bool MASK>
-__device__ __forceinline__ void cat_row_norm(const float (&lg)[2], const bool (&ok)[2], int lane, int A, int& il, float (&a0)[2], float (&ex)[2], float& z) {
+__device__ __forceinline__ void cat_row_norm(const float (&lg)[2], const bool (&ok)[2], int lane, int A, int& il, float (&a0)[2], float (&ex)[2], float& z, int first = 0) {
     float bl = -INFINITY;
-    il = MASK ? A : 0;
+    il = MASK ? A : first;
 #pragma unroll
     for (int e = 0; e < 2; ++e)
         if (ok[e]) cat_take<MASK>(lg[e], lane + 64 * e, A, bl, il);
@@ -806,14 +808,66 @@ __device__ __forceinline__ float cat_row_pick(const float (&a0)[2], const bool (
 // neglogp and the train model's are the same bits on the same weights (first-epoch ratio exactly 1)
 // CAT: the head's columns are logits; action / det_action are ONE float per row (the category index).  MASK (with CAT): a.mask [n, A] takes the forbidden
 // categories out of both argmaxes and of the normaliser; the lane that owns category j reads the mask entry next to its logit.
+// MULTI (with CAT): K categorical components over the one logits row (SampleArgsBM::comp), policy_step_kernel<.., MULTI>'s rules per component in this geometry: the lanes
+// keep their two logits, mask entries and uniforms (keyed by the global logit index j) and walk the components; in component k = [o, e) an element takes part iff it
+// exists, is allowed and o <= j < e, every other lane holds the identity of the 64-lane butterflies, "none yet" is e.  neglogp is the sum of the components' in
+// component order; lane k keeps component k's two indices (minus o) and stores them as action / det_action [n, K].  K = 1: the <CAT> form's operations on the row.
 #define BS_ROWS 4
-template <bool CAT = false, bool MASK = false>
-__global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(SampleArgsB a) {
+template <bool CAT = false, bool MASK = false, bool MULTI = false>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(std::conditional_t<MULTI, SampleArgsBM, SampleArgsB> a) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
     const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * BS_ROWS + r;
     const bool live = row < a.n;
-    if constexpr (CAT) {
+    if constexpr (MULTI) {
+        if (!live) return;                                   // (a row is a whole wave and the kernel has no barrier)
+        float lg[2], pl[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = lane + 64 * e;
+            float u = 0.5f;
+            lg[e] = 0.f; ok[e] = j < a.A;
+            if (j < a.A) {
+                lg[e] = head_sum(a.head[0], (size_t)row * a.ldh + j, a.hsplit, a.hstride);
+                if constexpr (MASK) ok[e] = a.mask[(size_t)row * a.A + j] != 0.f;
+                u = a.noise ? a.noise[(size_t)row * a.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);     // (a forbidden category keeps its uniform)
+            }
+            pl[e] = gumbel(lg[e], u);
+        }
+        float nlp = 0.f, my_a = 0.f, my_d = 0.f;             // lane k keeps component k's two indices
+        for (int k = 0; k < a.comp.K; ++k) {
+            const int o = a.comp.off[k], ce = a.comp.off[k + 1];
+            bool okk[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) { const int j = lane + 64 * e; okk[e] = ok[e] && j >= o && j < ce; }
+            // the Gumbel argmax over the component's allowed set (gumbel, cat_take)
+            float bp = -INFINITY;
+            int ip = MASK ? ce : o;
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                if (okk[e] && (pl[e] > bp || (MASK && ip == ce))) { bp = pl[e]; ip = lane + 64 * e; }
+            wave_argmax(bp, ip);
+            int il;
+            float a0[2], ex[2], z;
+            cat_row_norm<MASK>(lg, okk, lane, ce, il, a0, ex, z, o);
+            ip = min(ip, ce - 1); il = min(il, ce - 1);      // (a component without an allowed category, which the host checks refuse, ends at e)
+            const float la = cat_row_pick(a0, okk, lane, ip);
+            const float nk = logf(z) - la;
+            nlp = k == 0 ? nk : nlp + nk;
+            if (lane == k) { my_a = (float)(ip - o); my_d = (float)(il - o); }
+        }
+        if (lane < a.comp.K) {
+            if (a.action) a.action[(size_t)row * a.comp.K + lane] = my_a;
+            if (a.det_action) a.det_action[(size_t)row * a.comp.K + lane] = my_d;
+        }
+        if (lane == 0) {
+            if (a.neglogp) a.neglogp[row] = nlp;
+            if (a.value) a.value[row] = head_sum(a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride);
+        }
+        return;
+    } else if constexpr (CAT) {
         if (!live) return;                                   // (a row is a whole wave and the kernel has no barrier)
         float lg[2], u[2];
         bool ok[2];
@@ -889,6 +943,7 @@ struct LossArgsB {
     float* slots[2]; int slot_w, slot_head, slot_aux, slot_loss;
     const float* mask;                  // [n][A] action masks in minibatch order (non-zero = allowed); read by the <CAT, MASK> instantiation only
 };
+struct LossArgsBM : LossArgsB { CompTable comp; };   // the <.., MULTI> instantiations' arguments (`actions`: K floats per row, the index within each component)
 
 #ifndef BL_ROWS
 #define BL_ROWS 16                 // rows per block of the loss kernel: one slot row of partial sums per block
@@ -900,9 +955,14 @@ struct LossArgsB {
 // CAT: `actions` holds ONE float per row (the category index, read once and compared with the lane's j: nothing is indexed with it); d logits go where d mu goes, the
 // aux (d logstd) slot words are zeros, pt[1] is the row's categorical entropy.  MASK (with CAT): a.mask [n][A]; maximum, normaliser, neglogp and entropy run over the
 // allowed categories, d logits of a forbidden one is exactly +0.  Same lane loops and butterflies as <CAT>: an all-ones mask gives its bits.
-template <bool CAT = false, bool MASK = false>
-__global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
+// MULTI (with CAT): K categorical components over the one logits row (LossArgsBM::comp), train_fwd_bwd_kernel<.., MULTI>'s arithmetic in this geometry.  `actions` holds K
+// floats per row: lane k < K loads its one and the walk broadcasts it.  Per component k = [o, e) the <CAT> row statistics run over the elements that exist, are allowed
+// and lie in [o, e) (every other lane: the butterflies' identity; "none yet" is e); neglogp and entropy are the components' sums in component order.  An element belongs to
+// exactly one component and keeps that component's a0, exp, z, log z, entropy H_k and action column as the walk passes it: cat_grad_elem runs once per element, after the walk.
+template <bool CAT = false, bool MASK = false, bool MULTI = false>
+__global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(std::conditional_t<MULTI, LossArgsBM, LossArgsB> a) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
     extern __shared__ __attribute__((aligned(16))) float ls[];      // [R][Ap] dmu | [R][Ap] dlogstd | [R][4] pi terms | [R][2] vf terms
     float* dmu_s = ls; float* dls_s = ls + BL_ROWS * a.Ap; float* pt = dls_s + BL_ROWS * a.Ap; float* vt = pt + 4 * BL_ROWS;
     const int tid = threadIdx.x, r = tid >> 6, lane = tid & 63;
@@ -929,7 +989,9 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
         }
     }
     int cact = -1;                                  // CAT: the row's category index
-    if constexpr (CAT) { if (live) cact = (int)a.actions[row]; }
+    [[maybe_unused]] int kact = 0;                               // MULTI: lane k < K holds component k's index within the component
+    if constexpr (MULTI) { if (live && lane < a.comp.K) kact = (int)a.actions[(size_t)row * a.comp.K + lane]; }
+    else if constexpr (CAT) { if (live) cact = (int)a.actions[row]; }
     float vp[GB_HEAD_SPLIT];
 #pragma unroll
     for (int k = 0; k < GB_HEAD_SPLIT; ++k) vp[k] = (lane == 0 && live && k < a.hsplit) ? a.head[1][(size_t)k * a.hstride + (size_t)row * a.ldh] : 0.f;
@@ -941,7 +1003,40 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
     float mu[BL_EPT], z[BL_EPT], sigma[BL_EPT];       // CAT: mu = a0 = l - m, z = exp(a0), sigma unused
     float ssq = 0.f, slog = 0.f, sent = 0.f;
     float cz = 1.f, clz = 0.f, cnlp = 0.f;          // CAT: normaliser, its log, neglogp
-    if constexpr (CAT) {
+    [[maybe_unused]] float ez[BL_EPT], elz[BL_EPT], eh[BL_EPT];      // MULTI: normaliser, its log and entropy of the element's own component ...
+    [[maybe_unused]] int eact[BL_EPT];                               // ... and that component's action column
+    if constexpr (MULTI) {
+        float lg[BL_EPT];
+#pragma unroll
+        for (int e = 0; e < BL_EPT; ++e) {
+            float m = hp[e][0];
+#pragma unroll
+            for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < a.hsplit) m += hp[e][k];   // the partial products in range order (head_sum)
+            lg[e] = live ? m : 0.f;
+            mu[e] = 0.f; z[e] = 0.f; ez[e] = 1.f; elz[e] = 0.f; eh[e] = 0.f; eact[e] = -1;
+        }
+        for (int k = 0; k < a.comp.K; ++k) {
+            const int o = a.comp.off[k], ce = a.comp.off[k + 1];
+            const int act = live ? o + __shfl(kact, k) : -1;
+            bool in[BL_EPT], okk[BL_EPT];
+#pragma unroll
+            for (int e = 0; e < BL_EPT; ++e) { const int j = lane + 64 * e; in[e] = j >= o && j < ce; okk[e] = ok[e] && in[e]; }
+            int il;
+            float a0[BL_EPT], ex[BL_EPT], zk;
+            cat_row_norm<MASK>(lg, okk, lane, ce, il, a0, ex, zk, o);
+            const float lz = logf(zk);
+            const float la = cat_row_pick(a0, okk, lane, act);
+            float ent = 0.f;
+#pragma unroll
+            for (int e = 0; e < BL_EPT; ++e) if (okk[e]) ent += cat_entropy_term(ex[e], zk, lz, a0[e]);
+            ent = wave_sum_all(ent);
+            const float nk = lz - la;
+            cnlp = k == 0 ? nk : cnlp + nk;
+            sent = k == 0 ? ent : sent + ent;
+#pragma unroll
+            for (int e = 0; e < BL_EPT; ++e) if (in[e]) { mu[e] = a0[e]; z[e] = ex[e]; ez[e] = zk; elz[e] = lz; eh[e] = ent; eact[e] = act; }
+        }
+    } else if constexpr (CAT) {
         float lg[BL_EPT];
 #pragma unroll
         for (int e = 0; e < BL_EPT; ++e) {
@@ -985,7 +1080,10 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsB a) {
         const int j = lane + 64 * e;
         if (j < a.Ap) {
             float dmu = 0.f, dl = 0.f;
-            if constexpr (CAT) {
+            if constexpr (MULTI) {
+                // cat_grad_elem with the entropy H_k of j's own component (dl stays 0; forbidden and padding columns: +0)
+                if (live && ok[e]) dmu = cat_grad_elem(d_nlp, z[e], ez[e], mu[e], elz[e], eh[e], j, eact[e], a.ent_coef, g);
+            } else if constexpr (CAT) {
                 // cat_grad_elem with the row's entropy (dl stays 0: no logstd; forbidden and padding columns: +0)
                 if (live && ok[e]) dmu = cat_grad_elem(d_nlp, z[e], cz, mu[e], clz, sent, j, cact, a.ent_coef, g);
             } else if (j < a.A && live) gauss_grad_elem(d_nlp, z[e], sigma[e], a.ent_coef, g, dmu, dl);

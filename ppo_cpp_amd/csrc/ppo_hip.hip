@@ -68,7 +68,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK,
                      KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK,
                      KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK,
-                     KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK, KV_COUNT };
+                     KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
+                     KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK, KV_COUNT };
 static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
@@ -92,7 +93,9 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "train8_kernel<mcat>", "train8_kernel<mcat,mask>",
                                        // a narrow categorical / multi-categorical handle with ppo_set_host_step_fused on, <= 32 environments behind a host Env: one per act
                                        // launch, counted INSTEAD of the act launches of "narrow_step_kernel<cat|mcat[,mask]>" (a bookkeeping-only launch is not counted)
-                                       "narrow_host_step<cat>", "narrow_host_step<cat,mask>", "narrow_host_step<mcat>", "narrow_host_step<mcat,mask>"};
+                                       "narrow_host_step<cat>", "narrow_host_step<cat,mask>", "narrow_host_step<mcat>", "narrow_host_step<mcat,mask>",
+                                       // a multi-categorical PPO_BF16 handle (ppo_create_multi_ex with PPO_ACT_BF16_MULTI_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence"
+                                       "bf16_step_sequence<mcat>", "bf16_step_sequence<mcat,mask>", "bf16_train_sequence<mcat>", "bf16_train_sequence<mcat,mask>"};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -122,6 +125,7 @@ struct ppo_handle {
     int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
+    bool bf16_multi_head = false;     // created with PPO_ACT_BF16_MULTI_HEAD as a multi-categorical PPO_BF16 handle (ppo_create_multi_ex): bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>
     bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical or multi-categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
@@ -982,7 +986,12 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     sa.mask = a.mask;
     if (n.A > 128) return fail(h, "bf16 path: more than 128 actions");
     const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
-    if (a.mask) hipLaunchKernelGGL((bf16_sample_kernel<true, true>), grid, blk, 0, h->stream, sa);
+    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {         // the component table rides behind the arguments, as in launch_step_t
+        SampleArgsBM sm;
+        static_cast<SampleArgsB&>(sm) = sa; sm.comp = h->comp;
+        if (a.mask) hipLaunchKernelGGL((bf16_sample_kernel<true, true, true>), grid, blk, 0, h->stream, sm);
+        else hipLaunchKernelGGL((bf16_sample_kernel<true, false, true>), grid, blk, 0, h->stream, sm);
+    } else if (a.mask) hipLaunchKernelGGL((bf16_sample_kernel<true, true>), grid, blk, 0, h->stream, sa);
     else if (h->dist == PPO_ACT_CATEGORICAL) hipLaunchKernelGGL((bf16_sample_kernel<true, false>), grid, blk, 0, h->stream, sa);
     else hipLaunchKernelGGL((bf16_sample_kernel<false, false>), grid, blk, 0, h->stream, sa);
     HIP_OK(h, hipGetLastError());
@@ -1014,7 +1023,12 @@ int bf16_train_fwd_bwd(ppo_handle* h, const TrainArgs& ta, int Rp, bool links_on
     if (n.A > 64 * BL_EPT) return fail(h, "bf16 path: more than %d actions", 64 * BL_EPT);
     const dim3 lgrid(Rp / BL_ROWS), lblk(64 * BL_ROWS);
     const size_t llds = (size_t)(2 * BL_ROWS * n.Ap + 6 * BL_ROWS) * sizeof(float);
-    if (ta.mask) hipLaunchKernelGGL((bf16_loss_kernel<true, true>), lgrid, lblk, llds, h->stream, la);
+    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {
+        LossArgsBM lm;
+        static_cast<LossArgsB&>(lm) = la; lm.comp = h->comp;
+        if (ta.mask) hipLaunchKernelGGL((bf16_loss_kernel<true, true, true>), lgrid, lblk, llds, h->stream, lm);
+        else hipLaunchKernelGGL((bf16_loss_kernel<true, false, true>), lgrid, lblk, llds, h->stream, lm);
+    } else if (ta.mask) hipLaunchKernelGGL((bf16_loss_kernel<true, true>), lgrid, lblk, llds, h->stream, la);
     else if (h->dist == PPO_ACT_CATEGORICAL) hipLaunchKernelGGL((bf16_loss_kernel<true, false>), lgrid, lblk, llds, h->stream, la);
     else hipLaunchKernelGGL((bf16_loss_kernel<false, false>), lgrid, lblk, llds, h->stream, la);
     HIP_OK(h, hipGetLastError());
@@ -1148,10 +1162,13 @@ void launch_narrow_step_multi(ppo_handle* h, const StepArgs& a) {
 #undef X
 }
 int launch_step(ppo_handle* h, const StepArgs& a) {
-    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (never bf16; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
+    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (bf16 only when created with PPO_ACT_BF16_MULTI_HEAD; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
     const bool cat = h->dist == PPO_ACT_CATEGORICAL;
     if (a.mask && !cat && !multi) return fail(h, "policy step: an action mask needs a categorical handle");
-    if (h->bf.on) { ++h->kv[a.mask ? KV_BF16_STEP_CAT_MASK : cat ? KV_BF16_STEP_CAT : KV_BF16_STEP]; return launch_step_bf16(h, a); }
+    if (h->bf.on) {
+        ++h->kv[multi ? (a.mask ? KV_BF16_STEP_MCAT_MASK : KV_BF16_STEP_MCAT) : a.mask ? KV_BF16_STEP_CAT_MASK : cat ? KV_BF16_STEP_CAT : KV_BF16_STEP];
+        return launch_step_bf16(h, a);
+    }
     ProfScope ps(h, PK_STEP);
     if (nw_mcat(h)) {
         ++h->kv[a.mask ? KV_NARROW_STEP_MCAT_MASK : KV_NARROW_STEP_MCAT];
@@ -1466,8 +1483,9 @@ static int bf16_reduce_adam(ppo_handle* h, const ReduceArgs& ra, int n_old, floa
 
 static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool bucketed, AdamParts& parts) {
     const int Rp = ru(ta.n, GB_PAD);
-    if (ta.mask && h->dist != PPO_ACT_CATEGORICAL) return fail(h, "train step: an action mask needs a categorical handle");
-    ++h->kv[ta.mask ? KV_BF16_TRAIN_CAT_MASK : h->dist == PPO_ACT_CATEGORICAL ? KV_BF16_TRAIN_CAT : KV_BF16_TRAIN];
+    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (PPO_ACT_BF16_MULTI_HEAD, ppo_create_multi_ex)
+    if (ta.mask && h->dist != PPO_ACT_CATEGORICAL && !multi) return fail(h, "train step: an action mask needs a categorical handle");
+    ++h->kv[multi ? (ta.mask ? KV_BF16_TRAIN_MCAT_MASK : KV_BF16_TRAIN_MCAT) : ta.mask ? KV_BF16_TRAIN_CAT_MASK : h->dist == PPO_ACT_CATEGORICAL ? KV_BF16_TRAIN_CAT : KV_BF16_TRAIN];
     h->bf.lazy.enqueued.on = false;
     if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
     { ProfScope ps(h, PK_TRAIN_FB); if (bf16_train_fwd_bwd(h, ta, Rp)) return -1; }
@@ -1775,7 +1793,9 @@ int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) 
 int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out) { return ppo_create_multi_ex(cfg, nvec, n_components, 0, out); }
 
 // K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns; flags: PPO_ACT_SHAPE_KERNELS (the narrow family on a
-// qualifying shape), PPO_ACT_PAIR_KERNELS (the [256,256] pair on a qualifying shape), PPO_ACT_BF16_HEAD (accepted, nothing to select: this head has no bf16 kernels)
+// qualifying shape), PPO_ACT_PAIR_KERNELS (the [256,256] pair on a qualifying shape), PPO_ACT_BF16_HEAD (accepted, nothing to select: that flag belongs to ppo_create_ex's
+// categorical head and PPO_BF16 stays refused with it), PPO_ACT_BF16_MULTI_HEAD (with compute_dtype PPO_BF16: the bf16 path with bf16_sample_kernel / bf16_loss_kernel
+// <mcat[,mask]>, sum(nvec) <= 128, the other two flags beside it ignored; with PPO_F32: changes nothing)
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out) {
     if (!cfg || !out) return fail(nullptr, "ppo_create_multi: null argument");
     *out = nullptr;
@@ -1788,12 +1808,14 @@ int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_co
         sum += nvec[k];
     }
     if (sum != cfg->act_dim) return fail(nullptr, "ppo_create_multi: act_dim %d is not the sum of nvec (%lld)", (int)cfg->act_dim, (long long)sum);
-    if (cfg->compute_dtype == PPO_BF16)
+    const int32_t known = PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_MULTI_HEAD;
+    if (cfg->compute_dtype == PPO_BF16 && !(flags & PPO_ACT_BF16_MULTI_HEAD))
         return fail(nullptr, "ppo_create_multi: compute_dtype PPO_BF16 is not supported (the multi-categorical head runs on the PPO_F32 path)");
-    const int32_t known = PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_HEAD;
     if (flags & ~known)
-        return fail(nullptr, "ppo_create_multi_ex: unknown flag bit 0x%x (PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS or PPO_ACT_BF16_HEAD)", (unsigned)(flags & ~known));
-    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & (PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS)), nvec, n_components, out);
+        return fail(nullptr, "ppo_create_multi_ex: unknown flag bit 0x%x (PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS, PPO_ACT_BF16_HEAD or PPO_ACT_BF16_MULTI_HEAD)", (unsigned)(flags & ~known));
+    if (cfg->compute_dtype == PPO_BF16 && sum > 128)
+        return fail(nullptr, "ppo_create_multi_ex: PPO_ACT_BF16_MULTI_HEAD: the multi-categorical head of the PPO_BF16 path holds at most 128 logits (sum of nvec is %lld)", (long long)sum);
+    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & (PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_MULTI_HEAD)), nvec, n_components, out);
 }
 
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {
@@ -1814,6 +1836,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the flags; whatever else is left must be a distribution
     const bool bf16_head = (action_dist & PPO_ACT_BF16_HEAD) != 0;
     const bool pair_kernels = (action_dist & PPO_ACT_PAIR_KERNELS) != 0;
+    const bool bf16_multi_head = nvec && (action_dist & PPO_ACT_BF16_MULTI_HEAD) != 0;      // (ppo_create_multi_ex only: from ppo_create_ex the bit stays in action_dist and is refused below)
+    if (nvec) action_dist &= ~(int32_t)PPO_ACT_BF16_MULTI_HEAD;
     action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS);
     if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
         return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
@@ -1834,6 +1858,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     h->dist = action_dist;
     h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN;          // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
+    h->bf16_multi_head = bf16_multi_head && cfg->compute_dtype == PPO_BF16;   // (PPO_F32: the flag changes nothing)
     h->pair_kernels = pair_kernels && (action_dist == PPO_ACT_CATEGORICAL || action_dist == PPO_ACT_MULTI_CATEGORICAL) && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
     h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : action_dist == PPO_ACT_MULTI_CATEGORICAL ? n_components : cfg->act_dim;
     if (action_dist == PPO_ACT_MULTI_CATEGORICAL) {
@@ -3782,6 +3807,8 @@ struct UidByValue { char b[128]; };
 int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128]) {
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
     if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
+    if (h->bf16_multi_head)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD");
     if (h->shape_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");

@@ -176,7 +176,7 @@ struct ppo_host_args {
     int obs_dim, act_dim;        // SeededEnvMock's shape (0 = 18): 36 / 18 is the hexapod with observed velocities (hexapod_closed_loop_env.hpp:20)
     float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
     int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for; a multi-discrete Env's: PPO2::create_handle), 2 = PPO_ACT_PAIR_KERNELS (a multi-discrete Env's: PPO2::create_handle's extra_flags)
-    int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD)
+    int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD, a multi-discrete Env's with PPO_ACT_BF16_MULTI_HEAD)
     int n_components, nvec[16];  // ppo_host_learn_multi: the components of MultiDiscreteTargetEnv (act_dim is their sum)
     int multi_masked;            // ppo_host_learn_multi: the environments also carry IActionMask
     int host_step_fused;         // ppo_set_host_step_fused(h, 1) on the created handle before PPO2 sees it: the one-launch host-Env step of a narrow discrete handle (discrete_kernels == 1, <= 32 environments); nothing changes anywhere else
@@ -364,7 +364,7 @@ int ppo_host_discrete_checkpoint(const char* prefix, const float* obs, int n, fl
 
 // The learning check of the multi-categorical head (tests/test_multi_discrete.py): n_envs x MultiDiscreteTargetEnv(nvec) -> VecEnv -> EnvNormalize -> PPO2::learn with the
 // library's own sampling and shuffles, through the HBM-resident loop or, with args->reference_loop, the literal one.  The handle comes from PPO2::create_handle (the Env
-// carries IMultiDiscrete: ppo_create_multi_ex, with PPO_ACT_SHAPE_KERNELS when args->discrete_kernels == 1, with PPO_ACT_PAIR_KERNELS when it is 2).  args as for ppo_host_learn_masked plus n_components / nvec / multi_masked (the environments also carry IActionMask: PPO2 masks
+// carries IMultiDiscrete: ppo_create_multi_ex, with PPO_ACT_SHAPE_KERNELS when args->discrete_kernels == 1, with PPO_ACT_PAIR_KERNELS when it is 2, with PPO_ACT_BF16_MULTI_HEAD when args->compute_dtype is PPO_BF16).  args as for ppo_host_learn_masked plus n_components / nvec / multi_masked (the environments also carry IActionMask: PPO2 masks
 // by itself).  reward_curve [n_updates]; *forbidden_received: steps on which an environment was sent a forbidden action; playback_actions [n_playback][K] /
 // playback_legal [n_playback] (may be null / 0): PPO2::eval on the stack for n_playback steps after training (environment 0's row) and whether the environment's own mask
 // allowed every component's action.  count_names / counts / n_counts (all three or none): ppo_kernel_counts of the run's handle, up to 64 entries.
@@ -385,7 +385,9 @@ int ppo_host_learn_multi(const ppo_host_args* a, float* reward_curve, long long*
         std::vector<std::shared_ptr<MultiDiscreteTargetEnv>> kids;
         std::vector<std::shared_ptr<Env>> envs;
         for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MultiDiscreteTargetEnv>(1234u, (uint32_t)i, O, nvec, 100, a->multi_masked != 0)); envs.push_back(kids.back()); }
-        if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : 0) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        // (PPO_BF16: the bf16 path's multi-categorical head is opt-in, as PPO_ACT_BF16_HEAD is for a discrete Env's handle)
+        const int32_t extra_flags = (a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : 0) | (a->compute_dtype == PPO_BF16 ? PPO_ACT_BF16_MULTI_HEAD : 0);
+        if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, extra_flags) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         {

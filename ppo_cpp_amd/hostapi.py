@@ -115,7 +115,8 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
     PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "pair": with PPO_ACT_PAIR_KERNELS (hidden [256, 256]: train8_kernel<cat[,mask]> +
     weight_grad_assemble_kernel), "generic" (the default): without either.
-    compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD.
+    compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD, a multi-discrete Env's (nvec) with
+    PPO_ACT_BF16_MULTI_HEAD (bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>, sum(nvec) <= 128).
     nvec=[n_0, ..]: MultiDiscreteTargetEnv with these components (act_dim is ignored: their sum) and a multi-categorical handle (PPO2::create_handle ->
     ppo_create_multi_ex; discrete_kernels="narrow": with PPO_ACT_SHAPE_KERNELS, the narrow <mcat> kernels where the shape qualifies; "pair": with
     PPO_ACT_PAIR_KERNELS, train8_kernel<mcat[,mask]> + weight_grad_assemble_kernel where hidden is [256, 256] and sum(nvec) <= 64), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)
