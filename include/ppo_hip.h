@@ -301,6 +301,26 @@ int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, c
 int ppo_set_value_clip(ppo_handle* h, int32_t mode, float range);
 /* the handle's current setting; range reads 0 outside PPO_VCLIP_RANGE */
 int ppo_get_value_clip(const ppo_handle* h, int32_t* mode, float* range);
+/* Target-KL early stopping (no reference counterpart; the knob stable-baselines3 and spinning-up call target_kl).  0 = off (the default).  With target_kl > 0:
+ *   limit = 1.5f * target_kl, computed in fp32 on the host (stable-baselines3's factor).  The ESTIMATOR is the project's own approxkl -- losses[3], the graph's
+ *   half mean squared log-ratio 1/2 mean((neglogp - old_neglogp)^2) -- NOT stable-baselines3's k3 estimator mean(exp(r) - 1 - r); the two agree to second order.
+ *   Train step k of a ppo_update computes its losses and gradient as always, with the weights as they stand.  If approxkl_k > limit NOTHING of step k is applied:
+ *   the weights, both Adam slots and the beta powers stay bit for bit as they were, and every later step of that update does nothing.  The comparison is taken on
+ *   the device, inside the launch that applies the step, with the fp32 expression that writes the returned row: a host that compares loss_rows[k][3] against
+ *   1.5f * target_kl reproduces it exactly.  (A NaN approxkl does not exceed the limit: such a step is applied, as it is with the setting off.)
+ *   A stopped update returns loss_rows[0..k] as computed (the triggering row included), quiet NaN in every row behind k, mean_losses = the column means of rows
+ *   0..k only; ppo_get_last_grad and its norm are those of step k.  The next ppo_update starts with the stop condition cleared (also when it replays the captured
+ *   graph; a changed target_kl is honoured by a replay, switching between off and on re-captures).  ppo_train_step[_masked] follows the same rule for its single
+ *   step: the losses are returned, the step is not applied when its approxkl exceeds the limit.
+ *   Form selection: with the setting on, ppo_update takes the launch sequences that end every train step in adam_kernel -- what PPO_HIP_NO_LAZY_ADAM=1 +
+ *   PPO_HIP_NO_NARROW_EPOCH=1 select (no narrow_epoch_kernel in ppo_kernel_counts); the narrow reference shape gives up its deferred Adam and resident epochs for it.
+ *   With the setting off a handle enqueues exactly what it always did.
+ *   Refused, with an error that leaves the handle usable and the previous setting in place: a negative, NaN or infinite value; target_kl > 0 on a PPO_BF16
+ *   handle; target_kl > 0 on a handle with a communicator (and ppo_dist_init on a handle with the setting on). */
+int ppo_set_target_kl(ppo_handle* h, float target_kl);
+int ppo_get_target_kl(const ppo_handle* h, float* target_kl);
+/* Adam steps applied / train steps enqueued by the last ppo_update or ppo_train_step[_masked] (applied == total with the setting off) */
+int ppo_update_applied(ppo_handle* h, int32_t* applied, int32_t* total);
 /* gradient of the last train step (of ppo_train_step, or the last one of ppo_update) BEFORE clipping (debug/parity), dense flat order.
  * PPO_BF16 handles on one GPU do not keep it: it is rebuilt here from the step's partial sums (same bits), which stay valid until the next train step. */
 int ppo_get_last_grad(ppo_handle* h, float* dst, int64_t count, float* global_norm);

@@ -273,6 +273,23 @@ class PPOHip:
         self._ck(self.lib.ppo_get_value_clip(self.h, C.byref(m), C.byref(r)))
         return {v: k for k, v in VALUE_CLIP_MODES.items()}[m.value], r.value
 
+    def set_target_kl(self, target_kl):
+        """Target-KL early stopping from the next train_step / update on (include/ppo_hip.h, ppo_set_target_kl): a train step whose approxkl (losses[3], the
+        project's half mean squared log-ratio) exceeds 1.5 * target_kl is not applied and ends the update.  0 = off (the default); a negative, NaN or infinite
+        value, a PPO_BF16 handle and a handle with a communicator are errors that leave the previous setting in place."""
+        self._ck(self.lib.ppo_set_target_kl(self.h, C.c_float(target_kl)))
+
+    def target_kl(self):
+        x = C.c_float()
+        self._ck(self.lib.ppo_get_target_kl(self.h, C.byref(x)))
+        return x.value
+
+    def update_applied(self):
+        """(Adam steps applied, train steps enqueued) of the last update() or train_step(); with target_kl off both are the number of train steps"""
+        a, t = C.c_int32(), C.c_int32()
+        self._ck(self.lib.ppo_update_applied(self.h, C.byref(a), C.byref(t)))
+        return a.value, t.value
+
     def last_grad(self):
         g = np.empty(self.P, np.float32); norm = C.c_float()
         self._ck(self.lib.ppo_get_last_grad(self.h, _fp(g), C.c_int64(self.P), C.byref(norm)))

@@ -453,6 +453,16 @@ __global__ __launch_bounds__(DW2_THREADS) void weight_grad_assemble_kernel(Dw2Ar
     dw2_body<KP0, AP>(a, lds, (int)blockIdx.x);
 }
 
+// ... launched while target-KL early stopping is on (update_stopped, ppo_kernels.hpp): a kernel of its own, the one above stays what it was.  The exit is grid-uniform,
+// so `counters` are never left half-counted.
+template <int KP0, int AP>
+__global__ __launch_bounds__(DW2_THREADS) void weight_grad_assemble_stop_kernel(Dw2Args a, const unsigned* stop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(Dw2Args) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    dw2_body<KP0, AP>(a, lds, (int)blockIdx.x);
+}
+
 template <int KP0, int AP>
 __global__ __launch_bounds__(DW2_THREADS) void weight_grad_assemble_peer_kernel(Dw2Args a, PeerDev p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];

@@ -145,6 +145,9 @@ struct ppo_handle {
     int32_t vclip_mode = PPO_VCLIP_POLICY;   // ppo_set_value_clip; set_hyper turns it into hyper[2], hyper[3]
     float vclip_range = 0.f;
     float* norm_out = nullptr;        // [1]
+    // target-KL early stopping (ppo_set_target_kl; 0 = off): the device stop block {flag, Adam steps applied} that adam_kernel<.., ADAM_GATE> keeps and every train-step
+    // kernel reads at entry; hyper[4] carries the limit.  last_*: what ppo_update_applied reports
+    float target_kl = 0.f; unsigned* stop = nullptr; uint32_t stop_back[2] = {0, 0}; int32_t last_applied = 0, last_total = 0;
     GradSrc* grad_src = nullptr;
     int n_tiled = 0; AdamArgs::Tiled tiled[ADAM_MAX_TILED]{};   // matrices whose transposed copy adam_kernel writes tile by tile
     // train workspaces (sized for ws_rows minibatch rows)
@@ -202,13 +205,13 @@ struct ppo_handle {
     int upd_cap_rows = 0, upd_cap_steps = 0;
     hipGraphExec_t upd_graph = nullptr;
     hipGraph_t upd_graph_tmpl = nullptr;      // the captured graph the executable one was instantiated from: kept until the executable one goes (drop_graph)
-    int g_epochs = 0, g_nmb = 0, g_E = 0, g_T = 0, g_explicit = -1, g_world = 0;
+    int g_epochs = 0, g_nmb = 0, g_E = 0, g_T = 0, g_explicit = -1, g_world = 0, g_gate = 0;
     bool use_graph = true;
     uint32_t rng_calls = 0;
     uint32_t rng_seed = 0x5EEDu;      // ppo_seed
     int norm_obs_flag = 1, norm_rew_flag = 1;   // EnvNormalize's norm_obs / norm_reward (env_normalize.hpp:75,95)
     float* env_in = nullptr;          // [E*O | E | E] raw obs | raw reward | dones of the current env step, one block: one H2D per env step
-    float* hyper_host = nullptr;      // pinned {lr, cliprange, vclip_range, vclip_off}: the source of set_hyper's asynchronous copy
+    float* hyper_host = nullptr;      // pinned {lr, cliprange, vclip_range, vclip_off, target-KL limit}: the source of set_hyper's asynchronous copy
     float* pin_in = nullptr;          // pinned host mirror of env_in (hipHostMalloc, owned by the handle)
     // ONE environment behind a host Env, resident three-wave kernel: the transition ALSO goes straight into device memory through the BAR (posted writes) with its own
     // sequence word, so the kernel polls and reads local memory instead of host memory over PCIe (large-BAR devices; PPO_HIP_NO_VRAM_INBOX=1 keeps the pinned block only)
@@ -1276,6 +1279,10 @@ int pick_split(ppo_handle* h, int n) {
 // has to be resident at once; the bf16 path's 20 k workgroups are not.
 bool adam_can_meet(const ppo_handle* h) { return h->comm && h->adam_meet && (h->n_blocks + 3) / 4 <= ADAM_MEET_MAX_GRID && !h->bf.on; }
 
+// target-KL early stopping is on: the step's launches are the *_stop_kernel forms, which read the handle's stop flag at entry, and the step ends in adam_kernel<.., ADAM_GATE>;
+// off, a handle launches the kernels it always launched
+static bool kl_gate(const ppo_handle* h) { return h->target_kl > 0.f; }
+
 // clip + Adam on the assembled gradient (after the optional all-reduce)
 // meet (data parallel, see adam_kernel): 2 = the ranks' tiles sit in the peer slots (weight_grad_assemble_kernel<.., PEER> pushed them).  (1 = `grad` is
 // reduced but its sums of squares are not formed -- measured on the RCCL path against the grad_sumsq_kernel launch it would replace: 43.1 vs 42.2 us per
@@ -1304,6 +1311,13 @@ int enqueue_adam(ppo_handle* h, float* loss_row, int n_sumsq = 0, const float* p
         HIP_OK(h, hipGetLastError());
         return 0;
     }
+    if (kl_gate(h)) {                                       // (never with a communicator or on a bf16 handle: ppo_set_target_kl / ppo_dist_init refuse)
+        aa.meet_words = h->stop;                            // (the gate form's stop block travels in the meeting's pointer: AdamArgs)
+        if (h->adam_fast) hipLaunchKernelGGL((adam_kernel<true, ADAM_GATE>), grid, dim3(256), 0, h->stream, aa);
+        else hipLaunchKernelGGL((adam_kernel<false, ADAM_GATE>), grid, dim3(256), 0, h->stream, aa);
+        HIP_OK(h, hipGetLastError());
+        return 0;
+    }
     // (the handle whose train kernels may apply Adam in their prologue uses the same 1-ulp quotient in its launches: bit-identical forms)
     if (h->adam_fast) hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(256), 0, h->stream, aa);
     else hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, h->stream, aa);
@@ -1313,16 +1327,20 @@ int enqueue_adam(ppo_handle* h, float* loss_row, int n_sumsq = 0, const float* p
 
 // the [256,256] pair's launches (PAIR_DISPATCH picks the instantiation)
 static void launch_train8(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+    const unsigned* stop = h->stop;
 #define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL; \
-                        hipLaunchKernelGGL((train8_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+                        if (kl_gate(h)) hipLaunchKernelGGL((train8_stop_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
+                        else hipLaunchKernelGGL((train8_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
 }
 // its categorical forms (a handle created with PPO_ACT_PAIR_KERNELS): the same carve, the same dynamic LDS
 template <bool MASK>
 static void launch_train8_cat(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+    const unsigned* stop = h->stop;
 #define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL; \
-                        hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+                        if (kl_gate(h)) hipLaunchKernelGGL((train8_stop_kernel<KP0, AP, true, MASK>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
+                        else hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
 }
@@ -1332,15 +1350,19 @@ static void launch_train8_multi(ppo_handle* h, dim3 grid, const TrainArgs& ta0) 
     TrainArgsM ta;
     static_cast<TrainArgs&>(ta) = ta0;
     ta.comp = h->comp;
+    const unsigned* stop = h->stop;
 #define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL_M; \
-                        hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK, true>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+                        if (kl_gate(h)) hipLaunchKernelGGL((train8_stop_kernel<KP0, AP, true, MASK, true>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
+                        else hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK, true>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
 }
 // peer: the tiles' finishers push to the peers' regions themselves
 static void launch_dw2(ppo_handle* h, const Dw2Args& da, bool peer) {
+    const unsigned* stop = h->stop;
 #define X(KP0, AP) do { const size_t lds = sizeof(float) * Dw2L<KP0, AP>::LDS_FLOATS; \
-                        if (peer) hipLaunchKernelGGL((weight_grad_assemble_peer_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da, h->peer.dev); \
+                        if (kl_gate(h) && !peer) hipLaunchKernelGGL((weight_grad_assemble_stop_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da, stop); \
+                        else if (peer) hipLaunchKernelGGL((weight_grad_assemble_peer_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da, h->peer.dev); \
                         else hipLaunchKernelGGL((weight_grad_assemble_kernel<KP0, AP>), dim3(DW2_GRID), dim3(DW2_THREADS), lds, h->stream, da); } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
@@ -1351,10 +1373,15 @@ static bool set_lds_pair(const ppo_handle* h) {
     auto set = [&](const void* f, size_t floats) { ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * floats)) == hipSuccess; };
 #define X(KP0, AP) do { set((const void*)weight_grad_assemble_peer_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
                         set((const void*)weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); \
+                        set((const void*)weight_grad_assemble_stop_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_stop_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
                         if (h->dist == PPO_ACT_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false>, T8L<KP0, AP>::TOTAL); \
-                                                              set((const void*)train8_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); } \
+                                                              set((const void*)train8_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); \
+                                                              set((const void*)train8_stop_kernel<KP0, AP, true, false>, T8L<KP0, AP>::TOTAL); \
+                                                              set((const void*)train8_stop_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); } \
                         if (h->dist == PPO_ACT_MULTI_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false, true>, T8L<KP0, AP>::TOTAL_M); \
-                                                                    set((const void*)train8_kernel<KP0, AP, true, true, true>, T8L<KP0, AP>::TOTAL_M); } } while (0)
+                                                                    set((const void*)train8_kernel<KP0, AP, true, true, true>, T8L<KP0, AP>::TOTAL_M); \
+                                                                    set((const void*)train8_stop_kernel<KP0, AP, true, false, true>, T8L<KP0, AP>::TOTAL_M); \
+                                                                    set((const void*)train8_stop_kernel<KP0, AP, true, true, true>, T8L<KP0, AP>::TOTAL_M); } } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
     return ok;
@@ -1507,8 +1534,11 @@ template <bool LAZY, bool EXACT, bool CAT, bool MASK>
 static void launch_narrow_train(ppo_handle* h, int groups, const NwTrainArgs& na, const NwLazyArgs& z) {
     const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
 #define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, LAZY, EXACT, CAT, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, z)
-    if constexpr (LAZY) { if (h->net.Kp0 == 32) X(32, 64, 32, 2); else X(64, 64, 32, 2); }
+#define XS(a, b, c, d) hipLaunchKernelGGL((narrow_train_stop_kernel<a, b, c, d, CAT, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, (const unsigned*)h->stop)
+    if constexpr (LAZY) { if (h->net.Kp0 == 32) X(32, 64, 32, 2); else X(64, 64, 32, 2); }      // (never with target-KL early stopping on: enqueue_update does not defer then)
+    else if (kl_gate(h)) NW_DISPATCH(h, XS);
     else NW_DISPATCH(h, X);
+#undef XS
 #undef X
 }
 
@@ -1520,7 +1550,10 @@ static void launch_narrow_train_multi(ppo_handle* h, int groups, const NwTrainAr
     static_cast<NwTrainArgs&>(na) = na0;
     na.comp = h->comp;
 #define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true, MASK, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na)
-    NW_DISPATCH(h, X);
+#define XS(a, b, c, d) hipLaunchKernelGGL((narrow_train_stop_multi_kernel<a, b, c, d, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, (const unsigned*)h->stop)
+    if (kl_gate(h)) NW_DISPATCH(h, XS);
+    else NW_DISPATCH(h, X);
+#undef XS
 #undef X
 }
 
@@ -1553,7 +1586,8 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
     const int n_chunks = h->P_pad / 64;
     ProfScope ps(h, PK_REDUCE);
     NwReduceArgs ra{h->grad_src, n_chunks, h->nw_partials, groups, h->nw_stride, h->P_pad, h->grad, h->sumsq, (float)ta.n, h->beta_pow};
-    hipLaunchKernelGGL(narrow_reduce_kernel, dim3(n_chunks + 1), dim3(256), 0, h->stream, ra);
+    if (kl_gate(h)) hipLaunchKernelGGL(narrow_reduce_stop_kernel, dim3(n_chunks + 1), dim3(256), 0, h->stream, ra, (const unsigned*)h->stop);
+    else hipLaunchKernelGGL(narrow_reduce_kernel, dim3(n_chunks + 1), dim3(256), 0, h->stream, ra);
     HIP_OK(h, hipGetLastError());
     parts = AdamParts{n_chunks, nullptr};
     return 0;
@@ -1645,7 +1679,10 @@ static int train_generic(ppo_handle* h, TrainArgs ta) {
     ProfScope ps(h, PK_REDUCE);
     ReduceArgs ra = reduce_args(h, ta, n_pad / ROWS_PER_BLOCK);
     ra.nsplit = split;
-    hipLaunchKernelGGL(grad_reduce_kernel, dim3(h->n_blocks + 1), dim3(256), 0, h->stream, ra);
+    // (target-KL early stopping on: the assembly leaves h->grad and the loss tail those of the step that stopped the update; the generic family's train and
+    // weight-gradient kernels have no stop form and compute on)
+    if (kl_gate(h)) hipLaunchKernelGGL(grad_reduce_stop_kernel, dim3(h->n_blocks + 1), dim3(256), 0, h->stream, ra, (const unsigned*)h->stop);
+    else hipLaunchKernelGGL(grad_reduce_kernel, dim3(h->n_blocks + 1), dim3(256), 0, h->stream, ra);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1723,7 +1760,9 @@ int set_hyper(ppo_handle* h, float lr, float cr) {
     h->hyper_host[0] = lr; h->hyper_host[1] = cr;
     h->hyper_host[2] = h->vclip_mode == PPO_VCLIP_RANGE ? h->vclip_range : h->vclip_mode == PPO_VCLIP_OFF ? 0.f : cr;
     h->hyper_host[3] = h->vclip_mode == PPO_VCLIP_OFF ? INFINITY : 0.f;          // vf_loss_row: subtracted from the clipped square
-    HIP_OK(h, hipMemcpyAsync(h->hyper, h->hyper_host, 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    // the target-KL limit, 1.5 x target_kl in fp32 (stable-baselines3's factor): a fifth float, copied only while the setting is on -- off, the copy is the one it always was
+    h->hyper_host[4] = 1.5f * h->target_kl;
+    HIP_OK(h, hipMemcpyAsync(h->hyper, h->hyper_host, (kl_gate(h) ? 5 : 4) * sizeof(float), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
@@ -1921,8 +1960,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (!attr_ok) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); return bail(0); }
     const size_t P = (size_t)h->P_pad;
     if (dev_alloc(h, &h->par, (size_t)2 * h->net.par_total) || dev_alloc(h, &h->thetaT, (size_t)h->PT) || dev_alloc(h, &h->theta, P) || dev_alloc(h, &h->adam_m, P) || dev_alloc(h, &h->adam_v, P) || dev_alloc(h, &h->grad, P + 256) ||
-        dev_alloc(h, &h->sumsq, (size_t)4 * h->n_blocks) || dev_alloc(h, &h->sumsq2, (size_t)(h->n_blocks + 1023) / 1024) || dev_alloc(h, &h->beta_pow, 4) || dev_alloc(h, &h->hyper, 4) ||
-        dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8))
+        dev_alloc(h, &h->sumsq, (size_t)4 * h->n_blocks) || dev_alloc(h, &h->sumsq2, (size_t)(h->n_blocks + 1023) / 1024) || dev_alloc(h, &h->beta_pow, 4) || dev_alloc(h, &h->hyper, 8) ||
+        dev_alloc(h, &h->stop, 4) || dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8))
         return bail(0);
     build_narrow_layout(h);
     if (h->dist == PPO_ACT_MULTI_CATEGORICAL) h->shape_kernels = h->narrow;       // from here on: the flag took effect (a shape that does not qualify runs the generic <mcat> kernels, data parallel included)
@@ -1967,6 +2006,12 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (h->narrow) {
         attr_ok = true;
         auto big_lds = [&](const void* f) { attr_ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
+        // the train kernels launched while target-KL early stopping is on (ppo_set_target_kl): every head this handle can have
+#define XS(a, b, c, d) do { if (nw_mcat(h)) { big_lds((const void*)narrow_train_stop_multi_kernel<a, b, c, d, false>); big_lds((const void*)narrow_train_stop_multi_kernel<a, b, c, d, true>); } \
+                            else if (nw_cat(h)) { big_lds((const void*)narrow_train_stop_kernel<a, b, c, d, true, false>); big_lds((const void*)narrow_train_stop_kernel<a, b, c, d, true, true>); } \
+                            else big_lds((const void*)narrow_train_stop_kernel<a, b, c, d, false, false>); } while (0)
+        XS(0, 0, 0, 0); XS(32, 64, 32, 2); XS(64, 64, 32, 2);
+#undef XS
 #define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d>); big_lds((const void*)narrow_step_kernel<a, b, c, d>); big_lds((const void*)narrow_collect_kernel<a, b, c, d>); \
                            big_lds((const void*)narrow_rollout_kernel<a, b, c, d, false>); big_lds((const void*)narrow_rollout_kernel<a, b, c, d, true>); \
                            big_lds((const void*)narrow_rollout_coop_kernel<a, b, c, d>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d>); } while (0)
@@ -2049,7 +2094,7 @@ void ppo_destroy(ppo_handle* h) {
                     h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->stats_xch, h->stats_part, h->stats_counter, h->adv_xch, h->ro_obs, h->ro_act,
                     h->ro_val, h->ro_nlp, h->ro_done, h->ro_rew, h->ro_ret, h->env_in /* raw_obs, raw_rew, cur_done live inside */, h->raw_done,
                     h->last_val, h->ro_noise, h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp, h->d_perms, h->d_inv, h->d_gidx, h->d_advstats, h->d_keys, h->d_loss_rows, h->d_loss_mean,
-                    h->ro_mask, h->mb_mask, h->st_mask};
+                    h->ro_mask, h->mb_mask, h->st_mask, h->stop};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int t = 0; t < 2; ++t) for (int l = 0; l < PPO_MAX_LAYERS; ++l) { if (h->hg[t][l]) (void)hipFree(h->hg[t][l]); if (h->dyg[t][l]) (void)hipFree(h->dyg[t][l]); }
     for (int i = 0; i < 6; ++i) if (h->st_vec[i]) (void)hipFree(h->st_vec[i]);
@@ -2313,6 +2358,31 @@ int ppo_get_value_clip(const ppo_handle* h, int32_t* mode, float* range) {
     return 0;
 }
 
+// Target-KL early stopping.  Host state: the next ppo_train_step / ppo_update writes the limit into hyper[4] ahead of its launches or graph replay (a replayed graph
+// follows a changed value); on / off selects other launches and is part of the captured graph's key (run_update).
+int ppo_set_target_kl(ppo_handle* h, float target_kl) {
+    if (!h) return fail(nullptr, "ppo_set_target_kl: null handle");
+    if (!(std::isfinite(target_kl) && target_kl >= 0.f)) return fail(h, "ppo_set_target_kl: needs a finite value >= 0 (0 = off; got %g)", (double)target_kl);
+    if (target_kl > 0.f && h->bf.on)
+        return fail(h, "ppo_set_target_kl: not supported on a PPO_BF16 handle (its train step applies Adam in bf16_reduce_adam_kernel, which has no target-KL gate)");
+    if (target_kl > 0.f && h->comm)
+        return fail(h, "ppo_set_target_kl: not supported on a data-parallel handle (the ranks' Adam forms have no target-KL gate; set it on a handle without a communicator)");
+    h->target_kl = target_kl;
+    return 0;
+}
+
+int ppo_get_target_kl(const ppo_handle* h, float* target_kl) {
+    if (!h || !target_kl) return fail(nullptr, "ppo_get_target_kl: null argument");
+    *target_kl = h->target_kl;
+    return 0;
+}
+
+int ppo_update_applied(ppo_handle* h, int32_t* applied, int32_t* total) {
+    if (!h || !applied || !total) return fail(h, "ppo_update_applied: null argument");
+    *applied = h->last_applied; *total = h->last_total;
+    return 0;
+}
+
 int ppo_train_step(ppo_handle* h, float lr, float cliprange, const float* obs, const float* actions, const float* advs,
                    const float* returns, const float* old_neglogp, const float* old_values, int32_t n, float losses[5]) {
     return ppo_train_step_masked(h, lr, cliprange, obs, actions, nullptr, advs, returns, old_neglogp, old_values, n, losses);
@@ -2346,10 +2416,13 @@ int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float*
     ta.old_values = h->st_vec[5]; ta.adv_stats = nullptr; ta.n = n; ta.mask = mask ? h->st_mask : nullptr;
     ta.inv_n = 1.0f / (float)((int64_t)n * h->world);
     if (h->dw2 && zero_words(h, h->dw2_counters, DW2_TILES)) return -1;
+    if (kl_gate(h) && zero_words(h, h->stop, 2)) return -1;
     if (enqueue_train(h, ta, h->st_loss)) return -1;
     h->bf.lazy.ran = h->bf.lazy.enqueued;
     HIP_OK(h, hipMemcpyAsync(losses, h->st_loss, 5 * fb, hipMemcpyDeviceToHost, h->stream));
+    if (kl_gate(h)) HIP_OK(h, hipMemcpyAsync(h->stop_back, h->stop, sizeof h->stop_back, hipMemcpyDeviceToHost, h->stream));
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    h->last_total = 1; h->last_applied = kl_gate(h) ? (int32_t)h->stop_back[1] : 1;
     prof_collect(h);
     return adam_meet_check(h) || bf16_chain_check(h) ? -1 : 0;
 }
@@ -3591,10 +3664,14 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
     // the per-tile arrival counters of weight_grad_assemble_kernel are reset by their last arriver; an update that was cut short
     // (a failed launch) must not leave them half-counted for the next one: zeroed here, a memset node of the replayed graph
     if (h->dw2 && zero_words(h, h->dw2_counters, DW2_TILES)) return -1;
+    // target-KL early stopping: every update starts with the stop block cleared (a kernel node, so a replay clears it too), and takes the forms that end in
+    // adam_kernel -- no resident epoch, no deferred Adam (what PPO_HIP_NO_NARROW_EPOCH=1 + PPO_HIP_NO_LAZY_ADAM=1 select)
+    const bool gate = kl_gate(h);
+    if (gate && zero_words(h, h->stop, 2)) return -1;
     h->nw_pending = false; h->nw_cur = 0;                      // outside an update the weights always live in set 0
     // the resident epoch launch: beside the shared terms, the deferred Adam it continues, the switch, and the partial vectors' capacities
     const int egroups = (M + NW_ROWS - 1) / NW_ROWS;
-    const bool resident = narrow_epoch_shape(h, M) && h->nw_lazy && egroups <= h->nw_groups_cap && use_narrow_epoch();
+    const bool resident = narrow_epoch_shape(h, M) && h->nw_lazy && egroups <= h->nw_groups_cap && use_narrow_epoch() && !gate;
     const bool xl = narrow_epoch_xl_shape(h, M) && h->nw_epoch_partials && (size_t)nmb * 2 * egroups * h->nw_stride <= h->nw_epoch_cap;
     for (int ep = 0; ep < epochs; ++ep) {
         if (enqueue_epoch_prepare(h, ep, nmb, explicit_perms)) return -1;
@@ -3609,11 +3686,12 @@ static int enqueue_update(ppo_handle* h, int epochs, int nmb, bool explicit_perm
             ta.old_neglogp = h->mb_nlp + r0; ta.advs = h->mb_adv + r0; ta.adv_stats = nullptr; ta.n = M;
             ta.mask = h->masking ? h->mb_mask + r0 * h->net.A : nullptr;
             ta.inv_n = 1.0f / (float)((int64_t)M * h->world);
-            if (enqueue_train(h, ta, h->d_loss_rows + (size_t)(ep * nmb + k) * 5, /*defer*/ true)) return -1;
+            if (enqueue_train(h, ta, h->d_loss_rows + (size_t)(ep * nmb + k) * 5, /*defer*/ !gate)) return -1;
         }
     }
     if (flush_pending_adam(h)) return -1;
-    hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(320), 0, h->stream, h->d_loss_rows, epochs * nmb, h->d_loss_mean);
+    if (gate) hipLaunchKernelGGL(loss_mean_stop_kernel, dim3(1), dim3(320), 0, h->stream, h->d_loss_rows, h->stop, h->d_loss_mean);
+    else hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(320), 0, h->stream, h->d_loss_rows, epochs * nmb, h->d_loss_mean);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -3714,7 +3792,7 @@ static int run_update(ppo_handle* h, int epochs, int nmb, bool explicit_perms) {
     if (!graph_ok) return enqueue_update(h, epochs, nmb, explicit_perms);
     const int world_key = global_shuffle_on(h) ? -h->world : h->world;
     const bool same = h->upd_graph && h->g_epochs == epochs && h->g_nmb == nmb && h->g_E == h->E && h->g_T == h->T &&
-                      h->g_explicit == (int)explicit_perms && h->g_world == world_key;
+                      h->g_explicit == (int)explicit_perms && h->g_world == world_key && h->g_gate == (int)kl_gate(h);
     if (!same) {
         drop_graph(h);
         HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -3735,7 +3813,7 @@ static int run_update(ppo_handle* h, int epochs, int nmb, bool explicit_perms) {
             h->use_graph = false;
             fprintf(stderr, "libppo_hip: hipGraph capture of the update failed (%s); continuing with eager launches\n", h->err.c_str());
         } else {
-            h->g_epochs = epochs; h->g_nmb = nmb; h->g_E = h->E; h->g_T = h->T; h->g_explicit = (int)explicit_perms; h->g_world = world_key;
+            h->g_epochs = epochs; h->g_nmb = nmb; h->g_E = h->E; h->g_T = h->T; h->g_explicit = (int)explicit_perms; h->g_world = world_key; h->g_gate = (int)kl_gate(h);
         }
     }
     if (!h->upd_graph) return enqueue_update(h, epochs, nmb, explicit_perms);
@@ -3765,7 +3843,9 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
     h->bf.lazy.ran = h->bf.lazy.enqueued;
     if (loss_rows) HIP_OK(h, hipMemcpyAsync(loss_rows, h->d_loss_rows, (size_t)steps * 5 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(h, hipMemcpyAsync(mean_losses, h->d_loss_mean, 5 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (kl_gate(h)) HIP_OK(h, hipMemcpyAsync(h->stop_back, h->stop, sizeof h->stop_back, hipMemcpyDeviceToHost, h->stream));
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    h->last_total = steps; h->last_applied = kl_gate(h) ? (int32_t)h->stop_back[1] : steps;
     prof_collect(h);
     if (adam_meet_check(h) || bf16_chain_check(h) || nw_epoch_check(h)) return -1;
     return peer_check(h);
@@ -3806,6 +3886,7 @@ struct UidByValue { char b[128]; };
 
 int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128]) {
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
+    if (h->target_kl > 0.f) return fail(h, "ppo_dist_init: data parallel is not supported with target-KL early stopping on (ppo_set_target_kl(h, 0) first)");
     if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
     if (h->bf16_multi_head)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD");

@@ -184,6 +184,14 @@ __device__ __forceinline__ void warm_kernargs() {
     asm volatile("" :: "s"(acc));
 }
 
+// Target-KL early stopping (ppo_set_target_kl): the handle's stop block is {flag, Adam steps applied}.  adam_kernel<.., ADAM_GATE> raises the flag in the train step
+// whose approxkl exceeds the limit.  The kernels enqueued behind it while the setting is on are the *_stop_kernel forms -- train8_stop_kernel, weight_grad_assemble_stop_kernel,
+// narrow_train_stop_kernel, grad_reduce_stop_kernel, narrow_reduce_stop_kernel: the same bodies behind a check of this word at entry, before any barrier, counter or LDS
+// use.  The word was written by an EARLIER launch of the same stream, so the answer is the same in every wave of the grid (arrival counters are never left
+// half-counted).  They are kernels of their own, launched only with the setting on: the kernels a handle launches with the setting off carry no check and no argument
+// for it -- a null-pointer test at their entry cost the [256,256] pair 0.3 - 1 % (profiles/EXPERIMENTS.md).
+__device__ __forceinline__ bool update_stopped(const unsigned* stop) { return stop != nullptr && *stop != 0u; }
+
 // reduce over the 16 lanes that share (lane >> 4)
 // DPP lane permutes (vector-ALU data path, ~4 cycles each) instead of __shfl_xor's ds_bpermute (an LDS-crossbar round
 // trip each): pairs, quads, then the two mirrors -- every lane of the 16 ends with the same total.
@@ -1702,7 +1710,7 @@ struct ReduceArgs {
     float* beta_pow;             // {cur b1, cur b2, next b1, next b2}: cur <- next here (adam writes next)
 };
 
-__global__ __launch_bounds__(256) void grad_reduce_kernel(ReduceArgs a) {
+__device__ __forceinline__ void grad_reduce_body(ReduceArgs a) {
     __shared__ float red[4];
     const int blk = blockIdx.x, tid = threadIdx.x;
     if (blk == a.n_blocks) {
@@ -1754,6 +1762,9 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(ReduceArgs a) {
     __syncthreads();
     if (tid == 0) st_wt<PPO_WT_C1>(a.sumsq + blk, (red[0] + red[1]) + (red[2] + red[3]));
 }
+__global__ __launch_bounds__(256) void grad_reduce_kernel(ReduceArgs a) { grad_reduce_body(a); }
+// ... with the target-KL setting on (update_stopped)
+__global__ __launch_bounds__(256) void grad_reduce_stop_kernel(ReduceArgs a, const unsigned* stop) { if (update_stopped(stop)) return; grad_reduce_body(a); }
 
 // rebuild every transposed copy from theta (after parameters were written from the host)
 __device__ __forceinline__ void write_images(const GradSrc& gs, float* img, int e, float x) {
@@ -1795,7 +1806,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* grad, floa
 struct AdamArgs {
     float* theta; float* m; float* v; const float* grad; const float* sumsq; int n_blocks;
     float* thetaT; float* par; const GradSrc* src;
-    const float* hyper;          // {lr, cliprange, vclip_range, vclip_off}
+    const float* hyper;          // {lr, cliprange, vclip_range, vclip_off, target-KL limit (read by the ADAM_GATE form only)}
     float* beta_pow;             // {cur b1, cur b2, next b1, next b2}
     float beta1, beta2, eps, max_norm;
     float* loss_row;             // [5] destination for this train step (may be null)
@@ -1811,8 +1822,11 @@ struct AdamArgs {
     const float* theta_in; const float* m_in; const float* v_in;   // read from another parameter set (narrow path's deferred Adam); null = in place
     // data parallel, MEET > 0 (see adam_kernel): the grid-wide meeting's table -- one epoch word and one partial sum of squares per workgroup, an
     // error word behind the epoch words -- and, MEET == 2, the peer regions whose slots this kernel adds up itself
+    // MEET = ADAM_GATE (target-KL early stopping, single GPU: no meeting): meet_words is the handle's stop block {flag, Adam steps applied} -- the struct, and with it
+    // the kernarg layout of every other instantiation, stays what it was
     unsigned* meet_words; float* meet_parts; int meet_grid;
     PeerDev peer;
+    __device__ unsigned* stop_block() const { return meet_words; }      // the ONLY reader of meet_words under MEET = ADAM_GATE (static_assert in adam_kernel)
 #ifdef PPO_STAMPS
     unsigned long long* stamps;  // diagnostic builds only: [block][8]
 #endif
@@ -1870,7 +1884,18 @@ __device__ __forceinline__ void adam_element(float gscaled, float m, float v, fl
 // 256-thread, 4 KB kernel).  No read-modify-write on a shared word: workgroup b reads its own epoch word e at entry, stores e + 1 behind its partial,
 // and 256 threads watch the table.  The wait is bounded: on a time-out the error word is raised, the step's result is garbage and the next
 // synchronising call reports it.
+// MEET = ADAM_GATE (single GPU like MEET = 0, with the target-KL gate; ppo_set_target_kl > 0 -- the launch without it is adam_kernel<FAST, 0>, the kernel it always was): target-KL early stopping is decided HERE, because this is
+// the one launch that both sees the step's losses and applies the step.  Every workgroup reads the stop flag at entry and forms the step's approxkl from the two tail
+// floats with the expression that writes loss_row[3] (the same two fp32 operations in the same order: a host that compares the returned row against the limit
+// reproduces the decision).  skip = flag || approxkl > hyper[4] is workgroup-uniform and taken before any store:
+//   flag already set : a train step behind the one that stopped the update.  Its train kernels returned at entry (update_stopped), the tail is stale: block 0 writes a
+//                      quiet-NaN loss row, nobody stores anything else (norm_out and the gradient stay those of the step that stopped).
+//   this step stops  : nothing of the step is applied -- no element, mirror, image or beta-power store; block 0 writes the real loss row and the norm, and raises the flag.
+//   otherwise        : the ordinary step, bit for bit; block 0 counts it in stop[1].
+// The flag only changes in a launch in which every workgroup skips anyway (all of them derive the same approxkl from the same two floats), so no ordering between
+// the workgroups is needed; the next launch sees it across the kernel boundary.  The host clears the block at the head of every update / train step (a kernel launch).
 #define ADAM_MEET_MAX_GRID 1024
+#define ADAM_GATE (-1)
 __device__ __forceinline__ f32x4 adam_ld4_sys(const float* p) {
     f32x4 v;
     asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v) : "v"(p) : "memory");
@@ -1878,10 +1903,30 @@ __device__ __forceinline__ f32x4 adam_ld4_sys(const float* p) {
 }
 template <bool FAST, int MEET = 0>
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
+    constexpr bool GATE = MEET == ADAM_GATE;
     __shared__ float red[4];
     __shared__ float tt[32][33];
     ASTAMP(0);
     const int tid = threadIdx.x;
+    static_assert(!(GATE && MEET > 0), "the stop block travels in AdamArgs::meet_words: the gate form holds no meeting, a meeting form no gate");
+    // GATE: this step's approxkl exceeds the limit.  Every workgroup derives it from the same two floats, so it is the same in all of them.  The FLAG read below
+    // is uniform within a launch except the one launch that raises it: there block 0 stores 1 behind its own barriers while waves of OTHER workgroups may still be
+    // arriving, and one of them can read 1 and return in front of the norm reduction's __syncthreads while its siblings read 0 and go on.  That is harmless: every
+    // workgroup of that launch has stop_now set and stores nothing either way, a wave that has left counts as arrived at a barrier, and block 0's own waves have all
+    // read the flag before it is raised (the store sits behind the __syncthreads they all pass).
+    bool stop_now = false;
+    unsigned* stop = nullptr;                                                    // GATE: the stop block
+    if constexpr (GATE) {
+        stop = a.stop_block();
+        if (stop[0] != 0u) {
+            if (blockIdx.x == 0 && a.loss_row && tid < 5) a.loss_row[tid] = __builtin_nanf("");
+            return;
+        }
+        const float* tail = a.grad + (size_t)a.n_blocks * 256;
+        float kl = tail[3] / tail[5];                                            // loss_row[3]'s expression, below
+        kl = 0.5f * kl;
+        stop_now = kl > a.hyper[4];
+    }
     unsigned epoch = 0;
     if constexpr (MEET > 0) epoch = __hip_atomic_load(a.meet_words + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;   // (only this workgroup writes its word)
     size_t idx = ((size_t)blockIdx.x * 256 + tid) * 4;
@@ -1993,7 +2038,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
     float scale = a.max_norm * tf_min(1.0f / norm, 1.0f / a.max_norm);          // G:24289-24472
     if (!isfinite(norm)) scale = __builtin_nanf("");                            // G:24493-24543
     const float alpha = lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
-    if (live) {
+    bool apply = live, tile_out = tiled >= 0;                                    // GATE: nothing is stored by a step that stops the update
+    if constexpr (GATE) { apply = live && !stop_now; tile_out = tiled >= 0 && !stop_now; }
+    if (apply) {
         const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, mv[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, tv[4] = {t4.x, t4.y, t4.z, t4.w};
         float mo[4], vo[4], to[4];
 #pragma unroll
@@ -2028,7 +2075,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
         }
     }
     ASTAMP(4);
-    if (tiled >= 0) {                                      // (block-uniform) the transposed tile: row r' = column 32 tj + r' of the matrix, 128 bytes per row
+    if (tile_out) {                                        // (block-uniform) the transposed tile: row r' = column 32 tj + r' of the matrix, 128 bytes per row
         __syncthreads();
         const int rp = tid >> 3, q4 = 4 * (tid & 7);
         const float4 o = make_float4(tt[rp][q4], tt[rp][q4 + 1], tt[rp][q4 + 2], tt[rp][q4 + 3]);
@@ -2041,9 +2088,14 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
 #endif
     if (blockIdx.x == 0) {
         if (tid == 0) {
-            a.beta_pow[2] = b1p * a.beta1;                                      // G:31217-31342 (after the applies)
-            a.beta_pow[3] = b2p * a.beta2;
+            bool powers = true;
+            if constexpr (GATE) powers = !stop_now;
+            if (powers) {
+                a.beta_pow[2] = b1p * a.beta1;                                  // G:31217-31342 (after the applies)
+                a.beta_pow[3] = b2p * a.beta2;
+            }
             if (a.norm_out) *a.norm_out = norm;
+            if constexpr (GATE) { if (stop_now) stop[0] = 1u; else stop[1] = stop[1] + 1u; }
         }
         if (a.loss_row && tid < 5) {
             const float* tail = a.grad + (size_t)a.n_blocks * 256;
@@ -2061,6 +2113,15 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
 // column means of the loss rows (ppo2.hpp:335)
 __global__ void loss_mean_kernel(const float* rows, int n, float* mean) {      // launch with 5 * 64 threads
     const int j = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    float s = 0.f;
+    for (int i = ln; i < n; i += 64) s += rows[i * 5 + j];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (ln == 0) mean[j] = s / (float)n;
+}
+// ... of an update under target-KL early stopping: the rows that were computed -- applied + stopped (0 or 1) of them, read from the stop block; the rows behind are NaN
+__global__ void loss_mean_stop_kernel(const float* rows, const unsigned* stop, float* mean) {      // launch with 5 * 64 threads
+    const int j = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    const int n = (int)(stop[1] + (stop[0] != 0u ? 1u : 0u));
     float s = 0.f;
     for (int i = ln; i < n; i += 64) s += rows[i * 5 + j];
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);

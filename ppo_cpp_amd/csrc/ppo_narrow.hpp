@@ -751,6 +751,39 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_train_kernel(NetDev net, Nw
     nw_train_body<KP0, HP, AP, LL, true, true, MASK, true>(net, lay, a, lds, tower, grp, (int)threadIdx.x, act_k);
 }
 
+// The forms launched while target-KL early stopping is on (update_stopped): the non-deferred kernels above behind the entry check.  Kernels of their own, so that the
+// ones a handle launches with the setting off stay what they were.
+template <int KP0, int HP, int AP, int LL, bool CAT, bool MASK>
+__global__ __launch_bounds__(NW_THREADS) void narrow_train_stop_kernel(NetDev net, NwLayout lay, NwTrainArgs a, const unsigned* stop) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwTrainArgs) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    const int tower = blockIdx.y, grp = blockIdx.x;
+    const int row0 = grp * NW_ROWS;
+    NSTAMP(0);
+    nw_stage<S, CAT, MASK>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
+                a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2, (int)threadIdx.x, a.mask);
+    nw_train_body<KP0, HP, AP, LL, true, CAT, MASK>(net, lay, a, lds, tower, grp);
+}
+template <int KP0, int HP, int AP, int LL, bool MASK>
+__global__ __launch_bounds__(NW_THREADS) void narrow_train_stop_multi_kernel(NetDev net, NwLayout lay, NwTrainArgsM a, const unsigned* stop) {
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwTrainArgsM) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    const int tower = blockIdx.y, grp = blockIdx.x;
+    const int row0 = grp * NW_ROWS;
+    NSTAMP(0);
+    const int arow = row0 + ((int)threadIdx.x >> 4), ak = (int)threadIdx.x & 15;
+    float act_k = 0.f;
+    if (tower == 0 && arow < a.n && ak < a.comp.K) act_k = a.actions[(size_t)arow * a.comp.K + ak];
+    nw_stage<S, true, MASK, true>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
+                a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2, (int)threadIdx.x, a.mask);
+    nw_train_body<KP0, HP, AP, LL, true, true, MASK, true>(net, lay, a, lds, tower, grp, (int)threadIdx.x, act_k);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // Gradient assembly for the narrow path: 64 consecutive elements per block, 4 threads per element (each adds a quarter of
 // the row groups in index order, the four meet in a fixed order).  Emits the sum of squares per 64-element chunk for the
@@ -762,7 +795,7 @@ struct NwReduceArgs {
     float* grad; float* sumsq; float n_local; float* beta_pow;
 };
 
-__global__ __launch_bounds__(256) void narrow_reduce_kernel(NwReduceArgs a) {
+__device__ __forceinline__ void narrow_reduce_body(NwReduceArgs a) {
     __shared__ float red[4];
     const int tid = threadIdx.x, blk = blockIdx.x;
     if (blk == a.n_chunks) {
@@ -805,6 +838,9 @@ __global__ __launch_bounds__(256) void narrow_reduce_kernel(NwReduceArgs a) {
     __syncthreads();
     if (tid == 0) a.sumsq[blk] = (red[0] + red[1]) + (red[2] + red[3]);
 }
+__global__ __launch_bounds__(256) void narrow_reduce_kernel(NwReduceArgs a) { narrow_reduce_body(a); }
+// ... with the target-KL setting on (update_stopped)
+__global__ __launch_bounds__(256) void narrow_reduce_stop_kernel(NwReduceArgs a, const unsigned* stop) { if (update_stopped(stop)) return; narrow_reduce_body(a); }
 
 // ------------------------------------------------------------------------------------------------------------------------
 // ALL minibatches of an epoch in ONE launch, for minibatches of <= 64 rows on the deferred-Adam shapes (the reference's own command line: 1 environment x

@@ -590,3 +590,28 @@ __global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArg
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsM)>();
     train8_body<KP0, AP, CAT, MASK, MULTI>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
 }
+
+// The forms launched while target-KL early stopping is on (update_stopped, ppo_kernels.hpp): the kernels above behind the entry check.  Kernels of their own, so that
+// the ones a handle launches with the setting off stay what they were.
+template <int KP0, int AP>
+__global__ __launch_bounds__(T8_THREADS) void train8_stop_kernel(NetDev net, TrainArgs a, const unsigned* stop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    train8_body<KP0, AP>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}
+template <int KP0, int AP, bool CAT, bool MASK>
+__global__ __launch_bounds__(T8_THREADS) void train8_stop_kernel(NetDev net, TrainArgs a, const unsigned* stop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgs) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    train8_body<KP0, AP, CAT, MASK>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}
+template <int KP0, int AP, bool CAT, bool MASK, bool MULTI>
+__global__ __launch_bounds__(T8_THREADS) void train8_stop_kernel(NetDev net, TrainArgsM a, const unsigned* stop) {
+    static_assert(MULTI && CAT, "the multi-categorical overload: a form of the categorical head");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsM) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    train8_body<KP0, AP, CAT, MASK, MULTI>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}

@@ -37,7 +37,7 @@ const char* kAliases[][2] = {{"-d", "dir"}, {"--dir", "dir"}, {"-p", "path"}, {"
                              {"--minibatches", "minibatches"}, {"--seed", "seed"}, {"-g", "graph"}, {"--graph", "graph"}, {"--graph_path", "graph"}, {"--obs", "obs"},
                              {"--ranks", "ranks"}, {"--rank", "rank"}, {"--world", "world"}, {"--ctl_fd", "ctl_fd"}, {"--devices", "devices"}, {"--collective", "collective"},
                              {"--explicit_dir", "explicit_dir"}, {"--dump_dir", "dump_dir"}, {"--time_limit", "time_limit"},
-                             {"--discrete_kernels", "discrete_kernels"}};
+                             {"--discrete_kernels", "discrete_kernels"}, {"--target_kl", "target_kl"}};
 const char* kSwitches[][2] = {{"-r", "resume"}, {"--resume", "resume"}, {"-v", "verbose"}, {"--verbose", "verbose"}, {"--seeded", "seeded"},
                               {"--replica_saves", "replica_saves"}, {"--ctl_selftest", "ctl_selftest"}, {"--no_bootstrap_truncated", "no_bootstrap_truncated"}};
 
@@ -71,8 +71,10 @@ int main(int argc, char** argv) {
                         "                   [--minibatches N]\n"
                         "                   [--hidden 256,256] [--saves N --dir DIR --id ID] [--path CKPT_PREFIX] [--resume] [--seeded] [--seed N]\n"
                         "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n"
-                        "                   [--time_limit N] [--no_bootstrap_truncated] [--discrete_kernels narrow|pair|generic]\n"
+                        "                   [--time_limit N] [--no_bootstrap_truncated] [--discrete_kernels narrow|pair|generic] [--target_kl X]\n"
                         "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n"
+                        "  --target_kl X: early stopping; a train step whose approxkl exceeds 1.5 X is not applied and ends its update (0 = off, the default;\n"
+                        "                 one GPU, fp32 path)\n"
                         "  --time_limit N: every environment ends its episodes after N steps (a TimeLimit wrapper); the value is bootstrapped at those truncations\n"
                         "  --no_bootstrap_truncated: treat them as terminal states instead (the reference's behaviour)\n"
                         "  --discrete_kernels: kernels of a discrete environment's categorical policy; narrow = the LDS-resident family where the network's shape\n"
@@ -149,6 +151,14 @@ int main(int argc, char** argv) {
         if (v != "off" && (v.empty() || *end != '\0')) { std::fprintf(stderr, "--cliprange_vf: expected a number, inf or off, not '%s'\n", v.c_str()); return 1; }
         cliprange_vf = (float)x;
     }
+    float target_kl = 0.f;                                                      // PPO2::set_target_kl (0 = off)
+    if (f.has("target_kl")) {
+        const std::string v = f.str("target_kl", "");
+        char* end = nullptr;
+        const double x = std::strtod(v.c_str(), &end);
+        if (v.empty() || *end != '\0' || !std::isfinite(x) || x < 0) { std::fprintf(stderr, "--target_kl: expected a finite number >= 0, not '%s'\n", v.c_str()); return 1; }
+        target_kl = (float)x;
+    }
     const std::string dk = f.str("discrete_kernels", "generic");
     if (dk != "narrow" && dk != "pair" && dk != "generic") { std::fprintf(stderr, "--discrete_kernels: expected narrow, pair or generic, not '%s'\n", dk.c_str()); return 1; }
     int rc = 0;
@@ -192,6 +202,7 @@ int main(int argc, char** argv) {
         algorithm.replica_saves = f.has("replica_saves");
         algorithm.bootstrap_truncated = !f.has("no_bootstrap_truncated");
         if (f.has("path")) algorithm.load(f.str("path", ""));
+        if (f.has("target_kl") || !f.has("path")) algorithm.set_target_kl(target_kl);      // (a loaded checkpoint brings its own unless the flag is given)
         if (training) {
             const int steps = (int)f.num("steps", 2e7);
             const int saves = f.has("saves") ? (int)f.num("saves", 0) : 0;

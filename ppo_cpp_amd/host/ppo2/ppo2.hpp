@@ -87,7 +87,13 @@ public:
         return s + "]";
     }
 
-    struct UpdateLog { int fps; float losses[5]; double collect_ms, update_ms; float mean_reward; };     // mean_reward: the rollout's un-normalised rewards (the learning curve)
+    // mean_reward: the rollout's un-normalised rewards (the learning curve); applied / total: Adam steps applied / train steps of the update (they differ when
+    // target-KL early stopping ended it)
+    struct UpdateLog { int fps; float losses[5]; double collect_ms, update_ms; float mean_reward; int applied, total; };
+    // Target-KL early stopping (ppo_set_target_kl, include/ppo_hip.h; no reference counterpart): a train step whose approxkl exceeds 1.5 * target_kl is not applied
+    // and ends the update.  0 = off (the default).  Forwarded to the handle by learn() and load(), like cliprange_vf; saved in the side-car as "target_kl".
+    void set_target_kl(float target_kl) { target_kl_ = target_kl; }
+    float target_kl() const { return target_kl_; }
     // Data parallel (no reference counterpart): this PPO2 is rank `rank` of `world` processes, one per GPU, whose handles share a
     // communicator (ppo_dist_init, see dist.hpp).  `env` holds THIS rank's share of the environments; n_batch, total_timesteps, the fps of the
     // CSV line and the checkpoint's n_envs are job-wide quantities.  The replicas stay bit-identical, so rank 0 alone prints and saves
@@ -146,6 +152,7 @@ public:
         // (JSON has no NaN or inf: NaN and -inf, both PPO_VCLIP_POLICY, are written as -1; +inf is written as null, which load() reads back as +inf)
         json["cliprange_vf"] = std::isnan(cliprange_vf_) || cliprange_vf_ == -INFINITY ? -1.f : cliprange_vf_; json["observation_space"] = env_.get_observation_space();
         json["action_space"] = env_.get_action_space(); json["n_envs"] = n_envs_ * world_; json["model_filename"] = model_filename;
+        json["target_kl"] = target_kl_;
         if (ppo_action_dist(h_) == PPO_ACT_MULTI_CATEGORICAL) json["action_nvec"] = handle_nvec(h_);        // a multi-categorical policy: "discrete" plus its components
         std::ofstream f(save_path + ".json");
         if (!f) throw std::runtime_error("PPO2::save: unable to open " + save_path + ".json");
@@ -173,8 +180,16 @@ public:
         nminibatches_ = json["nminibatches"].get<int>(); noptepochs_ = json["noptepochs"].get<int>();
         cliprange_ = json["cliprange"].get<float>();
         cliprange_vf_ = json.contains("cliprange_vf") && json["cliprange_vf"].is_null() ? INFINITY : json["cliprange_vf"].get<float>();
+        target_kl_ = json.contains("target_kl") ? json["target_kl"].get<float>() : 0.f;      // (a side-car from before the setting: off)
         n_batch_ = n_envs_ * n_steps_;
         apply_value_clip();
+        // a handle that refuses the setting (PPO_BF16, a communicator: include/ppo_hip.h) still loads the checkpoint: early stopping drops to off, with a warning
+        if (target_kl_ > 0.f && ppo_set_target_kl(h_, target_kl_) != 0) {
+            std::fprintf(stderr, "PPO2::load: %s holds target_kl = %g, which this handle refuses (%s); continuing with target_kl off\n", save_path.c_str(), (double)target_kl_,
+                         ppo_last_error(h_));
+            target_kl_ = 0.f;
+        }
+        apply_target_kl();
         extra_tensors_.clear();
         const int nt = ppo_num_tensors(h_);
         for (int i = 0; i < nt; ++i) {
@@ -201,6 +216,7 @@ public:
     // ids 0, 1, ..., plus a trailing save when the interval does not divide the number of updates
     void learn(int total_timesteps, int num_saves = 0, const std::string& save_path = "") {
         apply_value_clip();                                        // every rank: the replicas must train the same loss
+        apply_target_kl();
         num_timesteps_ = 0;
         updates_this_learn_ = 0;
         if (!seeded_ || seeded_with_ != seed) {                    // exploration noise AND epoch shuffles follow PPO2::seed / --seed; a repeated
@@ -290,6 +306,7 @@ private:
             // every rank shuffles its OWN rows (include/ppo_hip.h, ppo_dist_global_shuffle 0): the rank is part of the key
             check(ppo_update(h_, learning_rate_, cliprange_, noptepochs_, nminibatches_, perms,
                              seed + (unsigned long long)(++shuffle_updates_) + ((unsigned long long)rank_ << 40), nullptr, log.losses));
+            { int32_t ap = 0, tot = 0; check(ppo_update_applied(h_, &ap, &tot)); log.applied = ap; log.total = tot; }
             const auto t2 = clk::now();
             finish_update(log, t0, t1, t2, rew_view, done_view);
         }
@@ -311,7 +328,9 @@ private:
             std::iota(perm.begin(), perm.end(), 0);
             num_timesteps_ += n_batch_;
             double acc[5] = {0, 0, 0, 0, 0};
-            for (int epoch = 0; epoch < noptepochs_; ++epoch) {
+            int computed = 0, applied_steps = 0;                            // train steps whose losses were computed / whose Adam step was applied
+            bool stopped = false;                                           // target-KL early stopping: a step was not applied, the update ends
+            for (int epoch = 0; epoch < noptepochs_ && !stopped; ++epoch) {
                 if (explicit_perms) std::memcpy(perm.data(), explicit_perms + ((size_t)(update - 1) * noptepochs_ + epoch) * n_batch_, sizeof(int) * (size_t)n_batch_);
                 else std::shuffle(perm.begin(), perm.end(), rng);            // cumulative, like ppo2.hpp:288
                 std::vector<Mat> shuffled;
@@ -320,7 +339,7 @@ private:
                     for (int i = 0; i < n_batch_; ++i) mat_set_row(o, perm[i], mat_row_ptr(*v, i));
                     shuffled.push_back(o);
                 }
-                for (int start = 0; start < n_batch_; start += batch_size) {
+                for (int start = 0; start < n_batch_ && !stopped; start += batch_size) {
                     std::vector<Mat> sl;
                     for (const Mat& v : shuffled) {
                         Mat s(batch_size, v.cols());
@@ -329,11 +348,16 @@ private:
                     }
                     const Mat l = _train_step(learning_rate_, cliprange_, sl[0], sl[1], sl[2], sl[3], sl[4], sl[5], sl.size() > 6 ? &sl[6] : nullptr);
                     for (int j = 0; j < 5; ++j) acc[j] += l(0, j);
+                    ++computed;
+                    int32_t ap = 0, tot = 0;
+                    check(ppo_update_applied(h_, &ap, &tot));
+                    if (ap == 0) stopped = true; else ++applied_steps;
                 }
             }
             const auto t2 = clk::now();
             UpdateLog log{};
-            for (int j = 0; j < 5; ++j) log.losses[j] = (float)(acc[j] / (noptepochs_ * nminibatches_));   // colwise().mean() (ppo2.hpp:335)
+            for (int j = 0; j < 5; ++j) log.losses[j] = (float)(acc[j] / computed);   // colwise().mean() (ppo2.hpp:335) over the computed rows: all noptepochs * nminibatches of them unless the update stopped
+            log.applied = applied_steps; log.total = noptepochs_ * nminibatches_;
             Mat rew_view(n_envs_, n_steps_), done_view(n_envs_, n_steps_);
             std::memcpy(rew_view.data(), mb.unnormalized_rewards->data(), sizeof(float) * (size_t)n_batch_);
             std::memcpy(done_view.data(), mb.dones->data(), sizeof(float) * (size_t)n_batch_);
@@ -371,6 +395,8 @@ private:
         else check(ppo_set_value_clip(h_, PPO_VCLIP_RANGE, r));
     }
 
+    void apply_target_kl() { check(ppo_set_target_kl(h_, target_kl_)); }
+
     void check(int rc) { if (rc != 0) throw std::runtime_error(std::string("PPO2: ") + ppo_last_error(h_)); }
 
     ppo_handle* h_;
@@ -382,6 +408,7 @@ private:
     float ent_coef_, learning_rate_, vf_coef_, max_grad_norm_, lam_;
     int nminibatches_, noptepochs_;
     float cliprange_, cliprange_vf_;
+    float target_kl_ = 0.f;
     std::string tensorboard_log_;
     int n_envs_, n_batch_, num_timesteps_;
     MlpPolicy act_model_;

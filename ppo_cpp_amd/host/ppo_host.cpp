@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <regex>
 #include <thread>
 
 #include "env/env_mock.hpp"
@@ -208,6 +209,9 @@ struct ppo_host_explicit {
     float* ret_mean; float* ret_var; double* ret_count;      // ret_rms [1], [1], [1]
     float* reward_curve;         // [n_updates] mean un-normalised reward of every update's rollout
     char (*count_names)[32]; long long* counts; int* n_counts;     // ppo_kernel_counts of the run's handle after learn(): up to 64 entries (all three or none)
+    int* applied_out;            // [n_updates][2] Adam steps applied / train steps of every update (target-KL early stopping)
+    float target_kl;             // PPO2::set_target_kl: target-KL early stopping, 0 = off.  (Here and not in ppo_host_args: that struct's last member is pinned by
+                                 // tests/test_narrow_host_step.py)
 };
 
 static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_host_explicit* x) {
@@ -267,6 +271,7 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
             literal.quiet = true;
             PPO2& algo = a->reference_loop ? literal : algorithm;
             algo.seed = a->seed;
+            if (x) algo.set_target_kl(x->target_kl);
             if (x) { algo.explicit_noise = x->noise; algo.explicit_perms = x->perms; }
             const auto t0 = std::chrono::steady_clock::now();
             algo.learn(a->n_updates * a->n_envs * a->n_steps);
@@ -293,6 +298,7 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
             if (x) {
                 if (x->losses_out) for (size_t i = 0; i < hist.size(); ++i) std::memcpy(x->losses_out + 5 * i, hist[i].losses, sizeof(float) * 5);
                 if (x->reward_curve) for (size_t i = 0; i < hist.size(); ++i) x->reward_curve[i] = hist[i].mean_reward;
+                if (x->applied_out) for (size_t i = 0; i < hist.size(); ++i) { x->applied_out[2 * i] = hist[i].applied; x->applied_out[2 * i + 1] = hist[i].total; }
                 if (x->theta_out && ppo_get_flat(h, 0, x->theta_out, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
                 if (x->obs_mean && ppo_norm_get_stats(h, 0, x->obs_mean, x->obs_var, x->obs_count) != 0) throw std::runtime_error(ppo_last_error(h));
                 if (x->ret_mean && ppo_norm_get_stats(h, 1, x->ret_mean, x->ret_var, x->ret_count) != 0) throw std::runtime_error(ppo_last_error(h));
@@ -670,5 +676,47 @@ int ppo_host_value_clip_checkpoint(const char* prefix, float cliprange_vf, int32
     for (ppo_handle* x : h) if (x) ppo_destroy(x);
     return rc;
 }
+
+// PPO2::save of a [64,64] Gaussian policy with set_target_kl(target_kl) under `prefix` (no training), then PPO2::load into a FRESH handle: *loaded is that handle's
+// ppo_get_target_kl.  strip_key: the "target_kl" key is first removed from the side-car -- a checkpoint from before the setting.  Returns 0; -1 = error (message on stderr).
+int ppo_host_target_kl_checkpoint(const char* prefix, float target_kl, int strip_key, float* loaded) {
+    ppo_handle* h[2] = {nullptr, nullptr};
+    int rc = 0;
+    try {
+        ppo_config cfg; const int32_t hidden[2] = {64, 64};
+        ppo_config_default(&cfg, 18, 18, 2, hidden);
+        for (int k = 0; k < 2; ++k)
+            if (ppo_create(&cfg, &h[k]) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0) throw std::runtime_error(ppo_last_error(h[k]));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new EnvMock()), h[0], /*training=*/false};
+            PPO2 algo{h[0], env};
+            algo.set_target_kl(target_kl);
+            algo.save(prefix);
+        }
+        if (strip_key) {
+            const std::string path = std::string(prefix) + ".json";
+            if (!nlohmann::json::parse(ckpt::slurp(path)).contains("target_kl")) throw std::runtime_error("the side-car has no target_kl key");
+            // (the keys are written in sorted order: this one is neither the first nor the last)
+            const std::string text = std::regex_replace(ckpt::slurp(path), std::regex("\"target_kl\"\\s*:\\s*[^,}]*,\\s*"), "");
+            if (nlohmann::json::parse(text).contains("target_kl")) throw std::runtime_error("could not strip target_kl from the side-car");
+            std::ofstream f(path);
+            f << text;
+        }
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new EnvMock()), h[1], /*training=*/false};
+            PPO2 algo{h[1], env};
+            algo.set_target_kl(0.5f);                                 // (what load must overwrite)
+            algo.load(prefix);
+            if (ppo_get_target_kl(h[1], loaded) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+            if (algo.target_kl() != *loaded) throw std::runtime_error("PPO2::load left PPO2 and the handle with different target_kl");
+        }
+    } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = -1; }
+    for (ppo_handle* x : h) if (x) ppo_destroy(x);
+    return rc;
+}
+
+// sizeof(ppo_host_args), sizeof(ppo_host_explicit): the Python mirrors check their layouts against these
+int ppo_host_args_size(void) { return (int)sizeof(ppo_host_args); }
+int ppo_host_explicit_size(void) { return (int)sizeof(ppo_host_explicit); }
 
 }  // extern "C"

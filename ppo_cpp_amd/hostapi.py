@@ -72,7 +72,7 @@ class HostExplicit(C.Structure):
     _fields_ = [("theta_in", C.c_void_p), ("noise", C.c_void_p), ("perms", C.c_void_p), ("losses_out", C.c_void_p), ("theta_out", C.c_void_p),
                 ("obs_mean", C.c_void_p), ("obs_var", C.c_void_p), ("obs_count", C.c_void_p),
                 ("ret_mean", C.c_void_p), ("ret_var", C.c_void_p), ("ret_count", C.c_void_p), ("reward_curve", C.c_void_p),
-                ("count_names", C.c_void_p), ("counts", C.c_void_p), ("n_counts", C.c_void_p)]
+                ("count_names", C.c_void_p), ("counts", C.c_void_p), ("n_counts", C.c_void_p), ("applied_out", C.c_void_p), ("target_kl", C.c_float)]
 
 
 def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, lr=3.93141e-4, cliprange=0.161023, gamma=0.99, lam=0.95,
@@ -109,7 +109,7 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
                 obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, nvec=None, masked=False, n_playback=0,
-                host_step_fused=False):
+                host_step_fused=False, target_kl=0.0):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
@@ -123,7 +123,9 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     and the result carries "forbidden_received"; n_playback: that many PPO2::eval steps afterwards, "playback_actions" [n_playback, K] and "playback_legal".
     "kernel_counts": the handle's ppo_kernel_counts after the run.
     host_step_fused=True: ppo_set_host_step_fused(h, 1) on the created handle (ppo_host_args::host_step_fused): with discrete_kernels="narrow" and at most 32
-    environments the act side runs narrow_host_step_kernel<cat|mcat[,mask]>, one launch per env step; nothing changes anywhere else."""
+    environments the act side runs narrow_host_step_kernel<cat|mcat[,mask]>, one launch per env step; nothing changes anywhere else.
+    target_kl (default 0 = off): PPO2::set_target_kl, target-KL early stopping (include/ppo_hip.h, ppo_set_target_kl); "applied" [n_updates, 2] then holds the Adam
+    steps applied / train steps of every update (ppo_host_explicit::target_kl / applied_out; not through the nvec form)."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -140,6 +142,8 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
         a.n_components, a.multi_masked = len(nvec), int(bool(masked))
         a.discrete_kernels = _discrete_kernels(discrete_kernels)
         a.host_step_fused = int(bool(host_step_fused))
+        if target_kl:
+            raise ValueError("target_kl is not carried through the nvec form")
         for i, x in enumerate(nvec):
             a.nvec[i] = x
         out = {"reward_curve": np.zeros(n_updates, np.float32), "playback_actions": np.zeros((n_playback, len(nvec)), np.float32),
@@ -166,10 +170,10 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     a.discrete_kernels = _discrete_kernels(discrete_kernels)
     a.compute_dtype = int(compute_dtype)
     a.host_step_fused = int(bool(host_step_fused))
-    out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32)}
+    out = {"losses": np.zeros((n_updates, 5), np.float32), "reward_curve": np.zeros(n_updates, np.float32), "applied": np.zeros((n_updates, 2), np.int32)}
     names = ((C.c_char * 32) * 64)(); cnt = (C.c_longlong * 64)(); ncnt = C.c_int(0)
     x = HostExplicit(None, None, None, out["losses"].ctypes.data, None, None, None, None, None, None, None, out["reward_curve"].ctypes.data,
-                     C.addressof(names), C.addressof(cnt), C.addressof(ncnt))
+                     C.addressof(names), C.addressof(cnt), C.addressof(ncnt), out["applied"].ctypes.data, float(target_kl))
     r = HostResult()
     if lib.ppo_host_learn_explicit(C.byref(a), C.byref(x), C.byref(r)) != 0:
         raise RuntimeError(r.error.decode())
@@ -246,6 +250,16 @@ def value_clip_checkpoint(prefix, cliprange_vf):
     if lib.ppo_host_value_clip_checkpoint(prefix.encode(), C.c_float(cliprange_vf), C.byref(m), C.byref(r)) != 0:
         raise RuntimeError("ppo_host_value_clip_checkpoint failed (see stderr)")
     return m.value, r.value
+
+
+def target_kl_checkpoint(prefix, target_kl, strip_key=False):
+    """PPO2::save of a policy with set_target_kl(target_kl), PPO2::load into a fresh handle (ppo_host_target_kl_checkpoint): returns the fresh handle's
+    target_kl.  strip_key: the "target_kl" key is removed from the side-car before the load (a checkpoint from before the setting)."""
+    lib = load_host_library()
+    x = C.c_float(-1.0)
+    if lib.ppo_host_target_kl_checkpoint(prefix.encode(), C.c_float(target_kl), int(bool(strip_key)), C.byref(x)) != 0:
+        raise RuntimeError("ppo_host_target_kl_checkpoint failed (see stderr)")
+    return x.value
 
 
 def multi_checkpoint(prefix, obs, nvec, other_nvec):
