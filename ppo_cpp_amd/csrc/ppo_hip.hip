@@ -97,6 +97,27 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a multi-categorical PPO_BF16 handle (ppo_create_multi_ex with PPO_ACT_BF16_MULTI_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence"
                                        "bf16_step_sequence<mcat>", "bf16_step_sequence<mcat,mask>", "bf16_train_sequence<mcat>", "bf16_train_sequence<mcat,mask>"};
 
+// The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat> or <mcat,mask>.  index(): its column below.
+struct Head {
+    bool cat, mask, multi;
+    int index() const { return multi ? 3 + mask : cat ? 1 + mask : 0; }
+};
+// which entry a launch of a kernel family with a head bumps: a row per family, a column per head form.  (The narrow Gaussian entries say whether the compile-time
+// shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.)
+enum HeadFamily { KF_POLICY_STEP = 0, KF_TRAIN_FB, KF_TRAIN8, KF_NARROW_STEP_STATIC, KF_NARROW_STEP, KF_NARROW_TRAIN_STATIC, KF_NARROW_TRAIN, KF_NARROW_HOST_STEP, KF_BF16_STEP,
+                  KF_BF16_TRAIN, KF_COUNT };
+constexpr KernelVariant kHeadVariant[KF_COUNT][5] = {
+    {KV_POLICY_STEP, KV_POLICY_STEP_CAT, KV_POLICY_STEP_CAT_MASK, KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK},
+    {KV_TRAIN_FB, KV_TRAIN_FB_CAT, KV_TRAIN_FB_CAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK},
+    {KV_TRAIN8, KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK},
+    {KV_NARROW_STEP_STATIC, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK},
+    {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK},
+    {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK},
+    {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK},
+    {KV_COUNT, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK},
+    {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK},
+    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK}};
+
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
     void* lib = nullptr;
@@ -753,6 +774,38 @@ int ensure_staging(ppo_handle* h, int rows) {
 
 ObsNorm no_norm_fwd() { return ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}; }
 
+// ---- the policy head of a launch ------------------------------------------------------------------------------------
+// A launch site decides the head once (head_of), turns it into compile-time constants once (with_head calls f with a HeadTag) and asks its family's picker
+// (bf16_sample_kernel / bf16_loss_kernel below; step_fn, train_fb_fn, nw_step_fn, nw_train_fn, train8_fn, nw_host_step_fn under "launches") for the instantiation.
+// ppo_create_ex asks the same pickers for every head the handle can launch (for_each_head) when it raises the dynamic-LDS limits.
+template <bool CAT, bool MASK, bool MULTI>
+struct HeadTag { static constexpr bool cat = CAT, mask = MASK, multi = MULTI; };
+using GaussHead = HeadTag<false, false, false>;
+
+// (a mask on a Gaussian handle: the entry points and launch_step refuse it before any launch)
+static Head head_of(const ppo_handle* h, bool masked) {
+    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL, cat = multi || h->dist == PPO_ACT_CATEGORICAL;
+    return Head{cat, cat && masked, multi};
+}
+template <class F>
+static void with_head(Head hd, F&& f) {
+    if (hd.multi) { if (hd.mask) f(HeadTag<true, true, true>{}); else f(HeadTag<true, false, true>{}); }
+    else if (hd.cat) { if (hd.mask) f(HeadTag<true, true, false>{}); else f(HeadTag<true, false, false>{}); }
+    else f(GaussHead{});
+}
+// every head a handle of this distribution can launch: Gaussian one; categorical and multi-categorical two (plain, masked)
+template <class F>
+static void for_each_head(const ppo_handle* h, F&& f) {
+    with_head(head_of(h, false), f);
+    if (h->dist != PPO_ACT_GAUSSIAN) with_head(head_of(h, true), f);
+}
+// the arguments of a launch with head tag T: `a` itself, or (multi-categorical) the M struct -- `a` with the component table behind it
+template <class M, class T, class Base>
+static auto head_args(T, const ppo_handle* h, const Base& a) {
+    if constexpr (T::multi) { M m{}; static_cast<Base&>(m) = a; m.comp = h->comp; return m; }
+    else return a;
+}
+
 // ---- bf16 matrix-core path (ppo_bf16.hpp) ------------------------------------------------------------------------
 // bf16 operand copy of the fp32 master weights: a cast of the whole padded vector (adam_kernel keeps it current afterwards)
 int bf16_refresh_mirrors(ppo_handle* h) {
@@ -989,14 +1042,10 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     sa.mask = a.mask;
     if (n.A > 128) return fail(h, "bf16 path: more than 128 actions");
     const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
-    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {         // the component table rides behind the arguments, as in launch_step_t
-        SampleArgsBM sm;
-        static_cast<SampleArgsB&>(sm) = sa; sm.comp = h->comp;
-        if (a.mask) hipLaunchKernelGGL((bf16_sample_kernel<true, true, true>), grid, blk, 0, h->stream, sm);
-        else hipLaunchKernelGGL((bf16_sample_kernel<true, false, true>), grid, blk, 0, h->stream, sm);
-    } else if (a.mask) hipLaunchKernelGGL((bf16_sample_kernel<true, true>), grid, blk, 0, h->stream, sa);
-    else if (h->dist == PPO_ACT_CATEGORICAL) hipLaunchKernelGGL((bf16_sample_kernel<true, false>), grid, blk, 0, h->stream, sa);
-    else hipLaunchKernelGGL((bf16_sample_kernel<false, false>), grid, blk, 0, h->stream, sa);
+    with_head(head_of(h, a.mask != nullptr), [&](auto H) {
+        using Hd = decltype(H);
+        hipLaunchKernelGGL((bf16_sample_kernel<Hd::cat, Hd::mask, Hd::multi>), grid, blk, 0, h->stream, head_args<SampleArgsBM>(H, h, sa));
+    });
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1026,14 +1075,10 @@ int bf16_train_fwd_bwd(ppo_handle* h, const TrainArgs& ta, int Rp, bool links_on
     if (n.A > 64 * BL_EPT) return fail(h, "bf16 path: more than %d actions", 64 * BL_EPT);
     const dim3 lgrid(Rp / BL_ROWS), lblk(64 * BL_ROWS);
     const size_t llds = (size_t)(2 * BL_ROWS * n.Ap + 6 * BL_ROWS) * sizeof(float);
-    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {
-        LossArgsBM lm;
-        static_cast<LossArgsB&>(lm) = la; lm.comp = h->comp;
-        if (ta.mask) hipLaunchKernelGGL((bf16_loss_kernel<true, true, true>), lgrid, lblk, llds, h->stream, lm);
-        else hipLaunchKernelGGL((bf16_loss_kernel<true, false, true>), lgrid, lblk, llds, h->stream, lm);
-    } else if (ta.mask) hipLaunchKernelGGL((bf16_loss_kernel<true, true>), lgrid, lblk, llds, h->stream, la);
-    else if (h->dist == PPO_ACT_CATEGORICAL) hipLaunchKernelGGL((bf16_loss_kernel<true, false>), lgrid, lblk, llds, h->stream, la);
-    else hipLaunchKernelGGL((bf16_loss_kernel<false, false>), lgrid, lblk, llds, h->stream, la);
+    with_head(head_of(h, ta.mask != nullptr), [&](auto H) {
+        using Hd = decltype(H);
+        hipLaunchKernelGGL((bf16_loss_kernel<Hd::cat, Hd::mask, Hd::multi>), lgrid, lblk, llds, h->stream, head_args<LossArgsBM>(H, h, la));
+    });
     HIP_OK(h, hipGetLastError());
     if (links_only) return 0;
     GemmArgs bl[PPO_MAX_LAYERS];
@@ -1109,6 +1154,8 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------
+// A launch site picks along its family's own axes here (the rung, NW_DISPATCH, PAIR_DISPATCH, stop or not); the head comes in as a HeadTag ("the policy head of
+// a launch" above) and the counter out of kHeadVariant.  A new head, or a new kernel with a head, is named in its family's picker and nowhere else.
 // narrow kernels: compile-time shapes <32, 64, 32, 2> / <64, 64, 32, 2> (observation tile of 32 / 64 columns) or the runtime-shape form;
 // X(KP0, HP, AP, L) is the launch statement
 #define NW_DISPATCH(h, X) do { if (!(h)->nw_static) { X(0, 0, 0, 0); } else if ((h)->net.Kp0 == 32) { X(32, 64, 32, 2); } else { X(64, 64, 32, 2); } } while (0)
@@ -1116,75 +1163,76 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 #define PAIR_DISPATCH(h, X) do { const int kp_ = (h)->net.Kp0, ap_ = (h)->net.Ap; \
     if (kp_ == 32 && ap_ == 32) { X(32, 32); } else if (kp_ == 64 && ap_ == 32) { X(64, 32); } else if (kp_ == 32 && ap_ == 64) { X(32, 64); } else { X(64, 64); } } while (0)
 
-// a categorical handle on the narrow family (created with PPO_ACT_SHAPE_KERNELS, qualifying shape).  It runs narrow_step_kernel / narrow_train_kernel<cat[,mask]>
-// only: every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the resident host step) asks
+// a categorical handle on the narrow family (created with PPO_ACT_SHAPE_KERNELS, qualifying shape) or a multi-categorical one (ppo_create_multi_ex with the flag)
+// runs narrow_step_kernel / narrow_train_kernel<cat|mcat[,mask]> only -- the head is a HeadTag of the one launch function either has, not a function of its own:
+// every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the resident host step) asks
 // nw_gauss() where it is decided.  The fused host step has discrete forms of its own, opt-in per handle: host_fused_discrete().
-static bool nw_cat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_CATEGORICAL; }
-// ... and a multi-categorical one (ppo_create_multi_ex with the flag): narrow_step_kernel / narrow_train_kernel<mcat[,mask]> only, under the same rule
-static bool nw_mcat(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_MULTI_CATEGORICAL; }
 static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
+static bool nw_discrete(const ppo_handle* h) { return h->narrow && h->dist != PPO_ACT_GAUSSIAN; }
 
-// policy_step_kernel: the (CT, KS, CTH, WIDE) ladder of the handle's layout, once; the caller picks the head
-template <bool CAT, bool MASK, bool MULTI = false>
-void launch_step_t(ppo_handle* h, const StepArgs& a0) {
-    std::conditional_t<MULTI, StepArgsM, StepArgs> a;
-    static_cast<StepArgs&>(a) = a0;
-    if constexpr (MULTI) a.comp = h->comp;                          // (the component table rides behind the arguments every other head takes)
-    const dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
-    SET_STAMPS(a.stamps, grid.x <= 256, 4096 * 44);
-    const size_t lds = (size_t)h->lds_step_total * sizeof(float);
-#define X(CT, KS, CTH, WIDE) hipLaunchKernelGGL((policy_step_kernel<CT, KS, CTH, WIDE, CAT, MASK, MULTI>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, a)
-    if (h->net.wide) { if (h->CT == 4) X(4, 2, 0, true); else X(1, 1, 0, true); }
-    else if (h->CT == 4 && h->CTH == 2) X(4, 2, 2, false);
-    else if (h->CT == 4) X(4, 2, 0, false);
-    else X(1, 1, 0, false);
+// The pickers: the instantiation of a kernel family for a head and the family's own axes, named HERE and nowhere else -- the launch below each and the
+// dynamic-LDS pass of ppo_create_ex (lds_opt_in) both ask them.
+// policy_step_kernel / train_fwd_bwd_kernel: the (CT, KS, CTH, WIDE[, EARLY]) ladder of the handle's layout, a rung per instantiation
+enum { RUNG_WIDE4 = 0, RUNG_WIDE1, RUNG_42_EARLY, RUNG_42, RUNG_4, RUNG_1, RUNG_COUNT };      // (RUNG_42_EARLY: the train kernel's; the step kernel's RUNG_42)
+static int ladder_rung(const ppo_handle* h) {
+    if (h->net.wide) return h->CT == 4 ? RUNG_WIDE4 : RUNG_WIDE1;
+    if (h->CT == 4 && h->CTH == 2) return h->early ? RUNG_42_EARLY : RUNG_42;
+    return h->CT == 4 ? RUNG_4 : RUNG_1;
+}
+template <class T>
+static auto step_fn(T, int rung) {
+#define X(CT, KS, CTH, WIDE) return policy_step_kernel<CT, KS, CTH, WIDE, T::cat, T::mask, T::multi>
+    switch (rung) { case RUNG_WIDE4: X(4, 2, 0, true); case RUNG_WIDE1: X(1, 1, 0, true); case RUNG_42_EARLY: case RUNG_42: X(4, 2, 2, false); case RUNG_4: X(4, 2, 0, false); default: X(1, 1, 0, false); }
 #undef X
 }
-// narrow_step_kernel: the packed weight image stands in for the padded parameter vector
-template <bool CAT, bool MASK>
-void launch_narrow_step(ppo_handle* h, const StepArgs& a) {
-    const dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
-    StepArgs sa = a;
-    sa.theta = h->nw_img;
-    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, CAT, MASK>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
-    NW_DISPATCH(h, X);
+template <class T>
+static auto train_fb_fn(T, int rung) {
+#define X(CT, KS, CTH, WIDE, EARLY) return train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, T::cat, T::mask, T::multi>
+    switch (rung) { case RUNG_WIDE4: X(4, 2, 0, true, false); case RUNG_WIDE1: X(1, 1, 0, true, false); case RUNG_42_EARLY: X(4, 2, 2, false, true); case RUNG_42: X(4, 2, 2, false, false);
+                    case RUNG_4: X(4, 2, 0, false, false); default: X(1, 1, 0, false, false); }
 #undef X
 }
-// its multi-categorical forms: the component table rides behind the arguments, as in launch_step_t
-template <bool MASK>
-void launch_narrow_step_multi(ppo_handle* h, const StepArgs& a) {
-    const dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
-    StepArgsM sa;
-    static_cast<StepArgs&>(sa) = a;
-    sa.theta = h->nw_img;
-    sa.comp = h->comp;
-    const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_step_kernel<a, b, c, d, true, MASK, true>), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, sa)
-    NW_DISPATCH(h, X);
-#undef X
+// the narrow kernels, per NW_DISPATCH shape: the overloads that take the component table (and narrow_train_stop_multi_kernel) are the multi-categorical forms
+template <int KP0, int HP, int AP, int LL, class T>
+static auto nw_step_fn(T) {
+    if constexpr (T::multi) return narrow_step_kernel<KP0, HP, AP, LL, true, T::mask, true>;
+    else return narrow_step_kernel<KP0, HP, AP, LL, T::cat, T::mask>;
 }
-int launch_step(ppo_handle* h, const StepArgs& a) {
-    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (bf16 only when created with PPO_ACT_BF16_MULTI_HEAD; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
-    const bool cat = h->dist == PPO_ACT_CATEGORICAL;
-    if (a.mask && !cat && !multi) return fail(h, "policy step: an action mask needs a categorical handle");
-    if (h->bf.on) {
-        ++h->kv[multi ? (a.mask ? KV_BF16_STEP_MCAT_MASK : KV_BF16_STEP_MCAT) : a.mask ? KV_BF16_STEP_CAT_MASK : cat ? KV_BF16_STEP_CAT : KV_BF16_STEP];
-        return launch_step_bf16(h, a);
-    }
+template <bool STOP, int KP0, int HP, int AP, int LL, class T>
+static auto nw_train_fn(T) {
+    if constexpr (STOP && T::multi) return narrow_train_stop_multi_kernel<KP0, HP, AP, LL, T::mask>;
+    else if constexpr (STOP) return narrow_train_stop_kernel<KP0, HP, AP, LL, T::cat, T::mask>;
+    else if constexpr (T::multi) return narrow_train_kernel<KP0, HP, AP, LL, false, false, true, T::mask, true>;
+    else return narrow_train_kernel<KP0, HP, AP, LL, false, false, T::cat, T::mask>;
+}
+template <int KP0, int HP, int AP, int LL, class T>
+static auto nw_host_step_fn(T) {
+    if constexpr (T::multi) return narrow_host_step_kernel<KP0, HP, AP, LL, true, T::mask, true>;
+    else if constexpr (T::cat) return narrow_host_step_kernel<KP0, HP, AP, LL, true, T::mask>;
+    else return narrow_host_step_kernel<KP0, HP, AP, LL>;
+}
+
+int launch_step(ppo_handle* h, const StepArgs& a0) {
+    const Head hd = head_of(h, a0.mask != nullptr);                 // (a multi-categorical handle: bf16 only when created with PPO_ACT_BF16_MULTI_HEAD; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
+    if (a0.mask && !hd.cat) return fail(h, "policy step: an action mask needs a categorical handle");
+    ++h->kv[kHeadVariant[h->bf.on ? KF_BF16_STEP : !h->narrow ? KF_POLICY_STEP : h->nw_static ? KF_NARROW_STEP_STATIC : KF_NARROW_STEP][hd.index()]];
+    if (h->bf.on) return launch_step_bf16(h, a0);
     ProfScope ps(h, PK_STEP);
-    if (nw_mcat(h)) {
-        ++h->kv[a.mask ? KV_NARROW_STEP_MCAT_MASK : KV_NARROW_STEP_MCAT];
-        if (a.mask) launch_narrow_step_multi<true>(h, a); else launch_narrow_step_multi<false>(h, a);
-    } else if (h->narrow) {                                       // (a categorical handle here: created with PPO_ACT_SHAPE_KERNELS)
-        ++h->kv[a.mask ? KV_NARROW_STEP_CAT_MASK : cat ? KV_NARROW_STEP_CAT : h->nw_static ? KV_NARROW_STEP_STATIC : KV_NARROW_STEP];
-        if (a.mask) launch_narrow_step<true, true>(h, a); else if (cat) launch_narrow_step<true, false>(h, a); else launch_narrow_step<false, false>(h, a);
-    } else {
-        if (multi) ++h->kv[a.mask ? KV_POLICY_STEP_MCAT_MASK : KV_POLICY_STEP_MCAT];
-        else ++h->kv[a.mask ? KV_POLICY_STEP_CAT_MASK : cat ? KV_POLICY_STEP_CAT : KV_POLICY_STEP];
-        if (multi) { if (a.mask) launch_step_t<true, true, true>(h, a); else launch_step_t<true, false, true>(h, a); }
-        else if (a.mask) launch_step_t<true, true>(h, a); else if (cat) launch_step_t<true, false>(h, a); else launch_step_t<false, false>(h, a);
-    }
+    with_head(hd, [&](auto H) {
+        auto a = head_args<StepArgsM>(H, h, a0);
+        if (h->narrow) {                                            // narrow_step_kernel: the packed weight image stands in for the padded parameter vector
+            const dim3 grid((a.n + NW_ROWS - 1) / NW_ROWS, 2);
+            a.theta = h->nw_img;
+            const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
+#define X(p, q, r, s) hipLaunchKernelGGL((nw_step_fn<p, q, r, s>(H)), grid, dim3(NW_THREADS), lds, h->stream, h->net, h->nw, a)
+            NW_DISPATCH(h, X);
+#undef X
+        } else {
+            const dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
+            SET_STAMPS(a.stamps, grid.x <= 256, 4096 * 44);
+            hipLaunchKernelGGL(step_fn(H, ladder_rung(h)), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
+        }
+    });
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1325,35 +1373,25 @@ int enqueue_adam(ppo_handle* h, float* loss_row, int n_sumsq = 0, const float* p
     return 0;
 }
 
-// the [256,256] pair's launches (PAIR_DISPATCH picks the instantiation)
-static void launch_train8(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
-    const unsigned* stop = h->stop;
-#define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL; \
-                        if (kl_gate(h)) hipLaunchKernelGGL((train8_stop_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
-                        else hipLaunchKernelGGL((train8_kernel<KP0, AP>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
-    PAIR_DISPATCH(h, X);
-#undef X
+// the [256,256] pair (PAIR_DISPATCH picks the widths).  train8_kernel / train8_stop_kernel, the picker: the Gaussian head is the two-parameter overload, the
+// categorical ones (a handle created with PPO_ACT_PAIR_KERNELS) the four-parameter one with the same carve and the same dynamic LDS, the multi-categorical ones
+// (ppo_create_multi_ex with the flag) the one that takes the component table, with the action rows' region behind the carve
+template <bool STOP, int KP0, int AP, class T>
+static auto train8_fn(T) {
+    if constexpr (T::multi) { if constexpr (STOP) return train8_stop_kernel<KP0, AP, true, T::mask, true>; else return train8_kernel<KP0, AP, true, T::mask, true>; }
+    else if constexpr (T::cat) { if constexpr (STOP) return train8_stop_kernel<KP0, AP, true, T::mask>; else return train8_kernel<KP0, AP, true, T::mask>; }
+    else { if constexpr (STOP) return train8_stop_kernel<KP0, AP>; else return train8_kernel<KP0, AP>; }
 }
-// its categorical forms (a handle created with PPO_ACT_PAIR_KERNELS): the same carve, the same dynamic LDS
-template <bool MASK>
-static void launch_train8_cat(ppo_handle* h, dim3 grid, const TrainArgs& ta) {
+template <int KP0, int AP, class T>
+constexpr size_t train8_lds_floats(T) { return T::multi ? T8L<KP0, AP>::TOTAL_M : T8L<KP0, AP>::TOTAL; }
+
+template <class T>
+static void launch_train8(T H, ppo_handle* h, dim3 grid, const TrainArgs& ta0) {
+    const auto ta = head_args<TrainArgsM>(H, h, ta0);
     const unsigned* stop = h->stop;
-#define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL; \
-                        if (kl_gate(h)) hipLaunchKernelGGL((train8_stop_kernel<KP0, AP, true, MASK>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
-                        else hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
-    PAIR_DISPATCH(h, X);
-#undef X
-}
-// its multi-categorical forms (ppo_create_multi_ex with PPO_ACT_PAIR_KERNELS): the component table rides behind the arguments, the action rows' region behind the carve
-template <bool MASK>
-static void launch_train8_multi(ppo_handle* h, dim3 grid, const TrainArgs& ta0) {
-    TrainArgsM ta;
-    static_cast<TrainArgs&>(ta) = ta0;
-    ta.comp = h->comp;
-    const unsigned* stop = h->stop;
-#define X(KP0, AP) do { const size_t lds = sizeof(float) * T8L<KP0, AP>::TOTAL_M; \
-                        if (kl_gate(h)) hipLaunchKernelGGL((train8_stop_kernel<KP0, AP, true, MASK, true>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
-                        else hipLaunchKernelGGL((train8_kernel<KP0, AP, true, MASK, true>), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
+#define X(KP0, AP) do { const size_t lds = sizeof(float) * train8_lds_floats<KP0, AP>(H); \
+                        if (kl_gate(h)) hipLaunchKernelGGL((train8_fn<true, KP0, AP>(H)), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta, stop); \
+                        else hipLaunchKernelGGL((train8_fn<false, KP0, AP>(H)), grid, dim3(T8_THREADS), lds, h->stream, h->net, ta); } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
 }
@@ -1367,23 +1405,21 @@ static void launch_dw2(ppo_handle* h, const Dw2Args& da, bool peer) {
     PAIR_DISPATCH(h, X);
 #undef X
 }
-// the dynamic LDS of the handle's three pair kernels (ppo_create_ex)
+// the dynamic LDS of the handle's pair kernels (ppo_create_ex): the three assemblies and, for the Gaussian head and every head the handle can launch, train8_fn's two
 static bool set_lds_pair(const ppo_handle* h) {
     bool ok = true;
-    auto set = [&](const void* f, size_t floats) { ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * floats)) == hipSuccess; };
-#define X(KP0, AP) do { set((const void*)weight_grad_assemble_peer_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
-                        set((const void*)weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); \
-                        set((const void*)weight_grad_assemble_stop_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set((const void*)train8_stop_kernel<KP0, AP>, T8L<KP0, AP>::TOTAL); \
-                        if (h->dist == PPO_ACT_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false>, T8L<KP0, AP>::TOTAL); \
-                                                              set((const void*)train8_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); \
-                                                              set((const void*)train8_stop_kernel<KP0, AP, true, false>, T8L<KP0, AP>::TOTAL); \
-                                                              set((const void*)train8_stop_kernel<KP0, AP, true, true>, T8L<KP0, AP>::TOTAL); } \
-                        if (h->dist == PPO_ACT_MULTI_CATEGORICAL) { set((const void*)train8_kernel<KP0, AP, true, false, true>, T8L<KP0, AP>::TOTAL_M); \
-                                                                    set((const void*)train8_kernel<KP0, AP, true, true, true>, T8L<KP0, AP>::TOTAL_M); \
-                                                                    set((const void*)train8_stop_kernel<KP0, AP, true, false, true>, T8L<KP0, AP>::TOTAL_M); \
-                                                                    set((const void*)train8_stop_kernel<KP0, AP, true, true, true>, T8L<KP0, AP>::TOTAL_M); } } while (0)
+    auto set = [&](auto f, size_t floats) { ok = ok && hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * floats)) == hipSuccess; };
+    auto heads = [&](auto H) {
+#define X(KP0, AP) do { set(train8_fn<false, KP0, AP>(H), train8_lds_floats<KP0, AP>(H)); set(train8_fn<true, KP0, AP>(H), train8_lds_floats<KP0, AP>(H)); } while (0)
+        PAIR_DISPATCH(h, X);
+#undef X
+    };
+#define X(KP0, AP) do { set(weight_grad_assemble_peer_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); set(weight_grad_assemble_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); \
+                        set(weight_grad_assemble_stop_kernel<KP0, AP>, Dw2L<KP0, AP>::LDS_FLOATS); } while (0)
     PAIR_DISPATCH(h, X);
 #undef X
+    if (h->dist != PPO_ACT_GAUSSIAN) heads(GaussHead{});
+    for_each_head(h, heads);
     return ok;
 }
 
@@ -1510,9 +1546,9 @@ static int bf16_reduce_adam(ppo_handle* h, const ReduceArgs& ra, int n_old, floa
 
 static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool bucketed, AdamParts& parts) {
     const int Rp = ru(ta.n, GB_PAD);
-    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;        // (PPO_ACT_BF16_MULTI_HEAD, ppo_create_multi_ex)
-    if (ta.mask && h->dist != PPO_ACT_CATEGORICAL && !multi) return fail(h, "train step: an action mask needs a categorical handle");
-    ++h->kv[multi ? (ta.mask ? KV_BF16_TRAIN_MCAT_MASK : KV_BF16_TRAIN_MCAT) : ta.mask ? KV_BF16_TRAIN_CAT_MASK : h->dist == PPO_ACT_CATEGORICAL ? KV_BF16_TRAIN_CAT : KV_BF16_TRAIN];
+    const Head hd = head_of(h, ta.mask != nullptr);                 // (a multi-categorical handle: PPO_ACT_BF16_MULTI_HEAD, ppo_create_multi_ex)
+    if (ta.mask && !hd.cat) return fail(h, "train step: an action mask needs a categorical handle");
+    ++h->kv[kHeadVariant[KF_BF16_TRAIN][hd.index()]];
     h->bf.lazy.enqueued.on = false;
     if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
     { ProfScope ps(h, PK_TRAIN_FB); if (bf16_train_fwd_bwd(h, ta, Rp)) return -1; }
@@ -1529,31 +1565,25 @@ static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool 
     return 0;
 }
 
-// narrow_train_kernel: LAZY (the previous step's clip + Adam in the prologue) exists for the static shapes only
-template <bool LAZY, bool EXACT, bool CAT, bool MASK>
-static void launch_narrow_train(ppo_handle* h, int groups, const NwTrainArgs& na, const NwLazyArgs& z) {
+// narrow_train_kernel with the step's own Adam behind it, any head: the stop form with target-KL early stopping on.  (Only the forms that can defer take NwLazyArgs.)
+template <class T>
+static void launch_narrow_train(T H, ppo_handle* h, int groups, const NwTrainArgs& na0) {
     const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, LAZY, EXACT, CAT, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, z)
-#define XS(a, b, c, d) hipLaunchKernelGGL((narrow_train_stop_kernel<a, b, c, d, CAT, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, (const unsigned*)h->stop)
-    if constexpr (LAZY) { if (h->net.Kp0 == 32) X(32, 64, 32, 2); else X(64, 64, 32, 2); }      // (never with target-KL early stopping on: enqueue_update does not defer then)
-    else if (kl_gate(h)) NW_DISPATCH(h, XS);
-    else NW_DISPATCH(h, X);
-#undef XS
+    const dim3 grid(groups, 2), blk(NW_THREADS);
+    const auto na = head_args<NwTrainArgsM>(H, h, na0);
+    const unsigned* stop = h->stop;
+#define X(a, b, c, d) do { if (kl_gate(h)) hipLaunchKernelGGL((nw_train_fn<true, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na, stop); \
+                           else if constexpr (T::multi) hipLaunchKernelGGL((nw_train_fn<false, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na); \
+                           else hipLaunchKernelGGL((nw_train_fn<false, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na, NwLazyArgs{}); } while (0)
+    NW_DISPATCH(h, X);
 #undef X
 }
-
-// its multi-categorical forms (never deferred): the component table rides behind the arguments
-template <bool MASK>
-static void launch_narrow_train_multi(ppo_handle* h, int groups, const NwTrainArgs& na0) {
+// ... with the previous step's clip + Adam in its prologue (LAZY): the Gaussian head on the static shapes only, never with target-KL early stopping on (enqueue_update does not defer then)
+template <bool EXACT>
+static void launch_narrow_train_lazy(ppo_handle* h, int groups, const NwTrainArgs& na, const NwLazyArgs& z) {
     const size_t lds = (size_t)h->nw.lds_total * sizeof(float);
-    NwTrainArgsM na;
-    static_cast<NwTrainArgs&>(na) = na0;
-    na.comp = h->comp;
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, false, false, true, MASK, true>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na)
-#define XS(a, b, c, d) hipLaunchKernelGGL((narrow_train_stop_multi_kernel<a, b, c, d, MASK>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, (const unsigned*)h->stop)
-    if (kl_gate(h)) NW_DISPATCH(h, XS);
-    else NW_DISPATCH(h, X);
-#undef XS
+#define X(a, b, c, d) hipLaunchKernelGGL((narrow_train_kernel<a, b, c, d, true, EXACT>), dim3(groups, 2), dim3(NW_THREADS), lds, h->stream, h->net, h->nw, na, z)
+    if (h->net.Kp0 == 32) X(32, 64, 32, 2); else X(64, 64, 32, 2);
 #undef X
 }
 
@@ -1564,23 +1594,18 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
         NwTrainArgs na{h->nw_img, ta.obs, ta.actions, ta.advs, ta.returns, ta.old_values, ta.old_neglogp, h->hyper, ta.n, ta.inv_n,
                        h->nw_partials, groups, h->nw_stride, nullptr, ta.mask};
         SET_STAMPS(na.stamps, true, 0);
-        NwLazyArgs z{};
-        ++h->kv[nw_mcat(h) ? (ta.mask ? KV_NARROW_TRAIN_MCAT_MASK : KV_NARROW_TRAIN_MCAT) : nw_cat(h) ? (ta.mask ? KV_NARROW_TRAIN_CAT_MASK : KV_NARROW_TRAIN_CAT) :
-                h->nw_static ? KV_NARROW_TRAIN_STATIC : KV_NARROW_TRAIN];
-        if (nw_mcat(h)) { if (na.mask) launch_narrow_train_multi<true>(h, groups, na); else launch_narrow_train_multi<false>(h, groups, na); }
-        else if (nw_cat(h)) {                                          // (never deferred: nw_lazy is a Gaussian handle's)
-            if (na.mask) launch_narrow_train<false, false, true, true>(h, groups, na, z); else launch_narrow_train<false, false, true, false>(h, groups, na, z);
-        }
-        else if (h->nw_pending) {
+        const Head hd = head_of(h, ta.mask != nullptr);
+        ++h->kv[kHeadVariant[h->nw_static ? KF_NARROW_TRAIN_STATIC : KF_NARROW_TRAIN][hd.index()]];
+        if (!hd.cat && h->nw_pending) {                                // (a discrete head never defers: nw_lazy is a Gaussian handle's)
             // the previous step's clip + Adam rides in this launch: read set nw_cur, write the other one
             float* set[2][3] = {{h->theta, h->adam_m, h->adam_v}, {h->nw_theta1, h->nw_m1, h->nw_v1}};
             const int ci = h->nw_cur, co = ci ^ 1;
-            z = NwLazyArgs{h->grad, h->sumsq, h->nw_pending_parts, set[ci][0], set[ci][1], set[ci][2], set[co][0], set[co][1], set[co][2], h->beta_pow,
-                           h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm, h->nw_pending_loss, h->norm_out};
-            if (h->adam_exact) launch_narrow_train<true, true, false, false>(h, groups, na, z); else launch_narrow_train<true, false, false, false>(h, groups, na, z);
+            const NwLazyArgs z{h->grad, h->sumsq, h->nw_pending_parts, set[ci][0], set[ci][1], set[ci][2], set[co][0], set[co][1], set[co][2], h->beta_pow,
+                               h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->cfg.max_grad_norm, h->nw_pending_loss, h->norm_out};
+            if (h->adam_exact) launch_narrow_train_lazy<true>(h, groups, na, z); else launch_narrow_train_lazy<false>(h, groups, na, z);
             h->nw_cur = co; h->nw_pending = false;
         }
-        else launch_narrow_train<false, false, false, false>(h, groups, na, z);
+        else with_head(hd, [&](auto H) { launch_narrow_train(H, h, groups, na); });
         HIP_OK(h, hipGetLastError());
     }
     const int n_chunks = h->P_pad / 64;
@@ -1593,40 +1618,17 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
     return 0;
 }
 
-// train_fwd_bwd_kernel: the (CT, KS, CTH, WIDE, EARLY) ladder of the handle's layout, once; the caller picks the head
-template <bool CAT, bool MASK, bool MULTI = false>
-static void launch_train_fb(ppo_handle* h, dim3 grid, const TrainArgs& ta0) {
-    const size_t lds = (size_t)h->net.lds_total * sizeof(float);
-    std::conditional_t<MULTI, TrainArgsM, TrainArgs> ta;
-    static_cast<TrainArgs&>(ta) = ta0;
-    if constexpr (MULTI) ta.comp = h->comp;
-#define X(CT, KS, CTH, WIDE, EARLY) hipLaunchKernelGGL((train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, CAT, MASK, MULTI>), grid, dim3(BLOCK_THREADS), lds, h->stream, h->net, ta)
-    if (h->net.wide) { if (h->CT == 4) X(4, 2, 0, true, false); else X(1, 1, 0, true, false); }
-    else if (h->CT == 4 && h->CTH == 2 && h->early) X(4, 2, 2, false, true);
-    else if (h->CT == 4 && h->CTH == 2) X(4, 2, 2, false, false);
-    else if (h->CT == 4) X(4, 2, 0, false, false);
-    else X(1, 1, 0, false, false);
-#undef X
-}
-
-// fp32 forward + loss + backward over n_pad rows (the kernels zero-fill the rows of their last partial tile)
+// fp32 forward + loss + backward over n_pad rows (the kernels zero-fill the rows of their last partial tile): train8_kernel where the handle has it (t8: not wide;
+// a categorical or multi-categorical handle only with PPO_ACT_PAIR_KERNELS: ppo_create_ex / ppo_create_multi_ex), else train_fwd_bwd_kernel on the handle's rung
 static int enqueue_train_fb(ppo_handle* h, const TrainArgs& ta, int n_pad) {
     ProfScope ps(h, PK_TRAIN_FB);
     const dim3 grid(n_pad / ROWS_PER_BLOCK, 2);
-    const bool cat = h->dist == PPO_ACT_CATEGORICAL;              // (a mask: a categorical handle, the entry points check; t8: not wide, Gaussian or categorical with PPO_ACT_PAIR_KERNELS, ppo_create_ex)
-    const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL;
-    const bool cat8 = cat && h->t8, multi8 = multi && h->t8;      // (a multi-categorical handle: t8 only with PPO_ACT_PAIR_KERNELS, ppo_create_multi_ex)
-    if (multi8) ++h->kv[ta.mask ? KV_TRAIN8_MCAT_MASK : KV_TRAIN8_MCAT];
-    else if (multi) ++h->kv[ta.mask ? KV_TRAIN_FB_MCAT_MASK : KV_TRAIN_FB_MCAT];
-    else if (cat8) ++h->kv[ta.mask ? KV_TRAIN8_CAT_MASK : KV_TRAIN8_CAT];
-    else ++h->kv[ta.mask ? KV_TRAIN_FB_CAT_MASK : cat ? KV_TRAIN_FB_CAT : h->t8 ? KV_TRAIN8 : KV_TRAIN_FB];
-    if (multi8) { if (ta.mask) launch_train8_multi<true>(h, grid, ta); else launch_train8_multi<false>(h, grid, ta); }
-    else if (multi) { if (ta.mask) launch_train_fb<true, true, true>(h, grid, ta); else launch_train_fb<true, false, true>(h, grid, ta); }
-    else if (cat8) { if (ta.mask) launch_train8_cat<true>(h, grid, ta); else launch_train8_cat<false>(h, grid, ta); }
-    else if (ta.mask) launch_train_fb<true, true>(h, grid, ta);
-    else if (cat) launch_train_fb<true, false>(h, grid, ta);
-    else if (h->t8) launch_train8(h, grid, ta);
-    else launch_train_fb<false, false>(h, grid, ta);
+    const Head hd = head_of(h, ta.mask != nullptr);               // (a mask: a categorical handle, the entry points check)
+    ++h->kv[kHeadVariant[h->t8 ? KF_TRAIN8 : KF_TRAIN_FB][hd.index()]];
+    with_head(hd, [&](auto H) {
+        if (h->t8) launch_train8(H, h, grid, ta);
+        else hipLaunchKernelGGL(train_fb_fn(H, ladder_rung(h)), grid, dim3(BLOCK_THREADS), (size_t)h->net.lds_total * sizeof(float), h->stream, h->net, head_args<TrainArgsM>(H, h, ta));
+    });
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1922,39 +1924,13 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     // hardware maximum (160 KB) so that a later, narrower handle cannot lower the limit under a live wider one.
     const int lds_bytes = 160 * 1024;
     bool attr_ok = true;
-    auto set_lds = [&](const void* f) { attr_ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess; };
-    set_lds((const void*)policy_step_kernel<4, 2, 2, false>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false>);
-    set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, true>);
+    auto set_lds = [&](auto f) { attr_ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess; };
     { const NetDev& nn = h->net;
       h->early = !nn.wide && h->CT == 4 && h->CTH == 2 && nn.L >= 2 && nn.Kp0 == 32 && nn.Ap == 32 && nn.Hp[0] == 256 && nn.Hp[nn.L - 1] == 256; }
-    set_lds((const void*)policy_step_kernel<4, 2, 0, false>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, false>);
-    set_lds((const void*)policy_step_kernel<1, 1, 0, false>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false>);
-    set_lds((const void*)policy_step_kernel<4, 2, 0, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true>);
-    set_lds((const void*)policy_step_kernel<1, 1, 0, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true>);
-    if (h->dist == PPO_ACT_CATEGORICAL) {
-        set_lds((const void*)policy_step_kernel<4, 2, 2, false, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, false, true>);
-        set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, true, true>);
-        set_lds((const void*)policy_step_kernel<4, 2, 0, false, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, false, false, true>);
-        set_lds((const void*)policy_step_kernel<1, 1, 0, false, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false, false, true>);
-        set_lds((const void*)policy_step_kernel<4, 2, 0, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true, false, true>);
-        set_lds((const void*)policy_step_kernel<1, 1, 0, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true, false, true>);
-        // ... and their action-mask forms (ppo_step_masked / ppo_set_action_masking)
-        set_lds((const void*)policy_step_kernel<4, 2, 2, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, false, true, true>);
-        set_lds((const void*)train_fwd_bwd_kernel<4, 2, 2, false, true, true, true>);
-        set_lds((const void*)policy_step_kernel<4, 2, 0, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, false, false, true, true>);
-        set_lds((const void*)policy_step_kernel<1, 1, 0, false, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, false, false, true, true>);
-        set_lds((const void*)policy_step_kernel<4, 2, 0, true, true, true>); set_lds((const void*)train_fwd_bwd_kernel<4, 2, 0, true, false, true, true>);
-        set_lds((const void*)policy_step_kernel<1, 1, 0, true, true, true>); set_lds((const void*)train_fwd_bwd_kernel<1, 1, 0, true, false, true, true>);
-    }
-    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) {
-        // every (CT, KS, CTH, WIDE[, EARLY]) combination of launch_step_t / launch_train_fb, unmasked and masked
-#define XS(CT, KS, CTH, WIDE) do { set_lds((const void*)policy_step_kernel<CT, KS, CTH, WIDE, true, false, true>); set_lds((const void*)policy_step_kernel<CT, KS, CTH, WIDE, true, true, true>); } while (0)
-#define XT(CT, KS, CTH, WIDE, EARLY) do { set_lds((const void*)train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, true, false, true>); set_lds((const void*)train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, true, true, true>); } while (0)
-        XS(4, 2, 2, false); XS(4, 2, 0, false); XS(1, 1, 0, false); XS(4, 2, 0, true); XS(1, 1, 0, true);
-        XT(4, 2, 2, false, true); XT(4, 2, 2, false, false); XT(4, 2, 0, false, false); XT(1, 1, 0, false, false); XT(4, 2, 0, true, false); XT(1, 1, 0, true, false);
-#undef XS
-#undef XT
-    }
+    // every rung of the ladder (not only the handle's), for the Gaussian head and every head this handle can launch
+    auto lds_opt_in = [&](auto H) { for (int r = 0; r < RUNG_COUNT; ++r) { set_lds(step_fn(H, r)); set_lds(train_fb_fn(H, r)); } };
+    if (h->dist != PPO_ACT_GAUSSIAN) lds_opt_in(GaussHead{});
+    for_each_head(h, lds_opt_in);
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
     if (!attr_ok) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); return bail(0); }
@@ -2005,32 +1981,22 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (h->bf.on && bf16_create(h)) return bail(0);
     if (h->narrow) {
         attr_ok = true;
-        auto big_lds = [&](const void* f) { attr_ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
-        // the train kernels launched while target-KL early stopping is on (ppo_set_target_kl): every head this handle can have
-#define XS(a, b, c, d) do { if (nw_mcat(h)) { big_lds((const void*)narrow_train_stop_multi_kernel<a, b, c, d, false>); big_lds((const void*)narrow_train_stop_multi_kernel<a, b, c, d, true>); } \
-                            else if (nw_cat(h)) { big_lds((const void*)narrow_train_stop_kernel<a, b, c, d, true, false>); big_lds((const void*)narrow_train_stop_kernel<a, b, c, d, true, true>); } \
-                            else big_lds((const void*)narrow_train_stop_kernel<a, b, c, d, false, false>); } while (0)
-        XS(0, 0, 0, 0); XS(32, 64, 32, 2); XS(64, 64, 32, 2);
-#undef XS
-#define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d>); big_lds((const void*)narrow_step_kernel<a, b, c, d>); big_lds((const void*)narrow_collect_kernel<a, b, c, d>); \
-                           big_lds((const void*)narrow_rollout_kernel<a, b, c, d, false>); big_lds((const void*)narrow_rollout_kernel<a, b, c, d, true>); \
-                           big_lds((const void*)narrow_rollout_coop_kernel<a, b, c, d>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d>); } while (0)
+        auto big_lds = [&](auto f) { attr_ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
+        // the kernels with a head, every shape: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl), host step -- for the
+        // Gaussian head and every head this handle can launch
+        auto nw_heads = [&](auto H) {
+#define X(a, b, c, d) do { big_lds(nw_step_fn<a, b, c, d>(H)); big_lds(nw_train_fn<false, a, b, c, d>(H)); big_lds(nw_train_fn<true, a, b, c, d>(H)); \
+                           big_lds(nw_host_step_fn<a, b, c, d>(H)); } while (0)
+            X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
+#undef X
+        };
+        if (!nw_gauss(h)) nw_heads(GaussHead{});
+        for_each_head(h, nw_heads);
+        // the kernels without a head axis
+#define X(a, b, c, d) do { big_lds(narrow_collect_kernel<a, b, c, d>); big_lds(narrow_rollout_kernel<a, b, c, d, false>); big_lds(narrow_rollout_kernel<a, b, c, d, true>); \
+                           big_lds(narrow_rollout_coop_kernel<a, b, c, d>); } while (0)
         X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
-        if (nw_cat(h)) {
-#define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true>); \
-                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true>); \
-                           big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, false>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, true>); } while (0)
-            X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
-#undef X
-        }
-        if (nw_mcat(h)) {
-#define X(a, b, c, d) do { big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, false, true>); big_lds((const void*)narrow_train_kernel<a, b, c, d, false, false, true, true, true>); \
-                           big_lds((const void*)narrow_step_kernel<a, b, c, d, true, false, true>); big_lds((const void*)narrow_step_kernel<a, b, c, d, true, true, true>); \
-                           big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, false, true>); big_lds((const void*)narrow_host_step_kernel<a, b, c, d, true, true, true>); } while (0)
-            X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
-#undef X
-        }
         big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true>);
         big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true, true>);
         big_lds((const void*)narrow_epoch_kernel<32, false>); big_lds((const void*)narrow_epoch_kernel<64, false>);
@@ -2717,7 +2683,7 @@ static bool host_fused_discrete(const ppo_handle* h);           // (with the for
 int ppo_set_host_step_fused(ppo_handle* h, int32_t on) {
     if (!h) return fail(nullptr, "ppo_set_host_step_fused: null handle");
     if ((on != 0) == h->host_step_fused) return 0;
-    if (nw_cat(h) || nw_mcat(h)) {
+    if (nw_discrete(h)) {
         // the rollout belongs to the old form (a posted transition, the pinned mask block): dropped, as ppo_set_action_masking does
         ENTER_Q(h);                                                 // (a posted transition is booked first)
         HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -2869,7 +2835,7 @@ static size_t one_group_lds(const ppo_handle* h) { return ((size_t)h->nw.lds_tot
 // the handle runs the per-step form, silently.  Such a handle never takes a resident form: those keep a Gaussian head and have no channel for a per-step mask.
 static bool host_fused_discrete(const ppo_handle* h) {
     const NetDev& n = h->net;
-    return h->host_step_fused && (nw_cat(h) || nw_mcat(h)) && !h->opt_no_host_fused && !h->comm && h->E <= NW_ROWS && n.O <= 64 && n.A <= 64 && h->pin_flag &&
+    return h->host_step_fused && nw_discrete(h) && !h->opt_no_host_fused && !h->comm && h->E <= NW_ROWS && n.O <= 64 && n.A <= 64 && h->pin_flag &&
            one_group_lds(h) <= 160 * 1024;
 }
 
@@ -2948,28 +2914,25 @@ static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_
     q.seed = h->rng_seed; q.rng_step = rng_step; q.row_base = (uint32_t)(h->rank * h->E);
     const size_t lds = one_group_lds(h);
     ProfScope ps(h, PK_STEP);
-    if (nw_gauss(h)) {
-#define X(a, b, c, d) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, d>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q)
-        NW_DISPATCH(h, X);
+    const Head hd = head_of(h, masked);
+    if (act && hd.cat) ++h->kv[kHeadVariant[KF_NARROW_HOST_STEP][hd.index()]];
+    with_head(hd, [&](auto H) {
+        auto launch = [&](const auto& args) {
+#define X(a, b, c, d) hipLaunchKernelGGL((nw_host_step_fn<a, b, c, d>(H)), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, args)
+            NW_DISPATCH(h, X);
 #undef X
-    } else {
-        // the discrete forms: the mask block and row t of the mask buffer behind the arguments above, the component table behind those
-        const bool multi = nw_mcat(h);
-        NwHostStepArgsDM d{};
-        static_cast<NwHostStepArgs&>(d) = q;
-        d.host_mask = masked ? h->pin_mask_dev : nullptr;
-        d.ro_mask = (act && h->masking) ? h->ro_mask + t * E * n.A : nullptr;
-        d.Aw = h->Aw;
-        d.comp = h->comp;
-        const NwHostStepArgsD& dc = d;
-        if (act) ++h->kv[multi ? (masked ? KV_NARROW_HOST_STEP_MCAT_MASK : KV_NARROW_HOST_STEP_MCAT) : (masked ? KV_NARROW_HOST_STEP_CAT_MASK : KV_NARROW_HOST_STEP_CAT)];
-#define X(a, b, c, e) do { if (multi) { if (masked) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, true, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, d); \
-                                        else hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, false, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, d); } \
-                           else if (masked) hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, dc); \
-                           else hipLaunchKernelGGL((narrow_host_step_kernel<a, b, c, e, true, false>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, dc); } while (0)
-        NW_DISPATCH(h, X);
-#undef X
-    }
+        };
+        if constexpr (!decltype(H)::cat) launch(q);
+        else {
+            // the discrete forms: the mask block and row t of the mask buffer behind the arguments above, the component table (multi-categorical) behind those
+            NwHostStepArgsD d{};
+            static_cast<NwHostStepArgs&>(d) = q;
+            d.host_mask = masked ? h->pin_mask_dev : nullptr;
+            d.ro_mask = (act && h->masking) ? h->ro_mask + t * E * n.A : nullptr;
+            d.Aw = h->Aw;
+            launch(head_args<NwHostStepArgsDM>(H, h, d));
+        }
+    });
     HIP_OK(h, hipGetLastError());
     h->host_pending = false;
     return 0;

@@ -18,8 +18,12 @@ SWITCHES = ("PPO_HIP_NO_ROLLOUT1", "PPO_HIP_NO_PERSISTENT_COLLECT", "PPO_HIP_NO_
 UNSET = ("PPO_HIP_DIRECT_ACT_MAX_BLOCKS", "PPO_HIP_HOST_POLLS")
 
 
-def case(side, hidden, E, O=18, env=(), noise=False, dist="gaussian", masking=False, mask=False):
-    return dict(side=side, hidden=hidden, E=E, O=O, env=tuple(env), noise=noise, dist=dist, masking=masking, mask=mask)
+NVEC = (3, 5, 4, 6)                                                    # the multi-categorical cases' components: sum = the A = 18 of every case
+
+
+def case(side, hidden, E, O=18, env=(), noise=False, dist="gaussian", masking=False, mask=False, shape_kernels=False, host_fused=False):
+    return dict(side=side, hidden=hidden, E=E, O=O, env=tuple(env), noise=noise, dist=dist, masking=masking, mask=mask,
+                nvec=NVEC if dist == "multi_categorical" else None, shape_kernels=shape_kernels, host_fused=host_fused)
 
 
 CASES = {
@@ -47,6 +51,18 @@ CASES = {
     "host_cat_masking_256_e16_mask": case("host", (256, 256), 16, dist="categorical", masking=True, mask=True),
     "host_cat_masking_256_e16_plain": case("host", (256, 256), 16, dist="categorical", masking=True),
 }
+# the head forms the table above does not reach (recorded before the launch sites' head dispatch was gathered in one place).  Kept apart from CASES:
+# tests/test_counter_draws.py derives its rollouts from CASES, and its draw model knows the heads above only.
+HEAD_CASES = {
+    # ---- a multi-categorical [256,256] handle ----
+    "dev_mcat_256_e16": case("dev", (256, 256), 16, dist="multi_categorical"),
+    "host_mcat_256_e16": case("host", (256, 256), 16, dist="multi_categorical"),
+}
+# ---- host Env, set_host_step_fused on a narrow discrete handle: one launch per env step ----
+for _d, _n in (("categorical", "cat"), ("multi_categorical", "mcat")):
+    HEAD_CASES["host_fused_%s_e8" % _n] = case("host", (64, 64), 8, dist=_d, shape_kernels=True, host_fused=True)
+    HEAD_CASES["host_fused_%s_e8_mask" % _n] = case("host", (64, 64), 8, dist=_d, shape_kernels=True, host_fused=True, masking=True, mask=True)
+ALL_CASES = dict(CASES, **HEAD_CASES)
 
 FIELDS = ("obs", "actions", "values", "neglogp", "rewards", "returns", "dones")
 
@@ -64,9 +80,11 @@ def run_case(c, rollouts=1, outputs=False):
     The switches are read from the environment: set_switches first."""
     import ppo_cpp_amd
     E, O, A = c["E"], c["O"], 18
-    g = ppo_cpp_amd.PPOHip(O, A, list(c["hidden"]), action_dist=c["dist"])
+    g = ppo_cpp_amd.PPOHip(O, A, list(c["hidden"]), action_dist=c["dist"], nvec=c["nvec"], shape_kernels=c["shape_kernels"])
     try:
         g.init_orthogonal(0)
+        if c["host_fused"]:
+            g.set_host_step_fused(True)
         if c["masking"]:
             g.set_action_masking(True)
         g.norm_init(E); g.rollout_alloc(E, T); g.seed(99)
@@ -81,11 +99,13 @@ def run_case(c, rollouts=1, outputs=False):
             else:
                 for t in range(T):
                     noise = rng.normal(size=(E, A)).astype(np.float32) if c["noise"] else None
-                    if c["dist"] == "categorical" and noise is not None:
+                    if c["dist"] != "gaussian" and noise is not None:
                         noise = rng.uniform(0.01, 0.99, (E, A)).astype(np.float32)
                     mask = None
                     if c["mask"]:
                         mask = (rng.uniform(size=(E, A)) < 0.6).astype(np.float32); mask[:, 0] = 1.0
+                        if c["nvec"]:
+                            mask[:, np.cumsum(c["nvec"][:-1])] = 1.0    # an open category in every component
                     g.rollout_act(t, noise, mask=mask)
                     g.rollout_observe(t, rng.uniform(-1, 1, (E, O)).astype(np.float32), rng.uniform(-1, 1, E).astype(np.float32),
                                       (rng.uniform(size=E) < 0.1).astype(np.float32))
@@ -106,14 +126,14 @@ def run_case(c, rollouts=1, outputs=False):
 
 def test_the_table_names_every_case():
     table = json.load(open(GOLDEN))
-    assert table["T"] == T and sorted(table["cases"]) == sorted(CASES)
+    assert table["T"] == T and sorted(table["cases"]) == sorted(ALL_CASES)
     assert len(table["parent"]) == 40
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
+@pytest.mark.parametrize("name", sorted(ALL_CASES))
 def test_rollout_form_kernel_counts(name, monkeypatch):
     want = json.load(open(GOLDEN))["cases"][name]
-    set_switches(CASES[name], monkeypatch.setenv, lambda s: monkeypatch.delenv(s, raising=False))
-    got, _ = run_case(CASES[name])
+    set_switches(ALL_CASES[name], monkeypatch.setenv, lambda s: monkeypatch.delenv(s, raising=False))
+    got, _ = run_case(ALL_CASES[name])
     print(name, got)
     assert got == want, (name, got, want)

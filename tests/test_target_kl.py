@@ -2,7 +2,9 @@
 
 A train step whose approxkl (losses[3]) exceeds 1.5 * target_kl is not applied and ends its ppo_update; the decision is taken on the device, in adam_kernel.  The
 reference is tests/target_kl_ref.py: the update as a manual minibatch loop over the oracle's pieces that stops before the Adam step.  Four handles: the generic
-Gaussian (4,5), the narrow Gaussian (64,64), the (256,256) pair, and the narrow categorical (64,64) with 6 categories and action masks.
+Gaussian (4,5), the narrow Gaussian (64,64), the (256,256) pair, and the narrow categorical (64,64) with 6 categories and action masks.  The stop forms of the
+other discrete heads (narrow and pair, categorical and multi-categorical, plain and masked) are launched by the two test_discrete_stop_forms_* tests, which need no
+reference: they compare bits with the handle itself.
 
 Tolerances are those of tests/test_hip_parity.py::test_update_phase_matches_oracle (rows rtol 2e-4 / atol 2e-6, theta rtol 2e-4 / atol 5e-6, powers rtol 1e-5;
 its second update: rows rtol 3e-4 / atol 3e-6).  The categorical reference is float64: its clipfrac column may differ by one row of the minibatch, as in
@@ -378,6 +380,99 @@ def test_applied_steps_are_the_ordinary_steps(name, monkeypatch):
     np.testing.assert_array_equal(mean_on.view(np.uint32), mean_off.view(np.uint32))
     same_bits(state(on), state(off), "a limit that never triggers")
     on.close(); off.close()
+
+
+# ---- the stop forms of the discrete heads: bits against the handle itself, no reference model -----------------------------------------
+HEAD_E, HEAD_T, HEAD_EPOCHS, HEAD_NMB = 16, 4, 2, 2
+HEAD_NVEC = (3, 5, 4, 6)
+HEAD_FAMILIES = {"narrow": ((64, 64), "shape_kernels", "narrow_train_kernel"), "pair": ((256, 256), "pair_kernels", "train8_kernel")}
+HEAD_FORMS = {"cat": ("categorical", False), "cat_mask": ("categorical", True), "mcat": ("multi_categorical", False), "mcat_mask": ("multi_categorical", True)}
+HEAD_CASES = [f + "_" + h for f in HEAD_FAMILIES for h in HEAD_FORMS if f + "_" + h != "narrow_cat_mask"]       # (narrow_cat_mask: CASES above)
+_HEAD_ROLLOUTS = {}
+
+
+def head_handle(name):
+    """a fresh handle of the case with its rollout uploaded: rows from a fixed RandomState, actions / values / neglogp from the handle's own act model
+    (computed once per case and shared: every handle of a case starts from the same weights)"""
+    import ppo_cpp_amd
+    family, form = name.split("_", 1)
+    hidden, flag, _ = HEAD_FAMILIES[family]
+    dist, masked = HEAD_FORMS[form]
+    g = ppo_cpp_amd.PPOHip(18, 18, list(hidden), action_dist=dist, nvec=HEAD_NVEC if dist == "multi_categorical" else None, **{flag: True})
+    g.init_orthogonal(0)
+    if masked:
+        g.set_action_masking(True)
+    g.norm_init(HEAD_E)
+    g.rollout_alloc(HEAD_E, HEAD_T)
+    if name not in _HEAD_ROLLOUTS:
+        rng = np.random.RandomState(31)
+        n = HEAD_E * HEAD_T
+        obs = rng.normal(size=(n, 18)).astype(np.float32)
+        mask = None
+        if masked:
+            mask = (rng.uniform(size=(n, 18)) < 0.6).astype(np.float32)
+            mask[:, np.cumsum((0,) + HEAD_NVEC[:-1])] = 1.0                 # an open category in every component (and in the single one)
+        act, val, nlp = g.step(obs, rng.uniform(0.01, 0.99, (n, 18)).astype(np.float32), mask=mask)
+        ro = {"obs": obs, "actions": act, "values": val, "neglogp": nlp, "returns": (val + rng.normal(size=n) * 0.1).astype(np.float32)}
+        if masked:
+            ro["masks"] = mask
+        _HEAD_ROLLOUTS[name] = {k: np.ascontiguousarray(v.reshape((HEAD_T, HEAD_E) + v.shape[1:])) for k, v in ro.items()}
+    for f, v in _HEAD_ROLLOUTS[name].items():
+        g.rollout_set(f, v)
+    return g
+
+
+def head_count(g, name):
+    family, form = name.split("_", 1)
+    return g.kernel_counts()["%s<%s>" % (HEAD_FAMILIES[family][2], form.replace("_", ","))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", HEAD_CASES)
+def test_discrete_stop_forms_apply_the_ordinary_steps(name):
+    """a limit that never triggers (target_kl = 1e30) launches the *_stop_kernel forms of the head and leaves weights, Adam slots and beta powers bitwise those
+    of a fresh handle with the setting off that ran the same update"""
+    total = HEAD_EPOCHS * HEAD_NMB
+    off = head_handle(name)
+    rows_off, _ = off.update(LR, CR, HEAD_EPOCHS, HEAD_NMB, seed=5)
+    on = head_handle(name)
+    on.set_target_kl(1e30)
+    rows_on, _ = on.update(LR, CR, HEAD_EPOCHS, HEAD_NMB, seed=5)
+    assert on.update_applied() == (total, total) and off.update_applied() == (total, total)
+    assert head_count(on, name) == total and head_count(off, name) == total, on.kernel_counts()      # (the flag took effect: the family's own train kernel ran)
+    assert not np.array_equal(off.get_flat(0), head_handle_theta0(name))
+    same_bits(state(on), state(off), "a limit that never triggers")
+    np.testing.assert_array_equal(rows_on.view(np.uint32), rows_off.view(np.uint32))
+    on.close(); off.close()
+
+
+def head_handle_theta0(name):
+    g = head_handle(name)
+    theta = g.get_flat(0)
+    g.close()
+    return theta
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", HEAD_CASES)
+def test_discrete_stop_forms_skip_a_step(name):
+    """the old neglogp shifted by 0.1 (approxkl = 0.005 against a limit of 0.0015), as in test_a_skipped_step_applies_nothing: after one ordinary update, so that
+    the slots are not zeros, the stopped update changes nothing bitwise and reports 0 applied steps"""
+    total = HEAD_EPOCHS * HEAD_NMB
+    g = head_handle(name)
+    g.update(LR, CR, 1, HEAD_NMB, seed=5)
+    assert g.update_applied() == (HEAD_NMB, HEAD_NMB)
+    before = state(g)
+    assert np.abs(before["m"]).max() > 0 and np.abs(before["v"]).max() > 0
+    g.rollout_set("neglogp", (_HEAD_ROLLOUTS[name]["neglogp"] + np.float32(0.1)).astype(np.float32))
+    g.set_target_kl(0.001)
+    rows, _ = g.update(LR, CR, HEAD_EPOCHS, HEAD_NMB, seed=5)
+    print(name, "approxkl", rows[:, 3])
+    assert g.update_applied() == (0, total)
+    assert np.all(np.isfinite(rows[0])) and rows[0, 3] > 0.0015 and np.all(np.isnan(rows[1:])), rows
+    assert head_count(g, name) == HEAD_NMB + total, g.kernel_counts()
+    same_bits(before, state(g), "after the stopped update")
+    g.close()
 
 
 @pytest.mark.gpu

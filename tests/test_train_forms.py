@@ -22,12 +22,16 @@ SWITCHES = ("PPO_HIP_NO_NARROW_EPOCH", "PPO_HIP_NO_NARROW_EPOCH_XL", "PPO_HIP_NO
 UNSET = ("PPO_HIP_NO_NARROW", "PPO_HIP_NO_GRAPH", "PPO_HIP_NO_PEER_TILES", "PPO_HIP_NO_ADAM_MEET", "PPO_HIP_NO_ROLLOUT1", "PPO_HIP_NO_PERSISTENT_COLLECT")
 
 
-def case(hidden, O=18, A=18, E=16, T=4, nmb=2, n=128, env=(), dist="gaussian", shape_kernels=False, masking=False, bf16=False):
-    return dict(hidden=hidden, O=O, A=A, E=E, T=T, nmb=nmb, n=n, env=tuple(env), dist=dist, shape_kernels=shape_kernels, masking=masking, bf16=bf16)
+NVEC = (3, 5, 4, 6)                                                    # the multi-categorical cases' components: sum = the A = 18 of every case
 
 
-def bf16_case(env=()):
-    return case((512, 512), O=64, E=64, T=8, nmb=4, env=env, bf16=True)
+def case(hidden, O=18, A=18, E=16, T=4, nmb=2, n=128, env=(), dist="gaussian", shape_kernels=False, masking=False, bf16=False, pair_kernels=False, bf16_head=False):
+    return dict(hidden=hidden, O=O, A=A, E=E, T=T, nmb=nmb, n=n, env=tuple(env), dist=dist, shape_kernels=shape_kernels, masking=masking, bf16=bf16,
+                nvec=NVEC if dist == "multi_categorical" else None, pair_kernels=pair_kernels, bf16_head=bf16_head)
+
+
+def bf16_case(env=(), **kw):
+    return case((512, 512), O=64, E=64, T=8, nmb=4, env=env, bf16=True, **kw)
 
 
 CASES = {
@@ -60,6 +64,17 @@ CASES = {
     "bf16_adam_fast": bf16_case(env=("PPO_HIP_ADAM_FAST",)),
     "bf16_no_chain": bf16_case(env=("PPO_HIP_NO_BF16_CHAIN",)),
 }
+# ---- every head form of every family that has one, plain and with masking (recorded before the launch sites' head dispatch was gathered in one place) ----
+for _m in (False, True):
+    _s = "_masking" if _m else ""
+    CASES.update({
+        "mcat_256" + _s: case((256, 256), dist="multi_categorical", masking=_m),                                       # the generic fp32 family
+        "pair_cat" + _s: case((256, 256), dist="categorical", pair_kernels=True, masking=_m),                          # the [256,256] pair
+        "pair_mcat" + _s: case((256, 256), dist="multi_categorical", pair_kernels=True, masking=_m),
+        "nw_mcat" + _s: case((64, 64), dist="multi_categorical", shape_kernels=True, masking=_m),                      # narrow
+        "bf16_cat" + _s: bf16_case(dist="categorical", bf16_head=True, masking=_m),                                    # bf16
+        "bf16_mcat" + _s: bf16_case(dist="multi_categorical", bf16_head=True, masking=_m),
+    })
 
 
 def set_switches(c, setenv, delenv):
@@ -75,11 +90,13 @@ def minibatch(g, c):
     rng = np.random.RandomState(11)
     n, O, A = c["n"], c["O"], c["A"]
     obs = rng.normal(size=(n, O)).astype(np.float32)
-    cat = c["dist"] == "categorical"
+    cat = c["dist"] != "gaussian"
     noise = rng.uniform(0.01, 0.99, (n, A)).astype(np.float32) if cat else rng.normal(size=(n, A)).astype(np.float32)
     mask = None
     if c["masking"]:
         mask = (rng.uniform(size=(n, A)) < 0.6).astype(np.float32); mask[:, 0] = 1.0
+        if c["nvec"]:
+            mask[:, np.cumsum(c["nvec"][:-1])] = 1.0                    # an open category in every component
     act, val, nlp = g.step(obs, noise, mask=mask)
     advs = rng.normal(size=n).astype(np.float32)
     returns = (val + rng.normal(size=n) * 0.1).astype(np.float32)
@@ -94,7 +111,8 @@ def run_case(c):
     """{"train_step": delta, "update": delta} of kernel_counts(), non-zero entries only.  The switches are read from the environment: set_switches first."""
     import ppo_cpp_amd
     over = dict(compute_dtype=BF16) if c["bf16"] else {}
-    g = ppo_cpp_amd.PPOHip(c["O"], c["A"], list(c["hidden"]), action_dist=c["dist"], shape_kernels=c["shape_kernels"], **over)
+    g = ppo_cpp_amd.PPOHip(c["O"], c["A"], list(c["hidden"]), action_dist=c["dist"], shape_kernels=c["shape_kernels"], nvec=c["nvec"],
+                           pair_kernels=c["pair_kernels"], bf16_head=c["bf16_head"], **over)
     try:
         g.init_orthogonal(0)
         if c["masking"]:

@@ -27,9 +27,9 @@ def main():
         os.environ.pop(s, None)
 
     table = {"parent": args.commit, "T": F.T, "cases": {}}
-    for name in sorted(F.CASES):
-        F.set_switches(F.CASES[name], os.environ.__setitem__, delenv)
-        table["cases"][name], _ = F.run_case(F.CASES[name])
+    for name in sorted(F.ALL_CASES):
+        F.set_switches(F.ALL_CASES[name], os.environ.__setitem__, delenv)
+        table["cases"][name], _ = F.run_case(F.ALL_CASES[name])
         print(name, table["cases"][name], flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
