@@ -217,12 +217,28 @@ def emu_loss_dlogits_f32(logits, act, adv, old_nlp, cr, ent_coef, mask=None, dro
     return np.where(ok, dl, F(0.0)).astype(F)
 
 
-def check_dlogits(name, q, lo, share_ref, rec=None):
-    """q [n][A]: the device's bf16 d logits as fp32.  Forbidden categories exactly 0; the allowed ones by rules (1) and (2) of tests/bf16_ref.py"""
+def normal_size(lo, normal=0.0):
+    """the allowed d logits of at least `normal` in size (0: every allowed one): the elements rule (2) counts"""
+    return lo["ok"] & (np.abs(lo["dl"]) >= normal)
+
+
+def check_dlogits(name, q, lo, share_ref, rec=None, floor=0.0, normal=0.0):
+    """q [n][A]: the device's bf16 d logits as fp32.  Forbidden categories exactly 0; the allowed ones by rules (1) and (2) of tests/bf16_ref.py.
+    floor, normal (tests/test_head_edges.py: logits spread by hundreds, where exp(a0) underflows): every bound gets `floor` (below the smallest normal float32 a
+    term may be flushed to zero or keep only some of its bits), every allowed element must be inside its bracket, and rule (2) counts the elements of
+    normal_size(lo, normal) only -- share_ref is then the emulation's share on those"""
     q = np.asarray(q, np.float64)
     ok = lo["ok"]
     assert not q[~ok].any(), "%s: %d non-zero d logits on forbidden categories" % (name, int(np.count_nonzero(q[~ok])))
-    R.check_bf16(name, q[ok], lo["dl"][ok], lo["E_dl"][ok], share_ref, rec)
+    if not floor and not normal:
+        R.check_bf16(name, q[ok], lo["dl"][ok], lo["E_dl"][ok], share_ref, rec)
+        return
+    outside = R.bf16_findings(q[ok], lo["dl"][ok], lo["E_dl"][ok] + floor, 0.0)[0]
+    assert not outside.any(), "%s: %d of %d elements leave the bracket (first: device %.9g, float64 %.12g)" % (
+        name, outside.sum(), outside.size, q[ok][outside][0], lo["dl"][ok][outside][0])
+    sel = normal_size(lo, normal)
+    if sel.any():
+        R.check_bf16(name, q[sel], lo["dl"][sel], lo["E_dl"][sel] + floor, share_ref, rec)
 
 
 def synth_batch_from(obs, act, v, nlp, seed, cr):

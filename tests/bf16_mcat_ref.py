@@ -179,9 +179,9 @@ def emu_loss_dlogits_f32(logits, act, adv, old_nlp, cr, ent_coef, nvec, mask=Non
     return np.concatenate(out, axis=1)
 
 
-def check_dlogits(name, q, lo, share_ref, rec=None):
-    """bf16_cat_ref.check_dlogits on the whole row: forbidden columns exactly 0, the allowed ones by rules (1) and (2) of tests/bf16_ref.py"""
-    C.check_dlogits(name, q, lo, share_ref, rec)
+def check_dlogits(name, q, lo, share_ref, rec=None, floor=0.0, normal=0.0):
+    """bf16_cat_ref.check_dlogits on the whole row: forbidden columns exactly 0, the allowed ones by rules (1) and (2) of tests/bf16_ref.py (floor, normal: see there)"""
+    C.check_dlogits(name, q, lo, share_ref, rec, floor, normal)
 
 
 def synth_batch_from(obs, act, v, nlp, seed, cr):
