@@ -389,6 +389,34 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
  * fused form does against its general path; with normalisation off the two forms give the same bits.  Measured per env step: DESIGN.md section 5. */
 int ppo_set_host_step_fused(ppo_handle* h, int32_t on);   /* before ppo_rollout_alloc; changing it drops an allocated rollout, like ppo_set_action_masking */
 int ppo_host_step_fused(const ppo_handle* h);             /* the setting (0 / 1), not whether it took effect: ppo_kernel_counts says that */
+/* The RESIDENT rollout for a NARROW DISCRETE handle: one launch per rollout (default off; opt-in per handle).  It takes effect on a categorical or multi-categorical
+ * handle on which PPO_ACT_SHAPE_KERNELS took effect, without a communicator, with at most 64 environments, at most 64 observations and logits, and the image + the
+ * rollout state of the handle's environments within 160 KB of LDS.
+ *   Device env (ppo_collect_synthetic), unless PPO_HIP_NO_PERSISTENT_COLLECT=1: ONE launch of narrow_rollout_kernel<cat|mcat> runs all T env steps, with or without
+ * explicit [T, E, A] uniforms; the values come from one batched pass afterwards.  Every field has the bits of the per-step form.  A masking handle samples
+ * unmasked and records ones, as before.
+ *   Host Env (ppo_rollout_act[_masked]), when no explicit noise is passed and PPO_HIP_NO_HOST_RESIDENT / PPO_HIP_NO_HOST_FUSED are unset: the kernel stays on the GPU
+ * for the whole rollout, as the Gaussian resident form does (above): actions and transitions travel through pinned memory behind sequence words, every device-side
+ * wait is bounded (PPO_HIP_HOST_POLLS), a kernel that gave up waiting parks itself and is relaunched by the next act, and any other entry point called in between
+ * sees the state the per-step form would show.  With explicit noise the step leaves the resident form: the fused step if ppo_set_host_step_fused is also on and took
+ * effect, the per-step form otherwise.  With both settings on and no explicit noise the resident form serves the step.
+ *   The mask protocol: ppo_rollout_observe(t - 1) lets the running kernel start row t at once, but the mask of row t is known only at ppo_rollout_act_masked(t, ..).
+ * A masking handle therefore runs the <..,mask> instantiation for plain and masked steps alike: the call copies the checked mask (the plain call: ones) into a
+ * pinned [E, A] block and raises a third sequence word; the kernel runs row t's policy tower without waiting, waits (bounded) for that word before it samples, reads
+ * the block in place and stores it into row t of the mask buffer as the host wrote it.  A refused mask launches nothing and posts nothing; the rollout goes on with
+ * the next valid call.
+ *   ppo_kernel_counts names, one per launch (a rollout behind a host Env: one, plus one per relaunch of a parked kernel), counted INSTEAD of the act launches of
+ * "narrow_step_kernel<cat|mcat[,mask]>" / "narrow_host_step<..>": "narrow_rollout<cat>", "narrow_rollout<cat,mask>", "narrow_rollout<mcat>",
+ * "narrow_rollout<mcat,mask>".  Anywhere else -- a Gaussian handle (its own resident forms are not affected), a discrete handle that is not on the narrow family,
+ * more than 64 environments, a state too large for LDS, data parallel -- the call is accepted and nothing changes: same bits, same ppo_kernel_counts.
+ * On the device env every field and both statistics have the bits of the per-step launches, with normalisation on or off (the kernel sums a batch's moments in
+ * the order of the per-step form's statistics kernel); behind a host Env the same holds with normalisation off, and with it on the two forms are held to the
+ * project's tolerances.
+ * Measured per env step ((18, 6, [64,64]), resident against per-step): behind a host Env 17.6 against 34.7 us at one environment (masked 21.0
+ * against 38.8; (6, 6, 6) masked 23.6 against 40.1), 22.1 against 36.8 at 32, 27.5 against 34.1 at 64 ((6, 6, 6) masked 36.5 against 40.5); on the device env 6.7
+ * against 25.1 us of GPU time at one environment, 12.8 against 26.3 at 64. */
+int ppo_set_rollout_resident(ppo_handle* h, int32_t on);   /* before ppo_rollout_alloc; changing it drops an allocated rollout, like ppo_set_host_step_fused */
+int ppo_rollout_resident(const ppo_handle* h);             /* the setting (0 / 1), not whether it took effect: ppo_kernel_counts says that */
 int ppo_rollout_observe(ppo_handle* h, int32_t t, const float* raw_obs, const float* raw_rew, const float* dones);
 /* Time-limit truncations (no reference counterpart).  The `done` of step t of the environments env_ids [count] (int32) was raised by a time limit, not by a
  * terminal state; terminal_raw_obs [count, O] are the RAW observations those episodes ended on (raw_obs of ppo_rollout_observe holds the observation after the

@@ -371,6 +371,18 @@ class PPOHip:
         """the setting, not whether it took effect"""
         return bool(self.lib.ppo_host_step_fused(self.h))
 
+    def set_rollout_resident(self, on=True):
+        """One launch per rollout for a narrow categorical / multi-categorical handle (include/ppo_hip.h, ppo_set_rollout_resident): collect_synthetic and, behind
+        a host Env without explicit noise, rollout_act / rollout_observe are served by the resident kernel's discrete forms.  Takes effect with shape_kernels on a
+        qualifying shape, at most 64 environments, no communicator; any other handle accepts it and nothing changes (kernel_counts says which ran).  Call it before
+        rollout_alloc: changing the setting drops an allocated rollout."""
+        self._ck(self.lib.ppo_set_rollout_resident(self.h, int(bool(on))))
+
+    @property
+    def rollout_resident(self):
+        """the setting, not whether it took effect"""
+        return bool(self.lib.ppo_rollout_resident(self.h))
+
     def rollout_act(self, t, noise=None, mask=None):
         out = np.empty((self.E,) + self._act_shape, np.float32)
         nz = _f32(noise, (self.E, self.A)) if noise is not None else None

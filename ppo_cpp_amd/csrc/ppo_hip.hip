@@ -69,7 +69,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK,
                      KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK,
                      KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
-                     KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK, KV_COUNT };
+                     KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
+                     KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK, KV_COUNT };
 static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
@@ -95,7 +96,11 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // launch, counted INSTEAD of the act launches of "narrow_step_kernel<cat|mcat[,mask]>" (a bookkeeping-only launch is not counted)
                                        "narrow_host_step<cat>", "narrow_host_step<cat,mask>", "narrow_host_step<mcat>", "narrow_host_step<mcat,mask>",
                                        // a multi-categorical PPO_BF16 handle (ppo_create_multi_ex with PPO_ACT_BF16_MULTI_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence"
-                                       "bf16_step_sequence<mcat>", "bf16_step_sequence<mcat,mask>", "bf16_train_sequence<mcat>", "bf16_train_sequence<mcat,mask>"};
+                                       "bf16_step_sequence<mcat>", "bf16_step_sequence<mcat,mask>", "bf16_train_sequence<mcat>", "bf16_train_sequence<mcat,mask>",
+                                       // a narrow categorical / multi-categorical handle with ppo_set_rollout_resident on, <= 64 environments: one per launch of the resident
+                                       // rollout kernel's discrete instantiation (a rollout on the device env; behind a host Env one per rollout, plus one per relaunch after the
+                                       // kernel parked itself), counted INSTEAD of the act launches of "narrow_step_kernel<cat|mcat[,mask]>" / "narrow_host_step<..>"
+                                       "narrow_rollout<cat>", "narrow_rollout<cat,mask>", "narrow_rollout<mcat>", "narrow_rollout<mcat,mask>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat> or <mcat,mask>.  index(): its column below.
 struct Head {
@@ -105,7 +110,7 @@ struct Head {
 // which entry a launch of a kernel family with a head bumps: a row per family, a column per head form.  (The narrow Gaussian entries say whether the compile-time
 // shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.)
 enum HeadFamily { KF_POLICY_STEP = 0, KF_TRAIN_FB, KF_TRAIN8, KF_NARROW_STEP_STATIC, KF_NARROW_STEP, KF_NARROW_TRAIN_STATIC, KF_NARROW_TRAIN, KF_NARROW_HOST_STEP, KF_BF16_STEP,
-                  KF_BF16_TRAIN, KF_COUNT };
+                  KF_BF16_TRAIN, KF_NARROW_ROLLOUT, KF_COUNT };
 constexpr KernelVariant kHeadVariant[KF_COUNT][5] = {
     {KV_POLICY_STEP, KV_POLICY_STEP_CAT, KV_POLICY_STEP_CAT_MASK, KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK},
     {KV_TRAIN_FB, KV_TRAIN_FB_CAT, KV_TRAIN_FB_CAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK},
@@ -116,7 +121,8 @@ constexpr KernelVariant kHeadVariant[KF_COUNT][5] = {
     {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK},
     {KV_COUNT, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK},
     {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK},
-    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK}};
+    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK},
+    {KV_ROLLOUT_PERSISTENT, KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK}};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -249,6 +255,10 @@ struct ppo_handle {
     // ... and the RESIDENT form (narrow_rollout_kernel in host mode): one launch serves many env steps, host and kernel talk
     // through sequence words in pinned memory (pin_flag[PCTL_*])
     bool opt_no_host_fused = false, opt_no_host_resident = false;     // PPO_HIP_NO_HOST_FUSED / _RESIDENT, read once in ppo_create
+    // ... its discrete forms (ppo_set_rollout_resident on a narrow categorical / multi-categorical handle; resident_discrete() says whether it took effect, on the
+    // device env as well): the mask of row t travels in pin_mask behind a sequence word of its own (PCTL_MASK)
+    bool rollout_resident = false;
+    bool host_values_due = false;     // an act of this rollout ran a form that leaves the values to ppo_rollout_finish's batched pass (resident / fused)
     float* pin_in_dev = nullptr; float* pin_out_dev = nullptr; unsigned* pin_flag_dev = nullptr;   // the pinned blocks as the device sees them
     // general host-Env path: policy_step_kernel's policy-tower workgroups store their 16 rows of actions into pin_out themselves and raise their
     // word of this pinned table to wg_seq; ppo_rollout_act watches the table (PPO_HIP_NO_DIRECT_ACT=1: D2H copy + stream query as in round 4)
@@ -1165,8 +1175,8 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 
 // a categorical handle on the narrow family (created with PPO_ACT_SHAPE_KERNELS, qualifying shape) or a multi-categorical one (ppo_create_multi_ex with the flag)
 // runs narrow_step_kernel / narrow_train_kernel<cat|mcat[,mask]> only -- the head is a HeadTag of the one launch function either has, not a function of its own:
-// every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the persistent / cooperative / fused rollouts, the resident host step) asks
-// nw_gauss() where it is decided.  The fused host step has discrete forms of its own, opt-in per handle: host_fused_discrete().
+// every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the cooperative / fused rollouts) asks nw_gauss() where it is decided.  The
+// fused host step and the resident rollout in the 32-row workgroup have discrete forms of their own, opt-in per handle: host_fused_discrete(), resident_discrete().
 static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
 static bool nw_discrete(const ppo_handle* h) { return h->narrow && h->dist != PPO_ACT_GAUSSIAN; }
 
@@ -1210,6 +1220,13 @@ static auto nw_host_step_fn(T) {
     if constexpr (T::multi) return narrow_host_step_kernel<KP0, HP, AP, LL, true, T::mask, true>;
     else if constexpr (T::cat) return narrow_host_step_kernel<KP0, HP, AP, LL, true, T::mask>;
     else return narrow_host_step_kernel<KP0, HP, AP, LL>;
+}
+// the resident rollout in the 32-row workgroup; MG: more than one group of 32 rows (33..NW_RO_MAX_E environments)
+template <int KP0, int HP, int AP, int LL, bool MG, class T>
+static auto nw_rollout_fn(T) {
+    if constexpr (T::multi) return narrow_rollout_kernel<KP0, HP, AP, LL, MG, true, T::mask, true>;
+    else if constexpr (T::cat) return narrow_rollout_kernel<KP0, HP, AP, LL, MG, true, T::mask>;
+    else return narrow_rollout_kernel<KP0, HP, AP, LL, MG>;
 }
 
 int launch_step(ppo_handle* h, const StepArgs& a0) {
@@ -1982,19 +1999,18 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (h->narrow) {
         attr_ok = true;
         auto big_lds = [&](auto f) { attr_ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
-        // the kernels with a head, every shape: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl), host step -- for the
-        // Gaussian head and every head this handle can launch
+        // the kernels with a head, every shape: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl), host step, resident
+        // rollout (one and two groups of rows) -- for the Gaussian head and every head this handle can launch
         auto nw_heads = [&](auto H) {
 #define X(a, b, c, d) do { big_lds(nw_step_fn<a, b, c, d>(H)); big_lds(nw_train_fn<false, a, b, c, d>(H)); big_lds(nw_train_fn<true, a, b, c, d>(H)); \
-                           big_lds(nw_host_step_fn<a, b, c, d>(H)); } while (0)
+                           big_lds(nw_host_step_fn<a, b, c, d>(H)); big_lds(nw_rollout_fn<a, b, c, d, false>(H)); big_lds(nw_rollout_fn<a, b, c, d, true>(H)); } while (0)
             X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
         };
         if (!nw_gauss(h)) nw_heads(GaussHead{});
         for_each_head(h, nw_heads);
         // the kernels without a head axis
-#define X(a, b, c, d) do { big_lds(narrow_collect_kernel<a, b, c, d>); big_lds(narrow_rollout_kernel<a, b, c, d, false>); big_lds(narrow_rollout_kernel<a, b, c, d, true>); \
-                           big_lds(narrow_rollout_coop_kernel<a, b, c, d>); } while (0)
+#define X(a, b, c, d) do { big_lds(narrow_collect_kernel<a, b, c, d>); big_lds(narrow_rollout_coop_kernel<a, b, c, d>); } while (0)
         X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
         big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true>);
@@ -2678,6 +2694,7 @@ int ppo_set_action_masking(ppo_handle* h, int on) {
 int ppo_get_action_masking(const ppo_handle* h) { return h && h->masking ? 1 : 0; }
 
 static bool host_fused_discrete(const ppo_handle* h);           // (with the form decisions below)
+static bool host_resident_discrete(const ppo_handle* h);
 // The fused host-Env step of a narrow discrete handle (host_fused_discrete).  Any handle accepts the call; on a Gaussian handle, or a discrete one that is not on
 // the narrow family, only the bit is recorded: the rollout stays, same launches, same bits.
 int ppo_set_host_step_fused(ppo_handle* h, int32_t on) {
@@ -2698,6 +2715,25 @@ int ppo_set_host_step_fused(ppo_handle* h, int32_t on) {
 }
 int ppo_host_step_fused(const ppo_handle* h) { return h && h->host_step_fused ? 1 : 0; }
 
+// The resident rollout of a narrow discrete handle (resident_discrete).  As above: any handle accepts the call, and only a narrow discrete one drops its rollout.
+int ppo_set_rollout_resident(ppo_handle* h, int32_t on) {
+    if (!h) return fail(nullptr, "ppo_set_rollout_resident: null handle");
+    if ((on != 0) == h->rollout_resident) return 0;
+    if (nw_discrete(h)) {
+        // the rollout belongs to the old form (a resident kernel, a posted transition, the pinned mask block): dropped, as ppo_set_host_step_fused does
+        ENTER_Q(h);                                                 // (a resident kernel is retired, a posted transition is booked first)
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        drop_graph(h);
+        h->E = 0; h->T = 0;
+        h->upd_cap_rows = 0; h->upd_cap_steps = 0;
+        h->host_proto = false; h->pin_in_busy = false;
+        trunc_clear(h);
+    }
+    h->rollout_resident = on != 0;
+    return 0;
+}
+int ppo_rollout_resident(const ppo_handle* h) { return h && h->rollout_resident ? 1 : 0; }
+
 int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
     ENTER(h);
     if (E < 1 || T < 1) return fail(h, "ppo_rollout_alloc: bad shape");
@@ -2713,11 +2749,11 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
         dev_alloc(h, &h->last_val, E) || dev_alloc(h, &h->ro_noise, B * n.A))
         return -1;
     if (h->masking && (dev_alloc(h, &h->ro_mask, B * n.A) || mask_fill_ones(h, h->ro_mask, B * n.A))) return -1;
-    h->E = E; h->T = T;
+    h->E = E; h->T = T; h->host_values_due = false;
     HIP_OK(h, hipStreamSynchronize(h->stream));
-    // the pinned mask block of the fused discrete host-Env step (only while masking is on and that form took effect)
+    // the pinned mask block of the discrete host-Env forms, fused and resident (only while masking is on and either can take effect)
     if (h->pin_mask) { (void)hipHostFree(h->pin_mask); h->pin_mask = nullptr; h->pin_mask_dev = nullptr; }
-    if (h->masking && host_fused_discrete(h)) {
+    if (h->masking && (host_fused_discrete(h) || host_resident_discrete(h))) {
         void* d = nullptr;
         HIP_OK(h, hipHostMalloc((void**)&h->pin_mask, (size_t)E * n.A * sizeof(float), hipHostMallocDefault));
         HIP_OK(h, hipHostGetDevicePointer(&d, h->pin_mask, 0)); h->pin_mask_dev = (float*)d;
@@ -2832,16 +2868,27 @@ static size_t one_group_lds(const ppo_handle* h) { return ((size_t)h->nw.lds_tot
 // block: the transition is booked by the next launch / the resident kernel.  (The LDS bound covers both kernels, whichever serves the step.)
 // The discrete forms of the fused step (narrow_host_step_kernel<cat|mcat[,mask]>) are opt-in per handle, ppo_set_host_step_fused; this says whether the setting
 // TOOK EFFECT: a narrow categorical / multi-categorical handle (created with PPO_ACT_SHAPE_KERNELS on a qualifying shape), one rank, one row group.  Anywhere else
-// the handle runs the per-step form, silently.  Such a handle never takes a resident form: those keep a Gaussian head and have no channel for a per-step mask.
+// the handle runs the per-step form, silently.
 static bool host_fused_discrete(const ppo_handle* h) {
     const NetDev& n = h->net;
     return h->host_step_fused && nw_discrete(h) && !h->opt_no_host_fused && !h->comm && h->E <= NW_ROWS && n.O <= 64 && n.A <= 64 && h->pin_flag &&
            one_group_lds(h) <= 160 * 1024;
 }
+// The discrete forms of the resident rollout (narrow_rollout_kernel<cat|mcat[,mask]>) are opt-in per handle as well, ppo_set_rollout_resident; this says whether
+// that setting TOOK EFFECT for the handle's rollout shape: a narrow categorical / multi-categorical handle, one rank, up to NW_RO_MAX_E environments whose state
+// fits behind the image.  dev_form asks it for a rollout on the device env; behind a host Env (host_resident_discrete) the switches of host_small and the pinned
+// words come on top, and a step that brings explicit noise still leaves the resident form (host_form).  Anywhere else the handle runs what it ran before, silently.
+static bool resident_discrete(const ppo_handle* h) {
+    const NetDev& n = h->net;
+    return h->rollout_resident && nw_discrete(h) && !h->comm && n.O <= 64 && n.A <= 64 && h->E <= NW_RO_MAX_E && rollout_lds(h) <= 160 * 1024;
+}
+static bool host_resident_discrete(const ppo_handle* h) {
+    return resident_discrete(h) && !h->opt_no_host_fused && !h->opt_no_host_resident && h->pin_flag;
+}
 
 static bool host_small(const ppo_handle* h) {
     if (h->opt_no_host_fused) return false;
-    if (host_fused_discrete(h)) return true;
+    if (host_fused_discrete(h) || host_resident_discrete(h)) return true;
     const NetDev& n = h->net;
     return nw_gauss(h) && !h->comm && !h->bf.on && h->E <= NW_RO_MAX_E && n.O <= 64 && n.A <= 64 && h->pin_flag &&
            ((size_t)h->nw.lds_total + std::max(nw_ro_extra(h->E, n.O), NW_RO_EXTRA)) * sizeof(float) <= 160 * 1024;
@@ -2849,8 +2896,9 @@ static bool host_small(const ppo_handle* h) {
 
 // explicit noise (one [E, A] block per call) cannot feed a kernel that is resident over the whole rollout: it leaves the fused step on
 static HostForm host_form(const ppo_handle* h, bool explicit_noise) {
-    if (host_fused_discrete(h)) return HF_FUSED;                 // (with or without explicit noise; never a resident form)
-    if (host_small(h)) {
+    if (host_resident_discrete(h) && !explicit_noise) return HF_RESIDENT;     // (both settings on: resident wins, the Gaussian rule)
+    if (host_fused_discrete(h)) return HF_FUSED;                 // (with or without explicit noise)
+    if (nw_gauss(h) && host_small(h)) {
         if (!h->opt_no_host_resident && !explicit_noise) return use_rollout1(h) ? HF_RESIDENT1 : HF_RESIDENT;
         if (h->E <= NW_ROWS) return HF_FUSED;
     }
@@ -2867,8 +2915,10 @@ static HostForm host_form(const ppo_handle* h, bool explicit_noise) {
 static DevForm dev_form(const ppo_handle* h) {
     const NetDev& n = h->net;
     const int E = h->E, G = (E + NW_ROWS - 1) / NW_ROWS;
-    const bool small_net = nw_gauss(h) && !h->comm && n.O <= 64;          // (the resident / fused rollout kernels keep a Gaussian head)
     const char* npe = getenv("PPO_HIP_NO_PERSISTENT_COLLECT");
+    // a discrete handle: the one-workgroup form only, and only where ppo_set_rollout_resident took effect
+    if (nw_discrete(h)) return resident_discrete(h) && !(npe && npe[0] == '1') ? DF_PERSISTENT : DF_PER_STEP;
+    const bool small_net = nw_gauss(h) && !h->comm && n.O <= 64;          // (the one-wave, cooperative and fused rollout kernels keep a Gaussian head)
     const bool resident = small_net && n.A <= 64 && !(npe && npe[0] == '1');
     // the whole rollout in ONE launch of one persistent workgroup: state in LDS, only stores leave the CU
     // (up to NW_RO_MAX_E environments: the one workgroup walks them in groups of 32 rows)
@@ -2938,8 +2988,9 @@ static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_
     return 0;
 }
 
-// the resident rollout of q.E == h->E environments: in one wave (DF_ROLLOUT1 / HF_RESIDENT1) or in the 32-row workgroup
-static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, bool one_wave) {
+// the resident rollout of q.E == h->E environments: in one wave (DF_ROLLOUT1 / HF_RESIDENT1, Gaussian) or in the 32-row workgroup
+// masked: (a masking discrete handle behind a host Env) every row samples under the mask the host posts for it, plain calls under ones
+static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, bool one_wave, bool masked = false) {
     const NetDev& n = h->net;
     if (one_wave) {
         ++h->kv[KV_ROLLOUT1];
@@ -2951,13 +3002,28 @@ static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, bool on
         else hipLaunchKernelGGL((narrow_rollout1_kernel<64, false>), dim3(1), dim3(192), 0, h->stream, n, h->nw, q);
         return;
     }
-    const bool multi = q.E > NW_ROWS;
+    const bool groups = q.E > NW_ROWS;
     const size_t lds = rollout_lds(h);
-    ++h->kv[KV_ROLLOUT_PERSISTENT];
-#define X(a, b, c, d) do { if (multi) hipLaunchKernelGGL((narrow_rollout_kernel<a, b, c, d, true>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q); \
-                           else hipLaunchKernelGGL((narrow_rollout_kernel<a, b, c, d, false>), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, q); } while (0)
-    NW_DISPATCH(h, X);
+    const Head hd = head_of(h, masked);
+    ++h->kv[kHeadVariant[KF_NARROW_ROLLOUT][hd.index()]];
+    with_head(hd, [&](auto H) {
+        auto launch = [&](const auto& args) {
+#define X(a, b, c, d) do { if (groups) hipLaunchKernelGGL((nw_rollout_fn<a, b, c, d, true>(H)), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, args); \
+                           else hipLaunchKernelGGL((nw_rollout_fn<a, b, c, d, false>(H)), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, args); } while (0)
+            NW_DISPATCH(h, X);
 #undef X
+        };
+        if constexpr (!decltype(H)::cat) launch(q);
+        else {
+            // the discrete forms: the mask block and the mask buffer behind the arguments above, the component table (multi-categorical) behind those
+            NwRolloutArgsD d{};
+            static_cast<NwRolloutArgs&>(d) = q;
+            d.host_mask = masked ? h->pin_mask_dev : nullptr;
+            d.ro_mask = masked ? h->ro_mask : nullptr;
+            d.Aw = h->Aw;
+            launch(head_args<NwRolloutArgsDM>(H, h, d));
+        }
+    });
 }
 
 // the VRAM inbox's sequence word, stored by the host through the BAR (write-combined: fenced on both sides)
@@ -2971,9 +3037,12 @@ static void vram_word(ppo_handle* h, unsigned v) {
 // ---- resident host-Env rollout kernel (see NwRolloutArgs) -----------------------------------------------------------------------
 // control words live at pin_flag + 64 (the first line is the per-launch completion word of narrow_host_step_kernel)
 static unsigned* hp_ctl(ppo_handle* h) { return h->pin_flag + 64; }
-// both sequence words and the VRAM inbox's word back to zero: the next rollout counts from clean words
+// the three sequence words and the VRAM inbox's word back to zero: the next rollout counts from clean words
 static void host_words_reset(ppo_handle* h) {
-    if (h->pin_flag) { __atomic_store_n(hp_ctl(h) + PCTL_H2D, 0u, __ATOMIC_RELEASE); __atomic_store_n(hp_ctl(h) + PCTL_D2H, 0u, __ATOMIC_RELEASE); vram_word(h, 0u); }
+    if (h->pin_flag) {
+        __atomic_store_n(hp_ctl(h) + PCTL_H2D, 0u, __ATOMIC_RELEASE); __atomic_store_n(hp_ctl(h) + PCTL_D2H, 0u, __ATOMIC_RELEASE);
+        __atomic_store_n(hp_ctl(h) + PCTL_MASK, 0u, __ATOMIC_RELEASE); vram_word(h, 0u);
+    }
 }
 static int hp_launch(ppo_handle* h, HostForm form, int t0, uint32_t rng_step_t0) {
     NwRolloutArgs q = nw_args<NwRolloutArgs>(h);
@@ -2985,7 +3054,7 @@ static int hp_launch(ppo_handle* h, HostForm form, int t0, uint32_t rng_step_t0)
     q.poll_cap = pc ? (unsigned)atol(pc) : 150000u;                 // ~2 us per poll over PCIe: a fraction of a second, then the kernel parks itself
     __atomic_store_n(hp_ctl(h) + PCTL_EXIT, 0u, __ATOMIC_RELEASE);
     __atomic_store_n(hp_ctl(h) + PCTL_STOP, 0u, __ATOMIC_RELEASE);
-    launch_rollout_kernel(h, q, form == HF_RESIDENT1);
+    launch_rollout_kernel(h, q, form == HF_RESIDENT1, h->masking);     // (a masking handle: the mask form for plain and masked steps alike)
     HIP_OK(h, hipGetLastError());
     h->hp_active = true; h->host_pending = false;
     return 0;
@@ -3032,7 +3101,7 @@ int ppo_rollout_reset(ppo_handle* h, const float* raw_obs) {
     const size_t on = (size_t)h->E * h->net.O;
     if (host_quiesce(h)) return -1;                             // (a transition observed before the reset is still booked, as on the general path)
     if (h->pin_in_busy) HIP_OK(h, hipStreamSynchronize(h->stream));
-    h->pin_in_busy = false; h->host_pending = false; h->hp_posted = 0;
+    h->pin_in_busy = false; h->host_pending = false; h->hp_posted = 0; h->host_values_due = false;
     trunc_clear(h);
     host_words_reset(h);
     memcpy(h->pin_in, raw_obs, on * sizeof(float));
@@ -3061,19 +3130,29 @@ static int host_spin(ppo_handle* h, unsigned long poll_mask, const char* msg, in
 
 // the kernel stays resident over the rollout: actions and transitions travel through the pinned blocks, sequence words
 // order them; (re)launched here when it is not running (first step, or it parked itself after a long host pause)
-static int act_resident(ppo_handle* h, HostForm form, int t) {
+// mask: (a masking handle) the [E, A] mask of row t, checked by the caller; null: the plain call, ones
+static int act_resident(ppo_handle* h, HostForm form, int t, const float* mask) {
     unsigned* ctl = hp_ctl(h);
     const uint32_t rng_step = h->rng_calls++;
     if (t == 0) {
         // a rollout abandoned without ppo_rollout_finish / _reset (an env exception, say) leaves its kernel resident and its
         // sequence words raised: retire it, book what it posted, and start this rollout from clean words -- stale actions
         // must never be handed out for step 0
-        if (h->hp_active || __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) != 0u || __atomic_load_n(ctl + PCTL_H2D, __ATOMIC_ACQUIRE) != 0u) {
+        if (h->hp_active || __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) != 0u || __atomic_load_n(ctl + PCTL_H2D, __ATOMIC_ACQUIRE) != 0u ||
+            __atomic_load_n(ctl + PCTL_MASK, __ATOMIC_ACQUIRE) != 0u) {
             if (host_quiesce(h)) return -1;
             HIP_OK(h, hipStreamSynchronize(h->stream));
             host_words_reset(h);
         }
         h->hp_posted = 0;
+    }
+    if (h->masking) {
+        // the mask channel: the kernel has run row t's policy tower since the last transition was posted and waits (bounded) for this word before it samples;
+        // it reads the block in place.  The block is free: row t - 1's mask was read before that row was published, and a kernel that parked is relaunched at row t.
+        const size_t mc = (size_t)h->E * h->net.A;
+        if (mask) memcpy(h->pin_mask, mask, mc * sizeof(float));
+        else std::fill(h->pin_mask, h->pin_mask + mc, 1.0f);
+        __atomic_store_n(ctl + PCTL_MASK, (unsigned)(t + 1), __ATOMIC_RELEASE);
     }
     auto published = [&] { return __atomic_load_n(ctl + PCTL_D2H, __ATOMIC_ACQUIRE) >= (unsigned)(t + 1); };
     for (int attempt = 0; ; ++attempt) {
@@ -3144,12 +3223,11 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
     if (mask && check_masks(h, "ppo_rollout_act_masked", mask, (size_t)h->E, nullptr)) return -1;
     ENTER(h);
     float* mask_row = nullptr;
-    const bool fused_mask = h->masking && host_fused_discrete(h);
-    if (fused_mask) {
-        // the fused discrete step reads the mask from the pinned block in place and stores row t of the mask buffer itself (the plain call: ones);
-        // the block is free: the launch that read it last was waited for
-        if (mask) memcpy(h->pin_mask, mask, (size_t)h->E * h->net.A * sizeof(float));
-    } else if (h->masking) {
+    const HostForm form = host_form(h, noise != nullptr);
+    // the discrete forms of the fused and the resident step read the mask from the pinned block in place and store row t of the mask buffer themselves
+    const bool fused_mask = h->masking && nw_discrete(h) && form == HF_FUSED, resident_mask = h->masking && nw_discrete(h) && form == HF_RESIDENT;
+    // (the pinned block is filled below: behind the retirement of a resident kernel that may still run, or by act_resident in front of the mask's sequence word)
+    if (h->masking && !fused_mask && !resident_mask) {
         // row t of the mask buffer: what was passed, or ones (the plain call on a masking handle: the unmasked kernel, the same bits)
         const size_t mc = (size_t)h->E * h->net.A;
         if (mask) { mask_row = h->ro_mask + (size_t)t * mc; HIP_OK(h, hipMemcpyAsync(mask_row, mask, mc * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
@@ -3159,18 +3237,20 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
     float* nd = nullptr;                                         // the noise is [E, A]
     if (noise) { nd = h->ro_noise; HIP_OK(h, hipMemcpyAsync(nd, noise, (size_t)h->E * h->net.A * sizeof(float), hipMemcpyHostToDevice, h->stream)); }
 
-    const HostForm form = host_form(h, noise != nullptr);
     if (form > HF_RESIDENT) {
         // no resident kernel serves this step: one that still runs is asked to leave, and a transition it left unbooked is booked now
         // unless the fused step does that itself (both are no-ops on a handle that never ran the resident form)
         if (hp_retire(h, true)) return -1;
         if (form != HF_FUSED && host_flush_pending(h)) return -1;
     }
+    // the fused discrete step's mask (the plain call launches the unmasked form); the block is free: the launch that read it last was waited for
+    if (fused_mask && mask) memcpy(h->pin_mask, mask, (size_t)h->E * h->net.A * sizeof(float));
     h->host_proto = form <= HF_FUSED;                            // the kernel reads the next transition from the pinned block in place: ppo_rollout_observe only posts it
+    if (h->host_proto) h->host_values_due = true;
     int rc = -1;
     switch (form) {
         case HF_RESIDENT1:
-        case HF_RESIDENT: rc = act_resident(h, form, t); break;
+        case HF_RESIDENT: rc = act_resident(h, form, t, mask); break;
         case HF_FUSED: rc = act_fused(h, t, nd, fused_mask && mask); break;
         case HF_DIRECT: rc = act_direct(h, t, nd, mask_row, actions_out); break;
         case HF_COPY: rc = act_copy(h, t, nd, mask_row); break;
@@ -3215,8 +3295,11 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
         // stopped early it is asked to leave
         if (hp_retire(h, h->hp_posted < h->T)) return -1;
         host_words_reset(h);
-        if (host_flush_pending(h) || enqueue_values_all_rows(h)) return -1;               // the last transition's bookkeeping, then the values
+        if (host_flush_pending(h)) return -1;                                             // the last transition's bookkeeping, then the values
+        // (a discrete handle on which only the resident setting took effect and whose every act brought explicit noise ran the per-step form: its values are there)
+        if ((h->host_values_due || !host_resident_discrete(h) || host_fused_discrete(h)) && enqueue_values_all_rows(h)) return -1;
     }
+    h->host_values_due = false;
     const bool marks = h->tr_K > 0;                                 // none: the launches of a rollout without time limits, nothing else
     if (marks && enqueue_truncations(h)) { trunc_clear(h); return -1; }
     h->tval_live = marks;

@@ -1712,6 +1712,406 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, 
     }
 }
 
+// The DISCRETE forms of the resident rollout (a narrow categorical / multi-categorical handle with ppo_set_rollout_resident on): the kernel above with
+// narrow_step_kernel<cat[,mask]>'s / <mcat[,mask]>'s head, as nw_host_step_discrete writes it out, in its sampling phase.  Entry and exit, read_host,
+// the normalise-into-tile loop with s_istd, the live_pipe layers, the logits tile in P + lay.mu, the LDS-only barriers and the device-env transition are the
+// Gaussian kernel's, statement for statement.  The bookkeeping keeps the Gaussian kernel's pieces (rs_merge, en_istd, en_reward, en_ret_reset) but sums a batch's
+// moments in norm_batch_kernel's order (nw_chunk_moments_lds below), not in the Gaussian kernel's sequential column loop: the per-step form of a DISCRETE handle
+// books with norm_batch_kernel, and the resident forms give that form's bits with normalisation on (tests/test_narrow_resident_discrete.py).  A lane owns the logit columns part + 16 k (four: A <= 64); its uniforms are q.noise ([T][E][A], device env) or the
+// counter draw keyed by the GLOBAL logit index -- the per-step form's keys, so the same seed draws what the per-step form draws.  (No helper-pipe pre-draw at
+// <= 16 environments: a uniform is one hash, not the Gaussian draw's two with log, cos and sqrt.)  Actions are [E, Aw] (Aw = 1, or K) in rollout row t and in
+// host_act.
+// MASK (host mode, a masking handle): the mask of row t reaches the RUNNING kernel through a third sequence word.  The host posts the transition of row t - 1
+// (PCTL_H2D) long before it knows the mask of row t, so the kernel normalises and runs the policy tower of row t without waiting; before the first group samples,
+// thread 0 polls ctl[PCTL_MASK] >= t + 1 with the loop of the transition wait (bounded by poll_cap, ended by the stop word), an LDS word carries the outcome to
+// the workgroup, and an acquire fence at system scope stands in front of the mask reads.  The lane reads its mask words from the pinned block in place and stores
+// them into row t of ro_mask as the host wrote them.  A wait that gives up leaves by the exit path: the transition of row t - 1 is booked (report 1 + t), the next
+// act relaunches at t0 = t with nothing pending, and rewriting row t's observations, dones and mask row is idempotent.  Nothing is indexed with the sampled
+// category or with a mask value.
+// OVERLOADS behind new argument structs (see narrow_host_step_kernel's), not defaulted parameters of the template above: the Gaussian instantiations keep their
+// symbols, their kernarg layout and their machine code.
+#define PCTL_MASK 64
+struct NwRolloutArgsD : NwRolloutArgs {
+    const float* host_mask;      // pinned host [E][A]: the mask of the row the host asked for last (MASK forms)
+    float* ro_mask;              // the rollout's mask buffer [T][E][A] (MASK forms; null otherwise)
+    int Aw;                      // action columns per row: 1 (categorical) or K
+};
+struct NwRolloutArgsDM : NwRolloutArgsD { CompTable comp; };
+
+// The batch moments of the discrete forms' bookkeeping, in norm_batch_kernel's ORDER OF SUMMATION.  A discrete handle's per-step form books a transition with
+// norm_batch_kernel (the Gaussian one's with narrow_collect_kernel, whose sequential column loop the Gaussian resident kernel shares), and the discrete resident
+// forms are held to that form's bits: so this is chunk_moments (ppo_kernels.hpp) over the observations in LDS -- the first 256 threads of the workgroup stand for
+// its block: thread (rsub, col) sums rows r0 + rsub + u rpp of its column, eight in a fixed tree and the rest in sequence, and the row sweeps meet in a fixed-shape
+// tree; two passes (mean, then squared deviations) -- and, per column, combine_group over the chunks enqueue_norm_batch would deal (one or two for at most 64 x 64
+// values).  Whole workgroup (barriers).  out: [0] = n, [1 + c] = mean, [65 + c] = M2 of the chunk; sh: 512 floats.
+#define NW_NB_SET 130
+__device__ __forceinline__ int nw_nb_rows_per_chunk(int E, int O) {           // enqueue_norm_batch's row-chunk deal
+    int g = max(1, min(O <= 32 ? NB_MAX_OBS_BLOCKS : 64, (E * O + 2047) / 2048));
+    g = min(g, E);
+    return (E + g - 1) / g;
+}
+__device__ __forceinline__ void nw_chunk_moments_lds(const float* x, int r0, int r1, int D, float* out, float* sh) {
+    const int tid = threadIdx.x;
+    const float n = (float)(r1 - r0);
+    if (tid == 0) out[0] = n;
+    float* cm = sh + NB_THREADS;
+    constexpr int U = 8;
+    const int rpp = NB_THREADS / D;
+    const int col = tid % D, rsub = tid / D;
+    const bool act = tid < NB_THREADS && rsub < rpp;
+    const int top = pow2_ceil(rpp) >> 1;
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) { const int r = r0 + rsub + u * rpp; v[u] = (act && r < r1) ? x[r * D + col] : 0.f; }
+    for (int pass = 0; pass < 2; ++pass) {
+        const float bm = pass ? cm[col] : 0.f;
+        float t[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float a0 = v[u] - bm;
+            t[u] = (act && r0 + rsub + u * rpp < r1) ? (pass ? a0 * a0 : a0) : 0.f;
+        }
+        float s = ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+        if (act) for (int r = r0 + rsub + U * rpp; r < r1; r += rpp) { const float a0 = x[r * D + col] - bm; s += pass ? a0 * a0 : a0; }
+        lds_barrier();
+        if (tid < NB_THREADS) sh[tid] = s;
+        lds_barrier();
+        for (int h = top; h > 0; h >>= 1) {
+            if (act && rsub < h && rsub + h < rpp) sh[tid] += sh[tid + h * D];
+            lds_barrier();
+        }
+        if (tid < D) {
+            if (pass == 0) cm[tid] = sh[tid] / n;
+            else { out[1 + tid] = cm[tid]; out[65 + tid] = sh[tid]; }
+        }
+        lds_barrier();
+    }
+}
+
+template <int KP0, int HP, int AP, int LL, bool MULTI, bool MASK, bool MCAT>
+__device__ __forceinline__ void nw_rollout_discrete(const NetDev& net, const NwLayout& lay, const NwRolloutArgsD& q, const CompTable& comp) {
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, pipe = tid >> 8, ptid = tid & 255;
+    const int L = S::L(net), Kp0 = S::Kp0(net), Ap = S::Ap(net);
+    const int E = q.E, O = net.O, A = net.A;
+    // stride of the per-environment vectors / size of the observation block: compile-time for the single-group instantiation
+    const int ES = MULTI ? (E + NW_ROWS - 1) / NW_ROWS * NW_ROWS : NW_ROWS;
+    float* xs = lds + lay.lds_total;                        // [E][O] raw observations of the current state
+    float* s_mean = xs + (MULTI ? ES * O : NW_RO_XS); float* s_var = s_mean + 64;
+    float* rs = s_var + 64;                                 // [ES] rewards | [ES] dones | [ES] returns
+    float* s_retstat = rs + 3 * ES;                         // ret_rms mean, var
+    float* s_istd = s_retstat + 8;                          // 1 / sqrt(var + eps) per column: the expression of the per-step kernels, evaluated once per statistics update
+    // ---- entry: image + state, one round trip ----------------------------------------------------------------------------
+    {
+        const int n4 = lay.w_fwd / 4;
+        for (int e = tid; e < n4; e += NW_THREADS) reinterpret_cast<float4*>(lds)[e] = reinterpret_cast<const float4*>(q.img)[e];
+        for (int i = tid; i < E * O; i += NW_THREADS) xs[i] = q.st.raw_obs[i];
+        if (tid < O) { s_mean[tid] = q.st.obs_mean[tid]; const float v0 = q.st.obs_var[tid]; s_var[tid] = v0; s_istd[tid] = en_istd(v0, q.eps); }
+        if (tid < E) { rs[ES + tid] = q.st.done[tid]; rs[2 * ES + tid] = q.st.ret[tid]; }
+        if (tid == 0) { s_retstat[0] = *q.st.ret_mean; s_retstat[1] = *q.st.ret_var; }
+    }
+    double obs_cnt = *q.st.obs_count, ret_cnt = *q.st.ret_count;          // replicated: every thread that merges holds the count
+    __syncthreads();
+    float* P = lds + lay.w_total + pipe * lay.pipe_total;
+    const float* par = lds + lay.par;
+    const int r = ptid >> 4, part = ptid & 15;
+    const int row = 16 * pipe + r;
+    int* s_ok = reinterpret_cast<int*>(s_retstat + 4);
+    // host transition -> xs / rs (zero-copy reads of the pinned block)
+    auto read_host = [&]() __attribute__((always_inline)) {
+        for (int i = tid; i < E * O; i += NW_THREADS) xs[i] = q.host_in[i];
+        if (tid < E) { rs[tid] = q.host_in[(size_t)E * O + tid]; rs[ES + tid] = q.host_in[(size_t)E * O + E + tid]; }
+    };
+    // EnvNormalize::step bookkeeping of the transition in xs / rs (env_normalize.hpp:64-116, running_statistics.hpp:26-104); rewards -> row tr.  The batch moments are
+    // summed in norm_batch_kernel's order (above): the per-step form's bits.  Whole workgroup.
+    float* nb_sh = s_istd + 64;                             // 512 floats of tree scratch, then two chunk sets (the Gaussian kernel's s_eps block: 1024 floats)
+    float* nb_set = nb_sh + 2 * NB_THREADS;
+    const int nb_rpb = nw_nb_rows_per_chunk(E, O), nb_G = (E + nb_rpb - 1) / nb_rpb;
+    auto bookkeeping = [&](int tr) __attribute__((always_inline)) {
+        if (q.norm_obs) {
+            for (int k = 0; k < nb_G; ++k) nw_chunk_moments_lds(xs, k * nb_rpb, min(E, (k + 1) * nb_rpb), O, nb_set + k * NW_NB_SET, nb_sh);
+            if (tid < O) {
+                // combine_group over the chunks (index order; a set per row sweep, so the tree adds them last), then RunningStatistics::update's merge
+                float nn = 0.f;
+                for (int k = 0; k < nb_G; ++k) nn += nb_set[k * NW_NB_SET];
+                float s = 0.f;
+                for (int k = 0; k < nb_G; ++k) { float sk = 0.f; sk += nb_set[k * NW_NB_SET] * nb_set[k * NW_NB_SET + 1 + tid]; s = k ? s + sk : sk; }
+                const float bmean = s / nn;
+                float m2 = 0.f;
+                for (int k = 0; k < nb_G; ++k) {
+                    const float d = nb_set[k * NW_NB_SET + 1 + tid] - bmean;
+                    float sk = 0.f; sk += nb_set[k * NW_NB_SET + 65 + tid] + nb_set[k * NW_NB_SET] * (d * d);
+                    m2 = k ? m2 + sk : sk;
+                }
+                float m1, v1;
+                rs_merge(s_mean[tid], s_var[tid], obs_cnt, bmean, m2, nn, m1, v1);
+                s_mean[tid] = m1; s_var[tid] = v1; s_istd[tid] = en_istd(v1, q.eps);
+                obs_cnt = (double)nn + obs_cnt;                                         // :103
+            }
+        }
+        if (tid >= 64 && tid < 128) {                           // (a different wave than the observation columns) lane l: environment l (E <= 64)
+            const int l = tid - 64;
+            const bool have = l < E;
+            float* ret = rs + 2 * ES;
+            const float nv = (have ? ret[l] : 0.f) * q.gamma + (have ? rs[l] : 0.f);       // env_normalize.hpp:66
+            float m1 = s_retstat[0], v1 = s_retstat[1];
+            if (q.norm_rew) {                                                                // :75-77 (training)
+                // chunk_moments of the one reward chunk (a row per thread, the tree over the row sweeps inside this wave: combine_single_column's remark), then
+                // combine_single_column over that one set
+                const float nE = (float)E;
+                float t0 = have ? nv - 0.f : 0.f;
+                float s = t0 + 0.f;
+                for (int h = 32; h > 0; h >>= 1) s += __shfl_down(s, h);
+                const float cmean = __shfl(s, 0) / nE;
+                const float a0 = nv - cmean;
+                t0 = have ? a0 * a0 : 0.f;
+                s = t0 + 0.f;
+                for (int h = 32; h > 0; h >>= 1) s += __shfl_down(s, h);
+                const float cM2 = __shfl(s, 0);
+                float nn = 0.f; nn += nE;
+                const float bmean = (nE * cmean) / nn;
+                const float d = cmean - bmean;
+                const float m2 = cM2 + nE * (d * d);
+                if (l == 0) {
+                    rs_merge(s_retstat[0], s_retstat[1], ret_cnt, bmean, m2, nn, m1, v1);
+                    ret_cnt = (double)nn + ret_cnt;
+                }
+                m1 = __shfl(m1, 0); v1 = __shfl(v1, 0);
+            }
+            if (l == 0) { s_retstat[0] = m1; s_retstat[1] = v1; }
+            const float inv = en_istd(v1, q.eps);                                                    // :79
+            if (have) {
+                q.ro_rew[(size_t)tr * E + l] = en_reward(rs[l], inv, q.norm_rew, q.clip_rew);
+                ret[l] = en_ret_reset(nv, rs[ES + l]);                                                // :88-91
+            }
+        }
+    };
+    int booked = q.t0;                                          // transitions whose bookkeeping is done (host mode's exit report)
+    if (q.host_mode && q.pending) {                             // a transition posted before this launch: rewards row t0 - 1
+        booked = q.t0 - 1;
+        read_host();
+        lds_barrier();
+        bookkeeping(q.t0 - 1);
+        lds_barrier();
+        booked = q.t0;
+    }
+    for (int t = q.t0; t < q.T; ++t) {
+        if (tid < E) q.ro_done[(size_t)t * E + tid] = rs[ES + tid];                  // the flags that arrived with obs_t
+        bool parked = false;                                    // (MASK) the wait for row t's mask gave up: uniform over the workgroup
+        // the environments go through the two 16-row pipes in groups of 32 (one group at <= 32 environments)
+        for (int g0 = 0; g0 < (MULTI ? E : 1); g0 += NW_ROWS) {
+            const int grow = g0 + row;                          // this thread's environment in the sampling phase
+            const bool live_pipe = g0 + 16 * pipe < E;          // a pipe without environments skips the matrix work (it shares the SIMDs' matrix pipes with the live one)
+            // the lane's uniforms of this step: requested (explicit noise) or drawn now, consumed after the forward pass
+            float uk[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = part + 16 * k;
+                uk[k] = 0.5f;
+                if (j < A && grow < E) uk[k] = q.noise ? q.noise[((size_t)t * E + grow) * A + j] : ctr_uniform(q.seed, (uint32_t)q.env0 + grow, q.step0 + (uint32_t)t, j);
+            }
+            // ---- normalise the group's observations (env_normalize.hpp:99-104) -> input tiles + rollout row t ----------------
+            for (int i = tid; i < NW_ROWS * Kp0; i += NW_THREADS) {
+                const int rr = i / Kp0, j = i - rr * Kp0, ge = g0 + rr;
+                float x = 0.f;
+                if (ge < E && j < O) {
+                    x = xs[ge * O + j];
+                    if (q.norm_obs) x = obs_scale(x, s_mean[j], s_istd[j], q.clip_obs);
+                    q.ro_obs[((size_t)t * E + ge) * O + j] = x;
+                }
+                lds[lay.w_total + (rr >> 4) * lay.pipe_total + lay.x[0] + (rr & 15) * lay.ldx[0] + j] = x;
+            }
+            lds_barrier();
+            // ---- forward: narrow_step_kernel's, written out (see the Gaussian kernel) ----------------------------------------------
+            for (int l = 0; l < L; ++l) {
+                const float* bias = par + net.par_b[l];
+                float* Ys = P + lay.x[l + 1]; const int ldy = lay.ldx[l + 1];
+                auto ep = [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+                    const float b = bias[col];
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) Ys[(4 * g + rr) * ldy + col] = fast_tanh(acc[rr] + b);
+                };
+                if (live_pipe) {
+                    if (l == 0) nw_dense<KP0>(P + lay.x[0], lay.ldx[0], Kp0, lds + lay.wf[0], lay.wf_ld[0], S::Hp(net, 0), ep);
+                    else nw_dense<HP>(P + lay.x[l], lay.ldx[l], S::Hp(net, l - 1), lds + lay.wf[l], lay.wf_ld[l], S::Hp(net, l), ep);
+                }
+                lds_barrier();
+            }
+            const float* hL = P + lay.x[L]; const int ldh = lay.ldx[L]; const int HpL = S::Hp(net, L - 1);
+            float* mus = P + lay.mu; const int ldm = lay.ldm;
+            if (live_pipe) nw_dense<HP>(hL, ldh, HpL, lds + lay.wh, lay.wh_ld, Ap, [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+                const float b = par[net.par_bmu + col];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) mus[(4 * g + k) * ldm + col] = acc[k] + b;
+            });
+            lds_barrier();
+            // ---- (MASK) the mask of row t: posted by the host's act call, which may come long after the transition that started this row -----
+            float mv[4] = {1.0f, 1.0f, 1.0f, 1.0f}; bool mk[4] = {true, true, true, true};      // mv: the words as the host wrote them
+            if constexpr (MASK) {
+                if (g0 == 0) {
+                    if (tid == 0) {
+                        unsigned n = 0; int ok = 1;
+                        while (peer_ld_sys(q.ctl + PCTL_MASK) < (unsigned)(t + 1)) {
+                            if (++n > q.poll_cap || peer_ld_sys(q.ctl + PCTL_STOP)) { ok = 0; break; }
+                            __builtin_amdgcn_s_sleep(4);
+                        }
+                        *s_ok = ok;
+                    }
+                    __syncthreads();
+                    if (!*s_ok) { parked = true; break; }           // bounded wait over (or stop requested): save the state and leave; row t - 1 is booked
+                    __atomic_thread_fence(__ATOMIC_ACQUIRE);        // system scope: the mask's bytes are read after its sequence word
+                }
+                if (grow < E) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = part + 16 * k;
+                        if (j < A) { mv[k] = q.host_mask[(size_t)grow * A + j]; mk[k] = mv[k] != 0.f; q.ro_mask[((size_t)t * E + grow) * A + j] = mv[k]; }
+                    }
+                }
+            }
+            // ---- sample + neglogp: narrow_step_kernel<cat|mcat[,mask]>'s head (nw_host_step_discrete's statements) -----------------------------
+            if (live_pipe) {
+                if constexpr (!MCAT) {
+                    // the MASKed pair starts at A ("none yet"); a row without any allowed category (refused by the host checks) ends at A and is brought
+                    // back inside the tile
+                    float bp = -INFINITY, bl = -INFINITY;
+                    int ip = MASK ? A : 0, il = MASK ? A : 0;
+                    float lk[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = part + 16 * k;
+                        lk[k] = 0.f;
+                        if (j < A) {
+                            const float l = mus[r * ldm + j];
+                            lk[k] = l;
+                            const float pl = gumbel(l, uk[k]);
+                            if (mk[k]) { cat_take<MASK>(pl, j, A, bp, ip); cat_take<MASK>(l, j, A, bl, il); }
+                        }
+                    }
+                    group16_argmax(bp, ip);
+                    group16_argmax(bl, il);
+                    if constexpr (MASK) ip = min(ip, A - 1);
+                    const float m = bl;
+                    float z = 0.f, la = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = part + 16 * k;
+                        if (j < A) {
+                            if (j == ip) la = lk[k] - m;              // (one lane of the row holds it; the others add zeros)
+                            if (mk[k]) z += expf(lk[k] - m);
+                        }
+                    }
+                    z = group16_sum(z); la = group16_sum(la);
+                    if (part == 0 && grow < E) {
+                        q.ro_act[(size_t)t * E + grow] = (float)ip; if (q.host_mode) q.host_act[grow] = (float)ip;
+                        q.ro_nlp[(size_t)t * E + grow] = logf(z) - la;
+                    }
+                } else {
+                    // the components walked over the lane's four columns; lane k of the row keeps component k's index
+                    float lk[4], pk[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = part + 16 * k;
+                        lk[k] = j < A ? mus[r * ldm + j] : 0.f;
+                        pk[k] = gumbel(lk[k], uk[k]);
+                    }
+                    float nlp = 0.f, my_a = 0.f;
+                    for (int c = 0; c < comp.K; ++c) {
+                        const int o = comp.off[c], e = comp.off[c + 1];
+                        float bp = -INFINITY, bl = -INFINITY;
+                        int ip = MASK ? e : o, il = MASK ? e : o;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int j = part + 16 * k;
+                            if (j >= o && j < e && mk[k]) { cat_take<MASK>(pk[k], j, e, bp, ip); cat_take<MASK>(lk[k], j, e, bl, il); }
+                        }
+                        group16_argmax(bp, ip);
+                        group16_argmax(bl, il);
+                        if constexpr (MASK) ip = min(ip, e - 1);
+                        const float m = bl;
+                        float z = 0.f, la = 0.f;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int j = part + 16 * k;
+                            if (j >= o && j < e) {
+                                if (j == ip) la = lk[k] - m;          // (one lane of the row holds it; the others add zeros)
+                                if (mk[k]) z += expf(lk[k] - m);
+                            }
+                        }
+                        z = group16_sum(z); la = group16_sum(la);
+                        const float nk = logf(z) - la;
+                        nlp = c == 0 ? nk : nlp + nk;
+                        if (part == c) my_a = (float)(ip - o);
+                    }
+                    if (part < comp.K && grow < E) {
+                        q.ro_act[((size_t)t * E + grow) * q.Aw + part] = my_a;
+                        if (q.host_mode) q.host_act[(size_t)grow * q.Aw + part] = my_a;
+                    }
+                    if (part == 0 && grow < E) q.ro_nlp[(size_t)t * E + grow] = nlp;
+                }
+            }
+        }
+        if (parked) break;
+        if (q.host_mode) {
+            // ---- publish the actions, wait for the host's transition ---------------------------------------------------------------
+            __threadfence_system();                             // every thread's stores into host_act have landed
+            __syncthreads();
+            if (tid == 0) {
+                peer_st_sys(q.ctl + PCTL_D2H, (unsigned)(t + 1));
+                unsigned n = 0; int ok = 1;
+                while (peer_ld_sys(q.ctl + PCTL_H2D) < (unsigned)(t + 1)) {
+                    if (++n > q.poll_cap || peer_ld_sys(q.ctl + PCTL_STOP)) { ok = 0; break; }
+                    __builtin_amdgcn_s_sleep(4);
+                }
+                *s_ok = ok;
+            }
+            __syncthreads();
+            if (!*s_ok) break;                                  // bounded wait over (or stop requested): save the state and leave
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);            // system scope: the transition's bytes are read after its sequence word
+            read_host();
+        } else {
+            // ---- env transition (counter hash) -> new raw observations, rewards, dones -------------------------------------------
+            const uint32_t env_step = q.step0 + (uint32_t)t + 1u;
+            for (int i = tid; i < E * (O + 2); i += NW_THREADS) {
+                int e, j;
+                const uint32_t hsh = seeded_env_elem(q.seed, q.env0, env_step, i, O, e, j);
+                if (j < O) xs[e * O + j] = seeded_value(hsh);
+                else if (j == O) rs[e] = seeded_value(hsh);
+                else rs[ES + e] = seeded_done(hsh);
+            }
+        }
+        lds_barrier();
+        bookkeeping(t);
+        booked = t + 1;
+        lds_barrier();
+    }
+    // ---- exit: the state goes home ----------------------------------------------------------------------------------------------
+    for (int i = tid; i < E * O; i += NW_THREADS) q.st.raw_obs[i] = xs[i];
+    if (tid < O) { q.st.obs_mean[tid] = s_mean[tid]; q.st.obs_var[tid] = s_var[tid]; }
+    if (tid < E) { q.st.done[tid] = rs[ES + tid]; q.st.ret[tid] = rs[2 * ES + tid]; }
+    if (tid == 0) *q.st.obs_count = obs_cnt;
+    if (tid == 64) { *q.st.ret_mean = s_retstat[0]; *q.st.ret_var = s_retstat[1]; *q.st.ret_count = ret_cnt; }
+    if (q.host_mode) {
+        __threadfence_system();
+        __syncthreads();
+        if (tid == 0) peer_st_sys(q.ctl + PCTL_EXIT, 1u + (unsigned)booked);
+    }
+}
+
+template <int KP0, int HP, int AP, int LL, bool MULTI, bool CAT, bool MASK>
+__global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, NwLayout lay, NwRolloutArgsD q) {
+    static_assert(CAT, "the discrete overloads: a form of the categorical head");
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwRolloutArgsD)>();
+    nw_rollout_discrete<KP0, HP, AP, LL, MULTI, MASK, false>(net, lay, q, CompTable{});
+}
+template <int KP0, int HP, int AP, int LL, bool MULTI, bool CAT, bool MASK, bool MCAT>
+__global__ __launch_bounds__(NW_THREADS) void narrow_rollout_kernel(NetDev net, NwLayout lay, NwRolloutArgsDM q) {
+    static_assert(MCAT && CAT, "the multi-categorical overload: a form of the categorical head");
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwRolloutArgsDM)>();
+    nw_rollout_discrete<KP0, HP, AP, LL, MULTI, MASK, true>(net, lay, q, q.comp);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // Host-Env rollout step for small environment counts (n_envs <= 32; BASELINE configs[1]: ONE environment stepped on the
 // host): one launch per env step instead of {H2D copy, statistics kernel, policy step of both towers, D2H copy}.

@@ -39,7 +39,8 @@ const char* kAliases[][2] = {{"-d", "dir"}, {"--dir", "dir"}, {"-p", "path"}, {"
                              {"--explicit_dir", "explicit_dir"}, {"--dump_dir", "dump_dir"}, {"--time_limit", "time_limit"},
                              {"--discrete_kernels", "discrete_kernels"}, {"--target_kl", "target_kl"}};
 const char* kSwitches[][2] = {{"-r", "resume"}, {"--resume", "resume"}, {"-v", "verbose"}, {"--verbose", "verbose"}, {"--seeded", "seeded"},
-                              {"--replica_saves", "replica_saves"}, {"--ctl_selftest", "ctl_selftest"}, {"--no_bootstrap_truncated", "no_bootstrap_truncated"}};
+                              {"--replica_saves", "replica_saves"}, {"--ctl_selftest", "ctl_selftest"}, {"--no_bootstrap_truncated", "no_bootstrap_truncated"},
+                              {"--resident_rollout", "resident_rollout"}};
 
 // raw little-endian arrays: the parity hooks' on-disk format (--explicit_dir / --dump_dir; tests/test_host_dp.py writes and reads them with numpy)
 template <typename T>
@@ -72,6 +73,7 @@ int main(int argc, char** argv) {
                         "                   [--hidden 256,256] [--saves N --dir DIR --id ID] [--path CKPT_PREFIX] [--resume] [--seeded] [--seed N]\n"
                         "                   [--obs 36   (with --seeded: observation width of the mock environment; 36 = the hexapod that observes its velocities)]\n"
                         "                   [--time_limit N] [--no_bootstrap_truncated] [--discrete_kernels narrow|pair|generic] [--target_kl X]\n"
+                        "                   [--resident_rollout]\n"
                         "  --cliprange_vf (--cr_vf): value-function clipping; < 0 = clip with --cr (the default, -1), >= 0 = its own range, inf or off = none\n"
                         "  --target_kl X: early stopping; a train step whose approxkl exceeds 1.5 X is not applied and ends its update (0 = off, the default;\n"
                         "                 one GPU, fp32 path)\n"
@@ -80,7 +82,9 @@ int main(int argc, char** argv) {
                         "  --discrete_kernels: kernels of a discrete environment's categorical policy; narrow = the LDS-resident family where the network's shape\n"
                         "                      qualifies (hidden widths <= 64), pair = the [256,256] train kernel pair where it qualifies (--hidden 256,256),\n"
                         "                      generic = the generic fp32 family (the default).  A multi-discrete environment's multi-categorical policy\n"
-                        "                      likewise (at most 64 logits in all).  Continuous environments: no effect\n");
+                        "                      likewise (at most 64 logits in all).  Continuous environments: no effect\n"
+                        "  --resident_rollout: with --discrete_kernels narrow, a discrete or multi-discrete environment's rollout is served by one resident kernel\n"
+                        "                      (at most 64 environments, one GPU; ppo_set_rollout_resident).  Anywhere else: no effect\n");
             return 0;
         }
         for (auto& al : kAliases) if (a == al[0] && i + 1 < argc) { f.kv[al[1]] = argv[++i]; ok = true; break; }
@@ -174,6 +178,7 @@ int main(int argc, char** argv) {
             if (PPO2::create_handle(cfg, *probe, &h, dk == "narrow", dk == "pair" ? PPO_ACT_PAIR_KERNELS : 0) != 0) throw std::runtime_error(ppo_last_error(nullptr));
             if (ppo_init_orthogonal(h, (uint64_t)f.num("seed", 0)) != 0) throw std::runtime_error(ppo_last_error(h));     // same seed on every rank: replicated weights
         }
+        if (f.has("resident_rollout") && ppo_set_rollout_resident(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));      // (only the bit is recorded unless the narrow discrete kernels took effect)
         const std::string xdir = f.str("explicit_dir", ""), ddir = f.str("dump_dir", "");
         if (!xdir.empty()) {
             const std::vector<float> theta = read_raw<float>(xdir + "/theta.f32", false);

@@ -182,6 +182,26 @@ struct ppo_host_args {
     int multi_masked;            // ppo_host_learn_multi: the environments also carry IActionMask
     int host_step_fused;         // ppo_set_host_step_fused(h, 1) on the created handle before PPO2 sees it: the one-launch host-Env step of a narrow discrete handle (discrete_kernels == 1, <= 32 environments); nothing changes anywhere else
 };
+// ppo_set_rollout_resident(h, 1) on the handle the next learn entry creates (run_learn, the masked and the multi entry), directly behind the host_step_fused line:
+// the resident rollout of a narrow discrete handle (discrete_kernels == 1, <= 64 environments); nothing changes anywhere else.  A process-wide default set through
+// ppo_host_set_rollout_resident, not a member of ppo_host_args: that struct's layout and last member are pinned by tests/test_narrow_host_step.py.
+static int g_rollout_resident = 0;
+void ppo_host_set_rollout_resident(int on) { g_rollout_resident = on != 0; }
+// ppo_kernel_counts of the handle of the last ppo_host_learn_masked run, taken before the handle is destroyed (that entry has no count outputs of its own)
+static char g_last_count_names[64][32];
+static long long g_last_counts[64];
+static int g_last_n_counts = 0;
+static void keep_kernel_counts(ppo_handle* h) {
+    int64_t c64[64];
+    g_last_n_counts = ppo_kernel_counts(h, 64, g_last_count_names, c64);
+    if (g_last_n_counts < 0) g_last_n_counts = 0;
+    for (int i = 0; i < g_last_n_counts; ++i) g_last_counts[i] = (long long)c64[i];
+}
+int ppo_host_last_kernel_counts(int max, char (*names)[32], long long* counts) {
+    const int n = g_last_n_counts < max ? g_last_n_counts : max;
+    for (int i = 0; i < n; ++i) { std::memcpy(names[i], g_last_count_names[i], 32); counts[i] = g_last_counts[i]; }
+    return n;
+}
 // the handle's action_dist for `env`: PPO2's choice, plus the opt-ins: the [256,256] pair for a categorical head, the one such a head needs on the bf16 path
 static int32_t host_action_dist(Env& env, const ppo_host_args* a) {
     int32_t d = PPO2::action_dist_for(env, a->discrete_kernels == 1);
@@ -234,6 +254,7 @@ static int run_learn(const ppo_host_args* a, ppo_host_result* out, const ppo_hos
           if (ppo_create_ex(&cfg, host_action_dist(*probe, a), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
+        if (g_rollout_resident && ppo_set_rollout_resident(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         if (x && x->theta_in && ppo_set_flat(h, 0, x->theta_in, ppo_num_params(h)) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<Env>> envs;
         auto make_env = [&](uint32_t i) -> Env* {
@@ -396,6 +417,7 @@ int ppo_host_learn_multi(const ppo_host_args* a, float* reward_curve, long long*
         if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, extra_flags) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
+        if (g_rollout_resident && ppo_set_rollout_resident(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         {
             EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, a->max_workers)), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
             struct Plain : Env, IActionMask, IMultiDiscrete {       // hides the EnvNormalize type to force the reference loop; the two mixins stay visible
@@ -594,6 +616,7 @@ int ppo_host_learn_masked(const ppo_host_args* a, float* reward_curve, long long
           if (ppo_create_ex(&cfg, host_action_dist(probe, a), &h) != 0) throw std::runtime_error(ppo_last_error(nullptr)); }
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
+        if (g_rollout_resident && ppo_set_rollout_resident(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
         std::vector<std::shared_ptr<MaskedTargetEnv>> kids;
         std::vector<std::shared_ptr<Env>> envs;
         for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MaskedTargetEnv>(1234u, (uint32_t)i, O, A)); envs.push_back(kids.back()); }
@@ -642,6 +665,7 @@ int ppo_host_learn_masked(const ppo_host_args* a, float* reward_curve, long long
                 obs = top.step(act)[0];
             }
         }
+        keep_kernel_counts(h);
         ppo_destroy(h);
         return 0;
     } catch (const std::exception& e) {

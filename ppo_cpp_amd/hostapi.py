@@ -109,7 +109,7 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
                 obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, nvec=None, masked=False, n_playback=0,
-                host_step_fused=False, target_kl=0.0):
+                host_step_fused=False, target_kl=0.0, rollout_resident=False):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
@@ -124,10 +124,23 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     "kernel_counts": the handle's ppo_kernel_counts after the run.
     host_step_fused=True: ppo_set_host_step_fused(h, 1) on the created handle (ppo_host_args::host_step_fused): with discrete_kernels="narrow" and at most 32
     environments the act side runs narrow_host_step_kernel<cat|mcat[,mask]>, one launch per env step; nothing changes anywhere else.
+    rollout_resident=True: ppo_set_rollout_resident(h, 1) on the created handle (through the process-wide default ppo_host_set_rollout_resident, cleared again when
+    the call returns): with discrete_kernels="narrow" and at most 64 environments the rollout is served by the resident kernel's discrete forms
+    (narrow_rollout_kernel<cat|mcat[,mask]>, one launch per rollout); nothing changes anywhere else.
     target_kl (default 0 = off): PPO2::set_target_kl, target-KL early stopping (include/ppo_hip.h, ppo_set_target_kl); "applied" [n_updates, 2] then holds the Adam
     steps applied / train steps of every update (ppo_host_explicit::target_kl / applied_out; not through the nvec form)."""
-    import numpy as np
     lib = load_host_library()
+    lib.ppo_host_set_rollout_resident(int(bool(rollout_resident)))
+    try:
+        return _learn_curve(lib, n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma, lam, seed, reference_loop, device, obs_dim, act_dim,
+                            discrete, cliprange_vf, discrete_kernels, compute_dtype, nvec, masked, n_playback, host_step_fused, target_kl)
+    finally:
+        lib.ppo_host_set_rollout_resident(0)
+
+
+def _learn_curve(lib, n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma, lam, seed, reference_loop, device, obs_dim, act_dim,
+                 discrete, cliprange_vf, discrete_kernels, compute_dtype, nvec, masked, n_playback, host_step_fused, target_kl):
+    import numpy as np
     a = HostArgs()
     if nvec is not None:
         nvec = [int(x) for x in nvec]
@@ -211,11 +224,12 @@ def learn_time_limit(n_envs, n_steps, hidden, n_updates, nminibatches, noptepoch
 
 
 def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
-                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, host_step_fused=False):
+                 obs_dim=18, act_dim=18, n_playback=0, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, host_step_fused=False, rollout_resident=False):
     """PPO2::learn on MaskedTargetEnv x n_envs (host/env/env_mock.hpp: DiscreteTargetEnv's task with about half of the categories forbidden at every step) behind
     VecEnv + EnvNormalize, with the library's own exploration noise and shuffles (ppo_host_learn_masked).  PPO2 finds the IActionMask mixin and masks by itself.
     Returns the mean un-normalised reward of every update's rollout [n_updates], the count of forbidden actions the environments received over the whole run, and
-    n_playback deterministic playback actions with their legality.  discrete_kernels, compute_dtype, host_step_fused: as in learn_curve."""
+    n_playback deterministic playback actions with their legality.  discrete_kernels, compute_dtype, host_step_fused, rollout_resident: as in learn_curve.
+    "kernel_counts": the handle's ppo_kernel_counts after the run."""
     import numpy as np
     lib = load_host_library()
     a = HostArgs()
@@ -235,10 +249,18 @@ def learn_masked(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, l
     forbidden = C.c_longlong(-1)
     r = HostResult()
     fp = C.POINTER(C.c_float)
-    if lib.ppo_host_learn_masked(C.byref(a), out["reward_curve"].ctypes.data_as(fp), C.byref(forbidden), int(n_playback), out["playback_actions"].ctypes.data_as(fp),
-                                 out["playback_legal"].ctypes.data_as(fp), C.byref(r)) != 0:
+    lib.ppo_host_set_rollout_resident(int(bool(rollout_resident)))
+    try:
+        rc = lib.ppo_host_learn_masked(C.byref(a), out["reward_curve"].ctypes.data_as(fp), C.byref(forbidden), int(n_playback), out["playback_actions"].ctypes.data_as(fp),
+                                       out["playback_legal"].ctypes.data_as(fp), C.byref(r))
+    finally:
+        lib.ppo_host_set_rollout_resident(0)
+    if rc != 0:
         raise RuntimeError(r.error.decode())
     out["forbidden_received"] = int(forbidden.value)
+    names = ((C.c_char * 32) * 64)(); cnt = (C.c_longlong * 64)()
+    n = lib.ppo_host_last_kernel_counts(64, names, cnt)
+    out["kernel_counts"] = {names[i].value.decode(): int(cnt[i]) for i in range(n)}
     return out
 
 
