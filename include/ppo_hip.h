@@ -118,7 +118,7 @@ int ppo_create(const ppo_config* cfg, ppo_handle** out);
 #define PPO_ACT_BF16_HEAD 0x200
 #define PPO_ACT_PAIR_KERNELS 0x400
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out);
-int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_CATEGORICAL */
+int ppo_action_dist(const ppo_handle* h);          /* PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL, PPO_ACT_MULTI_CATEGORICAL or PPO_ACT_MULTI_BINARY */
 /* ---- multi-categorical head: several independent choices per step (stable-baselines' MultiCategoricalProbabilityDistribution; env side: a multi-discrete space) ----
  * K components over ONE logits vector l = h_L W_pi + b_pi of width A = cfg->act_dim = n_0 + .. + n_{K-1}; component k owns columns S_k = [o_k, o_k + n_k), o_k the
  * running sum of the widths before it.  Tensor list, flat vector, orthogonal init and checkpoint tensors are those of a categorical handle with act_dim = A (4L+4
@@ -201,10 +201,36 @@ int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_compo
  * Any other bit is an error ("ppo_create_multi_ex: unknown flag bit 0x.."). */
 #define PPO_ACT_BF16_MULTI_HEAD 0x1000
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out);
-/* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian handle, 1 with nvec[0] = A for a categorical one */
+/* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian or multi-binary handle, 1 with nvec[0] = A for a categorical one */
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec);
-/* columns of one action row: A (Gaussian), 1 (categorical) or K (multi-categorical) */
+/* columns of one action row: A (Gaussian, multi-binary), 1 (categorical) or K (multi-categorical) */
 int ppo_action_width(const ppo_handle* h);
+/* Multi-binary action spaces (stable-baselines' BernoulliProbabilityDistribution over MultiBinary(A)): ppo_create_ex(cfg, PPO_ACT_MULTI_BINARY, out), A = cfg->act_dim
+ * >= 1 independent on / off decisions per step over the logits l = h_L W_pi + b_pi of width A.  (The name is multi_binary everywhere; "bernoulli" is no action_dist.)
+ *   Tensors: a categorical handle's 4L+4 (no pi/logstd; the padded logstd region of weights, gradient and both Adam slots keeps its place and is never moved).
+ *   Actions: A floats per row, each exactly 0 or 1: ppo_action_width = A, every buffer that holds action rows has the Gaussian handle's shape; ppo_action_dist = 3,
+ *   ppo_action_nvec = 0.  Noise: [n, A] uniforms in [0, 1), as for the categorical head; without explicit noise column j draws ctr_uniform(seed, row, step, j) under the
+ *   categorical head's keys.
+ *   Per element, with e = exp(-|l|), sp = log1p(e), q = e / (1 + e) (ppo_head.hpp: bern_parts, bern_nlp_elem, bern_entropy_elem, bern_grad_elem):
+ *     p = l >= 0 ? 1 / (1 + e) : q;  sampled x = u < p ? 1 : 0;  deterministic x = l > 0 ? 1 : 0 (tf.round(sigmoid(l)): a logit of +-0 gives 0)
+ *     neglogp_j = sp + (x_j == (l_j > 0) ? 0 : |l_j|)   (= TF's relu(l) - l x + log1p(exp(-|l|)));   H_j = sp + |l_j| q_j;   the row's neglogp and entropy: sums over j
+ *     d loss / d l_j = d_nlp (p_j - x_j) + ent_coef g l_j p_j (1 - p_j), p (1 - p) = e / (1 + e)^2; padding columns and dead rows get exactly +0; the aux (d logstd)
+ *     words are zeros.  This is the derivative of the SMOOTH identity softplus(l) - l x: at a logit of exactly +-0 TensorFlow's composed graph (and autograd of the
+ *     literal relu / abs expression) differentiates the kinks to 0 and gives another value there.
+ *   Surrogate, value loss, approxkl and clipfrac see the row's neglogp unchanged.  float32 against float64 at 4096 x 18 logits: neglogp within 3.0e-6 abs at a spread
+ *   of +-1.5, 9e-7 at +-40, 5e-7 at +-120; entropy within 3.0e-6 / 5e-7 / 2e-7; nothing overflows.
+ *   The handle always runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts, instead of the plain names) on any
+ *   hidden widths: never narrow, never train8_kernel, deferred Adam, the resident epoch kernel or a one-launch rollout -- the rules of an unflagged categorical handle.
+ *   PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS and PPO_ACT_BF16_HEAD beside it on a PPO_F32 handle are accepted and change nothing (same bits, same counts).
+ *   Every entry point of a categorical PPO_F32 handle works, actions [., A]; data parallel (ppo_dist_init, both shuffles) included.
+ *   Host checks before anything is uploaded: every action of ppo_train_step / ppo_rollout_upload field 1 is exactly 0 or 1 (the message names row and column; NaN is
+ *   refused); the masked entry points and ppo_set_action_masking refuse the handle ("action masks need a categorical ...").
+ *   Errors of ppo_create_ex, each naming the limit: act_dim < 1; compute_dtype PPO_BF16.  2 stays an "unknown action_dist" error, as does 3 with an unknown flag bit.
+ *   Measured on an MI355X (us of device time per call at 18 obs, hidden [256,256]; this head | a categorical handle of 18 categories | a
+ *   multi-categorical one with nvec = (2,) x 16): policy step 16.6 | 16.5 | 29.1 at 16 rows, 17.6 | 18.6 | 29.7 at 1024; train_fwd_bwd_kernel 25.5 | 24.3 | 39.4 at 64 rows,
+ *   26.6 | 26.0 | 40.4 at 2048.  The elementwise head is about 1 us SLOWER than <cat> per train launch; it has not been tuned.
+ *   Out of scope for this head: the narrow LDS-resident kernels, the [256,256] pair, the bf16 path, the fused host step and the resident rollouts, action masks. */
+#define PPO_ACT_MULTI_BINARY 3
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);

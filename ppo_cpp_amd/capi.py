@@ -54,7 +54,7 @@ def _f32(a, shape=None):
     return a
 
 
-ACTION_DISTS = {"gaussian": 0, "categorical": 1, "multi_categorical": 2}   # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL / PPO_ACT_MULTI_CATEGORICAL
+ACTION_DISTS = {"gaussian": 0, "categorical": 1, "multi_categorical": 2, "multi_binary": 3}   # PPO_ACT_GAUSSIAN / PPO_ACT_CATEGORICAL / PPO_ACT_MULTI_CATEGORICAL / PPO_ACT_MULTI_BINARY
 MAX_COMPONENTS = 16                                     # PPO_MAX_COMPONENTS
 ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS, OR-ed into ppo_create_ex's action_dist
 ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, likewise
@@ -94,6 +94,12 @@ class PPOHip:
     PPOHip(O, None, hidden, action_dist="multi_categorical", nvec=[..], compute_dtype=1, bf16_head=True).  Without it that combination is refused; on a
     compute_dtype=0 handle bf16_head changes nothing (no flag is passed).
 
+    action_dist="multi_binary" (PPO_ACT_MULTI_BINARY; stable-baselines' Bernoulli distribution over a MultiBinary space -- "bernoulli" is no action_dist here):
+    act_dim independent on / off decisions per step.  Actions are (n, act_dim) float arrays of exactly 0 or 1 (train_step and rollout_set("actions") refuse anything
+    else, naming row and column); explicit noise is (n, act_dim) uniforms, bit j is 1 where u_j < sigmoid(logit_j); act_deterministic gives logit_j > 0.  The tensor
+    list is a categorical handle's (no pi/logstd), `.nvec` is [].  compute_dtype=0 only; the handle runs policy_step_kernel<mbin> / train_fwd_bwd_kernel<mbin> on any
+    hidden widths, shape_kernels / pair_kernels / bf16_head are accepted and change nothing, and mask= raises the library's error.
+
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
     and update() train under them."""
@@ -129,7 +135,7 @@ class PPOHip:
         self.shape_kernels = bool(shape_kernels)
         self.bf16_head = bool(bf16_head)
         self.pair_kernels = bool(pair_kernels)
-        self._act_shape = (act_dim,) if action_dist == "gaussian" else (len(nvec),) if multi else ()      # per row
+        self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
             nv = (C.c_int32 * max(len(nvec), 1))(*nvec)
@@ -155,7 +161,7 @@ class PPOHip:
 
     @property
     def nvec(self):
-        """component widths as the handle reports them (ppo_action_nvec): [] Gaussian, [A] categorical, the K widths multi-categorical"""
+        """component widths as the handle reports them (ppo_action_nvec): [] Gaussian and multi-binary, [A] categorical, the K widths multi-categorical"""
         out = (C.c_int32 * MAX_COMPONENTS)()
         k = self.lib.ppo_action_nvec(self.h, MAX_COMPONENTS, out)
         return [int(out[i]) for i in range(max(k, 0))]

@@ -75,3 +75,27 @@ __device__ __forceinline__ float cat_grad_elem(float d_nlp, float ex, float z, f
     const float p = ex / z;
     return d_nlp * (p - (j == act ? 1.0f : 0.0f)) + ent_coef * g * (p * ((a0 - lz) + H));
 }
+
+// ---- multi-binary head (stable-baselines BernoulliProbabilityDistribution: A independent on / off decisions over the logits l in place of mu) -----------------------
+// One element, from e = exp(-|l|) (never overflows), sp = log1p(e) = softplus(-|l|), q = e / (1 + e) = the probability of the LESS likely value:
+//   p = sigmoid(l) = l >= 0 ? 1 / (1 + e) : q;  sample x = u < p (u uniform in [0, 1): p == 1 always gives 1, p == 0 always 0);  deterministic x = l > 0, which is
+//   tf.round(sigmoid(l)) -- a logit of +-0 gives 0
+//   neglogp = sp + (x == (l > 0) ? 0 : |l|)      = TF's sigmoid_cross_entropy_with_logits(l, x) = relu(l) - l x + log1p(exp(-|l|))
+//   entropy = sp + |l| q                         = the same expression with the label p
+//   d loss / d l = d_nlp (p - x) + ent_coef g l p (1 - p), p (1 - p) = e / (1 + e)^2: the derivative of the SMOOTH identity softplus(l) - l x.  At a logit of exactly
+//   +-0 TensorFlow's composed graph differentiates the relu and abs kinks to 0 and gives another value; this is the smooth one everywhere.
+// Padding columns and dead rows are not passed here: the caller writes exactly +0 for them.
+struct BernParts { float e, sp, q, p; };
+__device__ __forceinline__ BernParts bern_parts(float l) {
+    const float e = expf(-fabsf(l));
+    const float q = e / (1.0f + e);
+    return {e, log1pf(e), q, l >= 0.0f ? 1.0f / (1.0f + e) : q};
+}
+__device__ __forceinline__ float bern_sample(float p, float u) { return u < p ? 1.0f : 0.0f; }
+__device__ __forceinline__ float bern_mode(float l) { return l > 0.0f ? 1.0f : 0.0f; }
+__device__ __forceinline__ float bern_nlp_elem(BernParts b, float l, float x) { return b.sp + (((x != 0.0f) == (l > 0.0f)) ? 0.0f : fabsf(l)); }
+__device__ __forceinline__ float bern_entropy_elem(BernParts b, float l) { return b.sp + fabsf(l) * b.q; }
+__device__ __forceinline__ float bern_grad_elem(float d_nlp, BernParts b, float l, float x, float ent_coef, float g) {
+    const float d = 1.0f + b.e;
+    return d_nlp * (b.p - x) + ent_coef * g * (l * (b.e / (d * d)));
+}

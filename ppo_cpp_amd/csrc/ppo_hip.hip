@@ -70,7 +70,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK,
                      KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
                      KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
-                     KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK, KV_COUNT };
+                     KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
+                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_COUNT };
 static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
@@ -100,29 +101,32 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // a narrow categorical / multi-categorical handle with ppo_set_rollout_resident on, <= 64 environments: one per launch of the resident
                                        // rollout kernel's discrete instantiation (a rollout on the device env; behind a host Env one per rollout, plus one per relaunch after the
                                        // kernel parked itself), counted INSTEAD of the act launches of "narrow_step_kernel<cat|mcat[,mask]>" / "narrow_host_step<..>"
-                                       "narrow_rollout<cat>", "narrow_rollout<cat,mask>", "narrow_rollout<mcat>", "narrow_rollout<mcat,mask>"};
+                                       "narrow_rollout<cat>", "narrow_rollout<cat,mask>", "narrow_rollout<mcat>", "narrow_rollout<mcat,mask>",
+                                       // a multi-binary handle (ppo_create_ex with PPO_ACT_MULTI_BINARY): counted INSTEAD of the plain names of the generic fp32 family, the only one it runs
+                                       "policy_step_kernel<mbin>", "train_fwd_bwd_kernel<mbin>"};
 
-// The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat> or <mcat,mask>.  index(): its column below.
+// The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
-    bool cat, mask, multi;
-    int index() const { return multi ? 3 + mask : cat ? 1 + mask : 0; }
+    bool cat, mask, multi, bin;
+    int index() const { return bin ? 5 : multi ? 3 + mask : cat ? 1 + mask : 0; }
 };
 // which entry a launch of a kernel family with a head bumps: a row per family, a column per head form.  (The narrow Gaussian entries say whether the compile-time
-// shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.)
+// shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.  KV_COUNT: the family
+// has no kernel of that head, and no handle of that head reaches it -- a multi-binary handle runs the generic fp32 family only.)
 enum HeadFamily { KF_POLICY_STEP = 0, KF_TRAIN_FB, KF_TRAIN8, KF_NARROW_STEP_STATIC, KF_NARROW_STEP, KF_NARROW_TRAIN_STATIC, KF_NARROW_TRAIN, KF_NARROW_HOST_STEP, KF_BF16_STEP,
                   KF_BF16_TRAIN, KF_NARROW_ROLLOUT, KF_COUNT };
-constexpr KernelVariant kHeadVariant[KF_COUNT][5] = {
-    {KV_POLICY_STEP, KV_POLICY_STEP_CAT, KV_POLICY_STEP_CAT_MASK, KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK},
-    {KV_TRAIN_FB, KV_TRAIN_FB_CAT, KV_TRAIN_FB_CAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK},
-    {KV_TRAIN8, KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK},
-    {KV_NARROW_STEP_STATIC, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK},
-    {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK},
-    {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK},
-    {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK},
-    {KV_COUNT, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK},
-    {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK},
-    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK},
-    {KV_ROLLOUT_PERSISTENT, KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK}};
+constexpr KernelVariant kHeadVariant[KF_COUNT][6] = {
+    {KV_POLICY_STEP, KV_POLICY_STEP_CAT, KV_POLICY_STEP_CAT_MASK, KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_POLICY_STEP_MBIN},
+    {KV_TRAIN_FB, KV_TRAIN_FB_CAT, KV_TRAIN_FB_CAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK, KV_TRAIN_FB_MBIN},
+    {KV_TRAIN8, KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK, KV_COUNT},
+    {KV_NARROW_STEP_STATIC, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_COUNT},
+    {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_COUNT},
+    {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_COUNT},
+    {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_COUNT},
+    {KV_COUNT, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK, KV_COUNT},
+    {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_COUNT},
+    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK, KV_COUNT},
+    {KV_ROLLOUT_PERSISTENT, KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK, KV_COUNT}};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -149,12 +153,12 @@ struct ppo_handle {
     int CT = 1;                       // column tiles per wave in the dense layers (4 for wide nets)
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
-    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex)
+    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family only (never narrow, t8, dw2 or bf16)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
     bool bf16_multi_head = false;     // created with PPO_ACT_BF16_MULTI_HEAD as a multi-categorical PPO_BF16 handle (ppo_create_multi_ex): bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>
     bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical or multi-categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
-    int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian), 1 (categorical: the category index) or K (multi-categorical)
+    int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian; multi-binary: the bits), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
     // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
@@ -788,31 +792,35 @@ ObsNorm no_norm_fwd() { return ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}; }
 // A launch site decides the head once (head_of), turns it into compile-time constants once (with_head calls f with a HeadTag) and asks its family's picker
 // (bf16_sample_kernel / bf16_loss_kernel below; step_fn, train_fb_fn, nw_step_fn, nw_train_fn, train8_fn, nw_host_step_fn under "launches") for the instantiation.
 // ppo_create_ex asks the same pickers for every head the handle can launch (for_each_head) when it raises the dynamic-LDS limits.
-template <bool CAT, bool MASK, bool MULTI>
-struct HeadTag { static constexpr bool cat = CAT, mask = MASK, multi = MULTI; };
+template <bool CAT, bool MASK, bool MULTI, bool BIN = false>
+struct HeadTag { static constexpr bool cat = CAT, mask = MASK, multi = MULTI, bin = BIN; };
+using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn) know it, no other
 using GaussHead = HeadTag<false, false, false>;
 
 // (a mask on a Gaussian handle: the entry points and launch_step refuse it before any launch)
 static Head head_of(const ppo_handle* h, bool masked) {
     const bool multi = h->dist == PPO_ACT_MULTI_CATEGORICAL, cat = multi || h->dist == PPO_ACT_CATEGORICAL;
-    return Head{cat, cat && masked, multi};
+    return Head{cat, cat && masked, multi, h->dist == PPO_ACT_MULTI_BINARY};
 }
 template <class F>
 static void with_head(Head hd, F&& f) {
     if (hd.multi) { if (hd.mask) f(HeadTag<true, true, true>{}); else f(HeadTag<true, false, true>{}); }
     else if (hd.cat) { if (hd.mask) f(HeadTag<true, true, false>{}); else f(HeadTag<true, false, false>{}); }
+    else if (hd.bin) f(MbinTag{});
     else f(GaussHead{});
 }
-// every head a handle of this distribution can launch: Gaussian one; categorical and multi-categorical two (plain, masked)
+// every head a handle of this distribution can launch: Gaussian and multi-binary one; categorical and multi-categorical two (plain, masked)
 template <class F>
 static void for_each_head(const ppo_handle* h, F&& f) {
     with_head(head_of(h, false), f);
-    if (h->dist != PPO_ACT_GAUSSIAN) with_head(head_of(h, true), f);
+    if (h->dist == PPO_ACT_CATEGORICAL || h->dist == PPO_ACT_MULTI_CATEGORICAL) with_head(head_of(h, true), f);
 }
-// the arguments of a launch with head tag T: `a` itself, or (multi-categorical) the M struct -- `a` with the component table behind it
+// the arguments of a launch with head tag T: `a` itself, (multi-categorical) the M struct -- `a` with the component table behind it -- or (multi-binary) `a` under
+// the type that picks that head's kernel overloads
 template <class M, class T, class Base>
 static auto head_args(T, const ppo_handle* h, const Base& a) {
     if constexpr (T::multi) { M m{}; static_cast<Base&>(m) = a; m.comp = h->comp; return m; }
+    else if constexpr (T::bin) { BinArgs<Base> b{}; static_cast<Base&>(b) = a; return b; }
     else return a;
 }
 
@@ -1191,13 +1199,13 @@ static int ladder_rung(const ppo_handle* h) {
 }
 template <class T>
 static auto step_fn(T, int rung) {
-#define X(CT, KS, CTH, WIDE) return policy_step_kernel<CT, KS, CTH, WIDE, T::cat, T::mask, T::multi>
+#define X(CT, KS, CTH, WIDE) if constexpr (T::bin) return policy_step_kernel<CT, KS, CTH, WIDE, MbinHead>; else return policy_step_kernel<CT, KS, CTH, WIDE, T::cat, T::mask, T::multi>
     switch (rung) { case RUNG_WIDE4: X(4, 2, 0, true); case RUNG_WIDE1: X(1, 1, 0, true); case RUNG_42_EARLY: case RUNG_42: X(4, 2, 2, false); case RUNG_4: X(4, 2, 0, false); default: X(1, 1, 0, false); }
 #undef X
 }
 template <class T>
 static auto train_fb_fn(T, int rung) {
-#define X(CT, KS, CTH, WIDE, EARLY) return train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, T::cat, T::mask, T::multi>
+#define X(CT, KS, CTH, WIDE, EARLY) if constexpr (T::bin) return train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, MbinHead>; else return train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, T::cat, T::mask, T::multi>
     switch (rung) { case RUNG_WIDE4: X(4, 2, 0, true, false); case RUNG_WIDE1: X(1, 1, 0, true, false); case RUNG_42_EARLY: X(4, 2, 2, false, true); case RUNG_42: X(4, 2, 2, false, false);
                     case RUNG_4: X(4, 2, 0, false, false); default: X(1, 1, 0, false, false); }
 #undef X
@@ -1878,7 +1886,7 @@ int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_co
 
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {
     if (!h) return -1;
-    if (h->dist == PPO_ACT_GAUSSIAN) return 0;
+    if (h->dist == PPO_ACT_GAUSSIAN || h->dist == PPO_ACT_MULTI_BINARY) return 0;
     if (h->dist == PPO_ACT_CATEGORICAL) { if (max > 0 && nvec) nvec[0] = h->net.A; return 1; }
     for (int k = 0; k < h->comp.K && k < max && nvec; ++k) nvec[k] = h->comp.off[k + 1] - h->comp.off[k];
     return h->comp.K;
@@ -1890,6 +1898,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (!cfg || !out) return fail(nullptr, "ppo_create: null argument");
     *out = nullptr;
     if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
+    if ((action_dist & 0xff) == PPO_ACT_MULTI_BINARY && cfg->obs_dim >= 1 && cfg->act_dim < 1)
+        return fail(nullptr, "ppo_create_ex: a multi-binary head needs act_dim >= 1 bits (got %d)", (int)cfg->act_dim);
     if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
     const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the flags; whatever else is left must be a distribution
     const bool bf16_head = (action_dist & PPO_ACT_BF16_HEAD) != 0;
@@ -1897,8 +1907,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     const bool bf16_multi_head = nvec && (action_dist & PPO_ACT_BF16_MULTI_HEAD) != 0;      // (ppo_create_multi_ex only: from ppo_create_ex the bit stays in action_dist and is refused below)
     if (nvec) action_dist &= ~(int32_t)PPO_ACT_BF16_MULTI_HEAD;
     action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS);
-    if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
-        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN or PPO_ACT_CATEGORICAL, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
+    if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && action_dist != PPO_ACT_MULTI_BINARY && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
                              "a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
@@ -1906,6 +1916,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
         return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && cfg->act_dim > 128)
         return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
+    if (action_dist == PPO_ACT_MULTI_BINARY && cfg->compute_dtype == PPO_BF16)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
     for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -1914,7 +1926,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     ppo_handle* h = new ppo_handle();
     h->cfg = *cfg;
     h->dist = action_dist;
-    h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN;          // (a Gaussian handle takes its shape's kernels anyway: the flag changes nothing)
+    h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_MULTI_BINARY;   // (a Gaussian handle takes its shape's kernels anyway, a multi-binary one never: the flag changes nothing)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
     h->bf16_multi_head = bf16_multi_head && cfg->compute_dtype == PPO_BF16;   // (PPO_F32: the flag changes nothing)
     h->pair_kernels = pair_kernels && (action_dist == PPO_ACT_CATEGORICAL || action_dist == PPO_ACT_MULTI_CATEGORICAL) && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
@@ -2258,6 +2270,16 @@ static int check_multi_actions(ppo_handle* h, const char* who, const float* acti
         }
     return 0;
 }
+// every action value of a multi-binary handle's rows [rows, A] is exactly 0 or 1 (a NaN is neither)
+static int check_binary_actions(ppo_handle* h, const char* who, const float* actions, size_t rows) {
+    const size_t A = (size_t)h->net.A;
+    for (size_t i = 0; i < rows; ++i)
+        for (size_t j = 0; j < A; ++j) {
+            const float x = actions[i * A + j];
+            if (!(x == 0.f || x == 1.f)) return fail(h, "%s: row %lld, column %d: action %g is not 0 or 1 (a multi-binary handle)", who, (long long)i, (int)j, (double)x);
+        }
+    return 0;
+}
 static int need_categorical(ppo_handle* h, const char* who) {
     if (h->dist != PPO_ACT_CATEGORICAL && h->dist != PPO_ACT_MULTI_CATEGORICAL) return fail(h, "%s: action masks need a categorical (PPO_ACT_CATEGORICAL) handle", who);
     return 0;
@@ -2376,6 +2398,7 @@ int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float*
     if (n < 2) return fail(h, "ppo_train_step: n=%d (the reference asserts more than one row, ppo2.hpp:402)", n);
     if (mask && need_categorical(h, "ppo_train_step_masked")) return -1;
     if (h->dist == PPO_ACT_MULTI_CATEGORICAL && check_multi_actions(h, "ppo_train_step", actions, (size_t)n)) return -1;
+    if (h->dist == PPO_ACT_MULTI_BINARY && check_binary_actions(h, "ppo_train_step", actions, (size_t)n)) return -1;
     if (h->dist == PPO_ACT_CATEGORICAL)
         for (int32_t i = 0; i < n; ++i) {
             const float x = actions[i];
@@ -3536,6 +3559,7 @@ int ppo_rollout_upload(ppo_handle* h, int field, const float* src, int64_t count
     if (!p || (size_t)count != c) return fail(h, "ppo_rollout_upload: bad field/count");
     if (field == 8 && check_masks(h, "ppo_rollout_upload", src, (size_t)h->E * h->T, nullptr)) return -1;
     if (field == 1 && h->dist == PPO_ACT_MULTI_CATEGORICAL && check_multi_actions(h, "ppo_rollout_upload", src, (size_t)h->E * h->T)) return -1;
+    if (field == 1 && h->dist == PPO_ACT_MULTI_BINARY && check_binary_actions(h, "ppo_rollout_upload", src, (size_t)h->E * h->T)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     HIP_OK(h, hipMemcpy(p, src, c * sizeof(float), hipMemcpyHostToDevice));
     return 0;

@@ -1006,6 +1006,105 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
     PSTAMP(5);
 }
 
+// Multi-binary head (stable-baselines BernoulliProbabilityDistribution, bern_* of ppo_head.hpp; "policy_step_kernel<mbin>" of ppo_kernel_counts): the action is A
+// floats per row, each exactly 0 or 1, `noise` holds the uniforms u [n,A] (null: ctr_uniform under the categorical head's keys), x_j = u_j < sigmoid(l_j),
+// det_action_j = l_j > 0.  Elementwise, in the Gaussian branch's lane geometry -- lane `part` owns columns part, part + 16, .. -- with one group16_sum for the row's
+// neglogp: no maximum, no argmax, no component walk.
+// A kernel of its own, not a further template parameter or a shared body: either changes the other heads' symbols or (measured: register counts of 41 of them, the
+// instruction stream of 4) their machine code.  Everything in front of and behind the head is policy_step_kernel's, statement for statement; the arguments are the
+// Gaussian head's under a type of their own (StepArgsB), and the name is an overload with a head TYPE where policy_step_kernel has its first bool.
+struct MbinHead {};
+template <class Base> struct BinArgs : Base {};
+using StepArgsB = BinArgs<StepArgs>;
+template <int CT, int KS, int CTH, bool WIDE, class HEAD>
+__global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev net, StepArgsB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    PSTAMP(0);
+    warm_kernargs<sizeof(NetDev) + sizeof(a)>();
+    const int tower = blockIdx.y;
+    if (tower == 1 && !a.value) return;
+    if (tower == 0 && !a.action && !a.det_action && !a.neglogp && !a.obs_out) return;
+    const int row0 = blockIdx.x * ROWS_PER_BLOCK;
+    const int ld0 = net.Kp0 + LDS_PAD;
+    WRing<CT, KS> wpre;
+    HeadFrag<CTH> hpre;
+    dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][0], net.Hp[0], net.Hp[0], net.Kp0);
+    float* par = lds + net.lds_par - net.par_skip;      // indexed with absolute mirror offsets
+    stage_block_inputs(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, a.nz,
+                       tower == 0 ? a.obs_out : nullptr, nullptr, RowScalars{nullptr, nullptr, nullptr, nullptr, nullptr, 0}, nullptr, nullptr);
+    lds_barrier();
+    PSTAMP(1);
+    int K = net.Kp0, ldx = ld0;
+    for (int l = 0; l < net.L; ++l) {
+        const int Np = net.Hp[l], ldy = Np + LDS_PAD;
+        dense_tile<CT, KS, EP_BIAS_TANH>(wpre, a.theta + net.w_off[tower][l], Np, WIDE ? a.par + tower * net.par_total + net.par_b[l] : par + net.par_b[l], lds + net.lds_h[l], ldx, K,
+                                         lds + net.lds_h[l + 1], ldy, Np, nullptr, 0, nullptr, 0, row0, a.n, [&]() __attribute__((always_inline)) {
+                                             if (l + 1 < net.L) dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][l + 1], net.Hp[l + 1], net.Hp[l + 1], Np);
+                                             else if constexpr (CTH > 0) head_prefetch<CTH>(hpre.w, a.theta + net.wmu_off, net.Ap, Np);   // (both towers: uniform code)
+                                         });
+        lds_barrier();
+        if (l == 0) PSTAMP(2);
+        K = Np; ldx = ldy;
+    }
+    PSTAMP(3);
+    const float* hL = lds + net.lds_h[net.L];
+    if (tower == 1) {
+        const float v = value_head(hL, ldx, K, par + net.par_wv, par[net.par_bv]);
+        const int row = row0 + (threadIdx.x >> 4);
+        if ((threadIdx.x & 15) == 0 && row < a.n) a.value[row] = v;
+        PSTAMP(5);
+        return;
+    }
+    policy_head<CTH>(net, a.theta, hpre, hL, ldx, K, lds);
+    PSTAMP(4);
+    const float* mus = lds + net.lds_mu;
+    const int ldm = net.Ap + LDS_PAD;
+    // sampling + neglogp: 16 lanes per row, each lane owns bits j = part, part+16, ...
+    const int r = threadIdx.x >> 4, part = threadIdx.x & 15;
+    const int row = row0 + r;
+    float snlp = 0.f;
+    for (int j = part; j < net.A; j += 16) {
+        const float l = mus[r * ldm + j];
+        const BernParts b = bern_parts(l);
+        float u = 0.5f;
+        if (row < a.n) u = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+        const float x = bern_sample(b.p, u);
+        snlp += bern_nlp_elem(b, l, x);
+        if (row < a.n) {
+            if (a.action) a.action[(size_t)row * net.A + j] = x;
+            if (a.det_action) a.det_action[(size_t)row * net.A + j] = bern_mode(l);
+        }
+        if (a.host_action) lds[net.lds_mu + r * ldm + j] = x;         // (this lane owns element (r, j): the logit has been read)
+    }
+    snlp = group16_sum(snlp);
+    if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = snlp;
+    if (a.host_action) {
+        // the publish of policy_step_kernel with Aw = A: whole 16-byte pieces of the block's contiguous [16][A] rows, the odd elements one by one, ONE flag word last
+        lds_barrier();
+        const int Aw = net.A;                                            // action columns per row
+        const int live = min(ROWS_PER_BLOCK, a.n - row0) * Aw;          // elements of this block
+        float* dst = a.host_action + (size_t)row0 * Aw;
+        const float* tile = lds + net.lds_mu;
+        for (int k = threadIdx.x; 4 * k < live; k += BLOCK_THREADS) {
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const int e = min(4 * k + i, live - 1); v[i] = tile[(e / Aw) * ldm + e % Aw]; }
+            if (4 * k + 3 < live) {
+                typedef float f32x4_t __attribute__((ext_vector_type(4)));
+                const f32x4_t q = {v[0], v[1], v[2], v[3]};
+                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst + 4 * k), "v"(q) : "memory");
+            } else {
+                for (int i = 0; 4 * k + i < live; ++i) __hip_atomic_store(dst + 4 * k + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(a.host_flags + blockIdx.x, a.host_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    PSTAMP(5);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Train model forward + loss + backward down to the pre-activation gradients of every layer, for one 16-row
 // tile of the minibatch and one tower.  Everything a row needs stays in LDS; what the weight-gradient kernel
@@ -1342,6 +1441,216 @@ __global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net
         float* t = dcur; dcur = dnext; dnext = t;            // dcur = dY_l
         const int Np = net.Hp[l], ldd = Np + LDS_PAD;
         for (int j = tid; j < Np; j += BLOCK_THREADS) {      // db_l = sum_rows dY_l  (…/Add_grad/Sum_1)
+            float s = 0.f;
+            for (int q = 0; q < ROWS_PER_BLOCK; ++q) s += dcur[q * ldd + j];
+            slot[net.slot_db[l] + j] = s;
+        }
+        if (l > 0) {                                         // first-layer dX is never needed (obs is a placeholder)
+            const int Kp = net.Hp[l - 1];
+            // dY_{l-1} = (dY_l * W_l^T) .* (1 - h_l^2), W_l^T = transposed copy [Hp_l][Hp_{l-1}]
+            dense_tile<CT, KS, EP_TANHGRAD>(wpre, a.thetaT + net.wT_off[tower][l], Kp, nullptr, dcur, ldd, Np, dnext, Kp + LDS_PAD, Kp,
+                                            WIDE ? a.hg[tower][l - 1] + (size_t)row0 * Kp : lds + net.lds_h[l], WIDE ? Kp : Kp + LDS_PAD,
+                                            a.dyg[tower][l - 1], Kp, row0, a.n, [&]() __attribute__((always_inline)) {
+                                                if (l > 1) dense_prefetch<CT, KS>(wpre, a.thetaT + net.wT_off[tower][l - 1], net.Hp[l - 2], net.Hp[l - 2], Kp);
+                                            });
+        }
+        lds_barrier();
+        STAMP(9 + (net.L - 1 - l));
+    }
+}
+
+// Multi-binary head ("train_fwd_bwd_kernel<mbin>" of ppo_kernel_counts): `actions` holds A floats per row, each 0 or 1, staged and read from the action tile like the
+// Gaussian head's; neglogp and entropy are two group16_sums over bern_nlp_elem / bern_entropy_elem, d logits (bern_grad_elem) go where d mu goes, the aux (d logstd)
+// tile and slot words get zeros.  A dead row of the last tile takes x = 0 and contributes zeros through `live`.  A kernel of its own for the reason given at
+// policy_step_kernel's multi-binary overload; everything in front of and behind the head is train_fwd_bwd_kernel's, statement for statement.
+using TrainArgsB = BinArgs<TrainArgs>;
+template <int CT, int KS, int CTH, bool WIDE, bool EARLY, class HEAD>
+__global__ __launch_bounds__(BLOCK_THREADS) void train_fwd_bwd_kernel(NetDev net, TrainArgsB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(a)>();
+    // XCD-aware row mapping (speed only): see train_fwd_bwd_kernel
+    int tower = blockIdx.y;
+    int rb = (gridDim.x % 8 == 0) ? (int)((blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8) : (int)blockIdx.x;
+    if (a.xcd_map == 1 && gridDim.x % 4 == 0) {
+        const int lid = (int)(blockIdx.x + gridDim.x * blockIdx.y), x = lid & 7, q = lid >> 3;
+        tower = x & 1;
+        rb = (x >> 1) * (int)(gridDim.x / 4) + q;
+    }
+    const int row0 = rb * ROWS_PER_BLOCK;
+    const int tid = threadIdx.x;
+    const int ld0 = net.Kp0 + LDS_PAD;
+    float* misc = lds + net.lds_misc;          // [0,64) per-row loss terms | [64, 64+16Ap) dlogstd rows | then actions | row scalars
+    float* dls = misc + 64;
+    float* acts = dls + ROWS_PER_BLOCK * net.Ap;
+    float* rowv = acts + ROWS_PER_BLOCK * net.Ap;   // [16][2]: pi {adv, old_neglogp} ; vf {return, old_value}
+    float* slot = a.slots[tower] + (size_t)rb * net.slot_w;
+    STAMP(0);
+    WRing<CT, KS> wpre;
+    HeadFrag<CTH> hpre;
+    WFrag<CT, KS> wl0, whT;                              // EARLY: first-layer and transposed-head weights of this wave's 64 columns
+    if constexpr (!EARLY) dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][0], net.Hp[0], net.Hp[0], net.Kp0);
+    float* par = lds + net.lds_par - net.par_skip;      // indexed with absolute mirror offsets
+    ObsNorm nz = {nullptr, nullptr, 0.f, 0.f, 0};
+    RowScalars rs;
+    if (tower == 0) rs = RowScalars{a.actions, a.advs ? a.advs : a.returns, a.advs ? nullptr : a.old_values, a.old_neglogp, a.adv_stats, 1};
+    else rs = RowScalars{nullptr, a.returns, nullptr, a.old_values, nullptr, 2};
+    stage_block_inputs<0>(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, nz, nullptr,
+                       tower == 0 ? a.x0g : nullptr, rs, acts, rowv, [&]() __attribute__((always_inline)) {
+                           if constexpr (EARLY) {
+                               load_frag<CT, KS>(wl0, a.theta + net.w_off[tower][0], net.Hp[0]);
+                               dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][1], net.Hp[1], net.Hp[1], net.Hp[0]);
+                               if (tower == 0) {
+                                   if constexpr (CTH > 0) head_prefetch<CTH>(hpre.w, a.theta + net.wmu_off, net.Ap, net.Hp[net.L - 1]);
+                                   load_frag<CT, KS>(whT, a.thetaT + net.wmuT_off, net.Hp[net.L - 1]);
+                               }
+                           }
+                       });
+    lds_barrier();
+    STAMP(1);
+    // ---- forward ---------------------------------------------------------------------------------------------
+    int K = net.Kp0, ldx = ld0;
+    if constexpr (EARLY) {
+        const int Np = net.Hp[0], ldy = Np + LDS_PAD;
+        dense_tile_frag<CT, KS, EP_BIAS_TANH>(wl0, par + net.par_b[0], lds + net.lds_h[0], ld0, lds + net.lds_h[1], ldy, nullptr, 0, a.hg[tower][0], Np, row0, a.n);
+        lds_barrier();
+        STAMP(2);
+        K = Np; ldx = ldy;
+    }
+    for (int l = EARLY ? 1 : 0; l < net.L; ++l) {
+        const int Np = net.Hp[l], ldy = Np + LDS_PAD;
+        dense_tile<CT, KS, EP_BIAS_TANH>(wpre, a.theta + net.w_off[tower][l], Np, WIDE ? a.par + tower * net.par_total + net.par_b[l] : par + net.par_b[l], lds + net.lds_h[l], ldx, K,
+                                         lds + net.lds_h[l + 1], ldy, Np, nullptr, 0, (tower == 1 && l == net.L - 1) ? nullptr : a.hg[tower][l] /* the value head's weight gradient is formed in this kernel: nobody reads that copy */, Np, row0, a.n, [&]() __attribute__((always_inline)) {
+                                             if (l + 1 < net.L) dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][l + 1], net.Hp[l + 1], net.Hp[l + 1], Np);
+                                             else {
+                                                 if constexpr (CTH > 0 && !EARLY) head_prefetch<CTH>(hpre.w, a.theta + net.wmu_off, net.Ap, Np);
+                                                 // the backward pass's transposed second-layer weights: the ring is idle from here to the backward layer
+                                                 if ((tower == 1 || EARLY) && net.L > 1) dense_prefetch<CT, KS>(wpre, a.thetaT + net.wT_off[tower][net.L - 1], net.Hp[net.L - 2], net.Hp[net.L - 2], Np);
+                                             }
+                                         }
+#ifdef PPO_STAMPS
+                                         , a.stamps ? (l == PPO_STAMP_LAYER ? a.stamps + (size_t)(tower * gridDim.x + rb) * 32 + 16 : nullptr) : nullptr
+#endif
+                                         );
+        lds_barrier();
+        STAMP(2 + l);
+        K = Np; ldx = ldy;
+    }
+    const float* hL = lds + net.lds_h[net.L];
+    const int HpL = K, ldhL = ldx;
+    const float cr = a.hyper[1];
+    const int r = tid >> 4, part = tid & 15;
+    const int row = row0 + r;
+    const bool live = row < a.n;
+    float* dcur = lds + net.lds_d[0];
+    float* dnext = lds + net.lds_d[1];
+
+    if (tower == 0) {
+        // ---- policy head + surrogate loss and its gradient ---------------------------------------------------
+        policy_head<CTH>(net, a.theta, hpre, hL, ldhL, HpL, lds);
+        // the head's backward weights (transposed copy) stream in under the loss arithmetic (see train_fwd_bwd_kernel)
+        constexpr bool ONE = CTH > 0 && CTH == KS;
+        if constexpr (EARLY) {
+            // nothing to request: in registers since kernel entry
+        } else if constexpr (ONE) {
+            prefetch_one_stage<CT, KS, PPO_RING - 1>(wpre, a.thetaT + net.wmuT_off, HpL, HpL);
+            if (net.L > 1) dense_prefetch<CT, KS>(wpre, a.thetaT + net.wT_off[0][net.L - 1], net.Hp[net.L - 2], net.Hp[net.L - 2], HpL);
+        } else dense_prefetch<CT, KS>(wpre, a.thetaT + net.wmuT_off, HpL, HpL, net.Ap);
+        STAMP(6);
+        const float* mus = lds + net.lds_mu;
+        const int ldm = net.Ap + LDS_PAD;
+        float nlp = 0.f, sent = 0.f;
+        for (int j = part; j < net.A; j += 16) {
+            const float l = mus[r * ldm + j];
+            const BernParts b = bern_parts(l);
+            nlp += bern_nlp_elem(b, l, live ? acts[r * net.Ap + j] : 0.f);
+            sent += bern_entropy_elem(b, l);
+        }
+        nlp = group16_sum(nlp); sent = group16_sum(sent);
+        const float adv = live ? rowv[2 * r] : 0.f;
+        const float old_nlp = live ? rowv[2 * r + 1] : nlp;
+        const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
+        const float g = a.inv_n;
+        const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
+        if (part == 0) surrogate_terms(sr, nlp, old_nlp, sent, cr, live, misc, r);
+        // d logits (-> dcur tile, also the dY operand of the head weight gradient); the d logstd rows are zeros; padding columns and dead rows: exactly +0
+        for (int j = part; j < net.Ap; j += 16) {
+            float dmu = 0.f;
+            if (j < net.A && live) {
+                const float l = mus[r * ldm + j];
+                dmu = bern_grad_elem(d_nlp, bern_parts(l), l, acts[r * net.Ap + j], net.ent_coef, g);
+            }
+            dcur[r * ldm + j] = dmu;
+            dls[r * net.Ap + j] = 0.f;
+            a.dmug[(size_t)row * net.Ap + j] = dmu;             // dead rows of the last tile: zeros
+        }
+        lds_barrier();
+        // per-block partial sums: db_pi, the aux words (zeros), loss terms
+        for (int j = tid; j < net.Ap; j += BLOCK_THREADS) {
+            float sb = 0.f, sl = 0.f;
+            for (int q = 0; q < ROWS_PER_BLOCK; ++q) { sb += dcur[q * ldm + j]; sl += dls[q * net.Ap + j]; }
+            slot[net.slot_head + j] = sb;
+            slot[net.slot_aux + j] = sl;
+        }
+        if (tid < 4) {
+            float s = 0.f;
+            for (int q = 0; q < ROWS_PER_BLOCK; ++q) s += misc[q * 4 + tid];
+            slot[net.slot_loss + tid] = s;
+        }
+        STAMP(7);
+        // dh_L = (d logits * W_pi^T) .* (1 - h_L^2): a dense product against the transposed head weights [Ap][HpL]
+        if constexpr (EARLY)
+            dense_tile_frag<CT, KS, EP_TANHGRAD>(whT, nullptr, dcur, ldm, dnext, HpL + LDS_PAD, hL, ldhL, a.dyg[0][net.L - 1], HpL, row0, a.n);
+        else if constexpr (ONE)
+            dense_tile_one_stage<CT, KS, EP_TANHGRAD, PPO_RING - 1>(wpre, a.thetaT + net.wmuT_off, HpL, nullptr, dcur, ldm, dnext, HpL + LDS_PAD, HpL, hL, ldhL,
+                                                                    a.dyg[0][net.L - 1], HpL, row0, a.n);
+        else
+        dense_tile<CT, KS, EP_TANHGRAD>(wpre, a.thetaT + net.wmuT_off, HpL, nullptr, dcur, ldm, net.Ap, dnext, HpL + LDS_PAD, HpL, hL, ldhL,
+                                        a.dyg[0][net.L - 1], HpL, row0, a.n, [&]() __attribute__((always_inline)) {
+                                            if (net.L > 1) dense_prefetch<CT, KS>(wpre, a.thetaT + net.wT_off[0][net.L - 1], net.Hp[net.L - 2], net.Hp[net.L - 2], HpL);
+                                        });
+        lds_barrier();
+    } else {
+        // ---- value head + clipped value loss and its gradient ------------------------------------------------
+        const float* wv = par + net.par_wv;
+        const float v = value_head(hL, ldhL, HpL, wv, par[net.par_bv]);
+        float dv = 0.f, lossv = 0.f;
+        if (live) {
+            const float R = rowv[2 * r], vo = rowv[2 * r + 1];
+            vf_loss_row(v, R, vo, a.hyper[2], a.hyper[3], net.vf_coef * 0.5f * a.inv_n, lossv, dv);
+        }
+        if (part == 0) { misc[r] = dv; misc[16 + r] = lossv; }
+        lds_barrier();
+        STAMP(7);
+        if (tid == 0) {
+            float sb = 0.f, sl = 0.f;
+            for (int q = 0; q < ROWS_PER_BLOCK; ++q) { sb += misc[q]; sl += misc[16 + q]; }
+            slot[net.slot_aux] = sb;            // db_v
+            slot[net.slot_loss] = sl;           // sum of max((v-R)^2, (vclip-R)^2)
+        }
+        // dW_v[k] = sum_rows h_L[row,k] * dv[row] ; dh_L = dv (x) w_v .* (1 - h_L^2)
+        const int ldd = HpL + LDS_PAD;
+        for (int k = tid; k < HpL; k += BLOCK_THREADS) {
+            float s = 0.f;
+            for (int q = 0; q < ROWS_PER_BLOCK; ++q) s = fmaf(hL[q * ldhL + k], misc[q], s);
+            slot[net.slot_head + k] = s;
+            const float w = wv[k];
+            for (int q = 0; q < ROWS_PER_BLOCK; ++q) {
+                const float h = hL[q * ldhL + k];
+                const float d = (misc[q] * w) * (1.0f - h * h);
+                dnext[q * ldd + k] = d;
+                a.dyg[1][net.L - 1][(size_t)(row0 + q) * HpL + k] = d;   // dead rows: d == 0
+            }
+        }
+        lds_barrier();
+    }
+    STAMP(8);
+    // ---- hidden layers, top down: dnext holds dLoss/d(pre-activation of layer l) -------------------------------
+    if (WIDE) dcur = lds + net.lds_h[net.L];           // wide form: h_L's tile is free now and becomes the other ping-pong tile
+    for (int l = net.L - 1; l >= 0; --l) {
+        float* t = dcur; dcur = dnext; dnext = t;            // dcur = dY_l
+        const int Np = net.Hp[l], ldd = Np + LDS_PAD;
+        for (int j = tid; j < Np; j += BLOCK_THREADS) {      // db_l = sum_rows dY_l
             float s = 0.f;
             for (int q = 0; q < ROWS_PER_BLOCK; ++q) s += dcur[q * ldd + j];
             slot[net.slot_db[l] + j] = s;

@@ -18,6 +18,9 @@
 //                  carries IActionMask like MaskedTargetEnv: at every step a seeded subset (about half; the top bit of the stream's word (step, obs_dim + j) for
 //                  global column j) of each component's categories is forbidden, the component's target never; the reward is -1 when any component's action is
 //                  forbidden, and the environment counts the steps on which it received one.
+//   MultiBinaryTargetEnv  the same on a MULTI-BINARY action space (the IMultiBinary mixin, multi_binary.hpp): A bits, an action is [1, A] of 0 / 1; bit j's target is
+//                  (W obs)_j > 0 with TargetEnv's W; reward = the share of bits that hit their target, so a uniform policy earns 0.5; episodes of a fixed length
+//                  (tests/test_multi_binary.py).
 //   UnitRewardEnv  SeededEnvMock's observation stream, reward 1 on every step, never done by itself: behind a TimeLimit every episode ends by truncation, and
 //                  the value of every state is 1 / (1 - gamma) -- which a critic only learns when the value is bootstrapped there (tests/test_truncation.py).
 //                  reset() does NOT rewind the stream (it moves one draw on): no observation ever comes twice, so nothing tells a critic how far the
@@ -27,6 +30,7 @@
 
 #include "action_mask.hpp"
 #include "env.hpp"
+#include "multi_binary.hpp"
 #include "multi_discrete.hpp"
 
 class EnvMock : public Env {
@@ -204,6 +208,53 @@ private:
     uint64_t key_;
     int kDim, kAct, len_;
     std::vector<float> w_;          // [category][obs], row-major
+};
+
+class MultiBinaryTargetEnv : public Env, public IMultiBinary {
+public:
+    MultiBinaryTargetEnv(uint32_t seed, uint32_t env_id, int obs_dim = 18, int n_bits = 18, int episode_len = 100)
+        : step_(0), last_rew_(0.f), key_(ppo_detail::ctr_key(seed, env_id)), kDim(obs_dim), kAct(n_bits), len_(episode_len), w_((size_t)n_bits * obs_dim) {
+        const uint64_t wkey = ppo_detail::splitmix64(((uint64_t)seed << 32) | 0xffffffffull);       // TargetEnv's W
+        for (int j = 0; j < kAct; ++j)
+            for (int k = 0; k < kDim; ++k) w_[(size_t)j * kDim + k] = 0.5f * ppo_detail::sym_unit((uint32_t)(ppo_detail::splitmix64(wkey ^ (((uint64_t)j << 32) | (uint32_t)k)) >> 32));
+    }
+    std::string get_action_space() override { return Env::SPACE_DISCRETE; }
+    std::string get_observation_space() override { return Env::SPACE_CONTINOUS; }
+    int get_action_space_size() override { return kAct; }
+    int get_observation_space_size() override { return kDim; }
+    Mat reset() override { step_ = 0; return obs_at(0); }
+    std::vector<Mat> step(const Mat& actions) override {
+        const Mat cur = obs_at(step_);                       // the observation the action answers
+        int hits = 0;
+        for (int j = 0; j < kAct; ++j) {
+            float tgt = 0.f;
+            for (int k = 0; k < kDim; ++k) tgt += w_[(size_t)j * kDim + k] * cur(0, k);
+            if ((actions(0, j) != 0.f) == (tgt > 0.f)) ++hits;
+        }
+        last_rew_ = (float)hits / (float)kAct;
+        ++step_;
+        Mat rew(1, 1), done(1, 1);
+        rew(0, 0) = last_rew_;
+        done(0, 0) = (step_ % (uint32_t)len_ == 0u) ? 1.f : 0.f;
+        std::vector<Mat> out;
+        out.reserve(3);
+        out.push_back(obs_at(step_)); out.push_back(std::move(rew)); out.push_back(std::move(done));
+        return out;
+    }
+    Mat get_original_obs() override { return obs_at(step_); }
+    Mat get_original_rew() override { Mat r(1, 1); r(0, 0) = last_rew_; return r; }
+    void serialize(nlohmann::json&) override {}
+    void deserialize(nlohmann::json&) override {}
+    void render() override {}
+    float get_time() override { return 0.f; }
+
+private:
+    Mat obs_at(uint32_t step) const { Mat m(1, kDim); for (int j = 0; j < kDim; ++j) m(0, j) = ppo_detail::sym_unit(ppo_detail::ctr_hash_keyed(key_, step, (uint32_t)j)); return m; }
+    uint32_t step_;
+    float last_rew_;
+    uint64_t key_;
+    int kDim, kAct, len_;
+    std::vector<float> w_;          // [bit][obs], row-major
 };
 
 class MaskedTargetEnv : public Env, public IActionMask {

@@ -10,6 +10,7 @@
 #include "../../../include/ppo_hip.h"
 #include "env.hpp"
 #include "action_mask.hpp"
+#include "multi_binary.hpp"
 #include "multi_discrete.hpp"
 #include "time_limit.hpp"
 
@@ -17,8 +18,8 @@
 // RAW: the library scales it with the statistics as they stand when the rollout is finished (include/ppo_hip.h, ppo_rollout_mark_truncated), and it never
 // enters obs_rms.  normalize_terminal() is for callers outside the HBM-resident loop (Runner::run): the current statistics, no update.
 // Action masks (action_mask.hpp): forwarded from the wrapped Env unchanged (a mask is no observation: nothing is scaled); all ones when it has none.
-// Multi-discrete action spaces (multi_discrete.hpp): the components are forwarded from the wrapped Env.
-class EnvNormalize : public Env, public ITimeLimit, public IActionMask, public IMultiDiscrete {
+// Multi-discrete action spaces (multi_discrete.hpp): the components are forwarded from the wrapped Env.  Multi-binary ones (multi_binary.hpp): likewise.
+class EnvNormalize : public Env, public ITimeLimit, public IActionMask, public IMultiDiscrete, public IMultiBinary {
 public:
     EnvNormalize(std::unique_ptr<Env> env, ppo_handle* handle, bool training, bool norm_obs = true, bool norm_reward = true,
                  float clip_reward = 10, float clip_obs = 10, float gamma = 0.99f, float epsilon = 1e-8f)
@@ -73,6 +74,7 @@ public:
     bool has_action_mask() override { return am_ && am_->has_action_mask(); }
     std::vector<int> get_action_nvec() override { return action_nvec_of(env_.get()); }
     bool has_action_nvec() override { return !action_nvec_of(env_.get()).empty(); }
+    bool has_binary_actions() override { return binary_actions_of(env_.get()); }
     // [n_envs, obs] raw -> scaled and clipped with the current statistics, which stay as they are
     Mat normalize_terminal(const Mat& raw) {
         if (!norm_obs_) return raw;

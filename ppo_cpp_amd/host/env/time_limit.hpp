@@ -8,12 +8,13 @@
 // bootstrap the value at those steps (ppo_rollout_mark_truncated / ppo_gae_ex in include/ppo_hip.h); an Env without it behaves as before.
 //   TimeLimit   wraps any ONE-environment Env with max_episode_steps.
 //   VecEnv and EnvNormalize forward the mixin from their children (vec_env.hpp, env_normalize.hpp).
-//   TimeLimit forwards the multi-discrete mixin of the environment it wraps (multi_discrete.hpp).
+//   TimeLimit forwards the multi-discrete mixin of the environment it wraps (multi_discrete.hpp), and the multi-binary one (multi_binary.hpp).
 #pragma once
 #include <memory>
 #include <stdexcept>
 
 #include "env.hpp"
+#include "multi_binary.hpp"
 #include "multi_discrete.hpp"
 
 struct ITimeLimit {
@@ -26,7 +27,7 @@ struct ITimeLimit {
     virtual bool has_time_limit() { return true; }
 };
 
-class TimeLimit : public Env, public ITimeLimit, public IMultiDiscrete {
+class TimeLimit : public Env, public ITimeLimit, public IMultiDiscrete, public IMultiBinary {
 public:
     TimeLimit(std::shared_ptr<Env> env, int max_episode_steps)
         : env_(std::move(env)), limit_(max_episode_steps), steps_(0), truncated_(Mat::Zero(1, 1)), terminal_obs_(Mat::Zero(1, env_->get_observation_space_size())) {
@@ -60,6 +61,7 @@ public:
     Mat get_terminal_obs() override { return terminal_obs_; }
     std::vector<int> get_action_nvec() override { return action_nvec_of(env_.get()); }
     bool has_action_nvec() override { return !action_nvec_of(env_.get()).empty(); }
+    bool has_binary_actions() override { return binary_actions_of(env_.get()); }
 
     void render() override { env_->render(); }
     float get_time() override { return env_->get_time(); }

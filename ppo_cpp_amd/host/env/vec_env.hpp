@@ -36,6 +36,7 @@
 
 #include "env.hpp"
 #include "action_mask.hpp"
+#include "multi_binary.hpp"
 #include "multi_discrete.hpp"
 #include "time_limit.hpp"
 
@@ -73,7 +74,8 @@ inline int usable_cpus() {
 // idle); children without the mixin report every category allowed.
 // Multi-discrete action spaces (multi_discrete.hpp): the children's components are forwarded; children that disagree (or only some of which are multi-discrete)
 // are refused at construction.
-class VecEnv : public virtual Env, public ITimeLimit, public IActionMask, public IMultiDiscrete {
+// Multi-binary action spaces (multi_binary.hpp): forwarded likewise; children that disagree, and children that are both multi-discrete and multi-binary, are refused.
+class VecEnv : public virtual Env, public ITimeLimit, public IActionMask, public IMultiDiscrete, public IMultiBinary {
 public:
     explicit VecEnv(const std::vector<std::shared_ptr<Env>>& envs, int max_workers = 0)
         : envs_(envs), n_(static_cast<int>(envs.size())), generation_(0), terminate_(false), actions_(nullptr),
@@ -88,6 +90,10 @@ public:
         nvec_ = action_nvec_of(envs_[0].get());
         for (int i = 1; i < n_; ++i)
             if (action_nvec_of(envs_[i].get()) != nvec_) throw std::runtime_error("VecEnv: environment " + std::to_string(i) + " reports other action components (get_action_nvec) than environment 0");
+        binary_ = binary_actions_of(envs_[0].get());
+        for (int i = 1; i < n_; ++i)
+            if (binary_actions_of(envs_[i].get()) != binary_) throw std::runtime_error("VecEnv: environment " + std::to_string(i) + " disagrees with environment 0 about multi-binary actions (has_binary_actions)");
+        if (binary_ && !nvec_.empty()) throw std::runtime_error("VecEnv: the environments are both multi-discrete (IMultiDiscrete) and multi-binary (IMultiBinary)");
         truncated_ = Mat::Zero(n_, 1);
         if (any_tl_) terminal_obs_ = Mat::Zero(n_, obs_dim_);
         // first guess: 8 chunks per thread; recalibrated from measured time per environment after the first steps
@@ -163,6 +169,7 @@ public:
     bool has_action_mask() override { return any_am_; }
     std::vector<int> get_action_nvec() override { return nvec_; }
     bool has_action_nvec() override { return !nvec_.empty(); }
+    bool has_binary_actions() override { return binary_; }
     void serialize(nlohmann::json&) override {}
     void deserialize(nlohmann::json&) override {}
     void render() override { std::cout << "VecEnv::render() not implemented\n"; }
@@ -333,6 +340,7 @@ private:
     std::vector<IActionMask*> am_;     // per child: its action-mask mixin, or null
     bool any_am_ = false;
     std::vector<int> nvec_;            // the children's action components (multi_discrete.hpp), empty: not multi-discrete
+    bool binary_ = false;              // the children take multi-binary actions (multi_binary.hpp)
     Mat truncated_, terminal_obs_;     // [n, 1], [n, obs] of the last step
     int workers_ = 1, chunk_ = 1, n_chunks_ = 1, steps_ = 0;
     Mode mode_ = RESET;

@@ -14,7 +14,7 @@
 class MlpPolicy {
 public:
     explicit MlpPolicy(ppo_handle* handle, int act_dim) : h_(handle), act_dim_(action_width(handle, act_dim)) {}
-    // columns of an action matrix: act_dim (Gaussian), 1 (categorical: the category index) or K (multi-categorical) -- what the handle reports (ppo_action_width)
+    // columns of an action matrix: act_dim (Gaussian; multi-binary: the bits), 1 (categorical: the category index) or K (multi-categorical) -- what the handle reports (ppo_action_width)
     static int action_width(ppo_handle* handle, int act_dim) { return handle ? ppo_action_width(handle) : act_dim; }
     int action_width() const { return act_dim_; }
     virtual ~MlpPolicy() {}

@@ -35,20 +35,29 @@ public:
         // the handle's head must match the Env's action space (env/env.hpp:42-47): a Gaussian head for SPACE_CONTINOUS, a categorical
         // one (ppo_create_ex with PPO_ACT_CATEGORICAL, act_dim = number of categories) for SPACE_DISCRETE
         // an Env with the IMultiDiscrete mixin (env/multi_discrete.hpp) needs a multi-categorical handle (ppo_create_multi) with the Env's own components
+        // an Env with the IMultiBinary mixin (env/multi_binary.hpp) needs a multi-binary handle (ppo_create_ex with PPO_ACT_MULTI_BINARY, act_dim = number of bits)
         const std::vector<int> env_nvec = action_nvec_of(&env);
         const int dist = ppo_action_dist(handle);
         const bool discrete = env.get_action_space() == Env::SPACE_DISCRETE, multi = dist == PPO_ACT_MULTI_CATEGORICAL;
-        const bool categorical = dist == PPO_ACT_CATEGORICAL || multi;                  // (a head over logits: what masks and SPACE_DISCRETE need)
-        if (discrete != categorical)
+        const bool binary = dist == PPO_ACT_MULTI_BINARY, env_binary = binary_actions_of(&env);
+        const bool categorical = dist == PPO_ACT_CATEGORICAL || multi;                  // (a head over softmax logits: what masks need)
+        if (env_binary && !env_nvec.empty()) throw std::runtime_error("PPO2: the Env is both multi-discrete (IMultiDiscrete) and multi-binary (IMultiBinary)");
+        if (env_binary && !discrete) throw std::runtime_error(std::string("PPO2: the Env carries the IMultiBinary mixin but its action space is '") + env.get_action_space() + "'");
+        if (discrete != (categorical || binary))
             throw std::runtime_error(std::string("PPO2: the Env's action space is '") + env.get_action_space() + "' but the handle's policy head is " +
-                                     (categorical ? "categorical" : "Gaussian") + " (create the handle with ppo_create_ex and " +
-                                     (discrete ? "PPO_ACT_CATEGORICAL" : "PPO_ACT_GAUSSIAN") + ")");
+                                     (categorical ? "categorical" : binary ? "multi-binary" : "Gaussian") + " (create the handle with ppo_create_ex and " +
+                                     (env_binary ? "PPO_ACT_MULTI_BINARY" : discrete ? "PPO_ACT_CATEGORICAL" : "PPO_ACT_GAUSSIAN") + ")");
+        if (binary != env_binary)
+            throw std::runtime_error(std::string("PPO2: the Env's action space is ") + (env_binary ? "multi-binary (IMultiBinary)" : "not multi-binary") + " but the handle's policy head is " +
+                                     (binary ? "multi-binary" : categorical ? "categorical" : "Gaussian") + " (an Env with the IMultiBinary mixin needs a handle from ppo_create_ex with "
+                                     "PPO_ACT_MULTI_BINARY, and only such an Env does: PPO2::create_handle)");
         if (multi != !env_nvec.empty() || (multi && handle_nvec(handle) != env_nvec))
             throw std::runtime_error("PPO2: the Env's action components " + nvec_text(env_nvec) + " are not the handle's " + nvec_text(multi ? handle_nvec(handle) : std::vector<int>()) +
                                      " (an Env with the IMultiDiscrete mixin needs a handle from ppo_create_multi with the same nvec: PPO2::create_handle)");
         // an Env that carries the IActionMask mixin (env/action_mask.hpp): the handle's rollout carries masks from here on, and both loops and eval() pass them
         IActionMask* am = dynamic_cast<IActionMask*>(&env_);
         if (am && am->has_action_mask()) {
+            if (binary) throw std::runtime_error("PPO2: the Env reports action masks but its action space is multi-binary (action masks need a categorical head)");
             if (!categorical) throw std::runtime_error("PPO2: the Env reports action masks but its action space is not discrete");
             am_ = am;
             check(ppo_set_action_masking(h_, 1));
@@ -60,8 +69,10 @@ public:
     // shape qualifies (include/ppo_hip.h); a continuous Env is not affected.
     // An Env with the IMultiDiscrete mixin: the bare PPO_ACT_MULTI_CATEGORICAL -- a value for ppo_create_multi[_ex], which ppo_create_ex refuses and which takes its
     // flags as an argument of their own; create_handle below makes the right call (and passes PPO_ACT_SHAPE_KERNELS there).
+    // An Env with the IMultiBinary mixin: PPO_ACT_MULTI_BINARY (the head has the generic fp32 kernels only: the flag is not added, and the library ignores it).
     static int32_t action_dist_for(Env& env, bool discrete_shape_kernels = false) {
         if (env.get_action_space() != Env::SPACE_DISCRETE) return PPO_ACT_GAUSSIAN;
+        if (binary_actions_of(&env)) return PPO_ACT_MULTI_BINARY;
         if (!action_nvec_of(&env).empty()) return PPO_ACT_MULTI_CATEGORICAL;
         return PPO_ACT_CATEGORICAL | (discrete_shape_kernels ? PPO_ACT_SHAPE_KERNELS : 0);
     }
@@ -117,7 +128,7 @@ public:
     // env step after that capture a one-off runtime hiccup)
     double phase_env_ms = 0, phase_act_ms = 0, phase_observe_ms = 0;
 
-    // Checkpoint in the reference's on-disk format (ppo2.hpp:107-166): the 15 model tensors (14 for a categorical head: no pi/logstd) as a TF bundle
+    // Checkpoint in the reference's on-disk format (ppo2.hpp:107-166): the 15 model tensors (14 for a categorical or multi-binary head: no pi/logstd) as a TF bundle
     // (<path>[.<id>].index / .data-00000-of-00001, names "model/<tensor>"; the untrained q/w, q/b ride along so that the
     // reference's restore_all finds every variable) and the JSON side-car with hyper-parameters + Env::serialize.
     void save(std::string save_path, int save_id = -1) {
@@ -154,6 +165,7 @@ public:
         json["action_space"] = env_.get_action_space(); json["n_envs"] = n_envs_ * world_; json["model_filename"] = model_filename;
         json["target_kl"] = target_kl_;
         if (ppo_action_dist(h_) == PPO_ACT_MULTI_CATEGORICAL) json["action_nvec"] = handle_nvec(h_);        // a multi-categorical policy: "discrete" plus its components
+        if (ppo_action_dist(h_) == PPO_ACT_MULTI_BINARY) json["action_binary"] = true;                       // a multi-binary policy: "discrete" plus this key
         std::ofstream f(save_path + ".json");
         if (!f) throw std::runtime_error("PPO2::save: unable to open " + save_path + ".json");
         f << json.dump();
@@ -173,6 +185,11 @@ public:
         const std::vector<int> mine = ppo_action_dist(h_) == PPO_ACT_MULTI_CATEGORICAL ? handle_nvec(h_) : std::vector<int>();
         if (saved_nvec != mine)
             throw std::runtime_error("PPO2::load: " + save_path + " holds a policy with action components " + nvec_text(saved_nvec) + " but the handle's are " + nvec_text(mine));
+        // "action_binary": a multi-binary policy; a side-car without the key holds none
+        const bool saved_binary = json.contains("action_binary") && json["action_binary"].get<bool>(), my_binary = ppo_action_dist(h_) == PPO_ACT_MULTI_BINARY;
+        if (saved_binary != my_binary)
+            throw std::runtime_error("PPO2::load: " + save_path + " holds a " + (saved_binary ? "multi-binary" : "categorical") + " policy but the handle's head is " +
+                                     (my_binary ? "multi-binary" : "categorical"));
         env_.deserialize(json);
         gamma_ = json["gamma"].get<float>(); n_steps_ = json["n_steps"].get<int>(); vf_coef_ = json["vf_coef"].get<float>();
         ent_coef_ = json["ent_coef"].get<float>(); max_grad_norm_ = json["max_grad_norm"].get<float>();

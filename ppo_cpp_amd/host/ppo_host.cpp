@@ -538,6 +538,132 @@ int ppo_host_multi_checkpoint(const char* prefix, const int* nvec_in, const int*
     return rc;
 }
 
+// The learning check of the multi-binary head (tests/test_multi_binary.py): n_envs x MultiBinaryTargetEnv(act_dim bits) -> VecEnv -> EnvNormalize -> PPO2::learn with the
+// library's own sampling and shuffles, through the HBM-resident loop or, with args->reference_loop, the literal one.  The handle comes from PPO2::create_handle (the Env
+// carries IMultiBinary: ppo_create_ex with PPO_ACT_MULTI_BINARY; args->discrete_kernels asks for the flags of a discrete Env's handle, which this head accepts and
+// ignores).  The head has neither a fused host step nor a resident rollout: args->host_step_fused and the process-wide resident default are not applied.
+// reward_curve [n_updates], losses_out [n_updates][5] (may be null); count_names / counts / n_counts (all three or none): ppo_kernel_counts of the run's handle.
+int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* losses_out, char (*count_names)[32], long long* counts, int* n_counts, ppo_host_result* out) {
+    std::memset(out, 0, sizeof *out);
+    ppo_handle* h = nullptr;
+    try {
+        const int O = a->obs_dim > 0 ? a->obs_dim : 18, A = a->act_dim > 0 ? a->act_dim : 18;
+        ppo_config cfg;
+        ppo_config_default(&cfg, O, A, a->n_hidden, a->hidden);
+        cfg.device = a->device;
+        cfg.compute_dtype = a->compute_dtype;
+        std::vector<std::shared_ptr<Env>> envs;
+        for (int i = 0; i < a->n_envs; ++i) envs.push_back(std::make_shared<MultiBinaryTargetEnv>(1234u, (uint32_t)i, O, A));
+        if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : 0) != 0) throw std::runtime_error(ppo_last_error(nullptr));
+        if (ppo_action_dist(h) != PPO_ACT_MULTI_BINARY) throw std::runtime_error("PPO2::create_handle did not create a multi-binary handle for an IMultiBinary Env");
+        if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, a->max_workers)), h, /*training=*/true, a->norm_obs != 0, a->norm_reward != 0, 10.f, 10.f, a->gamma};
+            struct Plain : Env, IMultiBinary {       // hides the EnvNormalize type to force the reference loop; the mixin stays visible
+                EnvNormalize& e; explicit Plain(EnvNormalize& x) : e(x) {}
+                std::string get_action_space() override { return e.get_action_space(); }
+                std::string get_observation_space() override { return e.get_observation_space(); }
+                int get_action_space_size() override { return e.get_action_space_size(); }
+                int get_observation_space_size() override { return e.get_observation_space_size(); }
+                int get_num_envs() override { return e.get_num_envs(); }
+                Mat reset() override { return e.reset(); }
+                std::vector<Mat> step(const Mat& x) override { return e.step(x); }
+                void render() override {}
+                float get_time() override { return 0; }
+                Mat get_original_obs() override { return e.get_original_obs(); }
+                Mat get_original_rew() override { return e.get_original_rew(); }
+                void serialize(nlohmann::json& j) override { e.serialize(j); }
+                void deserialize(nlohmann::json& j) override { e.deserialize(j); }
+                bool has_binary_actions() override { return e.has_binary_actions(); }
+            } plain{env};
+            Env& top = a->reference_loop ? static_cast<Env&>(plain) : static_cast<Env&>(env);
+            PPO2 algo{h, top, a->gamma, a->n_steps, cfg.ent_coef, a->lr, 0.5f, 0.5f, a->lam, a->nminibatches, a->noptepochs, a->cliprange, a->cliprange_vf};
+            if (ppo_get_action_masking(h) != 0) throw std::runtime_error("PPO2 set action masking for a multi-binary Env");
+            algo.quiet = true;
+            algo.seed = a->seed;
+            algo.learn(a->n_updates * a->n_envs * a->n_steps);
+            const auto& hist = algo.history();
+            if (hist.empty()) throw std::runtime_error("no update ran");
+            std::memcpy(out->losses, hist.back().losses, sizeof out->losses);
+            out->fps_last = hist.back().fps;
+            if (reward_curve) for (size_t i = 0; i < hist.size(); ++i) reward_curve[i] = hist[i].mean_reward;
+            if (losses_out) for (size_t i = 0; i < hist.size(); ++i) std::memcpy(losses_out + 5 * i, hist[i].losses, sizeof(float) * 5);
+            if (count_names && counts && n_counts) {
+                int64_t c64[64];
+                const int nc = ppo_kernel_counts(h, 64, count_names, c64);
+                for (int i = 0; i < nc; ++i) counts[i] = (long long)c64[i];
+                *n_counts = nc;
+            }
+        }
+        ppo_destroy(h);
+        return 0;
+    } catch (const std::exception& e) {
+        std::snprintf(out->error, sizeof out->error, "%s", e.what());
+        if (h) ppo_destroy(h);
+        return -1;
+    }
+}
+
+// PPO2::save of a multi-binary policy (a [64,64] handle of 6 bits behind MultiBinaryTargetEnv x 4 + EnvNormalize, one short learn()) under `prefix`, then PPO2::load into
+// a FRESH multi-binary handle: every tensor and the deterministic actions of `n` observations must be identical (actions_out [2][n][6]: before / after).  Loading it
+// into a categorical handle of the same width must fail, and so must loading a categorical policy's checkpoint (written under <prefix>.cat) into the multi-binary
+// handle.  Returns 0; 1 = tensors differ, 2 = the categorical handle's load went through, 3 = the multi-binary handle's load of the categorical checkpoint; -1 = error
+// (message on stderr).
+int ppo_host_binary_checkpoint(const char* prefix, const float* obs, int n, float* actions_out) {
+    ppo_handle* h[3] = {nullptr, nullptr, nullptr};
+    int rc = 0;
+    try {
+        const int A = 6;
+        ppo_config cfg; const int32_t hidden[2] = {64, 64};
+        ppo_config_default(&cfg, 18, A, 2, hidden);
+        MultiBinaryTargetEnv probe(1234u, 0, 18, A);
+        DiscreteTargetEnv probe_cat(1234u, 0, 18, A);
+        Env* probes[3] = {&probe, &probe, &probe_cat};
+        for (int k = 0; k < 3; ++k)
+            if (PPO2::create_handle(cfg, *probes[k], &h[k]) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0) throw std::runtime_error(ppo_last_error(h[k]));
+        std::vector<std::shared_ptr<Env>> envs;
+        for (uint32_t i = 0; i < 4; ++i) envs.push_back(std::make_shared<MultiBinaryTargetEnv>(1234u, i, 18, A));
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new VecEnv(envs, 1)), h[0], /*training=*/true};
+            PPO2 algo{h[0], env, 0.99f, 16, cfg.ent_coef, 1e-3f, 0.5f, 0.5f, 0.95f, 4, 2, 0.2f};
+            algo.quiet = true;
+            algo.learn(2 * 4 * 16);
+            algo.save(prefix);
+            if (ppo_act_deterministic(h[0], obs, n, actions_out) != 0) throw std::runtime_error(ppo_last_error(h[0]));
+        }
+        {
+            EnvNormalize env{std::unique_ptr<Env>(new MultiBinaryTargetEnv(1234u, 0, 18, A)), h[1], /*training=*/false};
+            PPO2 algo{h[1], env};
+            algo.load(prefix);
+            if (ppo_act_deterministic(h[1], obs, n, actions_out + (size_t)n * A) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+        }
+        for (int i = 0; i < ppo_num_tensors(h[0]) && !rc; ++i) {
+            int32_t r = 0, c = 0;
+            ppo_tensor_info(h[0], i, nullptr, &r, &c);
+            std::vector<float> x((size_t)r * (c ? c : 1)), y(x.size());
+            if (ppo_get_tensor(h[0], 0, i, x.data(), (int64_t)x.size()) != 0 || ppo_get_tensor(h[1], 0, i, y.data(), (int64_t)y.size()) != 0) throw std::runtime_error(ppo_last_error(h[1]));
+            if (std::memcmp(x.data(), y.data(), sizeof(float) * x.size()) != 0) rc = 1;
+        }
+        if (!rc) {
+            EnvNormalize env{std::unique_ptr<Env>(new DiscreteTargetEnv(1234u, 0, 18, A)), h[2], /*training=*/false};
+            PPO2 algo{h[2], env};
+            bool threw = false;
+            try { algo.load(prefix); } catch (const std::exception& ex) { threw = true; std::fprintf(stderr, "expected: %s\n", ex.what()); }
+            if (!threw) rc = 2;
+            algo.save(std::string(prefix) + ".cat");
+        }
+        if (!rc) {
+            EnvNormalize env{std::unique_ptr<Env>(new MultiBinaryTargetEnv(1234u, 0, 18, A)), h[1], /*training=*/false};
+            PPO2 algo{h[1], env};
+            bool threw = false;
+            try { algo.load(std::string(prefix) + ".cat"); } catch (const std::exception& ex) { threw = true; std::fprintf(stderr, "expected: %s\n", ex.what()); }
+            if (!threw) rc = 3;
+        }
+    } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = -1; }
+    for (ppo_handle* x : h) if (x) ppo_destroy(x);
+    return rc;
+}
+
 // PPO2::learn with EXPLICIT exploration noise and epoch permutations on the reference's stack (SeededEnvMock x N -> VecEnv ->
 // EnvNormalize -> PPO2; ppo2.cpp:188-250), through the HBM-resident loop or (reference_loop) the literal one: what
 // tests/test_host_layer.py holds against oracle.collect + oracle.update update by update (ppo2.hpp:264-349).

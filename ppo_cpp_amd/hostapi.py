@@ -109,7 +109,7 @@ def learn_explicit(n_envs, n_steps, hidden, theta, noise, perms, nminibatches, l
 
 def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma=0.99, lam=0.95, seed=0, reference_loop=False, device=-1,
                 obs_dim=18, act_dim=18, discrete=False, cliprange_vf=-1.0, discrete_kernels="generic", compute_dtype=0, nvec=None, masked=False, n_playback=0,
-                host_step_fused=False, target_kl=0.0, rollout_resident=False):
+                host_step_fused=False, target_kl=0.0, rollout_resident=False, binary=False):
     """PPO2::learn on TargetEnv x n_envs (a learnable task, host/env/env_mock.hpp) behind VecEnv + EnvNormalize with the library's own exploration noise and shuffles:
     returns the mean un-normalised reward of every update's rollout [n_updates], the per-update mean losses and the final weights.
     discrete=True: DiscreteTargetEnv (act_dim categories) and a categorical handle; discrete_kernels="narrow": that handle is created with
@@ -127,15 +127,46 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     rollout_resident=True: ppo_set_rollout_resident(h, 1) on the created handle (through the process-wide default ppo_host_set_rollout_resident, cleared again when
     the call returns): with discrete_kernels="narrow" and at most 64 environments the rollout is served by the resident kernel's discrete forms
     (narrow_rollout_kernel<cat|mcat[,mask]>, one launch per rollout); nothing changes anywhere else.
+    binary=True: MultiBinaryTargetEnv (act_dim bits, the IMultiBinary mixin) and a multi-binary handle (PPO2::create_handle -> ppo_create_ex with
+    PPO_ACT_MULTI_BINARY), through ppo_host_learn_binary; discrete_kernels asks for the flags of a discrete Env's handle, which this head accepts and ignores.  The head
+    has no fused host step, no resident rollout, no masks and no bf16 path: host_step_fused, rollout_resident, masked, nvec, discrete and target_kl are refused with it.
     target_kl (default 0 = off): PPO2::set_target_kl, target-KL early stopping (include/ppo_hip.h, ppo_set_target_kl); "applied" [n_updates, 2] then holds the Adam
     steps applied / train steps of every update (ppo_host_explicit::target_kl / applied_out; not through the nvec form)."""
     lib = load_host_library()
+    if binary:
+        if host_step_fused or rollout_resident or masked or discrete or nvec is not None or target_kl or n_playback:
+            raise ValueError("binary=True goes with none of host_step_fused, rollout_resident, masked, discrete, nvec, target_kl, n_playback")
+        return _learn_binary(lib, n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma, lam, seed, reference_loop, device, obs_dim, act_dim,
+                             cliprange_vf, discrete_kernels, compute_dtype)
     lib.ppo_host_set_rollout_resident(int(bool(rollout_resident)))
     try:
         return _learn_curve(lib, n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma, lam, seed, reference_loop, device, obs_dim, act_dim,
                             discrete, cliprange_vf, discrete_kernels, compute_dtype, nvec, masked, n_playback, host_step_fused, target_kl)
     finally:
         lib.ppo_host_set_rollout_resident(0)
+
+
+def _learn_binary(lib, n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma, lam, seed, reference_loop, device, obs_dim, act_dim,
+                  cliprange_vf, discrete_kernels, compute_dtype):
+    import numpy as np
+    a = HostArgs()
+    a.n_envs, a.n_steps, a.n_hidden = n_envs, n_steps, len(hidden)
+    for i, h in enumerate(hidden):
+        a.hidden[i] = h
+    a.nminibatches, a.noptepochs, a.n_updates = nminibatches, noptepochs, n_updates
+    a.lr, a.cliprange, a.gamma, a.lam = lr, cliprange, gamma, lam
+    a.device, a.max_workers, a.reference_loop = device, 0, int(reference_loop)
+    a.norm_obs, a.norm_reward, a.seed = 1, 1, seed
+    a.obs_dim, a.act_dim, a.cliprange_vf, a.compute_dtype = obs_dim, act_dim, cliprange_vf, int(compute_dtype)
+    a.discrete_kernels = _discrete_kernels(discrete_kernels)
+    out = {"reward_curve": np.zeros(n_updates, np.float32), "losses": np.zeros((n_updates, 5), np.float32)}
+    names = ((C.c_char * 32) * 64)(); cnt = (C.c_longlong * 64)(); ncnt = C.c_int(0)
+    r = HostResult()
+    fp = C.POINTER(C.c_float)
+    if lib.ppo_host_learn_binary(C.byref(a), out["reward_curve"].ctypes.data_as(fp), out["losses"].ctypes.data_as(fp), names, cnt, C.byref(ncnt), C.byref(r)) != 0:
+        raise RuntimeError(r.error.decode())
+    out["kernel_counts"] = {names[i].value.decode(): int(cnt[i]) for i in range(ncnt.value)}
+    return out
 
 
 def _learn_curve(lib, n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr, cliprange, gamma, lam, seed, reference_loop, device, obs_dim, act_dim,
@@ -308,4 +339,17 @@ def discrete_checkpoint(prefix, obs):
     n = obs.shape[0]
     acts = np.zeros((2, n), np.float32)
     rc = lib.ppo_host_discrete_checkpoint(prefix.encode(), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)))
+    return rc, acts[0], acts[1]
+
+
+def binary_checkpoint(prefix, obs):
+    """PPO2::save of a multi-binary policy of 6 bits, PPO2::load into a fresh multi-binary handle, into a categorical one of the same width, and of a categorical
+    policy's checkpoint (written under prefix + ".cat") into the multi-binary handle (ppo_host_binary_checkpoint): returns (status, deterministic actions before
+    [n, 6], after); status 0 = identical tensors and both foreign loads refused"""
+    import numpy as np
+    lib = load_host_library()
+    obs = np.ascontiguousarray(obs, np.float32)
+    n = obs.shape[0]
+    acts = np.zeros((2, n, 6), np.float32)
+    rc = lib.ppo_host_binary_checkpoint(prefix.encode(), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)))
     return rc, acts[0], acts[1]
