@@ -271,6 +271,39 @@ int ppo_value(ppo_handle* h, const float* obs, int32_t n, float* value);
 /* MlpPolicy::get_deterministic_action (ppo2/policies.hpp:49-62) */
 int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* action);
 
+/* ---- querying the policy: given actions and the action distribution (no reference counterpart: its MlpPolicy fetches action, value_flat, neglogp and
+ * deterministic_action only; stable-baselines 2 ActorCriticPolicy.proba_step / BaseRLModel.action_probability, stable-baselines 3 evaluate_actions) -------------
+ * All three run policy_eval_kernel: the act model's two towers on policy_step_kernel's geometry, no random draw, the head arithmetic of
+ * ppo_head.hpp.  Every PPO_F32 handle runs this one generic kernel -- also a handle whose step runs the narrow family (its results then agree with ppo_step's to
+ * rounding, not bit for bit; on a handle whose step runs policy_step_kernel neglogp and value are ppo_step's bits).  A PPO_BF16 handle is refused: its step's neglogp
+ * comes out of bf16 GEMMs and an fp32 evaluation would disagree with it (a bf16 form is future work).  A data-parallel handle evaluates its own rows, no collective.
+ * The calls are STATELESS: they do not advance the counter RNG and touch neither rollout, normaliser nor Adam state; they are legal in the middle of a rollout on
+ * every rollout form (a resident rollout kernel is retired and relaunched as for ppo_value) and see the weights of the last finished ppo_update / ppo_train_step.
+ * One exception to "one launch, nothing written but the outputs": on a handle whose step runs the narrow family, the train forms keep the weights and the packed
+ * image current but not the small-parameter mirror ("par") and the transposed copies ("thetaT") that only the generic kernels read.  The first query behind a
+ * ppo_train_step / ppo_update on such a handle therefore launches transpose_refresh_kernel once in front of its own kernel: both buffers are rewritten from the
+ * weights -- derived copies, no weight, Adam slot or random state changes, and no narrow kernel reads them.  That launch is not counted by ppo_kernel_counts either and
+ * is not timed under a ppo_prof_read class.
+ * They are NOT counted by ppo_kernel_counts (its rows and every count stay what they were); ppo_prof_read books them under "policy_step".  (In the middle of a
+ * rollout that a resident kernel serves, the relaunch of that kernel behind the query is counted like every launch of it, as behind ppo_value.)
+ *   ppo_distribution_width  W, the columns of one parameter row: Gaussian 2A (mu[0..A) | std[0..A)), categorical A (probabilities), multi-categorical sum(nvec)
+ *                           (each component's probabilities, in logit order), multi-binary A (P(bit = 1)).
+ *   ppo_evaluate_actions    obs [n,O] as ppo_step takes them, actions [n, ppo_action_width] as ppo_train_step takes them, mask NULL or [n,A] as ppo_step_masked takes
+ *                           it; value / neglogp / entropy each [n] or NULL, not all NULL.  neglogp is that of the GIVEN action, entropy the row's.  Host checks
+ *                           before anything is uploaded, as for ppo_train_step[_masked]: a categorical index is an integer in [0, A) (per component [0, n_k)), a
+ *                           bit is 0 or 1, a mask row (component) allows a category and its own action; a mask on a Gaussian or multi-binary handle is refused.
+ *   ppo_action_probability  params [n,W], count = n * W.  A forbidden category's probability is exactly +0.
+ *   ppo_rollout_evaluate    the same kernel straight on the device-resident rollout -- fields 0 (obs), 1 (actions) and, on a masking handle, 8 (masks): T*E rows in
+ *                           time-major order, nothing staged from the host -- each output [T,E] or NULL, not all NULL.  Needs a FINISHED rollout (ppo_rollout_finish /
+ *                           ppo_collect_synthetic since the last ppo_rollout_alloc / ppo_rollout_act); otherwise an error.  After ppo_update: the true neglogp, entropy
+ *                           and value of the batch just trained on under the new weights.
+ * A refusal launches nothing and leaves the handle usable.  n has ppo_step's limits. */
+int ppo_distribution_width(const ppo_handle* h);
+int ppo_evaluate_actions(ppo_handle* h, const float* obs, const float* actions, int32_t n, const float* mask, float* value, float* neglogp,
+                         float* entropy);
+int ppo_action_probability(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* params, int64_t count);
+int ppo_rollout_evaluate(ppo_handle* h, float* value, float* neglogp, float* entropy);
+
 /* ---- action masks of the categorical head (invalid-action masking; no reference counterpart) ---------------
  * A mask is one float per (row, category), [n, A]: non-zero = allowed, 0 = forbidden.  For a masked row with logits l and allowed set S:
  *   forbidden categories are EXCLUDED, not pushed down by a constant:  m = max_{j in S} l_j,  z = sum_{j in S} exp(l_j - m),

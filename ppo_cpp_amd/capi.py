@@ -251,6 +251,38 @@ class PPOHip:
         self._ck(self.lib.ppo_act_deterministic(self.h, _fp(obs), n, _fp(a)))
         return a
 
+    # ---- querying the policy (include/ppo_hip.h; stateless: no RNG advance, no rollout / normaliser / Adam state touched) -------
+    @property
+    def distribution_width(self):
+        """W, the columns of one action_probability row: Gaussian 2A (mu | std), categorical A, multi-categorical sum(nvec), multi-binary A"""
+        return int(self.lib.ppo_distribution_width(self.h))
+
+    def evaluate_actions(self, obs, actions, mask=None):
+        """(value, neglogp, entropy), each (n,): the current policy's value, the neglogp of the GIVEN actions and the rows' entropy (stable-baselines 3
+        evaluate_actions).  actions as train_step takes them, mask as step takes it."""
+        obs = _f32(obs); n = obs.shape[0]
+        act = _f32(actions, (n,) + self._act_shape)
+        mk = _f32(mask, (n, self.A)) if mask is not None else None
+        v = np.empty(n, np.float32); nlp = np.empty(n, np.float32); ent = np.empty(n, np.float32)
+        self._ck(self.lib.ppo_evaluate_actions(self.h, _fp(obs), _fp(act), n, _fp(mk) if mk is not None else None, _fp(v), _fp(nlp), _fp(ent)))
+        return v, nlp, ent
+
+    def action_probability(self, obs, mask=None):
+        """(n, W) distribution parameters (stable-baselines 2 proba_step): Gaussian mu | std, categorical and multi-categorical the probabilities of every category
+        (exactly 0 for a forbidden one), multi-binary P(bit = 1)."""
+        obs = _f32(obs); n = obs.shape[0]
+        mk = _f32(mask, (n, self.A)) if mask is not None else None
+        out = np.empty((n, self.distribution_width), np.float32)
+        self._ck(self.lib.ppo_action_probability(self.h, _fp(obs), n, _fp(mk) if mk is not None else None, _fp(out), C.c_int64(out.size)))
+        return out
+
+    def rollout_evaluate(self):
+        """(value, neglogp, entropy), each (T, E): evaluate_actions over the finished device-resident rollout (its obs, actions and, on a masking handle, masks)
+        under the current weights, without staging anything from the host"""
+        outs = [np.empty((self.T, self.E), np.float32) for _ in range(3)]
+        self._ck(self.lib.ppo_rollout_evaluate(self.h, *[_fp(x) for x in outs]))
+        return tuple(outs)
+
     # ---- train ------------------------------------------------------------------------------------
     def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v, mask=None):
         arrs = [_f32(x) for x in (obs, actions, advs, returns, old_nlp, old_v)]

@@ -164,6 +164,11 @@ struct ppo_handle {
     // st_mask stages the masks of the host-pointer calls (ppo_step_masked / ppo_train_step_masked)
     bool masking = false;
     float *ro_mask = nullptr, *mb_mask = nullptr, *st_mask = nullptr; int st_mask_rows = 0;
+    // policy queries (ppo_evaluate_actions / ppo_action_probability / ppo_rollout_evaluate): the [rows, W] parameter staging, allocated by the first call that asks for
+    // parameters; does the rollout hold a finished collect (ppo_rollout_finish / ppo_collect_synthetic since the last alloc / act)
+    float* st_params = nullptr; size_t st_params_cap = 0; bool ro_finished = false;
+    float* ev_out[3]{}; size_t ev_out_rows = 0;      // ppo_rollout_evaluate's [T*E] output vectors, allocated by its first call
+    bool mirror_stale = false;        // a narrow handle has trained since `par` was last written from theta (launch_eval)
     NetDev net{};
     std::vector<Tensor> tensors;
     int P_dense = 0, P_pad = 0, n_blocks = 0, PT = 0;
@@ -820,7 +825,7 @@ static void for_each_head(const ppo_handle* h, F&& f) {
 template <class M, class T, class Base>
 static auto head_args(T, const ppo_handle* h, const Base& a) {
     if constexpr (T::multi) { M m{}; static_cast<Base&>(m) = a; m.comp = h->comp; return m; }
-    else if constexpr (T::bin) { BinArgs<Base> b{}; static_cast<Base&>(b) = a; return b; }
+    else if constexpr (T::bin && !std::is_same_v<Base, EvalArgs>) { BinArgs<Base> b{}; static_cast<Base&>(b) = a; return b; }      // (policy_eval_kernel's head is a template argument)
     else return a;
 }
 
@@ -1203,6 +1208,13 @@ static auto step_fn(T, int rung) {
     switch (rung) { case RUNG_WIDE4: X(4, 2, 0, true); case RUNG_WIDE1: X(1, 1, 0, true); case RUNG_42_EARLY: case RUNG_42: X(4, 2, 2, false); case RUNG_4: X(4, 2, 0, false); default: X(1, 1, 0, false); }
 #undef X
 }
+// policy_eval_kernel (the policy queries): the step kernel's rungs
+template <class T>
+static auto eval_fn(T, int rung) {
+#define X(CT, KS, CTH, WIDE) return policy_eval_kernel<CT, KS, CTH, WIDE, T::cat, T::mask, T::multi, T::bin>
+    switch (rung) { case RUNG_WIDE4: X(4, 2, 0, true); case RUNG_WIDE1: X(1, 1, 0, true); case RUNG_42_EARLY: case RUNG_42: X(4, 2, 2, false); case RUNG_4: X(4, 2, 0, false); default: X(1, 1, 0, false); }
+#undef X
+}
 template <class T>
 static auto train_fb_fn(T, int rung) {
 #define X(CT, KS, CTH, WIDE, EARLY) if constexpr (T::bin) return train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, MbinHead>; else return train_fwd_bwd_kernel<CT, KS, CTH, WIDE, EARLY, T::cat, T::mask, T::multi>
@@ -1257,6 +1269,28 @@ int launch_step(ppo_handle* h, const StepArgs& a0) {
             SET_STAMPS(a.stamps, grid.x <= 256, 4096 * 44);
             hipLaunchKernelGGL(step_fn(H, ladder_rung(h)), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
         }
+    });
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
+// the policy queries' launch: policy_eval_kernel of the handle's rung on the generic layout (theta + the small-parameter mirror, which every fp32 handle keeps),
+// also where the step runs the narrow family.  Not counted in ppo_kernel_counts (include/ppo_hip.h); profiling class policy_step.
+int launch_eval(ppo_handle* h, const EvalArgs& a0) {
+    const Head hd = head_of(h, a0.mask != nullptr);
+    // a narrow handle's train forms (deferred Adam, the resident epoch) keep theta and the packed image current but not the small-parameter mirror this kernel
+    // reads: the first query behind a train step / update brings `par` and thetaT up from theta with one transpose_refresh_kernel launch (derived copies of
+    // theta, which no narrow kernel reads; not counted, not timed under a profiling class -- include/ppo_hip.h says so)
+    if (h->narrow && h->mirror_stale) {
+        hipLaunchKernelGGL(transpose_refresh_kernel, dim3(h->n_blocks), dim3(256), 0, h->stream, h->theta, h->thetaT, h->par, h->grad_src, (float*)nullptr);
+        HIP_OK(h, hipGetLastError());
+        h->mirror_stale = false;
+    }
+    ProfScope ps(h, PK_STEP);
+    with_head(hd, [&](auto H) {
+        const auto a = head_args<EvalArgsM>(H, h, a0);
+        const dim3 grid((a.n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 2);
+        hipLaunchKernelGGL(eval_fn(H, ladder_rung(h)), grid, dim3(BLOCK_THREADS), (size_t)h->lds_step_total * sizeof(float), h->stream, h->net, a);
     });
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1957,7 +1991,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     { const NetDev& nn = h->net;
       h->early = !nn.wide && h->CT == 4 && h->CTH == 2 && nn.L >= 2 && nn.Kp0 == 32 && nn.Ap == 32 && nn.Hp[0] == 256 && nn.Hp[nn.L - 1] == 256; }
     // every rung of the ladder (not only the handle's), for the Gaussian head and every head this handle can launch
-    auto lds_opt_in = [&](auto H) { for (int r = 0; r < RUNG_COUNT; ++r) { set_lds(step_fn(H, r)); set_lds(train_fb_fn(H, r)); } };
+    auto lds_opt_in = [&](auto H) { for (int r = 0; r < RUNG_COUNT; ++r) { set_lds(step_fn(H, r)); set_lds(train_fb_fn(H, r)); if (r != RUNG_42_EARLY) set_lds(eval_fn(H, r)); } };
     if (h->dist != PPO_ACT_GAUSSIAN) lds_opt_in(GaussHead{});
     for_each_head(h, lds_opt_in);
     attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
@@ -2088,7 +2122,7 @@ void ppo_destroy(ppo_handle* h) {
                     h->obs_rms.var, h->obs_rms.count, h->ret_rms.mean, h->ret_rms.var, h->ret_rms.count, h->nz_ret, h->stats_xch, h->stats_part, h->stats_counter, h->adv_xch, h->ro_obs, h->ro_act,
                     h->ro_val, h->ro_nlp, h->ro_done, h->ro_rew, h->ro_ret, h->env_in /* raw_obs, raw_rew, cur_done live inside */, h->raw_done,
                     h->last_val, h->ro_noise, h->mb_obs, h->mb_act, h->mb_adv, h->mb_ret, h->mb_val, h->mb_nlp, h->d_perms, h->d_inv, h->d_gidx, h->d_advstats, h->d_keys, h->d_loss_rows, h->d_loss_mean,
-                    h->ro_mask, h->mb_mask, h->st_mask, h->stop};
+                    h->ro_mask, h->mb_mask, h->st_mask, h->stop, h->st_params, h->ev_out[0], h->ev_out[1], h->ev_out[2]};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int t = 0; t < 2; ++t) for (int l = 0; l < PPO_MAX_LAYERS; ++l) { if (h->hg[t][l]) (void)hipFree(h->hg[t][l]); if (h->dyg[t][l]) (void)hipFree(h->dyg[t][l]); }
     for (int i = 0; i < 6; ++i) if (h->st_vec[i]) (void)hipFree(h->st_vec[i]);
@@ -2343,6 +2377,99 @@ int ppo_act_deterministic_masked(ppo_handle* h, const float* obs, int32_t n, con
     return step_common(h, obs, n, nullptr, false, nullptr, action, nullptr, nullptr, mask);
 }
 
+// ---- policy queries (include/ppo_hip.h "querying the policy") ---------------------------------------------------------
+int ppo_distribution_width(const ppo_handle* h) { return h ? (h->dist == PPO_ACT_GAUSSIAN ? 2 * h->net.A : h->net.A) : -1; }
+
+static int eval_refuse_bf16(ppo_handle* h, const char* who) {
+    if (h->bf.on) return fail(h, "%s: not supported on a PPO_BF16 handle (its step's neglogp comes out of bf16 GEMMs; the fp32 evaluation kernel would disagree with it)", who);
+    return 0;
+}
+static int ensure_params_staging(ppo_handle* h, size_t floats) {
+    if (floats <= h->st_params_cap) return 0;
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (dev_alloc(h, &h->st_params, floats)) return -1;
+    h->st_params_cap = floats;
+    return 0;
+}
+// the host-pointer queries: checks, staging, one launch, the copies back
+static int eval_common(ppo_handle* h, const char* who, const float* obs, const float* actions, int n, const float* mask, float* value, float* neglogp, float* entropy,
+                       float* params) {
+    ENTER_Q(h);
+    if (eval_refuse_bf16(h, who)) return -1;
+    if (n < 1) return fail(h, "%s: n must be positive", who);
+    if (!obs) return fail(h, "%s: null obs", who);
+    if (mask && need_categorical(h, who)) return -1;
+    if (actions) {
+        if (h->dist == PPO_ACT_MULTI_CATEGORICAL && check_multi_actions(h, who, actions, (size_t)n)) return -1;
+        if (h->dist == PPO_ACT_MULTI_BINARY && check_binary_actions(h, who, actions, (size_t)n)) return -1;
+        if (h->dist == PPO_ACT_CATEGORICAL)
+            for (int32_t i = 0; i < n; ++i) {
+                const float x = actions[i];
+                if (!(x >= 0.f && x < (float)h->net.A && x == floorf(x)))
+                    return fail(h, "%s: actions[%d] = %g is not a category index in [0, %d)", who, (int)i, (double)x, h->net.A);
+            }
+    }
+    if (mask && check_masks(h, who, mask, (size_t)n, actions)) return -1;
+    const int W = ppo_distribution_width(h);
+    if (ensure_staging(h, n) || (mask && ensure_mask_staging(h, n)) || (params && ensure_params_staging(h, (size_t)n * W))) return -1;
+    const NetDev& net = h->net;
+    const size_t fb = sizeof(float);
+    HIP_OK(h, hipMemcpyAsync(h->st_obs, obs, (size_t)n * net.O * fb, hipMemcpyHostToDevice, h->stream));
+    if (actions) HIP_OK(h, hipMemcpyAsync(h->st_act, actions, (size_t)n * h->Aw * fb, hipMemcpyHostToDevice, h->stream));
+    if (mask) HIP_OK(h, hipMemcpyAsync(h->st_mask, mask, (size_t)n * net.A * fb, hipMemcpyHostToDevice, h->stream));
+    EvalArgs a{};
+    a.theta = h->theta; a.par = h->par; a.obs = h->st_obs; a.actions = actions ? h->st_act : nullptr; a.mask = mask ? h->st_mask : nullptr;
+    a.value = value ? h->st_vec[0] : nullptr; a.neglogp = neglogp ? h->st_vec[1] : nullptr; a.entropy = entropy ? h->st_vec[2] : nullptr;
+    a.params = params ? h->st_params : nullptr; a.n = n; a.W = W;
+    if (launch_eval(h, a)) return -1;
+    float* outs[3] = {value, neglogp, entropy};
+    for (int i = 0; i < 3; ++i) if (outs[i]) HIP_OK(h, hipMemcpyAsync(outs[i], h->st_vec[i], (size_t)n * fb, hipMemcpyDeviceToHost, h->stream));
+    if (params) HIP_OK(h, hipMemcpyAsync(params, h->st_params, (size_t)n * W * fb, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    prof_collect(h);
+    return 0;
+}
+
+int ppo_evaluate_actions(ppo_handle* h, const float* obs, const float* actions, int32_t n, const float* mask, float* value, float* neglogp, float* entropy) {
+    if (!h) return fail(nullptr, "ppo_evaluate_actions: null handle");
+    if (!value && !neglogp && !entropy) return fail(h, "ppo_evaluate_actions: value, neglogp and entropy are all NULL (nothing to compute)");
+    if (!actions) return fail(h, "ppo_evaluate_actions: null actions");
+    return eval_common(h, "ppo_evaluate_actions", obs, actions, n, mask, value, neglogp, entropy, nullptr);
+}
+
+int ppo_action_probability(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* params, int64_t count) {
+    if (!h) return fail(nullptr, "ppo_action_probability: null handle");
+    if (!params) return fail(h, "ppo_action_probability: null params");
+    if (n >= 1 && count != (int64_t)n * ppo_distribution_width(h))
+        return fail(h, "ppo_action_probability: count %lld is not n * W = %d * %d (ppo_distribution_width)", (long long)count, (int)n, ppo_distribution_width(h));
+    return eval_common(h, "ppo_action_probability", obs, nullptr, n, mask, nullptr, nullptr, nullptr, params);
+}
+
+int ppo_rollout_evaluate(ppo_handle* h, float* value, float* neglogp, float* entropy) {
+    if (!h) return fail(nullptr, "ppo_rollout_evaluate: null handle");
+    ENTER_Q(h);
+    if (eval_refuse_bf16(h, "ppo_rollout_evaluate")) return -1;
+    if (!value && !neglogp && !entropy) return fail(h, "ppo_rollout_evaluate: value, neglogp and entropy are all NULL (nothing to compute)");
+    if (!h->E) return fail(h, "ppo_rollout_evaluate: no rollout allocated (ppo_rollout_alloc + collect first)");
+    if (!h->ro_finished) return fail(h, "ppo_rollout_evaluate: the rollout is not finished (ppo_rollout_finish or ppo_collect_synthetic first)");
+    const int B = h->E * h->T;
+    if ((size_t)B > h->ev_out_rows) {                               // three row vectors of the rollout's size and nothing else: no input is staged
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < 3; ++i) if (dev_alloc(h, &h->ev_out[i], (size_t)B)) return -1;
+        h->ev_out_rows = (size_t)B;
+    }
+    EvalArgs a{};
+    a.theta = h->theta; a.par = h->par; a.obs = h->ro_obs; a.actions = h->ro_act; a.mask = h->masking ? h->ro_mask : nullptr;
+    a.value = value ? h->ev_out[0] : nullptr; a.neglogp = neglogp ? h->ev_out[1] : nullptr; a.entropy = entropy ? h->ev_out[2] : nullptr;
+    a.params = nullptr; a.n = B; a.W = ppo_distribution_width(h);
+    if (launch_eval(h, a)) return -1;
+    float* outs[3] = {value, neglogp, entropy};
+    for (int i = 0; i < 3; ++i) if (outs[i]) HIP_OK(h, hipMemcpyAsync(outs[i], h->ev_out[i], (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    prof_collect(h);
+    return 0;
+}
+
 // ---- train op -------------------------------------------------------------------------------------------------------
 int ppo_set_value_clip(ppo_handle* h, int32_t mode, float range) {
     if (!h) return fail(nullptr, "ppo_set_value_clip: null handle");
@@ -2406,6 +2533,7 @@ int ppo_train_step_masked(ppo_handle* h, float lr, float cliprange, const float*
                 return fail(h, "ppo_train_step: actions[%d] = %g is not a category index in [0, %d)", (int)i, (double)x, h->net.A);
         }
     if (mask && check_masks(h, "ppo_train_step_masked", mask, (size_t)n, actions)) return -1;
+    h->mirror_stale = true;                                         // (the checks have passed: weights move from here on)
     h->bf.epoch_staged = false;
     if (ensure_staging(h, n) || ensure_train_ws(h, n) || (mask && ensure_mask_staging(h, n))) return -1;
     const NetDev& net = h->net;
@@ -2772,7 +2900,7 @@ int ppo_rollout_alloc(ppo_handle* h, int32_t E, int32_t T) {
         dev_alloc(h, &h->last_val, E) || dev_alloc(h, &h->ro_noise, B * n.A))
         return -1;
     if (h->masking && (dev_alloc(h, &h->ro_mask, B * n.A) || mask_fill_ones(h, h->ro_mask, B * n.A))) return -1;
-    h->E = E; h->T = T; h->host_values_due = false;
+    h->E = E; h->T = T; h->host_values_due = false; h->ro_finished = false;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     // the pinned mask block of the discrete host-Env forms, fused and resident (only while masking is on and either can take effect)
     if (h->pin_mask) { (void)hipHostFree(h->pin_mask); h->pin_mask = nullptr; h->pin_mask_dev = nullptr; }
@@ -3245,6 +3373,7 @@ int ppo_rollout_act_masked(ppo_handle* h, int32_t t, const float* noise, const f
     if (mask && !h->masking) return fail(h, "ppo_rollout_act_masked: action masking is off for this handle (ppo_set_action_masking)");
     if (mask && check_masks(h, "ppo_rollout_act_masked", mask, (size_t)h->E, nullptr)) return -1;
     ENTER(h);
+    h->ro_finished = false;                                         // (ppo_rollout_evaluate: rows of two collects from here to the next finish)
     float* mask_row = nullptr;
     const HostForm form = host_form(h, noise != nullptr);
     // the discrete forms of the fused and the resident step read the mask from the pinned block in place and store row t of the mask buffer themselves
@@ -3331,6 +3460,7 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
     HIP_OK(h, hipStreamSynchronize(h->stream));
     prof_collect(h);
     if (bf16_chain_err_test(h)) return -1;
+    h->ro_finished = true;
     return peer_check(h);
 }
 
@@ -3479,6 +3609,7 @@ static int collect_per_step(ppo_handle* h, const CollectIn& in) {
 int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t step0, int first, const float* noise, float gamma, float lam) {
     ENTER(h);
     if (!h->E) return fail(h, "ppo_collect_synthetic: no rollout allocated (call ppo_rollout_alloc first)");
+    h->ro_finished = false;
     const size_t E = h->E, BA = E * h->T * h->net.A;
     if (noise) HIP_OK(h, hipMemcpyAsync(h->ro_noise, noise, BA * sizeof(float), hipMemcpyHostToDevice, h->stream));
     // a masking handle: the seeded env has no notion of legality, every row is collected (unmasked kernels) and recorded as all allowed
@@ -3511,6 +3642,7 @@ int ppo_collect_synthetic(ppo_handle* h, uint32_t seed, int32_t env0, uint32_t s
         HIP_OK(h, hipMemcpy(&e, coop_words(h) + 16 * (size_t)h->nw_coop_G, sizeof e, hipMemcpyDeviceToHost));
         if (e) return fail(h, "ppo_collect_synthetic: workgroup %u of the cooperative rollout gave up waiting for the others", e - 1);
     }
+    h->ro_finished = true;
     return peer_check(h);
 }
 
@@ -3898,6 +4030,7 @@ int ppo_update(ppo_handle* h, float lr, float cliprange, int32_t epochs, int32_t
     if (!h->E) return fail(h, "ppo_update: no rollout allocated (ppo_rollout_alloc + collect first)");
     const int B = h->E * h->T;
     if (epochs < 1 || nmb < 1 || B % nmb) return fail(h, "ppo_update: n_batch %d not divisible by nminibatches %d", B, nmb);
+    h->mirror_stale = true;                                         // (launch_eval)
     const int M = B / nmb;
     if (ensure_train_ws(h, M)) return -1;
     const int steps = epochs * nmb;

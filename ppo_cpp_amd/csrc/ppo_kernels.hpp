@@ -1106,6 +1106,177 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_step_kernel(NetDev ne
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Policy query (ppo_evaluate_actions, ppo_action_probability, ppo_rollout_evaluate; no reference counterpart: stable-baselines' proba_step / evaluate_actions): the
+// act model for GIVEN actions.  policy_step_kernel's geometry -- one 16-row tile per workgroup, blockIdx.y = 0 policy tower, = 1 value tower, the same ladder -- and
+// its statements up to the head.  The given actions are read by the lanes that use them, requested in front of the head product, which hides the round trip: lane
+// `part` owns columns part, part + 16, .. of a Gaussian or multi-binary row, a categorical row has one index, lane k of a multi-categorical row fetches component k's.
+// (Not staged through stage_block_inputs' RowScalars::actions as train_fwd_bwd_kernel stages them: that form reads two row scalars this kernel does not have and holds
+// the tile's values in registers under the first layer's weight prefetch; here nothing of the actions exists before the forward chain has ended.)
+// The head block then forms, with the pieces of ppo_head.hpp only,
+//   neglogp[row] of the given action (the step kernel's lane loop, maximum, z and first-index rules with the given index in place of the drawn one: the step's bits),
+//   entropy[row] (the train kernel's terms and reduction order) and
+//   params[row][W]: Gaussian mu[0..A) | std[0..A); categorical / multi-categorical p_j = ex_j / z of j's own component, exactly +0 for a forbidden category;
+//   multi-binary bern_parts(l).p.  Padding columns are never stored.
+// Each output is stored only where its pointer is non-null.  No RNG, no host_action publish, no obs_out.  A kernel family of its own (every existing kernel keeps
+// its machine code); one template for the six head forms: CAT / MASK / MULTI as in policy_step_kernel, BIN the multi-binary head.
+// A categorical index is brought inside its component before it indexes the tile (the host calls check it; device-resident rollout fields are the caller's).
+struct EvalArgs {
+    const float* theta;
+    const float* par;        // small-parameter mirror [2][par_total]
+    const float* obs;        // [n,O], as the policy takes them
+    const float* actions;    // [n,Aw] or null (then neglogp is not asked for)
+    const float* mask;       // [n,A] (non-zero = allowed); read by the <.., CAT, MASK> instantiations only
+    float* value;            // [n] or null: the value tower's blocks exit
+    float* neglogp;          // [n] or null
+    float* entropy;          // [n] or null
+    float* params;           // [n,W] or null
+    int n, W;
+};
+struct EvalArgsM : EvalArgs { CompTable comp; };
+// stage_block_inputs under a hook type of this kernel's own: the instantiation <0, NoHook> stays the step kernels' alone.  The compiler specialises a helper on
+// what ALL its callers pass before it inlines it, so a further caller of a shared instantiation can change the existing callers' machine code (measured: twelve
+// policy_step_kernel<1, 1, 0, ..> instantiations, profiles/r19_a_policy_eval_kernels.txt)
+struct EvalHook { __device__ __forceinline__ void operator()() const {} };
+template <int CT, int KS, int CTH, bool WIDE, bool CAT, bool MASK, bool MULTI, bool BIN>
+__global__ __launch_bounds__(BLOCK_THREADS, 2) void policy_eval_kernel(NetDev net, std::conditional_t<MULTI, EvalArgsM, EvalArgs> a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
+    static_assert(!(CAT && BIN), "one head per instantiation");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(a)>();
+    const int tower = blockIdx.y;
+    if (tower == 1 && !a.value) return;
+    if (tower == 0 && !a.neglogp && !a.entropy && !a.params) return;
+    const int row0 = blockIdx.x * ROWS_PER_BLOCK;
+    const int ld0 = net.Kp0 + LDS_PAD;
+    WRing<CT, KS> wpre;
+    HeadFrag<CTH> hpre;
+    dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][0], net.Hp[0], net.Hp[0], net.Kp0);
+    float* par = lds + net.lds_par - net.par_skip;      // indexed with absolute mirror offsets
+    stage_block_inputs<0, EvalHook>(net, a.par + tower * net.par_total, par, lds + net.lds_h[0], ld0, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0},
+                                    nullptr, nullptr, RowScalars{nullptr, nullptr, nullptr, nullptr, nullptr, 0}, nullptr, nullptr, EvalHook());
+    lds_barrier();
+    int K = net.Kp0, ldx = ld0;
+    for (int l = 0; l < net.L; ++l) {
+        const int Np = net.Hp[l], ldy = Np + LDS_PAD;
+        dense_tile<CT, KS, EP_BIAS_TANH>(wpre, a.theta + net.w_off[tower][l], Np, WIDE ? a.par + tower * net.par_total + net.par_b[l] : par + net.par_b[l], lds + net.lds_h[l], ldx, K,
+                                         lds + net.lds_h[l + 1], ldy, Np, nullptr, 0, nullptr, 0, row0, a.n, [&]() __attribute__((always_inline)) {
+                                             if (l + 1 < net.L) dense_prefetch<CT, KS>(wpre, a.theta + net.w_off[tower][l + 1], net.Hp[l + 1], net.Hp[l + 1], Np);
+                                         });
+        lds_barrier();
+        K = Np; ldx = ldy;
+    }
+    const float* hL = lds + net.lds_h[net.L];
+    if (tower == 1) {
+        const float v = value_head(hL, ldx, K, par + net.par_wv, par[net.par_bv]);
+        const int row = row0 + (threadIdx.x >> 4);
+        if ((threadIdx.x & 15) == 0 && row < a.n) a.value[row] = v;
+        return;
+    }
+    // 16 lanes per row, each lane owns columns j = part, part+16, ...
+    const int r = threadIdx.x >> 4, part = threadIdx.x & 15;
+    const int row = row0 + r;
+    const bool live = row < a.n, given = live && a.actions;
+    float act0 = 0.f;                                                  // this lane's first action value (see above), in flight under the head product
+    if (given) {
+        if constexpr (MULTI) { if (part < a.comp.K) act0 = a.actions[(size_t)row * a.comp.K + part]; }
+        else if constexpr (CAT) act0 = a.actions[row];
+        else if (part < net.A) act0 = a.actions[(size_t)row * net.A + part];
+    }
+    // the split-K head's weights are requested HERE, behind the last layer, not under it as in the step kernel: 48 registers less at the kernel's fullest point.
+    // With them there the <4, 2, 2, false, ..> instantiations (the only ones with CTH > 0) filled the 256 registers that two workgroups per compute unit leave a
+    // wave and spilled two to four to scratch; the policy tower pays one weight round trip in the open for it (profiles/r19_a_policy_eval_kernels.txt)
+    if constexpr (CTH > 0) head_prefetch<CTH>(hpre.w, a.theta + net.wmu_off, net.Ap, K);
+    policy_head<CTH>(net, a.theta, hpre, hL, ldx, K, lds);
+    const float* mus = lds + net.lds_mu;
+    const int ldm = net.Ap + LDS_PAD;
+    float* prow = (a.params && live) ? a.params + (size_t)row * a.W : nullptr;
+    float nlp = 0.f, ent = 0.f;
+    if constexpr (CAT) {
+        // one component [o, e) of the row: the step kernel's maximum and normaliser over the allowed categories, the given index `ia` where it has the drawn one
+        auto component = [&](int o, int e, int ia, float& nk, float& hk) __attribute__((always_inline)) {
+            float bl = -INFINITY;
+            int il = MASK ? e : o;
+            for (int j = o + part; j < e; j += 16) {
+                const float l = mus[r * ldm + j];
+                bool mk = true;
+                if constexpr (MASK) mk = live ? a.mask[(size_t)row * net.A + j] != 0.f : true;
+                if (mk) cat_take<MASK>(l, j, e, bl, il);
+            }
+            group16_argmax(bl, il);
+            const float m = bl;
+            float z = 0.f;
+            for (int j = o + part; j < e; j += 16) {
+                if constexpr (MASK) { if (live && a.mask[(size_t)row * net.A + j] == 0.f) continue; }
+                z += expf(mus[r * ldm + j] - m);
+            }
+            z = group16_sum(z);
+            const float la = mus[r * ldm + ia] - m;
+            const float lz = logf(z);
+            nk = lz - la;
+            float h = 0.f;
+            for (int j = o + part; j < e; j += 16) {
+                bool mk = true;
+                if constexpr (MASK) mk = !live || a.mask[(size_t)row * net.A + j] != 0.f;
+                float p = 0.f;
+                if (mk) {
+                    const float a0 = mus[r * ldm + j] - m, ex = expf(a0);
+                    h += cat_entropy_term(ex, z, lz, a0);
+                    p = ex / z;
+                }
+                if (prow) prow[j] = p;
+            }
+            hk = group16_sum(h);
+        };
+        if constexpr (MULTI) {
+            for (int k = 0; k < a.comp.K; ++k) {
+                const int o = a.comp.off[k], e = a.comp.off[k + 1];
+                const float ak = __shfl(act0, k, 16);
+                const int ia = given ? min(max(o + (int)ak, o), e - 1) : o;
+                float nk, hk;
+                component(o, e, ia, nk, hk);
+                nlp = k == 0 ? nk : nlp + nk;
+                ent = k == 0 ? hk : ent + hk;
+            }
+        } else {
+            const int ia = given ? min(max((int)act0, 0), net.A - 1) : 0;
+            component(0, net.A, ia, nlp, ent);
+        }
+    } else if constexpr (BIN) {
+        for (int j = part; j < net.A; j += 16) {
+            const float l = mus[r * ldm + j];
+            const BernParts b = bern_parts(l);
+            const float x = given ? (j == part ? act0 : a.actions[(size_t)row * net.A + j]) : bern_mode(l);
+            nlp += bern_nlp_elem(b, l, x);
+            ent += bern_entropy_elem(b, l);
+            if (prow) prow[j] = b.p;
+        }
+        nlp = group16_sum(nlp);
+        ent = group16_sum(ent);
+    } else {
+        float ssq = 0.f, slog = 0.f;
+        for (int j = part; j < net.A; j += 16) {
+            const float mu = mus[r * ldm + j];
+            const GaussStd gs = gauss_std(mu, par[net.par_ls + j]);
+            const float act = given ? (j == part ? act0 : a.actions[(size_t)row * net.A + j]) : mu;
+            const float z = gauss_z(act, mu, gs.sigma);
+            ssq += z * z;
+            slog += gs.logstd;
+            ent += gauss_entropy_elem(gs.logstd);
+            if (prow) { prow[j] = mu; prow[net.A + j] = gs.sigma; }
+        }
+        ssq = group16_sum(ssq);
+        slog = group16_sum(slog);
+        ent = group16_sum(ent);
+        nlp = gauss_nlp(ssq, slog, net.A);
+    }
+    if (part == 0 && live) {
+        if (a.neglogp) a.neglogp[row] = nlp;
+        if (a.entropy) a.entropy[row] = ent;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Train model forward + loss + backward down to the pre-activation gradients of every layer, for one 16-row
 // tile of the minibatch and one tower.  Everything a row needs stays in LDS; what the weight-gradient kernel
 // needs (layer inputs X_l and pre-activation gradients dY_l) is written to HBM/L2 once.

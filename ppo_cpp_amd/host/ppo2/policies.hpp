@@ -39,6 +39,23 @@ public:
         check(ppo_value(h_, obs.data(), static_cast<int>(obs.rows()), v.data()), "value()");
         return v;
     }
+    // The policy for GIVEN actions (no reference counterpart; stable-baselines 3 evaluate_actions): {values [n,1], neglogps [n,1], entropies [n,1]}.  actions as step()
+    // returns them, mask as step() takes it.  Stateless: no draw, nothing of the rollout, the normaliser or Adam is touched (include/ppo_hip.h, ppo_evaluate_actions).
+    virtual std::vector<Mat> evaluate_actions(const Mat& obs, const Mat& actions, const Mat* mask = nullptr) {
+        const int n = static_cast<int>(obs.rows());
+        if (actions.rows() != obs.rows() || actions.cols() != act_dim_) throw std::runtime_error("evaluate_actions error: actions must be [n, action_width]");
+        Mat v(n, 1), nlp(n, 1), ent(n, 1);
+        check(ppo_evaluate_actions(h_, obs.data(), actions.data(), n, mask ? mask->data() : nullptr, v.data(), nlp.data(), ent.data()), "evaluate_actions");
+        return {v, nlp, ent};
+    }
+    // The action distribution's parameters [n, W] (stable-baselines 2 ActorCriticPolicy.proba_step): Gaussian mu | std, categorical / multi-categorical the
+    // probabilities of every category (0 for a forbidden one), multi-binary P(bit = 1); W = ppo_distribution_width
+    virtual Mat proba_step(const Mat& obs, const Mat* mask = nullptr) {
+        const int n = static_cast<int>(obs.rows()), W = ppo_distribution_width(h_);
+        Mat p(n, W);
+        check(ppo_action_probability(h_, obs.data(), n, mask ? mask->data() : nullptr, p.data(), (int64_t)n * W), "proba_step");
+        return p;
+    }
     // Runner::set_returns' GAE scan (runner.hpp:159-191) on the device; [T,E] time-major
     virtual void gae(const Mat& rewards, const Mat& values, const Mat& dones, const Mat& last_values, const Mat& last_dones, float gamma,
                      float lam, Mat& returns) {

@@ -229,6 +229,19 @@ public:
         return act_model_.get_deterministic_action(obs, &mask);
     }
 
+    // stable-baselines' BaseRLModel.action_probability(observation, actions=None, logp=False), observations as the policy takes them (no reference counterpart):
+    //   no actions: the distribution's parameters [n, W] (MlpPolicy::proba_step);  with actions: the probability (density, for a Gaussian head) of each row's action
+    //   [n,1] = exp(-neglogp);  with logp: its logarithm = -neglogp.  mask [n, categories] or null, as in MlpPolicy::step.
+    Mat action_probability(const Mat& obs, const Mat* actions = nullptr, bool logp = false, const Mat* mask = nullptr) {
+        return action_probability(act_model_, obs, actions, logp, mask);
+    }
+    // ... on any policy object (what the member calls)
+    static Mat action_probability(MlpPolicy& policy, const Mat& obs, const Mat* actions = nullptr, bool logp = false, const Mat* mask = nullptr) {
+        if (!actions) return policy.proba_step(obs, mask);
+        const Mat nlp = policy.evaluate_actions(obs, *actions, mask)[1];
+        return logp ? -nlp : nlp.unary([](float x) { return std::exp(-x); });
+    }
+
     // save cadence of the reference (ppo2.hpp:256-262, 361-376): a save every ceil(n_updates / num_saves) updates with
     // ids 0, 1, ..., plus a trailing save when the interval does not divide the number of updates
     void learn(int total_timesteps, int num_saves = 0, const std::string& save_path = "") {

@@ -865,6 +865,29 @@ int ppo_host_target_kl_checkpoint(const char* prefix, float target_kl, int strip
     return rc;
 }
 
+// The policy queries of the host layer on a handle the CALLER owns (`handle` is a ppo_handle*; nothing is created or destroyed here): an MlpPolicy on it, then
+// MlpPolicy::evaluate_actions -> values, neglogps, entropies [n]; MlpPolicy::proba_step -> params [n, ppo_distribution_width]; PPO2::action_probability with the
+// actions -> prob [n] and, with logp, logprob [n].  obs [n, obs_dim], actions [n, ppo_action_width], mask [n, mask_cols] or null.  Returns 0; -1 = error (stderr).
+int ppo_host_policy_query(void* handle, const float* obs, int obs_dim, const float* actions, const float* mask, int mask_cols, int n, float* values, float* neglogps,
+                          float* entropies, float* params, float* prob, float* logprob) {
+    try {
+        ppo_handle* h = static_cast<ppo_handle*>(handle);
+        MlpPolicy policy(h, 0);
+        auto mat = [](const float* src, int rows, int cols) { Mat m(rows, cols); std::memcpy(m.data(), src, sizeof(float) * (size_t)rows * cols); return m; };
+        auto put = [](const Mat& m, float* dst) { std::memcpy(dst, m.data(), sizeof(float) * (size_t)m.size()); };
+        const Mat o = mat(obs, n, obs_dim), a = mat(actions, n, policy.action_width());
+        Mat mk;
+        if (mask) mk = mat(mask, n, mask_cols);
+        const Mat* mp = mask ? &mk : nullptr;
+        const std::vector<Mat> r = policy.evaluate_actions(o, a, mp);
+        put(r[0], values); put(r[1], neglogps); put(r[2], entropies);
+        put(policy.proba_step(o, mp), params);
+        put(PPO2::action_probability(policy, o, &a, false, mp), prob);
+        put(PPO2::action_probability(policy, o, &a, true, mp), logprob);
+        return 0;
+    } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return -1; }
+}
+
 // sizeof(ppo_host_args), sizeof(ppo_host_explicit): the Python mirrors check their layouts against these
 int ppo_host_args_size(void) { return (int)sizeof(ppo_host_args); }
 int ppo_host_explicit_size(void) { return (int)sizeof(ppo_host_explicit); }

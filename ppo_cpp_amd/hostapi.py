@@ -353,3 +353,20 @@ def binary_checkpoint(prefix, obs):
     acts = np.zeros((2, n, 6), np.float32)
     rc = lib.ppo_host_binary_checkpoint(prefix.encode(), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)))
     return rc, acts[0], acts[1]
+
+
+def policy_query(g, obs, actions, mask=None):
+    """The host layer's policy queries on a capi.PPOHip handle `g` (ppo_host_policy_query): MlpPolicy::evaluate_actions, MlpPolicy::proba_step and
+    PPO2::action_probability with the actions, plain and with logp.  Returns {"values", "neglogps", "entropies", "prob", "logprob": (n,); "params": (n, W)}."""
+    import numpy as np
+    lib = load_host_library()
+    obs = np.ascontiguousarray(obs, np.float32); n = obs.shape[0]
+    actions = np.ascontiguousarray(actions, np.float32).reshape(n, g.action_width)
+    mk = np.ascontiguousarray(mask, np.float32).reshape(n, g.A) if mask is not None else None
+    out = {k: np.zeros(n, np.float32) for k in ("values", "neglogps", "entropies", "prob", "logprob")}
+    out["params"] = np.zeros((n, g.distribution_width), np.float32)
+    fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+    if lib.ppo_host_policy_query(g.h, fp(obs), obs.shape[1], fp(actions), fp(mk) if mk is not None else None, g.A, n, fp(out["values"]), fp(out["neglogps"]),
+                                 fp(out["entropies"]), fp(out["params"]), fp(out["prob"]), fp(out["logprob"])) != 0:
+        raise RuntimeError("ppo_host_policy_query failed (message on stderr)")
+    return out
