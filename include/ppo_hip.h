@@ -219,8 +219,9 @@ int ppo_action_width(const ppo_handle* h);
  *     literal relu / abs expression) differentiates the kinks to 0 and gives another value there.
  *   Surrogate, value loss, approxkl and clipfrac see the row's neglogp unchanged.  float32 against float64 at 4096 x 18 logits: neglogp within 3.0e-6 abs at a spread
  *   of +-1.5, 9e-7 at +-40, 5e-7 at +-120; entropy within 3.0e-6 / 5e-7 / 2e-7; nothing overflows.
- *   The handle always runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts, instead of the plain names) on any
- *   hidden widths: never narrow, never train8_kernel, deferred Adam, the resident epoch kernel or a one-launch rollout -- the rules of an unflagged categorical handle.
+ *   Without PPO_ACT_BINARY_SHAPE_KERNELS (below) the handle runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts,
+ *   instead of the plain names) on any hidden widths: never narrow, never train8_kernel, deferred Adam, the resident epoch kernel or a one-launch rollout -- the rules
+ *   of an unflagged categorical handle.
  *   PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS and PPO_ACT_BF16_HEAD beside it on a PPO_F32 handle are accepted and change nothing (same bits, same counts).
  *   Every entry point of a categorical PPO_F32 handle works, actions [., A]; data parallel (ppo_dist_init, both shuffles) included.
  *   Host checks before anything is uploaded: every action of ppo_train_step / ppo_rollout_upload field 1 is exactly 0 or 1 (the message names row and column; NaN is
@@ -229,8 +230,22 @@ int ppo_action_width(const ppo_handle* h);
  *   Measured on an MI355X (us of device time per call at 18 obs, hidden [256,256]; this head | a categorical handle of 18 categories | a
  *   multi-categorical one with nvec = (2,) x 16): policy step 16.6 | 16.5 | 29.1 at 16 rows, 17.6 | 18.6 | 29.7 at 1024; train_fwd_bwd_kernel 25.5 | 24.3 | 39.4 at 64 rows,
  *   26.6 | 26.0 | 40.4 at 2048.  The elementwise head is about 1 us SLOWER than <cat> per train launch; it has not been tuned.
- *   Out of scope for this head: the narrow LDS-resident kernels, the [256,256] pair, the bf16 path, the fused host step and the resident rollouts, action masks. */
+ *   Out of scope for this head: the [256,256] pair, the bf16 path, the fused host step and the resident rollouts, action masks.
+ *   PPO_ACT_BINARY_SHAPE_KERNELS  PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_SHAPE_KERNELS lets a multi-binary PPO_F32 handle take the narrow LDS-resident family's step and
+ *                        train kernels under the rule of a flagged categorical handle: at most 4 hidden layers, every padded hidden width <= 64, padded
+ *                        observation and action widths <= 64, the plain LDS image within 160 KB, PPO_HIP_NO_NARROW unset.  (A flag of its own: PPO_ACT_SHAPE_KERNELS
+ *                        on this head is accepted and changes nothing, and stays so.)  Same arithmetic per element as the generic <mbin> kernels, the same counter
+ *                        keys: the same seed and rows draw what the generic kernels draw wherever u is not within rounding of p.  ppo_kernel_counts_all names,
+ *                        counted INSTEAD of the generic <mbin> names: "narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>" (static and runtime shapes share a
+ *                        name; the form launched under ppo_set_target_kl counts as the train kernel).  A train step is that launch + narrow_reduce_kernel +
+ *                        adam_kernel; no deferred Adam, no resident epoch, no one-launch rollout: ppo_set_host_step_fused and ppo_set_rollout_resident are
+ *                        accepted and change nothing (per-step launches on the device env, the copy form behind a host Env).  Masks and PPO_BF16 stay refused, the
+ *                        0 / 1 action checks stay.  A shape that does not qualify runs the generic <mbin> kernels, as without the flag (same bits, same counts, data
+ *                        parallel included).  Where the flag took effect ppo_dist_init refuses ("... data parallel is not supported for a multi-binary handle
+ *                        created with PPO_ACT_BINARY_SHAPE_KERNELS") and leaves the handle usable.  With any other distribution the bit is an "unknown
+ *                        action_dist" error, whose text names it; ppo_create_multi_ex refuses it with its own "unknown flag bit 0x2000". */
 #define PPO_ACT_MULTI_BINARY 3
+#define PPO_ACT_BINARY_SHAPE_KERNELS 0x2000
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);
@@ -527,6 +542,7 @@ int ppo_dist_unique_id(char uid[128]);
  *  a multi-categorical one on which that flag took effect (ppo_create_multi_ex) likewise: "... for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS";
  *  one on which PPO_ACT_PAIR_KERNELS took effect likewise: "... data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a multi-categorical one on which PPO_ACT_PAIR_KERNELS took effect: "... data parallel is not supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS";
+ *  a multi-binary one on which PPO_ACT_BINARY_SHAPE_KERNELS took effect: "... data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS";
  *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD";
  *  a multi-categorical PPO_BF16 handle (PPO_ACT_BF16_MULTI_HEAD): "... data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
@@ -581,8 +597,11 @@ int ppo_prof_read(ppo_handle* h, int max, char names[][32], double* total_ms, in
 int ppo_sync(ppo_handle* h);
 /* which kernel VARIANT the calls so far took: the library picks its kernels from the shape, and a caller or a
  * test can ask which ones were ENQUEUED since ppo_create (a hipGraph capture counts once, its replays do not).  names: e.g.
- * "train8_kernel", "train8_kernel<cat>", "train8_kernel<mcat>", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries */
+ * "train8_kernel", "train8_kernel<cat>", "train8_kernel<mcat>", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries.
+ * ppo_kernel_counts is FROZEN at its 60 rows: callers hold its row count fixed.  Variants added later ("narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>") appear
+ * only in ppo_kernel_counts_all, which reports every row: the 60 in the same order, then the later ones.  Buffers of 64 entries hold either. */
 int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued);
+int ppo_kernel_counts_all(const ppo_handle* h, int32_t max, char (*names)[32], int64_t* counts);
 
 /* ---- debug: a raw device buffer by name, padding included (the getters above copy the dense part of every tensor) ----------------
  * "theta" "adam_m" "adam_v" (padded), "thetaT" / "par" (the transposed and small-parameter mirrors the train kernels read), "grad" (+ its tail), "sumsq", "beta_pow", "hyper",

@@ -60,6 +60,7 @@ ACT_SHAPE_KERNELS = 0x100                               # PPO_ACT_SHAPE_KERNELS,
 ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, likewise
 ACT_PAIR_KERNELS = 0x400                                # PPO_ACT_PAIR_KERNELS, likewise
 ACT_BF16_MULTI_HEAD = 0x1000                            # PPO_ACT_BF16_MULTI_HEAD, a flag of ppo_create_multi_ex only
+ACT_BINARY_SHAPE_KERNELS = 0x2000                       # PPO_ACT_BINARY_SHAPE_KERNELS, a flag of ppo_create_ex beside PPO_ACT_MULTI_BINARY only
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -99,6 +100,10 @@ class PPOHip:
     else, naming row and column); explicit noise is (n, act_dim) uniforms, bit j is 1 where u_j < sigmoid(logit_j); act_deterministic gives logit_j > 0.  The tensor
     list is a categorical handle's (no pi/logstd), `.nvec` is [].  compute_dtype=0 only; the handle runs policy_step_kernel<mbin> / train_fwd_bwd_kernel<mbin> on any
     hidden widths, shape_kernels / pair_kernels / bf16_head are accepted and change nothing, and mask= raises the library's error.
+    binary_shape_kernels=True with it (PPO_ACT_BINARY_SHAPE_KERNELS; default False; a ValueError with any other action_dist): a handle whose shape qualifies
+    (every hidden width <= 64, at most 64 observations and bits, ...) runs narrow_step_kernel<mbin> / narrow_train_kernel<mbin> -- same arithmetic, the same draws for
+    the same seed, no data parallel; set_host_step_fused / set_rollout_resident change nothing on it; any other shape runs the generic <mbin> kernels.  The two names
+    are rows of kernel_counts(all_rows=True) only.  The attribute binary_shape_kernels keeps what was asked for.
 
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -108,8 +113,11 @@ class PPOHip:
     MASK_FIELDS = {"masks": 8}                  # [T, E, A]; a masking handle only (set_action_masking)
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
-    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, **overrides):
+    def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, binary_shape_kernels=False,
+                 **overrides):
         multi = action_dist == "multi_categorical"
+        if binary_shape_kernels and action_dist != "multi_binary":
+            raise ValueError("binary_shape_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if nvec is not None and not multi:
             raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
         if multi:
@@ -135,6 +143,7 @@ class PPOHip:
         self.shape_kernels = bool(shape_kernels)
         self.bf16_head = bool(bf16_head)
         self.pair_kernels = bool(pair_kernels)
+        self.binary_shape_kernels = bool(binary_shape_kernels)
         self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
@@ -146,7 +155,7 @@ class PPOHip:
                     else self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h))) != 0:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())
         elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)
-                                    | (ACT_PAIR_KERNELS if pair_kernels else 0), C.byref(h)) != 0:
+                                    | (ACT_PAIR_KERNELS if pair_kernels else 0) | (ACT_BINARY_SHAPE_KERNELS if binary_shape_kernels else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)
@@ -533,10 +542,11 @@ class PPOHip:
         n = self.lib.ppo_prof_read(self.h, 16, names, ms, cnt)
         return {names[i].value.decode(): (ms[i], cnt[i]) for i in range(n)}
 
-    def kernel_counts(self):
-        """{kernel variant: times enqueued since creation} -- which of the shape-selected kernels the calls so far took"""
+    def kernel_counts(self, all_rows=False):
+        """{kernel variant: times enqueued since creation} -- which of the shape-selected kernels the calls so far took.  The default is ppo_kernel_counts' frozen
+        60 rows; all_rows=True (ppo_kernel_counts_all) adds the variants named later: narrow_step_kernel<mbin>, narrow_train_kernel<mbin>."""
         names = ((C.c_char * 32) * 64)(); cnt = (C.c_int64 * 64)()
-        n = self.lib.ppo_kernel_counts(self.h, 64, names, cnt)
+        n = (self.lib.ppo_kernel_counts_all if all_rows else self.lib.ppo_kernel_counts)(self.h, 64, names, cnt)
         return {names[i].value.decode(): cnt[i] for i in range(n)}
 
     def debug_buffer(self, name):

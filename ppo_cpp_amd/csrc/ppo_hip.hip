@@ -71,7 +71,10 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
                      KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
                      KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
-                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_COUNT };
+                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_COUNT };
+// ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all only
+constexpr int KV_LEGACY_COUNT = 60;
+static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
 static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
@@ -103,7 +106,10 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        // kernel parked itself), counted INSTEAD of the act launches of "narrow_step_kernel<cat|mcat[,mask]>" / "narrow_host_step<..>"
                                        "narrow_rollout<cat>", "narrow_rollout<cat,mask>", "narrow_rollout<mcat>", "narrow_rollout<mcat,mask>",
                                        // a multi-binary handle (ppo_create_ex with PPO_ACT_MULTI_BINARY): counted INSTEAD of the plain names of the generic fp32 family, the only one it runs
-                                       "policy_step_kernel<mbin>", "train_fwd_bwd_kernel<mbin>"};
+                                       "policy_step_kernel<mbin>", "train_fwd_bwd_kernel<mbin>",
+                                       // a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS on a narrow shape (static and runtime-shape instantiations share a name, the
+                                       // early-stopping form counts under the train name): counted INSTEAD of the two <mbin> names above; ppo_kernel_counts_all only
+                                       "narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -112,17 +118,18 @@ struct Head {
 };
 // which entry a launch of a kernel family with a head bumps: a row per family, a column per head form.  (The narrow Gaussian entries say whether the compile-time
 // shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.  KV_COUNT: the family
-// has no kernel of that head, and no handle of that head reaches it -- a multi-binary handle runs the generic fp32 family only.)
+// has no kernel of that head, and no handle of that head reaches it -- a multi-binary handle runs the generic fp32 family or, with PPO_ACT_BINARY_SHAPE_KERNELS, the narrow
+// step / train kernels, nothing else.)
 enum HeadFamily { KF_POLICY_STEP = 0, KF_TRAIN_FB, KF_TRAIN8, KF_NARROW_STEP_STATIC, KF_NARROW_STEP, KF_NARROW_TRAIN_STATIC, KF_NARROW_TRAIN, KF_NARROW_HOST_STEP, KF_BF16_STEP,
                   KF_BF16_TRAIN, KF_NARROW_ROLLOUT, KF_COUNT };
 constexpr KernelVariant kHeadVariant[KF_COUNT][6] = {
     {KV_POLICY_STEP, KV_POLICY_STEP_CAT, KV_POLICY_STEP_CAT_MASK, KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_POLICY_STEP_MBIN},
     {KV_TRAIN_FB, KV_TRAIN_FB_CAT, KV_TRAIN_FB_CAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK, KV_TRAIN_FB_MBIN},
     {KV_TRAIN8, KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK, KV_COUNT},
-    {KV_NARROW_STEP_STATIC, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_COUNT},
-    {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_COUNT},
-    {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_COUNT},
-    {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_COUNT},
+    {KV_NARROW_STEP_STATIC, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_STEP_MBIN},
+    {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_STEP_MBIN},
+    {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_NARROW_TRAIN_MBIN},
+    {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_NARROW_TRAIN_MBIN},
     {KV_COUNT, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK, KV_COUNT},
     {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_COUNT},
     {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK, KV_COUNT},
@@ -153,8 +160,9 @@ struct ppo_handle {
     int CT = 1;                       // column tiles per wave in the dense layers (4 for wide nets)
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
-    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family only (never narrow, t8, dw2 or bf16)
+    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (never t8, dw2 or bf16; narrow only with binary_shape_kernels)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
+    bool binary_shape_kernels = false;   // created with PPO_ACT_BINARY_SHAPE_KERNELS as a multi-binary handle: may take the narrow family's step / train kernels (build_narrow_layout); after ppo_create_ex: it did
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
     bool bf16_multi_head = false;     // created with PPO_ACT_BF16_MULTI_HEAD as a multi-categorical PPO_BF16 handle (ppo_create_multi_ex): bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>
     bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical or multi-categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
@@ -607,7 +615,8 @@ int build_layout(ppo_handle* h) {
 void build_narrow_layout(ppo_handle* h) {
     const NetDev& n = h->net;
     h->narrow = false;
-    if (h->bf.on || (h->dist != PPO_ACT_GAUSSIAN && !h->shape_kernels) || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
+    const bool asked = h->dist == PPO_ACT_GAUSSIAN || (h->dist == PPO_ACT_MULTI_BINARY ? h->binary_shape_kernels : h->shape_kernels);   // (each discrete head under its own flag)
+    if (h->bf.on || !asked || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
     for (int l = 0; l < n.L; ++l) if (n.Hp[l] > 64) return;
     const char* off = getenv("PPO_HIP_NO_NARROW");
     if (off && off[0] == '1') return;
@@ -799,7 +808,7 @@ ObsNorm no_norm_fwd() { return ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}; }
 // ppo_create_ex asks the same pickers for every head the handle can launch (for_each_head) when it raises the dynamic-LDS limits.
 template <bool CAT, bool MASK, bool MULTI, bool BIN = false>
 struct HeadTag { static constexpr bool cat = CAT, mask = MASK, multi = MULTI, bin = BIN; };
-using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn) know it, no other
+using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn) and the narrow step / train pickers (nw_step_fn, nw_train_fn) know it, no other
 using GaussHead = HeadTag<false, false, false>;
 
 // (a mask on a Gaussian handle: the entry points and launch_step refuse it before any launch)
@@ -1191,7 +1200,9 @@ int bf16_weight_grads(ppo_handle* h, const TrainArgs& ta, int Rp, int tile0 = -1
 // every form that keeps a Gaussian head (deferred Adam, resident epoch, rollout1, the cooperative / fused rollouts) asks nw_gauss() where it is decided.  The
 // fused host step and the resident rollout in the 32-row workgroup have discrete forms of their own, opt-in per handle: host_fused_discrete(), resident_discrete().
 static bool nw_gauss(const ppo_handle* h) { return h->narrow && h->dist == PPO_ACT_GAUSSIAN; }
-static bool nw_discrete(const ppo_handle* h) { return h->narrow && h->dist != PPO_ACT_GAUSSIAN; }
+static bool nw_discrete(const ppo_handle* h) { return h->narrow && (h->dist == PPO_ACT_CATEGORICAL || h->dist == PPO_ACT_MULTI_CATEGORICAL); }
+// (a narrow multi-binary handle -- PPO_ACT_BINARY_SHAPE_KERNELS took effect -- is neither: it has narrow_step_kernel / narrow_train_kernel<mbin> and nothing else, so
+// the fused host step, the resident rollouts and every Gaussian-only form pass it by: per-step launches on the device env, the copy form behind a host Env)
 
 // The pickers: the instantiation of a kernel family for a head and the family's own axes, named HERE and nowhere else -- the launch below each and the
 // dynamic-LDS pass of ppo_create_ex (lds_opt_in) both ask them.
@@ -1225,18 +1236,21 @@ static auto train_fb_fn(T, int rung) {
 // the narrow kernels, per NW_DISPATCH shape: the overloads that take the component table (and narrow_train_stop_multi_kernel) are the multi-categorical forms
 template <int KP0, int HP, int AP, int LL, class T>
 static auto nw_step_fn(T) {
-    if constexpr (T::multi) return narrow_step_kernel<KP0, HP, AP, LL, true, T::mask, true>;
+    if constexpr (T::bin) return narrow_step_kernel<KP0, HP, AP, LL, MbinHead>;
+    else if constexpr (T::multi) return narrow_step_kernel<KP0, HP, AP, LL, true, T::mask, true>;
     else return narrow_step_kernel<KP0, HP, AP, LL, T::cat, T::mask>;
 }
 template <bool STOP, int KP0, int HP, int AP, int LL, class T>
 static auto nw_train_fn(T) {
-    if constexpr (STOP && T::multi) return narrow_train_stop_multi_kernel<KP0, HP, AP, LL, T::mask>;
+    if constexpr (T::bin) { if constexpr (STOP) return narrow_train_stop_kernel<KP0, HP, AP, LL, MbinHead>; else return narrow_train_kernel<KP0, HP, AP, LL, MbinHead>; }
+    else if constexpr (STOP && T::multi) return narrow_train_stop_multi_kernel<KP0, HP, AP, LL, T::mask>;
     else if constexpr (STOP) return narrow_train_stop_kernel<KP0, HP, AP, LL, T::cat, T::mask>;
     else if constexpr (T::multi) return narrow_train_kernel<KP0, HP, AP, LL, false, false, true, T::mask, true>;
     else return narrow_train_kernel<KP0, HP, AP, LL, false, false, T::cat, T::mask>;
 }
 template <int KP0, int HP, int AP, int LL, class T>
 static auto nw_host_step_fn(T) {
+    static_assert(!T::bin, "the fused host step has no multi-binary form: host_form never chooses it for that head");
     if constexpr (T::multi) return narrow_host_step_kernel<KP0, HP, AP, LL, true, T::mask, true>;
     else if constexpr (T::cat) return narrow_host_step_kernel<KP0, HP, AP, LL, true, T::mask>;
     else return narrow_host_step_kernel<KP0, HP, AP, LL>;
@@ -1244,6 +1258,7 @@ static auto nw_host_step_fn(T) {
 // the resident rollout in the 32-row workgroup; MG: more than one group of 32 rows (33..NW_RO_MAX_E environments)
 template <int KP0, int HP, int AP, int LL, bool MG, class T>
 static auto nw_rollout_fn(T) {
+    static_assert(!T::bin, "the resident rollout has no multi-binary form: dev_form / host_form never choose it for that head");
     if constexpr (T::multi) return narrow_rollout_kernel<KP0, HP, AP, LL, MG, true, T::mask, true>;
     else if constexpr (T::cat) return narrow_rollout_kernel<KP0, HP, AP, LL, MG, true, T::mask>;
     else return narrow_rollout_kernel<KP0, HP, AP, LL, MG>;
@@ -1632,7 +1647,7 @@ static void launch_narrow_train(T H, ppo_handle* h, int groups, const NwTrainArg
     const auto na = head_args<NwTrainArgsM>(H, h, na0);
     const unsigned* stop = h->stop;
 #define X(a, b, c, d) do { if (kl_gate(h)) hipLaunchKernelGGL((nw_train_fn<true, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na, stop); \
-                           else if constexpr (T::multi) hipLaunchKernelGGL((nw_train_fn<false, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na); \
+                           else if constexpr (T::multi || T::bin) hipLaunchKernelGGL((nw_train_fn<false, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na); \
                            else hipLaunchKernelGGL((nw_train_fn<false, a, b, c, d>(H)), grid, blk, lds, h->stream, h->net, h->nw, na, NwLazyArgs{}); } while (0)
     NW_DISPATCH(h, X);
 #undef X
@@ -1655,7 +1670,7 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
         SET_STAMPS(na.stamps, true, 0);
         const Head hd = head_of(h, ta.mask != nullptr);
         ++h->kv[kHeadVariant[h->nw_static ? KF_NARROW_TRAIN_STATIC : KF_NARROW_TRAIN][hd.index()]];
-        if (!hd.cat && h->nw_pending) {                                // (a discrete head never defers: nw_lazy is a Gaussian handle's)
+        if (!hd.cat && !hd.bin && h->nw_pending) {                     // (a discrete head never defers: nw_lazy is a Gaussian handle's)
             // the previous step's clip + Adam rides in this launch: read set nw_cur, write the other one
             float* set[2][3] = {{h->theta, h->adam_m, h->adam_v}, {h->nw_theta1, h->nw_m1, h->nw_v1}};
             const int ci = h->nw_cur, co = ci ^ 1;
@@ -1941,9 +1956,12 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     const bool bf16_multi_head = nvec && (action_dist & PPO_ACT_BF16_MULTI_HEAD) != 0;      // (ppo_create_multi_ex only: from ppo_create_ex the bit stays in action_dist and is refused below)
     if (nvec) action_dist &= ~(int32_t)PPO_ACT_BF16_MULTI_HEAD;
     action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS);
+    // PPO_ACT_BINARY_SHAPE_KERNELS belongs to PPO_ACT_MULTI_BINARY alone: beside any other distribution the bit stays in and is refused below (ppo_create_multi_ex has refused it already: "unknown flag bit")
+    const bool binary_shape_kernels = !nvec && action_dist == (PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_SHAPE_KERNELS);
+    if (binary_shape_kernels) action_dist = PPO_ACT_MULTI_BINARY;
     if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && action_dist != PPO_ACT_MULTI_BINARY && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
         return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
-                             "a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
+                             "PPO_ACT_BINARY_SHAPE_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && !bf16_head)
@@ -1960,7 +1978,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     ppo_handle* h = new ppo_handle();
     h->cfg = *cfg;
     h->dist = action_dist;
-    h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_MULTI_BINARY;   // (a Gaussian handle takes its shape's kernels anyway, a multi-binary one never: the flag changes nothing)
+    h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_MULTI_BINARY;   // (a Gaussian handle takes its shape's kernels anyway, a multi-binary one only under its own flag: this one changes nothing)
+    h->binary_shape_kernels = binary_shape_kernels;
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
     h->bf16_multi_head = bf16_multi_head && cfg->compute_dtype == PPO_BF16;   // (PPO_F32: the flag changes nothing)
     h->pair_kernels = pair_kernels && (action_dist == PPO_ACT_CATEGORICAL || action_dist == PPO_ACT_MULTI_CATEGORICAL) && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
@@ -2003,6 +2022,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
         dev_alloc(h, &h->stop, 4) || dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8))
         return bail(0);
     build_narrow_layout(h);
+    if (h->dist == PPO_ACT_MULTI_BINARY) h->binary_shape_kernels = h->narrow;     // likewise: a shape that does not qualify runs the generic <mbin> kernels, data parallel included
     if (h->dist == PPO_ACT_MULTI_CATEGORICAL) h->shape_kernels = h->narrow;       // from here on: the flag took effect (a shape that does not qualify runs the generic <mcat> kernels, data parallel included)
     if (upload_grad_src(h)) return bail(0);
     const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels;        // the heads train8_kernel has; a categorical or multi-categorical one only where the flag asks for it
@@ -2049,7 +2069,8 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
         // rollout (one and two groups of rows) -- for the Gaussian head and every head this handle can launch
         auto nw_heads = [&](auto H) {
 #define X(a, b, c, d) do { big_lds(nw_step_fn<a, b, c, d>(H)); big_lds(nw_train_fn<false, a, b, c, d>(H)); big_lds(nw_train_fn<true, a, b, c, d>(H)); \
-                           big_lds(nw_host_step_fn<a, b, c, d>(H)); big_lds(nw_rollout_fn<a, b, c, d, false>(H)); big_lds(nw_rollout_fn<a, b, c, d, true>(H)); } while (0)
+                           if constexpr (!decltype(H)::bin) {      /* (the multi-binary head has a step and a train kernel, nothing else) */ \
+                           big_lds(nw_host_step_fn<a, b, c, d>(H)); big_lds(nw_rollout_fn<a, b, c, d, false>(H)); big_lds(nw_rollout_fn<a, b, c, d, true>(H)); } } while (0)
             X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
 #undef X
         };
@@ -3117,10 +3138,11 @@ static int enqueue_host_step(ppo_handle* h, int t, bool act, const float* noise_
     ProfScope ps(h, PK_STEP);
     const Head hd = head_of(h, masked);
     if (act && hd.cat) ++h->kv[kHeadVariant[KF_NARROW_HOST_STEP][hd.index()]];
+    if (hd.bin) return fail(h, "narrow_host_step_kernel has no multi-binary form");      // (host_form never chooses the fused step for that head)
     with_head(hd, [&](auto H) {
         auto launch = [&](const auto& args) {
 #define X(a, b, c, d) hipLaunchKernelGGL((nw_host_step_fn<a, b, c, d>(H)), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, args)
-            NW_DISPATCH(h, X);
+            if constexpr (!decltype(H)::bin) NW_DISPATCH(h, X);       // (refused above: the picker has no instantiation to name)
 #undef X
         };
         if constexpr (!decltype(H)::cat) launch(q);
@@ -3156,12 +3178,13 @@ static void launch_rollout_kernel(ppo_handle* h, const NwRolloutArgs& q, bool on
     const bool groups = q.E > NW_ROWS;
     const size_t lds = rollout_lds(h);
     const Head hd = head_of(h, masked);
+    if (hd.bin) { fail(h, "narrow_rollout_kernel has no multi-binary form"); return; }    // (dev_form / host_form never choose a resident rollout for that head)
     ++h->kv[kHeadVariant[KF_NARROW_ROLLOUT][hd.index()]];
     with_head(hd, [&](auto H) {
         auto launch = [&](const auto& args) {
 #define X(a, b, c, d) do { if (groups) hipLaunchKernelGGL((nw_rollout_fn<a, b, c, d, true>(H)), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, args); \
                            else hipLaunchKernelGGL((nw_rollout_fn<a, b, c, d, false>(H)), dim3(1), dim3(NW_THREADS), lds, h->stream, n, h->nw, args); } while (0)
-            NW_DISPATCH(h, X);
+            if constexpr (!decltype(H)::bin) NW_DISPATCH(h, X);       // (refused above: the picker has no instantiation to name)
 #undef X
         };
         if constexpr (!decltype(H)::cat) launch(q);
@@ -4093,6 +4116,8 @@ int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128
     if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
     if (h->bf16_multi_head)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD");
+    if (h->binary_shape_kernels)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS (create it without the flag)");
     if (h->shape_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
@@ -4387,11 +4412,14 @@ int ppo_prof_read(ppo_handle* h, int max, char names[][32], double* total_ms, in
     return n;
 }
 
-int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued) {
+// rows [0, limit) of the variant table
+static int kernel_count_rows(const ppo_handle* h, int limit, int max, char names[][32], int64_t* enqueued) {
     int n = 0;
-    for (int i = 0; i < KV_COUNT && n < max; ++i) { snprintf(names[n], 32, "%s", kVariantNames[i]); enqueued[n] = h->kv[i]; ++n; }
+    for (int i = 0; i < limit && n < max; ++i) { snprintf(names[n], 32, "%s", kVariantNames[i]); enqueued[n] = h->kv[i]; ++n; }
     return n;
 }
+int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued) { return kernel_count_rows(h, KV_LEGACY_COUNT, max, names, enqueued); }
+int ppo_kernel_counts_all(const ppo_handle* h, int32_t max, char (*names)[32], int64_t* counts) { return kernel_count_rows(h, KV_COUNT, max, names, counts); }
 
 // Raw device buffers by name, PADDING INCLUDED (ppo_get_flat and ppo_get_last_grad copy the dense part of every tensor only): the transposed mirrors, the small-parameter
 // mirrors, the assembled gradient with its tail, the workspaces of the last train step, the gathered epoch.  For bitwise comparisons of two runs (tests/test_other_shapes.py,

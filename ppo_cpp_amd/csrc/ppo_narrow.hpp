@@ -397,10 +397,15 @@ __device__ __forceinline__ void nw_lazy_apply(const NetDev& net, const NwLayout&
 // component.  neglogp and entropy are added in component order from the first one's value, so one component gives the <CAT> bits.  The action row never touches
 // LDS: `act_k` is component `part`'s index within its component, in the register of lane `part` of the row (requested by the kernel ahead of the prologue's loads) and
 // broadcast inside the row's wave, so no lane can see a half-written row and NwLayout is the categorical handle's.
-template <int KP0, int HP, int AP, int LL, bool WT = true, bool CAT = false, bool MASK = false, bool MULTI = false>
+// BIN (narrow_train_kernel's multi-binary overload; never with CAT): the logits stand in the `mu` tile and the action bits in the `acts` tile, staged exactly like a
+// Gaussian head's actions.  Elementwise in the Gaussian branch's lane geometry: the row's neglogp and entropy are two group16_sums over bern_nlp_elem /
+// bern_entropy_elem, a lane keeps its (at most four) elements' logit, bit, p and e for the second pass, which writes bern_grad_elem where d mu goes and NOTHING to the
+// shared acts / dls tile; the padded logstd slot's partial is 0 as under CAT.  Dead rows and padding columns: exactly +0.
+template <int KP0, int HP, int AP, int LL, bool WT = true, bool CAT = false, bool MASK = false, bool MULTI = false, bool BIN = false>
 __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout& lay, const std::conditional_t<MULTI, NwTrainArgsM, NwTrainArgs>& a, float* lds, const int tower, const int grp,
                                               const int tidx = (int)threadIdx.x, const float act_k = 0.f) {
     static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
+    static_assert(!(BIN && CAT), "the multi-binary head is a head of its own");
     typedef NwShape<KP0, HP, AP, LL> S;
     const int tid = tidx, pipe = uni(tid >> 8), ptid = tid & 255;
     const int row0 = grp * NW_ROWS;
@@ -447,6 +452,7 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
         // (an exp and a division per element) -- same values, same results
         float ssq = 0.f, slog = 0.f, sent = 0.f;
         float zk[4], sk[4];
+        float bpk[4], bek[4];                                         // BIN: zk / sk keep the logit and the bit, these p and e = exp(-|l|)
         // categorical: m = max_j l_j, a0 = l - m, z = sum exp(a0); neglogp = log z - a0[act], entropy = sum_j p_j (log z - a0_j); a lane keeps its categories' a0
         // (in zk) and whether they count (ok: inside A and, MASK, allowed -- dead rows of the last group: all allowed)
         float cz = 1.f, clz = 0.f, cnlp = 0.f;
@@ -517,6 +523,21 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             for (int k = 0; k < 4; ++k) if (ok[k]) sent += cat_entropy_term(expf(zk[k]), cz, clz, zk[k]);
             sent = group16_sum(sent);
             cnlp = clz - la;
+        } else if constexpr (BIN) {
+            cnlp = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                             // (compile-time k: the kept values stay in registers)
+                const int j = part + 16 * k;
+                zk[k] = 0.f; sk[k] = 0.f; bpk[k] = 0.f; bek[k] = 0.f;
+                if (j < net.A) {
+                    const float l = mus[r * ldm + j];
+                    const BernParts b = bern_parts(l);
+                    const float x = live ? acts[r * Ap + j] : 0.f;
+                    zk[k] = l; sk[k] = x; bpk[k] = b.p; bek[k] = b.e;
+                    cnlp += bern_nlp_elem(b, l, x); sent += bern_entropy_elem(b, l);
+                }
+            }
+            cnlp = group16_sum(cnlp); sent = group16_sum(sent);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                             // (compile-time k: the kept values stay in registers)
@@ -534,7 +555,7 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
             }
             ssq = group16_sum(ssq); slog = group16_sum(slog); sent = group16_sum(sent);
         }
-        const float nlp = CAT ? cnlp : gauss_nlp(ssq, slog, net.A);
+        const float nlp = (CAT || BIN) ? cnlp : gauss_nlp(ssq, slog, net.A);
         const float adv = live ? rowv[2 * r] : 0.f;
         const float old_nlp = live ? rowv[2 * r + 1] : nlp;
         const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
@@ -576,6 +597,9 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
                         dmu = d_nlp * (p - (j == cact ? 1.0f : 0.0f)) + net.ent_coef * gg * (p * ((a0 - clz) + sent));
                     }
                     dmu_t[r * ldm + j] = dmu;                                                // (no d logstd: the shared acts / dls tile keeps the mask rows)
+                } else if constexpr (BIN) {
+                    if (j < net.A && live) dmu = bern_grad_elem(d_nlp, BernParts{bek[k], 0.f, 0.f, bpk[k]}, zk[k], sk[k], net.ent_coef, gg);
+                    dmu_t[r * ldm + j] = dmu;                                                // (no d logstd: the shared acts / dls tile keeps the action bits)
                 } else {
                     if (j < net.A && live) {
                         const float z = zk[k], sigma = sk[k];
@@ -678,7 +702,7 @@ __device__ __forceinline__ void nw_train_body(const NetDev& net, const NwLayout&
     if (vec < L) { if (lane < S::Hp(net, vec)) pst(out + (net.b_off[tower][vec] + lane), colsum(lay.dy[vec], lay.ldy[vec], lane)); }
     if (tower == 0) {
         if (vec == L) { if (lane < Ap) pst(out + (net.bmu_off + lane), colsum(lay.dmu, lay.ldm, lane)); }
-        if (vec == L + 1) { if (lane < Ap) pst(out + (net.ls_off + lane), CAT ? 0.f : colsum(lay.dls, Ap, lane)); }       // (CAT: the padded logstd slot has no gradient)
+        if (vec == L + 1) { if (lane < Ap) pst(out + (net.ls_off + lane), (CAT || BIN) ? 0.f : colsum(lay.dls, Ap, lane)); }       // (CAT, BIN: the padded logstd slot has no gradient)
         if (vec == L + 2 && lane < 4) {                               // pg, entropy, kl, clipfrac sums
             const float s4 = colsum(lay.misc, 4, lane);
             pst(out + (net.n_theta + lane), s4);
@@ -782,6 +806,39 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_train_stop_multi_kernel(Net
     nw_stage<S, true, MASK, true>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
                 a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2, (int)threadIdx.x, a.mask);
     nw_train_body<KP0, HP, AP, LL, true, true, MASK, true>(net, lay, a, lds, tower, grp, (int)threadIdx.x, act_k);
+}
+
+// The multi-binary forms ("narrow_train_kernel<mbin>" of ppo_kernel_counts_all): OVERLOADS with a head TYPE where the templates above have their first bool and the
+// Gaussian arguments under a type of their own, as policy_step_kernel / train_fwd_bwd_kernel<.., MbinHead> are -- every other instantiation keeps its symbol, its
+// kernarg layout and its machine code.  Never deferred (no NwLazyArgs).  nw_stage is the Gaussian head's call: [16][Ap] action rows into the `acts` tile; the loss block
+// is nw_train_body<.., BIN>.
+using NwTrainArgsB = BinArgs<NwTrainArgs>;
+template <int KP0, int HP, int AP, int LL, class HEAD>
+__global__ __launch_bounds__(NW_THREADS) void narrow_train_kernel(NetDev net, NwLayout lay, NwTrainArgsB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwTrainArgsB)>();
+    const int tower = blockIdx.y, grp = blockIdx.x;
+    const int row0 = grp * NW_ROWS;
+    NSTAMP(0);
+    nw_stage<S>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
+                a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2);
+    nw_train_body<KP0, HP, AP, LL, true, false, false, false, true>(net, lay, a, lds, tower, grp);
+}
+template <int KP0, int HP, int AP, int LL, class HEAD>
+__global__ __launch_bounds__(NW_THREADS) void narrow_train_stop_kernel(NetDev net, NwLayout lay, NwTrainArgsB a, const unsigned* stop) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(NwTrainArgsB) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    const int tower = blockIdx.y, grp = blockIdx.x;
+    const int row0 = grp * NW_ROWS;
+    NSTAMP(0);
+    nw_stage<S>(net, lay, a.img + (size_t)tower * lay.w_total, lay.w_total, lds, a.obs, row0, a.n, ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}, nullptr, tower,
+                a.actions, tower == 0 ? a.advs : a.returns, tower == 0 ? a.old_neglogp : a.old_values, tower == 0 ? 1 : 2);
+    nw_train_body<KP0, HP, AP, LL, true, false, false, false, true>(net, lay, a, lds, tower, grp);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1319,6 +1376,84 @@ __global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwL
         if (a.action) a.action[(size_t)row * a.comp.K + part] = my_a;
         if (a.det_action) a.det_action[(size_t)row * a.comp.K + part] = my_d;
     }
+    if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = nlp;
+}
+
+// The multi-binary head ("narrow_step_kernel<mbin>" of ppo_kernel_counts_all; bern_* of ppo_head.hpp): an OVERLOAD with a head TYPE and the Gaussian arguments under a
+// type of their own (StepArgsB), selected the way policy_step_kernel<.., MbinHead> is.  Staging, forward, value tower and head product are narrow_step_kernel's,
+// written out for the reason given above.  Elementwise in the Gaussian branch's lane geometry: lane `part` owns columns part + 16 k, requests their uniforms (`noise`
+// or ctr_uniform under the categorical head's keys: the same seed draws what policy_step_kernel<mbin> draws) BEFORE the head product and keeps them in registers;
+// behind the product's barrier x = u < sigmoid(l), det = l > 0 and ONE group16_sum for the row's neglogp.  Padding columns are never read as logits and never stored;
+// nothing is indexed with a drawn bit.
+template <int KP0, int HP, int AP, int LL, class HEAD>
+__global__ __launch_bounds__(NW_THREADS) void narrow_step_kernel(NetDev net, NwLayout lay, StepArgsB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    typedef NwShape<KP0, HP, AP, LL> S;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(NwLayout) + sizeof(StepArgsB)>();
+    const int tower = blockIdx.y;
+    if (tower == 1 && !a.value) return;
+    if (tower == 0 && !a.action && !a.det_action && !a.neglogp && !a.obs_out) return;
+    const int tid = threadIdx.x, pipe = tid >> 8, ptid = tid & 255;
+    const int row0 = blockIdx.x * NW_ROWS;
+    const int L = S::L(net), Kp0 = S::Kp0(net), Ap = S::Ap(net);
+    nw_stage<S>(net, lay, a.theta + (size_t)tower * lay.w_total, lay.w_fwd, lds, a.obs, row0, a.n, a.nz, a.obs_out, tower, nullptr, nullptr, nullptr, 0);
+    __syncthreads();
+    float* P = lds + lay.w_total + pipe * lay.pipe_total;
+    const float* par = lds + lay.par;
+    for (int l = 0; l < L; ++l) {
+        const float* bias = par + net.par_b[l];
+        float* Ys = P + lay.x[l + 1]; const int ldy = lay.ldx[l + 1];
+        auto ep = [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+            const float b = bias[col];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Ys[(4 * g + r) * ldy + col] = fast_tanh(acc[r] + b);
+        };
+        if (l == 0) nw_dense<KP0>(P + lay.x[0], lay.ldx[0], Kp0, lds + lay.wf[0], lay.wf_ld[0], S::Hp(net, 0), ep);
+        else nw_dense<HP>(P + lay.x[l], lay.ldx[l], S::Hp(net, l - 1), lds + lay.wf[l], lay.wf_ld[l], S::Hp(net, l), ep);
+        __syncthreads();
+    }
+    const float* hL = P + lay.x[L]; const int ldh = lay.ldx[L]; const int HpL = S::Hp(net, L - 1);
+    const int r = ptid >> 4, part = ptid & 15;
+    const int row = row0 + 16 * pipe + r;
+    if (tower == 1) {
+        const float* wv = par + net.par_wv;
+        float s = 0.f;
+        for (int k = part; k < HpL; k += 16) s = fmaf(hL[r * ldh + k], wv[k], s);
+        s = group16_sum(s);
+        if (part == 0 && row < a.n) a.value[row] = s + par[net.par_bv];
+        return;
+    }
+    float* mus = P + lay.mu; const int ldm = lay.ldm;
+    float uk[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = part + 16 * k;
+        uk[k] = 0.5f;
+        if (j < net.A && row < a.n) uk[k] = a.noise ? a.noise[(size_t)row * net.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+    }
+    nw_dense<HP>(hL, ldh, HpL, lds + lay.wh, lay.wh_ld, Ap, [&](const f32x4& acc, int g, int col) __attribute__((always_inline)) {
+        const float b = par[net.par_bmu + col];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mus[(4 * g + q) * ldm + col] = acc[q] + b;
+    });
+    __syncthreads();
+    float nlp = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = part + 16 * k;
+        if (j < net.A) {
+            const float l = mus[r * ldm + j];
+            const BernParts b = bern_parts(l);
+            const float x = bern_sample(b.p, uk[k]);
+            nlp += bern_nlp_elem(b, l, x);
+            if (row < a.n) {
+                if (a.action) a.action[(size_t)row * net.A + j] = x;
+                if (a.det_action) a.det_action[(size_t)row * net.A + j] = bern_mode(l);
+            }
+        }
+    }
+    nlp = group16_sum(nlp);
     if (part == 0 && row < a.n && a.neglogp) a.neglogp[row] = nlp;
 }
 

@@ -69,7 +69,8 @@ public:
     // shape qualifies (include/ppo_hip.h); a continuous Env is not affected.
     // An Env with the IMultiDiscrete mixin: the bare PPO_ACT_MULTI_CATEGORICAL -- a value for ppo_create_multi[_ex], which ppo_create_ex refuses and which takes its
     // flags as an argument of their own; create_handle below makes the right call (and passes PPO_ACT_SHAPE_KERNELS there).
-    // An Env with the IMultiBinary mixin: PPO_ACT_MULTI_BINARY (the head has the generic fp32 kernels only: the flag is not added, and the library ignores it).
+    // An Env with the IMultiBinary mixin: PPO_ACT_MULTI_BINARY (PPO_ACT_SHAPE_KERNELS is not added, and the library ignores it on this head; its narrow kernels are
+    // asked for with a flag of their own through create_handle's extra_flags).
     static int32_t action_dist_for(Env& env, bool discrete_shape_kernels = false) {
         if (env.get_action_space() != Env::SPACE_DISCRETE) return PPO_ACT_GAUSSIAN;
         if (binary_actions_of(&env)) return PPO_ACT_MULTI_BINARY;
@@ -79,7 +80,9 @@ public:
     // The handle that will serve `env`: ppo_create_multi_ex with the Env's components for an IMultiDiscrete Env (cfg.act_dim must be their sum; flags:
     // PPO_ACT_SHAPE_KERNELS with discrete_shape_kernels -- the narrow kernels where the shape qualifies -- | extra_flags, e.g. PPO_ACT_PAIR_KERNELS: the
     // [256,256] train kernel pair where that shape qualifies), otherwise
-    // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  Returns the library's status; ppo_last_error(nullptr) has the message.
+    // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  For an IMultiBinary Env, create_handle(cfg, env, &h, false,
+    // PPO_ACT_BINARY_SHAPE_KERNELS) creates the multi-binary handle on the narrow <mbin> kernels where the shape qualifies (with any other Env the library refuses
+    // that flag).  Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);
         if (nvec.empty()) return ppo_create_ex(&cfg, action_dist_for(env, discrete_shape_kernels) | extra_flags, out);

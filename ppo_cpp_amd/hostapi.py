@@ -17,10 +17,11 @@ class HostArgs(C.Structure):
 
 
 def _discrete_kernels(name):
-    """ppo_host_args::discrete_kernels: 0 = the generic categorical kernels, 1 = PPO_ACT_SHAPE_KERNELS, 2 = PPO_ACT_PAIR_KERNELS"""
-    if name not in ("generic", "narrow", "pair"):
-        raise ValueError("discrete_kernels must be 'generic', 'narrow' or 'pair', not %r" % (name,))
-    return {"generic": 0, "narrow": 1, "pair": 2}[name]
+    """ppo_host_args::discrete_kernels: 0 = the generic categorical kernels, 1 = PPO_ACT_SHAPE_KERNELS, 2 = PPO_ACT_PAIR_KERNELS, 3 = PPO_ACT_BINARY_SHAPE_KERNELS (a
+    multi-binary Env's handle: ppo_host_learn_binary, ppo_host_binary_checkpoint_ex; every other entry treats it as 0)"""
+    if name not in ("generic", "narrow", "pair", "binary_narrow"):
+        raise ValueError("discrete_kernels must be 'generic', 'narrow', 'pair' or 'binary_narrow', not %r" % (name,))
+    return {"generic": 0, "narrow": 1, "pair": 2, "binary_narrow": 3}[name]
 
 
 class HostResult(C.Structure):
@@ -128,7 +129,9 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     the call returns): with discrete_kernels="narrow" and at most 64 environments the rollout is served by the resident kernel's discrete forms
     (narrow_rollout_kernel<cat|mcat[,mask]>, one launch per rollout); nothing changes anywhere else.
     binary=True: MultiBinaryTargetEnv (act_dim bits, the IMultiBinary mixin) and a multi-binary handle (PPO2::create_handle -> ppo_create_ex with
-    PPO_ACT_MULTI_BINARY), through ppo_host_learn_binary; discrete_kernels asks for the flags of a discrete Env's handle, which this head accepts and ignores.  The head
+    PPO_ACT_MULTI_BINARY), through ppo_host_learn_binary; discrete_kernels="binary_narrow" creates it with PPO_ACT_BINARY_SHAPE_KERNELS (narrow_step_kernel<mbin> /
+    narrow_train_kernel<mbin> where the shape qualifies), the other words ask for the flags of a discrete Env's handle, which this head accepts and ignores;
+    "kernel_counts" is then ppo_kernel_counts_all's.  The head
     has no fused host step, no resident rollout, no masks and no bf16 path: host_step_fused, rollout_resident, masked, nvec, discrete and target_kl are refused with it.
     target_kl (default 0 = off): PPO2::set_target_kl, target-KL early stopping (include/ppo_hip.h, ppo_set_target_kl); "applied" [n_updates, 2] then holds the Adam
     steps applied / train steps of every update (ppo_host_explicit::target_kl / applied_out; not through the nvec form)."""
@@ -342,16 +345,18 @@ def discrete_checkpoint(prefix, obs):
     return rc, acts[0], acts[1]
 
 
-def binary_checkpoint(prefix, obs):
+def binary_checkpoint(prefix, obs, discrete_kernels="generic"):
     """PPO2::save of a multi-binary policy of 6 bits, PPO2::load into a fresh multi-binary handle, into a categorical one of the same width, and of a categorical
-    policy's checkpoint (written under prefix + ".cat") into the multi-binary handle (ppo_host_binary_checkpoint): returns (status, deterministic actions before
-    [n, 6], after); status 0 = identical tensors and both foreign loads refused"""
+    policy's checkpoint (written under prefix + ".cat") into the multi-binary handle (ppo_host_binary_checkpoint_ex): returns (status, deterministic actions before
+    [n, 6], after); status 0 = identical tensors and both foreign loads refused.  discrete_kernels="binary_narrow": both multi-binary handles are created with
+    PPO_ACT_BINARY_SHAPE_KERNELS."""
     import numpy as np
     lib = load_host_library()
     obs = np.ascontiguousarray(obs, np.float32)
     n = obs.shape[0]
     acts = np.zeros((2, n, 6), np.float32)
-    rc = lib.ppo_host_binary_checkpoint(prefix.encode(), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)))
+    rc = lib.ppo_host_binary_checkpoint_ex(prefix.encode(), obs.ctypes.data_as(C.POINTER(C.c_float)), n, acts.ctypes.data_as(C.POINTER(C.c_float)),
+                                           _discrete_kernels(discrete_kernels))
     return rc, acts[0], acts[1]
 
 
