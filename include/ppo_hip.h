@@ -219,7 +219,7 @@ int ppo_action_width(const ppo_handle* h);
  *     literal relu / abs expression) differentiates the kinks to 0 and gives another value there.
  *   Surrogate, value loss, approxkl and clipfrac see the row's neglogp unchanged.  float32 against float64 at 4096 x 18 logits: neglogp within 3.0e-6 abs at a spread
  *   of +-1.5, 9e-7 at +-40, 5e-7 at +-120; entropy within 3.0e-6 / 5e-7 / 2e-7; nothing overflows.
- *   Without PPO_ACT_BINARY_SHAPE_KERNELS (below) the handle runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts,
+ *   Without PPO_ACT_BINARY_SHAPE_KERNELS or PPO_ACT_BINARY_PAIR_KERNELS (below) the handle runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts,
  *   instead of the plain names) on any hidden widths: never narrow, never train8_kernel, deferred Adam, the resident epoch kernel or a one-launch rollout -- the rules
  *   of an unflagged categorical handle.
  *   PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS and PPO_ACT_BF16_HEAD beside it on a PPO_F32 handle are accepted and change nothing (same bits, same counts).
@@ -230,7 +230,7 @@ int ppo_action_width(const ppo_handle* h);
  *   Measured on an MI355X (us of device time per call at 18 obs, hidden [256,256]; this head | a categorical handle of 18 categories | a
  *   multi-categorical one with nvec = (2,) x 16): policy step 16.6 | 16.5 | 29.1 at 16 rows, 17.6 | 18.6 | 29.7 at 1024; train_fwd_bwd_kernel 25.5 | 24.3 | 39.4 at 64 rows,
  *   26.6 | 26.0 | 40.4 at 2048.  The elementwise head is about 1 us SLOWER than <cat> per train launch; it has not been tuned.
- *   Out of scope for this head: the [256,256] pair, the bf16 path, the fused host step and the resident rollouts, action masks.
+ *   Out of scope for this head: the bf16 path, the fused host step and the resident rollouts, action masks.
  *   PPO_ACT_BINARY_SHAPE_KERNELS  PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_SHAPE_KERNELS lets a multi-binary PPO_F32 handle take the narrow LDS-resident family's step and
  *                        train kernels under the rule of a flagged categorical handle: at most 4 hidden layers, every padded hidden width <= 64, padded
  *                        observation and action widths <= 64, the plain LDS image within 160 KB, PPO_HIP_NO_NARROW unset.  (A flag of its own: PPO_ACT_SHAPE_KERNELS
@@ -243,9 +243,28 @@ int ppo_action_width(const ppo_handle* h);
  *                        0 / 1 action checks stay.  A shape that does not qualify runs the generic <mbin> kernels, as without the flag (same bits, same counts, data
  *                        parallel included).  Where the flag took effect ppo_dist_init refuses ("... data parallel is not supported for a multi-binary handle
  *                        created with PPO_ACT_BINARY_SHAPE_KERNELS") and leaves the handle usable.  With any other distribution the bit is an "unknown
- *                        action_dist" error, whose text names it; ppo_create_multi_ex refuses it with its own "unknown flag bit 0x2000". */
+ *                        action_dist" error, whose text names it; ppo_create_multi_ex refuses it with its own "unknown flag bit 0x2000".
+ *   PPO_ACT_BINARY_PAIR_KERNELS  PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_PAIR_KERNELS lets a multi-binary PPO_F32 handle take the [256,256] train kernel pair under the
+ *                        rule of a categorical handle created with PPO_ACT_PAIR_KERNELS: exactly two hidden layers of 256, padded observation and action widths
+ *                        <= 64 (at most 64 observations and 64 bits).  (A flag of its own: PPO_ACT_PAIR_KERNELS on this head is accepted and changes nothing, and
+ *                        stays so.)  A train step is train8_kernel<mbin> + weight_grad_assemble_kernel + adam_kernel: the Gaussian form's prologue, towers and
+ *                        backward, the head block elementwise in the Gaussian form's lane geometry with exp / log1p formed once per element; d logits go where
+ *                        d mu goes, the aux words are zeros and the padded logstd region of theta, Adam and the gradient is never touched.  The act side stays
+ *                        policy_step_kernel<mbin>: step and deterministic actions give the bits of the unflagged handle.  Counted under "train8_kernel<mbin>"
+ *                        INSTEAD of "train_fwd_bwd_kernel<mbin>" (the form launched under ppo_set_target_kl counts under the same name) -- a name of
+ *                        ppo_kernel_count / ppo_kernel_variant_name only -- and "weight_grad_assemble_kernel" as on every pair handle.  PPO_HIP_NO_T8 /
+ *                        PPO_HIP_NO_DW2 act as on a flagged categorical handle: one set, half the pair runs; both set, the flag did not take effect.  Masks and
+ *                        PPO_BF16 stay refused, the 0 / 1 action checks stay.  A shape that does not qualify runs the generic <mbin> kernels, as without the flag
+ *                        (same bits, same counts, data parallel included); beside PPO_ACT_BINARY_SHAPE_KERNELS each flag takes effect on its own shape.  Where the
+ *                        flag took effect ppo_dist_init refuses ("ppo_dist_init: data parallel is not supported for a multi-binary handle created with
+ *                        PPO_ACT_BINARY_PAIR_KERNELS (create it without the flag)") and leaves the handle usable.  With any other distribution the bit is an
+ *                        "unknown action_dist" error, whose text names it; ppo_create_multi_ex refuses it with its own "unknown flag bit 0x4000".
+ *                        Measured on an MI355X at (18 obs, 18 bits, [256,256]) against the unflagged handle of the same run (us of device
+ *                        time per call): train step 40.3 against 49.5 at 64 rows, 49.6 against 57.2 at 2048; the policy step runs the same kernel (16.8 | 16.5 at
+ *                        16 rows, 18.0 | 17.8 at 1024). */
 #define PPO_ACT_MULTI_BINARY 3
 #define PPO_ACT_BINARY_SHAPE_KERNELS 0x2000
+#define PPO_ACT_BINARY_PAIR_KERNELS 0x4000
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);
@@ -543,6 +562,7 @@ int ppo_dist_unique_id(char uid[128]);
  *  one on which PPO_ACT_PAIR_KERNELS took effect likewise: "... data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a multi-categorical one on which PPO_ACT_PAIR_KERNELS took effect: "... data parallel is not supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS";
  *  a multi-binary one on which PPO_ACT_BINARY_SHAPE_KERNELS took effect: "... data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS";
+ *  a multi-binary one on which PPO_ACT_BINARY_PAIR_KERNELS took effect: "... data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_PAIR_KERNELS";
  *  a categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD) likewise: "... data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD";
  *  a multi-categorical PPO_BF16 handle (PPO_ACT_BF16_MULTI_HEAD): "... data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD") */
 int ppo_dist_init(ppo_handle* h, int32_t world_size, int32_t rank, const char uid[128]);
@@ -599,9 +619,15 @@ int ppo_sync(ppo_handle* h);
  * test can ask which ones were ENQUEUED since ppo_create (a hipGraph capture counts once, its replays do not).  names: e.g.
  * "train8_kernel", "train8_kernel<cat>", "train8_kernel<mcat>", "weight_grad_assemble_kernel", "narrow_train_kernel<static>", "narrow_train_kernel<cat>", "narrow_epoch_kernel", "narrow_rollout1_kernel"; returns the count of entries.
  * ppo_kernel_counts is FROZEN at its 60 rows: callers hold its row count fixed.  Variants added later ("narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>") appear
- * only in ppo_kernel_counts_all, which reports every row: the 60 in the same order, then the later ones.  Buffers of 64 entries hold either. */
+ * only in ppo_kernel_counts_all: the 60 in the same order, then those two.  Buffers of 64 entries hold either.
+ * ppo_kernel_counts_all is FROZEN in turn, at its 62 rows: a caller holds that row count fixed too, so no fixed-length list can take a new variant.  Variants added
+ * after it ("train8_kernel<mbin>") are reached BY NAME: ppo_kernel_count returns the count of any variant of this build, the 62 included, or -1 where no variant has
+ * that name; ppo_kernel_variant_name(i) enumerates the names, i = 0, 1, .. until it returns NULL.  That list GROWS between versions (at most 64 names of at most 31
+ * characters): walk it to the NULL, never hold its length. */
 int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued);
 int ppo_kernel_counts_all(const ppo_handle* h, int32_t max, char (*names)[32], int64_t* counts);
+int64_t     ppo_kernel_count(const ppo_handle* h, const char* name);  /* any variant by name, later ones included; -1: no variant has that name */
+const char* ppo_kernel_variant_name(int32_t i);                        /* i-th variant of this build, NULL past the last: the list GROWS between versions */
 
 /* ---- debug: a raw device buffer by name, padding included (the getters above copy the dense part of every tensor) ----------------
  * "theta" "adam_m" "adam_v" (padded), "thetaT" / "par" (the transposed and small-parameter mirrors the train kernels read), "grad" (+ its tail), "sumsq", "beta_pow", "hyper",

@@ -39,6 +39,10 @@ def load_library(build=True):
     lib.ppo_last_error.argtypes = [C.c_void_p]
     lib.ppo_destroy.argtypes = [C.c_void_p]
     lib.ppo_destroy.restype = None
+    lib.ppo_kernel_count.restype = C.c_int64
+    lib.ppo_kernel_count.argtypes = [C.c_void_p, C.c_char_p]
+    lib.ppo_kernel_variant_name.restype = C.c_char_p
+    lib.ppo_kernel_variant_name.argtypes = [C.c_int32]
     _LIB = lib
     return lib
 
@@ -61,6 +65,7 @@ ACT_BF16_HEAD = 0x200                                   # PPO_ACT_BF16_HEAD, lik
 ACT_PAIR_KERNELS = 0x400                                # PPO_ACT_PAIR_KERNELS, likewise
 ACT_BF16_MULTI_HEAD = 0x1000                            # PPO_ACT_BF16_MULTI_HEAD, a flag of ppo_create_multi_ex only
 ACT_BINARY_SHAPE_KERNELS = 0x2000                       # PPO_ACT_BINARY_SHAPE_KERNELS, a flag of ppo_create_ex beside PPO_ACT_MULTI_BINARY only
+ACT_BINARY_PAIR_KERNELS = 0x4000                        # PPO_ACT_BINARY_PAIR_KERNELS, likewise
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -104,6 +109,10 @@ class PPOHip:
     (every hidden width <= 64, at most 64 observations and bits, ...) runs narrow_step_kernel<mbin> / narrow_train_kernel<mbin> -- same arithmetic, the same draws for
     the same seed, no data parallel; set_host_step_fused / set_rollout_resident change nothing on it; any other shape runs the generic <mbin> kernels.  The two names
     are rows of kernel_counts(all_rows=True) only.  The attribute binary_shape_kernels keeps what was asked for.
+    binary_pair_kernels=True with it (PPO_ACT_BINARY_PAIR_KERNELS; default False; a ValueError with any other action_dist): a handle of hidden [256, 256] with at
+    most 64 observations and bits trains with train8_kernel<mbin> + weight_grad_assemble_kernel -- the act side stays policy_step_kernel<mbin> (same bits), no data
+    parallel; any other shape runs the generic <mbin> kernels.  "train8_kernel<mbin>" is a name of kernel_count() / kernel_variants() only.  The attribute
+    binary_pair_kernels keeps what was asked for.
 
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -114,10 +123,12 @@ class PPOHip:
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, binary_shape_kernels=False,
-                 **overrides):
+                 binary_pair_kernels=False, **overrides):
         multi = action_dist == "multi_categorical"
         if binary_shape_kernels and action_dist != "multi_binary":
             raise ValueError("binary_shape_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
+        if binary_pair_kernels and action_dist != "multi_binary":
+            raise ValueError("binary_pair_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if nvec is not None and not multi:
             raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
         if multi:
@@ -144,6 +155,7 @@ class PPOHip:
         self.bf16_head = bool(bf16_head)
         self.pair_kernels = bool(pair_kernels)
         self.binary_shape_kernels = bool(binary_shape_kernels)
+        self.binary_pair_kernels = bool(binary_pair_kernels)
         self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
@@ -155,7 +167,8 @@ class PPOHip:
                     else self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h))) != 0:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())
         elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)
-                                    | (ACT_PAIR_KERNELS if pair_kernels else 0) | (ACT_BINARY_SHAPE_KERNELS if binary_shape_kernels else 0), C.byref(h)) != 0:
+                                    | (ACT_PAIR_KERNELS if pair_kernels else 0) | (ACT_BINARY_SHAPE_KERNELS if binary_shape_kernels else 0)
+                                    | (ACT_BINARY_PAIR_KERNELS if binary_pair_kernels else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)
@@ -544,10 +557,27 @@ class PPOHip:
 
     def kernel_counts(self, all_rows=False):
         """{kernel variant: times enqueued since creation} -- which of the shape-selected kernels the calls so far took.  The default is ppo_kernel_counts' frozen
-        60 rows; all_rows=True (ppo_kernel_counts_all) adds the variants named later: narrow_step_kernel<mbin>, narrow_train_kernel<mbin>."""
+        60 rows; all_rows=True (ppo_kernel_counts_all) adds narrow_step_kernel<mbin> and narrow_train_kernel<mbin>: 62 rows, frozen as well.  Variants named
+        after those are in kernel_variants() / kernel_count(name) only."""
         names = ((C.c_char * 32) * 64)(); cnt = (C.c_int64 * 64)()
         n = (self.lib.ppo_kernel_counts_all if all_rows else self.lib.ppo_kernel_counts)(self.h, 64, names, cnt)
         return {names[i].value.decode(): cnt[i] for i in range(n)}
+
+    def kernel_count(self, name):
+        """times the kernel variant `name` was enqueued since creation (ppo_kernel_count): any variant of this build, e.g. "train8_kernel<mbin>"; -1 where no
+        variant has that name"""
+        return int(self.lib.ppo_kernel_count(self.h, name.encode()))
+
+    def kernel_variants(self):
+        """{kernel variant: times enqueued since creation} over EVERY variant of this build (ppo_kernel_variant_name / ppo_kernel_count).  This dict GROWS between
+        versions: look names up in it, never hold its length.  (kernel_counts() and kernel_counts(all_rows=True) are its first 60 / 62 entries, frozen.)"""
+        out, i = {}, 0
+        while True:
+            name = self.lib.ppo_kernel_variant_name(i)
+            if name is None:
+                return out
+            out[name.decode()] = int(self.lib.ppo_kernel_count(self.h, name))
+            i += 1
 
     def debug_buffer(self, name):
         """a raw device buffer by name, padding included, as uint32 words (include/ppo_hip.h, ppo_debug_buffer); empty when this shape does not use it"""

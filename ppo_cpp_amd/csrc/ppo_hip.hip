@@ -71,10 +71,14 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
                      KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
                      KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
-                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_COUNT };
-// ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all only
+                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_COUNT };
+// ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all,
+// which is FROZEN in turn at the first KV_ALL_COUNT rows (a caller asserts that count too).  Every variant, later ones included, is reached by name through
+// ppo_kernel_count and enumerated by ppo_kernel_variant_name: no caller may hold THAT list's length.
 constexpr int KV_LEGACY_COUNT = 60;
+constexpr int KV_ALL_COUNT = 62;
 static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
+static_assert(KV_ALL_COUNT == KV_TRAIN8_MBIN, "the rows of ppo_kernel_counts_all end where the first variant named after it begins");
 static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
 const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
@@ -109,7 +113,10 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "policy_step_kernel<mbin>", "train_fwd_bwd_kernel<mbin>",
                                        // a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS on a narrow shape (static and runtime-shape instantiations share a name, the
                                        // early-stopping form counts under the train name): counted INSTEAD of the two <mbin> names above; ppo_kernel_counts_all only
-                                       "narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>"};
+                                       "narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>",
+                                       // a multi-binary handle created with PPO_ACT_BINARY_PAIR_KERNELS on a [256,256] shape (the early-stopping form counts under the same
+                                       // name): counted INSTEAD of "train_fwd_bwd_kernel<mbin>"; ppo_kernel_count / ppo_kernel_variant_name only
+                                       "train8_kernel<mbin>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -118,14 +125,14 @@ struct Head {
 };
 // which entry a launch of a kernel family with a head bumps: a row per family, a column per head form.  (The narrow Gaussian entries say whether the compile-time
 // shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.  KV_COUNT: the family
-// has no kernel of that head, and no handle of that head reaches it -- a multi-binary handle runs the generic fp32 family or, with PPO_ACT_BINARY_SHAPE_KERNELS, the narrow
-// step / train kernels, nothing else.)
+// has no kernel of that head, and no handle of that head reaches it -- a multi-binary handle runs the generic fp32 family, with PPO_ACT_BINARY_SHAPE_KERNELS the narrow
+// step / train kernels, with PPO_ACT_BINARY_PAIR_KERNELS train8_kernel, nothing else.)
 enum HeadFamily { KF_POLICY_STEP = 0, KF_TRAIN_FB, KF_TRAIN8, KF_NARROW_STEP_STATIC, KF_NARROW_STEP, KF_NARROW_TRAIN_STATIC, KF_NARROW_TRAIN, KF_NARROW_HOST_STEP, KF_BF16_STEP,
                   KF_BF16_TRAIN, KF_NARROW_ROLLOUT, KF_COUNT };
 constexpr KernelVariant kHeadVariant[KF_COUNT][6] = {
     {KV_POLICY_STEP, KV_POLICY_STEP_CAT, KV_POLICY_STEP_CAT_MASK, KV_POLICY_STEP_MCAT, KV_POLICY_STEP_MCAT_MASK, KV_POLICY_STEP_MBIN},
     {KV_TRAIN_FB, KV_TRAIN_FB_CAT, KV_TRAIN_FB_CAT_MASK, KV_TRAIN_FB_MCAT, KV_TRAIN_FB_MCAT_MASK, KV_TRAIN_FB_MBIN},
-    {KV_TRAIN8, KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK, KV_COUNT},
+    {KV_TRAIN8, KV_TRAIN8_CAT, KV_TRAIN8_CAT_MASK, KV_TRAIN8_MCAT, KV_TRAIN8_MCAT_MASK, KV_TRAIN8_MBIN},
     {KV_NARROW_STEP_STATIC, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_STEP_MBIN},
     {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_STEP_MBIN},
     {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_NARROW_TRAIN_MBIN},
@@ -160,12 +167,13 @@ struct ppo_handle {
     int CT = 1;                       // column tiles per wave in the dense layers (4 for wide nets)
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
-    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (never t8, dw2 or bf16; narrow only with binary_shape_kernels)
+    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (never bf16; narrow only with binary_shape_kernels, t8 / dw2 only with binary_pair_kernels)
     bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
     bool binary_shape_kernels = false;   // created with PPO_ACT_BINARY_SHAPE_KERNELS as a multi-binary handle: may take the narrow family's step / train kernels (build_narrow_layout); after ppo_create_ex: it did
     bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
     bool bf16_multi_head = false;     // created with PPO_ACT_BF16_MULTI_HEAD as a multi-categorical PPO_BF16 handle (ppo_create_multi_ex): bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>
     bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical or multi-categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
+    bool binary_pair_kernels = false; // created with PPO_ACT_BINARY_PAIR_KERNELS as a multi-binary handle: may take the [256,256] pair likewise; after ppo_create_ex: it did (t8 || dw2)
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian; multi-binary: the bits), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
@@ -808,7 +816,7 @@ ObsNorm no_norm_fwd() { return ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}; }
 // ppo_create_ex asks the same pickers for every head the handle can launch (for_each_head) when it raises the dynamic-LDS limits.
 template <bool CAT, bool MASK, bool MULTI, bool BIN = false>
 struct HeadTag { static constexpr bool cat = CAT, mask = MASK, multi = MULTI, bin = BIN; };
-using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn) and the narrow step / train pickers (nw_step_fn, nw_train_fn) know it, no other
+using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn), the narrow step / train pickers (nw_step_fn, nw_train_fn) and train8_fn know it, no other
 using GaussHead = HeadTag<false, false, false>;
 
 // (a mask on a Gaussian handle: the entry points and launch_step refuse it before any launch)
@@ -1449,10 +1457,12 @@ int enqueue_adam(ppo_handle* h, float* loss_row, int n_sumsq = 0, const float* p
 
 // the [256,256] pair (PAIR_DISPATCH picks the widths).  train8_kernel / train8_stop_kernel, the picker: the Gaussian head is the two-parameter overload, the
 // categorical ones (a handle created with PPO_ACT_PAIR_KERNELS) the four-parameter one with the same carve and the same dynamic LDS, the multi-categorical ones
-// (ppo_create_multi_ex with the flag) the one that takes the component table, with the action rows' region behind the carve
+// (ppo_create_multi_ex with the flag) the one that takes the component table, with the action rows' region behind the carve, the multi-binary one (a handle
+// created with PPO_ACT_BINARY_PAIR_KERNELS) the overload with a head type on TrainArgsB, carve and dynamic LDS as the Gaussian one
 template <bool STOP, int KP0, int AP, class T>
 static auto train8_fn(T) {
-    if constexpr (T::multi) { if constexpr (STOP) return train8_stop_kernel<KP0, AP, true, T::mask, true>; else return train8_kernel<KP0, AP, true, T::mask, true>; }
+    if constexpr (T::bin) { if constexpr (STOP) return train8_stop_kernel<KP0, AP, MbinHead>; else return train8_kernel<KP0, AP, MbinHead>; }
+    else if constexpr (T::multi) { if constexpr (STOP) return train8_stop_kernel<KP0, AP, true, T::mask, true>; else return train8_kernel<KP0, AP, true, T::mask, true>; }
     else if constexpr (T::cat) { if constexpr (STOP) return train8_stop_kernel<KP0, AP, true, T::mask>; else return train8_kernel<KP0, AP, true, T::mask>; }
     else { if constexpr (STOP) return train8_stop_kernel<KP0, AP>; else return train8_kernel<KP0, AP>; }
 }
@@ -1693,7 +1703,8 @@ static int train_narrow(ppo_handle* h, const TrainArgs& ta, AdamParts& parts) {
 }
 
 // fp32 forward + loss + backward over n_pad rows (the kernels zero-fill the rows of their last partial tile): train8_kernel where the handle has it (t8: not wide;
-// a categorical or multi-categorical handle only with PPO_ACT_PAIR_KERNELS: ppo_create_ex / ppo_create_multi_ex), else train_fwd_bwd_kernel on the handle's rung
+// a categorical or multi-categorical handle only with PPO_ACT_PAIR_KERNELS, a multi-binary one only with PPO_ACT_BINARY_PAIR_KERNELS: ppo_create_ex /
+// ppo_create_multi_ex), else train_fwd_bwd_kernel on the handle's rung
 static int enqueue_train_fb(ppo_handle* h, const TrainArgs& ta, int n_pad) {
     ProfScope ps(h, PK_TRAIN_FB);
     const dim3 grid(n_pad / ROWS_PER_BLOCK, 2);
@@ -1957,11 +1968,14 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (nvec) action_dist &= ~(int32_t)PPO_ACT_BF16_MULTI_HEAD;
     action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS);
     // PPO_ACT_BINARY_SHAPE_KERNELS belongs to PPO_ACT_MULTI_BINARY alone: beside any other distribution the bit stays in and is refused below (ppo_create_multi_ex has refused it already: "unknown flag bit")
-    const bool binary_shape_kernels = !nvec && action_dist == (PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_SHAPE_KERNELS);
-    if (binary_shape_kernels) action_dist = PPO_ACT_MULTI_BINARY;
+    // PPO_ACT_BINARY_PAIR_KERNELS likewise
+    const bool binary_flags_ok = !nvec && (action_dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS)) == PPO_ACT_MULTI_BINARY;
+    const bool binary_shape_kernels = binary_flags_ok && (action_dist & PPO_ACT_BINARY_SHAPE_KERNELS) != 0;
+    const bool binary_pair_kernels = binary_flags_ok && (action_dist & PPO_ACT_BINARY_PAIR_KERNELS) != 0;
+    if (binary_flags_ok) action_dist = PPO_ACT_MULTI_BINARY;
     if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && action_dist != PPO_ACT_MULTI_BINARY && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
         return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
-                             "PPO_ACT_BINARY_SHAPE_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
+                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
         return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && !bf16_head)
@@ -1980,6 +1994,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     h->dist = action_dist;
     h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_MULTI_BINARY;   // (a Gaussian handle takes its shape's kernels anyway, a multi-binary one only under its own flag: this one changes nothing)
     h->binary_shape_kernels = binary_shape_kernels;
+    h->binary_pair_kernels = binary_pair_kernels;      // (PPO_BF16 is refused above; a shape that does not qualify: below)
     h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
     h->bf16_multi_head = bf16_multi_head && cfg->compute_dtype == PPO_BF16;   // (PPO_F32: the flag changes nothing)
     h->pair_kernels = pair_kernels && (action_dist == PPO_ACT_CATEGORICAL || action_dist == PPO_ACT_MULTI_CATEGORICAL) && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
@@ -2025,7 +2040,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (h->dist == PPO_ACT_MULTI_BINARY) h->binary_shape_kernels = h->narrow;     // likewise: a shape that does not qualify runs the generic <mbin> kernels, data parallel included
     if (h->dist == PPO_ACT_MULTI_CATEGORICAL) h->shape_kernels = h->narrow;       // from here on: the flag took effect (a shape that does not qualify runs the generic <mcat> kernels, data parallel included)
     if (upload_grad_src(h)) return bail(0);
-    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels;        // the heads train8_kernel has; a categorical or multi-categorical one only where the flag asks for it
+    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels || h->binary_pair_kernels;   // the heads train8_kernel has; a discrete one only where its flag asks for it
     { const char* e = getenv("PPO_HIP_NO_DW2"); const NetDev& nn = h->net;
       h->dw2 = !(e && e[0] == '1') && pair_head && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
     { const char* e = getenv("PPO_HIP_NO_T8"); const NetDev& nn = h->net;
@@ -2060,7 +2075,9 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
             HIP_OK(h, hipStreamSynchronize(h->stream));
         }
     }
-    if (h->dist != PPO_ACT_GAUSSIAN) h->pair_kernels = h->t8 || h->dw2;        // from here on: the flag took effect (a shape that does not qualify, both switches set: it did not)
+    // from here on: the flag took effect (a shape that does not qualify, both switches set: it did not)
+    if (h->dist == PPO_ACT_MULTI_BINARY) h->binary_pair_kernels = h->t8 || h->dw2;
+    else if (h->dist != PPO_ACT_GAUSSIAN) h->pair_kernels = h->t8 || h->dw2;
     if (h->bf.on && bf16_create(h)) return bail(0);
     if (h->narrow) {
         attr_ok = true;
@@ -4118,6 +4135,8 @@ int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD");
     if (h->binary_shape_kernels)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS (create it without the flag)");
+    if (h->binary_pair_kernels)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_PAIR_KERNELS (create it without the flag)");
     if (h->shape_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
         return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
     if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
@@ -4419,7 +4438,14 @@ static int kernel_count_rows(const ppo_handle* h, int limit, int max, char names
     return n;
 }
 int ppo_kernel_counts(ppo_handle* h, int max, char names[][32], int64_t* enqueued) { return kernel_count_rows(h, KV_LEGACY_COUNT, max, names, enqueued); }
-int ppo_kernel_counts_all(const ppo_handle* h, int32_t max, char (*names)[32], int64_t* counts) { return kernel_count_rows(h, KV_COUNT, max, names, counts); }
+int ppo_kernel_counts_all(const ppo_handle* h, int32_t max, char (*names)[32], int64_t* counts) { return kernel_count_rows(h, KV_ALL_COUNT, max, names, counts); }
+// every variant of this build, by name and by index: the list grows between versions
+int64_t ppo_kernel_count(const ppo_handle* h, const char* name) {
+    if (!h || !name) return -1;
+    for (int i = 0; i < KV_COUNT; ++i) if (strcmp(name, kVariantNames[i]) == 0) return h->kv[i];
+    return -1;
+}
+const char* ppo_kernel_variant_name(int32_t i) { return i >= 0 && i < KV_COUNT ? kVariantNames[i] : nullptr; }
 
 // Raw device buffers by name, PADDING INCLUDED (ppo_get_flat and ppo_get_last_grad copy the dense part of every tensor only): the transposed mirrors, the small-parameter
 // mirrors, the assembled gradient with its tail, the workspaces of the last train step, the gathered epoch.  For bitwise comparisons of two runs (tests/test_other_shapes.py,

@@ -153,10 +153,16 @@ __device__ __forceinline__ void t8_exchange(const f32x4 (&acc)[4], float* xch, i
 // the component's normaliser, action a0 and entropy, adds neglogp and entropy up in component order and leaves each element its own component's z, log z, H and
 // action column for the gradient.  A lane's two elements may belong to two components (or both to one that spans column 32): every select is per element.
 // One component is the <cat> form statement by statement.  No barrier beyond the <cat> form's; nothing is indexed with an action or a mask value.
-template <int KP0, int AP, bool CAT = false, bool MASK = false, bool MULTI = false>
+// BIN (without CAT): multi-binary head (a handle created with PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_PAIR_KERNELS) -- train_fwd_bwd_kernel<.., MbinHead>'s arithmetic in
+// this kernel's geometry.  `actions` holds A floats per row, each 0 or 1: the Gaussian form's prologue requests and parks them in the ACT tile unchanged, and the same
+// lane reads them back.  The logits are mu[q]; the head is elementwise in the Gaussian branch's lane geometry: bern_parts is formed ONCE per element and serves
+// neglogp, entropy and gradient; the row's neglogp and entropy are two t8_sum32 (padding columns add exactly 0).  d logits go where d mu goes; the DLS tile and the
+// slot_aux words are zeros and par_ls is not read, as in the <cat> form.  No reduction, barrier or LDS region beyond the Gaussian form's.
+template <int KP0, int AP, bool CAT = false, bool MASK = false, bool MULTI = false, bool BIN = false>
 __device__ __forceinline__ void train8_body(const NetDev& net, const std::conditional_t<MULTI, TrainArgsM, TrainArgs>& a, float* lds, const unsigned bx, const unsigned by, const unsigned gx) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
     static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
+    static_assert(!(CAT && BIN), "the multi-binary head is a head of its own");
     typedef T8L<KP0, AP> L8;
     constexpr int KS0 = KP0 / 16, KSA = AP / 16;       // k-steps of 16 in the first layer / in the head's backward product
     constexpr int CTA = AP / 16;                       // column tiles of the policy head (all AP columns in every wave)
@@ -359,6 +365,8 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
         int cact = -1;
         float zq[NA], lzq[NA], hq[NA];                                                 // MULTI: z, log z and H of the element's OWN component ...
         int actq[NA];                                                                  // ... and that component's action column
+        BernParts bp[NA];                                                              // BIN: the element's exp / softplus / probabilities, formed once ...
+        float bx[NA];                                                                  // ... and its bit
         if constexpr (MULTI) {
             const int nK = a.comp.K;
             const float* arow = lds + L8::MACT + er * PPO_MAX_COMPONENTS_DEV;
@@ -431,6 +439,17 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
             for (int q = 0; q < NA; ++q) es += ok[q] ? cat_entropy_term(ex[q], cz, clz, a0[q]) : 0.f;
             sent = t8_sum32(es);
             nlp = clz - la;
+        } else if constexpr (BIN) {
+            float sn = 0.f, se_ = 0.f;
+#pragma unroll
+            for (int q = 0; q < NA; ++q) {
+                const bool lj = ej + 32 * q < nA;
+                bp[q] = bern_parts(mu[q]);
+                bx[q] = live ? lds[L8::ACT + er * AP + ej + 32 * q] : 0.f;
+                sn += lj ? bern_nlp_elem(bp[q], mu[q], bx[q]) : 0.f; se_ += lj ? bern_entropy_elem(bp[q], mu[q]) : 0.f;
+            }
+            nlp = t8_sum32(sn);
+            sent = t8_sum32(se_);
         } else {
             float zz = 0.f, sl_ = 0.f, se_ = 0.f;
 #pragma unroll
@@ -458,6 +477,7 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
             float dl = 0.f, dmu = 0.f;
             if constexpr (MULTI) { if (ok[q] && live) dmu = cat_grad_elem(d_nlp, ex[q], zq[q], a0[q], lzq[q], hq[q], ej + 32 * q, actq[q], net.ent_coef, gi); }   // H of j's own component
             else if constexpr (CAT) { if (ok[q] && live) dmu = cat_grad_elem(d_nlp, ex[q], cz, a0[q], clz, sent, ej + 32 * q, cact, net.ent_coef, gi); }   // d l_j; forbidden / padding columns, dead rows: +0
+            else if constexpr (BIN) { if (ej + 32 * q < nA && live) dmu = bern_grad_elem(d_nlp, bp[q], mu[q], bx[q], net.ent_coef, gi); }   // d l_j; padding columns, dead rows: +0
             else if (ej + 32 * q < nA && live) gauss_grad_elem(d_nlp, z[q], sigma[q], net.ent_coef, gi, dmu, dl);
             lds[L8::MU + er * L8::LDM + ej + 32 * q] = dmu;                         // the d mu tile: A operand of the head's backward product
             lds[L8::DLS + er * AP + ej + 32 * q] = dl;
@@ -590,6 +610,15 @@ __global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArg
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsM)>();
     train8_body<KP0, AP, CAT, MASK, MULTI>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
 }
+// the multi-binary form, train8_kernel<KP0, AP, MbinHead>: an overload with a head TYPE on the Gaussian arguments under a type of their own (TrainArgsB), as
+// train_fwd_bwd_kernel / narrow_train_kernel<.., MbinHead> are -- every other instantiation keeps its symbol.  The other forms' carve and dynamic LDS (T8L::TOTAL).
+template <int KP0, int AP, class HEAD>
+__global__ __launch_bounds__(T8_THREADS) void train8_kernel(NetDev net, TrainArgsB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsB)>();
+    train8_body<KP0, AP, false, false, false, true>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}
 
 // The forms launched while target-KL early stopping is on (update_stopped, ppo_kernels.hpp): the kernels above behind the entry check.  Kernels of their own, so that
 // the ones a handle launches with the setting off stay what they were.
@@ -614,4 +643,12 @@ __global__ __launch_bounds__(T8_THREADS) void train8_stop_kernel(NetDev net, Tra
     warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsM) + sizeof(stop)>();
     if (update_stopped(stop)) return;
     train8_body<KP0, AP, CAT, MASK, MULTI>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
+}
+template <int KP0, int AP, class HEAD>
+__global__ __launch_bounds__(T8_THREADS) void train8_stop_kernel(NetDev net, TrainArgsB a, const unsigned* stop) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    warm_kernargs<sizeof(NetDev) + sizeof(TrainArgsB) + sizeof(stop)>();
+    if (update_stopped(stop)) return;
+    train8_body<KP0, AP, false, false, false, true>(net, a, lds, blockIdx.x, blockIdx.y, gridDim.x);
 }

@@ -81,8 +81,8 @@ public:
     // PPO_ACT_SHAPE_KERNELS with discrete_shape_kernels -- the narrow kernels where the shape qualifies -- | extra_flags, e.g. PPO_ACT_PAIR_KERNELS: the
     // [256,256] train kernel pair where that shape qualifies), otherwise
     // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  For an IMultiBinary Env, create_handle(cfg, env, &h, false,
-    // PPO_ACT_BINARY_SHAPE_KERNELS) creates the multi-binary handle on the narrow <mbin> kernels where the shape qualifies (with any other Env the library refuses
-    // that flag).  Returns the library's status; ppo_last_error(nullptr) has the message.
+    // PPO_ACT_BINARY_SHAPE_KERNELS) creates the multi-binary handle on the narrow <mbin> kernels where the shape qualifies, and PPO_ACT_BINARY_PAIR_KERNELS there on
+    // the [256,256] train kernel pair where that shape qualifies (with any other Env the library refuses either flag).  Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);
         if (nvec.empty()) return ppo_create_ex(&cfg, action_dist_for(env, discrete_shape_kernels) | extra_flags, out);

@@ -176,7 +176,7 @@ struct ppo_host_args {
     unsigned long long seed;     // PPO2::seed (exploration noise + epoch shuffles)
     int obs_dim, act_dim;        // SeededEnvMock's shape (0 = 18): 36 / 18 is the hexapod with observed velocities (hexapod_closed_loop_env.hpp:20)
     float cliprange_vf;          // PPO2's cliprange_vf: < 0 = clip the value with cliprange (the default, -1), >= 0 = its own range, +inf = no value clipping
-    int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for; a multi-discrete Env's: PPO2::create_handle), 2 = PPO_ACT_PAIR_KERNELS (a multi-discrete Env's: PPO2::create_handle's extra_flags), 3 = "binary narrow": PPO_ACT_BINARY_SHAPE_KERNELS as extra_flags of a multi-binary Env's handle (ppo_host_learn_binary, ppo_host_binary_checkpoint_ex; every other entry treats 3 as 0)
+    int discrete_kernels;        // a discrete Env's handle: 0 = the generic categorical kernels (the default), 1 = PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for; a multi-discrete Env's: PPO2::create_handle), 2 = PPO_ACT_PAIR_KERNELS (a multi-discrete Env's: PPO2::create_handle's extra_flags), 3 = "binary narrow": PPO_ACT_BINARY_SHAPE_KERNELS as extra_flags of a multi-binary Env's handle (ppo_host_learn_binary, ppo_host_binary_checkpoint_ex; every other entry treats 3 as 0), 4 = "binary pair": PPO_ACT_BINARY_PAIR_KERNELS as extra_flags of the same two entries' handles (every other entry treats 4 as 0)
     int compute_dtype;           // ppo_config::compute_dtype (0 = PPO_F32, the default; 1 = PPO_BF16: a discrete Env's handle is then created with PPO_ACT_BF16_HEAD, a multi-discrete Env's with PPO_ACT_BF16_MULTI_HEAD)
     int n_components, nvec[16];  // ppo_host_learn_multi: the components of MultiDiscreteTargetEnv (act_dim is their sum)
     int multi_masked;            // ppo_host_learn_multi: the environments also carry IActionMask
@@ -541,8 +541,9 @@ int ppo_host_multi_checkpoint(const char* prefix, const int* nvec_in, const int*
 // The learning check of the multi-binary head (tests/test_multi_binary.py): n_envs x MultiBinaryTargetEnv(act_dim bits) -> VecEnv -> EnvNormalize -> PPO2::learn with the
 // library's own sampling and shuffles, through the HBM-resident loop or, with args->reference_loop, the literal one.  The handle comes from PPO2::create_handle (the Env
 // carries IMultiBinary: ppo_create_ex with PPO_ACT_MULTI_BINARY; args->discrete_kernels == 3 adds PPO_ACT_BINARY_SHAPE_KERNELS -- the narrow <mbin> kernels where
-// the shape qualifies -- 1 and 2 ask for the flags of a discrete Env's handle, which this head accepts and ignores).  The head has neither a fused host step nor a resident rollout: args->host_step_fused and the process-wide resident default are not applied.
-// reward_curve [n_updates], losses_out [n_updates][5] (may be null); count_names / counts / n_counts (all three or none): ppo_kernel_counts_all of the run's handle, up to 64 entries.
+// the shape qualifies -- 4 adds PPO_ACT_BINARY_PAIR_KERNELS -- the [256,256] train kernel pair where that shape qualifies -- 1 and 2 ask for the flags of a discrete Env's handle, which this head accepts and ignores).  The head has neither a fused host step nor a resident rollout: args->host_step_fused and the process-wide resident default are not applied.
+// reward_curve [n_updates], losses_out [n_updates][5] (may be null); count_names / counts / n_counts (all three or none): every kernel variant of the
+// run's handle (ppo_kernel_variant_name / ppo_kernel_count: the list grows between versions), up to 64 entries.
 int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* losses_out, char (*count_names)[32], long long* counts, int* n_counts, ppo_host_result* out) {
     std::memset(out, 0, sizeof *out);
     ppo_handle* h = nullptr;
@@ -554,7 +555,7 @@ int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* lo
         cfg.compute_dtype = a->compute_dtype;
         std::vector<std::shared_ptr<Env>> envs;
         for (int i = 0; i < a->n_envs; ++i) envs.push_back(std::make_shared<MultiBinaryTargetEnv>(1234u, (uint32_t)i, O, A));
-        const int32_t extra_flags = a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : a->discrete_kernels == 3 ? PPO_ACT_BINARY_SHAPE_KERNELS : 0;
+        const int32_t extra_flags = a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : a->discrete_kernels == 3 ? PPO_ACT_BINARY_SHAPE_KERNELS : a->discrete_kernels == 4 ? PPO_ACT_BINARY_PAIR_KERNELS : 0;
         if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, extra_flags) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_action_dist(h) != PPO_ACT_MULTI_BINARY) throw std::runtime_error("PPO2::create_handle did not create a multi-binary handle for an IMultiBinary Env");
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
@@ -590,9 +591,11 @@ int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* lo
             if (reward_curve) for (size_t i = 0; i < hist.size(); ++i) reward_curve[i] = hist[i].mean_reward;
             if (losses_out) for (size_t i = 0; i < hist.size(); ++i) std::memcpy(losses_out + 5 * i, hist[i].losses, sizeof(float) * 5);
             if (count_names && counts && n_counts) {
-                int64_t c64[64];
-                const int nc = ppo_kernel_counts_all(h, 64, count_names, c64);
-                for (int i = 0; i < nc; ++i) counts[i] = (long long)c64[i];
+                int nc = 0;
+                for (const char* nm; nc < 64 && (nm = ppo_kernel_variant_name(nc)) != nullptr; ++nc) {
+                    std::snprintf(count_names[nc], 32, "%s", nm);
+                    counts[nc] = (long long)ppo_kernel_count(h, nm);
+                }
                 *n_counts = nc;
             }
         }
@@ -610,19 +613,21 @@ int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* lo
 // into a categorical handle of the same width must fail, and so must loading a categorical policy's checkpoint (written under <prefix>.cat) into the multi-binary
 // handle.  Returns 0; 1 = tensors differ, 2 = the categorical handle's load went through, 3 = the multi-binary handle's load of the categorical checkpoint; -1 = error
 // (message on stderr).  discrete_kernels == 3 (ppo_host_args::discrete_kernels' "binary narrow"): both multi-binary handles are created with
-// PPO_ACT_BINARY_SHAPE_KERNELS; any other value: without.
+// PPO_ACT_BINARY_SHAPE_KERNELS; 4 ("binary pair"): with PPO_ACT_BINARY_PAIR_KERNELS, and every handle has hidden [256,256], the shape on which that flag takes
+// effect; any other value: without.
 int ppo_host_binary_checkpoint_ex(const char* prefix, const float* obs, int n, float* actions_out, int discrete_kernels) {
     ppo_handle* h[3] = {nullptr, nullptr, nullptr};
     int rc = 0;
     try {
         const int A = 6;
-        ppo_config cfg; const int32_t hidden[2] = {64, 64};
+        ppo_config cfg; const int32_t width = discrete_kernels == 4 ? 256 : 64, hidden[2] = {width, width};
         ppo_config_default(&cfg, 18, A, 2, hidden);
+        const int32_t binary_flags = discrete_kernels == 3 ? PPO_ACT_BINARY_SHAPE_KERNELS : discrete_kernels == 4 ? PPO_ACT_BINARY_PAIR_KERNELS : 0;
         MultiBinaryTargetEnv probe(1234u, 0, 18, A);
         DiscreteTargetEnv probe_cat(1234u, 0, 18, A);
         Env* probes[3] = {&probe, &probe, &probe_cat};
         for (int k = 0; k < 3; ++k)
-            if (PPO2::create_handle(cfg, *probes[k], &h[k], false, k < 2 && discrete_kernels == 3 ? PPO_ACT_BINARY_SHAPE_KERNELS : 0) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0) throw std::runtime_error(ppo_last_error(h[k]));
+            if (PPO2::create_handle(cfg, *probes[k], &h[k], false, k < 2 ? binary_flags : 0) != 0 || ppo_init_orthogonal(h[k], (uint64_t)k) != 0) throw std::runtime_error(ppo_last_error(h[k]));
         std::vector<std::shared_ptr<Env>> envs;
         for (uint32_t i = 0; i < 4; ++i) envs.push_back(std::make_shared<MultiBinaryTargetEnv>(1234u, i, 18, A));
         {

@@ -17,11 +17,11 @@ class HostArgs(C.Structure):
 
 
 def _discrete_kernels(name):
-    """ppo_host_args::discrete_kernels: 0 = the generic categorical kernels, 1 = PPO_ACT_SHAPE_KERNELS, 2 = PPO_ACT_PAIR_KERNELS, 3 = PPO_ACT_BINARY_SHAPE_KERNELS (a
-    multi-binary Env's handle: ppo_host_learn_binary, ppo_host_binary_checkpoint_ex; every other entry treats it as 0)"""
-    if name not in ("generic", "narrow", "pair", "binary_narrow"):
-        raise ValueError("discrete_kernels must be 'generic', 'narrow', 'pair' or 'binary_narrow', not %r" % (name,))
-    return {"generic": 0, "narrow": 1, "pair": 2, "binary_narrow": 3}[name]
+    """ppo_host_args::discrete_kernels: 0 = the generic categorical kernels, 1 = PPO_ACT_SHAPE_KERNELS, 2 = PPO_ACT_PAIR_KERNELS, 3 = PPO_ACT_BINARY_SHAPE_KERNELS,
+    4 = PPO_ACT_BINARY_PAIR_KERNELS (3 and 4: a multi-binary Env's handle: ppo_host_learn_binary, ppo_host_binary_checkpoint_ex; every other entry treats them as 0)"""
+    if name not in ("generic", "narrow", "pair", "binary_narrow", "binary_pair"):
+        raise ValueError("discrete_kernels must be 'generic', 'narrow', 'pair', 'binary_narrow' or 'binary_pair', not %r" % (name,))
+    return {"generic": 0, "narrow": 1, "pair": 2, "binary_narrow": 3, "binary_pair": 4}[name]
 
 
 class HostResult(C.Structure):
@@ -130,8 +130,9 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     (narrow_rollout_kernel<cat|mcat[,mask]>, one launch per rollout); nothing changes anywhere else.
     binary=True: MultiBinaryTargetEnv (act_dim bits, the IMultiBinary mixin) and a multi-binary handle (PPO2::create_handle -> ppo_create_ex with
     PPO_ACT_MULTI_BINARY), through ppo_host_learn_binary; discrete_kernels="binary_narrow" creates it with PPO_ACT_BINARY_SHAPE_KERNELS (narrow_step_kernel<mbin> /
-    narrow_train_kernel<mbin> where the shape qualifies), the other words ask for the flags of a discrete Env's handle, which this head accepts and ignores;
-    "kernel_counts" is then ppo_kernel_counts_all's.  The head
+    narrow_train_kernel<mbin> where the shape qualifies), "binary_pair" with PPO_ACT_BINARY_PAIR_KERNELS (train8_kernel<mbin> + weight_grad_assemble_kernel at hidden
+    [256, 256]), the other words ask for the flags of a discrete Env's handle, which this head accepts and ignores; "kernel_counts" then holds every variant of the
+    build (ppo_kernel_variant_name / ppo_kernel_count: a dict that grows between versions).  The head
     has no fused host step, no resident rollout, no masks and no bf16 path: host_step_fused, rollout_resident, masked, nvec, discrete and target_kl are refused with it.
     target_kl (default 0 = off): PPO2::set_target_kl, target-KL early stopping (include/ppo_hip.h, ppo_set_target_kl); "applied" [n_updates, 2] then holds the Adam
     steps applied / train steps of every update (ppo_host_explicit::target_kl / applied_out; not through the nvec form)."""
@@ -349,7 +350,7 @@ def binary_checkpoint(prefix, obs, discrete_kernels="generic"):
     """PPO2::save of a multi-binary policy of 6 bits, PPO2::load into a fresh multi-binary handle, into a categorical one of the same width, and of a categorical
     policy's checkpoint (written under prefix + ".cat") into the multi-binary handle (ppo_host_binary_checkpoint_ex): returns (status, deterministic actions before
     [n, 6], after); status 0 = identical tensors and both foreign loads refused.  discrete_kernels="binary_narrow": both multi-binary handles are created with
-    PPO_ACT_BINARY_SHAPE_KERNELS."""
+    PPO_ACT_BINARY_SHAPE_KERNELS; "binary_pair": with PPO_ACT_BINARY_PAIR_KERNELS, every handle at hidden [256, 256]."""
     import numpy as np
     lib = load_host_library()
     obs = np.ascontiguousarray(obs, np.float32)

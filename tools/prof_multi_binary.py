@@ -3,7 +3,9 @@ step at 16 / 1024 rows and of the train step at 64 / 2048 rows, at (18 obs, 18 l
 Handles, all without flags (policy_step_kernel / train_fwd_bwd_kernel<mbin | cat | mcat>): "multi_binary" (18 bits), "categorical" (18 categories) and
 "multi_categorical" with nvec = (2,) * 16 (32 logits: 16 on / off decisions the way a multi-categorical handle states them); and "multi_binary_narrow", the
 multi-binary handle created with binary_shape_kernels=True (PPO_ACT_BINARY_SHAPE_KERNELS): narrow_step_kernel / narrow_train_kernel<mbin> at [64,64], the generic
-<mbin> kernels again at [256,256], where the flag does not take effect (the "kernels" line says which ran).  One process; the handles alternate round by
+<mbin> kernels again at [256,256], where the flag does not take effect; and "multi_binary_pair", the multi-binary handle created with binary_pair_kernels=True
+(PPO_ACT_BINARY_PAIR_KERNELS): train8_kernel<mbin> + weight_grad_assemble_kernel at [256,256], the generic <mbin> kernels again at [64,64] (the "kernels" line,
+read from kernel_variants(), says which ran; both flagged handles keep policy_step_kernel<mbin> wherever their flag does not move the act side).  One process; the handles alternate round by
 round; every (handle, rows) pair is warmed up before the timed rounds.  Per call: the policy_step class, the train_fwd_bwd class and the whole train step (all
 classes), in microseconds, median over the rounds with the rounds' values beside it."""
 import json
@@ -18,6 +20,7 @@ O, ROUNDS, REPS = 18, 5, 50
 SHAPES = ([256, 256], [64, 64])
 STEP_ROWS, TRAIN_ROWS = (16, 1024), (64, 2048)
 HANDLES = (("multi_binary", dict(act_dim=18, action_dist="multi_binary")), ("multi_binary_narrow", dict(act_dim=18, action_dist="multi_binary", binary_shape_kernels=True)),
+           ("multi_binary_pair", dict(act_dim=18, action_dist="multi_binary", binary_pair_kernels=True)),
            ("categorical", dict(act_dim=18, action_dist="categorical")),
            ("multi_categorical", dict(act_dim=None, action_dist="multi_categorical", nvec=(2,) * 16)))
 
@@ -73,8 +76,8 @@ def main():
             print("  %-20s policy step %s | train_fwd_bwd %s | train step %s   (us, median of %d rounds x %d calls)" % (
                 name, " ".join("%d rows %.2f" % (n, np.median(r["step"][n])) for n in STEP_ROWS), " ".join("%d rows %.2f" % (n, np.median(r["train_fb"][n])) for n in TRAIN_ROWS),
                 " ".join("%d rows %.2f" % (n, np.median(r["train"][n])) for n in TRAIN_ROWS), ROUNDS, REPS))
-            print("     rounds: step %s train_fwd_bwd %s" % ({n: np.round(v, 2).tolist() for n, v in r["step"].items()}, {n: np.round(v, 2).tolist() for n, v in r["train_fb"].items()}))
-            print("     kernels:", {k: int(v) for k, v in g.kernel_counts(all_rows=True).items() if v})
+            print("     rounds: step %s train_fwd_bwd %s train step %s" % tuple({n: np.round(v, 2).tolist() for n, v in r[k].items()} for k in ("step", "train_fb", "train")))
+            print("     kernels:", {k: int(v) for k, v in g.kernel_variants().items() if v})
             g.close()
         out[",".join(map(str, hidden))] = {name: {k: {str(n): v for n, v in d.items()} for k, d in r.items()} for name, r in res.items()}
     if len(sys.argv) > 1:
