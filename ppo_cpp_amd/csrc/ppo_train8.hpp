@@ -13,8 +13,9 @@
 //   * the loss phase has one lane per (row, action) (two actions per lane when the action tile is 64 wide) instead of two serial
 //     passes over 16 lanes per row.
 // The padded widths of the observation and action tiles (KP0, AP: 32 or 64) are template parameters -- every loop is compile-time;
-// the dense widths O and A are uniform run-time values.  Weights of the thin products and the first two ring stages of the second
-// layer are requested at kernel entry behind the input loads (one workgroup of 8 waves per CU: 256 registers per wave).
+// the dense widths O and A are uniform run-time values.  The first layer's weights and the first ring stage of the second layer are
+// requested at kernel entry behind the input loads, the second stage behind the prologue's barrier (T8_PRO), the policy head's weights and their transpose behind
+// the second layer's product (T8_HEADW) (one workgroup of 8 waves per CU: 256 registers per wave).
 #pragma once
 #include "ppo_kernels.hpp"
 
@@ -39,6 +40,13 @@ struct T8L {
 #endif
 #ifndef T8_W1T
 #define T8_W1T 0                  // where the backward product's first two W1^T stages are requested: 0 before the K-halves' exchange, 1 after it, 2 one after it + one behind the epilogue's barrier
+#endif
+#ifndef T8_HEADW
+#define T8_HEADW 2                // where the policy tower requests its head's weights (W_mu rows and W_mu^T: 8 KB per wave, first read behind the second layer): 0 in the
+                                  // prologue's burst (39.04 / 38.93 / 39.07 us per train step), 1 behind the prologue's barrier, behind the second ring stage (40.12 /
+                                  // 40.06 / 39.95: the 16 requests per wave cost the first layer what they saved the prologue, and more), 2 behind the second layer's
+                                  // product, in front of the W1^T stages (38.76 / 38.60 / 38.68: the one stretch where the memory pipe is idle; in-order return puts them
+                                  // in front of stages nobody reads for 12 k cycles).  W_mu rows at 1 and W_mu^T at 2: 41.17 / 41.34 / 40.93, not kept in the source.
 #endif
 #ifndef T8_WT
 #define T8_WT 1                   // workspace stores write-through (sc1): drain while the kernel computes instead of at its end
@@ -232,10 +240,16 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
 #if T8_PRO == 0
     load_w_stage<4, 2>(fr[1], W1 + (size_t)t8_stage_row(1, rot) * 256, off_big);
 #endif
+    // the policy head's weights and their transpose (T8_HEADW: where they are requested).  A macro, not a lambda: this kernel's time moves by 1.5 us per train step
+    // with wrappers that change no instruction's meaning (profiles/EXPERIMENTS.md), so every placement keeps the statements themselves
+#define T8_REQUEST_WHD() load_w_stage<CTA, 2>(whd, uni(a.theta + net.wmu_off) + (size_t)(32 * wave) * AP, make_woff<2>(AP, g, CTA * c))   /* rows 32w .. 32w+31 of W_mu [256][AP] */
+#define T8_REQUEST_WHT() load_w_stage<2, KSA>(whT, uni(a.thetaT + net.wmuT_off), make_woff<KSA>(256, g, 32 * wave + 2 * c))               /* W_mu^T [AP][256] */
+#if T8_HEADW == 0
     if (tower == 0) {
-        load_w_stage<CTA, 2>(whd, uni(a.theta + net.wmu_off) + (size_t)(32 * wave) * AP, make_woff<2>(AP, g, CTA * c));   // rows 32w .. 32w+31 of W_mu [256][AP]
-        load_w_stage<2, KSA>(whT, uni(a.thetaT + net.wmuT_off), make_woff<KSA>(256, g, 32 * wave + 2 * c));               // W_mu^T [AP][256]
+        T8_REQUEST_WHD();
+        T8_REQUEST_WHT();
     }
+#endif
     STAMP(21);
     // consume the inputs
     if (tid < L8::NPAR / 4) *reinterpret_cast<float4*>(par + 4 * tid) = pv;
@@ -266,6 +280,9 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
 #if T8_PRO >= 1
     load_w_stage<4, 2>(fr[1], W1 + (size_t)t8_stage_row(1, rot) * 256, off_big);       // behind the barrier: lands while the first layer runs
 #endif
+#if T8_HEADW == 1
+    if (tower == 0) { T8_REQUEST_WHD(); T8_REQUEST_WHT(); }
+#endif
     // ---- first layer: h1 = tanh(x W0 + b0), 32 columns per wave ---------------------------------------------------------------------
     {
         f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -288,6 +305,9 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
         f32x4 acc[4];
         t8_big_product(fr, W1, off_big, lds + L8::H1 + 128 * kh, c, g, rot, acc);
         STAMP(11);
+#if T8_HEADW == 2
+        if (tower == 0) { T8_REQUEST_WHD(); T8_REQUEST_WHT(); }          // in front of the W1^T stages: vector-memory operations return in order, and the head reads these first
+#endif
         // the backward product's transposed weights: two stages per wave, in flight through the head and the loss
 #if T8_W1T == 0
         load_w_stage<4, 2>(fr[0], W1T + (size_t)t8_stage_row(0, rot) * 256, off_big);
@@ -585,6 +605,8 @@ __device__ __forceinline__ void train8_body(const NetDev& net, const std::condit
         st_wt<false>(slot + net.slot_db[tid < 256 ? 1 : 0] + k, s);
     }
     STAMP(10);
+#undef T8_REQUEST_WHD
+#undef T8_REQUEST_WHT
 }
 
 template <int KP0, int AP>

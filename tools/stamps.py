@@ -5,8 +5,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
 so = os.path.join(ROOT, "gpurun_out", "libppo_hip_stamps.so")            # never over the product library (bench.py / pytest keep loading the real one)
+if os.environ.get("STAMPS_LIBRARY"): so = os.environ["STAMPS_LIBRARY"]   # a stamped library built beforehand (several placements of one switch, one after the other)
 os.environ["PPO_HIP_LIBRARY"] = so
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
+if not os.environ.get("STAMPS_LIBRARY"): subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                        "-DPPO_STAMPS", "-DPPO_STAMP_LAYER=" + os.environ.get("STAMP_LAYER", "1")] + os.environ.get("PPO_HIP_EXTRA_FLAGS", "").split() + ["-o", so, os.path.join(ROOT, "ppo_cpp_amd/csrc/ppo_hip.hip"), "-ldl"])
 import ppo_cpp_amd
 H = [int(x) for x in os.environ.get("HIDDEN", "256,256").split(",")]
