@@ -167,13 +167,13 @@ struct ppo_handle {
     int CT = 1;                       // column tiles per wave in the dense layers (4 for wide nets)
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
-    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (never bf16; narrow only with binary_shape_kernels, t8 / dw2 only with binary_pair_kernels)
-    bool shape_kernels = false;       // created with PPO_ACT_SHAPE_KERNELS: a categorical or multi-categorical handle may take the narrow family (build_narrow_layout)
-    bool binary_shape_kernels = false;   // created with PPO_ACT_BINARY_SHAPE_KERNELS as a multi-binary handle: may take the narrow family's step / train kernels (build_narrow_layout); after ppo_create_ex: it did
-    bool bf16_head = false;           // created with PPO_ACT_BF16_HEAD as a categorical PPO_BF16 handle: bf16_sample_kernel / bf16_loss_kernel<cat[,mask]>
-    bool bf16_multi_head = false;     // created with PPO_ACT_BF16_MULTI_HEAD as a multi-categorical PPO_BF16 handle (ppo_create_multi_ex): bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>
-    bool pair_kernels = false;        // created with PPO_ACT_PAIR_KERNELS as a categorical or multi-categorical PPO_F32 handle: may take the [256,256] pair (t8 / dw2 below)
-    bool binary_pair_kernels = false; // created with PPO_ACT_BINARY_PAIR_KERNELS as a multi-binary handle: may take the [256,256] pair likewise; after ppo_create_ex: it did (t8 || dw2)
+    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (never bf16; narrow only with opt_narrow, t8 / dw2 only with opt_pair)
+    // a discrete handle's family opt-ins, each under its own distribution's flag (parse_create; a Gaussian handle has none: it takes its shape's kernels anyway).  Until
+    // create_handle has decided the families: what was asked for.  From its one write-back on: what took effect -- but a categorical handle's opt_narrow keeps "asked"
+    // (ppo_dist_init refuses such a handle on a shape that did not qualify as well)
+    bool opt_narrow = false;          // PPO_ACT_SHAPE_KERNELS (categorical, multi-categorical) / PPO_ACT_BINARY_SHAPE_KERNELS (multi-binary): the narrow family (build_narrow_layout)
+    bool opt_pair = false;            // PPO_ACT_PAIR_KERNELS / PPO_ACT_BINARY_PAIR_KERNELS, PPO_F32: the [256,256] pair (t8 / dw2 below)
+    bool opt_bf16 = false;            // PPO_ACT_BF16_HEAD (categorical) / PPO_ACT_BF16_MULTI_HEAD (ppo_create_multi_ex), PPO_BF16: bf16_sample_kernel / bf16_loss_kernel<cat|mcat[,mask]>
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian; multi-binary: the bits), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
@@ -384,6 +384,7 @@ int fail(ppo_handle* h, const char* fmt, ...) {
     if (h) h->err = buf; else g_create_error = buf;
     return -1;
 }
+bool is_on(const char* v) { return v && v[0] == '1'; }      // an environment switch: set to 1
 
 #define HIP_OK(h, expr)                                                                              \
     do {                                                                                             \
@@ -616,6 +617,7 @@ int build_layout(ppo_handle* h) {
     n.slot_aux = s; s += n.Ap;
     n.slot_loss = s; s += 8;
     n.slot_w = ru(s, 4);
+    h->early = !n.wide && h->CT == 4 && h->CTH == 2 && n.L >= 2 && n.Kp0 == 32 && n.Ap == 32 && n.Hp[0] == 256 && n.Hp[n.L - 1] == 256;
     return 0;
 }
 
@@ -623,11 +625,10 @@ int build_layout(ppo_handle* h) {
 void build_narrow_layout(ppo_handle* h) {
     const NetDev& n = h->net;
     h->narrow = false;
-    const bool asked = h->dist == PPO_ACT_GAUSSIAN || (h->dist == PPO_ACT_MULTI_BINARY ? h->binary_shape_kernels : h->shape_kernels);   // (each discrete head under its own flag)
+    const bool asked = h->dist == PPO_ACT_GAUSSIAN || h->opt_narrow;   // (each discrete head under its own flag)
     if (h->bf.on || !asked || n.L > NW_MAXL || n.Kp0 > 64 || n.Ap > 64) return;
     for (int l = 0; l < n.L; ++l) if (n.Hp[l] > 64) return;
-    const char* off = getenv("PPO_HIP_NO_NARROW");
-    if (off && off[0] == '1') return;
+    if (is_on(getenv("PPO_HIP_NO_NARROW"))) return;
     NwLayout lay{};
     int o = 0;
     auto region = [&](int rows, int cols, int pad, int& dst, int& ld) { dst = o; ld = cols + pad; o += rows * (cols + pad); };
@@ -868,8 +869,7 @@ int bf16_create(ppo_handle* h) {
     lds_attr((const void*)gemm_dw_bf16_kernel<4>, GB_LDS_BYTES(4)); lds_attr((const void*)gemm_dw_bf16_kernel<2>, GB_LDS_BYTES(2));
     lds_attr((const void*)gemm_chain_bf16_kernel<GEPI_TANH>, GB_LDS_BYTES(4)); lds_attr((const void*)gemm_chain_bf16_kernel<GEPI_TANHGRAD>, GB_LDS_BYTES(4));
     if (!ok) return fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the bf16 GEMM kernels");
-    { const char* e = getenv("PPO_HIP_NO_BF16_CHAIN");
-      b.chain = !(e && e[0] == '1');
+    { b.chain = !is_on(getenv("PPO_HIP_NO_BF16_CHAIN"));
       hipDeviceProp_t prop;
       if (hipGetDeviceProperties(&prop, h->device) == hipSuccess) b.n_cu = prop.multiProcessorCount;
       for (int d = 0; d < 2 && b.chain; ++d) if (dev_alloc(h, &b.chain_words[d], (size_t)GB_CHAIN_SHAPES * GB_CHAIN_WORDS + 32)) return -1; }
@@ -1506,6 +1506,42 @@ static bool set_lds_pair(const ppo_handle* h) {
     for_each_head(h, heads);
     return ok;
 }
+// the generic ladder likewise.  Large dynamic LDS needs an explicit opt-in.  The attribute is per function, not per handle: it is set to the hardware maximum
+// (160 KB) so that a later, narrower handle cannot lower the limit under a live wider one.  Every rung of the ladder (not only the handle's)
+static bool set_lds_ladder(const ppo_handle* h) {
+    bool ok = true;
+    auto set = [&](auto f, int bytes) { ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess; };
+    auto heads = [&](auto H) { for (int r = 0; r < RUNG_COUNT; ++r) { set(step_fn(H, r), 160 * 1024); set(train_fb_fn(H, r), 160 * 1024); if (r != RUNG_42_EARLY) set(eval_fn(H, r), 160 * 1024); } };
+    if (h->dist != PPO_ACT_GAUSSIAN) heads(GaussHead{});
+    for_each_head(h, heads);
+    set(weight_grad_kernel<4>, 4 * (64 * 64 + 1024) * 4); set(weight_grad_kernel<1>, 4 * (64 * 64 + 1024) * 4);
+    return ok;
+}
+// the narrow family likewise, every shape.  The kernels with a head: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl),
+// host step, resident rollout (one and two groups of rows); then the kernels without a head axis
+static bool set_lds_narrow(const ppo_handle* h) {
+    bool ok = true;
+    auto set = [&](auto f) { ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
+    auto heads = [&](auto H) {
+#define X(a, b, c, d) do { set(nw_step_fn<a, b, c, d>(H)); set(nw_train_fn<false, a, b, c, d>(H)); set(nw_train_fn<true, a, b, c, d>(H)); \
+                           if constexpr (!decltype(H)::bin) {      /* (the multi-binary head has a step and a train kernel, nothing else) */ \
+                           set(nw_host_step_fn<a, b, c, d>(H)); set(nw_rollout_fn<a, b, c, d, false>(H)); set(nw_rollout_fn<a, b, c, d, true>(H)); } } while (0)
+        X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
+#undef X
+    };
+    if (!nw_gauss(h)) heads(GaussHead{});
+    for_each_head(h, heads);
+#define X(a, b, c, d) do { set(narrow_collect_kernel<a, b, c, d>); set(narrow_rollout_coop_kernel<a, b, c, d>); } while (0)
+    X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
+#undef X
+    set((const void*)narrow_train_kernel<32, 64, 32, 2, true>); set((const void*)narrow_train_kernel<64, 64, 32, 2, true>);
+    set((const void*)narrow_train_kernel<32, 64, 32, 2, true, true>); set((const void*)narrow_train_kernel<64, 64, 32, 2, true, true>);
+    set((const void*)narrow_epoch_kernel<32, false>); set((const void*)narrow_epoch_kernel<64, false>);
+    set((const void*)narrow_epoch_kernel<32, true>); set((const void*)narrow_epoch_kernel<64, true>);
+    set((const void*)narrow_epoch_kernel<32, false, true>); set((const void*)narrow_epoch_kernel<64, false, true>);
+    set((const void*)narrow_epoch_kernel<32, true, true>); set((const void*)narrow_epoch_kernel<64, true, true>);
+    return ok;
+}
 
 // ---- one train step: which form, its argument blocks -----------------------------------------------------------------------
 // narrow: narrow_train_kernel + narrow_reduce_kernel | bf16, data parallel over the collective library: a gradient bucket per backward link | bf16: one assembly
@@ -1514,7 +1550,7 @@ static bool set_lds_pair(const ppo_handle* h) {
 enum TrainForm { TF_NARROW, TF_BF16_BUCKETED, TF_BF16, TF_PAIR_PEER, TF_PAIR, TF_GENERIC };
 
 // switches that are read per call: tests compare the forms in one process (a graph keeps what it captured)
-static bool env_set(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+static bool env_set(const char* name) { return is_on(getenv(name)); }
 static bool use_peer_tiles() { return !env_set("PPO_HIP_NO_PEER_TILES"); }
 // bf16, one GPU: assembly, clip and Adam in one persistent launch (ppo_bf16.hpp, bf16_reduce_adam_kernel)
 static bool use_reduce_adam(const ppo_handle* h) { return !h->comm && h->bf.fuse_ra && !h->adam_fast && !env_set("PPO_HIP_NO_REDUCE_ADAM"); }
@@ -1910,12 +1946,158 @@ void ppo_config_default(ppo_config* cfg, int32_t obs_dim, int32_t act_dim, int32
 
 const char* ppo_last_error(const ppo_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+// what a create entry point was asked for.  narrow / pair / bf16: the family opt-ins, gated on the distribution and dtype that give the flag a meaning (elsewhere: accepted, changes nothing)
+struct CreateRequest { int dist, Aw; CompTable comp; bool narrow, pair, bf16; };
+
+// nvec != null: a multi-categorical handle (ppo_create_multi_ex has checked the table).  No HIP call: a machine without a GPU reports a refusal's own reason
+static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, CreateRequest& rq) {
+    if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
+    if ((action_dist & 0xff) == PPO_ACT_MULTI_BINARY && cfg->obs_dim >= 1 && cfg->act_dim < 1)
+        return fail(nullptr, "ppo_create_ex: a multi-binary head needs act_dim >= 1 bits (got %d)", (int)cfg->act_dim);
+    if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
+    // the flags every distribution accepts go (PPO_ACT_BF16_MULTI_HEAD through ppo_create_multi_ex only); whatever else is left must be a distribution.  The two binary
+    // flags belong to PPO_ACT_MULTI_BINARY alone: beside any other distribution they stay in and are refused (ppo_create_multi_ex has refused them: "unknown flag bit")
+    int32_t dist = action_dist & ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS | (nvec ? PPO_ACT_BF16_MULTI_HEAD : 0));
+    if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
+    const bool cat = dist == PPO_ACT_CATEGORICAL, mcat = dist == PPO_ACT_MULTI_CATEGORICAL, mbin = dist == PPO_ACT_MULTI_BINARY, bf16 = cfg->compute_dtype == PPO_BF16;
+    if (dist != PPO_ACT_GAUSSIAN && !cat && !mbin && !(mcat && nvec))
+        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
+                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)", (int)dist);
+    if (cat && cfg->act_dim < 2) return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
+    if (cat && bf16 && !(action_dist & PPO_ACT_BF16_HEAD))
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
+    if (cat && bf16 && cfg->act_dim > 128)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
+    if (mbin && bf16) return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
+    for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
+    rq = CreateRequest{};
+    rq.dist = dist; rq.Aw = cat ? 1 : mcat ? n_components : cfg->act_dim;
+    rq.comp.K = mcat ? n_components : 0;
+    for (int k = 0; k < rq.comp.K; ++k) rq.comp.off[k + 1] = rq.comp.off[k] + nvec[k];
+    rq.narrow = (action_dist & (mbin ? PPO_ACT_BINARY_SHAPE_KERNELS : cat || mcat ? PPO_ACT_SHAPE_KERNELS : 0)) != 0;
+    rq.pair = (action_dist & (mbin ? PPO_ACT_BINARY_PAIR_KERNELS : cat || mcat ? PPO_ACT_PAIR_KERNELS : 0)) != 0 && cfg->compute_dtype == PPO_F32;
+    rq.bf16 = (action_dist & (cat ? PPO_ACT_BF16_HEAD : mcat ? PPO_ACT_BF16_MULTI_HEAD : 0)) != 0 && bf16;
+    return 0;
+}
+
+// ---- ppo_create's stages, in create_handle's order; each reports through fail(h, ..) ---------------------------------------
+static int open_device(ppo_handle* h, int ndev, int& n_cu) {
+    int dev = h->cfg.device;
+    if (dev < 0) { const char* lr = getenv("LOCAL_RANK"); dev = lr ? atoi(lr) % ndev : 0; }
+    h->device = dev;
+    if (hipSetDevice(dev) != hipSuccess) return fail(h, "hipSetDevice(%d) failed", dev);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(h, "hipGetDeviceProperties failed");
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(h, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName);
+    n_cu = prop.multiProcessorCount;
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(h, "hipStreamCreate failed");
+    h->use_graph = !is_on(getenv("PPO_HIP_NO_GRAPH"));
+    if (h->cfg.compute_dtype != PPO_F32 && h->cfg.compute_dtype != PPO_BF16) return fail(h, "ppo_create: compute_dtype must be PPO_F32 or PPO_BF16");
+    h->bf.on = h->cfg.compute_dtype == PPO_BF16;
+    return 0;
+}
+static int alloc_core(ppo_handle* h) {
+    const size_t P = (size_t)h->P_pad;
+    return dev_alloc(h, &h->par, (size_t)2 * h->net.par_total) || dev_alloc(h, &h->thetaT, (size_t)h->PT) || dev_alloc(h, &h->theta, P) || dev_alloc(h, &h->adam_m, P) || dev_alloc(h, &h->adam_v, P) || dev_alloc(h, &h->grad, P + 256) ||
+           dev_alloc(h, &h->sumsq, (size_t)4 * h->n_blocks) || dev_alloc(h, &h->sumsq2, (size_t)(h->n_blocks + 1023) / 1024) || dev_alloc(h, &h->beta_pow, 4) || dev_alloc(h, &h->hyper, 8) ||
+           dev_alloc(h, &h->stop, 4) || dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8) ? -1 : 0;
+}
+// t8 / dw2: the heads train8_kernel has (a discrete one only under its flag), any observation / action width up to 64 (tiles of 32 or 64 columns) in front of [256,256]
+static int decide_pair(ppo_handle* h) {
+    const NetDev& n = h->net;
+    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->opt_pair;
+    const bool shape = pair_head && !n.wide && h->CT == 4 && n.L == 2 && n.Hp[0] == 256 && n.Hp[1] == 256 && n.Kp0 <= 64 && n.Ap <= 64;
+    h->dw2 = shape && !is_on(getenv("PPO_HIP_NO_DW2"));
+    h->t8 = shape && !is_on(getenv("PPO_HIP_NO_T8"));
+    if ((h->t8 || h->dw2) && !set_lds_pair(h)) return fail(h, "hipFuncSetAttribute failed for train8_kernel / weight_grad_assemble_kernel");
+    return 0;
+}
+// dw2's slot jobs: every element the train kernel leaves as per-row-block partial sums (bias / logstd / value-head gradients), then the loss sums
+static int build_dw2_jobs(ppo_handle* h) {
+    if (!h->dw2) return 0;
+    const NetDev& nn = h->net;
+    std::vector<SlotJob> jobs;
+    for (const Tensor& t : h->tensors) {
+        const std::string nm = t.name;
+        const int tower = nm[0] == 'v' ? 1 : 0;
+        int l = -1;
+        if (nm.find("_fc") != std::string::npos) l = atoi(nm.c_str() + 5);
+        int so = -1, cnt = 0, po = 0;                 // po: the tensor's place in the small-parameter mirror (upload_grad_src's p_off)
+        if (l >= 0 && nm.substr(nm.size() - 2) == "/b") { so = nn.slot_db[l]; cnt = nn.Hp[l]; po = tower * nn.par_total + nn.par_b[l]; }
+        else if (nm == "vf/w") { so = nn.slot_head; cnt = nn.Hp[nn.L - 1]; po = nn.par_total + nn.par_wv; }
+        else if (nm == "vf/b") { so = nn.slot_aux; cnt = 1; po = nn.par_total + nn.par_bv; }
+        else if (nm == "pi/b") { so = nn.slot_head; cnt = nn.Ap; po = nn.par_bmu; }
+        else if (nm == "pi/logstd") { so = nn.slot_aux; cnt = nn.Ap; po = nn.par_ls; }
+        for (int e2 = 0; e2 < cnt; ++e2) jobs.push_back(SlotJob{tower, so + e2, t.off_pad + e2, 1 + po + e2});
+    }
+    for (int q = 0; q < 5; ++q) jobs.push_back(SlotJob{q == 1 ? 1 : 0, nn.slot_loss + (q <= 1 ? 0 : q - 1), h->P_pad + q, 0});   // {pg, vf, ent, kl, cf} sums
+    h->dw2_n_jobs = (int)jobs.size();
+    h->dw2_jpw = (h->dw2_n_jobs + DW2_GRID - 1) / DW2_GRID;
+    if (h->dw2_jpw > DW2_THREADS / 32) { h->dw2 = false; return 0; }       // (more jobs than the assembly's waves take: no dw2 after all)
+    if (dev_alloc(h, &h->dw2_jobs, jobs.size()) || dev_alloc(h, &h->dw2_counters, (size_t)DW2_TILES) || dev_alloc(h, &h->dw2_parts, (size_t)DW2_TILES + DW2_GRID)) return -1;
+    HIP_OK(h, hipMemcpyAsync(h->dw2_jobs, jobs.data(), jobs.size() * sizeof(SlotJob), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+// a narrow handle: the family's dynamic LDS, its switches, the deferred Adam and the resident epoch of the static Gaussian shapes, the weight image
+static int narrow_extras(ppo_handle* h, int n_cu) {
+    if (!h->narrow) return 0;
+    if (!set_lds_narrow(h)) return fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the narrow kernels");
+    h->opt_no_host_fused = is_on(getenv("PPO_HIP_NO_HOST_FUSED")); h->opt_no_host_resident = is_on(getenv("PPO_HIP_NO_HOST_RESIDENT"));
+    if (h->nw_static && nw_gauss(h) && !is_on(getenv("PPO_HIP_NO_LAZY_ADAM"))) {       // (the static shapes: [64,64] behind a 32- or 64-column observation tile -- 18 / 36 observations -- and 32 action columns)
+        // second parameter / moment set of the deferred Adam (zero-filled: the padding elements are never written and must read 0)
+        const size_t P = (size_t)h->P_pad;
+        if (dev_alloc(h, &h->nw_theta1, P) || dev_alloc(h, &h->nw_m1, P) || dev_alloc(h, &h->nw_v1, P)) return -1;
+        h->nw_lazy = true;
+        // the deferred / resident forms compute TF's quotient with the correctly rounded square root and division by DEFAULT since round 6 (no deviation from the
+        // reference's arithmetic; 6 - 9 % of this shape's train step); PPO_HIP_ADAM_FAST=1 (init_adam) opts into the hardware's 1-ulp reciprocal / square root
+        h->adam_exact = true; h->adam_fast = false;
+        h->nw_epoch = use_narrow_epoch() && n_cu >= 2 * 2 * NW_EPOCH_MAX_G;
+        if (h->nw_epoch && dev_alloc(h, &h->nw_epoch_words, NW_EPOCH_WORDS)) return -1;
+        h->nw_epoch_xl = h->nw_epoch && !is_on(getenv("PPO_HIP_NO_NARROW_EPOCH_XL")) && n_cu >= 64;
+    }
+    return dev_alloc(h, &h->nw_img, (size_t)2 * h->nw.w_total);
+}
+static int init_adam(ppo_handle* h) {
+    if (is_on(getenv("PPO_HIP_ADAM_FAST"))) { h->adam_fast = true; h->adam_exact = false; }      // every Adam step of the handle, so that its forms agree bit for bit
+    const float pw[2] = {h->cfg.adam_beta1, h->cfg.adam_beta2};
+    return ppo_set_beta_powers(h, pw);
+}
+
+static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, ppo_handle** out) {
+    if (!cfg || !out) return fail(nullptr, "ppo_create: null argument");
+    *out = nullptr;
+    CreateRequest rq;
+    if (parse_create(cfg, action_dist, nvec, n_components, rq)) return -1;
+    int ndev = 0, n_cu = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1) return fail(nullptr, "ppo_create: no HIP device available (%s); libppo_hip has no CPU fallback", hipGetErrorString(e));
+    ppo_handle* h = new ppo_handle();
+    h->cfg = *cfg; h->dist = rq.dist; h->Aw = rq.Aw; h->comp = rq.comp;
+    h->opt_narrow = rq.narrow; h->opt_pair = rq.pair; h->opt_bf16 = rq.bf16;
+    // every failure from here on leaves through this one exit: the message moves to the create error, the handle and what it holds go
+    auto bail = [&] { g_create_error = h->err; ppo_destroy(h); return -1; };
+    if (open_device(h, ndev, n_cu)) return bail();                 // the device (LOCAL_RANK), its arch, the stream, the graph switch, the dtype
+    if (build_layout(h)) return bail();
+    if (!set_lds_ladder(h)) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); return bail(); }
+    if (alloc_core(h)) return bail();
+    build_narrow_layout(h);                                        // h->narrow
+    if (upload_grad_src(h)) return bail();
+    if (decide_pair(h)) return bail();                             // h->t8, h->dw2
+    if (build_dw2_jobs(h)) return bail();                          // (may still drop dw2)
+    // the families are decided.  From here on the opt-ins say what took effect: a shape that does not qualify (or a switch that turns the family off) runs the generic
+    // kernels of its head, data parallel included (ppo_dist_init).  A categorical handle's opt_narrow keeps "asked" (ppo_handle)
+    if (h->dist != PPO_ACT_CATEGORICAL) h->opt_narrow = h->opt_narrow && h->narrow;
+    h->opt_pair = h->opt_pair && (h->t8 || h->dw2);
+    if (h->bf.on && bf16_create(h)) return bail();
+    if (narrow_extras(h, n_cu)) return bail();
+    if (init_adam(h)) return bail();
+    *out = h;
+    return 0;
+}
+
 int ppo_create(const ppo_config* cfg, ppo_handle** out) { return ppo_create_ex(cfg, PPO_ACT_GAUSSIAN, out); }
-
-static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, ppo_handle** out);
-
 int ppo_create_ex(const ppo_config* cfg, int32_t action_dist, ppo_handle** out) { return create_handle(cfg, action_dist, nullptr, 0, out); }
-
 int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, ppo_handle** out) { return ppo_create_multi_ex(cfg, nvec, n_components, 0, out); }
 
 // K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns; flags: PPO_ACT_SHAPE_KERNELS (the narrow family on a
@@ -1952,180 +2134,6 @@ int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {
     return h->comp.K;
 }
 int ppo_action_width(const ppo_handle* h) { return h ? h->Aw : -1; }
-
-// nvec != null: a multi-categorical handle (ppo_create_multi has checked the table)
-static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, ppo_handle** out) {
-    if (!cfg || !out) return fail(nullptr, "ppo_create: null argument");
-    *out = nullptr;
-    if (cfg->n_hidden < 1 || cfg->n_hidden > PPO_MAX_LAYERS) return fail(nullptr, "ppo_create: n_hidden must be 1..%d", PPO_MAX_LAYERS);
-    if ((action_dist & 0xff) == PPO_ACT_MULTI_BINARY && cfg->obs_dim >= 1 && cfg->act_dim < 1)
-        return fail(nullptr, "ppo_create_ex: a multi-binary head needs act_dim >= 1 bits (got %d)", (int)cfg->act_dim);
-    if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
-    const bool shape_kernels = (action_dist & PPO_ACT_SHAPE_KERNELS) != 0;       // the flags; whatever else is left must be a distribution
-    const bool bf16_head = (action_dist & PPO_ACT_BF16_HEAD) != 0;
-    const bool pair_kernels = (action_dist & PPO_ACT_PAIR_KERNELS) != 0;
-    const bool bf16_multi_head = nvec && (action_dist & PPO_ACT_BF16_MULTI_HEAD) != 0;      // (ppo_create_multi_ex only: from ppo_create_ex the bit stays in action_dist and is refused below)
-    if (nvec) action_dist &= ~(int32_t)PPO_ACT_BF16_MULTI_HEAD;
-    action_dist &= ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS);
-    // PPO_ACT_BINARY_SHAPE_KERNELS belongs to PPO_ACT_MULTI_BINARY alone: beside any other distribution the bit stays in and is refused below (ppo_create_multi_ex has refused it already: "unknown flag bit")
-    // PPO_ACT_BINARY_PAIR_KERNELS likewise
-    const bool binary_flags_ok = !nvec && (action_dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS)) == PPO_ACT_MULTI_BINARY;
-    const bool binary_shape_kernels = binary_flags_ok && (action_dist & PPO_ACT_BINARY_SHAPE_KERNELS) != 0;
-    const bool binary_pair_kernels = binary_flags_ok && (action_dist & PPO_ACT_BINARY_PAIR_KERNELS) != 0;
-    if (binary_flags_ok) action_dist = PPO_ACT_MULTI_BINARY;
-    if (action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_CATEGORICAL && action_dist != PPO_ACT_MULTI_BINARY && !(action_dist == PPO_ACT_MULTI_CATEGORICAL && nvec))
-        return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
-                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)", (int)action_dist);
-    if (action_dist == PPO_ACT_CATEGORICAL && cfg->act_dim < 2)
-        return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
-    if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && !bf16_head)
-        return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
-    if (action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16 && cfg->act_dim > 128)
-        return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
-    if (action_dist == PPO_ACT_MULTI_BINARY && cfg->compute_dtype == PPO_BF16)
-        return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
-    for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail(nullptr, "ppo_create: no HIP device available (%s); libppo_hip has no CPU fallback", hipGetErrorString(e));
-    ppo_handle* h = new ppo_handle();
-    h->cfg = *cfg;
-    h->dist = action_dist;
-    h->shape_kernels = shape_kernels && action_dist != PPO_ACT_GAUSSIAN && action_dist != PPO_ACT_MULTI_BINARY;   // (a Gaussian handle takes its shape's kernels anyway, a multi-binary one only under its own flag: this one changes nothing)
-    h->binary_shape_kernels = binary_shape_kernels;
-    h->binary_pair_kernels = binary_pair_kernels;      // (PPO_BF16 is refused above; a shape that does not qualify: below)
-    h->bf16_head = bf16_head && action_dist == PPO_ACT_CATEGORICAL && cfg->compute_dtype == PPO_BF16;   // (PPO_F32 or Gaussian: the flag changes nothing)
-    h->bf16_multi_head = bf16_multi_head && cfg->compute_dtype == PPO_BF16;   // (PPO_F32: the flag changes nothing)
-    h->pair_kernels = pair_kernels && (action_dist == PPO_ACT_CATEGORICAL || action_dist == PPO_ACT_MULTI_CATEGORICAL) && cfg->compute_dtype == PPO_F32;   // (Gaussian or PPO_BF16: the flag changes nothing; a shape that does not qualify: below)
-    h->Aw = action_dist == PPO_ACT_CATEGORICAL ? 1 : action_dist == PPO_ACT_MULTI_CATEGORICAL ? n_components : cfg->act_dim;
-    if (action_dist == PPO_ACT_MULTI_CATEGORICAL) {
-        h->comp.K = n_components;
-        for (int k = 0; k < n_components; ++k) h->comp.off[k + 1] = h->comp.off[k] + nvec[k];
-    }
-    int dev = cfg->device;
-    if (dev < 0) { const char* lr = getenv("LOCAL_RANK"); dev = lr ? atoi(lr) % ndev : 0; }
-    h->device = dev;
-    auto bail = [&](int) { g_create_error = h->err; ppo_destroy(h); return -1; };
-    if (hipSetDevice(dev) != hipSuccess) { fail(h, "hipSetDevice(%d) failed", dev); return bail(0); }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { fail(h, "hipGetDeviceProperties failed"); return bail(0); }
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { fail(h, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName); return bail(0); }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { fail(h, "hipStreamCreate failed"); return bail(0); }
-    const char* ng = getenv("PPO_HIP_NO_GRAPH");
-    h->use_graph = !(ng && ng[0] == '1');
-    if (cfg->compute_dtype != PPO_F32 && cfg->compute_dtype != PPO_BF16) { fail(h, "ppo_create: compute_dtype must be PPO_F32 or PPO_BF16"); return bail(0); }
-    h->bf.on = cfg->compute_dtype == PPO_BF16;
-    if (build_layout(h)) return bail(0);
-    // large dynamic LDS needs an explicit opt-in.  The attribute is per function, not per handle: it is set to the
-    // hardware maximum (160 KB) so that a later, narrower handle cannot lower the limit under a live wider one.
-    const int lds_bytes = 160 * 1024;
-    bool attr_ok = true;
-    auto set_lds = [&](auto f) { attr_ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess; };
-    { const NetDev& nn = h->net;
-      h->early = !nn.wide && h->CT == 4 && h->CTH == 2 && nn.L >= 2 && nn.Kp0 == 32 && nn.Ap == 32 && nn.Hp[0] == 256 && nn.Hp[nn.L - 1] == 256; }
-    // every rung of the ladder (not only the handle's), for the Gaussian head and every head this handle can launch
-    auto lds_opt_in = [&](auto H) { for (int r = 0; r < RUNG_COUNT; ++r) { set_lds(step_fn(H, r)); set_lds(train_fb_fn(H, r)); if (r != RUNG_42_EARLY) set_lds(eval_fn(H, r)); } };
-    if (h->dist != PPO_ACT_GAUSSIAN) lds_opt_in(GaussHead{});
-    for_each_head(h, lds_opt_in);
-    attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
-    attr_ok &= hipFuncSetAttribute((const void*)weight_grad_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 * 64 + 1024) * 4) == hipSuccess;
-    if (!attr_ok) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); return bail(0); }
-    const size_t P = (size_t)h->P_pad;
-    if (dev_alloc(h, &h->par, (size_t)2 * h->net.par_total) || dev_alloc(h, &h->thetaT, (size_t)h->PT) || dev_alloc(h, &h->theta, P) || dev_alloc(h, &h->adam_m, P) || dev_alloc(h, &h->adam_v, P) || dev_alloc(h, &h->grad, P + 256) ||
-        dev_alloc(h, &h->sumsq, (size_t)4 * h->n_blocks) || dev_alloc(h, &h->sumsq2, (size_t)(h->n_blocks + 1023) / 1024) || dev_alloc(h, &h->beta_pow, 4) || dev_alloc(h, &h->hyper, 8) ||
-        dev_alloc(h, &h->stop, 4) || dev_alloc(h, &h->norm_out, 1) || dev_alloc(h, &h->st_loss, 8))
-        return bail(0);
-    build_narrow_layout(h);
-    if (h->dist == PPO_ACT_MULTI_BINARY) h->binary_shape_kernels = h->narrow;     // likewise: a shape that does not qualify runs the generic <mbin> kernels, data parallel included
-    if (h->dist == PPO_ACT_MULTI_CATEGORICAL) h->shape_kernels = h->narrow;       // from here on: the flag took effect (a shape that does not qualify runs the generic <mcat> kernels, data parallel included)
-    if (upload_grad_src(h)) return bail(0);
-    const bool pair_head = h->dist == PPO_ACT_GAUSSIAN || h->pair_kernels || h->binary_pair_kernels;   // the heads train8_kernel has; a discrete one only where its flag asks for it
-    { const char* e = getenv("PPO_HIP_NO_DW2"); const NetDev& nn = h->net;
-      h->dw2 = !(e && e[0] == '1') && pair_head && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64; }
-    { const char* e = getenv("PPO_HIP_NO_T8"); const NetDev& nn = h->net;
-      // any observation / action width up to 64 (tiles of 32 or 64 columns) in front of hidden [256,256]
-      h->t8 = !(e && e[0] == '1') && pair_head && !nn.wide && h->CT == 4 && nn.L == 2 && nn.Hp[0] == 256 && nn.Hp[1] == 256 && nn.Kp0 <= 64 && nn.Ap <= 64;
-      if ((h->t8 || h->dw2) && !set_lds_pair(h)) {
-          fail(h, "hipFuncSetAttribute failed for train8_kernel / weight_grad_assemble_kernel"); return bail(0); } }
-    if (h->dw2) {
-        // slot jobs: every element the train kernel leaves as per-row-block partial sums (bias / logstd / value-head gradients), then the loss sums
-        const NetDev& nn = h->net;
-        std::vector<SlotJob> jobs;
-        for (const Tensor& t : h->tensors) {
-            const std::string nm = t.name;
-            const int tower = nm[0] == 'v' ? 1 : 0;
-            int l = -1;
-            if (nm.find("_fc") != std::string::npos) l = atoi(nm.c_str() + 5);
-            int so = -1, cnt = 0, po = 0;                 // po: the tensor's place in the small-parameter mirror (upload_grad_src's p_off)
-            if (l >= 0 && nm.substr(nm.size() - 2) == "/b") { so = nn.slot_db[l]; cnt = nn.Hp[l]; po = tower * nn.par_total + nn.par_b[l]; }
-            else if (nm == "vf/w") { so = nn.slot_head; cnt = nn.Hp[nn.L - 1]; po = nn.par_total + nn.par_wv; }
-            else if (nm == "vf/b") { so = nn.slot_aux; cnt = 1; po = nn.par_total + nn.par_bv; }
-            else if (nm == "pi/b") { so = nn.slot_head; cnt = nn.Ap; po = nn.par_bmu; }
-            else if (nm == "pi/logstd") { so = nn.slot_aux; cnt = nn.Ap; po = nn.par_ls; }
-            for (int e2 = 0; e2 < cnt; ++e2) jobs.push_back(SlotJob{tower, so + e2, t.off_pad + e2, 1 + po + e2});
-        }
-        for (int q = 0; q < 5; ++q) jobs.push_back(SlotJob{q == 1 ? 1 : 0, nn.slot_loss + (q <= 1 ? 0 : q - 1), h->P_pad + q, 0});   // {pg, vf, ent, kl, cf} sums
-        h->dw2_n_jobs = (int)jobs.size();
-        h->dw2_jpw = (h->dw2_n_jobs + DW2_GRID - 1) / DW2_GRID;
-        if (h->dw2_jpw > DW2_THREADS / 32) h->dw2 = false;
-        else {
-            if (dev_alloc(h, &h->dw2_jobs, jobs.size()) || dev_alloc(h, &h->dw2_counters, (size_t)DW2_TILES) || dev_alloc(h, &h->dw2_parts, (size_t)DW2_TILES + DW2_GRID)) return bail(0);
-            HIP_OK(h, hipMemcpyAsync(h->dw2_jobs, jobs.data(), jobs.size() * sizeof(SlotJob), hipMemcpyHostToDevice, h->stream));
-            HIP_OK(h, hipStreamSynchronize(h->stream));
-        }
-    }
-    // from here on: the flag took effect (a shape that does not qualify, both switches set: it did not)
-    if (h->dist == PPO_ACT_MULTI_BINARY) h->binary_pair_kernels = h->t8 || h->dw2;
-    else if (h->dist != PPO_ACT_GAUSSIAN) h->pair_kernels = h->t8 || h->dw2;
-    if (h->bf.on && bf16_create(h)) return bail(0);
-    if (h->narrow) {
-        attr_ok = true;
-        auto big_lds = [&](auto f) { attr_ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
-        // the kernels with a head, every shape: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl), host step, resident
-        // rollout (one and two groups of rows) -- for the Gaussian head and every head this handle can launch
-        auto nw_heads = [&](auto H) {
-#define X(a, b, c, d) do { big_lds(nw_step_fn<a, b, c, d>(H)); big_lds(nw_train_fn<false, a, b, c, d>(H)); big_lds(nw_train_fn<true, a, b, c, d>(H)); \
-                           if constexpr (!decltype(H)::bin) {      /* (the multi-binary head has a step and a train kernel, nothing else) */ \
-                           big_lds(nw_host_step_fn<a, b, c, d>(H)); big_lds(nw_rollout_fn<a, b, c, d, false>(H)); big_lds(nw_rollout_fn<a, b, c, d, true>(H)); } } while (0)
-            X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
-#undef X
-        };
-        if (!nw_gauss(h)) nw_heads(GaussHead{});
-        for_each_head(h, nw_heads);
-        // the kernels without a head axis
-#define X(a, b, c, d) do { big_lds(narrow_collect_kernel<a, b, c, d>); big_lds(narrow_rollout_coop_kernel<a, b, c, d>); } while (0)
-        X(0, 0, 0, 0); X(32, 64, 32, 2); X(64, 64, 32, 2);
-#undef X
-        big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true>);
-        big_lds((const void*)narrow_train_kernel<32, 64, 32, 2, true, true>); big_lds((const void*)narrow_train_kernel<64, 64, 32, 2, true, true>);
-        big_lds((const void*)narrow_epoch_kernel<32, false>); big_lds((const void*)narrow_epoch_kernel<64, false>);
-        big_lds((const void*)narrow_epoch_kernel<32, true>); big_lds((const void*)narrow_epoch_kernel<64, true>);
-        big_lds((const void*)narrow_epoch_kernel<32, false, true>); big_lds((const void*)narrow_epoch_kernel<64, false, true>);
-        big_lds((const void*)narrow_epoch_kernel<32, true, true>); big_lds((const void*)narrow_epoch_kernel<64, true, true>);
-        if (!attr_ok) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the narrow kernels"); return bail(0); }
-        { const char* e1 = getenv("PPO_HIP_NO_HOST_FUSED"); const char* e2 = getenv("PPO_HIP_NO_HOST_RESIDENT");
-          h->opt_no_host_fused = e1 && e1[0] == '1'; h->opt_no_host_resident = e2 && e2[0] == '1'; }
-        const char* nl = getenv("PPO_HIP_NO_LAZY_ADAM");
-        if (h->nw_static && nw_gauss(h) && !(nl && nl[0] == '1')) {       // (the static shapes: [64,64] behind a 32- or 64-column observation tile -- 18 / 36 observations -- and 32 action columns)
-            // second parameter / moment set of the deferred Adam (zero-filled: the padding elements are never written and must read 0)
-            if (dev_alloc(h, &h->nw_theta1, P) || dev_alloc(h, &h->nw_m1, P) || dev_alloc(h, &h->nw_v1, P)) return bail(0);
-            h->nw_lazy = true;
-            // the deferred / resident forms compute TF's quotient with the correctly rounded square root and division by DEFAULT since round 6 (no deviation from the
-            // reference's arithmetic; 6 - 9 % of this shape's train step); PPO_HIP_ADAM_FAST=1 (below) opts into the hardware's 1-ulp reciprocal / square root
-            h->adam_exact = true; h->adam_fast = false;
-            h->nw_epoch = use_narrow_epoch() && prop.multiProcessorCount >= 2 * 2 * NW_EPOCH_MAX_G;
-            if (h->nw_epoch && dev_alloc(h, &h->nw_epoch_words, NW_EPOCH_WORDS)) return bail(0);
-            { const char* nx = getenv("PPO_HIP_NO_NARROW_EPOCH_XL"); h->nw_epoch_xl = h->nw_epoch && !(nx && nx[0] == '1') && prop.multiProcessorCount >= 64; }
-        }
-        if (dev_alloc(h, &h->nw_img, (size_t)2 * h->nw.w_total)) return bail(0);
-    }
-    { const char* af = getenv("PPO_HIP_ADAM_FAST"); if (af && af[0] == '1') { h->adam_fast = true; h->adam_exact = false; } }      // every Adam step of the handle, so that its forms agree bit for bit
-    const float pw[2] = {cfg->adam_beta1, cfg->adam_beta2};
-    if (ppo_set_beta_powers(h, pw)) return bail(0);
-    *out = h;
-    return 0;
-}
 
 void ppo_destroy(ppo_handle* h) {
     if (!h) return;
@@ -2681,7 +2689,7 @@ int ppo_norm_init(ppo_handle* h, int32_t n_envs, float gamma, float clip_obs, fl
     h->pin_wgflag_n = (n_envs + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     HIP_OK(h, hipHostMalloc((void**)&h->pin_wgflag, (size_t)h->pin_wgflag_n * sizeof(unsigned), hipHostMallocDefault));
     memset(h->pin_wgflag, 0, (size_t)h->pin_wgflag_n * sizeof(unsigned)); h->wg_seq = 0;
-    { const char* e = getenv("PPO_HIP_NO_DIRECT_ACT"); h->opt_no_direct_act = e && e[0] == '1'; }
+    h->opt_no_direct_act = is_on(getenv("PPO_HIP_NO_DIRECT_ACT"));
     {
         void* d = nullptr;
         HIP_OK(h, hipHostGetDevicePointer(&d, h->pin_wgflag, 0)); h->pin_wgflag_dev = (unsigned*)d;
@@ -2694,8 +2702,7 @@ int ppo_norm_init(ppo_handle* h, int32_t n_envs, float gamma, float clip_obs, fl
     {
         if (h->vram_in) { (void)hipFree(h->vram_in); h->vram_in = nullptr; h->vram_h2d = nullptr; }
         int large_bar = 0;
-        const char* nv = getenv("PPO_HIP_NO_VRAM_INBOX");
-        if (n_envs == 1 && nw_gauss(h) && h->nw_static && !(nv && nv[0] == '1') &&
+        if (n_envs == 1 && nw_gauss(h) && h->nw_static && !is_on(getenv("PPO_HIP_NO_VRAM_INBOX")) &&
             hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) == hipSuccess && large_bar) {
             const size_t words = ru((int)in_n, 32) + 64;
             float* box = nullptr;
@@ -3041,8 +3048,7 @@ enum DevForm { DF_ROLLOUT1, DF_PERSISTENT, DF_COOP, DF_FUSED, DF_PER_STEP };
 // ONE environment on the reference shape (any observation width up to 64, any action width up to 32): a resident rollout runs in one wave,
 // weights in registers (ppo_rollout1.hpp), not in the 32-row workgroup.  (The switch is read per call: the tests compare both forms in one process.)
 static bool use_rollout1(const ppo_handle* h) {
-    const char* e1 = getenv("PPO_HIP_NO_ROLLOUT1");
-    return h->nw_static && nw_gauss(h) && h->E == 1 && !(e1 && e1[0] == '1');
+    return h->nw_static && nw_gauss(h) && h->E == 1 && !is_on(getenv("PPO_HIP_NO_ROLLOUT1"));
 }
 
 // dynamic LDS of narrow_rollout_kernel for the handle's E environments, and of the kernels that hold one group of 32 rows
@@ -3104,11 +3110,11 @@ static HostForm host_form(const ppo_handle* h, bool explicit_noise) {
 static DevForm dev_form(const ppo_handle* h) {
     const NetDev& n = h->net;
     const int E = h->E, G = (E + NW_ROWS - 1) / NW_ROWS;
-    const char* npe = getenv("PPO_HIP_NO_PERSISTENT_COLLECT");
+    const bool npe = is_on(getenv("PPO_HIP_NO_PERSISTENT_COLLECT"));
     // a discrete handle: the one-workgroup form only, and only where ppo_set_rollout_resident took effect
-    if (nw_discrete(h)) return resident_discrete(h) && !(npe && npe[0] == '1') ? DF_PERSISTENT : DF_PER_STEP;
+    if (nw_discrete(h)) return resident_discrete(h) && !npe ? DF_PERSISTENT : DF_PER_STEP;
     const bool small_net = nw_gauss(h) && !h->comm && n.O <= 64;          // (the one-wave, cooperative and fused rollout kernels keep a Gaussian head)
-    const bool resident = small_net && n.A <= 64 && !(npe && npe[0] == '1');
+    const bool resident = small_net && n.A <= 64 && !npe;
     // the whole rollout in ONE launch of one persistent workgroup: state in LDS, only stores leave the CU
     // (up to NW_RO_MAX_E environments: the one workgroup walks them in groups of 32 rows)
     if (resident && E <= NW_RO_MAX_E && rollout_lds(h) <= 160 * 1024) return use_rollout1(h) ? DF_ROLLOUT1 : DF_PERSISTENT;
@@ -4130,19 +4136,14 @@ struct UidByValue { char b[128]; };
 int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128]) {
     if (world < 1 || rank < 0 || rank >= world) return fail(h, "ppo_dist_init: bad world/rank");
     if (h->target_kl > 0.f) return fail(h, "ppo_dist_init: data parallel is not supported with target-KL early stopping on (ppo_set_target_kl(h, 0) first)");
-    if (h->bf16_head) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical PPO_BF16 handle created with PPO_ACT_BF16_HEAD");
-    if (h->bf16_multi_head)
-        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD");
-    if (h->binary_shape_kernels)
-        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_SHAPE_KERNELS (create it without the flag)");
-    if (h->binary_pair_kernels)
-        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-binary handle created with PPO_ACT_BINARY_PAIR_KERNELS (create it without the flag)");
-    if (h->shape_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
-        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
-    if (h->shape_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_SHAPE_KERNELS (create it without the flag)");
-    if (h->pair_kernels && h->dist == PPO_ACT_MULTI_CATEGORICAL)
-        return fail(h, "ppo_dist_init: data parallel is not supported for a multi-categorical handle created with PPO_ACT_PAIR_KERNELS (create it without the flag)");
-    if (h->pair_kernels) return fail(h, "ppo_dist_init: data parallel is not supported for a categorical handle created with PPO_ACT_PAIR_KERNELS (create it without the flag)");
+    // a discrete handle with a family opt-in (ppo_handle::opt_*): the bf16 head first, then the narrow family, then the pair, each under its distribution's flag
+    const bool mcat = h->dist == PPO_ACT_MULTI_CATEGORICAL, mbin = h->dist == PPO_ACT_MULTI_BINARY;
+    const char* kind = mcat ? "multi-categorical" : mbin ? "multi-binary" : "categorical";
+    if (h->opt_bf16)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a %s PPO_BF16 handle created with %s", kind, mcat ? "PPO_ACT_BF16_MULTI_HEAD" : "PPO_ACT_BF16_HEAD");
+    if (h->opt_narrow || h->opt_pair)
+        return fail(h, "ppo_dist_init: data parallel is not supported for a %s handle created with %s (create it without the flag)", kind,
+                    h->opt_narrow ? (mbin ? "PPO_ACT_BINARY_SHAPE_KERNELS" : "PPO_ACT_SHAPE_KERNELS") : (mbin ? "PPO_ACT_BINARY_PAIR_KERNELS" : "PPO_ACT_PAIR_KERNELS"));
     if (load_rccl(h->rccl, h->err)) return -1;
     HIP_OK(h, hipSetDevice(h->device));
     UidByValue u;
@@ -4153,8 +4154,7 @@ int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128
     if (rc) return fail(h, "ncclCommInitRank failed: %s", h->rccl.GetErrorString ? h->rccl.GetErrorString(rc) : "?");
     h->world = world; h->rank = rank;
     drop_graph(h);
-    { const char* e = getenv("PPO_HIP_NO_ADAM_MEET");
-      h->adam_meet = !(e && e[0] == '1');
+    { h->adam_meet = !is_on(getenv("PPO_HIP_NO_ADAM_MEET"));
       if (h->adam_meet && (dev_alloc(h, &h->adam_meet_words, ADAM_MEET_MAX_GRID + 32) || dev_alloc(h, &h->adam_meet_parts, ADAM_MEET_MAX_GRID))) return -1;
       HIP_OK(h, hipStreamSynchronize(h->stream)); }
     if (world > 1) {
