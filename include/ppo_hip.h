@@ -307,10 +307,21 @@ int ppo_act_deterministic(ppo_handle* h, const float* obs, int32_t n, float* act
 
 /* ---- querying the policy: given actions and the action distribution (no reference counterpart: its MlpPolicy fetches action, value_flat, neglogp and
  * deterministic_action only; stable-baselines 2 ActorCriticPolicy.proba_step / BaseRLModel.action_probability, stable-baselines 3 evaluate_actions) -------------
- * All three run policy_eval_kernel: the act model's two towers on policy_step_kernel's geometry, no random draw, the head arithmetic of
+ * On a PPO_F32 handle all three run policy_eval_kernel: the act model's two towers on policy_step_kernel's geometry, no random draw, the head arithmetic of
  * ppo_head.hpp.  Every PPO_F32 handle runs this one generic kernel -- also a handle whose step runs the narrow family (its results then agree with ppo_step's to
- * rounding, not bit for bit; on a handle whose step runs policy_step_kernel neglogp and value are ppo_step's bits).  A PPO_BF16 handle is refused: its step's neglogp
- * comes out of bf16 GEMMs and an fp32 evaluation would disagree with it (a bf16 form is future work).  A data-parallel handle evaluates its own rows, no collective.
+ * rounding, not bit for bit; on a handle whose step runs policy_step_kernel neglogp and value are ppo_step's bits).  A data-parallel handle evaluates its own
+ * rows, no collective.
+ * A PPO_BF16 handle (Gaussian, PPO_ACT_BF16_HEAD, PPO_ACT_BF16_MULTI_HEAD) is refused by default: its step's neglogp comes out of bf16 GEMMs and the fp32 kernel
+ * would disagree with it.  ppo_set_bf16_queries(h, 1) gives such a handle the bf16 form of the three calls: the step's own staging, hidden-layer GEMMs and
+ * bf16_heads_kernel on the given rows, then bf16_eval_kernel<[cat[,mask][,multi]]> on the head outputs -- bf16_sample_kernel's geometry (one wave per row, lane l owns
+ * elements l and l + 64, A <= 128, no LDS), the head's partial products added in range order, the fp32 arithmetic of ppo_head.hpp, no draw.  Bit for bit: value
+ * and the neglogp of the action ppo_step drew are ppo_step's (every head, masked or not); a Gaussian handle's mu is ppo_act_deterministic's action; one component
+ * gives the categorical handle's bits and a row of ones as mask the unmasked ones; before any update ppo_rollout_evaluate returns rollout fields 2 and 3.  Entropy
+ * and the parameters are fp32 from the same logits (the entropy terms of the train model's loss kernel).  More rows than cfg.max_rows (ppo_rollout_evaluate on a
+ * large rollout) are walked in chunks of at most max_rows rows: rows are independent, no bit changes, and the workspaces stay what a step of max_rows needs.  The
+ * calls overwrite the workspaces ppo_value overwrites (staged rows, tanh outputs, head outputs) and nothing ppo_get_last_grad rebuilds from; a raised chain error
+ * repeats the pass layer by layer, as for ppo_value.  The setting is host state: the default is off, the setter touches no device state and drops nothing, and a
+ * PPO_F32 handle accepts it and changes nothing (same bits, same counts).
  * The calls are STATELESS: they do not advance the counter RNG and touch neither rollout, normaliser nor Adam state; they are legal in the middle of a rollout on
  * every rollout form (a resident rollout kernel is retired and relaunched as for ppo_value) and see the weights of the last finished ppo_update / ppo_train_step.
  * One exception to "one launch, nothing written but the outputs": on a handle whose step runs the narrow family, the train forms keep the weights and the packed
@@ -337,6 +348,8 @@ int ppo_evaluate_actions(ppo_handle* h, const float* obs, const float* actions, 
                          float* entropy);
 int ppo_action_probability(ppo_handle* h, const float* obs, int32_t n, const float* mask, float* params, int64_t count);
 int ppo_rollout_evaluate(ppo_handle* h, float* value, float* neglogp, float* entropy);
+int ppo_set_bf16_queries(ppo_handle* h, int32_t on);      /* any time; host state only */
+int ppo_bf16_queries(const ppo_handle* h);                /* the setting (0 / 1) */
 
 /* ---- action masks of the categorical head (invalid-action masking; no reference counterpart) ---------------
  * A mask is one float per (row, category), [n, A]: non-zero = allowed, 0 = forbidden.  For a masked row with logits l and allowed set S:

@@ -305,6 +305,17 @@ class PPOHip:
         self._ck(self.lib.ppo_rollout_evaluate(self.h, *[_fp(x) for x in outs]))
         return tuple(outs)
 
+    def set_bf16_queries(self, on=True):
+        """The three queries above on a compute_dtype=1 (PPO_BF16) handle (include/ppo_hip.h, ppo_set_bf16_queries): off (the default) they are refused; on, they run
+        the step's bf16 forward and bf16_eval_kernel -- value and the neglogp of a drawn action are step()'s bits.  Host state only; a compute_dtype=0 handle
+        accepts it and nothing changes."""
+        self._ck(self.lib.ppo_set_bf16_queries(self.h, int(bool(on))))
+
+    @property
+    def bf16_queries(self):
+        """the setting"""
+        return bool(self.lib.ppo_bf16_queries(self.h))
+
     # ---- train ------------------------------------------------------------------------------------
     def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v, mask=None):
         arrs = [_f32(x) for x in (obs, actions, advs, returns, old_nlp, old_v)]

@@ -775,33 +775,46 @@ struct SampleArgsBM : SampleArgsB { CompTable comp; };   // the <.., MULTI> inst
 // ---- categorical head (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD): the arithmetic of policy_step_kernel<.., CAT, MASK> / train_fwd_bwd_kernel<.., CAT, MASK> (ppo_head.hpp) in the
 // geometry of the two kernels below -- one wave per row, lane l owns categories l and l + 64 -- with 64-lane __shfl_xor butterflies where those kernels reduce over 16 lanes.
 // (value, index) argmax over the wave: the larger value wins, a tie goes to the lower index; every lane ends with the same pair
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-    for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(i, o); argmax_step(v, i, ov, oi); }
+// __shfl / __shfl_xor over the whole wave.  INL: restated on the builtins and ALWAYS inlined -- the HIP header's are plain `inline`, and a kernel whose target features
+// differ from the translation unit's (bf16_eval_kernel, below, is compiled without packed fp32 instructions) cannot inline those and would call them.  Same
+// ds_bpermute_b32, same values; the default keeps the header's form for the kernels that had it.
+template <class T>
+__device__ __forceinline__ T wave_get(T v, int src) { return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v))); }
+template <bool INL = false, class T>
+__device__ __forceinline__ T wave_xor(T v, int o) {
+    if constexpr (INL) return wave_get(v, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) ^ o);
+    else return __shfl_xor(v, o);
 }
-__device__ __forceinline__ float wave_sum_all(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+template <bool INL = false>
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+    for (int o = 32; o > 0; o >>= 1) { const float ov = wave_xor<INL>(v, o); const int oi = wave_xor<INL>(i, o); argmax_step(v, i, ov, oi); }
+}
+template <bool INL = false>
+__device__ __forceinline__ float wave_sum_all(float v) { for (int o = 32; o > 0; o >>= 1) v += wave_xor<INL>(v, o); return v; }
 // The row statistics BOTH kernels need, in ONE shape (the sample kernel's neglogp and the loss kernel's are then the same bits on the same weights): maximum m and its
 // index over the allowed categories (ok[e]: category lane + 64 e exists and is allowed), a0 = l - m, ex = exp(a0), z = sum of ex over the allowed ones.
 // MASK: the index starts at A ("none yet"), so a lane without an allowed category loses every tie of the butterfly to a real index.
 // A component [first, A) of the multi-categorical head: ok[e] says membership too, a lane without a member holds the identity (-inf at `first`, or "none yet" = A).
-template <bool MASK>
+template <bool MASK, bool INL = false>
 __device__ __forceinline__ void cat_row_norm(const float (&lg)[2], const bool (&ok)[2], int lane, int A, int& il, float (&a0)[2], float (&ex)[2], float& z, int first = 0) {
     float bl = -INFINITY;
     il = MASK ? A : first;
 #pragma unroll
     for (int e = 0; e < 2; ++e)
         if (ok[e]) cat_take<MASK>(lg[e], lane + 64 * e, A, bl, il);
-    wave_argmax(bl, il);
+    wave_argmax<INL>(bl, il);
     float zs = 0.f;
 #pragma unroll
     for (int e = 0; e < 2; ++e) { a0[e] = lg[e] - bl; ex[e] = expf(a0[e]); if (ok[e]) zs += ex[e]; }
-    z = wave_sum_all(zs);
+    z = wave_sum_all<INL>(zs);
 }
 // a0 of category `act` (held by exactly one lane; the others add zeros)
+template <bool INL = false>
 __device__ __forceinline__ float cat_row_pick(const float (&a0)[2], const bool (&ok)[2], int lane, int act) {
     float la = 0.f;
 #pragma unroll
     for (int e = 0; e < 2; ++e) if (ok[e] && lane + 64 * e == act) la = a0[e];
-    return wave_sum_all(la);
+    return wave_sum_all<INL>(la);
 }
 
 // one wave per row, one lane per action (two past 64 actions): the row sums take the SAME shape as in bf16_loss_kernel, so the act model's
@@ -927,6 +940,135 @@ __global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(std::conditio
     if (lane == 0 && live) {
         if (a.neglogp) a.neglogp[row] = gauss_nlp(ssq, slog, a.A);
         if (a.value) a.value[row] = head_sum(a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride);
+    }
+}
+
+// ---- policy query on a PPO_BF16 handle (ppo_evaluate_actions, ppo_action_probability, ppo_rollout_evaluate behind ppo_set_bf16_queries): the head outputs of a
+// forward pass and GIVEN actions -> value, neglogp, entropy and the distribution's parameters, each stored only where its pointer is non-null.  No draw: the step's
+// epilogue with the given action where that kernel has the drawn one, so the action ppo_step sampled gets ppo_step's neglogp bit for bit -------------------------
+struct EvalArgsB {
+    const float* head[2]; int ldh; int hsplit; size_t hstride;      // as SampleArgsB
+    const float* logstd;                // fp32 master
+    const float* actions;               // [n, action width] or null (then neglogp is not asked for)
+    const float* mask;                  // [n, A] (non-zero = allowed); read by the <CAT, MASK> instantiations only
+    float* value; float* neglogp; float* entropy;      // [n] each
+    float* params;                      // [n, W]: Gaussian mu | std (W = 2 A), categorical forms the probabilities (W = A)
+    int n, A, W;
+};
+struct EvalArgsBM : EvalArgsB { CompTable comp; };
+
+// the lane's partial products of head element idx, all requested before the first is used ...
+__device__ __forceinline__ void head_parts(float (&p)[GB_HEAD_SPLIT], const float* f, size_t idx, int hsplit, size_t hstride, bool want) {
+#pragma unroll
+    for (int k = 0; k < GB_HEAD_SPLIT; ++k) p[k] = (want && k < hsplit) ? f[idx + (size_t)k * hstride] : 0.f;
+}
+// ... and their sum in range order: head_sum's bits
+__device__ __forceinline__ float head_parts_sum(const float (&p)[GB_HEAD_SPLIT], int hsplit) {
+    float s = p[0];
+#pragma unroll
+    for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < hsplit) s += p[k];
+    return s;
+}
+
+// bf16_sample_kernel's geometry: one wave per row, BS_ROWS rows per block, lane l owns elements l and l + 64 (A <= 128), no LDS, no barrier; a dead row's wave
+// returns at once.  Every load of the lane goes out first: the partial products of its two elements and (lane 0) of the value, its mask entries, its action value(s).
+// Gaussian: z = (act - mu) / sigma, the two row sums and their butterfly as bf16_sample_kernel writes them out, then gauss_nlp; the entropy's terms
+// (gauss_entropy_elem, policy_eval_kernel's) ride in the same butterfly; params = mu | std, mu being the sum ppo_act_deterministic stores.
+// CAT: the walk of bf16_sample_kernel<.., MULTI> over the components (one component [0, A) without MULTI: cat_row_norm and cat_row_pick then see exactly the <CAT> form's
+// arguments).  Lane k < K loads component k's action and the walk broadcasts it (bf16_loss_kernel<.., MULTI>); the index is compared with the lane's j and never
+// indexes anything.  Per component: cat_row_norm over the allowed set, neglogp log z - la, the entropy terms of bf16_loss_kernel<CAT> (cat_entropy_term over the allowed
+// elements, one butterfly), p_j = ex_j / z into params, exactly +0 for a forbidden category.  neglogp and entropy: the components' in component order, starting from
+// the first one's value.  A row of ones as mask: the unmasked bits.
+// Compiled without packed fp32 instructions (a target attribute of this kernel alone); hence the <.., INL = true> wave helpers.
+#ifdef __HIP_DEVICE_COMPILE__
+#define BF16_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define BF16_NO_PACKED_F32                                   // (the host pass does not know the feature)
+#endif
+template <bool CAT = false, bool MASK = false, bool MULTI = false>
+__global__ BF16_NO_PACKED_F32 __launch_bounds__(64 * BS_ROWS) void bf16_eval_kernel(std::conditional_t<MULTI, EvalArgsBM, EvalArgsB> a) {
+    static_assert(CAT || !MASK, "action masks belong to the categorical head");
+    static_assert(CAT || !MULTI, "the multi-categorical head is a form of the categorical one");
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    const bool given = a.actions != nullptr;
+    float hp[2][GB_HEAD_SPLIT], vp[GB_HEAD_SPLIT];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) head_parts(hp[e], a.head[0], (size_t)row * a.ldh + lane + 64 * e, a.hsplit, a.hstride, lane + 64 * e < a.A);
+    head_parts(vp, a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride, lane == 0 && a.value);
+    float* prow = a.params ? a.params + (size_t)row * a.W : nullptr;
+    float nlp = 0.f, ent = 0.f;
+    if constexpr (CAT) {
+        int K = 1;
+        if constexpr (MULTI) K = a.comp.K;
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = lane + 64 * e;
+            ok[e] = j < a.A;
+            if constexpr (MASK) { if (j < a.A) ok[e] = a.mask[(size_t)row * a.A + j] != 0.f; }
+        }
+        int kact = -1;                                       // lane k < K: component k's index within the component
+        if (given && lane < K) kact = (int)a.actions[(size_t)row * K + lane];
+        float lg[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) lg[e] = lane + 64 * e < a.A ? head_parts_sum(hp[e], a.hsplit) : 0.f;
+        for (int k = 0; k < K; ++k) {
+            int o = 0, ce = a.A;
+            if constexpr (MULTI) { o = a.comp.off[k]; ce = a.comp.off[k + 1]; }
+            const int ka = wave_get(kact, k);
+            const int act = given ? o + ka : -1;
+            bool in[2], okk[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) { const int j = lane + 64 * e; in[e] = j >= o && j < ce; okk[e] = ok[e] && in[e]; }
+            int il;
+            float a0[2], ex[2], z;
+            cat_row_norm<MASK, true>(lg, okk, lane, ce, il, a0, ex, z, o);
+            const float lz = logf(z);
+            const float la = cat_row_pick<true>(a0, okk, lane, act);
+            float hk = 0.f;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) if (okk[e]) hk += cat_entropy_term(ex[e], z, lz, a0[e]);
+            hk = wave_sum_all<true>(hk);
+            const float nk = lz - la;
+            nlp = k == 0 ? nk : nlp + nk;
+            ent = k == 0 ? hk : ent + hk;
+            if (prow) {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) if (in[e] && lane + 64 * e < a.A) prow[lane + 64 * e] = okk[e] ? ex[e] / z : 0.f;
+            }
+        }
+    } else {
+        float act_[2], ls_[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = lane + 64 * e;
+            act_[e] = (given && j < a.A) ? a.actions[(size_t)row * a.A + j] : 0.f;
+            ls_[e] = j < a.A ? a.logstd[j] : 0.f;
+        }
+        float ssq = 0.f, slog = 0.f;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = lane + 64 * e;
+            if (j < a.A) {
+                const float mu = head_parts_sum(hp[e], a.hsplit);
+                // gauss_std and gauss_z of ppo_head.hpp, written out as in bf16_sample_kernel
+                const float logstd = mu * 0.0f + ls_[e];
+                const float sigma = expf(logstd);
+                const float act = given ? act_[e] : mu;
+                const float z = (act - mu) / sigma;
+                ssq += z * z; slog += logstd; ent += gauss_entropy_elem(logstd);
+                if (prow) { prow[j] = mu; prow[a.A + j] = sigma; }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) { ssq += wave_xor<true>(ssq, o); slog += wave_xor<true>(slog, o); ent += wave_xor<true>(ent, o); }
+        nlp = gauss_nlp(ssq, slog, a.A);
+    }
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = nlp;
+        if (a.entropy) a.entropy[row] = ent;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.hsplit);
     }
 }
 

@@ -283,7 +283,8 @@ struct ppo_handle {
     // ... its discrete forms (ppo_set_rollout_resident on a narrow categorical / multi-categorical handle; resident_discrete() says whether it took effect, on the
     // device env as well): the mask of row t travels in pin_mask behind a sequence word of its own (PCTL_MASK)
     bool rollout_resident = false;
-    bool host_values_due = false;     // an act of this rollout ran a form that leaves the values to ppo_rollout_finish's batched pass (resident / fused)
+    bool bf16_queries = false;        // ppo_set_bf16_queries: the policy queries of a PPO_BF16 handle run bf16_eval_kernel (launch_eval_bf16) instead of being refused
+    bool host_values_due = false;    // an act of this rollout ran a form that leaves the values to ppo_rollout_finish's batched pass (resident / fused)
     float* pin_in_dev = nullptr; float* pin_out_dev = nullptr; unsigned* pin_flag_dev = nullptr;   // the pinned blocks as the device sees them
     // general host-Env path: policy_step_kernel's policy-tower workgroups store their 16 rows of actions into pin_out themselves and raise their
     // word of this pinned table to wg_seq; ppo_rollout_act watches the table (PPO_HIP_NO_DIRECT_ACT=1: D2H copy + stream query as in round 4)
@@ -1090,6 +1091,36 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     return 0;
 }
 
+// the policy queries of a PPO_BF16 handle (ppo_set_bf16_queries): the step's staging and forward on the given rows, then bf16_eval_kernel on the head outputs.
+// More rows than the handle's max_rows (a device-resident rollout) are walked in chunks of at most max_rows: rows are independent, the workspaces stay what a
+// step of max_rows needs.  Writes what ppo_value writes (x0, the tanh outputs, the head outputs).  Not counted in ppo_kernel_counts; profiling class policy_step.
+int launch_eval_bf16(ppo_handle* h, const EvalArgs& a) {
+    const NetDev& n = h->net;
+    if (n.A > 128) return fail(h, "bf16 path: more than 128 actions");
+    const int chunk = h->cfg.max_rows > 0 ? h->cfg.max_rows : 65536;
+    const int Aw = h->Aw;
+    for (int r0 = 0; r0 < a.n; r0 += chunk) {
+        const int rows = std::min(chunk, a.n - r0);
+        if (bf16_ensure_ws(h, rows)) return -1;
+        ProfScope ps(h, PK_STEP);
+        const int Rp = ru(rows, GB_PAD);
+        if (bf16_stage(h, a.obs + (size_t)r0 * n.O, rows, Rp, no_norm_fwd(), nullptr) || bf16_forward(h, Rp)) return -1;
+        EvalArgsB ea{};
+        ea.head[0] = h->bf.head_out[0]; ea.head[1] = h->bf.head_out[1]; ea.ldh = n.Ap; ea.hsplit = h->bf.head_split; ea.hstride = (size_t)h->bf.Rcap * n.Ap; ea.logstd = h->theta + n.ls_off;
+        ea.actions = a.actions ? a.actions + (size_t)r0 * Aw : nullptr; ea.mask = a.mask ? a.mask + (size_t)r0 * n.A : nullptr;
+        ea.value = a.value ? a.value + r0 : nullptr; ea.neglogp = a.neglogp ? a.neglogp + r0 : nullptr; ea.entropy = a.entropy ? a.entropy + r0 : nullptr;
+        ea.params = a.params ? a.params + (size_t)r0 * a.W : nullptr;
+        ea.n = rows; ea.A = n.A; ea.W = a.W;
+        const dim3 grid((rows + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
+        with_head(head_of(h, a.mask != nullptr), [&](auto H) {
+            using Hd = decltype(H);
+            hipLaunchKernelGGL((bf16_eval_kernel<Hd::cat, Hd::mask, Hd::multi>), grid, blk, 0, h->stream, head_args<EvalArgsBM>(H, h, ea));
+        });
+        HIP_OK(h, hipGetLastError());
+    }
+    return 0;
+}
+
 // rows of the epoch-staged observations this minibatch starts at, or -1 when the step stages its own rows
 long bf16_epoch_row(ppo_handle* h, const TrainArgs& ta, int Rp) {
     ppo_handle::Bf16& b = h->bf;
@@ -1300,6 +1331,7 @@ int launch_step(ppo_handle* h, const StepArgs& a0) {
 // the policy queries' launch: policy_eval_kernel of the handle's rung on the generic layout (theta + the small-parameter mirror, which every fp32 handle keeps),
 // also where the step runs the narrow family.  Not counted in ppo_kernel_counts (include/ppo_hip.h); profiling class policy_step.
 int launch_eval(ppo_handle* h, const EvalArgs& a0) {
+    if (h->bf.on) return launch_eval_bf16(h, a0);                   // (a PPO_BF16 handle with ppo_set_bf16_queries on: the callers refuse any other)
     const Head hd = head_of(h, a0.mask != nullptr);
     // a narrow handle's train forms (deferred Adam, the resident epoch) keep theta and the packed image current but not the small-parameter mirror this kernel
     // reads: the first query behind a train step / update brings `par` and thetaT up from theta with one transpose_refresh_kernel launch (derived copies of
@@ -2427,7 +2459,8 @@ int ppo_act_deterministic_masked(ppo_handle* h, const float* obs, int32_t n, con
 int ppo_distribution_width(const ppo_handle* h) { return h ? (h->dist == PPO_ACT_GAUSSIAN ? 2 * h->net.A : h->net.A) : -1; }
 
 static int eval_refuse_bf16(ppo_handle* h, const char* who) {
-    if (h->bf.on) return fail(h, "%s: not supported on a PPO_BF16 handle (its step's neglogp comes out of bf16 GEMMs; the fp32 evaluation kernel would disagree with it)", who);
+    if (h->bf.on && !h->bf16_queries)                               // (ppo_set_bf16_queries: launch_eval_bf16 serves the handle)
+        return fail(h, "%s: not supported on a PPO_BF16 handle (its step's neglogp comes out of bf16 GEMMs; the fp32 evaluation kernel would disagree with it)", who);
     return 0;
 }
 static int ensure_params_staging(ppo_handle* h, size_t floats) {
@@ -2471,7 +2504,13 @@ static int eval_common(ppo_handle* h, const char* who, const float* obs, const f
     float* outs[3] = {value, neglogp, entropy};
     for (int i = 0; i < 3; ++i) if (outs[i]) HIP_OK(h, hipMemcpyAsync(outs[i], h->st_vec[i], (size_t)n * fb, hipMemcpyDeviceToHost, h->stream));
     if (params) HIP_OK(h, hipMemcpyAsync(params, h->st_params, (size_t)n * W * fb, hipMemcpyDeviceToHost, h->stream));
+    if (bf16_chain_err_async(h)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (bf16_chain_err_test(h)) {
+        // a stateless pass: run it again, layer by layer this time (the handle has switched), and keep the finding on stderr -- as step_common does
+        fprintf(stderr, "libppo_hip: %s -- the pass was repeated with a launch per layer\n", h->err.c_str());
+        return eval_common(h, who, obs, actions, n, mask, value, neglogp, entropy, params);
+    }
     prof_collect(h);
     return 0;
 }
@@ -2511,7 +2550,12 @@ int ppo_rollout_evaluate(ppo_handle* h, float* value, float* neglogp, float* ent
     if (launch_eval(h, a)) return -1;
     float* outs[3] = {value, neglogp, entropy};
     for (int i = 0; i < 3; ++i) if (outs[i]) HIP_OK(h, hipMemcpyAsync(outs[i], h->ev_out[i], (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (bf16_chain_err_async(h)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (bf16_chain_err_test(h)) {                                   // (eval_common)
+        fprintf(stderr, "libppo_hip: %s -- the pass was repeated with a launch per layer\n", h->err.c_str());
+        return ppo_rollout_evaluate(h, value, neglogp, entropy);
+    }
     prof_collect(h);
     return 0;
 }
@@ -2910,6 +2954,14 @@ int ppo_set_host_step_fused(ppo_handle* h, int32_t on) {
     return 0;
 }
 int ppo_host_step_fused(const ppo_handle* h) { return h && h->host_step_fused ? 1 : 0; }
+
+// The policy queries of a PPO_BF16 handle (bf16_eval_kernel) are opt-in per handle: host state only, nothing on the device is touched and nothing is dropped.
+int ppo_set_bf16_queries(ppo_handle* h, int32_t on) {
+    if (!h) return fail(nullptr, "ppo_set_bf16_queries: null handle");
+    h->bf16_queries = on != 0;
+    return 0;
+}
+int ppo_bf16_queries(const ppo_handle* h) { return h && h->bf16_queries ? 1 : 0; }
 
 // The resident rollout of a narrow discrete handle (resident_discrete).  As above: any handle accepts the call, and only a narrow discrete one drops its rollout.
 int ppo_set_rollout_resident(ppo_handle* h, int32_t on) {

@@ -56,6 +56,8 @@ public:
         check(ppo_action_probability(h_, obs.data(), n, mask ? mask->data() : nullptr, p.data(), (int64_t)n * W), "proba_step");
         return p;
     }
+    // evaluate_actions / proba_step behind a PPO_BF16 handle: refused by default, served by the bf16 evaluation kernel once this is on (ppo_set_bf16_queries)
+    virtual void set_bf16_queries(bool on) { check(ppo_set_bf16_queries(h_, on ? 1 : 0), "set_bf16_queries"); }
     // Runner::set_returns' GAE scan (runner.hpp:159-191) on the device; [T,E] time-major
     virtual void gae(const Mat& rewards, const Mat& values, const Mat& dones, const Mat& last_values, const Mat& last_dones, float gamma,
                      float lam, Mat& returns) {

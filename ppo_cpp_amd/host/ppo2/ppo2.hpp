@@ -245,6 +245,9 @@ public:
         return logp ? -nlp : nlp.unary([](float x) { return std::exp(-x); });
     }
 
+    // action_probability behind a PPO_BF16 handle (MlpPolicy::set_bf16_queries; the act and the train model share the handle)
+    void set_bf16_queries(bool on) { act_model_.set_bf16_queries(on); }
+
     // save cadence of the reference (ppo2.hpp:256-262, 361-376): a save every ceil(n_updates / num_saves) updates with
     // ids 0, 1, ..., plus a trailing save when the interval does not divide the number of updates
     void learn(int total_timesteps, int num_saves = 0, const std::string& save_path = "") {
