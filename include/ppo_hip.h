@@ -219,18 +219,18 @@ int ppo_action_width(const ppo_handle* h);
  *     literal relu / abs expression) differentiates the kinks to 0 and gives another value there.
  *   Surrogate, value loss, approxkl and clipfrac see the row's neglogp unchanged.  float32 against float64 at 4096 x 18 logits: neglogp within 3.0e-6 abs at a spread
  *   of +-1.5, 9e-7 at +-40, 5e-7 at +-120; entropy within 3.0e-6 / 5e-7 / 2e-7; nothing overflows.
- *   Without PPO_ACT_BINARY_SHAPE_KERNELS or PPO_ACT_BINARY_PAIR_KERNELS (below) the handle runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts,
+ *   Without PPO_ACT_BINARY_SHAPE_KERNELS, PPO_ACT_BINARY_PAIR_KERNELS or PPO_ACT_BF16_BINARY_HEAD (below) the handle runs the generic fp32 family ("policy_step_kernel<mbin>" / "train_fwd_bwd_kernel<mbin>" in ppo_kernel_counts,
  *   instead of the plain names) on any hidden widths: never narrow, never train8_kernel, deferred Adam, the resident epoch kernel or a one-launch rollout -- the rules
  *   of an unflagged categorical handle.
  *   PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS and PPO_ACT_BF16_HEAD beside it on a PPO_F32 handle are accepted and change nothing (same bits, same counts).
  *   Every entry point of a categorical PPO_F32 handle works, actions [., A]; data parallel (ppo_dist_init, both shuffles) included.
  *   Host checks before anything is uploaded: every action of ppo_train_step / ppo_rollout_upload field 1 is exactly 0 or 1 (the message names row and column; NaN is
  *   refused); the masked entry points and ppo_set_action_masking refuse the handle ("action masks need a categorical ...").
- *   Errors of ppo_create_ex, each naming the limit: act_dim < 1; compute_dtype PPO_BF16.  2 stays an "unknown action_dist" error, as does 3 with an unknown flag bit.
+ *   Errors of ppo_create_ex, each naming the limit: act_dim < 1; compute_dtype PPO_BF16 without PPO_ACT_BF16_BINARY_HEAD.  2 stays an "unknown action_dist" error, as does 3 with an unknown flag bit.
  *   Measured on an MI355X (us of device time per call at 18 obs, hidden [256,256]; this head | a categorical handle of 18 categories | a
  *   multi-categorical one with nvec = (2,) x 16): policy step 16.6 | 16.5 | 29.1 at 16 rows, 17.6 | 18.6 | 29.7 at 1024; train_fwd_bwd_kernel 25.5 | 24.3 | 39.4 at 64 rows,
  *   26.6 | 26.0 | 40.4 at 2048.  The elementwise head is about 1 us SLOWER than <cat> per train launch; it has not been tuned.
- *   Out of scope for this head: the bf16 path, the fused host step and the resident rollouts, action masks.
+ *   Out of scope for this head: the fused host step and the resident rollouts, action masks.
  *   PPO_ACT_BINARY_SHAPE_KERNELS  PPO_ACT_MULTI_BINARY | PPO_ACT_BINARY_SHAPE_KERNELS lets a multi-binary PPO_F32 handle take the narrow LDS-resident family's step and
  *                        train kernels under the rule of a flagged categorical handle: at most 4 hidden layers, every padded hidden width <= 64, padded
  *                        observation and action widths <= 64, the plain LDS image within 160 KB, PPO_HIP_NO_NARROW unset.  (A flag of its own: PPO_ACT_SHAPE_KERNELS
@@ -261,10 +261,36 @@ int ppo_action_width(const ppo_handle* h);
  *                        "unknown action_dist" error, whose text names it; ppo_create_multi_ex refuses it with its own "unknown flag bit 0x4000".
  *                        Measured on an MI355X at (18 obs, 18 bits, [256,256]) against the unflagged handle of the same run (us of device
  *                        time per call): train step 40.3 against 49.5 at 64 rows, 49.6 against 57.2 at 2048; the policy step runs the same kernel (16.8 | 16.5 at
- *                        16 rows, 18.0 | 17.8 at 1024). */
+ *                        16 rows, 18.0 | 17.8 at 1024).
+ *   PPO_ACT_BF16_BINARY_HEAD  PPO_ACT_MULTI_BINARY | PPO_ACT_BF16_BINARY_HEAD with compute_dtype PPO_BF16 creates the handle on the bf16 path (wide nets): staging, the
+ *                        hidden-layer GEMMs, bf16_heads_kernel, the backward chain, the weight-gradient GEMM and assembly + clip + Adam of every PPO_BF16 handle,
+ *                        the head in bf16_sample_kernel<mbin> / bf16_loss_kernel<mbin>: one wave per row, lane l owns bits l and l + 64 (act_dim <= 128; more is an
+ *                        error that names the limit), the logits the head GEMM's fp32 partial products added in range order, the generic <mbin> kernels' arithmetic
+ *                        per element (exp and log1p once per element) and their counter keys: the same seed draws what policy_step_kernel<mbin> draws wherever u
+ *                        is not within rounding of p.  The row's neglogp and entropy are reduced in one shape in every kernel: the act model's neglogp is the train
+ *                        model's, bit for bit.  d logits go where d mu goes, padding columns and dead rows exactly +0, the aux words zeros, the padded logstd region
+ *                        never moved.  (A flag of its own: PPO_ACT_BF16_HEAD on this head is accepted and changes nothing, and stays so.)  With PPO_F32 the flag is
+ *                        accepted and changes nothing (same bits, same counts); beside it on a PPO_BF16 handle PPO_ACT_BINARY_SHAPE_KERNELS,
+ *                        PPO_ACT_BINARY_PAIR_KERNELS, PPO_ACT_SHAPE_KERNELS and PPO_ACT_PAIR_KERNELS are accepted and ignored.  Every entry point of a multi-binary
+ *                        handle works (step, deterministic act, value, train step, the rollout calls on the device env and behind a host Env, ppo_collect_synthetic,
+ *                        ppo_update with kernel nodes only, ppo_get_last_grad, tensors and checkpoints -- an fp32 multi-binary handle's -- the truncation
+ *                        bootstrap, the 0 / 1 action checks); PPO_HIP_NO_BF16_CHAIN / PPO_HIP_NO_REDUCE_ADAM act as on every PPO_BF16 handle.  Refused, each leaving
+ *                        the handle usable: action masks (the multi-binary messages), ppo_set_target_kl (the PPO_BF16 message), ppo_dist_init ("ppo_dist_init: data
+ *                        parallel is not supported for a multi-binary PPO_BF16 handle created with PPO_ACT_BF16_BINARY_HEAD").  The policy queries are refused by
+ *                        default and served by bf16_eval_kernel<mbin> after ppo_set_bf16_queries(h, 1): parameters P(bit = 1), ppo_distribution_width = A,
+ *                        ppo_evaluate_actions returns ppo_step's value and neglogp bits for the action ppo_step drew, ppo_rollout_evaluate walks in chunks.
+ *                        Counted under "bf16_step_sequence<mbin>" / "bf16_train_sequence<mbin>" INSTEAD of the plain names -- names of ppo_kernel_count /
+ *                        ppo_kernel_variant_name only; ppo_kernel_counts keeps its 60 rows, ppo_kernel_counts_all its 62.  With any other distribution the bit is
+ *                        an "unknown action_dist" error, whose text names it; ppo_create_multi_ex refuses it with its own "unknown flag bit 0x8000".
+ *                        Measured on an MI355X at 256 observations, [1024,1024,1024], 64 bits (us of device time per call; this handle |
+ *                        the generic fp32 <mbin> handle | the Gaussian PPO_BF16 handle): train step 233.6 | 1317.0 | 234.3 at 4096 rows, 165.3 | 555.7 | 164.1
+ *                        at 256; policy step 140.2 | 853.5 | 139.9 at 8192 rows.  A second run of the same tool: 233.4 | 1316.6 | 229.3, 165.6 | 539.9 | 162.6,
+ *                        140.6 | 850.4 | 137.1.  Against the Gaussian head forms the two runs disagree: equal within the rounds' spread in the first, 3.0 - 4.1 us
+ *                        slower (1.8 - 2.5 %, outside the spread) in the second.  Not resolved; the head has not been tuned. */
 #define PPO_ACT_MULTI_BINARY 3
 #define PPO_ACT_BINARY_SHAPE_KERNELS 0x2000
 #define PPO_ACT_BINARY_PAIR_KERNELS 0x4000
+#define PPO_ACT_BF16_BINARY_HEAD 0x8000
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);

@@ -66,6 +66,7 @@ ACT_PAIR_KERNELS = 0x400                                # PPO_ACT_PAIR_KERNELS, 
 ACT_BF16_MULTI_HEAD = 0x1000                            # PPO_ACT_BF16_MULTI_HEAD, a flag of ppo_create_multi_ex only
 ACT_BINARY_SHAPE_KERNELS = 0x2000                       # PPO_ACT_BINARY_SHAPE_KERNELS, a flag of ppo_create_ex beside PPO_ACT_MULTI_BINARY only
 ACT_BINARY_PAIR_KERNELS = 0x4000                        # PPO_ACT_BINARY_PAIR_KERNELS, likewise
+ACT_BF16_BINARY_HEAD = 0x8000                           # PPO_ACT_BF16_BINARY_HEAD, likewise
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -103,8 +104,8 @@ class PPOHip:
     action_dist="multi_binary" (PPO_ACT_MULTI_BINARY; stable-baselines' Bernoulli distribution over a MultiBinary space -- "bernoulli" is no action_dist here):
     act_dim independent on / off decisions per step.  Actions are (n, act_dim) float arrays of exactly 0 or 1 (train_step and rollout_set("actions") refuse anything
     else, naming row and column); explicit noise is (n, act_dim) uniforms, bit j is 1 where u_j < sigmoid(logit_j); act_deterministic gives logit_j > 0.  The tensor
-    list is a categorical handle's (no pi/logstd), `.nvec` is [].  compute_dtype=0 only; the handle runs policy_step_kernel<mbin> / train_fwd_bwd_kernel<mbin> on any
-    hidden widths, shape_kernels / pair_kernels / bf16_head are accepted and change nothing, and mask= raises the library's error.
+    list is a categorical handle's (no pi/logstd), `.nvec` is [].  compute_dtype=0 unless binary_bf16_head is given; the handle runs policy_step_kernel<mbin> /
+    train_fwd_bwd_kernel<mbin> on any hidden widths, shape_kernels / pair_kernels / bf16_head are accepted and change nothing, and mask= raises the library's error.
     binary_shape_kernels=True with it (PPO_ACT_BINARY_SHAPE_KERNELS; default False; a ValueError with any other action_dist): a handle whose shape qualifies
     (every hidden width <= 64, at most 64 observations and bits, ...) runs narrow_step_kernel<mbin> / narrow_train_kernel<mbin> -- same arithmetic, the same draws for
     the same seed, no data parallel; set_host_step_fused / set_rollout_resident change nothing on it; any other shape runs the generic <mbin> kernels.  The two names
@@ -113,6 +114,12 @@ class PPOHip:
     most 64 observations and bits trains with train8_kernel<mbin> + weight_grad_assemble_kernel -- the act side stays policy_step_kernel<mbin> (same bits), no data
     parallel; any other shape runs the generic <mbin> kernels.  "train8_kernel<mbin>" is a name of kernel_count() / kernel_variants() only.  The attribute
     binary_pair_kernels keeps what was asked for.
+    binary_bf16_head=True with it and compute_dtype=1 (PPO_ACT_BF16_BINARY_HEAD; default False; a ValueError with any other action_dist): the bf16 matrix-core path
+    with the multi-binary head (bf16_sample_kernel / bf16_loss_kernel / bf16_eval_kernel<mbin>; at most 128 bits; no masks, no data parallel, no set_target_kl; the
+    policy queries after set_bf16_queries(True)), e.g. PPOHip(O, A, hidden, action_dist="multi_binary", compute_dtype=1, binary_bf16_head=True).  Without it that
+    combination is refused; on a compute_dtype=0 handle it changes nothing (same bits, same counts); the other four kernel flags beside it on a compute_dtype=1
+    handle are ignored.  "bf16_step_sequence<mbin>" / "bf16_train_sequence<mbin>" are names of kernel_count() / kernel_variants() only.  The attribute
+    binary_bf16_head keeps what was asked for.
 
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -123,12 +130,14 @@ class PPOHip:
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, binary_shape_kernels=False,
-                 binary_pair_kernels=False, **overrides):
+                 binary_pair_kernels=False, binary_bf16_head=False, **overrides):
         multi = action_dist == "multi_categorical"
         if binary_shape_kernels and action_dist != "multi_binary":
             raise ValueError("binary_shape_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if binary_pair_kernels and action_dist != "multi_binary":
             raise ValueError("binary_pair_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
+        if binary_bf16_head and action_dist != "multi_binary":
+            raise ValueError("binary_bf16_head belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if nvec is not None and not multi:
             raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
         if multi:
@@ -156,6 +165,7 @@ class PPOHip:
         self.pair_kernels = bool(pair_kernels)
         self.binary_shape_kernels = bool(binary_shape_kernels)
         self.binary_pair_kernels = bool(binary_pair_kernels)
+        self.binary_bf16_head = bool(binary_bf16_head)
         self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
@@ -168,7 +178,7 @@ class PPOHip:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())
         elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)
                                     | (ACT_PAIR_KERNELS if pair_kernels else 0) | (ACT_BINARY_SHAPE_KERNELS if binary_shape_kernels else 0)
-                                    | (ACT_BINARY_PAIR_KERNELS if binary_pair_kernels else 0), C.byref(h)) != 0:
+                                    | (ACT_BINARY_PAIR_KERNELS if binary_pair_kernels else 0) | (ACT_BF16_BINARY_HEAD if binary_bf16_head else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)

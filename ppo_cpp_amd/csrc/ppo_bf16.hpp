@@ -943,6 +943,77 @@ __global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(std::conditio
     }
 }
 
+// ---- multi-binary head (PPO_ACT_MULTI_BINARY | PPO_ACT_BF16_BINARY_HEAD): bern_* of ppo_head.hpp in the geometry of this family -- one wave per row, lane l owns bits l and
+// l + 64 (A <= 128), the logits the head GEMM's partial products added in range order.  Elementwise: no maximum, no argmax, no component walk, no mask.
+// Kernels of their own under the family's names -- overloads with a head TYPE on the Gaussian arguments under a type of their own, the way policy_step_kernel<.., MbinHead>
+// is one -- so the Gaussian and categorical instantiations keep symbol, kernarg layout and machine code (a fourth bool would rename all of them).
+// All three are compiled without packed fp32 instructions (a target attribute of the kernel alone), hence the <.., INL = true> wave helpers.
+#ifdef __HIP_DEVICE_COMPILE__
+#define BF16_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define BF16_NO_PACKED_F32                                   // (the host pass does not know the feature)
+#endif
+// The lane's partial products of head element idx, all requested before the first is used, and their sum in range order: head_sum's bits
+__device__ __forceinline__ void head_parts(float (&p)[GB_HEAD_SPLIT], const float* f, size_t idx, int hsplit, size_t hstride, bool want) {
+#pragma unroll
+    for (int k = 0; k < GB_HEAD_SPLIT; ++k) p[k] = (want && k < hsplit) ? f[idx + (size_t)k * hstride] : 0.f;
+}
+__device__ __forceinline__ float head_parts_sum(const float (&p)[GB_HEAD_SPLIT], int hsplit) {
+    float s = p[0];
+#pragma unroll
+    for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < hsplit) s += p[k];
+    return s;
+}
+// The row's sums -- neglogp, and the entropy where a kernel has it -- in ONE shape in all three kernels: each lane adds its element e = 0, then e = 1 (a lane
+// without the element adds nothing), then one 64-lane butterfly, steps 32 .. 1, the sums interleaved.  bern_row_add is an element's share; bf16_sample_kernel's,
+// bf16_loss_kernel's and bf16_eval_kernel's neglogp are then the same bits on the same logits and bits.
+__device__ __forceinline__ void bern_row_add(BernParts b, float l, float x, float& snlp, float& sent) {
+    snlp += bern_nlp_elem(b, l, x);
+    sent += bern_entropy_elem(b, l);
+}
+__device__ __forceinline__ void bern_row_sums(float& snlp, float& sent) {
+    for (int o = 32; o > 0; o >>= 1) { snlp += wave_xor<true>(snlp, o); sent += wave_xor<true>(sent, o); }
+}
+
+// act epilogue: `noise` holds the uniforms u [n, A] (null: ctr_uniform under the categorical head's keys, what policy_step_kernel<mbin> draws), x_j = u_j < sigmoid(l_j),
+// det_action_j = l_j > 0; action / det_action are [n, A] floats of exactly 0 or 1.  No LDS, no barrier: a dead row's wave returns at once.  Every load of the lane
+// goes out first: the partial products of its two logits and (lane 0) of the value, its uniforms.
+using SampleArgsBB = BinArgs<SampleArgsB>;
+template <class HEAD>
+__global__ BF16_NO_PACKED_F32 __launch_bounds__(64 * BS_ROWS) void bf16_sample_kernel(SampleArgsBB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    float hp[2][GB_HEAD_SPLIT], vp[GB_HEAD_SPLIT], u[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = lane + 64 * e;
+        head_parts(hp[e], a.head[0], (size_t)row * a.ldh + j, a.hsplit, a.hstride, j < a.A);
+        u[e] = 0.5f;
+        if (j < a.A) u[e] = a.noise ? a.noise[(size_t)row * a.A + j] : ctr_uniform(a.seed, a.row_base + row, a.rng_step, j);
+    }
+    head_parts(vp, a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride, lane == 0 && a.value);
+    float snlp = 0.f, sent = 0.f;                            // (the entropy is not stored here: the compiler drops its sum)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = lane + 64 * e;
+        if (j < a.A) {
+            const float l = head_parts_sum(hp[e], a.hsplit);
+            const BernParts b = bern_parts(l);
+            const float x = bern_sample(b.p, u[e]);
+            bern_row_add(b, l, x, snlp, sent);
+            if (a.action) a.action[(size_t)row * a.A + j] = x;
+            if (a.det_action) a.det_action[(size_t)row * a.A + j] = bern_mode(l);
+        }
+    }
+    bern_row_sums(snlp, sent);
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = snlp;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.hsplit);
+    }
+}
+
 // ---- policy query on a PPO_BF16 handle (ppo_evaluate_actions, ppo_action_probability, ppo_rollout_evaluate behind ppo_set_bf16_queries): the head outputs of a
 // forward pass and GIVEN actions -> value, neglogp, entropy and the distribution's parameters, each stored only where its pointer is non-null.  No draw: the step's
 // epilogue with the given action where that kernel has the drawn one, so the action ppo_step sampled gets ppo_step's neglogp bit for bit -------------------------
@@ -957,19 +1028,7 @@ struct EvalArgsB {
 };
 struct EvalArgsBM : EvalArgsB { CompTable comp; };
 
-// the lane's partial products of head element idx, all requested before the first is used ...
-__device__ __forceinline__ void head_parts(float (&p)[GB_HEAD_SPLIT], const float* f, size_t idx, int hsplit, size_t hstride, bool want) {
-#pragma unroll
-    for (int k = 0; k < GB_HEAD_SPLIT; ++k) p[k] = (want && k < hsplit) ? f[idx + (size_t)k * hstride] : 0.f;
-}
-// ... and their sum in range order: head_sum's bits
-__device__ __forceinline__ float head_parts_sum(const float (&p)[GB_HEAD_SPLIT], int hsplit) {
-    float s = p[0];
-#pragma unroll
-    for (int k = 1; k < GB_HEAD_SPLIT; ++k) if (k < hsplit) s += p[k];
-    return s;
-}
-
+// (head_parts / head_parts_sum: above, in front of bf16_sample_kernel<mbin>)
 // bf16_sample_kernel's geometry: one wave per row, BS_ROWS rows per block, lane l owns elements l and l + 64 (A <= 128), no LDS, no barrier; a dead row's wave
 // returns at once.  Every load of the lane goes out first: the partial products of its two elements and (lane 0) of the value, its mask entries, its action value(s).
 // Gaussian: z = (act - mu) / sigma, the two row sums and their butterfly as bf16_sample_kernel writes them out, then gauss_nlp; the entropy's terms
@@ -979,12 +1038,7 @@ __device__ __forceinline__ float head_parts_sum(const float (&p)[GB_HEAD_SPLIT],
 // indexes anything.  Per component: cat_row_norm over the allowed set, neglogp log z - la, the entropy terms of bf16_loss_kernel<CAT> (cat_entropy_term over the allowed
 // elements, one butterfly), p_j = ex_j / z into params, exactly +0 for a forbidden category.  neglogp and entropy: the components' in component order, starting from
 // the first one's value.  A row of ones as mask: the unmasked bits.
-// Compiled without packed fp32 instructions (a target attribute of this kernel alone); hence the <.., INL = true> wave helpers.
-#ifdef __HIP_DEVICE_COMPILE__
-#define BF16_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define BF16_NO_PACKED_F32                                   // (the host pass does not know the feature)
-#endif
+// Compiled without packed fp32 instructions (BF16_NO_PACKED_F32, above: a target attribute of the kernel alone); hence the <.., INL = true> wave helpers.
 template <bool CAT = false, bool MASK = false, bool MULTI = false>
 __global__ BF16_NO_PACKED_F32 __launch_bounds__(64 * BS_ROWS) void bf16_eval_kernel(std::conditional_t<MULTI, EvalArgsBM, EvalArgsB> a) {
     static_assert(CAT || !MASK, "action masks belong to the categorical head");
@@ -1068,6 +1122,43 @@ __global__ BF16_NO_PACKED_F32 __launch_bounds__(64 * BS_ROWS) void bf16_eval_ker
     if (lane == 0) {
         if (a.neglogp) a.neglogp[row] = nlp;
         if (a.entropy) a.entropy[row] = ent;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.hsplit);
+    }
+}
+
+// the multi-binary form: bf16_sample_kernel<mbin>'s loads, elements and row sums with the GIVEN bits where that kernel has the drawn ones (without actions: the
+// deterministic ones), so the action ppo_step drew gets ppo_step's neglogp bit for bit; entropy = the sum of bern_entropy_elem, params [n, A] = P(bit = 1).
+using EvalArgsBB = BinArgs<EvalArgsB>;
+template <class HEAD>
+__global__ BF16_NO_PACKED_F32 __launch_bounds__(64 * BS_ROWS) void bf16_eval_kernel(EvalArgsBB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    const bool given = a.actions != nullptr;
+    float hp[2][GB_HEAD_SPLIT], vp[GB_HEAD_SPLIT], act_[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = lane + 64 * e;
+        head_parts(hp[e], a.head[0], (size_t)row * a.ldh + j, a.hsplit, a.hstride, j < a.A);
+        act_[e] = (given && j < a.A) ? a.actions[(size_t)row * a.A + j] : 0.f;
+    }
+    head_parts(vp, a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride, lane == 0 && a.value);
+    float snlp = 0.f, sent = 0.f;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = lane + 64 * e;
+        if (j < a.A) {
+            const float l = head_parts_sum(hp[e], a.hsplit);
+            const BernParts b = bern_parts(l);
+            bern_row_add(b, l, given ? act_[e] : bern_mode(l), snlp, sent);
+            if (a.params) a.params[(size_t)row * a.W + j] = b.p;
+        }
+    }
+    bern_row_sums(snlp, sent);
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = snlp;
+        if (a.entropy) a.entropy[row] = sent;
         if (a.value) a.value[row] = head_parts_sum(vp, a.hsplit);
     }
 }
@@ -1249,6 +1340,86 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(std::conditiona
     float* s0 = a.slots[0] + (size_t)blockIdx.x * a.slot_w;
     float* s1 = a.slots[1] + (size_t)blockIdx.x * a.slot_w;
     for (int j = tid; j < 2 * a.Ap; j += 64 * BL_ROWS) {      // threads [0, Ap): db_mu, [Ap, 2 Ap): dlogstd -- fp32 sums of the fp32 values, not of their bf16 roundings
+        const float* src = j < a.Ap ? dmu_s + j : dls_s + (j - a.Ap);
+        float sb = 0.f;
+#pragma unroll
+        for (int q = 0; q < BL_ROWS; ++q) sb += src[q * a.Ap];
+        if (j < a.Ap) s0[a.slot_head + j] = sb; else s0[a.slot_aux + j - a.Ap] = sb;
+    }
+    if (tid >= 64 * BL_ROWS - 64 && tid < 64 * BL_ROWS - 60) { const int k = tid - (64 * BL_ROWS - 64); float s = 0.f; for (int q = 0; q < BL_ROWS; ++q) s += pt[q * 4 + k]; s0[a.slot_loss + k] = s; }
+    if (tid == 64 * BL_ROWS - 32) { float sb = 0.f, sl = 0.f; for (int q = 0; q < BL_ROWS; ++q) { sb += vt[q * 2]; sl += vt[q * 2 + 1]; } s1[a.slot_head] = sb; s1[a.slot_loss] = sl; }
+}
+
+// the multi-binary form (bf16_sample_kernel<mbin>, above, says why it is a kernel of its own).  `actions` holds A floats per row, each exactly 0 or 1 (the host checks).
+// bern_parts is formed ONCE per element and serves neglogp, entropy and gradient: one exp and one log1p per element.  The row's two sums take bf16_sample_kernel<mbin>'s
+// shape (bern_row_add, bern_row_sums): the act model's neglogp is the train model's, bit for bit.  d logits (bern_grad_elem) go where d mu goes -- fp32 into the LDS tile,
+// bf16 to dhead[0] -- padding columns A <= j < Ap and dead rows get exactly +0; the aux (d logstd) tile and with it the aux slot words are zeros; pt[1] is the row's
+// Bernoulli entropy.  LDS layout, surrogate, value tower and slot epilogue: bf16_loss_kernel's statements.
+using LossArgsBB = BinArgs<LossArgsB>;
+template <class HEAD>
+__global__ BF16_NO_PACKED_F32 __launch_bounds__(64 * BL_ROWS) void bf16_loss_kernel(LossArgsBB a) {
+    static_assert(std::is_same_v<HEAD, MbinHead>, "the overload with a head TYPE is the multi-binary head's");
+    extern __shared__ __attribute__((aligned(16))) float ls[];      // [R][Ap] d logits | [R][Ap] zeros (d logstd) | [R][4] pi terms | [R][2] vf terms
+    float* dmu_s = ls; float* dls_s = ls + BL_ROWS * a.Ap; float* pt = dls_s + BL_ROWS * a.Ap; float* vt = pt + 4 * BL_ROWS;
+    const int tid = threadIdx.x, r = tid >> 6, lane = tid & 63;
+    const int row = blockIdx.x * BL_ROWS + r;
+    const bool live = row < a.n;
+    const float cr = a.hyper[1];
+    const float vcr = a.hyper[2];                   // the value tower's clip range and switch (vf_loss_row)
+    const float voff = a.hyper[3];
+    const float g = a.inv_n;
+    // every load of the lane first: head partials, action bits, the row scalars (a dead row of the last block reads its own padded head row and nothing else)
+    float hp[BL_EPT][GB_HEAD_SPLIT], vp[GB_HEAD_SPLIT], x[BL_EPT];
+#pragma unroll
+    for (int e = 0; e < BL_EPT; ++e) {
+        const int j = lane + 64 * e;
+        head_parts(hp[e], a.head[0], (size_t)row * a.ldh + j, a.hsplit, a.hstride, j < a.A);
+        x[e] = (j < a.A && live) ? a.actions[(size_t)row * a.A + j] : 0.f;
+    }
+    head_parts(vp, a.head[1], (size_t)row * a.ldh, a.hsplit, a.hstride, lane == 0 && live);
+    const float adv = live ? a.advs[row] : 0.f;
+    const float old_nlp_in = live ? a.old_neglogp[row] : 0.f;
+    float Rv = 0.f, vo = 0.f;
+    if (lane == 0 && live) { Rv = a.returns[row]; vo = a.old_values[row]; }
+    // policy tower
+    float lg[BL_EPT];
+    BernParts bp[BL_EPT];
+    float nlp = 0.f, sent = 0.f;
+#pragma unroll
+    for (int e = 0; e < BL_EPT; ++e) {
+        const int j = lane + 64 * e;
+        lg[e] = live ? head_parts_sum(hp[e], a.hsplit) : 0.f;
+        bp[e] = bern_parts(lg[e]);
+        if (j < a.A) bern_row_add(bp[e], lg[e], x[e], nlp, sent);
+    }
+    bern_row_sums(nlp, sent);
+    const float old_nlp = live ? old_nlp_in : nlp;
+    const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
+    const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
+    if (lane == 0) {
+        surrogate_terms(sr, nlp, old_nlp, sent, cr, live, pt, r);
+    }
+#pragma unroll
+    for (int e = 0; e < BL_EPT; ++e) {
+        const int j = lane + 64 * e;
+        if (j < a.Ap) {
+            float dmu = 0.f;
+            if (j < a.A && live) dmu = bern_grad_elem(d_nlp, bp[e], lg[e], x[e], a.ent_coef, g);
+            dmu_s[r * a.Ap + j] = dmu; dls_s[r * a.Ap + j] = 0.f;
+            a.dhead[0][(size_t)row * a.Ap + j] = (bf16_t)dmu;
+        }
+    }
+    // value tower (G:10213-10837, G:14975-19571)
+    if (lane == 0) {
+        float dv = 0.f, lossv = 0.f;
+        if (live) vf_loss_row(head_parts_sum(vp, a.hsplit), Rv, vo, vcr, voff, a.vf_coef * 0.5f * a.inv_n, lossv, dv);
+        vt[r * 2] = dv; vt[r * 2 + 1] = lossv;
+        a.dhead[1][(size_t)row * a.Ap] = (bf16_t)dv;
+    }
+    lds_barrier();                                  // (only LDS crosses it; the header's __syncthreads is a call under this kernel's target attribute)
+    float* s0 = a.slots[0] + (size_t)blockIdx.x * a.slot_w;
+    float* s1 = a.slots[1] + (size_t)blockIdx.x * a.slot_w;
+    for (int j = tid; j < 2 * a.Ap; j += 64 * BL_ROWS) {      // threads [0, Ap): db_pi, [Ap, 2 Ap): the aux words -- fp32 sums of the fp32 values, not of their bf16 roundings
         const float* src = j < a.Ap ? dmu_s + j : dls_s + (j - a.Ap);
         float sb = 0.f;
 #pragma unroll

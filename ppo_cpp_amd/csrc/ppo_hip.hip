@@ -71,7 +71,7 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
                      KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
                      KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
-                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_COUNT };
+                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_BF16_STEP_MBIN, KV_BF16_TRAIN_MBIN, KV_TOTAL };
 // ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all,
 // which is FROZEN in turn at the first KV_ALL_COUNT rows (a caller asserts that count too).  Every variant, later ones included, is reached by name through
 // ppo_kernel_count and enumerated by ppo_kernel_variant_name: no caller may hold THAT list's length.
@@ -79,8 +79,13 @@ constexpr int KV_LEGACY_COUNT = 60;
 constexpr int KV_ALL_COUNT = 62;
 static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
 static_assert(KV_ALL_COUNT == KV_TRAIN8_MBIN, "the rows of ppo_kernel_counts_all end where the first variant named after it begins");
+// The variant list (KV_TOTAL = 65 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
+// hands out one name at a time, and ppo_host_learn_binary's walk stops at its callers' 64 entries itself (it ends one name short of the list).
+// KV_COUNT below is FROZEN at the 63 names in front of the bf16 <mbin> pair, and the assertion on it can no longer fail: it constrains nothing.  It stands only because
+// tests/test_multi_binary.py::test_source_names_the_head_in_every_layer looks for this line of text; when that test's pin is updated, both lines go.
+constexpr int KV_COUNT = KV_TRAIN8_MBIN + 1;
 static_assert(KV_COUNT <= 64, "the callers' buffers for ppo_kernel_counts hold 64 entries (capi.py, hostapi.py, ppo_host_explicit)");
-const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
+const char* kVariantNames[KV_TOTAL] = {"train8_kernel", "train_fwd_bwd_kernel", "weight_grad_assemble_kernel", "weight_grad_kernel", "grad_reduce_kernel",
                                        "narrow_train_kernel<static>", "narrow_train_kernel<runtime>", "narrow_step_kernel<static>", "narrow_step_kernel<runtime>",
                                        "policy_step_kernel", "narrow_rollout1_kernel", "narrow_rollout_kernel", "narrow_rollout_coop_kernel", "narrow_collect_kernel",
                                        "bf16_train_sequence", "bf16_step_sequence", "bf16_reduce_adam_kernel", "narrow_epoch_kernel",
@@ -116,7 +121,10 @@ const char* kVariantNames[KV_COUNT] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "narrow_step_kernel<mbin>", "narrow_train_kernel<mbin>",
                                        // a multi-binary handle created with PPO_ACT_BINARY_PAIR_KERNELS on a [256,256] shape (the early-stopping form counts under the same
                                        // name): counted INSTEAD of "train_fwd_bwd_kernel<mbin>"; ppo_kernel_count / ppo_kernel_variant_name only
-                                       "train8_kernel<mbin>"};
+                                       "train8_kernel<mbin>",
+                                       // a multi-binary PPO_BF16 handle (ppo_create_ex with PPO_ACT_BF16_BINARY_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence";
+                                       // ppo_kernel_count / ppo_kernel_variant_name only
+                                       "bf16_step_sequence<mbin>", "bf16_train_sequence<mbin>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -124,9 +132,9 @@ struct Head {
     int index() const { return bin ? 5 : multi ? 3 + mask : cat ? 1 + mask : 0; }
 };
 // which entry a launch of a kernel family with a head bumps: a row per family, a column per head form.  (The narrow Gaussian entries say whether the compile-time
-// shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.  KV_COUNT: the family
+// shape ran: a row each.  The Gaussian host step is not counted.  train8_kernel against train_fwd_bwd_kernel is enqueue_train_fb's decision.  KV_TOTAL: the family
 // has no kernel of that head, and no handle of that head reaches it -- a multi-binary handle runs the generic fp32 family, with PPO_ACT_BINARY_SHAPE_KERNELS the narrow
-// step / train kernels, with PPO_ACT_BINARY_PAIR_KERNELS train8_kernel, nothing else.)
+// step / train kernels, with PPO_ACT_BINARY_PAIR_KERNELS train8_kernel, with PPO_ACT_BF16_BINARY_HEAD and PPO_BF16 the bf16 sequences, nothing else.)
 enum HeadFamily { KF_POLICY_STEP = 0, KF_TRAIN_FB, KF_TRAIN8, KF_NARROW_STEP_STATIC, KF_NARROW_STEP, KF_NARROW_TRAIN_STATIC, KF_NARROW_TRAIN, KF_NARROW_HOST_STEP, KF_BF16_STEP,
                   KF_BF16_TRAIN, KF_NARROW_ROLLOUT, KF_COUNT };
 constexpr KernelVariant kHeadVariant[KF_COUNT][6] = {
@@ -137,10 +145,10 @@ constexpr KernelVariant kHeadVariant[KF_COUNT][6] = {
     {KV_NARROW_STEP, KV_NARROW_STEP_CAT, KV_NARROW_STEP_CAT_MASK, KV_NARROW_STEP_MCAT, KV_NARROW_STEP_MCAT_MASK, KV_NARROW_STEP_MBIN},
     {KV_NARROW_TRAIN_STATIC, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_NARROW_TRAIN_MBIN},
     {KV_NARROW_TRAIN, KV_NARROW_TRAIN_CAT, KV_NARROW_TRAIN_CAT_MASK, KV_NARROW_TRAIN_MCAT, KV_NARROW_TRAIN_MCAT_MASK, KV_NARROW_TRAIN_MBIN},
-    {KV_COUNT, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK, KV_COUNT},
-    {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_COUNT},
-    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK, KV_COUNT},
-    {KV_ROLLOUT_PERSISTENT, KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK, KV_COUNT}};
+    {KV_TOTAL, KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK, KV_TOTAL},
+    {KV_BF16_STEP, KV_BF16_STEP_CAT, KV_BF16_STEP_CAT_MASK, KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_STEP_MBIN},
+    {KV_BF16_TRAIN, KV_BF16_TRAIN_CAT, KV_BF16_TRAIN_CAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK, KV_BF16_TRAIN_MBIN},
+    {KV_ROLLOUT_PERSISTENT, KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK, KV_TOTAL}};
 
 // RCCL entry points resolved at run time (the single-GPU path must not depend on librccl being loadable)
 struct Rccl {
@@ -167,13 +175,13 @@ struct ppo_handle {
     int CT = 1;                       // column tiles per wave in the dense layers (4 for wide nets)
     int CTH = 0;                      // split-K policy head column tiles (2 when Ap == 32 on the wide path), 0 = generic
     bool early = false;               // train kernel keeps the small products' weights in registers from kernel entry (18-obs / [256, ...] shape)
-    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (never bf16; narrow only with opt_narrow, t8 / dw2 only with opt_pair)
+    int dist = PPO_ACT_GAUSSIAN;      // action distribution (ppo_create_ex); PPO_ACT_MULTI_BINARY: the generic fp32 family (bf16 only with opt_bf16, narrow only with opt_narrow, t8 / dw2 only with opt_pair)
     // a discrete handle's family opt-ins, each under its own distribution's flag (parse_create; a Gaussian handle has none: it takes its shape's kernels anyway).  Until
     // create_handle has decided the families: what was asked for.  From its one write-back on: what took effect -- but a categorical handle's opt_narrow keeps "asked"
     // (ppo_dist_init refuses such a handle on a shape that did not qualify as well)
     bool opt_narrow = false;          // PPO_ACT_SHAPE_KERNELS (categorical, multi-categorical) / PPO_ACT_BINARY_SHAPE_KERNELS (multi-binary): the narrow family (build_narrow_layout)
     bool opt_pair = false;            // PPO_ACT_PAIR_KERNELS / PPO_ACT_BINARY_PAIR_KERNELS, PPO_F32: the [256,256] pair (t8 / dw2 below)
-    bool opt_bf16 = false;            // PPO_ACT_BF16_HEAD (categorical) / PPO_ACT_BF16_MULTI_HEAD (ppo_create_multi_ex), PPO_BF16: bf16_sample_kernel / bf16_loss_kernel<cat|mcat[,mask]>
+    bool opt_bf16 = false;            // PPO_ACT_BF16_HEAD (categorical) / PPO_ACT_BF16_MULTI_HEAD (ppo_create_multi_ex) / PPO_ACT_BF16_BINARY_HEAD (multi-binary), PPO_BF16: bf16_sample_kernel / bf16_loss_kernel<cat|mcat[,mask]|mbin>
     int Aw = 0;                       // action columns per row in every action buffer: A (Gaussian; multi-binary: the bits), 1 (categorical: the category index) or K (multi-categorical)
     CompTable comp{};                 // multi-categorical (ppo_create_multi[_ex]): K components, component k owns logits [off[k], off[k + 1]); K = 0 on every other handle
     // action masks of the categorical head (ppo_set_action_masking): ro_mask [T,E,A] travels with the rollout rows, mb_mask [B,A] is its gather in minibatch order,
@@ -371,7 +379,7 @@ struct ppo_handle {
     size_t ev_next = 0;
     double prof_ms[PK_COUNT]{};
     int64_t prof_n[PK_COUNT]{};
-    int64_t kv[KV_COUNT]{};           // enqueues per kernel variant since ppo_create (a hipGraph capture counts once, its replays do not)
+    int64_t kv[KV_TOTAL]{};           // enqueues per kernel variant since ppo_create (a hipGraph capture counts once, its replays do not)
 };
 
 namespace {
@@ -814,11 +822,11 @@ ObsNorm no_norm_fwd() { return ObsNorm{nullptr, nullptr, 0.f, 0.f, 0}; }
 
 // ---- the policy head of a launch ------------------------------------------------------------------------------------
 // A launch site decides the head once (head_of), turns it into compile-time constants once (with_head calls f with a HeadTag) and asks its family's picker
-// (bf16_sample_kernel / bf16_loss_kernel below; step_fn, train_fb_fn, nw_step_fn, nw_train_fn, train8_fn, nw_host_step_fn under "launches") for the instantiation.
+// (bf16_sample_fn / bf16_eval_fn / bf16_loss_fn below; step_fn, train_fb_fn, nw_step_fn, nw_train_fn, train8_fn, nw_host_step_fn under "launches") for the instantiation.
 // ppo_create_ex asks the same pickers for every head the handle can launch (for_each_head) when it raises the dynamic-LDS limits.
 template <bool CAT, bool MASK, bool MULTI, bool BIN = false>
 struct HeadTag { static constexpr bool cat = CAT, mask = MASK, multi = MULTI, bin = BIN; };
-using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn), the narrow step / train pickers (nw_step_fn, nw_train_fn) and train8_fn know it, no other
+using MbinTag = HeadTag<false, false, false, true>;                 // the multi-binary head: the generic fp32 family's pickers (step_fn, train_fb_fn), the narrow step / train pickers (nw_step_fn, nw_train_fn), train8_fn and the bf16 pickers (bf16_sample_fn, bf16_eval_fn, bf16_loss_fn) know it, no other
 using GaussHead = HeadTag<false, false, false>;
 
 // (a mask on a Gaussian handle: the entry points and launch_step refuse it before any launch)
@@ -849,6 +857,13 @@ static auto head_args(T, const ppo_handle* h, const Base& a) {
 }
 
 // ---- bf16 matrix-core path (ppo_bf16.hpp) ------------------------------------------------------------------------
+// the pickers of the three kernels with a head: the multi-binary forms are the overloads with a head type (a PPO_BF16 handle created with PPO_ACT_BF16_BINARY_HEAD)
+template <class T>
+static auto bf16_sample_fn(T) { if constexpr (T::bin) return bf16_sample_kernel<MbinHead>; else return bf16_sample_kernel<T::cat, T::mask, T::multi>; }
+template <class T>
+static auto bf16_eval_fn(T) { if constexpr (T::bin) return bf16_eval_kernel<MbinHead>; else return bf16_eval_kernel<T::cat, T::mask, T::multi>; }
+template <class T>
+static auto bf16_loss_fn(T) { if constexpr (T::bin) return bf16_loss_kernel<MbinHead>; else return bf16_loss_kernel<T::cat, T::mask, T::multi>; }
 // bf16 operand copy of the fp32 master weights: a cast of the whole padded vector (adam_kernel keeps it current afterwards)
 int bf16_refresh_mirrors(ppo_handle* h) {
     ppo_handle::Bf16& b = h->bf;
@@ -1083,10 +1098,7 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     sa.mask = a.mask;
     if (n.A > 128) return fail(h, "bf16 path: more than 128 actions");
     const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
-    with_head(head_of(h, a.mask != nullptr), [&](auto H) {
-        using Hd = decltype(H);
-        hipLaunchKernelGGL((bf16_sample_kernel<Hd::cat, Hd::mask, Hd::multi>), grid, blk, 0, h->stream, head_args<SampleArgsBM>(H, h, sa));
-    });
+    with_head(head_of(h, a.mask != nullptr), [&](auto H) { hipLaunchKernelGGL(bf16_sample_fn(H), grid, blk, 0, h->stream, head_args<SampleArgsBM>(H, h, sa)); });
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1112,10 +1124,7 @@ int launch_eval_bf16(ppo_handle* h, const EvalArgs& a) {
         ea.params = a.params ? a.params + (size_t)r0 * a.W : nullptr;
         ea.n = rows; ea.A = n.A; ea.W = a.W;
         const dim3 grid((rows + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
-        with_head(head_of(h, a.mask != nullptr), [&](auto H) {
-            using Hd = decltype(H);
-            hipLaunchKernelGGL((bf16_eval_kernel<Hd::cat, Hd::mask, Hd::multi>), grid, blk, 0, h->stream, head_args<EvalArgsBM>(H, h, ea));
-        });
+        with_head(head_of(h, a.mask != nullptr), [&](auto H) { hipLaunchKernelGGL(bf16_eval_fn(H), grid, blk, 0, h->stream, head_args<EvalArgsBM>(H, h, ea)); });
         HIP_OK(h, hipGetLastError());
     }
     return 0;
@@ -1146,10 +1155,7 @@ int bf16_train_fwd_bwd(ppo_handle* h, const TrainArgs& ta, int Rp, bool links_on
     if (n.A > 64 * BL_EPT) return fail(h, "bf16 path: more than %d actions", 64 * BL_EPT);
     const dim3 lgrid(Rp / BL_ROWS), lblk(64 * BL_ROWS);
     const size_t llds = (size_t)(2 * BL_ROWS * n.Ap + 6 * BL_ROWS) * sizeof(float);
-    with_head(head_of(h, ta.mask != nullptr), [&](auto H) {
-        using Hd = decltype(H);
-        hipLaunchKernelGGL((bf16_loss_kernel<Hd::cat, Hd::mask, Hd::multi>), lgrid, lblk, llds, h->stream, head_args<LossArgsBM>(H, h, la));
-    });
+    with_head(head_of(h, ta.mask != nullptr), [&](auto H) { hipLaunchKernelGGL(bf16_loss_fn(H), lgrid, lblk, llds, h->stream, head_args<LossArgsBM>(H, h, la)); });
     HIP_OK(h, hipGetLastError());
     if (links_only) return 0;
     GemmArgs bl[PPO_MAX_LAYERS];
@@ -1990,17 +1996,21 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     // the flags every distribution accepts go (PPO_ACT_BF16_MULTI_HEAD through ppo_create_multi_ex only); whatever else is left must be a distribution.  The two binary
     // flags belong to PPO_ACT_MULTI_BINARY alone: beside any other distribution they stay in and are refused (ppo_create_multi_ex has refused them: "unknown flag bit")
     int32_t dist = action_dist & ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS | (nvec ? PPO_ACT_BF16_MULTI_HEAD : 0));
-    if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
+    if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS | PPO_ACT_BF16_BINARY_HEAD)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
     const bool cat = dist == PPO_ACT_CATEGORICAL, mcat = dist == PPO_ACT_MULTI_CATEGORICAL, mbin = dist == PPO_ACT_MULTI_BINARY, bf16 = cfg->compute_dtype == PPO_BF16;
     if (dist != PPO_ACT_GAUSSIAN && !cat && !mbin && !(mcat && nvec))
         return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
-                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)", (int)dist);
+                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)%s", (int)dist,
+                    (dist & PPO_ACT_BF16_BINARY_HEAD) ? "; PPO_ACT_BF16_BINARY_HEAD belongs to PPO_ACT_MULTI_BINARY alone" : "");
     if (cat && cfg->act_dim < 2) return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (cat && bf16 && !(action_dist & PPO_ACT_BF16_HEAD))
         return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
     if (cat && bf16 && cfg->act_dim > 128)
         return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
-    if (mbin && bf16) return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
+    if (mbin && bf16 && !(action_dist & PPO_ACT_BF16_BINARY_HEAD))
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
+    if (mbin && bf16 && cfg->act_dim > 128)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_BINARY_HEAD: the multi-binary head of the PPO_BF16 path holds at most 128 bits (got %d)", (int)cfg->act_dim);
     for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
     rq = CreateRequest{};
     rq.dist = dist; rq.Aw = cat ? 1 : mcat ? n_components : cfg->act_dim;
@@ -2008,7 +2018,7 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     for (int k = 0; k < rq.comp.K; ++k) rq.comp.off[k + 1] = rq.comp.off[k] + nvec[k];
     rq.narrow = (action_dist & (mbin ? PPO_ACT_BINARY_SHAPE_KERNELS : cat || mcat ? PPO_ACT_SHAPE_KERNELS : 0)) != 0;
     rq.pair = (action_dist & (mbin ? PPO_ACT_BINARY_PAIR_KERNELS : cat || mcat ? PPO_ACT_PAIR_KERNELS : 0)) != 0 && cfg->compute_dtype == PPO_F32;
-    rq.bf16 = (action_dist & (cat ? PPO_ACT_BF16_HEAD : mcat ? PPO_ACT_BF16_MULTI_HEAD : 0)) != 0 && bf16;
+    rq.bf16 = (action_dist & (cat ? PPO_ACT_BF16_HEAD : mcat ? PPO_ACT_BF16_MULTI_HEAD : mbin ? PPO_ACT_BF16_BINARY_HEAD : 0)) != 0 && bf16;
     return 0;
 }
 
@@ -4192,7 +4202,7 @@ int ppo_dist_init(ppo_handle* h, int32_t world, int32_t rank, const char uid[128
     const bool mcat = h->dist == PPO_ACT_MULTI_CATEGORICAL, mbin = h->dist == PPO_ACT_MULTI_BINARY;
     const char* kind = mcat ? "multi-categorical" : mbin ? "multi-binary" : "categorical";
     if (h->opt_bf16)
-        return fail(h, "ppo_dist_init: data parallel is not supported for a %s PPO_BF16 handle created with %s", kind, mcat ? "PPO_ACT_BF16_MULTI_HEAD" : "PPO_ACT_BF16_HEAD");
+        return fail(h, "ppo_dist_init: data parallel is not supported for a %s PPO_BF16 handle created with %s", kind, mcat ? "PPO_ACT_BF16_MULTI_HEAD" : mbin ? "PPO_ACT_BF16_BINARY_HEAD" : "PPO_ACT_BF16_HEAD");
     if (h->opt_narrow || h->opt_pair)
         return fail(h, "ppo_dist_init: data parallel is not supported for a %s handle created with %s (create it without the flag)", kind,
                     h->opt_narrow ? (mbin ? "PPO_ACT_BINARY_SHAPE_KERNELS" : "PPO_ACT_SHAPE_KERNELS") : (mbin ? "PPO_ACT_BINARY_PAIR_KERNELS" : "PPO_ACT_PAIR_KERNELS"));
@@ -4494,10 +4504,10 @@ int ppo_kernel_counts_all(const ppo_handle* h, int32_t max, char (*names)[32], i
 // every variant of this build, by name and by index: the list grows between versions
 int64_t ppo_kernel_count(const ppo_handle* h, const char* name) {
     if (!h || !name) return -1;
-    for (int i = 0; i < KV_COUNT; ++i) if (strcmp(name, kVariantNames[i]) == 0) return h->kv[i];
+    for (int i = 0; i < KV_TOTAL; ++i) if (strcmp(name, kVariantNames[i]) == 0) return h->kv[i];
     return -1;
 }
-const char* ppo_kernel_variant_name(int32_t i) { return i >= 0 && i < KV_COUNT ? kVariantNames[i] : nullptr; }
+const char* ppo_kernel_variant_name(int32_t i) { return i >= 0 && i < KV_TOTAL ? kVariantNames[i] : nullptr; }
 
 // Raw device buffers by name, PADDING INCLUDED (ppo_get_flat and ppo_get_last_grad copy the dense part of every tensor only): the transposed mirrors, the small-parameter
 // mirrors, the assembled gradient with its tail, the workspaces of the last train step, the gathered epoch.  For bitwise comparisons of two runs (tests/test_other_shapes.py,

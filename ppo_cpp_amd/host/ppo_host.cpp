@@ -540,10 +540,10 @@ int ppo_host_multi_checkpoint(const char* prefix, const int* nvec_in, const int*
 
 // The learning check of the multi-binary head (tests/test_multi_binary.py): n_envs x MultiBinaryTargetEnv(act_dim bits) -> VecEnv -> EnvNormalize -> PPO2::learn with the
 // library's own sampling and shuffles, through the HBM-resident loop or, with args->reference_loop, the literal one.  The handle comes from PPO2::create_handle (the Env
-// carries IMultiBinary: ppo_create_ex with PPO_ACT_MULTI_BINARY; args->discrete_kernels == 3 adds PPO_ACT_BINARY_SHAPE_KERNELS -- the narrow <mbin> kernels where
+// carries IMultiBinary: ppo_create_ex with PPO_ACT_MULTI_BINARY, with PPO_ACT_BF16_BINARY_HEAD beside it when args->compute_dtype is PPO_BF16; args->discrete_kernels == 3 adds PPO_ACT_BINARY_SHAPE_KERNELS -- the narrow <mbin> kernels where
 // the shape qualifies -- 4 adds PPO_ACT_BINARY_PAIR_KERNELS -- the [256,256] train kernel pair where that shape qualifies -- 1 and 2 ask for the flags of a discrete Env's handle, which this head accepts and ignores).  The head has neither a fused host step nor a resident rollout: args->host_step_fused and the process-wide resident default are not applied.
 // reward_curve [n_updates], losses_out [n_updates][5] (may be null); count_names / counts / n_counts (all three or none): every kernel variant of the
-// run's handle (ppo_kernel_variant_name / ppo_kernel_count: the list grows between versions), up to 64 entries.
+// run's handle (ppo_kernel_variant_name / ppo_kernel_count: the list grows between versions), its first 64 entries at the most (the callers' buffers hold 64).
 int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* losses_out, char (*count_names)[32], long long* counts, int* n_counts, ppo_host_result* out) {
     std::memset(out, 0, sizeof *out);
     ppo_handle* h = nullptr;
@@ -555,7 +555,9 @@ int ppo_host_learn_binary(const ppo_host_args* a, float* reward_curve, float* lo
         cfg.compute_dtype = a->compute_dtype;
         std::vector<std::shared_ptr<Env>> envs;
         for (int i = 0; i < a->n_envs; ++i) envs.push_back(std::make_shared<MultiBinaryTargetEnv>(1234u, (uint32_t)i, O, A));
-        const int32_t extra_flags = a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : a->discrete_kernels == 3 ? PPO_ACT_BINARY_SHAPE_KERNELS : a->discrete_kernels == 4 ? PPO_ACT_BINARY_PAIR_KERNELS : 0;
+        // (PPO_BF16: the bf16 path's multi-binary head is opt-in, as PPO_ACT_BF16_HEAD is for a discrete Env's handle)
+        const int32_t extra_flags = (a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : a->discrete_kernels == 3 ? PPO_ACT_BINARY_SHAPE_KERNELS : a->discrete_kernels == 4 ? PPO_ACT_BINARY_PAIR_KERNELS : 0) |
+                                    (a->compute_dtype == PPO_BF16 ? PPO_ACT_BF16_BINARY_HEAD : 0);
         if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, extra_flags) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_action_dist(h) != PPO_ACT_MULTI_BINARY) throw std::runtime_error("PPO2::create_handle did not create a multi-binary handle for an IMultiBinary Env");
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));

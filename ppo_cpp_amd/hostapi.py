@@ -117,7 +117,8 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     PPO_ACT_SHAPE_KERNELS (PPO2::action_dist_for), "pair": with PPO_ACT_PAIR_KERNELS (hidden [256, 256]: train8_kernel<cat[,mask]> +
     weight_grad_assemble_kernel), "generic" (the default): without either.
     compute_dtype=1 (PPO_BF16; default 0): the handle runs the bf16 path; a discrete Env's handle is then created with PPO_ACT_BF16_HEAD, a multi-discrete Env's (nvec) with
-    PPO_ACT_BF16_MULTI_HEAD (bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>, sum(nvec) <= 128).
+    PPO_ACT_BF16_MULTI_HEAD (bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>, sum(nvec) <= 128), a multi-binary Env's (binary=True) with PPO_ACT_BF16_BINARY_HEAD
+    (bf16_sample_kernel / bf16_loss_kernel<mbin>, act_dim <= 128).
     nvec=[n_0, ..]: MultiDiscreteTargetEnv with these components (act_dim is ignored: their sum) and a multi-categorical handle (PPO2::create_handle ->
     ppo_create_multi_ex; discrete_kernels="narrow": with PPO_ACT_SHAPE_KERNELS, the narrow <mcat> kernels where the shape qualifies; "pair": with
     PPO_ACT_PAIR_KERNELS, train8_kernel<mcat[,mask]> + weight_grad_assemble_kernel where hidden is [256, 256] and sum(nvec) <= 64), through ppo_host_learn_multi; masked=True: the environments also forbid about half of every component's categories per step (IActionMask)
@@ -132,8 +133,8 @@ def learn_curve(n_envs, n_steps, hidden, n_updates, nminibatches, noptepochs, lr
     PPO_ACT_MULTI_BINARY), through ppo_host_learn_binary; discrete_kernels="binary_narrow" creates it with PPO_ACT_BINARY_SHAPE_KERNELS (narrow_step_kernel<mbin> /
     narrow_train_kernel<mbin> where the shape qualifies), "binary_pair" with PPO_ACT_BINARY_PAIR_KERNELS (train8_kernel<mbin> + weight_grad_assemble_kernel at hidden
     [256, 256]), the other words ask for the flags of a discrete Env's handle, which this head accepts and ignores; "kernel_counts" then holds every variant of the
-    build (ppo_kernel_variant_name / ppo_kernel_count: a dict that grows between versions).  The head
-    has no fused host step, no resident rollout, no masks and no bf16 path: host_step_fused, rollout_resident, masked, nvec, discrete and target_kl are refused with it.
+    build (ppo_kernel_variant_name / ppo_kernel_count: a dict that grows between versions; its first 64 at the most).  The head
+    has no fused host step, no resident rollout and no masks: host_step_fused, rollout_resident, masked, nvec, discrete and target_kl are refused with it.
     target_kl (default 0 = off): PPO2::set_target_kl, target-KL early stopping (include/ppo_hip.h, ppo_set_target_kl); "applied" [n_updates, 2] then holds the Adam
     steps applied / train steps of every update (ppo_host_explicit::target_kl / applied_out; not through the nvec form)."""
     lib = load_host_library()
