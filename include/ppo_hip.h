@@ -286,11 +286,44 @@ int ppo_action_width(const ppo_handle* h);
  *                        the generic fp32 <mbin> handle | the Gaussian PPO_BF16 handle): train step 233.6 | 1317.0 | 234.3 at 4096 rows, 165.3 | 555.7 | 164.1
  *                        at 256; policy step 140.2 | 853.5 | 139.9 at 8192 rows.  A second run of the same tool: 233.4 | 1316.6 | 229.3, 165.6 | 539.9 | 162.6,
  *                        140.6 | 850.4 | 137.1.  Against the Gaussian head forms the two runs disagree: equal within the rounds' spread in the first, 3.0 - 4.1 us
- *                        slower (1.8 - 2.5 %, outside the spread) in the second.  Not resolved; the head has not been tuned. */
+ *                        slower (1.8 - 2.5 %, outside the spread) in the second.  Not resolved; the head has not been tuned.
+ *   PPO_ACT_BF16_WIDE_HEAD  PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD with compute_dtype PPO_BF16 and 128 < act_dim <= 1024 creates a categorical
+ *                        handle on the bf16 path's WIDE head forms (masks included).  act_dim > 1024 is an error that names the flag, the limit and the value; without
+ *                        the flag act_dim > 128 keeps its refusal.  With act_dim <= 128, and with PPO_F32, the flag is accepted and changes nothing (same kernels,
+ *                        bits and counts).  Beside any other distribution the bit is an "unknown action_dist" error whose text names it; ppo_create_multi_ex refuses
+ *                        it with its own "unknown flag bit 0x10000".  The padded width Ap is act_dim rounded up to 128.  Kernels (ppo_bf16.hpp):
+ *                          bf16_logits_kernel<WM>: logits = H_L W_pi + b_pi as a tiled GEMM on the family's core (128 WM x 128 tiles, LDS-DMA ring of three 64-deep
+ *                            stages, v_mfma_f32_16x16x32_bf16), fp32 bias added and fp32 logits stored straight from the accumulators, one 16-byte store per
+ *                            register group; no reduction split, so a row's logits do not depend on tile height or workgroup.  256-row tiles when the row count is a
+ *                            multiple of 256 and they cover the chip, 128-row tiles otherwise (the 64-environment act step: one row tile).
+ *                          bf16_value_head_kernel: the value head alone with bf16_heads_kernel's arithmetic and reduction ranges, a 128-column output image.
+ *                          bf16_sample_wide_kernel / bf16_loss_wide_kernel / bf16_eval_wide_kernel<EPT, MASK>, EPT = 4 / 8 / 16 logits per lane for act_dim <= 256 /
+ *                            512 / 1024: one wave per row, the row's logits in registers as 16-byte quads (column 256 q + 4 lane + c), every load first, one (value,
+ *                            index) butterfly for maximum and argmax (lowest index on a tie), one for the normaliser, exp once per element, ONE row-statistics
+ *                            helper in all three: ppo_step's neglogp, the train model's and ppo_evaluate_actions' are the same bits.  The categorical head's
+ *                            arithmetic and counter keys (j up to 1023; a forbidden category keeps its uniform); forbidden categories, padding columns and dead
+ *                            rows get d logits of exactly +0; an all-ones mask gives the unmasked bits.  The loss kernel keeps the assembly's contract (a slot row
+ *                            per 16 rows, fp32 column sums of the fp32 d logits, aux words zeros, pt[1] the entropy) with a [16][Ap] fp32 LDS tile (64 KB + the
+ *                            term rows at Ap = 1024: its dynamic-LDS limit is raised at creation).
+ *                        Every entry point of a categorical PPO_BF16 handle works (step / act / value, train step, the masked forms, the rollout calls and field 8,
+ *                        ppo_collect_synthetic, ppo_update with kernel nodes only, ppo_get_last_grad, tensors and checkpoints -- an fp32 categorical handle's of the
+ *                        same act_dim -- the truncation bootstrap, the host checks, and behind ppo_set_bf16_queries(h, 1) the three policy queries,
+ *                        ppo_distribution_width = A).  PPO_HIP_NO_BF16_CHAIN / PPO_HIP_NO_REDUCE_ADAM act as on every PPO_BF16 handle; ppo_dist_init and
+ *                        ppo_set_target_kl refuse the handle as they refuse every PPO_ACT_BF16_HEAD handle.  Counted under "bf16_step_sequence<wcat>",
+ *                        "bf16_step_sequence<wcat,mask>", "bf16_train_sequence<wcat>", "bf16_train_sequence<wcat,mask>" INSTEAD of the <cat[,mask]> names -- names
+ *                        of ppo_kernel_count / ppo_kernel_variant_name only (31 characters at most: "<cat,mask,wide>" would not fit); ppo_kernel_counts keeps its 60
+ *                        rows, ppo_kernel_counts_all its 62.  Debug buffers: "bf_head_pi" is fp32 [1][Rcap][Ap] (unsplit logits), "bf_head_vf" fp32 [4][Rcap][128].
+ *                        Known cost, not solved: the value head keeps the policy head's padded width (vf/w is [HpL][Ap], dhead_vf [rows][Ap]), so at Ap = 1024 the
+ *                        value tower's backward link 0 reduces over 1024 columns of zeros, its weight-gradient tiles are mostly padding and Adam walks about 1 M
+ *                        padded words.  
+ *                        Measured on an MI355X at 256 observations, [1024,1024,1024] (tools/prof_bf16_wide.py; us of device time per call, median of 7 rounds; A = 1024 | A = 256 | the PPO_ACT_BF16_HEAD handle at A = 128):
+ *                        train step 343.6 | 276.9 | 233.1 at 4096 rows, 202.3 | 184.0 | 165.9 at 256;
+ *                        policy step 170.0 | 150.2 | 145.6 at 8192 rows (DESIGN.md section 5 has the per-kernel figures and the padded value head's share). */
 #define PPO_ACT_MULTI_BINARY 3
 #define PPO_ACT_BINARY_SHAPE_KERNELS 0x2000
 #define PPO_ACT_BINARY_PAIR_KERNELS 0x4000
 #define PPO_ACT_BF16_BINARY_HEAD 0x8000
+#define PPO_ACT_BF16_WIDE_HEAD 0x10000
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);
@@ -674,7 +707,7 @@ const char* ppo_kernel_variant_name(int32_t i);                        /* i-th v
  * narrow path's packed image and second weight set ("nw_img" "nw_theta1" ...), the normaliser's state.
  * A PPO_BF16 handle's workspaces (0 words on every other handle; "slots_pi" / "slots_vf", "slabs", "theta" and "grad" are shared with the fp32 path): "bf_theta" (bf16 operand
  * mirror of "theta", same padded offsets), "bf_x0" (staged observations, bf16 [Rcap][Kp0]), "bf_h_pi_<l>" / "bf_h_vf_<l>" (tanh outputs of hidden layer l = 0 .. PPO_MAX_LAYERS - 1,
- * bf16 [Rcap][Hp_l]), "bf_dy_pi_<l>" / "bf_dy_vf_<l>" (gradients w.r.t. the pre-activations, same shape), "bf_head_pi" / "bf_head_vf" (fp32 [4][Rcap][Ap]: the head GEMM's partial
+ * bf16 [Rcap][Hp_l]), "bf_dy_pi_<l>" / "bf_dy_vf_<l>" (gradients w.r.t. the pre-activations, same shape), "bf_head_pi" / "bf_head_vf" (fp32 [4][Rcap][Ap]; a wide categorical handle, PPO_ACT_BF16_WIDE_HEAD: [1][Rcap][Ap] unsplit logits and [4][Rcap][128]: the head GEMM's partial
  * products per reduction range, bias in range 0; the value is column 0), "bf_dhead_pi" / "bf_dhead_vf" (bf16 [Rcap][Ap]: loss gradient w.r.t. the head outputs) and "bf_dbias" (fp32
  * [row tiles][sum of Hp_l over towers and layers]: per-row-tile bias-gradient sums; tower-major, then layer).  Rcap = the largest row count seen so far rounded up to 128; a bf16
  * buffer of N elements reads as N / 2 words (view the words as uint16 for the bit patterns).  tests/test_bf16_stages.py checks every stage of the path through them.

@@ -67,6 +67,7 @@ ACT_BF16_MULTI_HEAD = 0x1000                            # PPO_ACT_BF16_MULTI_HEA
 ACT_BINARY_SHAPE_KERNELS = 0x2000                       # PPO_ACT_BINARY_SHAPE_KERNELS, a flag of ppo_create_ex beside PPO_ACT_MULTI_BINARY only
 ACT_BINARY_PAIR_KERNELS = 0x4000                        # PPO_ACT_BINARY_PAIR_KERNELS, likewise
 ACT_BF16_BINARY_HEAD = 0x8000                           # PPO_ACT_BF16_BINARY_HEAD, likewise
+ACT_BF16_WIDE_HEAD = 0x10000                            # PPO_ACT_BF16_WIDE_HEAD, a flag of ppo_create_ex beside PPO_ACT_CATEGORICAL only
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -82,6 +83,11 @@ class PPOHip:
     bf16_head=True (PPO_ACT_BF16_HEAD; default False): with action_dist="categorical" and compute_dtype=1 (PPO_BF16) the handle runs the bf16
     matrix-core path with a categorical head (at most 128 categories; masks included; no data parallel).  Without it that combination is
     refused; on a compute_dtype=0 or Gaussian handle it changes nothing.
+    bf16_wide_head=True with action_dist="categorical", compute_dtype=1 and bf16_head=True (PPO_ACT_BF16_WIDE_HEAD; default False; a ValueError with any other
+    action_dist): up to 1024 categories on the bf16 path (bf16_logits_kernel, bf16_value_head_kernel and the bf16_*_wide_kernel row kernels; masks and, after
+    set_bf16_queries(True), the policy queries included; no data parallel), e.g. PPOHip(O, 1024, hidden, action_dist="categorical", compute_dtype=1, bf16_head=True,
+    bf16_wide_head=True).  With at most 128 categories or compute_dtype=0 it changes nothing (same kernels, bits and counts).  "bf16_step_sequence<wcat[,mask]>" /
+    "bf16_train_sequence<wcat[,mask]>" are names of kernel_count() / kernel_variants() only.  The attribute bf16_wide_head keeps what was asked for.
     pair_kernels=True (PPO_ACT_PAIR_KERNELS; default False): a categorical compute_dtype=0 handle with hidden [256, 256] and at most 64 observations /
     categories trains with train8_kernel<cat[,mask]> + weight_grad_assemble_kernel instead of the generic kernels (no data parallel); any other
     shape, a Gaussian handle and a compute_dtype=1 handle are not affected.
@@ -130,7 +136,7 @@ class PPOHip:
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, binary_shape_kernels=False,
-                 binary_pair_kernels=False, binary_bf16_head=False, **overrides):
+                 binary_pair_kernels=False, binary_bf16_head=False, bf16_wide_head=False, **overrides):
         multi = action_dist == "multi_categorical"
         if binary_shape_kernels and action_dist != "multi_binary":
             raise ValueError("binary_shape_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
@@ -138,6 +144,8 @@ class PPOHip:
             raise ValueError("binary_pair_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if binary_bf16_head and action_dist != "multi_binary":
             raise ValueError("binary_bf16_head belongs to action_dist='multi_binary', not %r" % (action_dist,))
+        if bf16_wide_head and action_dist != "categorical":
+            raise ValueError("bf16_wide_head belongs to action_dist='categorical', not %r" % (action_dist,))
         if nvec is not None and not multi:
             raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
         if multi:
@@ -166,6 +174,7 @@ class PPOHip:
         self.binary_shape_kernels = bool(binary_shape_kernels)
         self.binary_pair_kernels = bool(binary_pair_kernels)
         self.binary_bf16_head = bool(binary_bf16_head)
+        self.bf16_wide_head = bool(bf16_wide_head)
         self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
@@ -178,7 +187,8 @@ class PPOHip:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())
         elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)
                                     | (ACT_PAIR_KERNELS if pair_kernels else 0) | (ACT_BINARY_SHAPE_KERNELS if binary_shape_kernels else 0)
-                                    | (ACT_BINARY_PAIR_KERNELS if binary_pair_kernels else 0) | (ACT_BF16_BINARY_HEAD if binary_bf16_head else 0), C.byref(h)) != 0:
+                                    | (ACT_BINARY_PAIR_KERNELS if binary_pair_kernels else 0) | (ACT_BF16_BINARY_HEAD if binary_bf16_head else 0)
+                                    | (ACT_BF16_WIDE_HEAD if bf16_wide_head else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)

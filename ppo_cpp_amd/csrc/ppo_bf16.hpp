@@ -1648,3 +1648,311 @@ __global__ __launch_bounds__(64 * BGR_WAVES) void bf16_reduce_adam_kernel(Reduce
         }
     }
 }
+
+// ==== wide categorical head (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD, 128 < A <= 1024) ======================================================
+// Past 128 columns the policy head is no thin product any more (8.6 GFLOP at 4096 x 1024 x 1024: one tower's hidden layer) and a row no longer fits "two elements per
+// lane".  Kernels of their own under new symbols: the 128-wide forms above keep symbol, kernarg layout and machine code.
+//   bf16_logits_kernel<WM>            logits = H_L W_pi + b_pi as a tiled GEMM on the family's core, fp32 out, no reduction split
+//   bf16_value_head_kernel            the value head alone: bh_tower<true, 1> with its GB_HEAD_SPLIT ranges, a 128-column output image (today's arithmetic and bits)
+//   bf16_{sample,loss,eval}_wide_kernel<EPT, MASK>     one wave per row, EPT = 4 / 8 / 16 logits per lane in registers (A <= 256 / 512 / 1024)
+
+// ---- logits product: [Rp x K] . [K x Ap], K = HpL.  gemm_nt_tile's operands and main loop -- H rows by LDS-DMA as they lie, the weights as they lie ([K][Ap], BT: [64][128]
+// images read back through the transposed reads), the three-stage ring, 32 matrix instructions per wave and stage -- and an epilogue of its own: the accumulators ARE the
+// result.  A lane holds four consecutive columns of a row per accumulator register group (GemmAcc), so bias + accumulator leaves as one 16-byte store per group, 16 lanes
+// covering 256 contiguous bytes of a row; nothing is parked in LDS and no bf16 rounding happens.  The whole reduction runs in one workgroup in stage order: a row's logits
+// do not depend on the tile height or on which workgroup computed them (act model and train model: same bits on the same weights).
+struct LogitsArgsB {
+    const bf16_t* H; int ldh;                 // last hidden layer's outputs of the policy tower, [rows_pad][K]
+    const bf16_t* W; int ldw;                 // pi/w as it lies, [K][Ap]
+    const float* bias;                        // [Ap] fp32
+    float* F; int ldf;                        // out [rows_pad][Ap] fp32
+    int K, tiles_i;                           // block id -> (ti, tj) = (id % tiles_i, id / tiles_i): consecutive workgroups share a weight panel
+};
+template <int WM>
+__global__ __launch_bounds__(GB_THREADS(WM)) void bf16_logits_kernel(LogitsArgsB a) {
+    extern __shared__ __attribute__((aligned(16))) char gb_lds[];
+    const int ti = blockIdx.x % a.tiles_i, tj = blockIdx.x / a.tiles_i;
+    const int i0 = ti * GB_BM(WM), j0 = tj * GB_N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, g = lane >> 4, c = lane & 15;
+    float4 bias4[4];                                         // this lane's 16 bias values: requested before the loop, used after it
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) bias4[nb] = *reinterpret_cast<const float4*>(a.bias + j0 + wn + 16 * nb + 4 * g);
+    GemmAcc acc;
+    gb_mainloop<WM, false, true>(acc, a.H, a.ldh, i0, a.W, a.ldw, j0, 0, a.K, gb_lds);
+#pragma unroll
+    for (int ma = 0; ma < 4; ++ma) {
+        float* row = a.F + (size_t)(i0 + wm + 16 * ma + c) * a.ldf + j0 + wn + 4 * g;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+            *reinterpret_cast<float4*>(row + 16 * nb) = make_float4(acc.v[ma][nb][0] + bias4[nb].x, acc.v[ma][nb][1] + bias4[nb].y, acc.v[ma][nb][2] + bias4[nb].z, acc.v[ma][nb][3] + bias4[nb].w);
+    }
+}
+
+// ---- value head of a wide handle: tower 1 of bf16_heads_kernel alone (one 16-column block, GB_HEAD_SPLIT reduction ranges, partial products added by the consumers in
+// range order).  vf/w keeps the policy head's padded width (ldw = Ap); the output image is 128 columns wide whatever Ap is (HeadArgsB::ldf = GB_N).
+__global__ __launch_bounds__(256) void bf16_value_head_kernel(HeadArgsB a) {
+    extern __shared__ __attribute__((aligned(16))) char bh_lds[];
+    bh_tower<true, 1>(a, 1, bh_lds);
+}
+
+// ---- the three row kernels.  One wave per row; a lane keeps EPT logits in registers as EPT / 4 quads: element e = 4 q + c is column 256 q + 4 lane + c, so quad q of the
+// wave is 1 KB of contiguous logits (one 16-byte load per lane) and a lane's elements are in rising column order.  Ap is a multiple of 128: a quad lies wholly inside or
+// wholly outside the padded row.  The [n, A] operands (masks, uniforms, probabilities) take the same quads, 16-byte accesses when A % 4 == 0 and scalar ones otherwise.
+// The two towers' images differ (logits [rows][Ap] unsplit; value [vsplit][rows][128]): a leading dimension and a split per tower.
+struct WideHeadIn {
+    const float* logits; int ldl;                            // [rows_pad][Ap] fp32 (bf16_logits_kernel)
+    const float* vhead; int ldv; int vsplit; size_t vstride; // [vsplit][rows_pad][ldv] fp32 partial products, column 0 (bf16_value_head_kernel)
+};
+__device__ __forceinline__ int wide_col(int lane, int e) { return 256 * (e >> 2) + 4 * lane + (e & 3); }
+template <int EPT>
+__device__ __forceinline__ void wide_load_logits(float (&lg)[EPT], const float* __restrict__ prow, int lane, int Ap) {
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        const int j = 256 * q + 4 * lane;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j < Ap) v = *reinterpret_cast<const float4*>(prow + j);
+        lg[4 * q] = v.x; lg[4 * q + 1] = v.y; lg[4 * q + 2] = v.z; lg[4 * q + 3] = v.w;
+    }
+}
+// row `prow` of an [n, A] operand; columns that do not exist read `fill`
+template <int EPT>
+__device__ __forceinline__ void wide_load_row(float (&x)[EPT], const float* __restrict__ prow, int lane, int A, float fill) {
+    const bool vec = (A & 3) == 0;
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        const int j = 256 * q + 4 * lane;
+        if (vec) {
+            float4 v = make_float4(fill, fill, fill, fill);
+            if (j < A) v = *reinterpret_cast<const float4*>(prow + j);
+            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) x[4 * q + c] = j + c < A ? prow[j + c] : fill;
+        }
+    }
+}
+// The row statistics ALL THREE kernels need, in ONE shape (their neglogp is then the same bits on the same logits): one (value, index) butterfly for the maximum m over
+// the allowed categories and its index (lowest on a tie; MASK: the index starts at A, "none yet", cat_take), a0 = l - m, ex = exp(a0) ONCE per element (normaliser, entropy,
+// gradient and probabilities reuse it), one butterfly for z = sum of ex over the allowed ones: a lane's elements in rising column order, then steps 32 .. 1.
+// ok[e]: column wide_col(lane, e) exists and is allowed.
+template <int EPT, bool MASK>
+__device__ __forceinline__ void wide_row_stats(const float (&lg)[EPT], const bool (&ok)[EPT], int lane, int A, int& il, float (&a0)[EPT], float (&ex)[EPT], float& z) {
+    float bl = -INFINITY;
+    il = MASK ? A : 0;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e)
+        if (ok[e]) cat_take<MASK>(lg[e], wide_col(lane, e), A, bl, il);
+    wave_argmax<true>(bl, il);
+    float zs = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { a0[e] = lg[e] - bl; ex[e] = expf(a0[e]); if (ok[e]) zs += ex[e]; }
+    z = wave_sum_all<true>(zs);
+}
+// a0 of category `act` (held by exactly one lane; the others add zeros)
+template <int EPT>
+__device__ __forceinline__ float wide_row_pick(const float (&a0)[EPT], const bool (&ok)[EPT], int lane, int act) {
+    float la = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) if (ok[e] && wide_col(lane, e) == act) la = a0[e];
+    return wave_sum_all<true>(la);
+}
+// the row's entropy: cat_entropy_term over the allowed elements, one butterfly
+template <int EPT>
+__device__ __forceinline__ float wide_row_entropy(const float (&a0)[EPT], const float (&ex)[EPT], const bool (&ok)[EPT], float z, float lz) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) if (ok[e]) s += cat_entropy_term(ex[e], z, lz, a0[e]);
+    return wave_sum_all<true>(s);
+}
+template <int EPT, bool MASK>
+__device__ __forceinline__ void wide_ok(bool (&ok)[EPT], const float (&mk)[EPT], int lane, int A) {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { ok[e] = wide_col(lane, e) < A; if constexpr (MASK) ok[e] = ok[e] && mk[e] != 0.f; }
+}
+
+// act epilogue (bf16_sample_kernel<CAT[, MASK]>'s rules): every load of the lane first -- its logit quads, mask quads, uniforms, (lane 0) the value's partial products --
+// then the Gumbel argmax over the allowed set, the row statistics, neglogp = log z - a0[action].  A forbidden category keeps its uniform: the counter draw is keyed by
+// (seed, global row, step, j), j up to 1023.  No LDS, no barrier: a dead row's wave returns at once.
+struct SampleArgsW {
+    WideHeadIn in;
+    const float* noise; const float* mask;              // [n, A] each; noise null: ctr_uniform; mask read by the <.., MASK> instantiations only
+    float* action; float* det_action; float* value; float* neglogp;
+    int n, A, Ap; uint32_t seed, rng_step, row_base;
+};
+template <int EPT, bool MASK>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_wide_kernel(SampleArgsW a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    float lg[EPT], u[EPT], mk[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+    if constexpr (MASK) wide_load_row<EPT>(mk, a.mask + (size_t)row * a.A, lane, a.A, 0.f);
+    if (a.noise) wide_load_row<EPT>(u, a.noise + (size_t)row * a.A, lane, a.A, 0.5f);
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && a.value);
+    bool ok[EPT];
+    wide_ok<EPT, MASK>(ok, mk, lane, a.A);
+    if (!a.noise) {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) { const int j = wide_col(lane, e); u[e] = j < a.A ? ctr_uniform(a.seed, a.row_base + row, a.rng_step, j) : 0.5f; }
+    }
+    float bp = -INFINITY;
+    int ip = MASK ? a.A : 0;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const float pl = gumbel(lg[e], u[e]);
+        if (ok[e] && (pl > bp || (MASK && ip == a.A))) { bp = pl; ip = wide_col(lane, e); }
+    }
+    wave_argmax<true>(bp, ip);
+    int il;
+    float a0[EPT], ex[EPT], z;
+    wide_row_stats<EPT, MASK>(lg, ok, lane, a.A, il, a0, ex, z);
+    ip = min(ip, a.A - 1); il = min(il, a.A - 1);            // (a row without an allowed category, which the host checks refuse, ends at A)
+    const float la = wide_row_pick<EPT>(a0, ok, lane, ip);
+    if (lane == 0) {
+        if (a.action) a.action[row] = (float)ip;
+        if (a.det_action) a.det_action[row] = (float)il;
+        if (a.neglogp) a.neglogp[row] = logf(z) - la;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.in.vsplit);
+    }
+}
+
+// policy query (bf16_eval_kernel<CAT[, MASK]>'s rules) with the GIVEN category where the step has the drawn one: the action ppo_step sampled gets ppo_step's neglogp bit
+// for bit.  params [n, W = A]: p_j = ex_j / z, exactly +0 for a forbidden category.  The index is compared with the lane's columns and never indexes anything.
+struct EvalArgsW {
+    WideHeadIn in;
+    const float* actions;               // [n] category indices or null (then neglogp is not asked for)
+    const float* mask;                  // [n, A]; read by the <.., MASK> instantiations only
+    float* value; float* neglogp; float* entropy; float* params;
+    int n, A, Ap, W;
+};
+template <int EPT, bool MASK>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_eval_wide_kernel(EvalArgsW a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    float lg[EPT], mk[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+    if constexpr (MASK) wide_load_row<EPT>(mk, a.mask + (size_t)row * a.A, lane, a.A, 0.f);
+    const int act = a.actions ? (int)a.actions[row] : -1;
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && a.value);
+    bool ok[EPT];
+    wide_ok<EPT, MASK>(ok, mk, lane, a.A);
+    int il;
+    float a0[EPT], ex[EPT], z;
+    wide_row_stats<EPT, MASK>(lg, ok, lane, a.A, il, a0, ex, z);
+    const float lz = logf(z);
+    const float la = wide_row_pick<EPT>(a0, ok, lane, act);
+    const float ent = wide_row_entropy<EPT>(a0, ex, ok, z, lz);
+    if (a.params) {
+        float* prow = a.params + (size_t)row * a.W;
+        const bool vec = ((a.A | a.W) & 3) == 0;
+#pragma unroll
+        for (int q = 0; q < EPT / 4; ++q) {
+            const int j = 256 * q + 4 * lane;
+            float p[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p[c] = ok[4 * q + c] ? ex[4 * q + c] / z : 0.f;
+            if (vec) { if (j < a.A) *reinterpret_cast<float4*>(prow + j) = make_float4(p[0], p[1], p[2], p[3]); }
+            else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) if (j + c < a.A) prow[j + c] = p[c];
+            }
+        }
+    }
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = lz - la;
+        if (a.entropy) a.entropy[row] = ent;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.in.vsplit);
+    }
+}
+
+// loss + d logits (bf16_loss_kernel<CAT[, MASK]>'s rules and the assembly's contract): BL_ROWS rows per block, one slot row per block; d logits leave as one 8-byte bf16
+// store per quad and as fp32 into the block's [BL_ROWS][Ap] LDS tile, whose column sums -- of the fp32 values, not of their bf16 roundings -- go to slot_head; the aux
+// (d logstd) words are written as zeros (the all-zero d logstd tile of the 128-wide form is not carried: at Ap = 1024 the tile is 64 KB, with the term rows just past
+// the default dynamic-LDS limit, which set_lds_bf16_wide raises); pt[1] is the entropy.  Forbidden categories, padding columns A <= j < Ap and dead rows: exactly +0.
+// Surrogate, value tower and the slot epilogue's tail: bf16_loss_kernel's statements.
+struct LossArgsW {
+    WideHeadIn in;
+    const float* actions; const float* advs; const float* returns; const float* old_values; const float* old_neglogp;
+    const float* hyper;                 // {lr, cliprange, vclip_range, vclip_off}
+    const float* mask;                  // [n][A] in minibatch order; read by the <.., MASK> instantiations only
+    int n, A, Ap; float inv_n, ent_coef, vf_coef;
+    bf16_t* dhead[2];                   // [rows_pad][Ap]  (tower 1: only column 0 is ever non-zero)
+    float* slots[2]; int slot_w, slot_head, slot_aux, slot_loss;
+};
+#define BLW_LDS_BYTES(Ap) ((size_t)(BL_ROWS * (Ap) + 6 * BL_ROWS) * sizeof(float))
+template <int EPT, bool MASK>
+__global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_wide_kernel(LossArgsW a) {
+    extern __shared__ __attribute__((aligned(16))) float ls[];      // [R][Ap] d logits | [R][4] pi terms | [R][2] vf terms
+    float* dl_s = ls; float* pt = ls + BL_ROWS * a.Ap; float* vt = pt + 4 * BL_ROWS;
+    const int tid = threadIdx.x, r = tid >> 6, lane = tid & 63;
+    const int row = blockIdx.x * BL_ROWS + r;
+    const bool live = row < a.n;
+    const float cr = a.hyper[1];
+    const float vcr = a.hyper[2];                   // the value tower's clip range and switch (vf_loss_row)
+    const float voff = a.hyper[3];
+    const float g = a.inv_n;
+    // every load of the lane first (a dead row of the last block reads its own padded logits row and nothing else)
+    float lg[EPT], mk[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) mk[e] = 1.f;
+    if constexpr (MASK) { if (live) wide_load_row<EPT>(mk, a.mask + (size_t)row * a.A, lane, a.A, 0.f); }
+    const int cact = live ? (int)a.actions[row] : -1;
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && live);
+    const float adv = live ? a.advs[row] : 0.f;
+    const float old_nlp_in = live ? a.old_neglogp[row] : 0.f;
+    float Rv = 0.f, vo = 0.f;
+    if (lane == 0 && live) { Rv = a.returns[row]; vo = a.old_values[row]; }
+    // policy tower
+    bool ok[EPT];
+    wide_ok<EPT, MASK>(ok, mk, lane, a.A);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) lg[e] = live ? lg[e] : 0.f;
+    int il;
+    float a0[EPT], ex[EPT], z;
+    wide_row_stats<EPT, MASK>(lg, ok, lane, a.A, il, a0, ex, z);
+    const float lz = logf(z);
+    const float la = wide_row_pick<EPT>(a0, ok, lane, cact);
+    const float sent = wide_row_entropy<EPT>(a0, ex, ok, z, lz);
+    const float nlp = lz - la;
+    const float old_nlp = live ? old_nlp_in : nlp;
+    const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
+    const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
+    if (lane == 0) surrogate_terms(sr, nlp, old_nlp, sent, cr, live, pt, r);
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        const int j = 256 * q + 4 * lane;
+        if (j < a.Ap) {
+            float d[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int e = 4 * q + c;
+                d[c] = 0.f;
+                if (live && ok[e]) d[c] = cat_grad_elem(d_nlp, ex[e], z, a0[e], lz, sent, j + c, cact, a.ent_coef, g);
+            }
+            *reinterpret_cast<float4*>(dl_s + r * a.Ap + j) = make_float4(d[0], d[1], d[2], d[3]);
+            bf16x4 o; o[0] = (bf16_t)d[0]; o[1] = (bf16_t)d[1]; o[2] = (bf16_t)d[2]; o[3] = (bf16_t)d[3];
+            *reinterpret_cast<bf16x4*>(a.dhead[0] + (size_t)row * a.Ap + j) = o;
+        }
+    }
+    // value tower (G:10213-10837, G:14975-19571)
+    if (lane == 0) {
+        float dv = 0.f, lossv = 0.f;
+        if (live) vf_loss_row(head_parts_sum(vp, a.in.vsplit), Rv, vo, vcr, voff, a.vf_coef * 0.5f * a.inv_n, lossv, dv);
+        vt[r * 2] = dv; vt[r * 2 + 1] = lossv;
+        a.dhead[1][(size_t)row * a.Ap] = (bf16_t)dv;
+    }
+    __syncthreads();
+    float* s0 = a.slots[0] + (size_t)blockIdx.x * a.slot_w;
+    float* s1 = a.slots[1] + (size_t)blockIdx.x * a.slot_w;
+    for (int j = tid; j < a.Ap; j += 64 * BL_ROWS) {          // db_pi: fp32 sums of the fp32 values in row order; the aux words: zeros
+        float sb = 0.f;
+#pragma unroll
+        for (int q = 0; q < BL_ROWS; ++q) sb += dl_s[q * a.Ap + j];
+        s0[a.slot_head + j] = sb; s0[a.slot_aux + j] = 0.f;
+    }
+    if (tid >= 64 * BL_ROWS - 64 && tid < 64 * BL_ROWS - 60) { const int k = tid - (64 * BL_ROWS - 64); float s = 0.f; for (int q = 0; q < BL_ROWS; ++q) s += pt[q * 4 + k]; s0[a.slot_loss + k] = s; }
+    if (tid == 64 * BL_ROWS - 32) { float sb = 0.f, sl = 0.f; for (int q = 0; q < BL_ROWS; ++q) { sb += vt[q * 2]; sl += vt[q * 2 + 1]; } s1[a.slot_head] = sb; s1[a.slot_loss] = sl; }
+}

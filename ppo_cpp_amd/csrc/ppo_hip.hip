@@ -71,7 +71,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_HOST_STEP_CAT, KV_NARROW_HOST_STEP_CAT_MASK, KV_NARROW_HOST_STEP_MCAT, KV_NARROW_HOST_STEP_MCAT_MASK,
                      KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
                      KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
-                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_BF16_STEP_MBIN, KV_BF16_TRAIN_MBIN, KV_TOTAL };
+                     KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_BF16_STEP_MBIN, KV_BF16_TRAIN_MBIN,
+                     KV_BF16_STEP_WCAT, KV_BF16_STEP_WCAT_MASK, KV_BF16_TRAIN_WCAT, KV_BF16_TRAIN_WCAT_MASK, KV_TOTAL };
 // ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all,
 // which is FROZEN in turn at the first KV_ALL_COUNT rows (a caller asserts that count too).  Every variant, later ones included, is reached by name through
 // ppo_kernel_count and enumerated by ppo_kernel_variant_name: no caller may hold THAT list's length.
@@ -79,7 +80,7 @@ constexpr int KV_LEGACY_COUNT = 60;
 constexpr int KV_ALL_COUNT = 62;
 static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
 static_assert(KV_ALL_COUNT == KV_TRAIN8_MBIN, "the rows of ppo_kernel_counts_all end where the first variant named after it begins");
-// The variant list (KV_TOTAL = 65 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
+// The variant list (KV_TOTAL = 69 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
 // hands out one name at a time, and ppo_host_learn_binary's walk stops at its callers' 64 entries itself (it ends one name short of the list).
 // KV_COUNT below is FROZEN at the 63 names in front of the bf16 <mbin> pair, and the assertion on it can no longer fail: it constrains nothing.  It stands only because
 // tests/test_multi_binary.py::test_source_names_the_head_in_every_layer looks for this line of text; when that test's pin is updated, both lines go.
@@ -124,7 +125,10 @@ const char* kVariantNames[KV_TOTAL] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "train8_kernel<mbin>",
                                        // a multi-binary PPO_BF16 handle (ppo_create_ex with PPO_ACT_BF16_BINARY_HEAD): counted INSTEAD of "bf16_step_sequence" / "bf16_train_sequence";
                                        // ppo_kernel_count / ppo_kernel_variant_name only
-                                       "bf16_step_sequence<mbin>", "bf16_train_sequence<mbin>"};
+                                       "bf16_step_sequence<mbin>", "bf16_train_sequence<mbin>",
+                                       // a wide categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD, act_dim > 128): counted INSTEAD of the "bf16_*_sequence<cat[,mask]>"
+                                       // names; ppo_kernel_count / ppo_kernel_variant_name only.  ("<cat,mask,wide>" would pass the 31 characters a variant name may have.)
+                                       "bf16_step_sequence<wcat>", "bf16_step_sequence<wcat,mask>", "bf16_train_sequence<wcat>", "bf16_train_sequence<wcat,mask>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -314,6 +318,8 @@ struct ppo_handle {
         bf16_t *hb[2][PPO_MAX_LAYERS]{}, *dy[2][PPO_MAX_LAYERS]{};     // [Rcap][Hp_l]: tanh outputs and the gradients w.r.t. the pre-activations
         float* head_out[2]{};                           // [GB_HEAD_SPLIT][Rcap][Ap] fp32 partial products of the head GEMM's reduction ranges
         int head_split = 1;                             // ranges the last bf16_forward used
+        bool wide = false;                              // PPO_ACT_BF16_WIDE_HEAD took effect (categorical, act_dim > 128): head_out[0] is [1][Rcap][Ap] unsplit logits (bf16_logits_kernel),
+                                                        // head_out[1] a 128-column image (bf16_value_head_kernel), the row kernels are the <EPT, MASK> wide forms
         // the fused assembly + Adam launch does not write the assembled gradient: whoever asks for it (ppo_get_last_grad, ppo_debug_buffer) has it rebuilt
         // from the last train step's slabs first (bf16_materialize_grad).  enqueued: the last train step ENQUEUED; captured: the last step of the captured update
         // graph (the host code of a train step does not run on a replay, so the whole value is restored after one); ran: the last train step that RAN -- on: h->grad
@@ -1030,6 +1036,93 @@ int bf16_gemm(ppo_handle* h, const GemmArgs& a, int I, int J) {
     return 0;
 }
 
+// ---- the wide categorical head (ppo_handle::Bf16::wide): launches of bf16_logits_kernel, bf16_value_head_kernel and the <EPT, MASK> row kernels ----------------------
+// the row kernels' instantiation for A categories: 4, 8 or 16 logits per lane (A <= 256 / 512 / 1024), plain or masked
+template <class F>
+static void with_wide_row(int A, bool masked, F&& f) {
+    auto ept = [&](auto M) {
+        if (A <= 256) f(std::integral_constant<int, 4>{}, M);
+        else if (A <= 512) f(std::integral_constant<int, 8>{}, M);
+        else f(std::integral_constant<int, 16>{}, M);
+    };
+    if (masked) ept(std::true_type{}); else ept(std::false_type{});
+}
+// Tile height of the logits product.  256-row tiles (WM 4) stream each weight panel half as often and are what the hidden layers use, so they are taken when the row
+// count is a whole number of them AND they cover the chip (one workgroup per CU at least); otherwise 128-row tiles (WM 2): twice the workgroups, and a row count that is
+// an odd multiple of 128 -- the act step's 64 environments are one 128-row tile -- pads no further than the workspaces already do.  The result does not depend on the
+// choice (bf16_logits_kernel).
+static int bf16_logits_wm(const ppo_handle* h, int Rp) {
+    const int tiles4 = (Rp / 256) * (h->net.Ap / GB_N);
+    return Rp % 256 == 0 && tiles4 >= std::max(h->bf.n_cu, 1) ? 4 : 2;
+}
+// logits = H_L W_pi + b_pi into head_out[0] ([Rcap][Ap], unsplit), the value's GB_HEAD_SPLIT partial products into head_out[1] ([split][Rcap][128])
+int bf16_wide_heads(ppo_handle* h, int Rp) {
+    ppo_handle::Bf16& b = h->bf;
+    const NetDev& n = h->net;
+    const int HpL = n.Hp[n.L - 1];
+    if (n.Ap % GB_N != 0 || n.Ap > 1024) return fail(h, "bf16 path: the wide head takes a padded width of 128 .. 1024 in steps of 128 (Ap = %d)", n.Ap);
+    LogitsArgsB la{};
+    la.H = b.hb[0][n.L - 1]; la.ldh = HpL; la.W = b.theta_bf + n.wmu_off; la.ldw = n.Ap; la.bias = h->theta + n.bmu_off; la.F = b.head_out[0]; la.ldf = n.Ap; la.K = HpL;
+    if (bf16_logits_wm(h, Rp) == 4) {
+        la.tiles_i = Rp / 256;
+        hipLaunchKernelGGL(bf16_logits_kernel<4>, dim3(la.tiles_i * (n.Ap / GB_N)), dim3(GB_THREADS(4)), GB_LDS_BYTES(4), h->stream, la);
+    } else {
+        la.tiles_i = Rp / 128;
+        hipLaunchKernelGGL(bf16_logits_kernel<2>, dim3(la.tiles_i * (n.Ap / GB_N)), dim3(GB_THREADS(2)), GB_LDS_BYTES(2), h->stream, la);
+    }
+    HIP_OK(h, hipGetLastError());
+    HeadArgsB ha{};
+    ha.H[1] = b.hb[1][n.L - 1]; ha.W[1] = b.theta_bf + n.wv_off; ha.bias[1] = h->theta + n.bv_off; ha.F[1] = b.head_out[1];
+    ha.ldh = HpL; ha.ldw = n.Ap; ha.ldf = GB_N; ha.K = HpL;
+    int ks = GB_HEAD_SPLIT;                                    // bf16_forward's rule: the act model and the train model cut the reduction alike
+    while (ks > 1 && (HpL / ks) % 32) ks /= 2;
+    ha.ksplit = ks; ha.f_split = (size_t)b.Rcap * GB_N; b.head_split = ks;
+    hipLaunchKernelGGL(bf16_value_head_kernel, dim3((Rp / BH_ROWS) * ks), dim3(256), BH_LDS_BYTES, h->stream, ha);
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+static WideHeadIn bf16_wide_in(const ppo_handle* h) {
+    const ppo_handle::Bf16& b = h->bf;
+    return WideHeadIn{b.head_out[0], h->net.Ap, b.head_out[1], GB_N, b.head_split, (size_t)b.Rcap * GB_N};
+}
+int bf16_wide_sample(ppo_handle* h, const StepArgs& a) {
+    const NetDev& n = h->net;
+    SampleArgsW sa{};
+    sa.in = bf16_wide_in(h); sa.noise = a.noise; sa.mask = a.mask; sa.action = a.action; sa.det_action = a.det_action; sa.value = a.value; sa.neglogp = a.neglogp;
+    sa.n = a.n; sa.A = n.A; sa.Ap = n.Ap; sa.seed = a.seed; sa.rng_step = a.rng_step; sa.row_base = a.row_base;
+    const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
+    with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_sample_wide_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, sa); });
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+int bf16_wide_eval(ppo_handle* h, const EvalArgs& a, int r0, int rows) {
+    const NetDev& n = h->net;
+    EvalArgsW ea{};
+    ea.in = bf16_wide_in(h);
+    ea.actions = a.actions ? a.actions + (size_t)r0 * h->Aw : nullptr; ea.mask = a.mask ? a.mask + (size_t)r0 * n.A : nullptr;
+    ea.value = a.value ? a.value + r0 : nullptr; ea.neglogp = a.neglogp ? a.neglogp + r0 : nullptr; ea.entropy = a.entropy ? a.entropy + r0 : nullptr;
+    ea.params = a.params ? a.params + (size_t)r0 * a.W : nullptr;
+    ea.n = rows; ea.A = n.A; ea.Ap = n.Ap; ea.W = a.W;
+    const dim3 grid((rows + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
+    with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_eval_wide_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, ea); });
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+int bf16_wide_loss(ppo_handle* h, const TrainArgs& ta, int Rp) {
+    ppo_handle::Bf16& b = h->bf;
+    const NetDev& n = h->net;
+    LossArgsW la{};
+    la.in = bf16_wide_in(h);
+    la.actions = ta.actions; la.advs = ta.advs; la.returns = ta.returns; la.old_values = ta.old_values; la.old_neglogp = ta.old_neglogp; la.hyper = h->hyper; la.mask = ta.mask;
+    la.n = ta.n; la.A = n.A; la.Ap = n.Ap; la.inv_n = ta.inv_n; la.ent_coef = n.ent_coef; la.vf_coef = n.vf_coef;
+    for (int t = 0; t < 2; ++t) { la.dhead[t] = b.dhead[t]; la.slots[t] = h->slots[t]; }
+    la.slot_w = n.slot_w; la.slot_head = n.slot_head; la.slot_aux = n.slot_aux; la.slot_loss = n.slot_loss;
+    const dim3 grid(Rp / BL_ROWS), blk(64 * BL_ROWS);
+    with_wide_row(n.A, ta.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_loss_wide_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, BLW_LDS_BYTES(n.Ap), h->stream, la); });
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+
 // forward of both towers on `rows` staged rows: hidden layers (bias + tanh) and the padded heads (fp32 out)
 int bf16_forward(ppo_handle* h, int Rp, const bf16_t* x0_override = nullptr) {
     ppo_handle::Bf16& b = h->bf;
@@ -1054,6 +1147,7 @@ int bf16_forward(ppo_handle* h, int Rp, const bf16_t* x0_override = nullptr) {
         for (int l = 0; l < n.L; ++l) if (bf16_gemm<GEPI_TANH>(h, fl[l], Rp, n.Hp[l])) return -1;
     // the heads: 64 rows of one tower and one reduction range per workgroup (bf16_heads_kernel)
     const int HpL = n.Hp[n.L - 1];
+    if (b.wide) return bf16_wide_heads(h, Rp);
     if (n.Ap != GB_N) return fail(h, "bf16 path: the head kernel's images are 128 columns wide (Ap = %d)", n.Ap);
     HeadArgsB ha{};
     for (int t = 0; t < 2; ++t) {
@@ -1091,6 +1185,7 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     const NetDev& n = h->net;
     const int Rp = ru(a.n, GB_PAD);
     if (bf16_stage(h, a.obs, a.n, Rp, a.nz, a.obs_out) || bf16_forward(h, Rp)) return -1;
+    if (h->bf.wide) return bf16_wide_sample(h, a);
     SampleArgsB sa{};
     sa.head[0] = h->bf.head_out[0]; sa.head[1] = h->bf.head_out[1]; sa.ldh = n.Ap; sa.hsplit = h->bf.head_split; sa.hstride = (size_t)h->bf.Rcap * n.Ap; sa.logstd = h->theta + n.ls_off;
     sa.noise = a.noise; sa.action = a.action; sa.det_action = a.det_action; sa.value = a.value; sa.neglogp = a.neglogp;
@@ -1108,7 +1203,7 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
 // step of max_rows needs.  Writes what ppo_value writes (x0, the tanh outputs, the head outputs).  Not counted in ppo_kernel_counts; profiling class policy_step.
 int launch_eval_bf16(ppo_handle* h, const EvalArgs& a) {
     const NetDev& n = h->net;
-    if (n.A > 128) return fail(h, "bf16 path: more than 128 actions");
+    if (n.A > 128 && !h->bf.wide) return fail(h, "bf16 path: more than 128 actions");
     const int chunk = h->cfg.max_rows > 0 ? h->cfg.max_rows : 65536;
     const int Aw = h->Aw;
     for (int r0 = 0; r0 < a.n; r0 += chunk) {
@@ -1117,6 +1212,7 @@ int launch_eval_bf16(ppo_handle* h, const EvalArgs& a) {
         ProfScope ps(h, PK_STEP);
         const int Rp = ru(rows, GB_PAD);
         if (bf16_stage(h, a.obs + (size_t)r0 * n.O, rows, Rp, no_norm_fwd(), nullptr) || bf16_forward(h, Rp)) return -1;
+        if (h->bf.wide) { if (bf16_wide_eval(h, a, r0, rows)) return -1; continue; }
         EvalArgsB ea{};
         ea.head[0] = h->bf.head_out[0]; ea.head[1] = h->bf.head_out[1]; ea.ldh = n.Ap; ea.hsplit = h->bf.head_split; ea.hstride = (size_t)h->bf.Rcap * n.Ap; ea.logstd = h->theta + n.ls_off;
         ea.actions = a.actions ? a.actions + (size_t)r0 * Aw : nullptr; ea.mask = a.mask ? a.mask + (size_t)r0 * n.A : nullptr;
@@ -1152,11 +1248,14 @@ int bf16_train_fwd_bwd(ppo_handle* h, const TrainArgs& ta, int Rp, bool links_on
     la.old_neglogp = ta.old_neglogp; la.hyper = h->hyper; la.n = ta.n; la.A = n.A; la.Ap = n.Ap; la.rows_pad = b.Rcap; la.inv_n = ta.inv_n;
     la.ent_coef = n.ent_coef; la.vf_coef = n.vf_coef; la.slot_w = n.slot_w; la.slot_head = n.slot_head; la.slot_aux = n.slot_aux; la.slot_loss = n.slot_loss;
     la.mask = ta.mask;
+    if (b.wide) { if (bf16_wide_loss(h, ta, Rp)) return -1; }
+    else {
     if (n.A > 64 * BL_EPT) return fail(h, "bf16 path: more than %d actions", 64 * BL_EPT);
     const dim3 lgrid(Rp / BL_ROWS), lblk(64 * BL_ROWS);
     const size_t llds = (size_t)(2 * BL_ROWS * n.Ap + 6 * BL_ROWS) * sizeof(float);
     with_head(head_of(h, ta.mask != nullptr), [&](auto H) { hipLaunchKernelGGL(bf16_loss_fn(H), lgrid, lblk, llds, h->stream, head_args<LossArgsBM>(H, h, la)); });
     HIP_OK(h, hipGetLastError());
+    }
     if (links_only) return 0;
     GemmArgs bl[PPO_MAX_LAYERS];
     int outw[PPO_MAX_LAYERS];
@@ -1312,7 +1411,8 @@ static auto nw_rollout_fn(T) {
 int launch_step(ppo_handle* h, const StepArgs& a0) {
     const Head hd = head_of(h, a0.mask != nullptr);                 // (a multi-categorical handle: bf16 only when created with PPO_ACT_BF16_MULTI_HEAD; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
     if (a0.mask && !hd.cat) return fail(h, "policy step: an action mask needs a categorical handle");
-    ++h->kv[kHeadVariant[h->bf.on ? KF_BF16_STEP : !h->narrow ? KF_POLICY_STEP : h->nw_static ? KF_NARROW_STEP_STATIC : KF_NARROW_STEP][hd.index()]];
+    if (h->bf.wide) ++h->kv[hd.mask ? KV_BF16_STEP_WCAT_MASK : KV_BF16_STEP_WCAT];
+    else ++h->kv[kHeadVariant[h->bf.on ? KF_BF16_STEP : !h->narrow ? KF_POLICY_STEP : h->nw_static ? KF_NARROW_STEP_STATIC : KF_NARROW_STEP][hd.index()]];
     if (h->bf.on) return launch_step_bf16(h, a0);
     ProfScope ps(h, PK_STEP);
     with_head(hd, [&](auto H) {
@@ -1555,6 +1655,17 @@ static bool set_lds_ladder(const ppo_handle* h) {
     set(weight_grad_kernel<4>, 4 * (64 * 64 + 1024) * 4); set(weight_grad_kernel<1>, 4 * (64 * 64 + 1024) * 4);
     return ok;
 }
+// the wide categorical head of the bf16 path likewise (ppo_handle::Bf16::wide): the logits product's ring, the value head's image, and the loss kernel's d-logits tile,
+// which at Ap = 1024 is 64 KB + the term rows -- past the default limit; every instantiation is set to the largest form's size
+static bool set_lds_bf16_wide(const ppo_handle* h) {
+    if (!h->bf.wide) return true;
+    bool ok = true;
+    auto set = [&](auto f, size_t bytes) { ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess; };
+    set(bf16_logits_kernel<4>, GB_LDS_BYTES(4)); set(bf16_logits_kernel<2>, GB_LDS_BYTES(2)); set(bf16_value_head_kernel, BH_LDS_BYTES);
+    for (int A : {256, 512, 1024}) for (bool m : {false, true})
+        with_wide_row(A, m, [&](auto E, auto M) { set(bf16_loss_wide_kernel<decltype(E)::value, decltype(M)::value>, BLW_LDS_BYTES(1024)); });
+    return ok;
+}
 // the narrow family likewise, every shape.  The kernels with a head: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl),
 // host step, resident rollout (one and two groups of rows); then the kernels without a head axis
 static bool set_lds_narrow(const ppo_handle* h) {
@@ -1706,7 +1817,8 @@ static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool 
     const int Rp = ru(ta.n, GB_PAD);
     const Head hd = head_of(h, ta.mask != nullptr);                 // (a multi-categorical handle: PPO_ACT_BF16_MULTI_HEAD, ppo_create_multi_ex)
     if (ta.mask && !hd.cat) return fail(h, "train step: an action mask needs a categorical handle");
-    ++h->kv[kHeadVariant[KF_BF16_TRAIN][hd.index()]];
+    if (h->bf.wide) ++h->kv[hd.mask ? KV_BF16_TRAIN_WCAT_MASK : KV_BF16_TRAIN_WCAT];
+    else ++h->kv[kHeadVariant[KF_BF16_TRAIN][hd.index()]];
     h->bf.lazy.enqueued.on = false;
     if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
     { ProfScope ps(h, PK_TRAIN_FB); if (bf16_train_fwd_bwd(h, ta, Rp)) return -1; }
@@ -1985,7 +2097,7 @@ void ppo_config_default(ppo_config* cfg, int32_t obs_dim, int32_t act_dim, int32
 const char* ppo_last_error(const ppo_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 // what a create entry point was asked for.  narrow / pair / bf16: the family opt-ins, gated on the distribution and dtype that give the flag a meaning (elsewhere: accepted, changes nothing)
-struct CreateRequest { int dist, Aw; CompTable comp; bool narrow, pair, bf16; };
+struct CreateRequest { int dist, Aw; CompTable comp; bool narrow, pair, bf16, wide; };
 
 // nvec != null: a multi-categorical handle (ppo_create_multi_ex has checked the table).  No HIP call: a machine without a GPU reports a refusal's own reason
 static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_t* nvec, int32_t n_components, CreateRequest& rq) {
@@ -1997,15 +2109,21 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     // flags belong to PPO_ACT_MULTI_BINARY alone: beside any other distribution they stay in and are refused (ppo_create_multi_ex has refused them: "unknown flag bit")
     int32_t dist = action_dist & ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS | (nvec ? PPO_ACT_BF16_MULTI_HEAD : 0));
     if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS | PPO_ACT_BF16_BINARY_HEAD)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
+    // PPO_ACT_BF16_WIDE_HEAD likewise belongs to PPO_ACT_CATEGORICAL alone
+    if (!nvec && (dist & ~(int32_t)PPO_ACT_BF16_WIDE_HEAD) == PPO_ACT_CATEGORICAL) dist = PPO_ACT_CATEGORICAL;
     const bool cat = dist == PPO_ACT_CATEGORICAL, mcat = dist == PPO_ACT_MULTI_CATEGORICAL, mbin = dist == PPO_ACT_MULTI_BINARY, bf16 = cfg->compute_dtype == PPO_BF16;
     if (dist != PPO_ACT_GAUSSIAN && !cat && !mbin && !(mcat && nvec))
         return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
-                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)%s", (int)dist,
-                    (dist & PPO_ACT_BF16_BINARY_HEAD) ? "; PPO_ACT_BF16_BINARY_HEAD belongs to PPO_ACT_MULTI_BINARY alone" : "");
+                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)%s%s", (int)dist,
+                    (dist & PPO_ACT_BF16_BINARY_HEAD) ? "; PPO_ACT_BF16_BINARY_HEAD belongs to PPO_ACT_MULTI_BINARY alone" : "",
+                    (dist & PPO_ACT_BF16_WIDE_HEAD) ? "; PPO_ACT_BF16_WIDE_HEAD belongs to PPO_ACT_CATEGORICAL alone" : "");
     if (cat && cfg->act_dim < 2) return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (cat && bf16 && !(action_dist & PPO_ACT_BF16_HEAD))
         return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
-    if (cat && bf16 && cfg->act_dim > 128)
+    const bool wide = cat && bf16 && (action_dist & PPO_ACT_BF16_WIDE_HEAD);
+    if (wide && cfg->act_dim > 1024)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_WIDE_HEAD: the wide categorical head of the PPO_BF16 path holds at most 1024 categories (got %d)", (int)cfg->act_dim);
+    if (cat && bf16 && !wide && cfg->act_dim > 128)
         return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
     if (mbin && bf16 && !(action_dist & PPO_ACT_BF16_BINARY_HEAD))
         return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
@@ -2019,6 +2137,7 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     rq.narrow = (action_dist & (mbin ? PPO_ACT_BINARY_SHAPE_KERNELS : cat || mcat ? PPO_ACT_SHAPE_KERNELS : 0)) != 0;
     rq.pair = (action_dist & (mbin ? PPO_ACT_BINARY_PAIR_KERNELS : cat || mcat ? PPO_ACT_PAIR_KERNELS : 0)) != 0 && cfg->compute_dtype == PPO_F32;
     rq.bf16 = (action_dist & (cat ? PPO_ACT_BF16_HEAD : mcat ? PPO_ACT_BF16_MULTI_HEAD : mbin ? PPO_ACT_BF16_BINARY_HEAD : 0)) != 0 && bf16;
+    rq.wide = wide && rq.bf16 && cfg->act_dim > 128;               // (up to 128 categories the flag changes nothing: the 128-wide kernels, their bits and their counters)
     return 0;
 }
 
@@ -2116,7 +2235,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (e != hipSuccess || ndev < 1) return fail(nullptr, "ppo_create: no HIP device available (%s); libppo_hip has no CPU fallback", hipGetErrorString(e));
     ppo_handle* h = new ppo_handle();
     h->cfg = *cfg; h->dist = rq.dist; h->Aw = rq.Aw; h->comp = rq.comp;
-    h->opt_narrow = rq.narrow; h->opt_pair = rq.pair; h->opt_bf16 = rq.bf16;
+    h->opt_narrow = rq.narrow; h->opt_pair = rq.pair; h->opt_bf16 = rq.bf16; h->bf.wide = rq.wide;
     // every failure from here on leaves through this one exit: the message moves to the create error, the handle and what it holds go
     auto bail = [&] { g_create_error = h->err; ppo_destroy(h); return -1; };
     if (open_device(h, ndev, n_cu)) return bail();                 // the device (LOCAL_RANK), its arch, the stream, the graph switch, the dtype
@@ -2132,6 +2251,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (h->dist != PPO_ACT_CATEGORICAL) h->opt_narrow = h->opt_narrow && h->narrow;
     h->opt_pair = h->opt_pair && (h->t8 || h->dw2);
     if (h->bf.on && bf16_create(h)) return bail();
+    if (!set_lds_bf16_wide(h)) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the wide categorical head's kernels"); return bail(); }
     if (narrow_extras(h, n_cu)) return bail();
     if (init_adam(h)) return bail();
     *out = h;
@@ -3822,7 +3942,8 @@ static std::vector<DbgEnt> debug_table(ppo_handle* h) {
     }();
     std::vector<DbgEnt> bfe = {
         {"bf_theta", b.on ? b.theta_bf : nullptr, P / 2}, {"bf_x0", b.on ? b.x0 : nullptr, RB * n.Kp0 / 2},
-        {"bf_head_pi", b.on ? b.head_out[0] : nullptr, (size_t)GB_HEAD_SPLIT * RB * n.Ap}, {"bf_head_vf", b.on ? b.head_out[1] : nullptr, (size_t)GB_HEAD_SPLIT * RB * n.Ap},
+        {"bf_head_pi", b.on ? b.head_out[0] : nullptr, (size_t)(b.wide ? 1 : GB_HEAD_SPLIT) * RB * n.Ap},        // (a wide categorical handle: [1][Rcap][Ap] unsplit logits)
+        {"bf_head_vf", b.on ? b.head_out[1] : nullptr, (size_t)GB_HEAD_SPLIT * RB * (b.wide ? GB_N : n.Ap)},
         {"bf_dhead_pi", b.on ? b.dhead[0] : nullptr, RB * n.Ap / 2}, {"bf_dhead_vf", b.on ? b.dhead[1] : nullptr, RB * n.Ap / 2},
         {"bf_dbias", b.on ? b.dbias : nullptr, (size_t)b.db_tiles * b.n_dbias},
     };

@@ -83,7 +83,9 @@ public:
     // ppo_create_ex with action_dist_for(env, discrete_shape_kernels) | extra_flags.  For an IMultiBinary Env, create_handle(cfg, env, &h, false,
     // PPO_ACT_BINARY_SHAPE_KERNELS) creates the multi-binary handle on the narrow <mbin> kernels where the shape qualifies, and PPO_ACT_BINARY_PAIR_KERNELS there on
     // the [256,256] train kernel pair where that shape qualifies, and PPO_ACT_BF16_BINARY_HEAD with cfg.compute_dtype = PPO_BF16 on the bf16 path (at most 128 bits);
-    // with any other Env the library refuses each of the three flags.  Returns the library's status; ppo_last_error(nullptr) has the message.
+    // with any other Env the library refuses each of the three flags.  For a discrete Env with more than 128 actions, PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD with
+    // cfg.compute_dtype = PPO_BF16 creates the handle on the bf16 path's wide categorical head (at most 1024 categories).
+    // Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);
         if (nvec.empty()) return ppo_create_ex(&cfg, action_dist_for(env, discrete_shape_kernels) | extra_flags, out);
