@@ -198,8 +198,35 @@ int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_compo
  *                        step: about 1.7 us per component of dependent butterflies.
  *                        Not the default (opt-in).  Data parallel is not available: ppo_dist_init refuses the handle ("... data parallel is not supported for a
  *                        multi-categorical PPO_BF16 handle created with PPO_ACT_BF16_MULTI_HEAD") and leaves it usable.
+ *   PPO_ACT_BF16_WIDE_MULTI_HEAD  beside PPO_ACT_BF16_MULTI_HEAD and compute_dtype PPO_BF16 it admits 128 < sum of nvec <= 1024 (more is an error that names the flag,
+ *                        the limit and the value; without the flag more than 128 keeps its refusal).  With at most 128 logits, and with PPO_F32, the flag is
+ *                        accepted and changes nothing (same kernels, bits and counts).  ppo_create_ex rejects the bit.  The logits and the value come from the wide
+ *                        categorical head's products (PPO_ACT_BF16_WIDE_HEAD, below: bf16_logits_kernel, bf16_value_head_kernel, Ap = sum of nvec rounded up to 128);
+ *                        the row arithmetic is bf16_sample_wide_multi_kernel / bf16_loss_wide_multi_kernel / bf16_eval_wide_multi_kernel<EPT, MASK> (ppo_bf16.hpp):
+ *                        that family's geometry (one wave per row, EPT = 4 / 8 / 16 logits per lane, column 256 q + 4 lane + c, every load first) and the
+ *                        multi-categorical arithmetic stated above per component, with the K reductions run FOUR COMPONENTS AT A TIME: a lane forms the partials of
+ *                        a batch of four from its registers in one sweep, the batch's 64-lane butterflies are issued interleaved (one component's cross-lane latency
+ *                        hides behind the others'), exp is taken once per element.  Three rounds of butterflies per four components where the 128-wide <mcat> walk
+ *                        has four to five per component.  A component's own reduction keeps the wide categorical kernels' one shape (a lane's elements in rising
+ *                        column order, then steps 32 .. 1): nvec = {A} gives the PPO_ACT_BF16_WIDE_HEAD handle's bits in every output, a mask of ones the unmasked
+ *                        bits, and ppo_step's neglogp, the train model's and ppo_evaluate_actions' are the same bits.  A lane's quad may hold columns of several
+ *                        components; membership is o_k <= column < o_k + n_k and an action index is only ever compared.  Forbidden categories, padding columns and
+ *                        dead rows get d logits of exactly +0; the loss kernel keeps the assembly's contract ([16][Ap] fp32 tile, fp32 column sums, aux words zeros,
+ *                        pt[1] the entropy).  Every entry point of a multi-categorical PPO_BF16 handle works as listed under PPO_ACT_BF16_MULTI_HEAD, and behind
+ *                        ppo_set_bf16_queries(h, 1) the three policy queries, ppo_distribution_width = sum of nvec; ppo_dist_init and ppo_set_target_kl refuse the
+ *                        handle as they refuse every PPO_ACT_BF16_MULTI_HEAD handle.  Counted under "bf16_step_sequence<wmcat>", "bf16_step_sequence<wmcat,mask>",
+ *                        "bf16_train_sequence<wmcat>", "bf16_train_sequence<wmcat,mask>" (31 characters, the limit) INSTEAD of the <mcat[,mask]> names -- names of
+ *                        ppo_kernel_count / ppo_kernel_variant_name only; ppo_kernel_counts keeps its 60 rows, ppo_kernel_counts_all its 62.
+ *                        Measured on an MI355X at 256 observations, [1024,1024,1024] (tools/prof_bf16_wide_multi.py; us of device time per call, median of 7 rounds, spreads 0.8 - 3.6;
+ *                        the wide categorical handle at A = 1024 | nvec = (1024,) | (256,) x 4 | (64,) x 16): train step 347.1 | 362.9 | 366.7 | 386.3 at 4096 rows,
+ *                        202.2 | 218.3 | 218.6 | 243.6 at 256; policy step 170.1 | 195.3 | 195.1 | 237.1 at 8192 rows.  Per component, (K = 16 minus K = 1) / 15, beside the
+ *                        128-wide <mcat> walk re-measured in the same run (nvec = (8,) x 16 against A = 128): 1.56 against 1.15 us (train, 4096 rows), 1.69 against
+ *                        1.47 (train, 256 rows), 2.79 against 3.52 (policy step).  The batched walk is cheaper per component in the policy step ONLY; in the train
+ *                        step it is NOT below the 128-wide walk, and one component costs 16 us (train) / 25 us (policy step) more than the wide categorical
+ *                        kernels (132 - 146 VGPRs at EPT 16 against 62 - 78; the membership tests run for all four slots of a batch).  Not tuned.
  * Any other bit is an error ("ppo_create_multi_ex: unknown flag bit 0x.."). */
 #define PPO_ACT_BF16_MULTI_HEAD 0x1000
+#define PPO_ACT_BF16_WIDE_MULTI_HEAD 0x20000
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out);
 /* the handle's component widths: returns K and fills at most `max` entries; 0 for a Gaussian or multi-binary handle, 1 with nvec[0] = A for a categorical one */
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec);

@@ -68,6 +68,7 @@ ACT_BINARY_SHAPE_KERNELS = 0x2000                       # PPO_ACT_BINARY_SHAPE_K
 ACT_BINARY_PAIR_KERNELS = 0x4000                        # PPO_ACT_BINARY_PAIR_KERNELS, likewise
 ACT_BF16_BINARY_HEAD = 0x8000                           # PPO_ACT_BF16_BINARY_HEAD, likewise
 ACT_BF16_WIDE_HEAD = 0x10000                            # PPO_ACT_BF16_WIDE_HEAD, a flag of ppo_create_ex beside PPO_ACT_CATEGORICAL only
+ACT_BF16_WIDE_MULTI_HEAD = 0x20000                      # PPO_ACT_BF16_WIDE_MULTI_HEAD, a flag of ppo_create_multi_ex only
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -106,6 +107,12 @@ class PPOHip:
     head (bf16_sample_kernel / bf16_loss_kernel<mcat[,mask]>; sum(nvec) <= 128; masks included; no data parallel), e.g.
     PPOHip(O, None, hidden, action_dist="multi_categorical", nvec=[..], compute_dtype=1, bf16_head=True).  Without it that combination is refused; on a
     compute_dtype=0 handle bf16_head changes nothing (no flag is passed).
+    multi_bf16_wide_head=True with it, compute_dtype=1 and bf16_head=True (PPO_ACT_BF16_WIDE_MULTI_HEAD; default False; a ValueError with any other action_dist):
+    up to sum(nvec) = 1024 logits on the bf16 path (bf16_logits_kernel, bf16_value_head_kernel and the bf16_*_wide_multi_kernel row kernels, which reduce four
+    components at a time; masks and, after set_bf16_queries(True), the policy queries included; no data parallel), e.g. PPOHip(O, None, hidden,
+    action_dist="multi_categorical", nvec=[..], compute_dtype=1, bf16_head=True, multi_bf16_wide_head=True).  With sum(nvec) <= 128 or compute_dtype=0 it changes
+    nothing (same kernels, bits and counts).  "bf16_step_sequence<wmcat[,mask]>" / "bf16_train_sequence<wmcat[,mask]>" are names of kernel_count() /
+    kernel_variants() only.  The attribute multi_bf16_wide_head keeps what was asked for.
 
     action_dist="multi_binary" (PPO_ACT_MULTI_BINARY; stable-baselines' Bernoulli distribution over a MultiBinary space -- "bernoulli" is no action_dist here):
     act_dim independent on / off decisions per step.  Actions are (n, act_dim) float arrays of exactly 0 or 1 (train_step and rollout_set("actions") refuse anything
@@ -136,7 +143,7 @@ class PPOHip:
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, binary_shape_kernels=False,
-                 binary_pair_kernels=False, binary_bf16_head=False, bf16_wide_head=False, **overrides):
+                 binary_pair_kernels=False, binary_bf16_head=False, bf16_wide_head=False, multi_bf16_wide_head=False, **overrides):
         multi = action_dist == "multi_categorical"
         if binary_shape_kernels and action_dist != "multi_binary":
             raise ValueError("binary_shape_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
@@ -146,6 +153,8 @@ class PPOHip:
             raise ValueError("binary_bf16_head belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if bf16_wide_head and action_dist != "categorical":
             raise ValueError("bf16_wide_head belongs to action_dist='categorical', not %r" % (action_dist,))
+        if multi_bf16_wide_head and not multi:
+            raise ValueError("multi_bf16_wide_head belongs to action_dist='multi_categorical', not %r" % (action_dist,))
         if nvec is not None and not multi:
             raise ValueError("nvec belongs to action_dist='multi_categorical', not %r" % (action_dist,))
         if multi:
@@ -175,6 +184,7 @@ class PPOHip:
         self.binary_pair_kernels = bool(binary_pair_kernels)
         self.binary_bf16_head = bool(binary_bf16_head)
         self.bf16_wide_head = bool(bf16_wide_head)
+        self.multi_bf16_wide_head = bool(multi_bf16_wide_head)
         self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
@@ -182,6 +192,8 @@ class PPOHip:
             flags = (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_PAIR_KERNELS if pair_kernels else 0)
             if bf16_head and cfg.compute_dtype == 1:
                 flags |= ACT_BF16_MULTI_HEAD
+            if multi_bf16_wide_head:
+                flags |= ACT_BF16_WIDE_MULTI_HEAD
             if (self.lib.ppo_create_multi_ex(C.byref(cfg), nv, len(nvec), flags, C.byref(h)) if flags
                     else self.lib.ppo_create_multi(C.byref(cfg), nv, len(nvec), C.byref(h))) != 0:
                 raise PPOHipError(self.lib.ppo_last_error(None).decode())

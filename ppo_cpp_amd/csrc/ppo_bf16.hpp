@@ -1956,3 +1956,357 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_wide_kernel(LossArgsW 
     if (tid >= 64 * BL_ROWS - 64 && tid < 64 * BL_ROWS - 60) { const int k = tid - (64 * BL_ROWS - 64); float s = 0.f; for (int q = 0; q < BL_ROWS; ++q) s += pt[q * 4 + k]; s0[a.slot_loss + k] = s; }
     if (tid == 64 * BL_ROWS - 32) { float sb = 0.f, sl = 0.f; for (int q = 0; q < BL_ROWS; ++q) { sb += vt[q * 2]; sl += vt[q * 2 + 1]; } s1[a.slot_head] = sb; s1[a.slot_loss] = sl; }
 }
+
+// ==== wide multi-categorical head (PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD, 128 < sum(nvec) <= 1024) ==================================================
+// K categorical components over the one wide logits row: the wide family's geometry (one wave per row, EPT logits per lane, wide_col, every load first, no LDS in the
+// sample and eval kernels), its inputs (WideHeadIn: bf16_logits_kernel, bf16_value_head_kernel) and its EPT choice, under symbols of their own.
+// The 128-wide <mcat> forms walk the components one after another: four to five DEPENDENT 64-lane butterflies per component, and a butterfly is six ds_bpermute round
+// trips that nothing hides (about 1.7 us per component).  The K reductions are independent, so here they run WM_BATCH at a time:
+//   pass A, per batch:  a lane forms the (maximum, index) partials of the batch's components from its registers in one sweep (the sample kernel: the Gumbel pairs too)
+//                       and the batch's butterflies are issued interleaved, step by step -- WM_BATCH (sample: 2 WM_BATCH) independent chains in flight; a member
+//                       element then takes a0 = l - m of its own component
+//   once per element:   ex = exp(a0)   (the 128-wide walk takes the exponential of every element once per component)
+//   pass B, per batch:  the normaliser and the pick of the action's a0, 2 WM_BATCH chains interleaved; then (loss, eval) the entropy, WM_BATCH chains
+// Three rounds of cross-lane latency per WM_BATCH components where the 128-wide walk has four to five per component (what that bought: below).  A (batch, quad) pair whose column ranges do not
+// meet is skipped on a scalar branch: a lane tests its element against the components that can hold it.
+// A component's own reduction keeps wide_row_stats / wide_row_pick / wide_row_entropy's ONE shape -- a lane's elements in rising column order, then steps 32 .. 1, the
+// identity in every lane without a member, "none yet" = one past the component's end -- so nvec = {A} gives the wide categorical kernels' bits, an all-ones mask gives
+// the unmasked bits, and step, train model and evaluate give one neglogp.  Membership is o <= col < e; an action index is compared and never indexes anything.
+// Measured (256 observations, [1024,1024,1024]): per component 1.56 us against the 128-wide walk's 1.15 in a 4096-row train step, 1.69 against 1.47 at 256
+// rows, 2.79 against 3.52 in an 8192-row policy step -- below the 128-wide walk in the policy step ONLY -- and one component costs 16 / 25 us more than the wide
+// categorical kernels (132 - 146 VGPRs at EPT 16; every slot of a batch, the empty ones included, is tested).  Not tuned.
+#define WM_BATCH 4
+struct WideBatch { int o[WM_BATCH], ce[WM_BATCH], lo, hi; };       // components k0 .. k0 + WM_BATCH - 1 (past K: empty) and the column range [lo, hi) they cover together
+__device__ __forceinline__ WideBatch wide_batch(const CompTable& t, int k0) {
+    WideBatch b;
+#pragma unroll
+    for (int c = 0; c < WM_BATCH; ++c) { const bool has = k0 + c < t.K; b.o[c] = has ? t.off[k0 + c] : 0; b.ce[c] = has ? t.off[k0 + c + 1] : 0; }
+    b.lo = b.o[0]; b.hi = t.off[min(k0 + WM_BATCH, t.K)];
+    return b;
+}
+__device__ __forceinline__ bool wide_quad_meets(const WideBatch& b, int q) { return 256 * q < b.hi && 256 * q + 256 > b.lo; }
+// pass A of one batch.  Out: il[c] / ip[c], the plain and (GUMBEL) the perturbed argmax of component c, the same pair in every lane; a0[e] of the batch's members.
+template <int EPT, bool MASK, bool GUMBEL>
+__device__ __forceinline__ void wide_batch_max(const WideBatch& b, const float (&lg)[EPT], const float (&pl)[EPT], const bool (&ok)[EPT], int lane,
+                                               float (&a0)[EPT], int (&il)[WM_BATCH], int (&ip)[WM_BATCH]) {
+    float bl[WM_BATCH], bp[WM_BATCH];
+#pragma unroll
+    for (int c = 0; c < WM_BATCH; ++c) { bl[c] = -INFINITY; bp[c] = -INFINITY; il[c] = MASK ? b.ce[c] : b.o[c]; ip[c] = il[c]; }
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        if (!wide_quad_meets(b, q)) continue;
+#pragma unroll
+        for (int e = 4 * q; e < 4 * q + 4; ++e) {
+            const int col = wide_col(lane, e);
+#pragma unroll
+            for (int c = 0; c < WM_BATCH; ++c) {
+                if (ok[e] && col >= b.o[c] && col < b.ce[c]) {
+                    cat_take<MASK>(lg[e], col, b.ce[c], bl[c], il[c]);
+                    if constexpr (GUMBEL) { if (pl[e] > bp[c] || (MASK && ip[c] == b.ce[c])) { bp[c] = pl[e]; ip[c] = col; } }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        float ov[WM_BATCH], pv[WM_BATCH];
+        int oi[WM_BATCH], pi[WM_BATCH];
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) {
+            ov[c] = wave_xor<true>(bl[c], s); oi[c] = wave_xor<true>(il[c], s);
+            if constexpr (GUMBEL) { pv[c] = wave_xor<true>(bp[c], s); pi[c] = wave_xor<true>(ip[c], s); }
+        }
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) {
+            argmax_step(bl[c], il[c], ov[c], oi[c]);
+            if constexpr (GUMBEL) argmax_step(bp[c], ip[c], pv[c], pi[c]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        if (!wide_quad_meets(b, q)) continue;
+#pragma unroll
+        for (int e = 4 * q; e < 4 * q + 4; ++e) {
+            const int col = wide_col(lane, e);
+#pragma unroll
+            for (int c = 0; c < WM_BATCH; ++c) if (col >= b.o[c] && col < b.ce[c]) a0[e] = lg[e] - bl[c];
+        }
+    }
+}
+// pass B of one batch.  act[c]: component c's action COLUMN (-1: none).  Out, per component: z, lz = log z, la = a0 of the action, (FIN >= 1) the entropy H.  A member
+// element is then finished where it lies: FIN >= 1: ex[e] becomes p = ex / z; FIN == 2 (the loss kernel): a0[e] becomes (a0 - lz) + H and hit[e] says "the action".
+template <int EPT, int FIN>
+__device__ __forceinline__ void wide_batch_sums(const WideBatch& b, float (&a0)[EPT], float (&ex)[EPT], const bool (&ok)[EPT], bool (&hit)[EPT], int lane, const int (&act)[WM_BATCH],
+                                                float (&lz)[WM_BATCH], float (&la)[WM_BATCH], float (&H)[WM_BATCH]) {
+    float z[WM_BATCH];
+#pragma unroll
+    for (int c = 0; c < WM_BATCH; ++c) { z[c] = 0.f; la[c] = 0.f; H[c] = 0.f; }
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        if (!wide_quad_meets(b, q)) continue;
+#pragma unroll
+        for (int e = 4 * q; e < 4 * q + 4; ++e) {
+            const int col = wide_col(lane, e);
+#pragma unroll
+            for (int c = 0; c < WM_BATCH; ++c) {
+                if (ok[e] && col >= b.o[c] && col < b.ce[c]) { z[c] += ex[e]; if (col == act[c]) la[c] = a0[e]; }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        float oz[WM_BATCH], ol[WM_BATCH];
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) { oz[c] = wave_xor<true>(z[c], s); ol[c] = wave_xor<true>(la[c], s); }
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) { z[c] += oz[c]; la[c] += ol[c]; }
+    }
+#pragma unroll
+    for (int c = 0; c < WM_BATCH; ++c) lz[c] = logf(z[c]);
+    if constexpr (FIN >= 1) {
+#pragma unroll
+        for (int q = 0; q < EPT / 4; ++q) {
+            if (!wide_quad_meets(b, q)) continue;
+#pragma unroll
+            for (int e = 4 * q; e < 4 * q + 4; ++e) {
+                const int col = wide_col(lane, e);
+#pragma unroll
+                for (int c = 0; c < WM_BATCH; ++c) if (ok[e] && col >= b.o[c] && col < b.ce[c]) H[c] += cat_entropy_term(ex[e], z[c], lz[c], a0[e]);
+            }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            float oh[WM_BATCH];
+#pragma unroll
+            for (int c = 0; c < WM_BATCH; ++c) oh[c] = wave_xor<true>(H[c], s);
+#pragma unroll
+            for (int c = 0; c < WM_BATCH; ++c) H[c] += oh[c];
+        }
+#pragma unroll
+        for (int q = 0; q < EPT / 4; ++q) {
+            if (!wide_quad_meets(b, q)) continue;
+#pragma unroll
+            for (int e = 4 * q; e < 4 * q + 4; ++e) {
+                const int col = wide_col(lane, e);
+#pragma unroll
+                for (int c = 0; c < WM_BATCH; ++c) {
+                    if (col >= b.o[c] && col < b.ce[c]) {
+                        if constexpr (FIN == 2) { a0[e] = cat_grad_t(a0[e], lz[c], H[c]); hit[e] = col == act[c]; }
+                        ex[e] = cat_grad_p(ex[e], z[c]);
+                    }
+                }
+            }
+        }
+    }
+}
+// row totals in component order, starting from the first component's value
+__device__ __forceinline__ void wide_batch_add(float& tot, float v, int k) { tot = k == 0 ? v : tot + v; }
+
+// act epilogue: bf16_sample_wide_kernel's loads and rules per component; action / det_action are [n, K], the index within each component, kept by lane k and stored by it
+struct SampleArgsWM : SampleArgsW { CompTable comp; };
+template <int EPT, bool MASK>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_wide_multi_kernel(SampleArgsWM a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    float lg[EPT], u[EPT], mk[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+    if constexpr (MASK) wide_load_row<EPT>(mk, a.mask + (size_t)row * a.A, lane, a.A, 0.f);
+    if (a.noise) wide_load_row<EPT>(u, a.noise + (size_t)row * a.A, lane, a.A, 0.5f);
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && a.value);
+    bool ok[EPT], hit[EPT];
+    wide_ok<EPT, MASK>(ok, mk, lane, a.A);
+    if (!a.noise) {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) { const int j = wide_col(lane, e); u[e] = j < a.A ? ctr_uniform(a.seed, a.row_base + row, a.rng_step, j) : 0.5f; }
+    }
+    float pl[EPT], a0[EPT], ex[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { pl[e] = gumbel(lg[e], u[e]); a0[e] = 0.f; hit[e] = false; }
+    const int K = a.comp.K;
+    int my_p = -1, my_o = 0, my_l = 0;                       // lane k: component k's drawn column, its first column, its deterministic column
+    for (int k0 = 0; k0 < K; k0 += WM_BATCH) {
+        const WideBatch b = wide_batch(a.comp, k0);
+        int il[WM_BATCH], ip[WM_BATCH];
+        wide_batch_max<EPT, MASK, true>(b, lg, pl, ok, lane, a0, il, ip);
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c)                   // (a component without an allowed category, which the host checks refuse, ends at e)
+            if (lane == k0 + c && k0 + c < K) { my_p = min(ip[c], b.ce[c] - 1); my_l = min(il[c], b.ce[c] - 1); my_o = b.o[c]; }
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) ex[e] = expf(a0[e]);
+    float nlp = 0.f;
+    for (int k0 = 0; k0 < K; k0 += WM_BATCH) {
+        const WideBatch b = wide_batch(a.comp, k0);
+        int act[WM_BATCH];
+        float lz[WM_BATCH], la[WM_BATCH], H[WM_BATCH];
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) act[c] = wave_get(my_p, k0 + c);
+        wide_batch_sums<EPT, 0>(b, a0, ex, ok, hit, lane, act, lz, la, H);
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) if (k0 + c < K) wide_batch_add(nlp, lz[c] - la[c], k0 + c);
+    }
+    if (lane < K) {
+        if (a.action) a.action[(size_t)row * K + lane] = (float)(my_p - my_o);
+        if (a.det_action) a.det_action[(size_t)row * K + lane] = (float)(my_l - my_o);
+    }
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = nlp;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.in.vsplit);
+    }
+}
+
+// policy query: bf16_eval_wide_kernel's loads and outputs with the GIVEN indices, K floats per row (lane k < K loads component k's and the walk broadcasts its column);
+// neglogp and entropy are the components' in component order; params [n, W = sum(nvec)]: p_j = ex_j / z of j's own component, exactly +0 for a forbidden category.
+struct EvalArgsWM : EvalArgsW { CompTable comp; };
+template <int EPT, bool MASK>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_eval_wide_multi_kernel(EvalArgsWM a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    const int K = a.comp.K;
+    float lg[EPT], mk[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+    if constexpr (MASK) wide_load_row<EPT>(mk, a.mask + (size_t)row * a.A, lane, a.A, 0.f);
+    const bool given = a.actions != nullptr;
+    int kact = 0;                                            // lane k < K: component k's index within the component
+    if (given && lane < K) kact = (int)a.actions[(size_t)row * K + lane];
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && a.value);
+    bool ok[EPT], hit[EPT];
+    wide_ok<EPT, MASK>(ok, mk, lane, a.A);
+    float a0[EPT], ex[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { a0[e] = 0.f; hit[e] = false; }
+    for (int k0 = 0; k0 < K; k0 += WM_BATCH) {
+        const WideBatch b = wide_batch(a.comp, k0);
+        int il[WM_BATCH], ip[WM_BATCH];
+        wide_batch_max<EPT, MASK, false>(b, lg, lg, ok, lane, a0, il, ip);
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) ex[e] = expf(a0[e]);
+    float nlp = 0.f, ent = 0.f;
+    for (int k0 = 0; k0 < K; k0 += WM_BATCH) {
+        const WideBatch b = wide_batch(a.comp, k0);
+        int act[WM_BATCH];
+        float lz[WM_BATCH], la[WM_BATCH], H[WM_BATCH];
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) { const int ka = wave_get(kact, k0 + c); act[c] = given ? b.o[c] + ka : -1; }
+        wide_batch_sums<EPT, 1>(b, a0, ex, ok, hit, lane, act, lz, la, H);
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) if (k0 + c < K) { wide_batch_add(nlp, lz[c] - la[c], k0 + c); wide_batch_add(ent, H[c], k0 + c); }
+    }
+    if (a.params) {
+        float* prow = a.params + (size_t)row * a.W;
+        const bool vec = ((a.A | a.W) & 3) == 0;
+#pragma unroll
+        for (int q = 0; q < EPT / 4; ++q) {
+            const int j = 256 * q + 4 * lane;
+            float p[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p[c] = ok[4 * q + c] ? ex[4 * q + c] : 0.f;
+            if (vec) { if (j < a.A) *reinterpret_cast<float4*>(prow + j) = make_float4(p[0], p[1], p[2], p[3]); }
+            else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) if (j + c < a.A) prow[j + c] = p[c];
+            }
+        }
+    }
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = nlp;
+        if (a.entropy) a.entropy[row] = ent;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.in.vsplit);
+    }
+}
+
+// loss + d logits: bf16_loss_wide_kernel's tile, slots, surrogate and value tower; `actions` holds K floats per row (lane k < K loads component k's, as
+// bf16_loss_kernel<.., MULTI> does); d logits with the entropy H_k of the element's own component (cat_grad_p / cat_grad_t as the component's statistics arrive,
+// cat_grad_finish once the row's d_nlp is known).  Dead rows, padding columns and forbidden categories: exactly +0.
+struct LossArgsWM : LossArgsW { CompTable comp; };
+template <int EPT, bool MASK>
+__global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_wide_multi_kernel(LossArgsWM a) {
+    extern __shared__ __attribute__((aligned(16))) float ls[];      // [R][Ap] d logits | [R][4] pi terms | [R][2] vf terms
+    float* dl_s = ls; float* pt = ls + BL_ROWS * a.Ap; float* vt = pt + 4 * BL_ROWS;
+    const int tid = threadIdx.x, r = tid >> 6, lane = tid & 63;
+    const int row = blockIdx.x * BL_ROWS + r;
+    const bool live = row < a.n;
+    const int K = a.comp.K;
+    const float cr = a.hyper[1];
+    const float vcr = a.hyper[2];                   // the value tower's clip range and switch (vf_loss_row)
+    const float voff = a.hyper[3];
+    const float g = a.inv_n;
+    // every load of the lane first (a dead row of the last block reads its own padded logits row and nothing else)
+    float lg[EPT], mk[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) mk[e] = 1.f;
+    if constexpr (MASK) { if (live) wide_load_row<EPT>(mk, a.mask + (size_t)row * a.A, lane, a.A, 0.f); }
+    int kact = 0;                                   // lane k < K: component k's index within the component
+    if (live && lane < K) kact = (int)a.actions[(size_t)row * K + lane];
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && live);
+    const float adv = live ? a.advs[row] : 0.f;
+    const float old_nlp_in = live ? a.old_neglogp[row] : 0.f;
+    float Rv = 0.f, vo = 0.f;
+    if (lane == 0 && live) { Rv = a.returns[row]; vo = a.old_values[row]; }
+    // policy tower
+    bool ok[EPT], hit[EPT];
+    wide_ok<EPT, MASK>(ok, mk, lane, a.A);
+    float a0[EPT], ex[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { lg[e] = live ? lg[e] : 0.f; a0[e] = 0.f; hit[e] = false; }
+    for (int k0 = 0; k0 < K; k0 += WM_BATCH) {
+        const WideBatch b = wide_batch(a.comp, k0);
+        int il[WM_BATCH], ip[WM_BATCH];
+        wide_batch_max<EPT, MASK, false>(b, lg, lg, ok, lane, a0, il, ip);
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) ex[e] = expf(a0[e]);
+    float nlp = 0.f, sent = 0.f;
+    for (int k0 = 0; k0 < K; k0 += WM_BATCH) {
+        const WideBatch b = wide_batch(a.comp, k0);
+        int act[WM_BATCH];
+        float lz[WM_BATCH], la[WM_BATCH], H[WM_BATCH];
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) { const int ka = wave_get(kact, k0 + c); act[c] = live ? b.o[c] + ka : -1; }
+        wide_batch_sums<EPT, 2>(b, a0, ex, ok, hit, lane, act, lz, la, H);         // a0 -> (a0 - lz) + H_k, ex -> p, hit: of the element's own component
+#pragma unroll
+        for (int c = 0; c < WM_BATCH; ++c) if (k0 + c < K) { wide_batch_add(nlp, lz[c] - la[c], k0 + c); wide_batch_add(sent, H[c], k0 + c); }
+    }
+    const float old_nlp = live ? old_nlp_in : nlp;
+    const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
+    const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
+    if (lane == 0) surrogate_terms(sr, nlp, old_nlp, sent, cr, live, pt, r);
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        const int j = 256 * q + 4 * lane;
+        if (j < a.Ap) {
+            float d[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int e = 4 * q + c;
+                d[c] = 0.f;
+                if (live && ok[e]) d[c] = cat_grad_finish(d_nlp, ex[e], a0[e], hit[e], a.ent_coef, g);
+            }
+            *reinterpret_cast<float4*>(dl_s + r * a.Ap + j) = make_float4(d[0], d[1], d[2], d[3]);
+            bf16x4 o; o[0] = (bf16_t)d[0]; o[1] = (bf16_t)d[1]; o[2] = (bf16_t)d[2]; o[3] = (bf16_t)d[3];
+            *reinterpret_cast<bf16x4*>(a.dhead[0] + (size_t)row * a.Ap + j) = o;
+        }
+    }
+    // value tower (G:10213-10837, G:14975-19571)
+    if (lane == 0) {
+        float dv = 0.f, lossv = 0.f;
+        if (live) vf_loss_row(head_parts_sum(vp, a.in.vsplit), Rv, vo, vcr, voff, a.vf_coef * 0.5f * a.inv_n, lossv, dv);
+        vt[r * 2] = dv; vt[r * 2 + 1] = lossv;
+        a.dhead[1][(size_t)row * a.Ap] = (bf16_t)dv;
+    }
+    __syncthreads();
+    float* s0 = a.slots[0] + (size_t)blockIdx.x * a.slot_w;
+    float* s1 = a.slots[1] + (size_t)blockIdx.x * a.slot_w;
+    for (int j = tid; j < a.Ap; j += 64 * BL_ROWS) {          // db_pi: fp32 sums of the fp32 values in row order; the aux words: zeros
+        float sb = 0.f;
+#pragma unroll
+        for (int q = 0; q < BL_ROWS; ++q) sb += dl_s[q * a.Ap + j];
+        s0[a.slot_head + j] = sb; s0[a.slot_aux + j] = 0.f;
+    }
+    if (tid >= 64 * BL_ROWS - 64 && tid < 64 * BL_ROWS - 60) { const int k = tid - (64 * BL_ROWS - 64); float s = 0.f; for (int q = 0; q < BL_ROWS; ++q) s += pt[q * 4 + k]; s0[a.slot_loss + k] = s; }
+    if (tid == 64 * BL_ROWS - 32) { float sb = 0.f, sl = 0.f; for (int q = 0; q < BL_ROWS; ++q) { sb += vt[q * 2]; sl += vt[q * 2 + 1]; } s1[a.slot_head] = sb; s1[a.slot_loss] = sl; }
+}

@@ -75,6 +75,14 @@ __device__ __forceinline__ float cat_grad_elem(float d_nlp, float ex, float z, f
     const float p = ex / z;
     return d_nlp * (p - (j == act ? 1.0f : 0.0f)) + ent_coef * g * (p * ((a0 - lz) + H));
 }
+// cat_grad_elem in two halves, for a kernel that knows an element's component statistics long before it knows d_nlp (the batched walk of the wide multi-categorical
+// head): p = ex / z and t = (a0 - lz) + H are formed when the component's statistics arrive, the rest when the row's surrogate is known.  The operations and their
+// order are cat_grad_elem's: the same bits.
+__device__ __forceinline__ float cat_grad_p(float ex, float z) { return ex / z; }
+__device__ __forceinline__ float cat_grad_t(float a0, float lz, float H) { return (a0 - lz) + H; }
+__device__ __forceinline__ float cat_grad_finish(float d_nlp, float p, float t, bool hit, float ent_coef, float g) {
+    return d_nlp * (p - (hit ? 1.0f : 0.0f)) + ent_coef * g * (p * t);
+}
 
 // ---- multi-binary head (stable-baselines BernoulliProbabilityDistribution: A independent on / off decisions over the logits l in place of mu) -----------------------
 // One element, from e = exp(-|l|) (never overflows), sp = log1p(e) = softplus(-|l|), q = e / (1 + e) = the probability of the LESS likely value:

@@ -72,7 +72,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_BF16_STEP_MCAT, KV_BF16_STEP_MCAT_MASK, KV_BF16_TRAIN_MCAT, KV_BF16_TRAIN_MCAT_MASK,
                      KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
                      KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_BF16_STEP_MBIN, KV_BF16_TRAIN_MBIN,
-                     KV_BF16_STEP_WCAT, KV_BF16_STEP_WCAT_MASK, KV_BF16_TRAIN_WCAT, KV_BF16_TRAIN_WCAT_MASK, KV_TOTAL };
+                     KV_BF16_STEP_WCAT, KV_BF16_STEP_WCAT_MASK, KV_BF16_TRAIN_WCAT, KV_BF16_TRAIN_WCAT_MASK,
+                     KV_BF16_STEP_WMCAT, KV_BF16_STEP_WMCAT_MASK, KV_BF16_TRAIN_WMCAT, KV_BF16_TRAIN_WMCAT_MASK, KV_TOTAL };
 // ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all,
 // which is FROZEN in turn at the first KV_ALL_COUNT rows (a caller asserts that count too).  Every variant, later ones included, is reached by name through
 // ppo_kernel_count and enumerated by ppo_kernel_variant_name: no caller may hold THAT list's length.
@@ -80,7 +81,7 @@ constexpr int KV_LEGACY_COUNT = 60;
 constexpr int KV_ALL_COUNT = 62;
 static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
 static_assert(KV_ALL_COUNT == KV_TRAIN8_MBIN, "the rows of ppo_kernel_counts_all end where the first variant named after it begins");
-// The variant list (KV_TOTAL = 69 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
+// The variant list (KV_TOTAL = 73 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
 // hands out one name at a time, and ppo_host_learn_binary's walk stops at its callers' 64 entries itself (it ends one name short of the list).
 // KV_COUNT below is FROZEN at the 63 names in front of the bf16 <mbin> pair, and the assertion on it can no longer fail: it constrains nothing.  It stands only because
 // tests/test_multi_binary.py::test_source_names_the_head_in_every_layer looks for this line of text; when that test's pin is updated, both lines go.
@@ -128,7 +129,10 @@ const char* kVariantNames[KV_TOTAL] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "bf16_step_sequence<mbin>", "bf16_train_sequence<mbin>",
                                        // a wide categorical PPO_BF16 handle (PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD, act_dim > 128): counted INSTEAD of the "bf16_*_sequence<cat[,mask]>"
                                        // names; ppo_kernel_count / ppo_kernel_variant_name only.  ("<cat,mask,wide>" would pass the 31 characters a variant name may have.)
-                                       "bf16_step_sequence<wcat>", "bf16_step_sequence<wcat,mask>", "bf16_train_sequence<wcat>", "bf16_train_sequence<wcat,mask>"};
+                                       "bf16_step_sequence<wcat>", "bf16_step_sequence<wcat,mask>", "bf16_train_sequence<wcat>", "bf16_train_sequence<wcat,mask>",
+                                       // a wide multi-categorical PPO_BF16 handle (PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD, sum(nvec) > 128): counted INSTEAD of the
+                                       // "bf16_*_sequence<mcat[,mask]>" names; ppo_kernel_count / ppo_kernel_variant_name only.  (The longest has the 31 characters a variant name may have.)
+                                       "bf16_step_sequence<wmcat>", "bf16_step_sequence<wmcat,mask>", "bf16_train_sequence<wmcat>", "bf16_train_sequence<wmcat,mask>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -318,8 +322,10 @@ struct ppo_handle {
         bf16_t *hb[2][PPO_MAX_LAYERS]{}, *dy[2][PPO_MAX_LAYERS]{};     // [Rcap][Hp_l]: tanh outputs and the gradients w.r.t. the pre-activations
         float* head_out[2]{};                           // [GB_HEAD_SPLIT][Rcap][Ap] fp32 partial products of the head GEMM's reduction ranges
         int head_split = 1;                             // ranges the last bf16_forward used
-        bool wide = false;                              // PPO_ACT_BF16_WIDE_HEAD took effect (categorical, act_dim > 128): head_out[0] is [1][Rcap][Ap] unsplit logits (bf16_logits_kernel),
-                                                        // head_out[1] a 128-column image (bf16_value_head_kernel), the row kernels are the <EPT, MASK> wide forms
+        bool wide = false;                              // PPO_ACT_BF16_WIDE_HEAD took effect (categorical, act_dim > 128) or PPO_ACT_BF16_WIDE_MULTI_HEAD did (multi-categorical,
+                                                        // sum(nvec) > 128): head_out[0] is [1][Rcap][Ap] unsplit logits (bf16_logits_kernel), head_out[1] a 128-column image
+                                                        // (bf16_value_head_kernel), the row kernels are the <EPT, MASK> wide forms -- of a multi-categorical handle the
+                                                        // bf16_*_wide_multi_kernel ones (wide_multi)
         // the fused assembly + Adam launch does not write the assembled gradient: whoever asks for it (ppo_get_last_grad, ppo_debug_buffer) has it rebuilt
         // from the last train step's slabs first (bf16_materialize_grad).  enqueued: the last train step ENQUEUED; captured: the last step of the captured update
         // graph (the host code of a train step does not run on a replay, so the whole value is restored after one); ran: the last train step that RAN -- on: h->grad
@@ -1081,6 +1087,10 @@ int bf16_wide_heads(ppo_handle* h, int Rp) {
     HIP_OK(h, hipGetLastError());
     return 0;
 }
+// a wide handle with components runs the multi forms of the three row kernels: the categorical form's arguments with the component table behind them
+static bool wide_multi(const ppo_handle* h) { return h->dist == PPO_ACT_MULTI_CATEGORICAL; }
+template <class M, class B>
+static M wide_multi_args(const ppo_handle* h, const B& base) { M m{}; static_cast<B&>(m) = base; m.comp = h->comp; return m; }
 static WideHeadIn bf16_wide_in(const ppo_handle* h) {
     const ppo_handle::Bf16& b = h->bf;
     return WideHeadIn{b.head_out[0], h->net.Ap, b.head_out[1], GB_N, b.head_split, (size_t)b.Rcap * GB_N};
@@ -1091,6 +1101,10 @@ int bf16_wide_sample(ppo_handle* h, const StepArgs& a) {
     sa.in = bf16_wide_in(h); sa.noise = a.noise; sa.mask = a.mask; sa.action = a.action; sa.det_action = a.det_action; sa.value = a.value; sa.neglogp = a.neglogp;
     sa.n = a.n; sa.A = n.A; sa.Ap = n.Ap; sa.seed = a.seed; sa.rng_step = a.rng_step; sa.row_base = a.row_base;
     const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
+    if (wide_multi(h)) {
+        const SampleArgsWM sm = wide_multi_args<SampleArgsWM>(h, sa);
+        with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_sample_wide_multi_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, sm); });
+    } else
     with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_sample_wide_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, sa); });
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1104,6 +1118,10 @@ int bf16_wide_eval(ppo_handle* h, const EvalArgs& a, int r0, int rows) {
     ea.params = a.params ? a.params + (size_t)r0 * a.W : nullptr;
     ea.n = rows; ea.A = n.A; ea.Ap = n.Ap; ea.W = a.W;
     const dim3 grid((rows + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
+    if (wide_multi(h)) {
+        const EvalArgsWM em = wide_multi_args<EvalArgsWM>(h, ea);
+        with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_eval_wide_multi_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, em); });
+    } else
     with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_eval_wide_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, ea); });
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1118,6 +1136,10 @@ int bf16_wide_loss(ppo_handle* h, const TrainArgs& ta, int Rp) {
     for (int t = 0; t < 2; ++t) { la.dhead[t] = b.dhead[t]; la.slots[t] = h->slots[t]; }
     la.slot_w = n.slot_w; la.slot_head = n.slot_head; la.slot_aux = n.slot_aux; la.slot_loss = n.slot_loss;
     const dim3 grid(Rp / BL_ROWS), blk(64 * BL_ROWS);
+    if (wide_multi(h)) {
+        const LossArgsWM lm = wide_multi_args<LossArgsWM>(h, la);
+        with_wide_row(n.A, ta.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_loss_wide_multi_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, BLW_LDS_BYTES(n.Ap), h->stream, lm); });
+    } else
     with_wide_row(n.A, ta.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_loss_wide_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, BLW_LDS_BYTES(n.Ap), h->stream, la); });
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1411,7 +1433,7 @@ static auto nw_rollout_fn(T) {
 int launch_step(ppo_handle* h, const StepArgs& a0) {
     const Head hd = head_of(h, a0.mask != nullptr);                 // (a multi-categorical handle: bf16 only when created with PPO_ACT_BF16_MULTI_HEAD; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
     if (a0.mask && !hd.cat) return fail(h, "policy step: an action mask needs a categorical handle");
-    if (h->bf.wide) ++h->kv[hd.mask ? KV_BF16_STEP_WCAT_MASK : KV_BF16_STEP_WCAT];
+    if (h->bf.wide) ++h->kv[hd.multi ? (hd.mask ? KV_BF16_STEP_WMCAT_MASK : KV_BF16_STEP_WMCAT) : hd.mask ? KV_BF16_STEP_WCAT_MASK : KV_BF16_STEP_WCAT];
     else ++h->kv[kHeadVariant[h->bf.on ? KF_BF16_STEP : !h->narrow ? KF_POLICY_STEP : h->nw_static ? KF_NARROW_STEP_STATIC : KF_NARROW_STEP][hd.index()]];
     if (h->bf.on) return launch_step_bf16(h, a0);
     ProfScope ps(h, PK_STEP);
@@ -1663,7 +1685,10 @@ static bool set_lds_bf16_wide(const ppo_handle* h) {
     auto set = [&](auto f, size_t bytes) { ok &= hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess; };
     set(bf16_logits_kernel<4>, GB_LDS_BYTES(4)); set(bf16_logits_kernel<2>, GB_LDS_BYTES(2)); set(bf16_value_head_kernel, BH_LDS_BYTES);
     for (int A : {256, 512, 1024}) for (bool m : {false, true})
-        with_wide_row(A, m, [&](auto E, auto M) { set(bf16_loss_wide_kernel<decltype(E)::value, decltype(M)::value>, BLW_LDS_BYTES(1024)); });
+        with_wide_row(A, m, [&](auto E, auto M) {
+            set(bf16_loss_wide_kernel<decltype(E)::value, decltype(M)::value>, BLW_LDS_BYTES(1024));
+            set(bf16_loss_wide_multi_kernel<decltype(E)::value, decltype(M)::value>, BLW_LDS_BYTES(1024));
+        });
     return ok;
 }
 // the narrow family likewise, every shape.  The kernels with a head: step, train (and the form launched while target-KL early stopping is on: ppo_set_target_kl),
@@ -1817,7 +1842,7 @@ static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool 
     const int Rp = ru(ta.n, GB_PAD);
     const Head hd = head_of(h, ta.mask != nullptr);                 // (a multi-categorical handle: PPO_ACT_BF16_MULTI_HEAD, ppo_create_multi_ex)
     if (ta.mask && !hd.cat) return fail(h, "train step: an action mask needs a categorical handle");
-    if (h->bf.wide) ++h->kv[hd.mask ? KV_BF16_TRAIN_WCAT_MASK : KV_BF16_TRAIN_WCAT];
+    if (h->bf.wide) ++h->kv[hd.multi ? (hd.mask ? KV_BF16_TRAIN_WMCAT_MASK : KV_BF16_TRAIN_WMCAT) : hd.mask ? KV_BF16_TRAIN_WCAT_MASK : KV_BF16_TRAIN_WCAT];
     else ++h->kv[kHeadVariant[KF_BF16_TRAIN][hd.index()]];
     h->bf.lazy.enqueued.on = false;
     if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
@@ -2107,7 +2132,7 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     if (cfg->obs_dim < 1 || cfg->act_dim < 1) return fail(nullptr, "ppo_create: bad obs/act dims");
     // the flags every distribution accepts go (PPO_ACT_BF16_MULTI_HEAD through ppo_create_multi_ex only); whatever else is left must be a distribution.  The two binary
     // flags belong to PPO_ACT_MULTI_BINARY alone: beside any other distribution they stay in and are refused (ppo_create_multi_ex has refused them: "unknown flag bit")
-    int32_t dist = action_dist & ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS | (nvec ? PPO_ACT_BF16_MULTI_HEAD : 0));
+    int32_t dist = action_dist & ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS | (nvec ? PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD : 0));
     if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS | PPO_ACT_BF16_BINARY_HEAD)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
     // PPO_ACT_BF16_WIDE_HEAD likewise belongs to PPO_ACT_CATEGORICAL alone
     if (!nvec && (dist & ~(int32_t)PPO_ACT_BF16_WIDE_HEAD) == PPO_ACT_CATEGORICAL) dist = PPO_ACT_CATEGORICAL;
@@ -2138,6 +2163,8 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     rq.pair = (action_dist & (mbin ? PPO_ACT_BINARY_PAIR_KERNELS : cat || mcat ? PPO_ACT_PAIR_KERNELS : 0)) != 0 && cfg->compute_dtype == PPO_F32;
     rq.bf16 = (action_dist & (cat ? PPO_ACT_BF16_HEAD : mcat ? PPO_ACT_BF16_MULTI_HEAD : mbin ? PPO_ACT_BF16_BINARY_HEAD : 0)) != 0 && bf16;
     rq.wide = wide && rq.bf16 && cfg->act_dim > 128;               // (up to 128 categories the flag changes nothing: the 128-wide kernels, their bits and their counters)
+    // PPO_ACT_BF16_WIDE_MULTI_HEAD likewise for the multi-categorical head (ppo_create_multi_ex has checked sum(nvec) = act_dim against 128 / 1024)
+    if (mcat && rq.bf16 && (action_dist & PPO_ACT_BF16_WIDE_MULTI_HEAD) && cfg->act_dim > 128) rq.wide = true;
     return 0;
 }
 
@@ -2251,7 +2278,7 @@ static int create_handle(const ppo_config* cfg, int32_t action_dist, const int32
     if (h->dist != PPO_ACT_CATEGORICAL) h->opt_narrow = h->opt_narrow && h->narrow;
     h->opt_pair = h->opt_pair && (h->t8 || h->dw2);
     if (h->bf.on && bf16_create(h)) return bail();
-    if (!set_lds_bf16_wide(h)) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the wide categorical head's kernels"); return bail(); }
+    if (!set_lds_bf16_wide(h)) { fail(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the wide heads' kernels"); return bail(); }
     if (narrow_extras(h, n_cu)) return bail();
     if (init_adam(h)) return bail();
     *out = h;
@@ -2265,7 +2292,8 @@ int ppo_create_multi(const ppo_config* cfg, const int32_t* nvec, int32_t n_compo
 // K independent categorical components over one logits vector of cfg->act_dim = n_0 + .. + n_{K-1} columns; flags: PPO_ACT_SHAPE_KERNELS (the narrow family on a
 // qualifying shape), PPO_ACT_PAIR_KERNELS (the [256,256] pair on a qualifying shape), PPO_ACT_BF16_HEAD (accepted, nothing to select: that flag belongs to ppo_create_ex's
 // categorical head and PPO_BF16 stays refused with it), PPO_ACT_BF16_MULTI_HEAD (with compute_dtype PPO_BF16: the bf16 path with bf16_sample_kernel / bf16_loss_kernel
-// <mcat[,mask]>, sum(nvec) <= 128, the other two flags beside it ignored; with PPO_F32: changes nothing)
+// <mcat[,mask]>, sum(nvec) <= 128, the other two flags beside it ignored; with PPO_F32: changes nothing), PPO_ACT_BF16_WIDE_MULTI_HEAD (beside PPO_ACT_BF16_MULTI_HEAD and
+// PPO_BF16: 128 < sum(nvec) <= 1024 on the bf16_*_wide_multi_kernel row kernels; up to 128 logits or with PPO_F32: changes nothing)
 int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_components, int32_t flags, ppo_handle** out) {
     if (!cfg || !out) return fail(nullptr, "ppo_create_multi: null argument");
     *out = nullptr;
@@ -2278,14 +2306,17 @@ int ppo_create_multi_ex(const ppo_config* cfg, const int32_t* nvec, int32_t n_co
         sum += nvec[k];
     }
     if (sum != cfg->act_dim) return fail(nullptr, "ppo_create_multi: act_dim %d is not the sum of nvec (%lld)", (int)cfg->act_dim, (long long)sum);
-    const int32_t known = PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_MULTI_HEAD;
+    const int32_t known = PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD;
     if (cfg->compute_dtype == PPO_BF16 && !(flags & PPO_ACT_BF16_MULTI_HEAD))
         return fail(nullptr, "ppo_create_multi: compute_dtype PPO_BF16 is not supported (the multi-categorical head runs on the PPO_F32 path)");
     if (flags & ~known)
-        return fail(nullptr, "ppo_create_multi_ex: unknown flag bit 0x%x (PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS, PPO_ACT_BF16_HEAD or PPO_ACT_BF16_MULTI_HEAD)", (unsigned)(flags & ~known));
-    if (cfg->compute_dtype == PPO_BF16 && sum > 128)
+        return fail(nullptr, "ppo_create_multi_ex: unknown flag bit 0x%x (PPO_ACT_SHAPE_KERNELS, PPO_ACT_PAIR_KERNELS, PPO_ACT_BF16_HEAD, PPO_ACT_BF16_MULTI_HEAD or PPO_ACT_BF16_WIDE_MULTI_HEAD)", (unsigned)(flags & ~known));
+    const bool widem = (flags & PPO_ACT_BF16_WIDE_MULTI_HEAD) != 0;
+    if (cfg->compute_dtype == PPO_BF16 && widem && sum > 1024)
+        return fail(nullptr, "ppo_create_multi_ex: PPO_ACT_BF16_WIDE_MULTI_HEAD: the wide multi-categorical head of the PPO_BF16 path holds at most 1024 logits (sum of nvec is %lld)", (long long)sum);
+    if (cfg->compute_dtype == PPO_BF16 && !widem && sum > 128)
         return fail(nullptr, "ppo_create_multi_ex: PPO_ACT_BF16_MULTI_HEAD: the multi-categorical head of the PPO_BF16 path holds at most 128 logits (sum of nvec is %lld)", (long long)sum);
-    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & (PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_MULTI_HEAD)), nvec, n_components, out);
+    return create_handle(cfg, PPO_ACT_MULTI_CATEGORICAL | (flags & (PPO_ACT_SHAPE_KERNELS | PPO_ACT_PAIR_KERNELS | PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD)), nvec, n_components, out);
 }
 
 int ppo_action_nvec(const ppo_handle* h, int32_t max, int32_t* nvec) {

@@ -85,6 +85,8 @@ public:
     // the [256,256] train kernel pair where that shape qualifies, and PPO_ACT_BF16_BINARY_HEAD with cfg.compute_dtype = PPO_BF16 on the bf16 path (at most 128 bits);
     // with any other Env the library refuses each of the three flags.  For a discrete Env with more than 128 actions, PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD with
     // cfg.compute_dtype = PPO_BF16 creates the handle on the bf16 path's wide categorical head (at most 1024 categories).
+    // For a multi-discrete Env with more than 128 logits, PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD with cfg.compute_dtype = PPO_BF16 creates it on the
+    // bf16 path's wide multi-categorical head (sum of nvec at most 1024).
     // Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);

@@ -413,7 +413,7 @@ int ppo_host_learn_multi(const ppo_host_args* a, float* reward_curve, long long*
         std::vector<std::shared_ptr<Env>> envs;
         for (int i = 0; i < a->n_envs; ++i) { kids.push_back(std::make_shared<MultiDiscreteTargetEnv>(1234u, (uint32_t)i, O, nvec, 100, a->multi_masked != 0)); envs.push_back(kids.back()); }
         // (PPO_BF16: the bf16 path's multi-categorical head is opt-in, as PPO_ACT_BF16_HEAD is for a discrete Env's handle)
-        const int32_t extra_flags = (a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : 0) | (a->compute_dtype == PPO_BF16 ? PPO_ACT_BF16_MULTI_HEAD : 0);
+        const int32_t extra_flags = (a->discrete_kernels == 2 ? PPO_ACT_PAIR_KERNELS : 0) | (a->compute_dtype == PPO_BF16 ? PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD : 0);     // (the wide flag: more than 128 logits; up to 128 it changes nothing)
         if (PPO2::create_handle(cfg, *envs[0], &h, a->discrete_kernels == 1, extra_flags) != 0) throw std::runtime_error(ppo_last_error(nullptr));
         if (ppo_init_orthogonal(h, 0) != 0) throw std::runtime_error(ppo_last_error(h));
         if (a->host_step_fused && ppo_set_host_step_fused(h, 1) != 0) throw std::runtime_error(ppo_last_error(h));
