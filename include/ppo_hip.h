@@ -345,12 +345,41 @@ int ppo_action_width(const ppo_handle* h);
  *                        padded words.  
  *                        Measured on an MI355X at 256 observations, [1024,1024,1024] (tools/prof_bf16_wide.py; us of device time per call, median of 7 rounds; A = 1024 | A = 256 | the PPO_ACT_BF16_HEAD handle at A = 128):
  *                        train step 343.6 | 276.9 | 233.1 at 4096 rows, 202.3 | 184.0 | 165.9 at 256;
- *                        policy step 170.0 | 150.2 | 145.6 at 8192 rows (DESIGN.md section 5 has the per-kernel figures and the padded value head's share). */
+ *                        policy step 170.0 | 150.2 | 145.6 at 8192 rows (DESIGN.md section 5 has the per-kernel figures and the padded value head's share).
+ *   PPO_ACT_BF16_WIDE_BINARY_HEAD  PPO_ACT_MULTI_BINARY | PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD with compute_dtype PPO_BF16 and 128 < act_dim <= 1024
+ *                        creates a multi-binary handle on the bf16 path's WIDE head forms.  act_dim > 1024 is an error that names the flag, the limit and the value;
+ *                        without the flag act_dim > 128 keeps its refusal.  With act_dim <= 128, and with PPO_F32, the flag is accepted and changes nothing (same
+ *                        kernels, bits and counts).  Beside any other distribution the bit is an "unknown action_dist" error whose text names it;
+ *                        ppo_create_multi_ex refuses it with its own "unknown flag bit 0x40000".  The logits and the value come from the wide categorical head's
+ *                        products (bf16_logits_kernel, bf16_value_head_kernel, Ap = act_dim rounded up to 128); the row arithmetic is
+ *                        bf16_sample_wide_binary_kernel / bf16_loss_wide_binary_kernel / bf16_eval_wide_binary_kernel<EPT> (ppo_bf16.hpp), EPT = 4 / 8 / 16 logits
+ *                        per lane for act_dim <= 256 / 512 / 1024: one wave per row, the logits in registers as 16-byte quads (column 256 q + 4 lane + c), every
+ *                        global load first, then the quads STREAM -- an element is finished from its own logit (the multi-binary arithmetic stated above: exp and
+ *                        log1p once per element, x_j = u_j < p_j, deterministic x_j = l_j > 0) and folded into the lane's two partial sums; no maximum, no argmax,
+ *                        no normaliser.  The only cross-lane work is ONE helper in all three kernels: a lane's elements in rising column order, then one 64-lane
+ *                        butterfly, steps 32 .. 1, the neglogp's and the entropy's interleaved -- ppo_step's neglogp, the train model's and ppo_evaluate_actions'
+ *                        are the same bits.  Drawn bits cross the butterfly as one 32-bit word per lane; the loss kernel keeps the logit, exp(-|l|) and the action
+ *                        bits as one word and rebuilds p behind the butterfly by the same operations (no second exp).  [n, A] actions, uniforms and parameters
+ *                        move as 16-byte accesses when act_dim % 4 == 0 and as scalar ones otherwise.  Counter keys: ctr_uniform(seed, global row, call counter,
+ *                        j), j up to 1023.  The loss kernel keeps the assembly's contract as bf16_loss_wide_kernel does ([16][Ap] fp32 LDS tile, fp32 column sums,
+ *                        aux words zeros, pt[1] the entropy, padding columns and dead rows exactly +0, the dynamic-LDS limit raised at creation).  Every entry
+ *                        point works as on a PPO_ACT_BF16_BINARY_HEAD handle, the refusals (masks, ppo_set_target_kl, ppo_dist_init) included with their messages;
+ *                        behind ppo_set_bf16_queries(h, 1) the three policy queries, parameters P(bit = 1), ppo_distribution_width = A.  Debug buffers as on a
+ *                        PPO_ACT_BF16_WIDE_HEAD handle.  Counted under "bf16_step_sequence<wmbin>" / "bf16_train_sequence<wmbin>" INSTEAD of the <mbin> names --
+ *                        names of ppo_kernel_count / ppo_kernel_variant_name only; ppo_kernel_counts keeps its 60 rows, ppo_kernel_counts_all its 62.  The wide
+ *                        heads' known cost stands: the value head carries the padded width Ap.
+ *                        Measured on an MI355X at 256 observations, [1024,1024,1024] (tools/prof_bf16_wide.py --head binary; us of device time per call, median of 7
+ *                        rounds, spreads 0.6 - 3.9 but 8.5 and 10.5 for this head at A = 1024 in the first and last figure; this head | the wide categorical handle,
+ *                        at A = 1024 and at A = 256, then the 128-bit PPO_ACT_BF16_BINARY_HEAD handle): train step 367.1 | 352.3 and 282.2 | 270.3, 243.7 at 4096
+ *                        rows; 221.2 | 201.8 and 190.5 | 184.8, 168.7 at 256 rows; policy step 191.1 | 171.4 and 157.4 | 149.8, 148.7 at 8192 rows.  SLOWER than the
+ *                        wide categorical kernels at equal A by 6 - 20 us, outside the spread, against the expectation for an elementwise head (52 - 86 VGPRs
+ *                        against their 62 - 78, so not occupancy; the head moves [n, A] actions where the categorical one moves [n]).  Not tuned. */
 #define PPO_ACT_MULTI_BINARY 3
 #define PPO_ACT_BINARY_SHAPE_KERNELS 0x2000
 #define PPO_ACT_BINARY_PAIR_KERNELS 0x4000
 #define PPO_ACT_BF16_BINARY_HEAD 0x8000
 #define PPO_ACT_BF16_WIDE_HEAD 0x10000
+#define PPO_ACT_BF16_WIDE_BINARY_HEAD 0x40000
 void ppo_destroy(ppo_handle* h);
 const char* ppo_last_error(const ppo_handle* h);   /* h may be NULL: error of the last failed ppo_create */
 int ppo_abi_version(void);

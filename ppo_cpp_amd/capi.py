@@ -69,6 +69,7 @@ ACT_BINARY_PAIR_KERNELS = 0x4000                        # PPO_ACT_BINARY_PAIR_KE
 ACT_BF16_BINARY_HEAD = 0x8000                           # PPO_ACT_BF16_BINARY_HEAD, likewise
 ACT_BF16_WIDE_HEAD = 0x10000                            # PPO_ACT_BF16_WIDE_HEAD, a flag of ppo_create_ex beside PPO_ACT_CATEGORICAL only
 ACT_BF16_WIDE_MULTI_HEAD = 0x20000                      # PPO_ACT_BF16_WIDE_MULTI_HEAD, a flag of ppo_create_multi_ex only
+ACT_BF16_WIDE_BINARY_HEAD = 0x40000                     # PPO_ACT_BF16_WIDE_BINARY_HEAD, a flag of ppo_create_ex beside PPO_ACT_MULTI_BINARY only
 VALUE_CLIP_MODES = {"policy": 0, "range": 1, "off": 2}  # PPO_VCLIP_POLICY / PPO_VCLIP_RANGE / PPO_VCLIP_OFF
 
 
@@ -133,6 +134,12 @@ class PPOHip:
     combination is refused; on a compute_dtype=0 handle it changes nothing (same bits, same counts); the other four kernel flags beside it on a compute_dtype=1
     handle are ignored.  "bf16_step_sequence<mbin>" / "bf16_train_sequence<mbin>" are names of kernel_count() / kernel_variants() only.  The attribute
     binary_bf16_head keeps what was asked for.
+    binary_bf16_wide_head=True with it, compute_dtype=1 and binary_bf16_head=True (PPO_ACT_BF16_WIDE_BINARY_HEAD; default False; a ValueError with any other
+    action_dist): up to 1024 bits on the bf16 path (bf16_logits_kernel, bf16_value_head_kernel and the bf16_*_wide_binary_kernel row kernels; no masks, no data
+    parallel, no set_target_kl; the policy queries after set_bf16_queries(True)), e.g. PPOHip(O, 1024, hidden, action_dist="multi_binary", compute_dtype=1,
+    binary_bf16_head=True, binary_bf16_wide_head=True).  With at most 128 bits or compute_dtype=0 it changes nothing (same kernels, bits and counts).
+    "bf16_step_sequence<wmbin>" / "bf16_train_sequence<wmbin>" are names of kernel_count() / kernel_variants() only.  The attribute binary_bf16_wide_head keeps
+    what was asked for.
 
     Action masks (categorical and multi-categorical; include/ppo_hip.h): step / act_deterministic / train_step take mask=(n, A), non-zero = allowed;
     set_action_masking(True) makes the rollout carry masks (rollout_act(t, mask=(E, A)), rollout_get / rollout_set("masks"))
@@ -143,7 +150,8 @@ class PPOHip:
     OUTPUT_FIELDS = {"terminal_values": 7}      # rollout_get only: what the last rollout_finish computed beside the rollout itself (an upload is refused)
 
     def __init__(self, obs_dim, act_dim, hidden, device=-1, action_dist="gaussian", shape_kernels=False, bf16_head=False, nvec=None, pair_kernels=False, binary_shape_kernels=False,
-                 binary_pair_kernels=False, binary_bf16_head=False, bf16_wide_head=False, multi_bf16_wide_head=False, **overrides):
+                 binary_pair_kernels=False, binary_bf16_head=False, bf16_wide_head=False, multi_bf16_wide_head=False, binary_bf16_wide_head=False,
+                 **overrides):
         multi = action_dist == "multi_categorical"
         if binary_shape_kernels and action_dist != "multi_binary":
             raise ValueError("binary_shape_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
@@ -151,6 +159,8 @@ class PPOHip:
             raise ValueError("binary_pair_kernels belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if binary_bf16_head and action_dist != "multi_binary":
             raise ValueError("binary_bf16_head belongs to action_dist='multi_binary', not %r" % (action_dist,))
+        if binary_bf16_wide_head and action_dist != "multi_binary":
+            raise ValueError("binary_bf16_wide_head belongs to action_dist='multi_binary', not %r" % (action_dist,))
         if bf16_wide_head and action_dist != "categorical":
             raise ValueError("bf16_wide_head belongs to action_dist='categorical', not %r" % (action_dist,))
         if multi_bf16_wide_head and not multi:
@@ -185,6 +195,7 @@ class PPOHip:
         self.binary_bf16_head = bool(binary_bf16_head)
         self.bf16_wide_head = bool(bf16_wide_head)
         self.multi_bf16_wide_head = bool(multi_bf16_wide_head)
+        self.binary_bf16_wide_head = bool(binary_bf16_wide_head)
         self._act_shape = (act_dim,) if action_dist in ("gaussian", "multi_binary") else (len(nvec),) if multi else ()      # per row
         h = C.c_void_p()
         if multi:
@@ -200,7 +211,7 @@ class PPOHip:
         elif self.lib.ppo_create_ex(C.byref(cfg), ACTION_DISTS[action_dist] | (ACT_SHAPE_KERNELS if shape_kernels else 0) | (ACT_BF16_HEAD if bf16_head else 0)
                                     | (ACT_PAIR_KERNELS if pair_kernels else 0) | (ACT_BINARY_SHAPE_KERNELS if binary_shape_kernels else 0)
                                     | (ACT_BINARY_PAIR_KERNELS if binary_pair_kernels else 0) | (ACT_BF16_BINARY_HEAD if binary_bf16_head else 0)
-                                    | (ACT_BF16_WIDE_HEAD if bf16_wide_head else 0), C.byref(h)) != 0:
+                                    | (ACT_BF16_WIDE_HEAD if bf16_wide_head else 0) | (ACT_BF16_WIDE_BINARY_HEAD if binary_bf16_wide_head else 0), C.byref(h)) != 0:
             raise PPOHipError(self.lib.ppo_last_error(None).decode())
         self.h = h
         self.P = self.lib.ppo_num_params(self.h)

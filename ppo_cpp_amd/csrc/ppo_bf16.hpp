@@ -2310,3 +2310,179 @@ __global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_wide_multi_kernel(Loss
     if (tid >= 64 * BL_ROWS - 64 && tid < 64 * BL_ROWS - 60) { const int k = tid - (64 * BL_ROWS - 64); float s = 0.f; for (int q = 0; q < BL_ROWS; ++q) s += pt[q * 4 + k]; s0[a.slot_loss + k] = s; }
     if (tid == 64 * BL_ROWS - 32) { float sb = 0.f, sl = 0.f; for (int q = 0; q < BL_ROWS; ++q) { sb += vt[q * 2]; sl += vt[q * 2 + 1]; } s1[a.slot_head] = sb; s1[a.slot_loss] = sl; }
 }
+
+// ==== wide multi-binary head (PPO_ACT_MULTI_BINARY | PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD, 128 < act_dim <= 1024) ================================
+// A independent Bernoulli decisions over the one wide logits row.  The wide family's inputs (WideHeadIn: bf16_logits_kernel's unsplit logits, bf16_value_head_kernel's
+// value), its geometry (one wave per row, EPT = 4 / 8 / 16 logits per lane as 16-byte quads, element e at column wide_col(lane, e), every global load first) and its
+// argument structs (no mask is ever read), under symbols of their own.  NOT the categorical head's arithmetic: no maximum, no argmax, no normaliser -- an element is
+// finished from its own logit (bern_parts: ONE exp and ONE log1p), and the only values that cross lanes are the row's two sums.  So the kernels STREAM: a quad is
+// loaded, its four elements are finished and folded into the lane's two partial sums, and nothing of it is carried on but what the kernel's own output needs --
+//   sample:  the drawn bits, ONE 32-bit word per lane (bit e = element e), turned back into 0.f / 1.f at the store; the deterministic bits are re-read from the logits
+//   eval:    p = P(bit = 1), the parameters' store
+//   loss:    the logit, e = exp(-|l|) and the action bits as one word: the gradient needs d_nlp, which exists only behind the butterfly, and bern_parts_kept
+//            rebuilds p from (l, e) with bern_parts' own operations (a division, no transcendental) -- 2 EPT + 1 registers across the butterfly, not the 4 EPT of a
+//            kept BernParts per element
+// A quad wholly past the row's last bit (256 q >= A: the same for every lane) is skipped on a scalar branch; inside a quad a column past A is finished like any other
+// (its padded logit is finite) and its share is replaced by +0 on a select, which leaves the sums' bits alone (every share is >= +0).
+// wide_bern_row is the ONE reduction of all three kernels: the lane's elements in rising column order (bern_row_add), then bern_row_sums' one interleaved 64-lane
+// butterfly, steps 32 .. 1 -- ppo_step's neglogp, the train model's and ppo_evaluate_actions' are the same bits on the same logits and bits.
+// bit(e, b): the element's bit as 0.f / 1.f -- drawn, given or deterministic; the kernel keeps what it needs of b there.
+template <int EPT, class BIT>
+__device__ __forceinline__ void wide_bern_row(const float (&lg)[EPT], int lane, int A, float& snlp, float& sent, BIT&& bit) {
+    snlp = 0.f; sent = 0.f;
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        if (256 * q < A) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int e = 4 * q + c;
+                const BernParts b = bern_parts(lg[e]);
+                float en = 0.f, ee = 0.f;
+                bern_row_add(b, lg[e], bit(e, b), en, ee);
+                const bool in = wide_col(lane, e) < A;
+                snlp += in ? en : 0.f; sent += in ? ee : 0.f;
+            }
+        }
+    }
+    bern_row_sums(snlp, sent);
+}
+// row `prow` of an [n, A] result, element e from f(e): 16-byte stores when the row stride allows (vec), scalar ones otherwise; columns past A are not written
+template <int EPT, class F>
+__device__ __forceinline__ void wide_store_row(float* __restrict__ prow, int lane, int A, bool vec, F&& f) {
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        const int j = 256 * q + 4 * lane;
+        if (vec) { if (j < A) *reinterpret_cast<float4*>(prow + j) = make_float4(f(4 * q), f(4 * q + 1), f(4 * q + 2), f(4 * q + 3)); }
+        else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) if (j + c < A) prow[j + c] = f(4 * q + c);
+        }
+    }
+}
+__device__ __forceinline__ float wide_bit(uint32_t word, int e) { return (word >> e) & 1u ? 1.0f : 0.0f; }
+
+// act epilogue (bf16_sample_kernel<mbin>'s rules): `noise` holds the uniforms u [n, A] (null: ctr_uniform(seed, global row, call counter, j) under the categorical head's
+// keys, j up to 1023), x_j = u_j < p_j, det_action_j = l_j > 0; action / det_action are [n, A] floats of exactly 0 or 1.  No LDS, no barrier: a dead row's wave
+// returns at once.
+template <int EPT>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_sample_wide_binary_kernel(SampleArgsW a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    float lg[EPT], u[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+    if (a.noise) wide_load_row<EPT>(u, a.noise + (size_t)row * a.A, lane, a.A, 0.5f);
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && a.value);
+    if (!a.noise) {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) { const int j = wide_col(lane, e); u[e] = j < a.A ? ctr_uniform(a.seed, a.row_base + row, a.rng_step, j) : 0.5f; }
+    }
+    uint32_t xw = 0u;
+    float snlp, sent;                                        // (the entropy is not stored here: the compiler drops its sum)
+    wide_bern_row<EPT>(lg, lane, a.A, snlp, sent, [&](int e, const BernParts& b) { const float x = bern_sample(b.p, u[e]); xw |= x != 0.f ? 1u << e : 0u; return x; });
+    const bool vec = (a.A & 3) == 0;
+    if (a.action) wide_store_row<EPT>(a.action + (size_t)row * a.A, lane, a.A, vec, [&](int e) { return wide_bit(xw, e); });
+    if (a.det_action) wide_store_row<EPT>(a.det_action + (size_t)row * a.A, lane, a.A, vec, [&](int e) { return bern_mode(lg[e]); });
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = snlp;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.in.vsplit);
+    }
+}
+
+// policy query (bf16_eval_kernel<mbin>'s rules): the step's loads, elements and row sums with the GIVEN bits where that kernel has the drawn ones (without actions: the
+// deterministic ones), so the action ppo_step drew gets ppo_step's neglogp bit for bit; entropy = the sum of bern_entropy_elem; params [n, W = A] = P(bit = 1).
+template <int EPT>
+__global__ __launch_bounds__(64 * BS_ROWS) void bf16_eval_wide_binary_kernel(EvalArgsW a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * BS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.n) return;                                  // (a row is a whole wave and the kernel has no barrier)
+    const bool given = a.actions != nullptr;
+    float lg[EPT], x[EPT], p[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+    if (given) wide_load_row<EPT>(x, a.actions + (size_t)row * a.A, lane, a.A, 0.f);
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && a.value);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) p[e] = 0.f;                // (a skipped quad: never stored)
+    float snlp, sent;
+    wide_bern_row<EPT>(lg, lane, a.A, snlp, sent, [&](int e, const BernParts& b) { p[e] = b.p; return given ? x[e] : bern_mode(lg[e]); });
+    if (a.params) wide_store_row<EPT>(a.params + (size_t)row * a.W, lane, a.A, ((a.A | a.W) & 3) == 0, [&](int e) { return p[e]; });
+    if (lane == 0) {
+        if (a.neglogp) a.neglogp[row] = snlp;
+        if (a.entropy) a.entropy[row] = sent;
+        if (a.value) a.value[row] = head_parts_sum(vp, a.in.vsplit);
+    }
+}
+
+// loss + d logits (bf16_loss_kernel<mbin>'s rules in bf16_loss_wide_kernel's contract with the assembly): BL_ROWS rows per block, one slot row per block; `actions` holds
+// A floats per row, each exactly 0 or 1 (the host checks).  d logits (bern_grad_elem on bern_parts_kept) leave as one 8-byte bf16 store per quad and as fp32 into the
+// block's [BL_ROWS][Ap] LDS tile, whose column sums -- of the fp32 values, not of their bf16 roundings -- go to slot_head; the aux (d logstd) words are written as zeros;
+// pt[1] is the row's Bernoulli entropy.  Padding columns A <= j < Ap and dead rows: exactly +0.  Surrogate, value tower and the slot epilogue: bf16_loss_wide_kernel's
+// statements.  The tile is BLW_LDS_BYTES(Ap), past the default dynamic-LDS limit at Ap = 1024 (set_lds_bf16_wide raises it).
+template <int EPT>
+__global__ __launch_bounds__(64 * BL_ROWS) void bf16_loss_wide_binary_kernel(LossArgsW a) {
+    extern __shared__ __attribute__((aligned(16))) float ls[];      // [R][Ap] d logits | [R][4] pi terms | [R][2] vf terms
+    float* dl_s = ls; float* pt = ls + BL_ROWS * a.Ap; float* vt = pt + 4 * BL_ROWS;
+    const int tid = threadIdx.x, r = tid >> 6, lane = tid & 63;
+    const int row = blockIdx.x * BL_ROWS + r;
+    const bool live = row < a.n;
+    const float cr = a.hyper[1];
+    const float vcr = a.hyper[2];                   // the value tower's clip range and switch (vf_loss_row)
+    const float voff = a.hyper[3];
+    const float g = a.inv_n;
+    // every load of the lane first (a dead row of the last block reads its own padded logits row and nothing else)
+    float lg[EPT], x[EPT], vp[GB_HEAD_SPLIT];
+    wide_load_logits<EPT>(lg, a.in.logits + (size_t)row * a.in.ldl, lane, a.Ap);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) x[e] = 0.f;
+    if (live) wide_load_row<EPT>(x, a.actions + (size_t)row * a.A, lane, a.A, 0.f);
+    head_parts(vp, a.in.vhead, (size_t)row * a.in.ldv, a.in.vsplit, a.in.vstride, lane == 0 && live);
+    const float adv = live ? a.advs[row] : 0.f;
+    const float old_nlp_in = live ? a.old_neglogp[row] : 0.f;
+    float Rv = 0.f, vo = 0.f;
+    if (lane == 0 && live) { Rv = a.returns[row]; vo = a.old_values[row]; }
+    // policy tower: what crosses the butterfly is lg, ek and one word of bits
+    float ek[EPT];
+    uint32_t xw = 0u;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { lg[e] = live ? lg[e] : 0.f; ek[e] = 1.f; }
+    float nlp, sent;
+    wide_bern_row<EPT>(lg, lane, a.A, nlp, sent, [&](int e, const BernParts& b) { ek[e] = b.e; xw |= x[e] != 0.f ? 1u << e : 0u; return x[e]; });
+    const float old_nlp = live ? old_nlp_in : nlp;
+    const SurrogateRow sr = surrogate_row(nlp, old_nlp, adv, cr);
+    const float d_nlp = surrogate_d_nlp(sr, adv, g, live);
+    if (lane == 0) surrogate_terms(sr, nlp, old_nlp, sent, cr, live, pt, r);
+#pragma unroll
+    for (int q = 0; q < EPT / 4; ++q) {
+        const int j = 256 * q + 4 * lane;
+        if (j < a.Ap) {
+            float d[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int e = 4 * q + c;
+                d[c] = 0.f;
+                if (live && j + c < a.A) d[c] = bern_grad_elem(d_nlp, bern_parts_kept(lg[e], ek[e]), lg[e], wide_bit(xw, e), a.ent_coef, g);
+            }
+            *reinterpret_cast<float4*>(dl_s + r * a.Ap + j) = make_float4(d[0], d[1], d[2], d[3]);
+            bf16x4 o; o[0] = (bf16_t)d[0]; o[1] = (bf16_t)d[1]; o[2] = (bf16_t)d[2]; o[3] = (bf16_t)d[3];
+            *reinterpret_cast<bf16x4*>(a.dhead[0] + (size_t)row * a.Ap + j) = o;
+        }
+    }
+    // value tower (G:10213-10837, G:14975-19571)
+    if (lane == 0) {
+        float dv = 0.f, lossv = 0.f;
+        if (live) vf_loss_row(head_parts_sum(vp, a.in.vsplit), Rv, vo, vcr, voff, a.vf_coef * 0.5f * a.inv_n, lossv, dv);
+        vt[r * 2] = dv; vt[r * 2 + 1] = lossv;
+        a.dhead[1][(size_t)row * a.Ap] = (bf16_t)dv;
+    }
+    __syncthreads();
+    float* s0 = a.slots[0] + (size_t)blockIdx.x * a.slot_w;
+    float* s1 = a.slots[1] + (size_t)blockIdx.x * a.slot_w;
+    for (int j = tid; j < a.Ap; j += 64 * BL_ROWS) {          // db_pi: fp32 sums of the fp32 values in row order; the aux words: zeros
+        float sb = 0.f;
+#pragma unroll
+        for (int q = 0; q < BL_ROWS; ++q) sb += dl_s[q * a.Ap + j];
+        s0[a.slot_head + j] = sb; s0[a.slot_aux + j] = 0.f;
+    }
+    if (tid >= 64 * BL_ROWS - 64 && tid < 64 * BL_ROWS - 60) { const int k = tid - (64 * BL_ROWS - 64); float s = 0.f; for (int q = 0; q < BL_ROWS; ++q) s += pt[q * 4 + k]; s0[a.slot_loss + k] = s; }
+    if (tid == 64 * BL_ROWS - 32) { float sb = 0.f, sl = 0.f; for (int q = 0; q < BL_ROWS; ++q) { sb += vt[q * 2]; sl += vt[q * 2 + 1]; } s1[a.slot_head] = sb; s1[a.slot_loss] = sl; }
+}

@@ -99,6 +99,12 @@ __device__ __forceinline__ BernParts bern_parts(float l) {
     const float q = e / (1.0f + e);
     return {e, log1pf(e), q, l >= 0.0f ? 1.0f / (1.0f + e) : q};
 }
+// bern_parts from a KEPT e = exp(-|l|), for a kernel that carries (l, e) across a reduction instead of the four parts (the wide multi-binary loss kernel): q and p by
+// bern_parts' own operations, the same bits; sp is not formed -- only bern_grad_elem, which does not read it, may take the result.
+__device__ __forceinline__ BernParts bern_parts_kept(float l, float e) {
+    const float q = e / (1.0f + e);
+    return {e, 0.0f, q, l >= 0.0f ? 1.0f / (1.0f + e) : q};
+}
 __device__ __forceinline__ float bern_sample(float p, float u) { return u < p ? 1.0f : 0.0f; }
 __device__ __forceinline__ float bern_mode(float l) { return l > 0.0f ? 1.0f : 0.0f; }
 __device__ __forceinline__ float bern_nlp_elem(BernParts b, float l, float x) { return b.sp + (((x != 0.0f) == (l > 0.0f)) ? 0.0f : fabsf(l)); }

@@ -73,7 +73,8 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_NARROW_ROLLOUT_CAT, KV_NARROW_ROLLOUT_CAT_MASK, KV_NARROW_ROLLOUT_MCAT, KV_NARROW_ROLLOUT_MCAT_MASK,
                      KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_BF16_STEP_MBIN, KV_BF16_TRAIN_MBIN,
                      KV_BF16_STEP_WCAT, KV_BF16_STEP_WCAT_MASK, KV_BF16_TRAIN_WCAT, KV_BF16_TRAIN_WCAT_MASK,
-                     KV_BF16_STEP_WMCAT, KV_BF16_STEP_WMCAT_MASK, KV_BF16_TRAIN_WMCAT, KV_BF16_TRAIN_WMCAT_MASK, KV_TOTAL };
+                     KV_BF16_STEP_WMCAT, KV_BF16_STEP_WMCAT_MASK, KV_BF16_TRAIN_WMCAT, KV_BF16_TRAIN_WMCAT_MASK,
+                     KV_BF16_STEP_WMBIN, KV_BF16_TRAIN_WMBIN, KV_TOTAL };
 // ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all,
 // which is FROZEN in turn at the first KV_ALL_COUNT rows (a caller asserts that count too).  Every variant, later ones included, is reached by name through
 // ppo_kernel_count and enumerated by ppo_kernel_variant_name: no caller may hold THAT list's length.
@@ -81,7 +82,7 @@ constexpr int KV_LEGACY_COUNT = 60;
 constexpr int KV_ALL_COUNT = 62;
 static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
 static_assert(KV_ALL_COUNT == KV_TRAIN8_MBIN, "the rows of ppo_kernel_counts_all end where the first variant named after it begins");
-// The variant list (KV_TOTAL = 73 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
+// The variant list (KV_TOTAL = 75 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
 // hands out one name at a time, and ppo_host_learn_binary's walk stops at its callers' 64 entries itself (it ends one name short of the list).
 // KV_COUNT below is FROZEN at the 63 names in front of the bf16 <mbin> pair, and the assertion on it can no longer fail: it constrains nothing.  It stands only because
 // tests/test_multi_binary.py::test_source_names_the_head_in_every_layer looks for this line of text; when that test's pin is updated, both lines go.
@@ -132,7 +133,10 @@ const char* kVariantNames[KV_TOTAL] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "bf16_step_sequence<wcat>", "bf16_step_sequence<wcat,mask>", "bf16_train_sequence<wcat>", "bf16_train_sequence<wcat,mask>",
                                        // a wide multi-categorical PPO_BF16 handle (PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD, sum(nvec) > 128): counted INSTEAD of the
                                        // "bf16_*_sequence<mcat[,mask]>" names; ppo_kernel_count / ppo_kernel_variant_name only.  (The longest has the 31 characters a variant name may have.)
-                                       "bf16_step_sequence<wmcat>", "bf16_step_sequence<wmcat,mask>", "bf16_train_sequence<wmcat>", "bf16_train_sequence<wmcat,mask>"};
+                                       "bf16_step_sequence<wmcat>", "bf16_step_sequence<wmcat,mask>", "bf16_train_sequence<wmcat>", "bf16_train_sequence<wmcat,mask>",
+                                       // a wide multi-binary PPO_BF16 handle (PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD, act_dim > 128): counted INSTEAD of the
+                                       // "bf16_*_sequence<mbin>" names; ppo_kernel_count / ppo_kernel_variant_name only
+                                       "bf16_step_sequence<wmbin>", "bf16_train_sequence<wmbin>"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -325,7 +329,8 @@ struct ppo_handle {
         bool wide = false;                              // PPO_ACT_BF16_WIDE_HEAD took effect (categorical, act_dim > 128) or PPO_ACT_BF16_WIDE_MULTI_HEAD did (multi-categorical,
                                                         // sum(nvec) > 128): head_out[0] is [1][Rcap][Ap] unsplit logits (bf16_logits_kernel), head_out[1] a 128-column image
                                                         // (bf16_value_head_kernel), the row kernels are the <EPT, MASK> wide forms -- of a multi-categorical handle the
-                                                        // bf16_*_wide_multi_kernel ones (wide_multi)
+                                                        // bf16_*_wide_multi_kernel ones (wide_multi).  Or PPO_ACT_BF16_WIDE_BINARY_HEAD did (multi-binary, act_dim > 128):
+                                                        // the same two images, the row kernels the bf16_*_wide_binary_kernel<EPT> ones (wide_binary)
         // the fused assembly + Adam launch does not write the assembled gradient: whoever asks for it (ppo_get_last_grad, ppo_debug_buffer) has it rebuilt
         // from the last train step's slabs first (bf16_materialize_grad).  enqueued: the last train step ENQUEUED; captured: the last step of the captured update
         // graph (the host code of a train step does not run on a replay, so the whole value is restored after one); ran: the last train step that RAN -- on: h->grad
@@ -1089,6 +1094,8 @@ int bf16_wide_heads(ppo_handle* h, int Rp) {
 }
 // a wide handle with components runs the multi forms of the three row kernels: the categorical form's arguments with the component table behind them
 static bool wide_multi(const ppo_handle* h) { return h->dist == PPO_ACT_MULTI_CATEGORICAL; }
+// a wide multi-binary handle runs the binary forms: the categorical form's arguments as they are (no mask is ever read), EPT the one template argument
+static bool wide_binary(const ppo_handle* h) { return h->dist == PPO_ACT_MULTI_BINARY; }
 template <class M, class B>
 static M wide_multi_args(const ppo_handle* h, const B& base) { M m{}; static_cast<B&>(m) = base; m.comp = h->comp; return m; }
 static WideHeadIn bf16_wide_in(const ppo_handle* h) {
@@ -1101,7 +1108,9 @@ int bf16_wide_sample(ppo_handle* h, const StepArgs& a) {
     sa.in = bf16_wide_in(h); sa.noise = a.noise; sa.mask = a.mask; sa.action = a.action; sa.det_action = a.det_action; sa.value = a.value; sa.neglogp = a.neglogp;
     sa.n = a.n; sa.A = n.A; sa.Ap = n.Ap; sa.seed = a.seed; sa.rng_step = a.rng_step; sa.row_base = a.row_base;
     const dim3 grid((a.n + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
-    if (wide_multi(h)) {
+    if (wide_binary(h))
+        with_wide_row(n.A, false, [&](auto E, auto) { hipLaunchKernelGGL((bf16_sample_wide_binary_kernel<decltype(E)::value>), grid, blk, 0, h->stream, sa); });
+    else if (wide_multi(h)) {
         const SampleArgsWM sm = wide_multi_args<SampleArgsWM>(h, sa);
         with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_sample_wide_multi_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, sm); });
     } else
@@ -1118,7 +1127,9 @@ int bf16_wide_eval(ppo_handle* h, const EvalArgs& a, int r0, int rows) {
     ea.params = a.params ? a.params + (size_t)r0 * a.W : nullptr;
     ea.n = rows; ea.A = n.A; ea.Ap = n.Ap; ea.W = a.W;
     const dim3 grid((rows + BS_ROWS - 1) / BS_ROWS), blk(64 * BS_ROWS);
-    if (wide_multi(h)) {
+    if (wide_binary(h))
+        with_wide_row(n.A, false, [&](auto E, auto) { hipLaunchKernelGGL((bf16_eval_wide_binary_kernel<decltype(E)::value>), grid, blk, 0, h->stream, ea); });
+    else if (wide_multi(h)) {
         const EvalArgsWM em = wide_multi_args<EvalArgsWM>(h, ea);
         with_wide_row(n.A, a.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_eval_wide_multi_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, 0, h->stream, em); });
     } else
@@ -1136,7 +1147,9 @@ int bf16_wide_loss(ppo_handle* h, const TrainArgs& ta, int Rp) {
     for (int t = 0; t < 2; ++t) { la.dhead[t] = b.dhead[t]; la.slots[t] = h->slots[t]; }
     la.slot_w = n.slot_w; la.slot_head = n.slot_head; la.slot_aux = n.slot_aux; la.slot_loss = n.slot_loss;
     const dim3 grid(Rp / BL_ROWS), blk(64 * BL_ROWS);
-    if (wide_multi(h)) {
+    if (wide_binary(h))
+        with_wide_row(n.A, false, [&](auto E, auto) { hipLaunchKernelGGL((bf16_loss_wide_binary_kernel<decltype(E)::value>), grid, blk, BLW_LDS_BYTES(n.Ap), h->stream, la); });
+    else if (wide_multi(h)) {
         const LossArgsWM lm = wide_multi_args<LossArgsWM>(h, la);
         with_wide_row(n.A, ta.mask != nullptr, [&](auto E, auto M) { hipLaunchKernelGGL((bf16_loss_wide_multi_kernel<decltype(E)::value, decltype(M)::value>), grid, blk, BLW_LDS_BYTES(n.Ap), h->stream, lm); });
     } else
@@ -1433,7 +1446,7 @@ static auto nw_rollout_fn(T) {
 int launch_step(ppo_handle* h, const StepArgs& a0) {
     const Head hd = head_of(h, a0.mask != nullptr);                 // (a multi-categorical handle: bf16 only when created with PPO_ACT_BF16_MULTI_HEAD; narrow only when created with PPO_ACT_SHAPE_KERNELS: ppo_create_multi_ex, build_narrow_layout)
     if (a0.mask && !hd.cat) return fail(h, "policy step: an action mask needs a categorical handle");
-    if (h->bf.wide) ++h->kv[hd.multi ? (hd.mask ? KV_BF16_STEP_WMCAT_MASK : KV_BF16_STEP_WMCAT) : hd.mask ? KV_BF16_STEP_WCAT_MASK : KV_BF16_STEP_WCAT];
+    if (h->bf.wide) ++h->kv[hd.bin ? KV_BF16_STEP_WMBIN : hd.multi ? (hd.mask ? KV_BF16_STEP_WMCAT_MASK : KV_BF16_STEP_WMCAT) : hd.mask ? KV_BF16_STEP_WCAT_MASK : KV_BF16_STEP_WCAT];
     else ++h->kv[kHeadVariant[h->bf.on ? KF_BF16_STEP : !h->narrow ? KF_POLICY_STEP : h->nw_static ? KF_NARROW_STEP_STATIC : KF_NARROW_STEP][hd.index()]];
     if (h->bf.on) return launch_step_bf16(h, a0);
     ProfScope ps(h, PK_STEP);
@@ -1688,6 +1701,7 @@ static bool set_lds_bf16_wide(const ppo_handle* h) {
         with_wide_row(A, m, [&](auto E, auto M) {
             set(bf16_loss_wide_kernel<decltype(E)::value, decltype(M)::value>, BLW_LDS_BYTES(1024));
             set(bf16_loss_wide_multi_kernel<decltype(E)::value, decltype(M)::value>, BLW_LDS_BYTES(1024));
+            if constexpr (!decltype(M)::value) set(bf16_loss_wide_binary_kernel<decltype(E)::value>, BLW_LDS_BYTES(1024));
         });
     return ok;
 }
@@ -1842,7 +1856,7 @@ static int train_bf16(ppo_handle* h, const TrainArgs& ta, float* loss_row, bool 
     const int Rp = ru(ta.n, GB_PAD);
     const Head hd = head_of(h, ta.mask != nullptr);                 // (a multi-categorical handle: PPO_ACT_BF16_MULTI_HEAD, ppo_create_multi_ex)
     if (ta.mask && !hd.cat) return fail(h, "train step: an action mask needs a categorical handle");
-    if (h->bf.wide) ++h->kv[hd.multi ? (hd.mask ? KV_BF16_TRAIN_WMCAT_MASK : KV_BF16_TRAIN_WMCAT) : hd.mask ? KV_BF16_TRAIN_WCAT_MASK : KV_BF16_TRAIN_WCAT];
+    if (h->bf.wide) ++h->kv[hd.bin ? KV_BF16_TRAIN_WMBIN : hd.multi ? (hd.mask ? KV_BF16_TRAIN_WMCAT_MASK : KV_BF16_TRAIN_WMCAT) : hd.mask ? KV_BF16_TRAIN_WCAT_MASK : KV_BF16_TRAIN_WCAT];
     else ++h->kv[kHeadVariant[KF_BF16_TRAIN][hd.index()]];
     h->bf.lazy.enqueued.on = false;
     if (bucketed) return bf16_train_bucketed(h, ta, Rp, loss_row) ? -1 : TRAIN_DONE;
@@ -2133,15 +2147,16 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     // the flags every distribution accepts go (PPO_ACT_BF16_MULTI_HEAD through ppo_create_multi_ex only); whatever else is left must be a distribution.  The two binary
     // flags belong to PPO_ACT_MULTI_BINARY alone: beside any other distribution they stay in and are refused (ppo_create_multi_ex has refused them: "unknown flag bit")
     int32_t dist = action_dist & ~(int32_t)(PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS | (nvec ? PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD : 0));
-    if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS | PPO_ACT_BF16_BINARY_HEAD)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
+    if (!nvec && (dist & ~(int32_t)(PPO_ACT_BINARY_SHAPE_KERNELS | PPO_ACT_BINARY_PAIR_KERNELS | PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD)) == PPO_ACT_MULTI_BINARY) dist = PPO_ACT_MULTI_BINARY;
     // PPO_ACT_BF16_WIDE_HEAD likewise belongs to PPO_ACT_CATEGORICAL alone
     if (!nvec && (dist & ~(int32_t)PPO_ACT_BF16_WIDE_HEAD) == PPO_ACT_CATEGORICAL) dist = PPO_ACT_CATEGORICAL;
     const bool cat = dist == PPO_ACT_CATEGORICAL, mcat = dist == PPO_ACT_MULTI_CATEGORICAL, mbin = dist == PPO_ACT_MULTI_BINARY, bf16 = cfg->compute_dtype == PPO_BF16;
     if (dist != PPO_ACT_GAUSSIAN && !cat && !mbin && !(mcat && nvec))
         return fail(nullptr, "ppo_create_ex: unknown action_dist %d (PPO_ACT_GAUSSIAN, PPO_ACT_CATEGORICAL or PPO_ACT_MULTI_BINARY, optionally | PPO_ACT_SHAPE_KERNELS | PPO_ACT_BF16_HEAD | PPO_ACT_PAIR_KERNELS; "
-                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)%s%s", (int)dist,
+                             "PPO_ACT_BINARY_SHAPE_KERNELS and PPO_ACT_BINARY_PAIR_KERNELS only beside PPO_ACT_MULTI_BINARY; a multi-categorical handle is created with ppo_create_multi)%s%s%s", (int)dist,
                     (dist & PPO_ACT_BF16_BINARY_HEAD) ? "; PPO_ACT_BF16_BINARY_HEAD belongs to PPO_ACT_MULTI_BINARY alone" : "",
-                    (dist & PPO_ACT_BF16_WIDE_HEAD) ? "; PPO_ACT_BF16_WIDE_HEAD belongs to PPO_ACT_CATEGORICAL alone" : "");
+                    (dist & PPO_ACT_BF16_WIDE_HEAD) ? "; PPO_ACT_BF16_WIDE_HEAD belongs to PPO_ACT_CATEGORICAL alone" : "",
+                    (dist & PPO_ACT_BF16_WIDE_BINARY_HEAD) ? "; PPO_ACT_BF16_WIDE_BINARY_HEAD belongs to PPO_ACT_MULTI_BINARY alone" : "");
     if (cat && cfg->act_dim < 2) return fail(nullptr, "ppo_create_ex: a categorical head needs act_dim >= 2 categories (got %d)", (int)cfg->act_dim);
     if (cat && bf16 && !(action_dist & PPO_ACT_BF16_HEAD))
         return fail(nullptr, "ppo_create_ex: PPO_ACT_CATEGORICAL with compute_dtype PPO_BF16 is not supported without PPO_ACT_BF16_HEAD (the categorical head runs on the PPO_F32 path unless that flag opts in)");
@@ -2152,7 +2167,10 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
         return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_HEAD: the categorical head of the PPO_BF16 path holds at most 128 categories (got %d)", (int)cfg->act_dim);
     if (mbin && bf16 && !(action_dist & PPO_ACT_BF16_BINARY_HEAD))
         return fail(nullptr, "ppo_create_ex: PPO_ACT_MULTI_BINARY with compute_dtype PPO_BF16 is not supported (the multi-binary head runs on the PPO_F32 path)");
-    if (mbin && bf16 && cfg->act_dim > 128)
+    const bool wideb = mbin && bf16 && (action_dist & PPO_ACT_BF16_WIDE_BINARY_HEAD);
+    if (wideb && cfg->act_dim > 1024)
+        return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_WIDE_BINARY_HEAD: the wide multi-binary head of the PPO_BF16 path holds at most 1024 bits (got %d)", (int)cfg->act_dim);
+    if (mbin && bf16 && !wideb && cfg->act_dim > 128)
         return fail(nullptr, "ppo_create_ex: PPO_ACT_BF16_BINARY_HEAD: the multi-binary head of the PPO_BF16 path holds at most 128 bits (got %d)", (int)cfg->act_dim);
     for (int l = 0; l < cfg->n_hidden; ++l) if (cfg->hidden[l] < 1) return fail(nullptr, "ppo_create: bad hidden size");
     rq = CreateRequest{};
@@ -2165,6 +2183,8 @@ static int parse_create(const ppo_config* cfg, int32_t action_dist, const int32_
     rq.wide = wide && rq.bf16 && cfg->act_dim > 128;               // (up to 128 categories the flag changes nothing: the 128-wide kernels, their bits and their counters)
     // PPO_ACT_BF16_WIDE_MULTI_HEAD likewise for the multi-categorical head (ppo_create_multi_ex has checked sum(nvec) = act_dim against 128 / 1024)
     if (mcat && rq.bf16 && (action_dist & PPO_ACT_BF16_WIDE_MULTI_HEAD) && cfg->act_dim > 128) rq.wide = true;
+    // PPO_ACT_BF16_WIDE_BINARY_HEAD likewise for the multi-binary head (up to 128 bits: the 128-wide <mbin> kernels, their bits and their counters)
+    if (wideb && rq.bf16 && cfg->act_dim > 128) rq.wide = true;
     return 0;
 }
 

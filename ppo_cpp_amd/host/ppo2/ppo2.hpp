@@ -87,6 +87,8 @@ public:
     // cfg.compute_dtype = PPO_BF16 creates the handle on the bf16 path's wide categorical head (at most 1024 categories).
     // For a multi-discrete Env with more than 128 logits, PPO_ACT_BF16_MULTI_HEAD | PPO_ACT_BF16_WIDE_MULTI_HEAD with cfg.compute_dtype = PPO_BF16 creates it on the
     // bf16 path's wide multi-categorical head (sum of nvec at most 1024).
+    // For an IMultiBinary Env with more than 128 bits, PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD with cfg.compute_dtype = PPO_BF16 creates it on the
+    // bf16 path's wide multi-binary head (at most 1024 bits).
     // Returns the library's status; ppo_last_error(nullptr) has the message.
     static int create_handle(const ppo_config& cfg, Env& env, ppo_handle** out, bool discrete_shape_kernels = false, int32_t extra_flags = 0) {
         const std::vector<int> nvec = action_nvec_of(&env);

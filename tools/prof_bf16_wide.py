@@ -1,9 +1,11 @@
-"""tools/prof_bf16_wide.py [out.json] -- the wide categorical head of the bf16 path (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD with compute_dtype
+"""tools/prof_bf16_wide.py [--head categorical|binary] [out.json] -- the wide categorical head of the bf16 path (PPO_ACT_CATEGORICAL | PPO_ACT_BF16_HEAD | PPO_ACT_BF16_WIDE_HEAD with compute_dtype
 PPO_BF16: bf16_logits_kernel, bf16_value_head_kernel, bf16_{sample,loss}_wide_kernel) at A = 1024 and A = 256 beside the nearest form there was before it, the
 PPO_ACT_BF16_HEAD handle at A = 128 (no fp32 family holds this net).  256 observations, hidden [1024, 1024, 1024].  Device time (ppo_prof_read, all classes added,
 and each class by itself) of one ppo_train_step on 4096 and on 256 rows and of one ppo_step on 8192 rows.  The three handles live in ONE process and alternate round
 by round (ROUNDS rounds of REPS calls after a warm-up); a handle's figure is the median of its rounds, the spread their max - min.  The per-class figures show where
 the padded value head's cost lands: train_fwd_bwd (link 0 over Ap columns), weight_grad (the vf/w tiles), grad_reduce (Adam over the padded words).
+--head binary: the wide multi-binary head (PPO_ACT_MULTI_BINARY | PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD: bf16_{sample,loss}_wide_binary_kernel) at
+A = 1024 and A = 256, in the SAME process and rounds the wide categorical handle at the same A and the 128-bit PPO_ACT_BF16_BINARY_HEAD handle.
 Per-kernel times (the logits product against a hidden layer's share of gemm_chain_bf16_kernel, the three row kernels) come from a kernel trace of this script."""
 import json
 import os
@@ -14,7 +16,17 @@ import ppo_cpp_amd
 
 O, HIDDEN = 256, [1024, 1024, 1024]
 TRAIN_ROWS, STEP_ROWS, ROUNDS, REPS = (4096, 256), (8192,), 7, 10
-HANDLES = {"cat_A128": (128, {}), "wide_A256": (256, dict(bf16_wide_head=True)), "wide_A1024": (1024, dict(bf16_wide_head=True))}
+CAT, BIN = dict(action_dist="categorical", bf16_head=True), dict(action_dist="multi_binary", binary_bf16_head=True)
+HANDLES = {"cat_A128": (128, CAT), "wide_A256": (256, dict(CAT, bf16_wide_head=True)), "wide_A1024": (1024, dict(CAT, bf16_wide_head=True))}
+args = sys.argv[1:]
+if "--head" in args:
+    head = args.pop(args.index("--head") + 1)
+    args.remove("--head")
+    if head == "binary":
+        HANDLES = {"mbin_A128": (128, BIN), "wide_A256": HANDLES["wide_A256"], "wbin_A256": (256, dict(BIN, binary_bf16_wide_head=True)),
+                   "wide_A1024": HANDLES["wide_A1024"], "wbin_A1024": (1024, dict(BIN, binary_bf16_wide_head=True))}
+    elif head != "categorical":
+        sys.exit("--head takes categorical or binary, not %r" % head)
 
 
 def timed(g, call):
@@ -29,7 +41,7 @@ def timed(g, call):
 rng = np.random.RandomState(0)
 jobs = {}
 for name, (A, kw) in HANDLES.items():
-    g = ppo_cpp_amd.PPOHip(O, A, HIDDEN, action_dist="categorical", compute_dtype=1, bf16_head=True, **kw)
+    g = ppo_cpp_amd.PPOHip(O, A, HIDDEN, compute_dtype=1, **kw)
     g.init_orthogonal(0)
     for n in TRAIN_ROWS + STEP_ROWS:
         obs = rng.uniform(-1, 1, (n, O)).astype(np.float32)
@@ -61,5 +73,5 @@ for what, rows in (("train", TRAIN_ROWS), ("step", STEP_ROWS)):
 for (what, n, name), (g, _) in jobs.items():
     if what == "step":
         print("%s kernels: %s" % (name, {k: v for k, v in g.kernel_variants().items() if v}))
-if len(sys.argv) > 1:
-    json.dump(out, open(sys.argv[1], "w"), indent=1)
+if args:
+    json.dump(out, open(args[0], "w"), indent=1)
