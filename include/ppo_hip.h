@@ -466,6 +466,31 @@ int ppo_rollout_evaluate(ppo_handle* h, float* value, float* neglogp, float* ent
 int ppo_set_bf16_queries(ppo_handle* h, int32_t on);      /* any time; host state only */
 int ppo_bf16_queries(const ppo_handle* h);                /* the setting (0 / 1) */
 
+/* ---- small-batch policy step of a PPO_BF16 handle (opt-in; no reference counterpart) ------------------------------------------------------------------------
+ * The bf16 path pads a step's rows to 128 and runs every hidden layer as 128-row x 128-column tile GEMMs: at 1 .. 64 rows -- the environments of a host Env
+ * rollout, one ppo_act_deterministic call in deployment -- that is 16 workgroups at width 1024, each pushing a tile of which at most half the rows are live through
+ * the whole reduction.  ppo_set_bf16_small_step(h, 1) gives such calls bf16_small_forward_kernel<RT> (ppo_bf16.hpp) for the hidden layers: RT = ceil(n / 16) MFMA
+ * row tiles, the COLUMNS split instead of the rows -- 2 towers x (width / 64) workgroups of four waves, a wave owning 16 columns for every row tile and the whole
+ * reduction, the weights streamed once as they lie through a ring of [64 k][64] LDS-DMA stages, one launch per hidden layer with both towers in it, nothing that
+ * waits on another workgroup.  In front (bf16_stage) and behind (the head kernels of every head form, narrow or wide, sample and eval) nothing changes.
+ * BIT FOR BIT the tile path's results on every live row: each output is one accumulator fed in rising k by the same matrix instruction with the same operand
+ * roles, then the same bias + tanh + rounding (DESIGN.md section 4 names the lines).  Rows of the activation workspaces behind 16 RT are not written while the
+ * setting is on (the kernels behind treat rows independently): what ppo_debug_buffer shows there is unspecified.
+ * Scope: the calls below when they launch a step or a query of n <= 64 rows -- ppo_step[_masked], ppo_act_deterministic, ppo_value, ppo_rollout_act[_masked] behind a
+ * host Env, the passes of ppo_rollout_finish (the bootstrap value pass over the E environments, the terminal-value pass over the K rows marked by
+ * ppo_rollout_mark_truncated, per chunk, and where a form left the values to it the pass over all T * E rows), and after ppo_set_bf16_queries the three policy
+ * queries (per chunk; a call counts once when any of its chunks took the form).  The launch layer marks exactly these callers (StepArgs::small_ok): more rows,
+ * ppo_train_step, ppo_update, ppo_collect_synthetic (its per-step launches and its value pass, at any number of environments) and the data-parallel train forms keep
+ * their kernels.  A PPO_F32 handle accepts the setting and changes nothing.  Host state only:
+ * any time, nothing on the device is touched, nothing is dropped.  Counted under "bf16_small_forward" (ppo_kernel_count / ppo_kernel_variant_name only; once per
+ * call that took the form, beside the call's "bf16_step_sequence[<..>]" count, which is unchanged); ppo_kernel_counts keeps its 60 rows, ppo_kernel_counts_all 62.
+ * Measured (MI355X, 256 observations, [1024,1024,1024], 64 actions, device time of one ppo_step, median of 7 rounds, off -> on):
+ * 1 row 53.4 -> 31.3 us, 16 rows 53.5 -> 31.5, 32 rows 53.9 -> 33.9, 64 rows 53.8 -> 38.7 (spreads 0.3 - 0.8); the wide categorical handle (A = 1024) at 64 rows
+ * 71.3 -> 56.1; a ppo_rollout_act / ppo_rollout_observe loop behind a stand-in host Env, wall time per env step: 77.3 -> 54.8 at one environment, 86.3 -> 71.1 at 64.
+ * The form wins at every RT, so the threshold is the kernel's limit, 64 rows (tools/prof_bf16_small.py, profiles/r28_a_bf16_small_step_timing.txt). */
+int ppo_set_bf16_small_step(ppo_handle* h, int32_t on);   /* 0 / 1; any time; host state only */
+int ppo_bf16_small_step(const ppo_handle* h);             /* the setting, not whether it took effect */
+
 /* ---- action masks of the categorical head (invalid-action masking; no reference counterpart) ---------------
  * A mask is one float per (row, category), [n, A]: non-zero = allowed, 0 = forbidden.  For a masked row with logits l and allowed set S:
  *   forbidden categories are EXCLUDED, not pushed down by a constant:  m = max_{j in S} l_j,  z = sum_{j in S} exp(l_j - m),

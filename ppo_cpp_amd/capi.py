@@ -359,6 +359,17 @@ class PPOHip:
         """the setting"""
         return bool(self.lib.ppo_bf16_queries(self.h))
 
+    def set_bf16_small_step(self, on=True):
+        """Steps and queries of at most 64 rows on a compute_dtype=1 (PPO_BF16) handle (include/ppo_hip.h, ppo_set_bf16_small_step): on, their hidden layers run
+        bf16_small_forward_kernel (16-row MFMA tiles, the columns split over the workgroups) instead of the 128-row tile GEMMs -- the same bits on every live row,
+        every head form; counted by kernel_count("bf16_small_forward").  Off is the default.  Host state only; a compute_dtype=0 handle accepts it and nothing changes."""
+        self._ck(self.lib.ppo_set_bf16_small_step(self.h, int(bool(on))))
+
+    @property
+    def bf16_small_step(self):
+        """the setting (not whether a call took the form)"""
+        return bool(self.lib.ppo_bf16_small_step(self.h))
+
     # ---- train ------------------------------------------------------------------------------------
     def train_step(self, lr, cliprange, obs, actions, advs, returns, old_nlp, old_v, mask=None):
         arrs = [_f32(x) for x in (obs, actions, advs, returns, old_nlp, old_v)]

@@ -371,6 +371,136 @@ __global__ __launch_bounds__(GB_THREADS(WM)) void gemm_nt_bf16_kernel(GemmArgs a
     gemm_nt_tile<WM, EPI>(a, tw, ti * GB_BM(WM), tj * GB_N, gb_lds, gst);
 }
 
+// ---- one hidden layer of BOTH towers for at most 64 live rows (ppo_set_bf16_small_step) -------------------------------------------------
+// The tile GEMM above gives a step of 1 .. 64 rows one 128-row tile per 128 columns: 16 workgroups at width 1024, each walking the whole reduction for a tile of which
+// at most half the rows are live.  Here the rows are RT = ceil(n / 16) MFMA row tiles and the COLUMNS are what is split: a workgroup owns CW columns, a wave 16 of them
+// for all RT row tiles (RT accumulators) and the whole of K, so the grid is 2 towers x (J / CW) workgroups of CW / 16 waves.  Nothing is shared between workgroups
+// and nothing waits on another one.
+// SAME BITS as gemm_nt_bf16_kernel<WM, GEPI_TANH> on every row below 16 RT: an output element is ONE accumulator that starts at zero (gb_mainloop's first loop) and
+// takes the 32-deep matrix instructions in rising k, two per 64-deep stage, ks = 0 then 1, the weight fragment as the first operand (gb_mainloop's
+// `for ks .. mfma(bfr[ks][b], af[ks][a], acc)`), a lane's fragment element e being k = 32 ks + 8 (lane >> 4) + e of its row / column on both sides (gb_frag, gt_frag);
+// then gb_epilogue_bf16's GEPI_TANH line, bf16_tanh_scaled(fmaf(acc, K2, bias * K2)), and its (bf16_t) rounding.  The reduction is never cut.
+// A stage of the LDS ring is the [16 RT][64 k] activation tile (gb_stage_piece's A pieces: 128-byte rows, gb_swz, read back with gb_frag) followed by the [64 k][CW]
+// weight image as it lies (rows of 2 CW bytes), both brought in by LDS-DMA; a workgroup streams its [K][CW] weight strip exactly once.  The ring is as deep as
+// 48 KB allow, 8 stages at most (SF_STAGES: no LDS opt-in): the launch is bound by the latency of its few requests, not by bytes, so what counts is how many are in flight.
+// Weight image, transposed reads (gt_frag's geometry): one read's 32-lane half covers rows {b .. b + 3} and {b + 8 .. b + 11} (b a multiple of 4) x the wave's two
+// 16-byte chunks 2 w, 2 w + 1.  Bank row = address mod 256.  CW = 64 (128-byte rows): row m covers half m & 1 of the bank row, so the four rows of one parity
+// ({b, b + 2, b + 8, b + 10}: they differ in bits 1 and 3) must put their chunk pair on four different pairs of the 8 slots: slot = chunk ^ (bit 1 of m << 1 | bit 3
+// of m << 2).  CW = 32 (64-byte rows): row m covers quarter m & 3, shared by m and m + 8 alone: slot = chunk ^ (bit 3 of m << 1).  Either way the 16 (row, chunk)
+// pairs of a half land on the 16 different 16-byte slots of the bank row: conflict-free.  The A tile's reads are gb_frag's (gb_swz).
+#ifndef SF_CW
+#define SF_CW 64                    // columns per workgroup: 32 workgroups of 4 waves at width 1024 (measured against 32: profiles/EXPERIMENTS.md)
+#endif
+#define SF_MAX_ROWS 64
+#define SF_WAVES(CW) ((CW) / 16)
+#define SF_STAGE_BYTES(RT, CW) ((RT) * 2048 + (CW) * GB_K * 2)
+#define SF_STAGES(RT, CW) (49152 / SF_STAGE_BYTES(RT, CW) < 8 ? 49152 / SF_STAGE_BYTES(RT, CW) : 8)
+#define SF_LDS_BYTES(RT, CW) (SF_STAGES(RT, CW) * SF_STAGE_BYTES(RT, CW))
+#define SF_PIECES(RT, CW) (2 * (RT) + (CW) / 8)                                            // 1-KB LDS-DMA pieces of a stage: A tile, then the weight image
+#define SF_NPW(RT, CW) ((SF_PIECES(RT, CW) + SF_WAVES(CW) - 1) / SF_WAVES(CW))             // ... per wave
+template <int CW> __device__ __forceinline__ int sf_swz(int m) { return CW == 64 ? (((m >> 1) & 1) << 1) | (((m >> 3) & 1) << 2) : ((m >> 3) & 1) << 1; }
+
+// every wave issues SF_NPW pieces per stage (the wait below counts them): where the pieces do not divide among the waves, the last ones are fetched twice, the same
+// bytes to the same place
+template <int RT, int CW>
+__device__ __forceinline__ void sf_stage(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb, int j0, int k0, char* st) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int PA = 2 * RT, TP = SF_PIECES(RT, CW), CH = CW / 8, RPP = 64 / CH;        // chunks per weight row, weight rows per piece
+    typedef const __attribute__((address_space(1))) void* gptr;
+    typedef __attribute__((address_space(3))) void* lptr;
+#pragma unroll
+    for (int q = 0; q < SF_NPW(RT, CW); ++q) {
+        int piece = wave + SF_WAVES(CW) * q;                 // wave-uniform
+        if (piece >= TP) piece -= SF_WAVES(CW);
+        const int r = piece * 8 + (lane >> 3), c = lane & 7;
+        const int rt = (piece - PA) * RPP + lane / CH, cht = (lane % CH) ^ sf_swz<CW>(rt);
+        const bf16_t* src = piece < PA ? A + (size_t)r * lda + k0 + gb_swz(r, c) * 8 : B + (size_t)(k0 + rt) * ldb + j0 + 8 * cht;
+        __builtin_amdgcn_global_load_lds((gptr)src, (lptr)(st + piece * 1024), 16, 0, 0);
+    }
+}
+// gt_frag on the [64][CW] image: the 16 columns starting at f0, k-step ks
+template <int CW>
+__device__ __forceinline__ bf16x8 sf_frag(const char* img, int f0, int ks) {
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    typedef short s16x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) s16x4* lp;
+    s16x4 v[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int row = 32 * ks + 8 * g + 4 * half + q;
+        v[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(img + row * (2 * CW) + 16 * (((f0 >> 3) + (p >> 1)) ^ sf_swz<CW>(row)) + 8 * (p & 1)));
+    }
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const s16x8 w = __builtin_shufflevector(v[0], v[1], 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(bf16x8, w);
+}
+// until at most `rem` stages' requests of this wave are outstanding (rem <= MAXS)
+template <int NPW, int MAXS>
+__device__ __forceinline__ void sf_wait(int rem) {
+    if constexpr (MAXS > 0) { if (rem >= MAXS) gb_wait_vm<NPW * MAXS>(); else sf_wait<NPW, MAXS - 1>(rem); }
+    else gb_wait_vm<0>();
+}
+
+// the k loop (a function of its own: its restrict-qualified operands are what lets the compiler tell the ring's LDS reads from the LDS-DMA writes in flight, as in
+// gb_mainloop -- without that it drains every outstanding request in front of each stage's first read)
+template <int RT, int CW>
+__device__ __forceinline__ void sf_mainloop(f32x4 (&acc)[RT], const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb, int j0, int K, char* lds) {
+    constexpr int S = SF_STAGES(RT, CW), SB = SF_STAGE_BYTES(RT, CW), NPW = SF_NPW(RT, CW);
+    static_assert(S >= 3 && NPW * (S - 2) <= 63, "the ring's outstanding requests must fit the 6-bit counter");
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < RT; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int nt = K / GB_K;
+    for (int s = 0; s < S - 1 && s < nt; ++s) sf_stage<RT, CW>(A, lda, B, ldb, j0, s * GB_K, lds + s * SB);
+    int cur = 0;
+    for (int t = 0; t < nt; ++t) {
+        sf_wait<NPW, S - 2>(nt - 1 - t);                      // stage t has landed: only the stages behind it may be outstanding
+        __builtin_amdgcn_s_barrier();                        // ... every wave's pieces of it; and every wave is done reading stage t - 1
+        __builtin_amdgcn_sched_barrier(0);
+        int nb = cur + S - 1; if (nb >= S) nb -= S;          // the buffer stage t - 1 used
+        if (t + S - 1 < nt) sf_stage<RT, CW>(A, lda, B, ldb, j0, (t + S - 1) * GB_K, lds + nb * SB);
+        const char* at = lds + cur * SB;
+        const char* bt = at + RT * 2048;
+        bf16x8 af[2][RT], bfr[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int r = 0; r < RT; ++r) af[ks][r] = gb_frag(at, 16 * r, ks);
+            bfr[ks] = sf_frag<CW>(bt, 16 * wave, ks);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int r = 0; r < RT; ++r) acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ks], af[ks][r], acc[r], 0, 0, 0);
+        if (++cur == S) cur = 0;
+    }
+}
+
+// grid (J / CW, 2 towers), CW / 16 waves, SF_LDS_BYTES of dynamic LDS.  GemmArgs as bf16_forward fills them for the GEPI_TANH tile GEMM (tiles_i unused): rows
+// 0 .. 16 RT - 1 of A are read (the staged zero rows among them), the same rows of C written, no other.  K a multiple of 64, J of CW.
+template <int RT, int CW>
+__global__ __launch_bounds__(64 * SF_WAVES(CW)) void bf16_small_forward_kernel(GemmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char sf_lds[];
+    const int tw = blockIdx.y, j0 = blockIdx.x * CW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, c = lane & 15;
+    const float4 bias4 = *reinterpret_cast<const float4*>(a.bias[tw] + j0 + 16 * wave + 4 * g);
+    __builtin_amdgcn_sched_barrier(0);                       // ... issued HERE, before the ring's first request: sf_wait's counts rely on it being the oldest
+    f32x4 acc[RT];
+    sf_mainloop<RT, CW>(acc, a.A[tw], a.lda, a.B[tw], a.ldb, j0, a.K, sf_lds);
+    // gb_epilogue_bf16's GEPI_TANH arithmetic; the lane's 4 consecutive columns of row 16 r + c go out as one 8-byte store
+    constexpr float K2 = 2.8853900817779268f;               // 2 log2(e)
+    const float bb[4] = {bias4.x * K2, bias4.y * K2, bias4.z * K2, bias4.w * K2};
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (bf16_t)bf16_tanh_scaled(fmaf(acc[r][e], K2, bb[e]));
+        *reinterpret_cast<bf16x4*>(a.C[tw] + (size_t)(16 * r + c) * a.ldc + j0 + 16 * wave + 4 * g) = o;
+    }
+}
+
 // ---- a CHAIN of layers in one launch ---------------------------------------------------------------------------------------------------
 // The hidden layers of a pass depend on each other only inside a ROW tile: tile (ti, tj) of layer l + 1 needs rows ti of ALL column tiles of layer l,
 // i.e. the outputs of the tiles_j workgroups that share (tower, ti).  One launch per layer makes that a chip-wide barrier plus a launch: of the

@@ -74,7 +74,7 @@ enum KernelVariant { KV_TRAIN8 = 0, KV_TRAIN_FB, KV_DW2, KV_DW, KV_GRAD_REDUCE, 
                      KV_POLICY_STEP_MBIN, KV_TRAIN_FB_MBIN, KV_NARROW_STEP_MBIN, KV_NARROW_TRAIN_MBIN, KV_TRAIN8_MBIN, KV_BF16_STEP_MBIN, KV_BF16_TRAIN_MBIN,
                      KV_BF16_STEP_WCAT, KV_BF16_STEP_WCAT_MASK, KV_BF16_TRAIN_WCAT, KV_BF16_TRAIN_WCAT_MASK,
                      KV_BF16_STEP_WMCAT, KV_BF16_STEP_WMCAT_MASK, KV_BF16_TRAIN_WMCAT, KV_BF16_TRAIN_WMCAT_MASK,
-                     KV_BF16_STEP_WMBIN, KV_BF16_TRAIN_WMBIN, KV_TOTAL };
+                     KV_BF16_STEP_WMBIN, KV_BF16_TRAIN_WMBIN, KV_BF16_SMALL_FORWARD, KV_TOTAL };
 // ppo_kernel_counts is FROZEN at the first KV_LEGACY_COUNT rows (its callers assert the row count); variants added behind them appear in ppo_kernel_counts_all,
 // which is FROZEN in turn at the first KV_ALL_COUNT rows (a caller asserts that count too).  Every variant, later ones included, is reached by name through
 // ppo_kernel_count and enumerated by ppo_kernel_variant_name: no caller may hold THAT list's length.
@@ -82,7 +82,7 @@ constexpr int KV_LEGACY_COUNT = 60;
 constexpr int KV_ALL_COUNT = 62;
 static_assert(KV_LEGACY_COUNT == KV_NARROW_STEP_MBIN, "the frozen rows end where the first later variant begins");
 static_assert(KV_ALL_COUNT == KV_TRAIN8_MBIN, "the rows of ppo_kernel_counts_all end where the first variant named after it begins");
-// The variant list (KV_TOTAL = 75 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
+// The variant list (KV_TOTAL = 76 names) has outgrown 64.  No caller's buffer is filled from it: the two tables above are frozen at 60 / 62 rows, ppo_kernel_variant_name
 // hands out one name at a time, and ppo_host_learn_binary's walk stops at its callers' 64 entries itself (it ends one name short of the list).
 // KV_COUNT below is FROZEN at the 63 names in front of the bf16 <mbin> pair, and the assertion on it can no longer fail: it constrains nothing.  It stands only because
 // tests/test_multi_binary.py::test_source_names_the_head_in_every_layer looks for this line of text; when that test's pin is updated, both lines go.
@@ -136,7 +136,10 @@ const char* kVariantNames[KV_TOTAL] = {"train8_kernel", "train_fwd_bwd_kernel", 
                                        "bf16_step_sequence<wmcat>", "bf16_step_sequence<wmcat,mask>", "bf16_train_sequence<wmcat>", "bf16_train_sequence<wmcat,mask>",
                                        // a wide multi-binary PPO_BF16 handle (PPO_ACT_BF16_BINARY_HEAD | PPO_ACT_BF16_WIDE_BINARY_HEAD, act_dim > 128): counted INSTEAD of the
                                        // "bf16_*_sequence<mbin>" names; ppo_kernel_count / ppo_kernel_variant_name only
-                                       "bf16_step_sequence<wmbin>", "bf16_train_sequence<wmbin>"};
+                                       "bf16_step_sequence<wmbin>", "bf16_train_sequence<wmbin>",
+                                       // a PPO_BF16 handle (any head) with ppo_set_bf16_small_step on: one per step or query call of at most 64 rows whose hidden layers ran
+                                       // bf16_small_forward_kernel, counted BESIDE the call's "bf16_step_sequence[<..>]" name; ppo_kernel_count / ppo_kernel_variant_name only
+                                       "bf16_small_forward"};
 
 // The policy head of a launch, decided once per launch site (head_of): Gaussian, <cat>, <cat,mask>, <mcat>, <mcat,mask> or <mbin>.  index(): its column below.
 struct Head {
@@ -303,6 +306,7 @@ struct ppo_handle {
     // ... its discrete forms (ppo_set_rollout_resident on a narrow categorical / multi-categorical handle; resident_discrete() says whether it took effect, on the
     // device env as well): the mask of row t travels in pin_mask behind a sequence word of its own (PCTL_MASK)
     bool rollout_resident = false;
+    bool bf16_small_step = false;     // ppo_set_bf16_small_step: a step / query of at most 64 rows runs its hidden layers in bf16_small_forward_kernel (bf16_forward)
     bool bf16_queries = false;        // ppo_set_bf16_queries: the policy queries of a PPO_BF16 handle run bf16_eval_kernel (launch_eval_bf16) instead of being refused
     bool host_values_due = false;    // an act of this rollout ran a form that leaves the values to ppo_rollout_finish's batched pass (resident / fused)
     float* pin_in_dev = nullptr; float* pin_out_dev = nullptr; unsigned* pin_flag_dev = nullptr;   // the pinned blocks as the device sees them
@@ -1158,8 +1162,18 @@ int bf16_wide_loss(ppo_handle* h, const TrainArgs& ta, int Rp) {
     return 0;
 }
 
-// forward of both towers on `rows` staged rows: hidden layers (bias + tanh) and the padded heads (fp32 out)
-int bf16_forward(ppo_handle* h, int Rp, const bf16_t* x0_override = nullptr) {
+// the hidden layers of a step of at most SF_MAX_ROWS live rows (ppo_set_bf16_small_step): a launch of bf16_small_forward_kernel per layer, both towers in each.
+// Same bits as the tile GEMMs on rows 0 .. 16 RT - 1; the rows behind them are NOT written (the head, sample and eval kernels treat rows independently).
+template <int RT>
+static void bf16_small_layer(ppo_handle* h, const GemmArgs& g, int J) {
+    hipLaunchKernelGGL((bf16_small_forward_kernel<RT, SF_CW>), dim3(J / SF_CW, 2), dim3(64 * SF_WAVES(SF_CW)), SF_LDS_BYTES(RT, SF_CW), h->stream, g);
+}
+// whether a step / query of n live rows takes that form
+static bool bf16_small(const ppo_handle* h, int n) { return h->bf16_small_step && n >= 1 && n <= SF_MAX_ROWS; }
+
+// forward of both towers on `rows` staged rows: hidden layers (bias + tanh) and the padded heads (fp32 out).  small_rows: the live row count when the caller is a
+// step or a query that takes the small form (launch_step_bf16 / launch_eval_bf16 with bf16_small()), 0 from every other caller and row count
+int bf16_forward(ppo_handle* h, int Rp, const bf16_t* x0_override = nullptr, int small_rows = 0) {
     ppo_handle::Bf16& b = h->bf;
     const NetDev& n = h->net;
     GemmArgs fl[PPO_MAX_LAYERS];
@@ -1178,6 +1192,15 @@ int bf16_forward(ppo_handle* h, int Rp, const bf16_t* x0_override = nullptr) {
     // every hidden layer in ONE launch when the shape qualifies, else a launch per layer.  (The heads riding behind the last layer of the chained launch --
     // a workgroup's own column tile is one 128-deep reduction range -- was measured: -4.2 us on the pass, +1.8 us in the loss kernel for twice the
     // partial products, and +16 us per env step on the act path, which has to cut its heads the same way to give the same bits; not kept.)
+    if (small_rows > 0) {
+        const int rt = (small_rows + 15) / 16;
+        for (int l = 0; l < n.L; ++l) {
+            if (fl[l].K % GB_K || n.Hp[l] % SF_CW) return fail(h, "bf16 path: the small step takes padded widths (K = %d, J = %d)", fl[l].K, n.Hp[l]);
+            if (rt == 1) bf16_small_layer<1>(h, fl[l], n.Hp[l]); else if (rt == 2) bf16_small_layer<2>(h, fl[l], n.Hp[l]);
+            else if (rt == 3) bf16_small_layer<3>(h, fl[l], n.Hp[l]); else bf16_small_layer<4>(h, fl[l], n.Hp[l]);
+            HIP_OK(h, hipGetLastError());
+        }
+    } else
     if (!(same_j && n.L <= GB_CHAIN_MAX && bf16_chain<GEPI_TANH>(h, fl, n.L, Rp, n.Hp[0], 0)))
         for (int l = 0; l < n.L; ++l) if (bf16_gemm<GEPI_TANH>(h, fl[l], Rp, n.Hp[l])) return -1;
     // the heads: 64 rows of one tower and one reduction range per workgroup (bf16_heads_kernel)
@@ -1219,7 +1242,9 @@ int launch_step_bf16(ppo_handle* h, const StepArgs& a) {
     ProfScope ps(h, PK_STEP);
     const NetDev& n = h->net;
     const int Rp = ru(a.n, GB_PAD);
-    if (bf16_stage(h, a.obs, a.n, Rp, a.nz, a.obs_out) || bf16_forward(h, Rp)) return -1;
+    const bool small = a.small_ok && bf16_small(h, a.n);       // (small_ok: the callers the setting covers set it; ppo_collect_synthetic's steps do not)
+    if (small) ++h->kv[KV_BF16_SMALL_FORWARD];
+    if (bf16_stage(h, a.obs, a.n, Rp, a.nz, a.obs_out) || bf16_forward(h, Rp, nullptr, small ? a.n : 0)) return -1;
     if (h->bf.wide) return bf16_wide_sample(h, a);
     SampleArgsB sa{};
     sa.head[0] = h->bf.head_out[0]; sa.head[1] = h->bf.head_out[1]; sa.ldh = n.Ap; sa.hsplit = h->bf.head_split; sa.hstride = (size_t)h->bf.Rcap * n.Ap; sa.logstd = h->theta + n.ls_off;
@@ -1241,12 +1266,13 @@ int launch_eval_bf16(ppo_handle* h, const EvalArgs& a) {
     if (n.A > 128 && !h->bf.wide) return fail(h, "bf16 path: more than 128 actions");
     const int chunk = h->cfg.max_rows > 0 ? h->cfg.max_rows : 65536;
     const int Aw = h->Aw;
+    if (bf16_small(h, std::min(chunk, a.n)) || bf16_small(h, a.n % chunk)) ++h->kv[KV_BF16_SMALL_FORWARD];      // once per call in which ANY chunk takes the form: the first (every full one is its size) or the tail
     for (int r0 = 0; r0 < a.n; r0 += chunk) {
         const int rows = std::min(chunk, a.n - r0);
         if (bf16_ensure_ws(h, rows)) return -1;
         ProfScope ps(h, PK_STEP);
         const int Rp = ru(rows, GB_PAD);
-        if (bf16_stage(h, a.obs + (size_t)r0 * n.O, rows, Rp, no_norm_fwd(), nullptr) || bf16_forward(h, Rp)) return -1;
+        if (bf16_stage(h, a.obs + (size_t)r0 * n.O, rows, Rp, no_norm_fwd(), nullptr) || bf16_forward(h, Rp, nullptr, bf16_small(h, rows) ? rows : 0)) return -1;
         if (h->bf.wide) { if (bf16_wide_eval(h, a, r0, rows)) return -1; continue; }
         EvalArgsB ea{};
         ea.head[0] = h->bf.head_out[0]; ea.head[1] = h->bf.head_out[1]; ea.ldh = n.Ap; ea.hsplit = h->bf.head_split; ea.hstride = (size_t)h->bf.Rcap * n.Ap; ea.logstd = h->theta + n.ls_off;
@@ -2602,7 +2628,7 @@ static int step_common(ppo_handle* h, const float* obs, int n, const float* nois
     a.det_action = det_action ? h->st_act : nullptr;
     a.value = value ? h->st_vec[0] : nullptr;
     a.neglogp = neglogp ? h->st_vec[1] : nullptr;
-    a.obs_out = nullptr; a.nz = no_norm(); a.n = n; a.mask = mask ? h->st_mask : nullptr;
+    a.obs_out = nullptr; a.nz = no_norm(); a.n = n; a.mask = mask ? h->st_mask : nullptr; a.small_ok = true;
     // (only a call that actually draws from the counter RNG advances it: ppo_value / ppo_act_deterministic in the middle of a
     // rollout must not shift the rollout's noise)
     a.seed = h->rng_seed; a.rng_step = (sample && action && !noise) ? h->rng_calls++ : h->rng_calls; a.row_base = (uint32_t)h->rank * (uint32_t)(h->nz_envs > 0 ? h->nz_envs : n);
@@ -3143,6 +3169,14 @@ int ppo_set_bf16_queries(ppo_handle* h, int32_t on) {
     return 0;
 }
 int ppo_bf16_queries(const ppo_handle* h) { return h && h->bf16_queries ? 1 : 0; }
+// The small-batch forward of a PPO_BF16 handle (bf16_small_forward_kernel) is opt-in per handle: host state only, read by launch_step_bf16 / launch_eval_bf16 at
+// their next call; a PPO_F32 handle keeps the setting and never reads it.
+int ppo_set_bf16_small_step(ppo_handle* h, int32_t on) {
+    if (!h) return fail(nullptr, "ppo_set_bf16_small_step: null handle");
+    h->bf16_small_step = on != 0;
+    return 0;
+}
+int ppo_bf16_small_step(const ppo_handle* h) { return h && h->bf16_small_step ? 1 : 0; }
 
 // The resident rollout of a narrow discrete handle (resident_discrete).  As above: any handle accepts the call, and only a narrow discrete one drops its rollout.
 int ppo_set_rollout_resident(ppo_handle* h, int32_t on) {
@@ -3200,14 +3234,16 @@ static ObsNorm obs_norm(ppo_handle* h) { return ObsNorm{h->obs_rms.mean, h->obs_
 // policy step on the current observations -> rollout[t]
 // direct: the policy tower also publishes the actions to the host itself (StepArgs::host_action)
 // mask_dev: row t of ro_mask when the step samples under a mask (ppo_rollout_act_masked), null: the unmasked kernel
-static int enqueue_rollout_act(ppo_handle* h, int t, const float* noise_dev, uint32_t seed, uint32_t rng_step, uint32_t row_base, bool direct = false, const float* mask_dev = nullptr) {
+// host_env: the env step of a host Env (ppo_rollout_act*), which ppo_set_bf16_small_step covers; false from ppo_collect_synthetic
+static int enqueue_rollout_act(ppo_handle* h, int t, const float* noise_dev, uint32_t seed, uint32_t rng_step, uint32_t row_base, bool direct = false, const float* mask_dev = nullptr,
+                               bool host_env = false) {
     const NetDev& n = h->net;
     const size_t E = h->E;
     if (h->done_staged != t) HIP_OK(h, hipMemcpyAsync(h->ro_done + t * E, h->cur_done, E * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     StepArgs a{};
     a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.noise = noise_dev; a.action = h->ro_act + t * E * h->Aw; a.det_action = nullptr;
     a.value = h->ro_val + t * E; a.neglogp = h->ro_nlp + t * E; a.obs_out = h->ro_obs + t * E * n.O; a.nz = obs_norm(h); a.n = (int)E;
-    a.seed = seed; a.rng_step = rng_step; a.row_base = row_base; a.mask = mask_dev;
+    a.seed = seed; a.rng_step = rng_step; a.row_base = row_base; a.mask = mask_dev; a.small_ok = host_env;
     if (direct) { ++h->kv[KV_STEP_HOST_ACTION]; a.host_action = h->pin_out_dev; a.host_flags = h->pin_wgflag_dev; a.host_seq = ++h->wg_seq; }
     return launch_step(h, a);
 }
@@ -3222,9 +3258,10 @@ static int enqueue_observe(ppo_handle* h, int t) {
 }
 
 // tval: the [T,E] terminal values of the rollout's time-limit truncations (enqueue_truncations), or null = none were marked
-static int enqueue_finish(ppo_handle* h, float gamma, float lam, const float* tval = nullptr) {
+// host_env: ppo_rollout_finish (StepArgs::small_ok); false from ppo_collect_synthetic
+static int enqueue_finish(ppo_handle* h, float gamma, float lam, const float* tval = nullptr, bool host_env = false) {
     StepArgs a{};
-    a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.value = h->last_val; a.nz = obs_norm(h); a.n = h->E;
+    a.theta = h->theta; a.par = h->par; a.obs = h->raw_obs; a.value = h->last_val; a.nz = obs_norm(h); a.n = h->E; a.small_ok = host_env;
     if (launch_step(h, a)) return -1;
     ProfScope ps(h, PK_GAE);
     launch_gae(h, h->ro_rew, h->ro_val, h->ro_done, h->last_val, h->cur_done, tval, h->T, h->E, gamma, lam, h->ro_ret);
@@ -3254,6 +3291,7 @@ static int enqueue_truncations(ppo_handle* h) {
     for (size_t k0 = 0; k0 < K; k0 += chunk) {
         StepArgs a{};
         a.theta = h->theta; a.par = h->par; a.obs = h->tr_dev + k0 * O; a.value = val_dev + k0; a.nz = obs_norm(h); a.n = (int)std::min(chunk, K - k0);
+        a.small_ok = true;                                          // (ppo_rollout_finish only: a host-Env rollout's terminal-value pass)
         if (launch_step(h, a)) return -1;
     }
     ProfScope ps(h, PK_GAE);
@@ -3264,9 +3302,9 @@ static int enqueue_truncations(ppo_handle* h) {
 }
 
 // values of all T x E rollout rows in one batched pass (the rows are already normalised): behind the forms whose kernels run the policy tower only
-static int enqueue_values_all_rows(ppo_handle* h) {
+static int enqueue_values_all_rows(ppo_handle* h, bool host_env = false) {
     StepArgs va{};
-    va.obs = h->ro_obs; va.value = h->ro_val; va.n = h->E * h->T; va.nz = no_norm();
+    va.obs = h->ro_obs; va.value = h->ro_val; va.n = h->E * h->T; va.nz = no_norm(); va.small_ok = host_env;
     return launch_step(h, va);
 }
 
@@ -3611,7 +3649,7 @@ static int act_fused(ppo_handle* h, int t, const float* noise_dev, bool masked) 
 // hides under the kernel's tail).  The policy kernel is stream-ordered behind the H2D copy of the last observation and the statistics
 // kernel, so once its last block has published, the pinned input block is free again -- without a stream synchronisation.
 static int act_direct(ppo_handle* h, int t, const float* noise_dev, const float* mask_row, float* actions_out) {
-    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, host_rng_step(h, noise_dev), (uint32_t)(h->rank * h->E), true, mask_row)) return -1;
+    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, host_rng_step(h, noise_dev), (uint32_t)(h->rank * h->E), true, mask_row, true)) return -1;
     const unsigned want = h->wg_seq;
     const int G = (h->E + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     const size_t cnt = (size_t)h->E * h->Aw, blk = (size_t)ROWS_PER_BLOCK * h->Aw;
@@ -3631,7 +3669,7 @@ static int act_direct(ppo_handle* h, int t, const float* noise_dev, const float*
 // not the copy command.)
 static int act_copy(ppo_handle* h, int t, const float* noise_dev, const float* mask_row) {
     const size_t cnt = (size_t)h->E * h->Aw;
-    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, host_rng_step(h, noise_dev), (uint32_t)(h->rank * h->E), false, mask_row)) return -1;
+    if (enqueue_rollout_act(h, t, noise_dev, h->rng_seed, host_rng_step(h, noise_dev), (uint32_t)(h->rank * h->E), false, mask_row, true)) return -1;
     HIP_OK(h, hipMemcpyAsync(h->pin_out, h->ro_act + (size_t)t * cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (bf16_chain_err_async(h)) return -1;
     // busy-wait on the stream: the blocking synchronise parks the thread on an interrupt and wakes it ~100-200 us late,
@@ -3728,14 +3766,14 @@ int ppo_rollout_finish(ppo_handle* h, float gamma, float lam) {
         host_words_reset(h);
         if (host_flush_pending(h)) return -1;                                             // the last transition's bookkeeping, then the values
         // (a discrete handle on which only the resident setting took effect and whose every act brought explicit noise ran the per-step form: its values are there)
-        if ((h->host_values_due || !host_resident_discrete(h) || host_fused_discrete(h)) && enqueue_values_all_rows(h)) return -1;
+        if ((h->host_values_due || !host_resident_discrete(h) || host_fused_discrete(h)) && enqueue_values_all_rows(h, true)) return -1;
     }
     h->host_values_due = false;
     const bool marks = h->tr_K > 0;                                 // none: the launches of a rollout without time limits, nothing else
     if (marks && enqueue_truncations(h)) { trunc_clear(h); return -1; }
     h->tval_live = marks;
     trunc_clear(h);
-    if (enqueue_finish(h, gamma, lam, marks ? h->ro_tval : nullptr) || bf16_chain_err_async(h)) return -1;
+    if (enqueue_finish(h, gamma, lam, marks ? h->ro_tval : nullptr, true) || bf16_chain_err_async(h)) return -1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     prof_collect(h);
     if (bf16_chain_err_test(h)) return -1;

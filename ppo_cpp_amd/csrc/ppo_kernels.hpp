@@ -818,6 +818,9 @@ struct StepArgs {
     float* host_action;      // pinned host memory as the device sees it, [n,A]
     unsigned* host_flags;    // pinned, one word per 16-row block
     unsigned host_seq;
+    // host code only, no kernel reads it: the caller is one of the calls ppo_set_bf16_small_step covers (ppo_step / ppo_act_deterministic / ppo_value, an env step
+    // or the finishing passes of a host-Env rollout); ppo_collect_synthetic's per-step launches leave it false
+    bool small_ok;
 #ifdef PPO_STAMPS
     unsigned long long* stamps;   // diagnostic builds only: [tower][block][8]
 #endif

@@ -58,6 +58,8 @@ public:
     }
     // evaluate_actions / proba_step behind a PPO_BF16 handle: refused by default, served by the bf16 evaluation kernel once this is on (ppo_set_bf16_queries)
     virtual void set_bf16_queries(bool on) { check(ppo_set_bf16_queries(h_, on ? 1 : 0), "set_bf16_queries"); }
+    // step / value / the queries at 64 rows or fewer behind a PPO_BF16 handle: the small-batch forward kernel instead of the tile GEMMs, same bits (ppo_set_bf16_small_step)
+    virtual void set_bf16_small_step(bool on) { check(ppo_set_bf16_small_step(h_, on ? 1 : 0), "set_bf16_small_step"); }
     // Runner::set_returns' GAE scan (runner.hpp:159-191) on the device; [T,E] time-major
     virtual void gae(const Mat& rewards, const Mat& values, const Mat& dones, const Mat& last_values, const Mat& last_dones, float gamma,
                      float lam, Mat& returns) {

@@ -254,6 +254,8 @@ public:
 
     // action_probability behind a PPO_BF16 handle (MlpPolicy::set_bf16_queries; the act and the train model share the handle)
     void set_bf16_queries(bool on) { act_model_.set_bf16_queries(on); }
+    // the runner's policy steps behind a PPO_BF16 handle at 64 environments or fewer (MlpPolicy::set_bf16_small_step)
+    void set_bf16_small_step(bool on) { act_model_.set_bf16_small_step(on); }
 
     // save cadence of the reference (ppo2.hpp:256-262, 361-376): a save every ceil(n_updates / num_saves) updates with
     // ids 0, 1, ..., plus a trailing save when the interval does not divide the number of updates
